@@ -3,7 +3,7 @@
 (BASELINE.json metric; SURVEY.md 8(d) config #3 at 4096^2) on one MI355X, plus the HBM roofline
 fraction of the dominant kernel and the CPU oracle timed on this box's host cores.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload ...] [--size 4096] [--nodes 32]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload ...] [--size 4096] [--nodes 32] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
 
@@ -38,6 +38,8 @@ Other workloads (parity-tested configs of BASELINE.json, reported in DESIGN.md):
     --cold                    (chain32 / mix1 / resize_blend, N = 1) the timed region itself rotates over 4 instances on different
                               inputs: the run whose kernel trace reproduces roofline.frac_cold
 Every workload run with N = 1 also carries a "parity" object: the timed graph's result against the oracle.
+--dump-outputs DIR writes the timed path's result of the last timed step as .npy files (float32; a fixed, seeded sample
+of each array when the whole would exceed 64 MB), so that two builds can be compared output for output.
 """
 import argparse
 import gc
@@ -50,7 +52,7 @@ ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 
-HBM_PEAK_GBS = 8000.0  # MI355X HBM3E spec peak, /opt/skills/guides/MI355X_MICROARCH.md (6.29 TB/s measured copy)
+HBM_PEAK_GBS = 8000.0  # MI355X HBM3E spec peak (6.29 TB/s measured copy)
 
 
 def add_chain(kc, lg, src_a, src_b, n_nodes):
@@ -94,6 +96,40 @@ def usable_cores():
     return n
 
 
+DUMP_BYTES = 64 * 10**6  # --dump-outputs: at most this many bytes of array data in all (every rank together)
+DUMP_SEED = 0x5EED
+
+
+def image_outputs(image):
+    """What a caller receives from an image result: its f32 planes, named by channel."""
+    planes = image.planes()
+    return list(zip(("result_r", "result_g", "result_b", "result_a") if len(planes) == 4 else ("result_gray",), planes))
+
+
+def dump_outputs(dirname, arrays, rank, world):
+    """Writes every (name, array) as DIR/<name>.npy in float32 (rank<r>_<name>.npy with several ranks).  An array larger than
+    its share of DUMP_BYTES is written as its elements at a fixed, seeded, sorted set of flat indices (the same set for every
+    array of that size), so that two builds run with the same arguments write files that compare element for element."""
+    import numpy as np
+    os.makedirs(dirname, exist_ok=True)
+    keep = (DUMP_BYTES // max(1, world * len(arrays)) - 4096) // 4  # float32 elements per file (4 KB left for the header)
+    picks, files = {}, {}
+    for name, a in arrays:
+        a = np.ascontiguousarray(a)
+        data = a.reshape(-1)
+        sampled = data.size > keep
+        if sampled:
+            if data.size not in picks:
+                picks[data.size] = np.sort(np.random.default_rng(DUMP_SEED).choice(data.size, keep, replace=False))
+            data = data[picks[data.size]]
+        else:
+            data = a
+        fname = name if world == 1 else "rank%d_%s" % (rank, name)
+        np.save(os.path.join(dirname, fname + ".npy"), data.astype(np.float32))
+        files[fname] = {"shape": list(a.shape), "dtype": str(a.dtype), "sampled_elements": int(data.size) if sampled else None}
+    return {"dir": dirname, "files": files, "sample_seed": DUMP_SEED}
+
+
 def embed(kc, lg, image, eid):
     lg.embed_slot_data_with_id(kc.SlotData(0, 0, image), eid)
     return lg.add_node(kc.Node.new(kc.NodeType.Embed(eid)))
@@ -116,10 +152,15 @@ def main():
     ap.add_argument("--nodes", type=int, default=32)
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-extras", action="store_true", help="skip the unfused and PCIe-inclusive side measurements")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the timed path computed in its last step (the arrays its caller receives) "
+                         "as DIR/<name>.npy in float32; arrays over the 64 MB budget are a fixed, seeded sample of their elements")
     ap.add_argument("--dist-backend", default="nccl", choices=["nccl", "gloo"],
                     help="torch.distributed backend for the barrier and the reductions of the timing (nccl = RCCL; gloo to rehearse "
                          "N > 1 with several processes on one GPU); plane data moves through the library's communicator either way")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
     if args.workload is None:
         args.workload = "chain32" if args.gpus == 1 else "chain32_rows"
         if args.size is None and args.gpus > 1:
@@ -210,6 +251,7 @@ def main():
             def cstep():
                 lgc.connect(ca, cfirst, 0, 0)
                 lgc.await_clean(clast)
+            cstep.outputs = lambda: image_outputs(lgc.slot_data(clast, 0).image)
             return cstep
 
         def step(gg=g):
@@ -219,6 +261,7 @@ def main():
                 return
             lg.connect(na, first, 0, 0)  # re-plugging the input dirties the whole chain (live_graph.rs:488-511)
             lg.await_clean(last)
+        step.outputs = lambda: image_outputs(band_keep[0] if band is not None else g[0].slot_data(g[3], 0).image)
 
         node_px = float(N) * S * rows
         # fused: R,G,B of A and B read once (24 B/px), R,G,B of the result written once (12 B/px);
@@ -240,6 +283,7 @@ def main():
         def step():
             lg.connect(na, m, 0, 0)
             lg.await_clean(m)
+        step.outputs = lambda: image_outputs(lg.slot_data(m, 0).image)
 
         def make_cold(i):
             ia = kc.SlotImage.from_planes([splitmix_plane(SEED_A + 0x1000 * (i + 1), c, S, S) for c in range(4)])
@@ -253,6 +297,7 @@ def main():
             def cstep():
                 lgc.connect(ca, cm, 0, 0)
                 lgc.await_clean(cm)
+            cstep.outputs = lambda: image_outputs(lgc.slot_data(cm, 0).image)
             return cstep
 
         node_px, alg_bytes, kernel = float(S) * S, 36.0 * S * S, "chain_kernel<2,4,0>"
@@ -277,6 +322,7 @@ def main():
         def step():
             lg.connect(na, n1, 0, 0)
             lg.await_clean(n3)
+        step.outputs = lambda: image_outputs(lg.slot_data(n3, 0).image)
 
         def make_cold(i):
             ia = kc.SlotImage.from_planes([splitmix_plane(SEED_A + 0x1000 * (i + 1), c, S, S) for c in range(4)])
@@ -292,6 +338,7 @@ def main():
             def cstep():
                 lgc.connect(ca, c1, 0, 0)
                 lgc.await_clean(c3)
+            cstep.outputs = lambda: image_outputs(lgc.slot_data(c3, 0).image)
             return cstep
 
         node_px = 3.0 * S * S
@@ -334,6 +381,7 @@ def main():
             e2e["img"] = pipe.upload((k + 1) % depth)  # next image: its copy runs during the kernels just enqueued
             e2e["last"] = (sl, k % depth)
             e2e["k"] = k + 1
+        step.outputs = lambda: [("result_rgba8", pipe.wait_download(e2e["last"][0]))]
 
         g = None
         node_px = float(N) * S * S
@@ -411,6 +459,7 @@ def main():
                 for k in mine:
                     lg.connect(srcs[k][0], firsts[k], 0, 0)  # re-plugging the input dirties the branch and what joins it
             keep[:] = [ev.evaluate()]
+        step.outputs = lambda: image_outputs(keep[0]) if keep and keep[0] is not None else []
 
         n_tree = n_branches - 1
         if ev.plan.kind == kc.PlanKind.Bands:
@@ -573,9 +622,10 @@ def main():
         def main_step():
             rot[rot_i[0] % len(rot)]()
             rot_i[0] += 1
-        args.steps = max(len(rot), args.steps // len(rot) * len(rot))
+        main_step.outputs = lambda: rot[(rot_i[0] - 1) % len(rot)].outputs()
         args.warmup = max(2 * len(rot), args.warmup // len(rot) * len(rot))
     wall, dev_s, launches = timed(main_step, args.steps, args.warmup)
+    dumped = dump_outputs(args.dump_outputs, main_step.outputs(), rank, world) if args.dump_outputs else None
     extra_main = extra_warmup[0]
     main_host_us = list(host_us)
     # Algorithmic bytes: the per-kernel figures of DESIGN.md section 3 summed by the library over the launches of a step
@@ -676,6 +726,8 @@ def main():
         },
     }
 
+    if dumped is not None:
+        out["dump_outputs"] = dumped
     if first_sightings:
         out["first_sightings"] = dict(first_sightings)
     if args.workload == "e2e":
