@@ -291,6 +291,47 @@ KC_API int kc_u8_pipe_download(kc_u8_pipe *pipe, int slot, kc_image *img, int sr
 KC_API int kc_u8_pipe_wait_download(kc_u8_pipe *pipe, int slot);
 KC_API int kc_image_from_f32(const float *const host_planes[], int n_planes, uint32_t width, uint32_t height, kc_image **out);
 KC_API int kc_image_to_f32(kc_image *img, float *const host_planes[], int n_planes);
+/* Images in DEVICE memory (a torch tensor, a renderer's buffer, the input of the next graph): converted on the device, no
+ * trip through host memory.  kc_plane_wrap borrows a single aligned f32 plane without a copy; these entries convert from and
+ * to the common element types and layouts, into library-owned planes / caller memory.
+ *   kc_device_image      a caller's buffer: `ptr` is device memory of the library's device; element (x, y, channel c) lies at
+ *                        ptr + y * row_pitch_bytes + (x * channels + c) * elem (INTERLEAVED, HWC) or
+ *                        ptr + c * channel_pitch_bytes + y * row_pitch_bytes + x * elem (PLANAR, CHW).
+ *   kc_device_image_validate  launches nothing.  Arithmetic checks first (no kc_init needed): channels 1..4, known dtype and
+ *                        layout, width and height > 0, ptr and the pitches multiples of the element size, row pitch >= the row's
+ *                        bytes, PLANAR planes that do not overlap (channel pitch >= height * row pitch, when channels > 1); a
+ *                        failure is KC_ERR_INVALID_ARG.  Then `*extent_bytes` (optional) = end of the last element - ptr.  Once
+ *                        initialised, [ptr, ptr + extent) must lie in ONE device allocation of the library's device
+ *                        (KC_ERR_INVALID_ARG otherwise, e.g. a host pointer); before kc_init the call returns KC_ERR_NO_DEVICE
+ *                        after the arithmetic, with the extent written.  The three entries below call it first.
+ *   kc_image_from_device deconstruct_image (src/shared.rs:16-56) on the device: U8 v / 255., U16 v / 65535., F16 / BF16 exact
+ *                        widening, F32 the bits as they are; an RGBA image with missing R, G, B = 0 and a missing A = 1 --
+ *                        or, with KC_DEVICE_GRAY and channels == 1, a Gray image.  `*out` (+1 ref) owns copies of the pixels.
+ *   kc_image_to_device   channel c (0..3) of `dst` = R, G, B, A of the image as to_u8 sees it (Gray = (v, v, v, 1)): U8
+ *                        exactly what kc_image_to_u8 writes (KC_DEVICE_SRGB: to_u8_srgb; another dtype with it is
+ *                        KC_ERR_UNSUPPORTED), U16 ((v.clamp(0,1) * 65535.).min(65535.)) truncated (NaN -> 65535), F16 / BF16
+ *                        round to nearest even (no clamp), F32 the bits.  Bytes outside the described elements are not touched.
+ *   kc_live_graph_buffer_device  the same for a slot's image (buffer_rgba, src/live_graph.rs:93-95).
+ * Ordering: the conversion is enqueued on the library's stream (kc_get_stream) and the calls return without waiting.  With a
+ * non-NULL `hip_stream` the library's stream first waits for the work already enqueued on `hip_stream`, and `hip_stream` then
+ * waits for the conversion; kc_set_stream is not changed.  NULL orders nothing: a caller on HIP's legacy NULL stream makes the
+ * two edges itself against kc_get_stream() (the Python binding does so for torch's default stream).  The caller's buffer may be overwritten or freed by work ordered
+ * after the conversion: on `hip_stream` after the call returns, or after kc_sync. */
+typedef enum kc_dtype { KC_DTYPE_U8 = 0, KC_DTYPE_U16 = 1, KC_DTYPE_F16 = 2, KC_DTYPE_BF16 = 3, KC_DTYPE_F32 = 4 } kc_dtype;
+typedef enum kc_layout { KC_LAYOUT_INTERLEAVED = 0 /* HWC */, KC_LAYOUT_PLANAR = 1 /* CHW */ } kc_layout;
+typedef struct kc_device_image {
+    void *ptr;                    /* device memory on the library's device */
+    uint32_t width, height;
+    int32_t channels;             /* 1..4 */
+    int32_t dtype, layout;        /* kc_dtype, kc_layout */
+    size_t row_pitch_bytes;       /* distance between rows */
+    size_t channel_pitch_bytes;   /* PLANAR only: distance between channel planes; ignored for INTERLEAVED */
+} kc_device_image;
+#define KC_DEVICE_SRGB 1u /* export, U8 only: to_u8_srgb on R, G, B (alpha stays linear), as kc_image_to_u8 */
+#define KC_DEVICE_GRAY 2u /* import, channels == 1 only: a Gray image instead of the RGBA rule */
+KC_API int kc_device_image_validate(const kc_device_image *d, size_t *extent_bytes);
+KC_API int kc_image_from_device(const kc_device_image *src, uint32_t flags, void *hip_stream, kc_image **out);
+KC_API int kc_image_to_device(kc_image *img, const kc_device_image *dst, uint32_t flags, void *hip_stream);
 /* read_slot_image, src/shared.rs:218-261 (PNG only; decode on host, planes built on device). */
 KC_API int kc_image_read_png(const char *path, kc_image **out);
 KC_API int kc_image_write_png(kc_image *img, const char *path);        /* src/node/write.rs:5-21 */
@@ -386,6 +427,9 @@ KC_API int kc_live_graph_slot_data_size(kc_live_graph *lg, uint32_t node_id, uin
 KC_API int kc_live_graph_slot_in_memory(kc_live_graph *lg, uint32_t node_id, uint32_t slot_id, int *in_memory); /* :410-412 */
 KC_API int kc_live_graph_node_slot_ids(kc_live_graph *lg, uint32_t node_id, uint32_t *slot_ids, uint32_t cap, uint32_t *count); /* node_slot_datas, :389-404 */
 KC_API int kc_live_graph_buffer_rgba(kc_live_graph *lg, uint32_t node_id, uint32_t slot_id, int srgb, uint8_t *host_rgba8); /* :93-95 */
+/* buffer_rgba into device memory in any kc_device_image form (see kc_image_to_device) */
+KC_API int kc_live_graph_buffer_device(kc_live_graph *lg, uint32_t node_id, uint32_t slot_id, const kc_device_image *dst, uint32_t flags,
+                                       void *hip_stream);
 KC_API int kc_live_graph_embed_slot_data_with_id(kc_live_graph *lg, kc_image *image, uint32_t slot_id, uint32_t embed_id); /* :324-341 */
 KC_API int kc_live_graph_add_input_slot_data(kc_live_graph *lg, uint32_t node_id, uint32_t slot_id, kc_image *image);     /* :347-350 */
 KC_API int kc_live_graph_changed_consume(kc_live_graph *lg, uint32_t *ids, uint32_t cap, uint32_t *count);               /* :156-160 */

@@ -553,6 +553,75 @@ def _edges(fn, handle):
     return [Edge(e.output_id, e.input_id, e.output_slot, e.input_slot) for e in arr[:n.value]]
 
 
+# ------------------------------------------------------------------ device-memory images (kc_image_from_device / _to_device)
+DEVICE_SRGB = 1  # export, U8 only: to_u8_srgb on R, G, B
+DEVICE_GRAY = 2  # import, one channel only: a Gray image
+LAYOUT_HWC, LAYOUT_CHW = 0, 1
+_DEVICE_DTYPES = {"uint8": (0, 1), "uint16": (1, 2), "float16": (2, 2), "bfloat16": (3, 2), "float32": (4, 4)}  # code, bytes
+
+
+def device_image_desc(t, layout="hwc"):
+    """kc_device_image of a tensor's memory, from its data pointer, shape and strides alone (no device access, so it maps CPU
+    tensors as well).  layout "hwc": (H, W) or (H, W, C) with the pixels' channels packed; "chw": (H, W) or (C, H, W) with
+    each row packed.  Rows and channel planes may lie anywhere (padding, slices of larger tensors); a non-unit inner stride
+    raises ValueError -- nothing is copied behind the caller's back."""
+    if layout not in ("hwc", "chw"):
+        raise ValueError("layout must be 'hwc' or 'chw', not %r" % (layout,))
+    name = str(t.dtype).split(".")[-1]
+    if name not in _DEVICE_DTYPES:
+        raise ValueError("dtype %s is not one of uint8, uint16, float16, bfloat16, float32" % name)
+    code, esize = _DEVICE_DTYPES[name]
+    shape, stride = tuple(t.shape), tuple(t.stride())
+    if len(shape) == 2:
+        shape, stride = ((1,) + shape, (0,) + stride) if layout == "chw" else (shape + (1,), stride + (1,))
+    if len(shape) != 3:
+        raise ValueError("expected a tensor of shape (H, W), %s, got %s" % ("(H, W, C)" if layout == "hwc" else "(C, H, W)", tuple(t.shape)))
+    if layout == "hwc":
+        (h, w, c), (sh, sw, sc) = shape, stride
+    else:
+        (c, h, w), (sc, sh, sw) = shape, stride
+    if not 1 <= c <= 4:
+        raise ValueError("1 to 4 channels, got %d" % c)
+    if h == 0 or w == 0:
+        raise ValueError("empty image %s" % (tuple(t.shape),))
+    # a dimension of size 1 has no meaningful stride
+    if layout == "hwc" and ((c > 1 and sc != 1) or (w > 1 and sw != c)):
+        raise ValueError("hwc needs each pixel's channels packed: strides (..., %d, 1) for shape %s, got %s" % (c, tuple(t.shape), t.stride()))
+    if layout == "chw" and w > 1 and sw != 1:
+        raise ValueError("chw needs each row packed: a unit stride along W, got strides %s" % (t.stride(),))
+    row = sh * esize if h > 1 else w * (c if layout == "hwc" else 1) * esize
+    chan = (sc * esize if c > 1 else h * row) if layout == "chw" else 0
+    return _lib.kc_device_image(t.data_ptr(), w, h, c, code, LAYOUT_HWC if layout == "hwc" else LAYOUT_CHW, row, chan)
+
+
+def _on_torch_stream(t, call):
+    """call(hip_stream) ordered against torch's current stream.  torch's default stream is HIP's legacy NULL stream, which
+    the C ABI cannot be handed (NULL = no ordering): there the same two edges are made here, with the library's stream
+    wrapped as a torch stream."""
+    import torch
+    if not t.is_cuda:
+        raise ValueError("the tensor must be in device memory on the library's device, not on %s" % t.device)
+    cur = torch.cuda.current_stream(t.device)
+    if cur.cuda_stream:
+        return call(C.c_void_p(cur.cuda_stream))
+    lib_stream = torch.cuda.ExternalStream(_lib.load().kc_get_stream(), device=t.device)
+    lib_stream.wait_stream(cur)
+    status = call(None)
+    cur.wait_stream(lib_stream)
+    return status
+
+
+def _device_export(call, size, dtype, layout, channels, srgb, out):
+    """Allocates (or takes) the output tensor and runs `call(desc, flags, stream)` into it."""
+    import torch
+    if out is None:
+        shape = (size.height, size.width, channels) if layout == "hwc" else (channels, size.height, size.width)
+        out = torch.empty(shape, dtype=torch.float32 if dtype is None else dtype, device=torch.device("cuda", torch.cuda.current_device()))
+    d = device_image_desc(out, layout)
+    _check(_on_torch_stream(out, lambda stream: call(C.byref(d), DEVICE_SRGB if srgb else 0, stream)))
+    return out
+
+
 # ------------------------------------------------------------------ SlotImage / SlotData
 class SlotImage:
     """SlotImage (src/slot_image.rs:15-264) backed by device planes."""
@@ -597,6 +666,18 @@ class SlotImage:
         return SlotImage(out.value)
 
     @staticmethod
+    def from_torch(t, layout="hwc", gray=False):
+        """deconstruct_image of a tensor in device memory (kc_image_from_device): uint8, uint16, float16, bfloat16 or float32,
+        (H, W), (H, W, C) for "hwc" or (C, H, W) for "chw", strides from the tensor (device_image_desc).  An RGBA image -- or
+        with gray=True and one channel, a Gray one -- owning a copy of the pixels.  Ordered on torch's current stream: the
+        tensor may be freed or overwritten by torch as soon as this returns."""
+        d = device_image_desc(t, layout)
+        out = C.c_void_p()
+        _check(_on_torch_stream(t, lambda stream: _lib.load().kc_image_from_device(C.byref(d), DEVICE_GRAY if gray else 0, stream,
+                                                                                    C.byref(out))))
+        return SlotImage(out.value)
+
+    @staticmethod
     def read_png(path):
         out = C.c_void_p()
         _check(_lib.load().kc_image_read_png(os.fspath(path).encode(), C.byref(out)))
@@ -627,6 +708,13 @@ class SlotImage:
 
     def to_u8_srgb(self):
         return self.to_u8(True)
+
+    def to_torch(self, dtype=None, layout="hwc", channels=4, srgb=False, out=None):
+        """The image as a tensor in device memory (kc_image_to_device): channels 1..4 of (R, G, B, A) as to_u8 sees them,
+        dtype torch.float32 by default (uint8: exactly to_u8 / to_u8_srgb).  `out` (any strided view, e.g. a slice of a larger
+        tensor) is written instead of a new tensor; its dtype and shape then decide.  Ready on torch's current stream."""
+        return _device_export(lambda d, f, s: _lib.load().kc_image_to_device(self._h, d, f, s), self.size(), dtype, layout, channels,
+                              srgb, out)
 
     def planes(self):
         """Downloads the f32 planes: list of (h, w) arrays (1 or 4)."""
@@ -968,6 +1056,11 @@ class LiveGraph:
         out = np.empty((s.height, s.width, 4), np.uint8)
         _check(_lib.load().kc_live_graph_buffer_rgba(self._h, node_id, slot_id, int(srgb), out.ctypes.data))
         return out
+
+    def buffer_torch(self, node_id, slot_id, dtype=None, layout="hwc", channels=4, srgb=False, out=None):
+        """buffer_rgba into a tensor in device memory (kc_live_graph_buffer_device); arguments as SlotImage.to_torch."""
+        return _device_export(lambda d, f, s: _lib.load().kc_live_graph_buffer_device(self._h, node_id, slot_id, d, f, s),
+                              self.slot_data_size(node_id, slot_id), dtype, layout, channels, srgb, out)
 
     @staticmethod
     def try_buffer_rgba(live_graph, node_id, slot_id, srgb=False):

@@ -712,6 +712,29 @@ try {
 }
 KC_CATCH
 
+int kc_device_image_validate(const kc_device_image *d, size_t *extent_bytes)
+try {
+    KC_ARG(d);
+    return device_image_validate(d, extent_bytes);
+}
+KC_CATCH
+
+int kc_image_from_device(const kc_device_image *src, uint32_t flags, void *hip_stream, kc_image **out)
+try {
+    Lock api_lock(ctx().mu);  // reference counts are plain integers, see kc_plane::refs
+    KC_ARG(src && out);
+    return image_from_device(src, flags, hip_stream, out);  // does not synchronise: see the header on reusing `src`
+}
+KC_CATCH
+
+int kc_image_to_device(kc_image *img, const kc_device_image *dst, uint32_t flags, void *hip_stream)
+try {
+    Lock api_lock(ctx().mu);  // reference counts are plain integers, see kc_plane::refs
+    KC_ARG(img && dst);
+    return image_to_device(img, dst, flags, hip_stream);
+}
+KC_CATCH
+
 int kc_image_from_f32(const float *const host_planes[], int n, uint32_t w, uint32_t h, kc_image **out)
 try {
     Lock api_lock(ctx().mu);  // reference counts are plain integers, see kc_plane::refs
@@ -1340,6 +1363,17 @@ try {
     const SlotData *sd = lg->find_slot(node, slot);
     if (!sd) return KC_ERR_NO_SLOT_DATA;
     return image_to_u8(sd->image, srgb != 0, host);
+}
+KC_CATCH
+
+int kc_live_graph_buffer_device(kc_live_graph *lg, uint32_t node, uint32_t slot, const kc_device_image *dst, uint32_t flags,
+                                void *hip_stream)
+try {
+    LG_LOCK(lg);
+    KC_ARG(dst);
+    const SlotData *sd = lg->find_slot(node, slot);
+    if (!sd) return KC_ERR_NO_SLOT_DATA;
+    return image_to_device(sd->image, dst, flags, hip_stream);
 }
 KC_CATCH
 

@@ -184,6 +184,20 @@ hipError_t launch_height_to_normal(const float *hgt, uint32_t hpitch, uint32_t w
                                    float *nx, float *ny, float *nz, uint32_t opitch, uint32_t nt_mask, hipStream_t s);
 hipError_t launch_to_u8(Operand r, Operand g, Operand b, Operand a, int gray, int srgb, uint32_t w, uint32_t h,
                         uint8_t *dst, uint32_t nt_mask, hipStream_t s);
+// Device-memory images (devimage.hip / devimage.cpp): a validated kc_device_image as the kernels take it.  vec != 0: the pointer
+// and the pitches are aligned for the widest access of a whole pixel quad (devimage.cpp, devimage_vec).
+struct DevImageArgs {
+    const char *ptr;
+    uint64_t row_pitch, channel_pitch;  // bytes
+    uint32_t w, h;
+    int channels, layout;  // 1..4, kc_layout
+    int vec;
+};
+// image_import_kernel: the first `channels` planes of `planes` are written (pitch in floats); nt_mask bit 8: nontemporal stores
+hipError_t launch_image_import(int dtype, const DevImageArgs &a, float *const planes[4], uint32_t ppitch, uint32_t nt_mask, hipStream_t s);
+// image_export_kernel: channel c of the output is op[c]; gray != 0: op[0] stands for R, G and B (read once); nt_mask bits 0-7:
+// nontemporal plane loads; srgb: U8 only
+hipError_t launch_image_export(int dtype, int srgb, const Operand op[4], int gray, const DevImageArgs &a, uint32_t nt_mask, hipStream_t s);
 hipError_t launch_from_u8(const uint8_t *src, int channels, uint32_t w, uint32_t h, float *const planes[4],
                           uint32_t pitch, uint32_t nt_mask, hipStream_t s);
 

@@ -343,6 +343,10 @@ int image_from_value(kc_size size, float v, bool rgba, kc_image **out);
 int image_as_type(kc_image *img, bool rgba, kc_image **out);
 int image_from_u8(const uint8_t *host, uint32_t w, uint32_t h, int channels, kc_image **out);
 int image_to_u8(kc_image *img, bool srgb, uint8_t *host);
+// device-memory images (devimage.cpp): the bodies of kc_device_image_validate / kc_image_from_device / kc_image_to_device
+int device_image_validate(const kc_device_image *d, size_t *extent_bytes);
+int image_from_device(const kc_device_image *src, uint32_t flags, void *hip_stream, kc_image **out);
+int image_to_device(kc_image *img, const kc_device_image *dst, uint32_t flags, void *hip_stream);
 int calculate_size(int policy, const kc_size *sizes, int n, int slot_index, kc_size specific, kc_size *out);
 int mix_process(kc_image *left, kc_image *right, int mix_type, kc_image **out);
 int separate_process(kc_image *in, kc_image *out[4]);
