@@ -189,7 +189,11 @@ KC_API int kc_stats_algorithmic_bytes(uint64_t *bytes);
 /* Named event counters since kc_init (tests and profiling: which kernel family a call went through).  Unknown names
  * read 0.  Names: "upsample_launches", "upsample_chain_launches" (the integer-ratio up-sampling kernels),
  * "resize_chain_launches" (the general fused resample + chain kernel), "chain1_launches" (one-step programs through the
- * ahead-of-time kernels), "replayed_evaluations". */
+ * ahead-of-time kernels), "replayed_evaluations".  The plain resize forms: "poly2_launches", "down2_launches",
+ * "resize_poly_launches", "resize_down_launches", "resize_lds_launches", "resize_wide_launches" (one per launch) and
+ * "resize_two_pass_launches" (one per plane: a vertical and a horizontal pass); the variant each launch took from its size:
+ * "poly_rows_<n>" / "poly2_rows_<n>" (band height), "poly2_xcd_order", "down2_xcd_order", "down2_by_rows" (job orders;
+ * neither of down2's: the plain 2-D grid), "upsample_nt_stores", "upsample_half_quads" (ratio 2). */
 KC_API int kc_stats_counter(const char *name, uint64_t *value);
 KC_API int kc_pool_trim(void);
 /* Run-time specialisation of the fused Mix-chain kernel.  A chain of N Mix nodes (src/node/mix.rs:136-192

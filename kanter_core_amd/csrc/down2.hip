@@ -248,7 +248,7 @@ __global__ __launch_bounds__(256) void resize_down2_kernel(const ResizePlanes P,
     }
 }
 
-hipError_t launch_resize_down2(const ResizePlanes &p, int batch, const Down2Args &a, hipStream_t s)
+hipError_t launch_resize_down2(const ResizePlanes &p, int batch, const Down2Args &a, hipStream_t s, ResizeVariant *var)
 {
     if (a.dw == 0 || a.dh == 0) return hipSuccess;
     if (batch < 1 || batch > 4) return hipErrorInvalidValue;
@@ -294,6 +294,10 @@ hipError_t launch_resize_down2(const ResizePlanes &p, int batch, const Down2Args
             a2.xcd_per = (uint32_t)((n + 7) / 8);
             grid = dim3(8u * a2.xcd_per, 1, batch);
         }
+    }
+    if (var) {
+        var->xcd = a2.xcd_per != 0 && !a2.by_rows;
+        var->by_rows = a2.by_rows != 0;
     }
 #define KC_D2(HC, NW4)                                                                     \
     do {                                                                                   \

@@ -90,6 +90,13 @@ struct ResizePlanes {
 //   strips   per strip of tile_w output columns: its first source column rounded down to a multiple of 4, and the width of its
 //            source window in column quads (<= 64: one per lane of the vertical pass)
 constexpr uint32_t KC_DOWN2_REC = 72, KC_DOWN2_MAX_CHUNKS = 4, KC_DOWN2_SLOTS = 256 + 32;
+// What a resize launcher chose from the launch size and its overrides, as it launched it (resize.cpp counts it: kc_stats_counter)
+struct ResizeVariant {
+    uint32_t rows = 0;     // band height (resize_poly_kernel, resize_poly2_kernel)
+    bool xcd = false;      // jobs dealt to the XCDs in eighths (resize_poly2_kernel, resize_down2_kernel)
+    bool by_rows = false;  // resize_down2_kernel: four strips of one row group per workgroup
+    bool wide = false;     // launch_resize_lds: resize_wide_kernel
+};
 struct Down2Args {
     const uint32_t *vrec;
     const uint32_t *hleft, *hcount, *strips;
@@ -105,9 +112,9 @@ struct Down2Args {
 };
 // output columns per lane of the horizontal pass: its weights live in registers (at most 9 quads per lane)
 inline uint32_t down2_cols_per_lane(uint32_t weight_quads) { return weight_quads <= 3 ? 3u : weight_quads == 4 ? 2u : 1u; }
-hipError_t launch_resize_down2(const ResizePlanes &p, int batch, const Down2Args &a, hipStream_t s);
+hipError_t launch_resize_down2(const ResizePlanes &p, int batch, const Down2Args &a, hipStream_t s, ResizeVariant *var);
 hipError_t launch_resize_lds(const ResizePlanes &p, int batch, uint32_t dw, uint32_t dh, TapsDev v, TapsDev h,
-                             uint32_t h_min_count, uint32_t tile_w, uint32_t tile_h, uint32_t ncp, hipStream_t s);
+                             uint32_t h_min_count, uint32_t tile_w, uint32_t tile_h, uint32_t ncp, hipStream_t s, ResizeVariant *var);
 hipError_t launch_resize_down(const ResizePlanes &p, int batch, uint32_t dw, uint32_t dh, TapsDev v, TapsDev h, uint32_t tile_w,
                               uint32_t tile_h, uint32_t ncp, hipStream_t s);
 // Tiles in XCD order (as resize_down2_kernel's): with per != 0 the grid is one-dimensional, workgroup id % 8 is the XCD and XCD k
@@ -130,11 +137,11 @@ inline XcdOrder xcd_order(uint32_t gx, uint32_t gy, bool want)
     return o;
 }
 hipError_t launch_resize_poly(const ResizePlanes &p, int batch, uint32_t dw, uint32_t dh, TapsDev v, TapsDev h, uint32_t tile_w,
-                              uint32_t ncp, uint32_t reg_a, uint32_t reg_b, uint32_t ages, uint32_t ratio, hipStream_t s);
+                              uint32_t ncp, uint32_t reg_a, uint32_t reg_b, uint32_t ages, uint32_t ratio, hipStream_t s, ResizeVariant *var);
 // The same ranges with two waves to a band's strip (8-byte lanes, a shared ring, the horizontal pass split by pixels): kernels.hip
 hipError_t launch_resize_poly2(const ResizePlanes &p, int batch, uint32_t dw, uint32_t dh, TapsDev v, TapsDev h, uint32_t tw,
                                uint32_t gen_tw, uint32_t gen_ncp, uint32_t reg_a, uint32_t reg_b, uint32_t ages, uint32_t ratio, bool xcd,
-                               hipStream_t s);
+                               hipStream_t s, ResizeVariant *var);
 // Fused resample + chain: input slot n_in - 1 of the program is produced by the resampler.
 hipError_t launch_resize_chain(const ChainProgram &p, int batch, uint32_t dw, uint32_t dh, TapsDev v, TapsDev h,
                                uint32_t tile_w, uint32_t tile_h, uint32_t ncp, hipStream_t s);

@@ -1212,13 +1212,14 @@ static void launch_resize_lds_t(dim3 grid, size_t lds, hipStream_t s, uint32_t m
 }
 
 hipError_t launch_resize_lds(const ResizePlanes &p, int batch, uint32_t dw, uint32_t dh, TapsDev v, TapsDev h,
-                             uint32_t h_min_count, uint32_t tile_w, uint32_t tile_h, uint32_t ncp, hipStream_t s)
+                             uint32_t h_min_count, uint32_t tile_w, uint32_t tile_h, uint32_t ncp, hipStream_t s, ResizeVariant *var)
 {
     if (dw == 0 || dh == 0) return hipSuccess;
     if (batch < 1 || batch > 4) return hipErrorInvalidValue;
     if (tile_w % 4 != 0 || tile_w > 1024 || 256u % (tile_w / 4) != 0 || tile_h > 64) return hipErrorInvalidValue;
     const size_t lds = resize_lds_bytes(tile_h, ncp, v.stride, tile_w, h.stride);
     dim3 grid((dw + tile_w - 1) / tile_w, (dh + tile_h - 1) / tile_h, batch);
+    if (var) var->wide = h.stride > KC_RESIZE_REG_TAPS;
     if (h.stride > KC_RESIZE_REG_TAPS)
         resize_wide_kernel<<<grid, 256, lds, s>>>(p, dw, dh, v, h, tile_w, tile_h, ncp,
                                                   (uint32_t)(lds / sizeof(float) - (2u * tile_w + (size_t)tile_w * h.stride)));
@@ -1255,7 +1256,7 @@ static void launch_resize_poly_a(dim3 grid, size_t lds, hipStream_t s, uint32_t 
 
 // Rows [reg_a, reg_b) of the vertical table are regular: `ages` x `ratio` taps each, windows `ratio` apart, equal weights.
 hipError_t launch_resize_poly(const ResizePlanes &p, int batch, uint32_t dw, uint32_t dh, TapsDev v, TapsDev h, uint32_t tile_w,
-                              uint32_t ncp, uint32_t reg_a, uint32_t reg_b, uint32_t ages, uint32_t ratio, hipStream_t s)
+                              uint32_t ncp, uint32_t reg_a, uint32_t reg_b, uint32_t ages, uint32_t ratio, hipStream_t s, ResizeVariant *var)
 {
     if (dw == 0 || dh == 0) return hipSuccess;
     if (batch < 1 || batch > 4) return hipErrorInvalidValue;
@@ -1315,6 +1316,7 @@ hipError_t launch_resize_poly(const ResizePlanes &p, int batch, uint32_t dw, uin
     const size_t lds = std::max(resize_down_lds_bytes(16, ncp, tile_w, h.stride), (size_t)4 * b.wave_floats * sizeof(float));
     if (lds > 64u * 1024u) return hipErrorInvalidValue;
     const dim3 grid(8u * b.xper + nt * b.gx, 1, batch);
+    if (var) var->rows = b.rows;
     if (ages == 2) launch_resize_poly_a<2>(grid, lds, s, ratio, p, dw, dh, v, h, tile_w, ncp, b);
     else if (ages == 4) launch_resize_poly_a<4>(grid, lds, s, ratio, p, dw, dh, v, h, tile_w, ncp, b);
     else launch_resize_poly_a<6>(grid, lds, s, ratio, p, dw, dh, v, h, tile_w, ncp, b);
@@ -1549,7 +1551,7 @@ static void launch_resize_poly2_a(dim3 grid, size_t lds, hipStream_t s, uint32_t
 // of 4, is at most 256 columns); gen_tw / gen_ncp: resize_down_kernel's tile for the border rows.
 hipError_t launch_resize_poly2(const ResizePlanes &p, int batch, uint32_t dw, uint32_t dh, TapsDev v, TapsDev h, uint32_t tw,
                                uint32_t gen_tw, uint32_t gen_ncp, uint32_t reg_a, uint32_t reg_b, uint32_t ages, uint32_t ratio, bool xcd,
-                               hipStream_t s)
+                               hipStream_t s, ResizeVariant *var)
 {
     if (dw == 0 || dh == 0) return hipSuccess;
     if (batch < 1 || batch > 4) return hipErrorInvalidValue;
@@ -1607,6 +1609,10 @@ hipError_t launch_resize_poly2(const ResizePlanes &p, int batch, uint32_t dw, ui
         x.n = b.n_band_wgs;
     }
     dim3 grid((x.per ? 8u * x.per : b.n_band_wgs) + nt * b.gen_gx, 1, batch);
+    if (var) {
+        var->rows = b.rows;
+        var->xcd = x.per != 0;
+    }
     if (ages == 2) launch_resize_poly2_a<2>(grid, lds, s, ratio, p, dw, dh, v, h, b, pair_floats, x);
     else if (ages == 4) launch_resize_poly2_a<4>(grid, lds, s, ratio, p, dw, dh, v, h, b, pair_floats, x);
     else launch_resize_poly2_a<6>(grid, lds, s, ratio, p, dw, dh, v, h, b, pair_floats, x);

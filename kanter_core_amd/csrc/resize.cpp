@@ -611,6 +611,8 @@ static int resize_run_taps(kc_plane *const *srcs, kc_plane *const *dsts, int n, 
         if (e != hipSuccess) return hip_fail(e, "launch_upsample");
         c.launches++;
         c.counters["upsample_launches"]++;
+        if (up.nt_mask & 0x100u) c.counters["upsample_nt_stores"]++;
+        if (ua.H.ratio == 2) c.counters["upsample_half_quads"]++;
         c.alg_bytes += (uint64_t)n * 4 * ((uint64_t)s0->w * s0->h + (uint64_t)size.width * size.height);
         return KC_OK;
     }
@@ -627,18 +629,24 @@ static int resize_run_taps(kc_plane *const *srcs, kc_plane *const *dsts, int n, 
             // both axes down-sampled: the wave-private form where its tables exist (down2.hip)
             // ... except where the streaming kernel of integer ratios is the faster one: ratios 4 and 8 (Lanczos3 4096^2 -> 1024^2
             // 23.5 against 26.7 us, CatmullRom 18.1 / 21.4; at ratio 2 down2 wins, 26.3 / 30.4 -- profiles/r03_down2_ab.txt)
-            // tiles in XCD order while source and result stay in the Infinity Cache (the budget of the cache policy)
-            const bool fits_cache = (uint64_t)n * 4 * ((uint64_t)s0->w * s0->h + (uint64_t)size.width * size.height) <= (208ull << 20);
+            // tiles in XCD order while source and result stay in the Infinity Cache (the budget of the cache policy,
+            // kc_set_option("cache_budget_mb")); resize_down2_kernel follows it, resize_poly2_kernel deals its bands to the XCDs
+            // at every size (launch_resize_poly2)
+            const bool fits_cache = (uint64_t)n * 4 * ((uint64_t)s0->w * s0->h + (uint64_t)size.width * size.height) <=
+                                    ((uint64_t)c.cache_budget_mb << 20);
+            ResizeVariant var{};
             // integer ratios: two waves to a band's strip (resize_poly2_kernel)
             // (where it measures faster than the forms below -- profiles/r04_poly2_sweep.txt: ratio 8 with windows of 4 or 6 ages,
             // Gaussian 4096^2 -> 512^2 27.6 -> 25.3 us, 8192^2 -> 1024^2 82.5 -> 72.5; at ratio 4 and 2 it is behind resize_poly_kernel
             // and resize_down2_kernel, 24.8 against 21.2 us and 34.3 against 24.5; kc_set_option("poly2_min_ratio") moves the line)
             if (t.poly && c.poly2 && tv->host.reg_ratio >= (uint32_t)c.poly2_min_ratio && tv->host.reg_ages >= 4 && th->host.p2_tile_w) {
                 hipError_t e2 = launch_resize_poly2(rp, n, size.width, size.height, tv->dev, th->dev, th->host.p2_tile_w, t.tile_w, t.ncp,
-                                                    tv->host.reg_a, tv->host.reg_b, tv->host.reg_ages, tv->host.reg_ratio, fits_cache, c.stream);
+                                                    tv->host.reg_a, tv->host.reg_b, tv->host.reg_ages, tv->host.reg_ratio, fits_cache, c.stream, &var);
                 if (e2 != hipSuccess) return hip_fail(e2, "launch_resize_poly2");
                 c.launches++;
                 c.counters["poly2_launches"]++;
+                c.counters["poly2_rows_" + std::to_string(var.rows)]++;
+                if (var.xcd) c.counters["poly2_xcd_order"]++;
                 c.alg_bytes += (uint64_t)n * 4 * ((uint64_t)s0->w * s0->h + (uint64_t)size.width * size.height);
                 return KC_OK;
             }
@@ -658,20 +666,29 @@ static int resize_run_taps(kc_plane *const *srcs, kc_plane *const *dsts, int n, 
                 a.dh = size.height;
                 a.xcd_per = fits_cache ? 1u : 0u;
                 a.by_rows = c.down2_by_rows < 0 ? (tv->host.d2_nc > 1 ? 1u : 0u) : (c.down2_by_rows ? 1u : 0u);
-                hipError_t e2 = launch_resize_down2(rp, n, a, c.stream);
+                hipError_t e2 = launch_resize_down2(rp, n, a, c.stream, &var);
                 if (e2 != hipSuccess) return hip_fail(e2, "launch_resize_down2");
                 c.launches++;
                 c.counters["down2_launches"]++;
+                if (var.xcd) c.counters["down2_xcd_order"]++;
+                if (var.by_rows) c.counters["down2_by_rows"]++;
                 c.alg_bytes += (uint64_t)n * 4 * ((uint64_t)s0->w * s0->h + (uint64_t)size.width * size.height);
                 return KC_OK;
             }
             hipError_t e = t.poly ? launch_resize_poly(rp, n, size.width, size.height, tv->dev, th->dev, t.tile_w, t.ncp, tv->host.reg_a,
-                                                       tv->host.reg_b, tv->host.reg_ages, tv->host.reg_ratio, c.stream)
+                                                       tv->host.reg_b, tv->host.reg_ages, tv->host.reg_ratio, c.stream, &var)
                            : t.down ? launch_resize_down(rp, n, size.width, size.height, tv->dev, th->dev, t.tile_w, t.tile_h, t.ncp, c.stream)
                                   : launch_resize_lds(rp, n, size.width, size.height, tv->dev, th->dev, th->host.min_count, t.tile_w,
-                                                      t.tile_h, t.ncp, c.stream);
+                                                      t.tile_h, t.ncp, c.stream, &var);
             if (e != hipSuccess) return hip_fail(e, "launch_resize_lds");
             c.launches++;
+            if (t.poly) {
+                c.counters["resize_poly_launches"]++;
+                c.counters["poly_rows_" + std::to_string(var.rows)]++;
+            } else if (t.down)
+                c.counters["resize_down_launches"]++;
+            else
+                c.counters[var.wide ? "resize_wide_launches" : "resize_lds_launches"]++;
             c.alg_bytes += (uint64_t)n * 4 * ((uint64_t)s0->w * s0->h + (uint64_t)size.width * size.height);
             return KC_OK;
         }
@@ -688,6 +705,7 @@ static int resize_run_taps(kc_plane *const *srcs, kc_plane *const *dsts, int n, 
         plane_release(tmp);
         if (e != hipSuccess) return hip_fail(e, "launch_resize two-pass");
         c.launches += 2;
+        c.counters["resize_two_pass_launches"]++;
         c.alg_bytes += 4 * ((uint64_t)s0->w * s0->h + 2 * (uint64_t)s0->w * size.height + (uint64_t)size.width * size.height);
     }
     return KC_OK;

@@ -54,6 +54,76 @@ def check_bands(kc, graph, images, root, what):
     return whole
 
 
+# Row bands of a resample against crops of the oracle's whole-image result.  The vertical table of a band (get_band_taps,
+# csrc/resize.cpp) is rebuilt relative to the band's first source row, and resize_down2_kernel's 4-row output groups and
+# 16-row source chunks with it; these shapes make the band tables reach the forms named (asserted by counter).
+BAND_FORMS = [
+    # (id, filter, A (w, h), B (w, h), the counter every band's resample adds to)
+    ("down2", "Lanczos3", (1030, 1030), (515, 515), "down2_launches"),
+    ("down2_chunks", "Gaussian", (2000, 2000), (700, 700), "down2_launches"),  # windows over several chunks
+    ("down", "Lanczos3", (4096, 600), (600, 88), "resize_down_launches"),
+    ("lds", "Lanczos3", (700, 700), (3000, 3000), "resize_lds_launches"),
+    ("two_pass", "Lanczos3", (8192, 8), (12, 5), "resize_two_pass_launches"),
+]
+
+
+def band_splits(h):
+    """1-row bands, bands that cut a 4-row output group, bands of 13 rows (their first source rows fall anywhere in a
+    16-row chunk), a band through the middle and a short last band; with the wrap of a HeightToNormal consumer, rows -1
+    and h."""
+    ones = sorted({y for y in (0, 1, 2, 3, 4, 5, h // 2, h - 2, h - 1) if 0 <= y < h})
+    out = [(y, y + 1) for y in ones]
+    out += [(a, b) for a, b in ((2, 7), (7, 13), (13, 18)) if b <= h]
+    out += [(y, y + 13) for y in range(3, min(h - 13, 3 + 13 * 6), 13)]
+    out += [(max(0, h // 2 - 9), min(h, h // 2 + 10)), (max(0, h - 3), h)]
+    return out
+
+
+def mix_band_graph(a_size, b_size, filt, h2n):
+    """Embed(A), Embed(B) -> Mix(Add) with A resampled to B's size [-> SeparateRgba -> HeightToNormal on its R]."""
+    g = G()
+    e0, e1 = g.add({"Embed": 0}), g.add({"Embed": 1})
+    down = a_size[0] * a_size[1] > b_size[0] * b_size[1]
+    mix = g.add({"Mix": "Add"}, policy="LeastPixels" if down else "MostPixels", filt=filt)
+    g.connect(e0, mix, 0, 0)
+    g.connect(e1, mix, 0, 1)
+    if not h2n:
+        return g.dict(), mix
+    sep = g.add("SeparateRgba")
+    g.connect(mix, sep, 0, 0)
+    n = g.add("HeightToNormal")
+    g.connect(sep, n, 0, 0)
+    return g.dict(), n
+
+
+@pytest.mark.parametrize("h2n", [False, True], ids=["mix", "height_to_normal"])
+@pytest.mark.parametrize("form", BAND_FORMS, ids=[f[0] for f in BAND_FORMS])
+def test_resize_bands_equal_oracle_crops(kc, form, h2n):
+    from oracle import oracle as orc
+    from util import edge_lines, resize_source, salt
+    name, filt, (aw, ah), (bw, bh), counter = form
+    splits = band_splits(bh)
+    rows = edge_lines(ah, [4, 16]) + [min(ah - 1, y * ah // bh) for band in splits for y in (band[0], band[1] - 1)]
+    cols = edge_lines(aw, [4, 64])
+    a = [salt(resize_source(SEED_A, c, ah, aw), rows[c::3] if h2n else rows[c::2], cols[c % 2::2], shift=c) for c in range(4)]
+    b = [resize_source(SEED_B, c, bh, bw) for c in range(4)]
+    if h2n:  # NaN and inf would reach every normal of their neighbourhood through the normalisation: keep them to one plane
+        a[0] = resize_source(SEED_A, 0, ah, aw)
+    mixed = [orc.mix_plane("Add", orc.resize_plane(a[c], bw, bh, filt), b[c]) for c in range(3)] + [np.ones((bh, bw), np.float32)]
+    want = list(orc.height_to_normal(mixed[0])) + [np.ones((bh, bw), np.float32)] if h2n else mixed
+    graph, root = mix_band_graph((aw, ah), (bw, bh), filt, h2n)
+    _, lg = build(kc, graph, {0: a, 1: b})
+    for (y0, y1) in splits:
+        n0 = kc.stats_counter(counter)
+        got = lg.evaluate_band(root, y0, y1).planes()
+        ran = kc.stats_counter(counter) - n0
+        # (a HeightToNormal band's first or last row wraps: the resample band then holds rows of both ends, whose table is
+        # not down2's -- KC_DOWN2_MAX_CHUNKS)
+        if not h2n or (y0 >= 1 and y1 <= bh - 1):
+            assert ran >= 1, "%s band %d..%d: the band's resample did not run through %s" % (name, y0, y1, counter)
+        assert_planes(got, [p[y0:y1] for p in want], what="%s %s band %d..%d" % (name, "h2n" if h2n else "mix", y0, y1))
+
+
 def chain_graph(n_nodes=12):
     g = G()
     a, b = g.add({"Embed": 0}), g.add({"Embed": 1})

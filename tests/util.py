@@ -82,3 +82,42 @@ def assert_planes(got, want, ulp=0, what=""):
                 what, c, int((~((g.view(np.uint32) == w.view(np.uint32)) | (np.isnan(g) & np.isnan(w)))).sum()), max_ulp(g, w))
         else:
             assert max_ulp(g, w) <= ulp, "%s plane %d: max ulp %s > %d" % (what, c, max_ulp(g, w), ulp)
+
+
+def resize_source(seed, channel, h, w):
+    """A plane of values in [-0.25, 1.25) (resampled results exercise the clamp to [0, 1] on both sides); numpy's
+    generator, which is much faster than splitmix_plane for the large planes of the resize tests."""
+    rng = np.random.default_rng([seed, channel, h, w])
+    return rng.random((h, w), dtype=np.float32) * np.float32(1.5) - np.float32(0.25)
+
+
+SALT_VALUES = [np.nan, np.inf, -np.inf, -0.0, 1e-40, 3e38, 1.25, -0.25]  # 3e38 is written as a vertical pair: its sums overflow
+
+
+def salt(plane, rows, cols, shift=0):
+    """Writes IEEE edge cases at the crossings of the given rows and columns (negative: from the end), cycling through
+    SALT_VALUES; a 3e38 sample gets a 3e38 neighbour below it (above it on the last row), so that vertical sums
+    overflow to inf although every sample is finite."""
+    h, w = plane.shape
+    rows = sorted({r % h for r in rows})
+    cols = sorted({c % w for c in cols})
+    k = shift
+    for r in rows:
+        for c in cols:
+            v = SALT_VALUES[k % len(SALT_VALUES)]
+            plane[r, c] = v
+            if v == 3e38:
+                plane[r + 1 if r + 1 < h else r - 1, c] = v
+            k += 1
+    return plane
+
+
+def edge_lines(n, periods, count=3):
+    """Line indices on the edges of tiles, bands or strips of the given periods along an axis of n: the first and last
+    two lines, and the two lines on each side of the first `count` multiples of every period (and of the last ones)."""
+    out = {0, 1, n - 2, n - 1}
+    for p in periods:
+        for k in range(1, count + 1):
+            for m in (k * p, n - (n % p or p) - (k - 1) * p):
+                out.update(x for x in (m - 1, m) if 0 <= x < n)
+    return sorted(out)
