@@ -159,7 +159,10 @@ KC_API int kc_get_cache_policy(void);
  *   (bit-identical; A/B and tests).
  *   "link_gbps" (153), "hbm_gbps" (6100): the rates kc_live_graph_partition prices a transfer / a streaming kernel with.
  *   "cache_budget_mb" (208, env KC_CACHE_BUDGET_MB): how much of a launch's streams the cache policy leaves cacheable -- 13/16 of
- *   the MI355X's 256 MB Infinity Cache; HIP reports no size for that cache, so another part sets this. */
+ *   the MI355X's 256 MB Infinity Cache; HIP reports no size for that cache, so another part sets this.
+ *   "chain_unroll" 0 (default: the measured choice) / 1 / 2 / 4 / 6 / 8 (initial value: env KC_CHAIN_UNROLL): float4 per lane of the
+ *   step interpreter for programs without divide or pow; "max_blocks" (4096, env KC_MAX_BLOCKS; >= 1): the interpreter's grid
+ *   cap, beyond which its workgroups stride over the plane (tuning and tests; bit-identical either way). */
 KC_API int kc_set_option(const char *name, int value);
 KC_API int kc_get_option(const char *name, int *value);
 /* Diagnostics (host only, works without a device): the structure the integer-ratio up-sampling kernels rely on,
@@ -193,7 +196,12 @@ KC_API int kc_stats_algorithmic_bytes(uint64_t *bytes);
  * "resize_poly_launches", "resize_down_launches", "resize_lds_launches", "resize_wide_launches" (one per launch) and
  * "resize_two_pass_launches" (one per plane: a vertical and a horizontal pass); the variant each launch took from its size:
  * "poly_rows_<n>" / "poly2_rows_<n>" (band height), "poly2_xcd_order", "down2_xcd_order", "down2_by_rows" (job orders;
- * neither of down2's: the plain 2-D grid), "upsample_nt_stores", "upsample_half_quads" (ratio 2). */
+ * neither of down2's: the plain 2-D grid), "upsample_nt_stores", "upsample_half_quads" (ratio 2).  The chain forms (one per
+ * launch): "chain_interp_k<K>_u<U>_m<MODE>" and the same with "_nt" (the step interpreter with K input planes, U float4 per
+ * lane, op set MODE 0 {+, -, *}, 1 + divide, 2 + pow, and its nontemporal form), "chain_k0_m<MODE>" (no input plane),
+ * "chain1_nt<0-7>" (a one-step kernel with its nontemporal bits: 1 the start plane, 2 the operand, 4 the result),
+ * "specialized_nt_<3 hex digits>" (a kernel compiled at run time and its cache-policy bits: 0x001 << k input plane k < 8,
+ * 0x100 the result). */
 KC_API int kc_stats_counter(const char *name, uint64_t *value);
 KC_API int kc_pool_trim(void);
 /* Run-time specialisation of the fused Mix-chain kernel.  A chain of N Mix nodes (src/node/mix.rs:136-192

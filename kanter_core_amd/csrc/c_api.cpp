@@ -246,6 +246,9 @@ try {
     else if (std::strcmp(name, "poly2") == 0 && value >= 0 && value <= 1) ctx().poly2 = value;
     else if (std::strcmp(name, "poly2_min_ratio") == 0 && value >= 2) ctx().poly2_min_ratio = value;
     else if (std::strcmp(name, "cache_budget_mb") == 0 && value >= 0) ctx().cache_budget_mb = value;
+    else if (std::strcmp(name, "chain_unroll") == 0 && (value == 0 || value == 1 || value == 2 || value == 4 || value == 6 || value == 8))
+        ctx().chain_unroll = value;
+    else if (std::strcmp(name, "max_blocks") == 0 && value >= 1) ctx().max_blocks = value;
     else if (std::strcmp(name, "link_gbps") == 0 && value > 0) ctx().link_gbps = value;
     else if (std::strcmp(name, "hbm_gbps") == 0 && value > 0) ctx().hbm_gbps = value;
     else {
@@ -268,6 +271,8 @@ try {
     else if (std::strcmp(name, "poly2") == 0) *value = ctx().poly2;
     else if (std::strcmp(name, "poly2_min_ratio") == 0) *value = ctx().poly2_min_ratio;
     else if (std::strcmp(name, "cache_budget_mb") == 0) *value = ctx().cache_budget_mb;
+    else if (std::strcmp(name, "chain_unroll") == 0) *value = ctx().chain_unroll;
+    else if (std::strcmp(name, "max_blocks") == 0) *value = ctx().max_blocks;
     else if (std::strcmp(name, "link_gbps") == 0) *value = ctx().link_gbps;
     else if (std::strcmp(name, "hbm_gbps") == 0) *value = ctx().hbm_gbps;
     else {

@@ -66,7 +66,7 @@ static void launch_chain1_code(const Chain1Args &a, dim3 grid, unsigned nt, hipS
 }
 
 // nt: bit 0 = the start plane, bit 1 = the operand plane, bit 2 = the result carry the nontemporal hint
-hipError_t launch_chain1(const Chain1Args &a, int batch, int code, unsigned nt, hipStream_t s)
+hipError_t launch_chain1(const Chain1Args &a, int batch, int code, unsigned nt, hipStream_t s, unsigned *launched_nt)
 {
     if (batch < 1 || batch > KC_CHAIN_MAX_BATCH) return hipErrorInvalidValue;
     const uint64_t total = (uint64_t)a.rows * a.row_units;
@@ -88,6 +88,7 @@ hipError_t launch_chain1(const Chain1Args &a, int batch, int code, unsigned nt, 
     case CH_MUL_INV: launch_chain1_code<CH_MUL_INV>(a, grid, nt, s); break;
     default: return hipErrorInvalidValue;
     }
+    if (launched_nt) *launched_nt = nt & 7u;
     return hipGetLastError();
 }
 

@@ -35,8 +35,14 @@ struct Operand {
 };
 
 // ---- kernel launchers (kernels.hip).  All enqueue on `s` and return hipGetLastError(). ----
+// What launch_chain launched (runtime.cpp counts it: kc_stats_counter): chain_kernel<k, u, mode, nt>, or
+// chain_kernel_k0<mode> for k = 0; k < 0: nothing (an empty plane)
+struct ChainVariant {
+    int k = -1, u = 0, mode = 0;
+    bool nt = false;
+};
 // mode: 0 = {+, -, *} only, 1 = + divide, 2 = + pow
-hipError_t launch_chain(const ChainProgram &p, int batch, int mode, int max_blocks, int unroll, hipStream_t s);
+hipError_t launch_chain(const ChainProgram &p, int batch, int mode, int max_blocks, int unroll, hipStream_t s, ChainVariant *var);
 // A one-step program for the ahead-of-time kernels of chain1.hip: result = op(start, operand), each a plane (pointer,
 // pitch in float4) or a broadcast constant (pointer null); c = the constant of the fused "c - ..." codes.
 struct Chain1Args {
@@ -46,8 +52,9 @@ struct Chain1Args {
     float start_c[KC_CHAIN_MAX_BATCH], operand_c[KC_CHAIN_MAX_BATCH], c[KC_CHAIN_MAX_BATCH];
     uint32_t row_units, rows;
 };
-// nt: bit 0 = the start plane, bit 1 = the operand plane, bit 2 = the result carry the nontemporal hint
-hipError_t launch_chain1(const Chain1Args &a, int batch, int code, unsigned nt, hipStream_t s);
+// nt: bit 0 = the start plane, bit 1 = the operand plane, bit 2 = the result carry the nontemporal hint.
+// *launched_nt: the bits of the instantiation launched (left alone when nothing is launched: an empty plane)
+hipError_t launch_chain1(const Chain1Args &a, int batch, int code, unsigned nt, hipStream_t s, unsigned *launched_nt);
 inline uint32_t chain_op_word(uint8_t code, int src) { return (uint32_t)code | ((uint32_t)(src + 1) << 8); }
 hipError_t launch_fill(float *dst, uint32_t pitch_floats, uint32_t w, uint32_t h, float v, hipStream_t s);
 hipError_t launch_resize_vertical(const float *src, uint32_t spitch, uint32_t sw, float *tmp, uint32_t tpitch,

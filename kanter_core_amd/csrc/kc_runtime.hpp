@@ -237,8 +237,8 @@ struct Context {
     int hbm_gbps = 6100;   // what a streaming kernel gets from HBM with nothing in the Infinity Cache (kc_set_option("hbm_gbps"))
     int cache_budget_mb = 208;  // what a launch may leave cacheable: 13/16 of the 256 MB Infinity Cache of an MI355X, the share that measured best (profiles/r03_tilecopy4.txt); kc_set_option("cache_budget_mb") / KC_CACHE_BUDGET_MB for another part
     int cache_policy = 1;  // 1: launches whose streams exceed the Infinity Cache mark them nontemporal (cache_policy_mask); 0: plain loads / stores (KC_CACHE_POLICY, kc_set_cache_policy)
-    int max_blocks = 4096;
-    int chain_unroll = 0;  // float4 per thread per decode in the chain kernel; 0 = heuristic (KC_CHAIN_UNROLL)
+    int max_blocks = 4096;  // grid cap of the chain interpreter (KC_MAX_BLOCKS, kc_set_option("max_blocks"))
+    int chain_unroll = 0;  // float4 per thread per decode in the chain kernel; 0 = heuristic (KC_CHAIN_UNROLL, kc_set_option("chain_unroll"))
     int resize_mode = 0;  // 0 auto (tiled single pass when a tile fits in LDS), 1 no resize_poly_kernel, 2 no resize_down_kernel either (A/B), 3 two passes through HBM only, 4 auto without the integer-ratio up-sampling kernels (KC_RESIZE_MODE, kc_set_resize_mode)
     int resize_tile_w = 0;  // > 0: force this tile width (KC_RESIZE_TILE_W, tuning only)
     int resize_tile_h = 0;  // > 0: force this tile height for 256-wide tiles (KC_RESIZE_TILE_H, tuning only)
@@ -368,7 +368,7 @@ int resize_force_many(kc_plane *const *planes, int n);  // same; equal resamples
 int chain_resize_launch(const ChainProgram &P, int batch, int mode, kc_plane *const *sampled, bool *launched);
 
 // ---- run-time specialisation of the chain kernel (specialize.cpp) ----
-hipError_t launch_chain_specialized(const ChainProgram &P, int batch, hipStream_t s, bool *launched);
+hipError_t launch_chain_specialized(const ChainProgram &P, int batch, hipStream_t s, bool *launched, uint32_t *nt_mask);
 // Which streams of a launch are marked nontemporal: `in_bytes` / `out_bytes` = what the launch reads from its n_resident
 // full-size input planes / writes, summed over its channels.  Returns the ChainProgram::nt_mask bits.
 uint32_t cache_policy_mask(uint64_t in_bytes, uint64_t out_bytes, uint32_t n_resident);

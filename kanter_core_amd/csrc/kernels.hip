@@ -258,12 +258,19 @@ __global__ __launch_bounds__(256) void chain_kernel_k0(const ChainProgram P)
 }
 
 template <int U, int MODE>
-static hipError_t launch_chain_k(const ChainProgram &p, dim3 grid, hipStream_t s)
+static hipError_t launch_chain_k(const ChainProgram &p, dim3 grid, hipStream_t s, ChainVariant *var)
 {
     // the nontemporal form exists for the default shapes only (U = 4 without pow, U = 1 with): tuning overrides stay plain
     constexpr bool HAS_NT = (MODE < 2 && U == 4) || (MODE == 2 && U == 1);
+    if (var) {
+        var->k = (int)p.n_in;
+        var->u = p.n_in == 0 ? 1 : U;
+        var->mode = MODE;
+        var->nt = false;
+    }
     if constexpr (HAS_NT) {
         if (p.nt_mask != 0) {
+            if (var) var->nt = p.n_in >= 1 && p.n_in <= 4;
             switch (p.n_in) {
             case 1: chain_kernel<1, U, MODE, true><<<grid, 256, 0, s>>>(p); return hipGetLastError();
             case 2: chain_kernel<2, U, MODE, true><<<grid, 256, 0, s>>>(p); return hipGetLastError();
@@ -279,36 +286,38 @@ static hipError_t launch_chain_k(const ChainProgram &p, dim3 grid, hipStream_t s
     case 2: chain_kernel<2, U, MODE><<<grid, 256, 0, s>>>(p); break;
     case 3: chain_kernel<3, U, MODE><<<grid, 256, 0, s>>>(p); break;
     case 4: chain_kernel<4, U, MODE><<<grid, 256, 0, s>>>(p); break;
-    default: return hipErrorInvalidValue;
+    default:
+        if (var) var->k = -1;
+        return hipErrorInvalidValue;
     }
     return hipGetLastError();
 }
 
 template <int U, int MODE>
-static hipError_t launch_chain_u(const ChainProgram &p, int batch, uint64_t total, int max_blocks, hipStream_t s)
+static hipError_t launch_chain_u(const ChainProgram &p, int batch, uint64_t total, int max_blocks, hipStream_t s, ChainVariant *var)
 {
     uint64_t blocks = (total + 256 * U - 1) / (256 * U);
     if (blocks > (uint64_t)max_blocks) blocks = max_blocks;
-    return launch_chain_k<U, MODE>(p, dim3((unsigned)blocks, batch, 1), s);
+    return launch_chain_k<U, MODE>(p, dim3((unsigned)blocks, batch, 1), s, var);
 }
 
-hipError_t launch_chain(const ChainProgram &p, int batch, int mode, int max_blocks, int unroll, hipStream_t s)
+hipError_t launch_chain(const ChainProgram &p, int batch, int mode, int max_blocks, int unroll, hipStream_t s, ChainVariant *var)
 {
     if (batch < 1 || batch > KC_CHAIN_MAX_BATCH || p.n_ops > KC_CHAIN_MAX_OPS || p.n_ops < 1) return hipErrorInvalidValue;
     const uint64_t total = (uint64_t)p.rows * p.row_units;
     if (total == 0) return hipSuccess;
     if (total > 0xFFFFFFFFull) return hipErrorInvalidValue;
-    if (mode >= 2) return launch_chain_u<1, 2>(p, batch, total, max_blocks, s);
-    if (mode == 1) return launch_chain_u<4, 1>(p, batch, total, max_blocks, s);
+    if (mode >= 2) return launch_chain_u<1, 2>(p, batch, total, max_blocks, s, var);
+    if (mode == 1) return launch_chain_u<4, 1>(p, batch, total, max_blocks, s, var);
     // U = float4 per lane per decode.  U = 4 (74-106 VGPRs, 4-6 waves/SIMD) is the measured optimum
     // on MI355X for 1-64 step chains: U = 2 doubles the scalar decode work per pixel, U = 8 drops to
-    // 2-3 waves/SIMD (profiles/r01_chain_unroll.md).  KC_CHAIN_UNROLL overrides for tuning.
+    // 2-3 waves/SIMD (profiles/r01_chain_unroll.md).  KC_CHAIN_UNROLL / kc_set_option("chain_unroll") override for tuning.
     switch (unroll) {
-    case 1: return launch_chain_u<1, 0>(p, batch, total, max_blocks, s);
-    case 2: return launch_chain_u<2, 0>(p, batch, total, max_blocks, s);
-    case 6: return launch_chain_u<6, 0>(p, batch, total, max_blocks, s);
-    case 8: return launch_chain_u<8, 0>(p, batch, total, max_blocks, s);
-    default: return launch_chain_u<4, 0>(p, batch, total, max_blocks, s);
+    case 1: return launch_chain_u<1, 0>(p, batch, total, max_blocks, s, var);
+    case 2: return launch_chain_u<2, 0>(p, batch, total, max_blocks, s, var);
+    case 6: return launch_chain_u<6, 0>(p, batch, total, max_blocks, s, var);
+    case 8: return launch_chain_u<8, 0>(p, batch, total, max_blocks, s, var);
+    default: return launch_chain_u<4, 0>(p, batch, total, max_blocks, s, var);
     }
 }
 

@@ -600,9 +600,44 @@ uint32_t cache_policy_mask(uint64_t in_bytes, uint64_t out_bytes, uint32_t n_res
     return mask;
 }
 
+// kc_stats_counter names of the chain forms chain_dispatch launches, built once.
+// chain_interp_k<K>_u<U>_m<MODE>[_nt]: chain_kernel<K, U, MODE, NT>; chain_k0_m<MODE>: chain_kernel_k0<MODE>;
+// chain1_nt<bits>: chain1_kernel's nontemporal bits (1 start, 2 operand, 4 result); specialized_nt_<hex>: the cache-policy
+// bits a compiled kernel carries (bits 0-7 inputs 0-7, 0x100 the result; the bits of inputs 8-15 are not part of the name).
+namespace {
+struct ChainCounterNames {
+    std::string interp[5][9][3][2];  // [K][U][MODE][NT]; U in {1, 2, 4, 6, 8}
+    std::string k0[3];
+    std::string chain1[8];
+    std::string spec[0x200];
+    ChainCounterNames()
+    {
+        char buf[64];
+        for (int k = 1; k <= 4; ++k)
+            for (int u : { 1, 2, 4, 6, 8 })
+                for (int m = 0; m < 3; ++m)
+                    for (int nt = 0; nt < 2; ++nt) {
+                        std::snprintf(buf, sizeof buf, "chain_interp_k%d_u%d_m%d%s", k, u, m, nt ? "_nt" : "");
+                        interp[k][u][m][nt] = buf;
+                    }
+        for (int m = 0; m < 3; ++m) k0[m] = "chain_k0_m" + std::to_string(m);
+        for (int b = 0; b < 8; ++b) chain1[b] = "chain1_nt" + std::to_string(b);
+        for (int b = 0; b < 0x200; ++b) {
+            std::snprintf(buf, sizeof buf, "specialized_nt_%03x", b);
+            spec[b] = buf;
+        }
+    }
+};
+const ChainCounterNames &chain_counter_names()
+{
+    static const ChainCounterNames n;
+    return n;
+}
+}  // namespace
+
 // Launches a (non-resampling) chain program whose inputs and outputs are set: the ahead-of-time kernel of a one-step
 // program, else the kernel compiled for the program at run time if there is one, else the interpreter.  Shared by
-// chain_launch and by the replay of a recorded evaluation (replay.cpp).
+// chain_launch and by the replay of a recorded evaluation (replay.cpp); counts the form it launched (kc_stats_counter).
 hipError_t chain_dispatch(ChainProgram &P, int batch, int mode, uint32_t w, uint32_t h, size_t out_pitch_bytes)
 {
     Context &c = ctx();
@@ -642,21 +677,28 @@ hipError_t chain_dispatch(ChainProgram &P, int batch, int mode, uint32_t w, uint
         a.row_units = P.row_units;
         const unsigned nt = (P.start_src >= 0 && (P.nt_mask >> P.start_src & 1u) ? 1u : 0u) | (from && (P.nt_mask >> (from - 1) & 1u) ? 2u : 0u) |
                             (P.nt_mask & 0x100u ? 4u : 0u);
-        hipError_t e = launch_chain1(a, batch, (int)(w0 & 0xffu), nt, c.stream);
+        unsigned launched_nt = ~0u;
+        hipError_t e = launch_chain1(a, batch, (int)(w0 & 0xffu), nt, c.stream, &launched_nt);
         if (e != hipSuccess) return e;
         c.counters["chain1_launches"]++;
+        if (launched_nt < 8) c.counters[chain_counter_names().chain1[launched_nt]]++;
         launched = true;
     }
     if (!launched) {
         // a program-specialised straight-line kernel if one has been compiled (specialize.cpp) ...
-        hipError_t e = launch_chain_specialized(P, batch, c.stream, &launched);
+        uint32_t spec_nt = 0;
+        hipError_t e = launch_chain_specialized(P, batch, c.stream, &launched, &spec_nt);
+        if (e == hipSuccess && launched) c.counters[chain_counter_names().spec[spec_nt & 0x1ffu]]++;
         // ... otherwise the interpreter -- which does not know the codes of a program that joins two chains (chain_launch
         // never sends it one; a replay of such a launch after kc_set_specialize(0) can)
         if (e == hipSuccess && !launched) {
             if (P.n_in > (uint32_t)KC_CHAIN_INTERP_IN) return hipErrorNotReady;  // as below: compiled kernels only
             for (uint32_t i = 0; i < P.n_ops; ++i)
                 if ((((i & 1u) ? P.step[0][i / 2].b.word : P.step[0][i / 2].a.word) & 0xffu) == CH_SAVE_LOAD) return hipErrorNotReady;
-            e = launch_chain(P, batch, mode, c.max_blocks, c.chain_unroll, c.stream);
+            ChainVariant v;
+            e = launch_chain(P, batch, mode, c.max_blocks, c.chain_unroll, c.stream, &v);
+            if (e == hipSuccess && v.k == 0) c.counters[chain_counter_names().k0[v.mode]]++;
+            else if (e == hipSuccess && v.k > 0) c.counters[chain_counter_names().interp[v.k][v.u][v.mode][v.nt ? 1 : 0]]++;
         }
         if (e != hipSuccess) return e;
     }

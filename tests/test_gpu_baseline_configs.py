@@ -11,7 +11,7 @@ import pytest
 
 from golden_graphs import G, HEART_256, INPUTS
 from pngio import read_png
-from util import SEED_A, SEED_B, assert_planes, bit_equal, splitmix_plane
+from util import SEED_A, SEED_B, assert_planes, assert_pow_planes, bit_equal, splitmix_plane
 
 pytestmark = pytest.mark.gpu
 
@@ -157,7 +157,7 @@ def test_config1_mix_pow_rgba_4096_within_one_ulp(kc, orc):
     b = [splitmix_plane(SEED_B, c, S, S) for c in range(3)] + [np.ones((S, S), np.float32)]
     got = kc.mix_process(kc.SlotImage.from_planes(a), kc.SlotImage.from_planes(b), kc.MixType.Pow).planes()
     want = [orc.mix_plane("Pow", a[c], b[c]) for c in range(3)] + [np.ones((S, S), np.float32)]
-    assert_planes(got[:3], want[:3], ulp=1, what="4096 Pow")
+    assert_pow_planes(got[:3], want[:3], what="4096 Pow")
     assert bit_equal(got[3], want[3])
     # and the fraction that is not bit-identical stays tiny (f64-rounded-once vs glibc powf)
     diff = sum(int((g.view(np.uint32) != w.view(np.uint32)).sum()) for g, w in zip(got[:3], want[:3]))

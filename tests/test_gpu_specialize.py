@@ -5,7 +5,7 @@ and identical between the two device paths."""
 import numpy as np
 import pytest
 
-from util import SEED_A, SEED_B, assert_planes, bit_equal, splitmix_plane, with_edge_cases
+from util import SEED_A, SEED_B, assert_planes, assert_pow_planes, bit_equal, splitmix_plane, with_edge_cases
 
 pytestmark = pytest.mark.gpu
 
@@ -86,7 +86,7 @@ def test_single_mix_every_op_and_operand_kind(kc, orc, op, side):
     assert launches == 1
     assert_planes(spec, interp, what="%s %s" % (op, side))  # the two device paths agree bit for bit, Pow included
     want = orc.mix_plane(op, a if side != "scalar_left" else cplane, b if side != "scalar_right" else cplane)
-    assert_planes(spec, [want], ulp=1 if op == "Pow" else 0, what="%s %s vs oracle" % (op, side))
+    (assert_pow_planes if op == "Pow" else assert_planes)(spec, [want], what="%s %s vs oracle" % (op, side))
 
 
 @pytest.mark.parametrize("shape", [(48, 200), (33, 130), (1, 7)])
@@ -136,7 +136,7 @@ def test_single_mix_ahead_of_time_kernels(kc, orc, op, side, shape):
             "same_plane": lambda: [m(a, a)], "then_invert": lambda: [orc.mix_plane("Subtract", ones, m(a, b))],
             "rgba": lambda: [m(a, b), m(b, b), m(a, a), ones]}[side]()
     if not (op == "Pow" and side == "then_invert"):  # 1 - x amplifies the one ulp Pow is allowed: interpreter-equal is the check there
-        assert_planes(got, want, ulp=1 if op == "Pow" else 0, what="%s %s vs oracle" % (op, side))
+        (assert_pow_planes if op == "Pow" else assert_planes)(got, want, what="%s %s vs oracle" % (op, side))
 
 
 def test_random_programs(kc, orc):

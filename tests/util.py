@@ -84,6 +84,32 @@ def assert_planes(got, want, ulp=0, what=""):
             assert max_ulp(g, w) <= ulp, "%s plane %d: max ulp %s > %d" % (what, c, max_ulp(g, w), ulp)
 
 
+def pow_mismatch(got, want):
+    """Where `got` breaks the Pow contract against `want` (both f32): a match is bit-equal (any NaN matches any NaN) or, for
+    two finite nonzero values of the same sign, one ulp apart.  So a zero's sign, inf against FLT_MAX and a flushed
+    subnormal are all mismatches, unlike under max_ulp's ordered distance."""
+    g = np.ascontiguousarray(got, np.float32)
+    w = np.ascontiguousarray(want, np.float32)
+    gi, wi = g.view(np.uint32).astype(np.int64), w.view(np.uint32).astype(np.int64)
+    same = (gi == wi) | (np.isnan(g) & np.isnan(w))
+    near = np.isfinite(g) & np.isfinite(w) & (g != 0) & (w != 0) & ((gi >> 31) == (wi >> 31)) & (np.abs(gi - wi) == 1)
+    return ~(same | near)
+
+
+def assert_pow_planes(got, want, what=""):
+    """Pow planes against a reference under the contract of pow_mismatch, plane by plane."""
+    assert len(got) == len(want), what
+    for c, (g, w) in enumerate(zip(got, want)):
+        g = np.asarray(g, np.float32)
+        w = np.asarray(w, np.float32)
+        assert g.shape == w.shape, "%s plane %d: shape %s != %s" % (what, c, g.shape, w.shape)
+        bad = pow_mismatch(g, w)
+        if bad.any():
+            i = np.flatnonzero(bad.reshape(-1))[:4]
+            raise AssertionError("%s plane %d: %d mismatches, e.g. got %s want %s at %s" % (
+                what, c, int(bad.sum()), g.reshape(-1)[i].tolist(), w.reshape(-1)[i].tolist(), i.tolist()))
+
+
 def resize_source(seed, channel, h, w):
     """A plane of values in [-0.25, 1.25) (resampled results exercise the clamp to [0, 1] on both sides); numpy's
     generator, which is much faster than splitmix_plane for the large planes of the resize tests."""
