@@ -124,45 +124,50 @@ KC_API void *kc_get_stream(void);
 KC_API int kc_sync(void);
 KC_API const char *kc_last_error(void);
 KC_API const char *kc_status_string(int status);
-/* 1 (default): pointwise Mix chains whose intermediates are never observed are evaluated by one
- * fused kernel; 0: every node materialises its planes.  Results are bit-identical either way. */
+/* The options "fusion", "resize_mode" and "cache_policy" of kc_set_option. */
 KC_API int kc_set_fusion(int enabled);
 KC_API int kc_get_fusion(void);
-/* Which resize kernels may run (an A/B and test knob; results are bit-identical in every mode; env KC_RESIZE_MODE):
- * 0 (default) all; 1 no resize_poly_kernel; 2 no resize_down_kernel either; 3 two passes through HBM only;
- * 4 everything except the integer-ratio up-sampling kernels.  Replaces nothing of the reference
- * (src/shared.rs:159-199 has one code path). */
 KC_API int kc_set_resize_mode(int mode);
 KC_API int kc_get_resize_mode(void);
-/* Cache policy (a throughput knob; results are identical): 1 (default, env KC_CACHE_POLICY) = a launch that streams more
- * than the 256 MB Infinity Cache can hold reads its full-size inputs with the nontemporal hint and keeps its result
- * cacheable while that fits; 0 = plain loads and stores everywhere. */
 KC_API int kc_set_cache_policy(int mode);
 KC_API int kc_get_cache_policy(void);
-/* Named A/B and test switches (results are identical whatever they say; unknown names are refused):
- *   "chain1" 1 (default): a single Mix step runs its ahead-of-time straight-line kernel; 0: the step interpreter / the
- *   run-time specialiser, as longer programs do;
- *   "replay" 1 (default): an evaluation that repeats the previous one of the same node exactly (same graph by content, same
- *   node states, same slot data and embedded images by identity) skips the node-by-node walk of src/engine.rs:200-307 and
- *   re-issues the recorded launches; 0: always walk.
- *   "join" 1 (default): a Mix whose two inputs are both chains that have not run keeps both in one program -- one launch,
- *   no plane in between (csrc/runtime.cpp plane_mix; only kernels compiled at run time implement it, and while such a kernel
- *   is not there the second chain runs on its own as before); 0: always run it on the spot.  Bit-identical either way.
- *   "wide" 1 (default): a fused chain may read up to 16 planes per channel (kernels compiled at run time only; cut to the
- *   interpreter's 4 while such a kernel is not there); 0: 4, as before.  Bit-identical either way.
- *   "down2" 0 / 1 (default) / 2: down-sampling with more than 8 taps on both axes runs resize_down2_kernel never / except
- *   where the integer-ratio streaming kernel runs at ratio 4 or 8 / wherever its tables exist (bit-identical; A/B and tests).
- *   "down2_by_rows" -1 (default) / 0 / 1: resize_down2_kernel's job order -- four strips of one row group per workgroup and the
- *   XCDs' eighths row by row (1), four row groups of one strip (0), or by the table (-1: 1 where the windows span several chunks).
- *   "poly2" 1 (default) / 0, "poly2_min_ratio" 8 (default; 2, 4): down-sampling with an integer vertical ratio of at least
- *   poly2_min_ratio and windows of 4 or 6 ages runs resize_poly2_kernel (two waves per band strip) / the kernels it replaces
- *   (bit-identical; A/B and tests).
- *   "link_gbps" (153), "hbm_gbps" (6100): the rates kc_live_graph_partition prices a transfer / a streaming kernel with.
- *   "cache_budget_mb" (208, env KC_CACHE_BUDGET_MB): how much of a launch's streams the cache policy leaves cacheable -- 13/16 of
- *   the MI355X's 256 MB Infinity Cache; HIP reports no size for that cache, so another part sets this.
- *   "chain_unroll" 0 (default: the measured choice) / 1 / 2 / 4 / 6 / 8 (initial value: env KC_CHAIN_UNROLL): float4 per lane of the
- *   step interpreter for programs without divide or pow; "max_blocks" (4096, env KC_MAX_BLOCKS; >= 1): the interpreter's grid
- *   cap, beyond which its workgroups stride over the plane (tuning and tests; bit-identical either way). */
+/* Named A/B and tuning switches: results are bit-identical whatever they say.  An unknown name or a value outside the
+ * accepted ones is refused (KC_ERR_INVALID_ARG, the option unchanged); a flag takes any integer and stores it as 0 / 1.
+ * kc_init reads each option from KC_<NAME> (the name in upper case, e.g. KC_DOWN2=0) if set, as a whole decimal integer
+ * (KC_NT_FORCE also 0x...); a value kc_set_option would refuse fails kc_init with KC_ERR_INVALID_ARG.  Name (default;
+ * accepted values): meaning --
+ *   "chain1" (1; flag): a single Mix step runs its ahead-of-time kernel; 0: the interpreter / specialiser, as longer programs.
+ *   "replay" (1; flag): an evaluation that repeats the previous one of the same node exactly (same graph by content, node
+ *     states, slot data and embedded images by identity) re-issues the recorded launches (src/engine.rs:200-307 not walked).
+ *   "join" (1; flag): a Mix of two chains that have not run keeps both in one program (one launch, csrc/runtime.cpp plane_mix;
+ *     only kernels compiled at run time, else the second chain runs on its own); 0: always run it on the spot.
+ *   "wide" (1; flag): a fused chain reads up to 16 planes per channel (kernels compiled at run time; else 4); 0: 4.
+ *   "fusion" (1; flag): pointwise Mix chains whose intermediates are never observed run as one kernel; 0: every node
+ *     materialises its planes.
+ *   "down2" (1; 0..2): down-sampling with more than 8 taps on both axes runs resize_down2_kernel never / except where
+ *     resize_poly_kernel runs at ratio 4 or 8 / wherever its tables exist.
+ *   "down2_by_rows" (-1; -1..1): resize_down2_kernel's jobs: four strips of one row group per workgroup, the XCDs' eighths row
+ *     by row (1), four row groups of one strip (0), 1 where the windows span several chunks (-1).
+ *   "poly2" (1; 0..1): integer vertical ratios from poly2_min_ratio with windows of 4 or 6 ages run resize_poly2_kernel.
+ *   "poly2_min_ratio" (8; >= 2): see poly2 (8: where it measures faster; 2: everywhere it can run).
+ *   "resize_mode" (0; 0..4): 0 every resize kernel; 1 no resize_poly_kernel; 2 no resize_down_kernel either; 3 two passes through
+ *     HBM only; 4 no integer-ratio up-sampling kernels.  (The reference has one code path, src/shared.rs:159-199.)
+ *   "resize_tile_w" (0; 0..1024), "resize_tile_h" (0; 0..64): the output tile of the tiled resize kernels where both are set and
+ *     it fits; resize_tile_w alone: the up-sampling kernels' tile width; resize_tile_h = 32: resize_down_kernel 8 rows per wave.
+ *   "poly_rows" (0; >= 0): rows per band of resize_poly(2)_kernel, rounded down to a multiple of 4, at least 4; 0: by the launch.
+ *   "poly2_xcd" (-1; -1..2): resize_poly2_kernel's bands in plain order (0), XCD eighths strip-major (2) / band-major (-1, 1).
+ *   "down2_xcd" (-1; -1..1): resize_down2_kernel's tiles in XCD order never (0), always (1), while they fit cache_budget_mb (-1).
+ *   "h2n_tiled" (-1; -1..1): HeightToNormal's workgroups as tiles of column blocks; 0: round 2's plain mapping.
+ *   "cache_policy" (1; 0..1): a launch that streams more than cache_budget_mb reads its full-size inputs nontemporal and keeps
+ *     its result cacheable while that fits; 0: plain loads and stores everywhere.
+ *   "cache_budget_mb" (208; >= 0): what the cache policy leaves cacheable: 13/16 of the MI355X's 256 MB Infinity Cache, the
+ *     share that measured best (profiles/r03_tilecopy4.txt); HIP reports no size for that cache, so another part sets this.
+ *   "nt_force" (-1; >= -1): this nontemporal mask for every launch the cache policy marks (bits 0-7 and 16-23 inputs, 8 result).
+ *   "chain_unroll" (0; one of 0, 1, 2, 4, 6, 8): float4 per lane of the step interpreter without divide or pow; 0: measured.
+ *   "max_blocks" (4096; >= 1): the step interpreter's grid cap, beyond which its workgroups stride over the plane.
+ *   "tune_cap" (0; >= 0): the grid cap of the grid-stride streaming kernels (to_u8, from_u8, height_to_normal); 0: none.
+ *   "upload_ring" (1; flag): kc_image_from_u8 of at most 4 MB copies into a pinned ring and returns; 0: copies and waits.
+ *   "link_gbps" (153; >= 1), "hbm_gbps" (6100; >= 1): what kc_live_graph_partition prices a transfer / a streaming kernel at. */
 KC_API int kc_set_option(const char *name, int value);
 KC_API int kc_get_option(const char *name, int *value);
 /* Diagnostics (host only, works without a device): the structure the integer-ratio up-sampling kernels rely on,

@@ -1,5 +1,7 @@
 // extern "C" surface declared in include/kanter_core_amd.h.
 #include <algorithm>
+#include <cctype>
+#include <climits>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -42,6 +44,69 @@ typedef std::lock_guard<std::recursive_mutex> Lock;
         return KC_ERR_GENERIC;                                          \
     }
 
+// ---------------------------------------------------------------- options
+// One row per field of Options, in the order of the list at kc_set_option (include/kanter_core_amd.h), which says what each means.
+namespace {
+struct OptionRow {
+    enum Kind { FLAG, RANGE, SET } kind;  // FLAG: any integer, stored as != 0; RANGE: lo .. hi; SET: v where bit v of `set` is 1
+    const char *name;
+    int Options::*field;
+    int dflt, lo, hi;
+    uint32_t set;
+    const char *accepted;  // for messages
+    bool accepts(int v) const { return kind == FLAG || (kind == RANGE ? v >= lo && v <= hi : v >= 0 && v < 32 && (set >> v & 1u)); }
+    void store(Options &o, int v) const { o.*field = kind == FLAG ? v != 0 : v; }
+};
+#define KC_FLAG(name, dflt) { OptionRow::FLAG, #name, &Options::name, dflt, 0, 0, 0, "any integer" }
+#define KC_RANGE(name, dflt, lo, hi) { OptionRow::RANGE, #name, &Options::name, dflt, lo, hi, 0, #lo ".." #hi }
+constexpr OptionRow kOptions[] = {
+    KC_FLAG(chain1, 1), KC_FLAG(replay, 1), KC_FLAG(join, 1), KC_FLAG(wide, 1), KC_FLAG(fusion, 1),
+    KC_RANGE(down2, 1, 0, 2), KC_RANGE(down2_by_rows, -1, -1, 1), KC_RANGE(poly2, 1, 0, 1), KC_RANGE(poly2_min_ratio, 8, 2, INT_MAX),
+    KC_RANGE(resize_mode, 0, 0, 4), KC_RANGE(resize_tile_w, 0, 0, 1024), KC_RANGE(resize_tile_h, 0, 0, 64),
+    KC_RANGE(poly_rows, 0, 0, INT_MAX), KC_RANGE(poly2_xcd, -1, -1, 2), KC_RANGE(down2_xcd, -1, -1, 1), KC_RANGE(h2n_tiled, -1, -1, 1),
+    KC_RANGE(cache_policy, 1, 0, 1), KC_RANGE(cache_budget_mb, 208, 0, INT_MAX), KC_RANGE(nt_force, -1, -1, INT_MAX),
+    { OptionRow::SET, "chain_unroll", &Options::chain_unroll, 0, 0, 0, 0x157u /* bits 0, 1, 2, 4, 6, 8 */, "one of 0, 1, 2, 4, 6, 8" },
+    KC_RANGE(max_blocks, 4096, 1, INT_MAX), KC_RANGE(tune_cap, 0, 0, INT_MAX), KC_FLAG(upload_ring, 1),
+    KC_RANGE(link_gbps, 153, 1, INT_MAX), KC_RANGE(hbm_gbps, 6100, 1, INT_MAX),
+};
+static_assert(sizeof kOptions / sizeof kOptions[0] == sizeof(Options) / sizeof(int), "one row per field of Options");
+
+const OptionRow *find_option(const char *name)
+{
+    for (const OptionRow &r : kOptions)
+        if (std::strcmp(r.name, name) == 0) return &r;
+    set_error(std::string("unknown option ") + name);
+    return nullptr;
+}
+
+// Stores every KC_<NAME> that is set in `o`, a copy the caller commits on success: whole decimal integers (nt_force, a bit
+// mask: also 0x...) that kc_set_option would accept.
+int options_from_env(Options &o)
+{
+    for (const OptionRow &r : kOptions) {
+        std::string var = "KC_";
+        for (const char *p = r.name; *p; ++p) var += (char)std::toupper((unsigned char)*p);
+        const char *e = std::getenv(var.c_str());
+        if (!e) continue;
+        char *end = nullptr;  // (an overflow of the long, LONG_MIN / LONG_MAX, fails the int range check below)
+        const long v = std::strtol(e, &end, r.field == &Options::nt_force ? 0 : 10);
+        if (end == e || *end || v < INT_MIN || v > INT_MAX || !r.accepts((int)v)) {
+            set_error(var + "=" + e + " refused: option " + r.name + " accepts " + r.accepted);
+            return KC_ERR_INVALID_ARG;
+        }
+        r.store(o, (int)v);
+    }
+    return KC_OK;
+}
+}  // namespace
+
+Options kc::option_defaults()
+{
+    Options o{};
+    for (const OptionRow &r : kOptions) o.*r.field = r.dflt;
+    return o;
+}
+
 extern "C" {
 
 // ---------------------------------------------------------------- context
@@ -54,6 +119,8 @@ try {
         set_error("kc_init: already bound to another device (one process per GPU)");
         return KC_ERR_INVALID_ARG;
     }
+    Options opt = c.opt;
+    KC_TRY(options_from_env(opt));  // before any HIP call: a refused value fails the same way with or without a device
     int count = 0;
     hipError_t e = hipGetDeviceCount(&count);
     if (e != hipSuccess || count <= 0) {
@@ -72,30 +139,11 @@ try {
     KC_HIP(hipStreamCreateWithFlags(&c.own_stream, hipStreamNonBlocking));
     c.stream = c.own_stream;
     c.device = device_ordinal;
-    if (const char *mb = std::getenv("KC_MAX_BLOCKS")) {
-        int v = std::atoi(mb);
-        if (v >= 1) c.max_blocks = v;
-    }
-    if (const char *rm = std::getenv("KC_RESIZE_MODE")) c.resize_mode = std::atoi(rm);
-    if (const char *cp = std::getenv("KC_CACHE_POLICY")) c.cache_policy = std::atoi(cp) != 0;
-    if (const char *cb = std::getenv("KC_CACHE_BUDGET_MB")) c.cache_budget_mb = std::max(0, std::atoi(cb));
-    if (const char *c1 = std::getenv("KC_CHAIN1")) c.chain1 = std::atoi(c1) != 0;
-    if (const char *j = std::getenv("KC_JOIN")) c.join = std::atoi(j) != 0;
-    if (const char *wd = std::getenv("KC_WIDE")) c.wide = std::atoi(wd) != 0;
-    if (const char *d2 = std::getenv("KC_DOWN2")) c.down2 = std::max(0, std::min(2, std::atoi(d2)));
-    if (const char *p2 = std::getenv("KC_POLY2")) c.poly2 = std::atoi(p2) != 0;
-    if (const char *br = std::getenv("KC_DOWN2_BY_ROWS")) c.down2_by_rows = std::max(-1, std::min(1, std::atoi(br)));
-    if (const char *p2r = std::getenv("KC_POLY2_MIN_RATIO")) c.poly2_min_ratio = std::max(2, std::atoi(p2r));
-    if (const char *rt = std::getenv("KC_RESIZE_TILE_H")) c.resize_tile_h = std::atoi(rt);
-    if (const char *rw = std::getenv("KC_RESIZE_TILE_W")) c.resize_tile_w = std::atoi(rw);
-    if (const char *cu = std::getenv("KC_CHAIN_UNROLL")) {
-        int v = std::atoi(cu);
-        if (v == 1 || v == 2 || v == 4 || v == 6 || v == 8) c.chain_unroll = v;
-    }
     if (const char *sp = std::getenv("KC_SPECIALIZE")) {
         int v = std::atoi(sp);
         if (v >= 0 && v <= 2) specialize_set_mode(v, 0);
     }
+    c.opt = opt;
     c.inited = true;
 #ifdef KC_HOST_SAMPLE
     sampler_start();
@@ -202,59 +250,24 @@ const char *kc_status_string(int s)
     return "unknown status";
 }
 
-int kc_set_fusion(int enabled)
-try {
-    ctx().fusion = enabled != 0;
-    return KC_OK;
-}
-KC_CATCH
-
-int kc_get_fusion(void) { return ctx().fusion ? 1 : 0; }
-
-int kc_set_resize_mode(int mode)
-try {
-    KC_ARG(mode >= 0 && mode <= 4);
-    std::lock_guard<std::recursive_mutex> lk(ctx().mu);
-    ctx().resize_mode = mode;
-    return KC_OK;
-}
-KC_CATCH
-
-int kc_get_resize_mode(void) { return ctx().resize_mode; }
-
-int kc_set_cache_policy(int mode)
-try {
-    KC_ARG(mode == 0 || mode == 1);
-    std::lock_guard<std::recursive_mutex> lk(ctx().mu);
-    ctx().cache_policy = mode;
-    return KC_OK;
-}
-KC_CATCH
-
-int kc_get_cache_policy(void) { return ctx().cache_policy; }
+int kc_set_fusion(int enabled) { return kc_set_option("fusion", enabled); }
+int kc_get_fusion(void) { return options().fusion; }
+int kc_set_resize_mode(int mode) { return kc_set_option("resize_mode", mode); }
+int kc_get_resize_mode(void) { return options().resize_mode; }
+int kc_set_cache_policy(int mode) { return kc_set_option("cache_policy", mode); }
+int kc_get_cache_policy(void) { return options().cache_policy; }
 
 int kc_set_option(const char *name, int value)
 try {
     KC_ARG(name);
-    std::lock_guard<std::recursive_mutex> lk(ctx().mu);
-    if (std::strcmp(name, "chain1") == 0) ctx().chain1 = value != 0;
-    else if (std::strcmp(name, "replay") == 0) ctx().replay = value != 0;
-    else if (std::strcmp(name, "join") == 0) ctx().join = value != 0;
-    else if (std::strcmp(name, "wide") == 0) ctx().wide = value != 0;
-    else if (std::strcmp(name, "down2") == 0 && value >= 0 && value <= 2) ctx().down2 = value;
-    else if (std::strcmp(name, "down2_by_rows") == 0 && value >= -1 && value <= 1) ctx().down2_by_rows = value;
-    else if (std::strcmp(name, "poly2") == 0 && value >= 0 && value <= 1) ctx().poly2 = value;
-    else if (std::strcmp(name, "poly2_min_ratio") == 0 && value >= 2) ctx().poly2_min_ratio = value;
-    else if (std::strcmp(name, "cache_budget_mb") == 0 && value >= 0) ctx().cache_budget_mb = value;
-    else if (std::strcmp(name, "chain_unroll") == 0 && (value == 0 || value == 1 || value == 2 || value == 4 || value == 6 || value == 8))
-        ctx().chain_unroll = value;
-    else if (std::strcmp(name, "max_blocks") == 0 && value >= 1) ctx().max_blocks = value;
-    else if (std::strcmp(name, "link_gbps") == 0 && value > 0) ctx().link_gbps = value;
-    else if (std::strcmp(name, "hbm_gbps") == 0 && value > 0) ctx().hbm_gbps = value;
-    else {
-        set_error(std::string("unknown option ") + name);
+    const OptionRow *r = find_option(name);
+    if (!r) return KC_ERR_INVALID_ARG;
+    if (!r->accepts(value)) {
+        set_error(std::string("option ") + name + " accepts " + r->accepted + ", not " + std::to_string(value));
         return KC_ERR_INVALID_ARG;
     }
+    std::lock_guard<std::recursive_mutex> lk(ctx().mu);
+    r->store(ctx().opt, value);
     return KC_OK;
 }
 KC_CATCH
@@ -262,23 +275,9 @@ KC_CATCH
 int kc_get_option(const char *name, int *value)
 try {
     KC_ARG(name && value);
-    if (std::strcmp(name, "chain1") == 0) *value = ctx().chain1 ? 1 : 0;
-    else if (std::strcmp(name, "replay") == 0) *value = ctx().replay ? 1 : 0;
-    else if (std::strcmp(name, "join") == 0) *value = ctx().join ? 1 : 0;
-    else if (std::strcmp(name, "wide") == 0) *value = ctx().wide ? 1 : 0;
-    else if (std::strcmp(name, "down2") == 0) *value = ctx().down2;
-    else if (std::strcmp(name, "down2_by_rows") == 0) *value = ctx().down2_by_rows;
-    else if (std::strcmp(name, "poly2") == 0) *value = ctx().poly2;
-    else if (std::strcmp(name, "poly2_min_ratio") == 0) *value = ctx().poly2_min_ratio;
-    else if (std::strcmp(name, "cache_budget_mb") == 0) *value = ctx().cache_budget_mb;
-    else if (std::strcmp(name, "chain_unroll") == 0) *value = ctx().chain_unroll;
-    else if (std::strcmp(name, "max_blocks") == 0) *value = ctx().max_blocks;
-    else if (std::strcmp(name, "link_gbps") == 0) *value = ctx().link_gbps;
-    else if (std::strcmp(name, "hbm_gbps") == 0) *value = ctx().hbm_gbps;
-    else {
-        set_error(std::string("unknown option ") + name);
-        return KC_ERR_INVALID_ARG;
-    }
+    const OptionRow *r = find_option(name);
+    if (!r) return KC_ERR_INVALID_ARG;
+    *value = options().*r->field;
     return KC_OK;
 }
 KC_CATCH

@@ -6,8 +6,6 @@
 // The channel count is a run-time argument: one switch per launch picks the loop compiled for it.
 #include "kc_internal.hpp"
 
-#include <cstdlib>
-
 namespace kc {
 
 #include "streaming.h"  // grid_cap, ld_policy / st_policy, quant_u8 / quant_u8_srgb: shared with kernels.hip

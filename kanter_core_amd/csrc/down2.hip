@@ -263,8 +263,8 @@ hipError_t launch_resize_down2(const ResizePlanes &p, int batch, const Down2Args
     // KC_DOWN2_XCD=0 / 1: never / always (A/B); default: when the planes fit the Infinity Cache (a.xcd_per as the caller's hint).
     // Measured (profiles/r03_down2_xcd.txt): one 4096^2 plane 27.9 -> 26.2 us, 3000^2 -> 700^2 17.9 -> 15.4; four 4096^2 planes
     // (268 MB of source, past the cache) 114.6 -> 122.7: there the plain order, whole rows at a time, is kinder to HBM.
-    static const int xcd_env = std::getenv("KC_DOWN2_XCD") ? std::atoi(std::getenv("KC_DOWN2_XCD")) : -1;
-    const bool xcd = xcd_env < 0 ? a.xcd_per != 0 : xcd_env != 0;
+    const int xcd_opt = options().down2_xcd;
+    const bool xcd = xcd_opt < 0 ? a.xcd_per != 0 : xcd_opt != 0;
     a2.xcd_per = 0;
     // Four strips of one row group per workgroup and the jobs dealt to the XCDs in eighths row by row (what resize_poly_kernel
     // gained 8 - 20 % from): here it pays where the row groups' windows span several chunks (ratios from about 1.6: CatmullRom

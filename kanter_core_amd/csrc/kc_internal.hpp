@@ -19,6 +19,16 @@ namespace kc {
 #include "chain_program.h"  // ChainCode, ChainStepRec / ChainStepPair, ChainProgram
 #include "upsample.h"       // UpAxis, UpsampleArgs
 
+// The A/B and tuning switches, one field per row of the option table (c_api.cpp, kOptions).  Their defaults, accepted values
+// and meaning are listed at kc_set_option (include/kanter_core_amd.h).  Context owns the instance; options() reads it.
+struct Options {
+    int chain1, replay, join, wide, fusion, down2, down2_by_rows, poly2, poly2_min_ratio, resize_mode, resize_tile_w, resize_tile_h;
+    int poly_rows, poly2_xcd, down2_xcd, h2n_tiled, cache_policy, cache_budget_mb, nt_force, chain_unroll, max_blocks, tune_cap;
+    int upload_ring, link_gbps, hbm_gbps;
+};
+Options option_defaults();
+const Options &options();
+
 // Per-axis tap table of the separable resampler, resident in HBM.
 struct TapsDev {
     const uint32_t *left;

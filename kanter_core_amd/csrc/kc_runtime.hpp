@@ -222,26 +222,8 @@ struct Context {
     int device = -1;
     hipStream_t own_stream = nullptr;
     hipStream_t stream = nullptr;
-    bool fusion = true;
-    bool replay = true;  // an evaluation that repeats the recorded one is replayed without the walk (kc_set_option("replay", 0); env KC_REPLAY)
-    int down2 = 1;       // resize_down2_kernel: 0 off, 1 except where resize_poly_kernel runs at ratio 4 or 8, 2 there too (kc_set_option("down2"); env KC_DOWN2)
-    int down2_by_rows = -1;   // resize_down2_kernel's job order: four strips of one row group per workgroup, XCDs in eighths row by row;
-                              // -1: where the row groups' windows span several chunks (kc_set_option("down2_by_rows"); env KC_DOWN2_BY_ROWS)
-    int poly2 = 1;            // integer-ratio down-sampling through resize_poly2_kernel (kc_set_option("poly2"); env KC_POLY2); 0: resize_poly_kernel / down2 as before
-    int poly2_min_ratio = 8;  // ... from this vertical ratio on (kc_set_option("poly2_min_ratio"); env KC_POLY2_MIN_RATIO): where it measures faster
+    Options opt = option_defaults();  // the A/B and tuning switches: the option table, c_api.cpp
     bool plain_chains = false;  // set during a graph's first evaluation: chains as the interpreter runs them (4 planes, no joins)
-    bool wide = true;    // chains of up to KC_CHAIN_MAX_IN input planes (compiled kernels only); 0: KC_CHAIN_INTERP_IN as before (kc_set_option("wide"); env KC_WIDE)
-    bool join = true;    // a Mix of two unevaluated chains keeps both in one program (kc_set_option("join", 0); env KC_JOIN)
-    bool chain1 = true;  // one-step programs run the ahead-of-time kernels of chain1.hip (kc_set_option("chain1", 0): interpreter / specialiser, A/B and tests)
-    int link_gbps = 153;   // one xGMI link, what the planner charges a transfer with (kc_set_option("link_gbps"))
-    int hbm_gbps = 6100;   // what a streaming kernel gets from HBM with nothing in the Infinity Cache (kc_set_option("hbm_gbps"))
-    int cache_budget_mb = 208;  // what a launch may leave cacheable: 13/16 of the 256 MB Infinity Cache of an MI355X, the share that measured best (profiles/r03_tilecopy4.txt); kc_set_option("cache_budget_mb") / KC_CACHE_BUDGET_MB for another part
-    int cache_policy = 1;  // 1: launches whose streams exceed the Infinity Cache mark them nontemporal (cache_policy_mask); 0: plain loads / stores (KC_CACHE_POLICY, kc_set_cache_policy)
-    int max_blocks = 4096;  // grid cap of the chain interpreter (KC_MAX_BLOCKS, kc_set_option("max_blocks"))
-    int chain_unroll = 0;  // float4 per thread per decode in the chain kernel; 0 = heuristic (KC_CHAIN_UNROLL, kc_set_option("chain_unroll"))
-    int resize_mode = 0;  // 0 auto (tiled single pass when a tile fits in LDS), 1 no resize_poly_kernel, 2 no resize_down_kernel either (A/B), 3 two passes through HBM only, 4 auto without the integer-ratio up-sampling kernels (KC_RESIZE_MODE, kc_set_resize_mode)
-    int resize_tile_w = 0;  // > 0: force this tile width (KC_RESIZE_TILE_W, tuning only)
-    int resize_tile_h = 0;  // > 0: force this tile height for 256-wide tiles (KC_RESIZE_TILE_H, tuning only)
     std::multimap<size_t, void *> free_blocks;
     uint64_t bytes_in_use = 0, bytes_cached = 0, launches = 0;
     std::map<std::string, uint64_t> counters;  // named event counts (kc_stats_counter): which kernel family ran, transfers ...

@@ -10,7 +10,6 @@
 #include "kc_internal.hpp"
 
 #include <algorithm>
-#include <cstdlib>
 
 namespace kc {
 
@@ -1263,6 +1262,9 @@ static void launch_resize_poly_a(dim3 grid, size_t lds, hipStream_t s, uint32_t 
     else resize_poly_kernel<A, 8><<<grid, 256, lds, s>>>(p, dw, dh, v, h, tile_w, ncp, b);
 }
 
+// The poly_rows option (tuning): 0 (chosen by the launch) or rows per band, rounded down to a multiple of 4 and at least 4
+static uint32_t poly_rows_option() { return options().poly_rows ? std::max(4u, (uint32_t)options().poly_rows / 4u * 4u) : 0u; }
+
 // Rows [reg_a, reg_b) of the vertical table are regular: `ages` x `ratio` taps each, windows `ratio` apart, equal weights.
 hipError_t launch_resize_poly(const ResizePlanes &p, int batch, uint32_t dw, uint32_t dh, TapsDev v, TapsDev h, uint32_t tile_w,
                               uint32_t ncp, uint32_t reg_a, uint32_t reg_b, uint32_t ages, uint32_t ratio, hipStream_t s, ResizeVariant *var)
@@ -1283,7 +1285,6 @@ hipError_t launch_resize_poly(const ResizePlanes &p, int batch, uint32_t dw, uin
     // not fill the chip take SHORT bands: 2048^2 -> 512^2 19.3 / 15.3 / 11.5 us with 12 / 8 / 4 rows, 2048^2 -> 256^2
     // 26.6 / 20.3 / 16.5, 1024^2 -> 256^2 16.7 / 13.2 / 9.6 (profiles/r04_poly_rows_small.txt); past about one wave per SIMD the
     // windows short bands re-read cost more than their trips save (4096^2 -> 1024^2: 22.2 / 24.7 / 33.5 us).
-    static const uint32_t rows_env = std::getenv("KC_POLY_ROWS") ? std::max(4u, (uint32_t)std::atoi(std::getenv("KC_POLY_ROWS")) / 4u * 4u) : 0u;
     // With four strips of a band per workgroup (round 4), same run, one plane, 8 / 12 / 16 / 24 rows: Lanczos3 4096^2 -> 1024^2
     // 23.5 / 22.4 / 26.1 / 29.2 us; RGBA launches 12 / 16 / 24 / 32 rows: Lanczos3 4:1 68.1 / 65.8 / 70.8 / 63.5, CatmullRom 4:1
     // 57.3 / 62.7 / 55.7 / 54.2, but 2048^2 -> 512^2 RGBA 26.4 / 26.3 / 34.2 / 34.4 (profiles/r04_poly_rows_by_band.txt): tall bands
@@ -1301,7 +1302,7 @@ hipError_t launch_resize_poly(const ResizePlanes &p, int batch, uint32_t dw, uin
             }
         if (!small && b.gx * ((regular + 11u) / 12u) * (uint64_t)batch >= 6000u) b.rows = 32u;
     }
-    if (rows_env) b.rows = rows_env;
+    if (const uint32_t rows = poly_rows_option()) b.rows = rows;
     b.n_bands = (b.yb - b.ya + b.rows - 1) / b.rows;
     // what is left: rows above the first band and below the last one, as general tiles of at most 16 rows
     uint32_t nt = 0;
@@ -1574,7 +1575,6 @@ hipError_t launch_resize_poly2(const ResizePlanes &p, int batch, uint32_t dw, ui
     b.n_strips = (dw + tw - 1) / tw;
     b.n_wgx = (b.n_strips + 1u) / 2u;
     // band height as resize_poly_kernel chooses it (a launch lasts as long as one wave lives), for twice the waves per strip
-    static const uint32_t rows_env = std::getenv("KC_POLY_ROWS") ? std::max(4u, (uint32_t)std::atoi(std::getenv("KC_POLY_ROWS")) / 4u * 4u) : 0u;
     b.rows = 12u;
     {
         // (2048^2 -> 256^2 Gaussian: 16.5 / 14.7 us with 4 / 8 rows = 1280 / 640 waves)
@@ -1587,7 +1587,7 @@ hipError_t launch_resize_poly2(const ResizePlanes &p, int batch, uint32_t dw, ui
         // at 4096^2 25.3 -> 30.3: profiles/r04_poly2_rows_rgba.txt, r04_poly2_sweep.txt)
         else if (4u * b.n_wgx * ((regular + 11u) / 12u) * (uint64_t)batch >= 6000u) b.rows = 24u;
     }
-    if (rows_env) b.rows = rows_env;
+    if (const uint32_t rows = poly_rows_option()) b.rows = rows;
     b.n_bands = (b.yb - b.ya + b.rows - 1) / b.rows;
     b.n_band_wgs = b.n_wgx * b.n_bands;
     b.gen_tw = gen_tw;
@@ -1608,12 +1608,12 @@ hipError_t launch_resize_poly2(const ResizePlanes &p, int batch, uint32_t dw, ui
     const uint32_t pair_floats = (8u * KC_POLY2_RING_PITCH + 256u + tw * (h.stride | 1u) + 3u) / 4u * 4u;
     const size_t lds = std::max((size_t)2 * pair_floats * sizeof(float), resize_down_lds_bytes(16, gen_ncp, gen_tw, h.stride));
     if (lds > 64u * 1024u) return hipErrorInvalidValue;
-    static const int xcd_env = std::getenv("KC_POLY2_XCD") ? std::atoi(std::getenv("KC_POLY2_XCD")) : -1;  // 0: plain order, 1: band-major eighths, 2: strip-major
+    const int xcd_opt = options().poly2_xcd;  // 0: plain order, 2: strip-major, else band-major eighths
     (void)xcd;
     XcdOrder x{ 0, 0, 0, 0 };
-    if (xcd_env == 2) {
+    if (xcd_opt == 2) {
         x = xcd_order(b.n_wgx, b.n_bands, true);
-    } else if (xcd_env != 0 && b.n_band_wgs >= 16u) {
+    } else if (xcd_opt != 0 && b.n_band_wgs >= 16u) {
         x.per = (b.n_band_wgs + 7u) / 8u;
         x.n = b.n_band_wgs;
     }
@@ -2053,13 +2053,12 @@ hipError_t launch_height_to_normal(const float *hgt, uint32_t hpitch, uint32_t w
     // Tile width: 128, 64 or 32 quads, the widest that cuts the row into a multiple of 8 column blocks (widths that are
     // multiples of 4096, 2048 or 1024 pixels), else the widest the row holds -- rows shared inside the workgroup pay even when
     // the column blocks wander over the XCDs (3000^2: 29.5 -> 26.3 us).  KC_H2N_TILED=0: the plain mapping (A/B).
-    static const int tiled_env = std::getenv("KC_H2N_TILED") ? std::atoi(std::getenv("KC_H2N_TILED")) : -1;
     uint32_t tq = 0;
     for (uint32_t t : { 7u, 6u, 5u })
         if (!tq && row_units % (8u << t) == 0) tq = t;
     for (uint32_t t : { 7u, 6u, 5u })
         if (!tq && row_units >= (1u << t)) tq = t;
-    bool tiled = tiled_env != 0 && tq != 0;
+    bool tiled = options().h2n_tiled != 0 && tq != 0;
     if (!tq) tq = 7;
     if ((((uint64_t)h + (256u >> tq) - 1) >> (8u - tq)) >= 65536u) tiled = false;
     uint64_t blocks = (total + 255) / 256;

@@ -52,7 +52,7 @@ int image_as_type(kc_image *img, bool rgba, kc_image **out)
     if (s != KC_OK) return s;
     *out = image_new(1, &t3);
     plane_release(t3);
-    if (!ctx().fusion) KC_TRY(image_force(*out));  // unfused mode: as_type is its own pass, like the reference's loop
+    if (!options().fusion) KC_TRY(image_force(*out));  // unfused mode: as_type is its own pass, like the reference's loop
     return KC_OK;
 }
 
@@ -86,8 +86,7 @@ int image_from_u8(const uint8_t *host, uint32_t w, uint32_t h, int channels, kc_
         // The caller may free `host` as soon as we return.  Small images (the reference's own sizes) go through a pinned
         // ring slot and the call does not wait for the stream; larger ones are copied from `host` directly and waited for.
         Context::UploadSlot *slot = nullptr;
-        static const bool ring_on = !std::getenv("KC_UPLOAD_RING") || std::atoi(std::getenv("KC_UPLOAD_RING")) != 0;  // 0: A/B
-        if (ring_on && nbytes <= Context::kUploadSlotMax) {
+        if (c.opt.upload_ring && nbytes <= Context::kUploadSlotMax) {
             slot = &c.upload_ring[c.upload_next];
             c.upload_next = (c.upload_next + 1) % Context::kUploadSlots;
             if (slot->bytes < nbytes) {
@@ -265,7 +264,7 @@ int mix_process(kc_image *left_in, kc_image *right_in, int mix_type, kc_image **
     image_release(right);
     // Fusion off: every node materialises its planes -- R, G and B in ONE launch (blockIdx.y),
     // where the reference loops over them sequentially on one thread (mix.rs:199-213).
-    if (s == KC_OK && *out && !ctx().fusion) {
+    if (s == KC_OK && *out && !options().fusion) {
         s = image_force(*out);
         if (s != KC_OK) {
             image_release(*out);

@@ -71,7 +71,7 @@ double node_weight(const Node &n, bool use_cache)
 double transfer_cost()
 {
     const Context &c = ctx();
-    return 0.3 * (double)c.hbm_gbps / (double)std::max(c.link_gbps, 1);
+    return 0.3 * (double)c.opt.hbm_gbps / (double)std::max(c.opt.link_gbps, 1);
 }
 
 }  // namespace

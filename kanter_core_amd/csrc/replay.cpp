@@ -60,12 +60,6 @@ struct kc_live_graph::ReplayEntry {
 
 namespace kc {
 
-bool replay_enabled()
-{
-    static const bool on = !(std::getenv("KC_REPLAY") && std::atoi(std::getenv("KC_REPLAY")) == 0);
-    return on && ctx().replay;
-}
-
 static uint64_t mix64(uint64_t h, uint64_t v)
 {
     h ^= v + 0x9E3779B97F4A7C15ull + (h << 6) + (h >> 2);
@@ -113,7 +107,7 @@ int replay_try(kc_live_graph &lg, uint32_t id, bool *hit)
 {
     *hit = false;
     const kc_live_graph::ReplayEntry *e = lg.replay;
-    if (!e || e->root != id || lg.use_cache || lg.auto_update || !ctx().fusion || !replay_enabled()) return KC_OK;
+    if (!e || e->root != id || lg.use_cache || lg.auto_update || !options().fusion || !options().replay) return KC_OK;
     if (e->pre_state.size() != lg.node_state.size()) return KC_OK;
     for (auto &ps : e->pre_state) {
         auto it = lg.node_state.find(ps.first);
@@ -219,7 +213,7 @@ static void note_resident(std::set<const void *> &set, const kc_image *img)
 ReplayRecorder *replay_begin(kc_live_graph &lg, uint32_t id)
 {
     Context &c = ctx();
-    if (lg.use_cache || lg.auto_update || !c.fusion || !replay_enabled() || c.capture || lg.depth > 0) return nullptr;
+    if (lg.use_cache || lg.auto_update || !c.opt.fusion || !c.opt.replay || c.capture || lg.depth > 0) return nullptr;
     if (lg.g.nodes.size() > 4096) return nullptr;  // the check is linear in the graph; keep it negligible
     auto *r = new ReplayRecorder();
     auto *e = new kc_live_graph::ReplayEntry();

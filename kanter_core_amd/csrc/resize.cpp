@@ -506,12 +506,12 @@ static bool tile_fits(const TapsEntry &tv, const TapsEntry &th, kc_size size, ui
 
 static TileChoice choose_tile(const TapsEntry &tv, const TapsEntry &th, kc_size size)
 {
-    Context &c = ctx();
+    const Options &o = options();
     TileChoice t;
     // Both axes down-sampled: the wave-uniform form.  Its vertical pass deals 64 column quads to a wave, so the widest
     // tile whose source window is at most 64 quads wastes no lanes; a wave walks 4 (tile of 16) or 8 (tile of 32) rows.
-    if (th.dev.stride > KC_RESIZE_REG_TAPS && tv.dev.stride > KC_RESIZE_REG_TAPS && c.resize_mode != 2) {
-        const uint32_t rows = c.resize_tile_h == 32 ? 32u : 16u;  // KC_RESIZE_TILE_H=32: tuning
+    if (th.dev.stride > KC_RESIZE_REG_TAPS && tv.dev.stride > KC_RESIZE_REG_TAPS && o.resize_mode != 2) {
+        const uint32_t rows = o.resize_tile_h == 32 ? 32u : 16u;  // KC_RESIZE_TILE_H=32: tuning
         for (uint32_t tw = 64; tw >= 4; tw -= 4) {
             const uint32_t groups = tile_groups(th.host, size.width, tw);
             if (groups > 64) continue;  // the intermediate rows hold 256 floats
@@ -521,14 +521,14 @@ static TileChoice choose_tile(const TapsEntry &tv, const TapsEntry &th, kc_size 
             t.ncp = 4u * groups;
             t.ok = t.down = true;
             const TapsHost &hv = tv.host;
-            t.poly = rows == 16 && c.resize_mode != 1 && (hv.reg_ages == 2 || hv.reg_ages == 4 || hv.reg_ages == 6) &&
+            t.poly = rows == 16 && o.resize_mode != 1 && (hv.reg_ages == 2 || hv.reg_ages == 4 || hv.reg_ages == 6) &&
                      (hv.reg_ratio == 2 || hv.reg_ratio == 4 || hv.reg_ratio == 8) && hv.reg_b - hv.reg_a >= 16 && hv.reg_a <= 16 &&
                      size.height - (hv.reg_a + (hv.reg_b - hv.reg_a) / 4 * 4) <= 48;
             return t;
         }
     }
-    if (c.resize_tile_w > 0 && c.resize_tile_h > 0 &&  // tuning override (KC_RESIZE_TILE_W / _H)
-        tile_fits(tv, th, size, (uint32_t)c.resize_tile_w, (uint32_t)c.resize_tile_h, 64 * 1024, t))
+    if (o.resize_tile_w > 0 && o.resize_tile_h > 0 &&  // tuning override (KC_RESIZE_TILE_W / _H)
+        tile_fits(tv, th, size, (uint32_t)o.resize_tile_w, (uint32_t)o.resize_tile_h, 64 * 1024, t))
         return t;
     // Wide horizontal windows (down-sampling): the vertical pass re-reads window rows per output row, so small tiles --
     // many workgroups, short dependent chains -- win (profiles/resize_tile_sweep.py).  With the intermediate rows
@@ -550,8 +550,8 @@ static TileChoice choose_tile(const TapsEntry &tv, const TapsEntry &th, kc_size 
 // Integer-ratio up-sampling on both axes (upsample.h): tile and LDS pitch for upsample_chain_tile, or false.
 static bool up_plan(const TapsEntry &tv, const TapsEntry &th, UpsampleArgs &u)
 {
-    Context &c = ctx();
-    if (c.resize_mode >= 3 || !tv.host.up_ok || !th.host.up_ok) return false;
+    const Options &o = options();
+    if (o.resize_mode >= 3 || !tv.host.up_ok || !th.host.up_ok) return false;
     u.H = th.host.up;
     u.V = tv.host.up;
     if (u.H.taps != u.V.taps || !u.H.qcls || !u.V.cls) return false;
@@ -567,8 +567,8 @@ static bool up_plan(const TapsEntry &tv, const TapsEntry &th, UpsampleArgs &u)
             best_pad = pad;
         }
     }
-    if (c.resize_tile_w > 0 && c.resize_tile_w % 4 == 0 && c.resize_tile_w <= 1024 && 256 % (c.resize_tile_w / 4) == 0)
-        best = (uint32_t)c.resize_tile_w;  // KC_RESIZE_TILE_W: tuning
+    if (o.resize_tile_w > 0 && o.resize_tile_w % 4 == 0 && 256 % (o.resize_tile_w / 4) == 0)
+        best = (uint32_t)o.resize_tile_w;  // KC_RESIZE_TILE_W: tuning
     u.tile_w = best;
     uint32_t quads = 1;  // the widest window any tile needs, in source quads, exactly as the kernel lays it out
     for (uint32_t x0 = 0; x0 < dw; x0 += u.tile_w) {
@@ -616,7 +616,7 @@ static int resize_run_taps(kc_plane *const *srcs, kc_plane *const *dsts, int n, 
         c.alg_bytes += (uint64_t)n * 4 * ((uint64_t)s0->w * s0->h + (uint64_t)size.width * size.height);
         return KC_OK;
     }
-    if (c.resize_mode != 3) {
+    if (c.opt.resize_mode != 3) {
         const TileChoice t = choose_tile(*tv, *th, size);
         if (t.ok) {
             ResizePlanes rp{};
@@ -633,13 +633,13 @@ static int resize_run_taps(kc_plane *const *srcs, kc_plane *const *dsts, int n, 
             // kc_set_option("cache_budget_mb")); resize_down2_kernel follows it, resize_poly2_kernel deals its bands to the XCDs
             // at every size (launch_resize_poly2)
             const bool fits_cache = (uint64_t)n * 4 * ((uint64_t)s0->w * s0->h + (uint64_t)size.width * size.height) <=
-                                    ((uint64_t)c.cache_budget_mb << 20);
+                                    ((uint64_t)c.opt.cache_budget_mb << 20);
             ResizeVariant var{};
             // integer ratios: two waves to a band's strip (resize_poly2_kernel)
             // (where it measures faster than the forms below -- profiles/r04_poly2_sweep.txt: ratio 8 with windows of 4 or 6 ages,
             // Gaussian 4096^2 -> 512^2 27.6 -> 25.3 us, 8192^2 -> 1024^2 82.5 -> 72.5; at ratio 4 and 2 it is behind resize_poly_kernel
             // and resize_down2_kernel, 24.8 against 21.2 us and 34.3 against 24.5; kc_set_option("poly2_min_ratio") moves the line)
-            if (t.poly && c.poly2 && tv->host.reg_ratio >= (uint32_t)c.poly2_min_ratio && tv->host.reg_ages >= 4 && th->host.p2_tile_w) {
+            if (t.poly && c.opt.poly2 && tv->host.reg_ratio >= (uint32_t)c.opt.poly2_min_ratio && tv->host.reg_ages >= 4 && th->host.p2_tile_w) {
                 hipError_t e2 = launch_resize_poly2(rp, n, size.width, size.height, tv->dev, th->dev, th->host.p2_tile_w, t.tile_w, t.ncp,
                                                     tv->host.reg_a, tv->host.reg_b, tv->host.reg_ages, tv->host.reg_ratio, fits_cache, c.stream, &var);
                 if (e2 != hipSuccess) return hip_fail(e2, "launch_resize_poly2");
@@ -651,7 +651,7 @@ static int resize_run_taps(kc_plane *const *srcs, kc_plane *const *dsts, int n, 
                 return KC_OK;
             }
             const bool poly_first = t.poly && tv->host.reg_ratio >= 4;
-            if (c.down2 > (poly_first ? 1 : 0) && tv->host.d2_nc && tv->host.d2_vrec_dev && th->host.d2_tile_w &&
+            if (c.opt.down2 > (poly_first ? 1 : 0) && tv->host.d2_nc && tv->host.d2_vrec_dev && th->host.d2_tile_w &&
                 th->host.d2_hw_dev && th->host.d2_strips_dev) {
                 Down2Args a{};
                 a.vrec = tv->host.d2_vrec_dev;
@@ -665,7 +665,7 @@ static int resize_run_taps(kc_plane *const *srcs, kc_plane *const *dsts, int n, 
                 a.dw = size.width;
                 a.dh = size.height;
                 a.xcd_per = fits_cache ? 1u : 0u;
-                a.by_rows = c.down2_by_rows < 0 ? (tv->host.d2_nc > 1 ? 1u : 0u) : (c.down2_by_rows ? 1u : 0u);
+                a.by_rows = c.opt.down2_by_rows < 0 ? (tv->host.d2_nc > 1 ? 1u : 0u) : (c.opt.down2_by_rows ? 1u : 0u);
                 hipError_t e2 = launch_resize_down2(rp, n, a, c.stream, &var);
                 if (e2 != hipSuccess) return hip_fail(e2, "launch_resize_down2");
                 c.launches++;
@@ -808,7 +808,7 @@ int chain_resize_launch(const ChainProgram &P, int batch, int mode, kc_plane *co
 {
     Context &c = ctx();
     *launched = false;
-    if (!c.fusion || c.resize_mode == 3 || mode != 0 || P.n_ops > 16 || P.n_in < 1 || P.n_in > 4) return KC_OK;
+    if (!c.opt.fusion || c.opt.resize_mode == 3 || mode != 0 || P.n_ops > 16 || P.n_in < 1 || P.n_in > 4) return KC_OK;
     const kc_plane *s0 = sampled[0];
     const kc_size size{ s0->w, s0->h };
     TapsEntry *tv = nullptr, *th = nullptr;
@@ -889,7 +889,7 @@ int resize_image(kc_image *src, kc_size size, int filter, kc_image **out)
             }
         if (!p[i]) s = resize_plane(src->planes[i], size, filter, &p[i]);
     }
-    if (s == KC_OK && !ctx().fusion) s = resize_force_many(p, src->n);  // one launch for the image's planes
+    if (s == KC_OK && !options().fusion) s = resize_force_many(p, src->n);  // one launch for the image's planes
     if (s == KC_OK) *out = image_new(src->n, p);
     for (int i = 0; i < src->n; ++i) plane_release(p[i]);
     return s;

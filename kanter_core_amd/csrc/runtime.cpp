@@ -28,6 +28,8 @@ Context &ctx()
     return c;
 }
 
+const Options &options() { return ctx().opt; }
+
 void set_error(const std::string &msg) { g_last_error = msg; }
 const std::string &last_error() { return g_last_error; }
 
@@ -303,7 +305,7 @@ ChainLink::~ChainLink()
 static int chain_in_limit()
 {
     const Context &c = ctx();
-    return (c.wide && c.fusion && !c.plain_chains && specialize_get_mode() != 0) ? KC_CHAIN_MAX_IN : KC_CHAIN_INTERP_IN;
+    return (c.opt.wide && c.opt.fusion && !c.plain_chains && specialize_get_mode() != 0) ? KC_CHAIN_MAX_IN : KC_CHAIN_INTERP_IN;
 }
 
 // Identity of a chain input, as input_index() sees it, as a value (see ChainLink::InKey).
@@ -567,12 +569,12 @@ static int chain_prepare(kc_plane *p)
 // to the same block every time but 98.9 us when a graph still holds its previous result, which is the usual case.
 uint32_t chain_cache_policy(const uint32_t *refs, uint32_t n, uint64_t stream_bytes, uint64_t out_bytes)
 {
-    if (!ctx().cache_policy) return 0;
-    static const long forced = std::getenv("KC_NT_FORCE") ? std::strtol(std::getenv("KC_NT_FORCE"), nullptr, 0) : -1;  // tuning: this mask for every launch
+    const Options &o = options();
+    if (!o.cache_policy) return 0;
     uint32_t all = 0;
     for (uint32_t k = 0; k < n; ++k) all |= KC_CHAIN_NT_BIT(k);
-    if (forced >= 0) return (uint32_t)forced & (all | 0x100u);
-    const uint64_t budget = (uint64_t)ctx().cache_budget_mb << 20;
+    if (o.nt_force >= 0) return (uint32_t)o.nt_force & (all | 0x100u);  // tuning: this mask for every launch
+    const uint64_t budget = (uint64_t)o.cache_budget_mb << 20;
     if (n * stream_bytes + out_bytes <= budget) return 0;
     uint32_t mask = all;
     uint64_t used = 0;
@@ -590,10 +592,10 @@ uint32_t chain_cache_policy(const uint32_t *refs, uint32_t n, uint64_t stream_by
 
 uint32_t cache_policy_mask(uint64_t in_bytes, uint64_t out_bytes, uint32_t n_resident)
 {
-    if (!ctx().cache_policy) return 0;
-    static const long forced = std::getenv("KC_NT_FORCE") ? std::strtol(std::getenv("KC_NT_FORCE"), nullptr, 0) : -1;  // tuning: this mask for every launch
-    if (forced >= 0) return (uint32_t)forced & (((1u << n_resident) - 1u) | 0x100u);
-    const uint64_t budget = (uint64_t)ctx().cache_budget_mb << 20;
+    const Options &o = options();
+    if (!o.cache_policy) return 0;
+    if (o.nt_force >= 0) return (uint32_t)o.nt_force & (((1u << n_resident) - 1u) | 0x100u);  // tuning: this mask for every launch
+    const uint64_t budget = (uint64_t)o.cache_budget_mb << 20;
     if (in_bytes + out_bytes <= budget) return 0;
     uint32_t mask = (1u << n_resident) - 1u;
     if (out_bytes > budget) mask |= 0x100u;
@@ -655,7 +657,7 @@ hipError_t chain_dispatch(ChainProgram &P, int batch, int mode, uint32_t w, uint
         P.rows = h;
         P.row_units = row_units;
     }
-    if (!launched && P.n_ops == 1 && c.chain1) {
+    if (!launched && P.n_ops == 1 && c.opt.chain1) {
         // a single Mix step: its ahead-of-time straight-line kernel (chain1.hip)
         Chain1Args a{};
         const uint32_t w0 = P.step[0][0].a.word, from = w0 >> 8;
@@ -696,7 +698,7 @@ hipError_t chain_dispatch(ChainProgram &P, int batch, int mode, uint32_t w, uint
             for (uint32_t i = 0; i < P.n_ops; ++i)
                 if ((((i & 1u) ? P.step[0][i / 2].b.word : P.step[0][i / 2].a.word) & 0xffu) == CH_SAVE_LOAD) return hipErrorNotReady;
             ChainVariant v;
-            e = launch_chain(P, batch, mode, c.max_blocks, c.chain_unroll, c.stream, &v);
+            e = launch_chain(P, batch, mode, c.opt.max_blocks, c.opt.chain_unroll, c.stream, &v);
             if (e == hipSuccess && v.k == 0) c.counters[chain_counter_names().k0[v.mode]]++;
             else if (e == hipSuccess && v.k > 0) c.counters[chain_counter_names().interp[v.k][v.u][v.mode][v.nt ? 1 : 0]]++;
         }
@@ -1041,7 +1043,7 @@ static kc_plane *lazy_pair_victim(kc_plane *l, kc_plane *r)
 static bool join_ok(const kc_plane *acc, const kc_plane *sub)
 {
     Context &c = ctx();
-    if (!c.join || !c.fusion || c.plain_chains || acc == sub || specialize_get_mode() == 0) return false;
+    if (!c.opt.join || !c.opt.fusion || c.plain_chains || acc == sub || specialize_get_mode() == 0) return false;
     const ChainLink &A = *acc->link, &B = *sub->link;
     const int limit = chain_in_limit();
     if (std::max<int>(A.saved, B.saved + 1) > KC_CHAIN_MAX_SAVED || A.n_in > limit - 1 || B.n_in > limit) return false;

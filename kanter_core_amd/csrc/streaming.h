@@ -3,16 +3,13 @@
 // Included inside namespace kc by both units; every definition is static, each unit keeps its own copy.
 #pragma once
 
-// Grid cap of the grid-stride streaming kernels (to_u8, from_u8, height_to_normal); KC_TUNE_CAP overrides (tuning).
+// Grid cap of the grid-stride streaming kernels (to_u8, from_u8, height_to_normal); the tune_cap option overrides (tuning).
 // Default: no cap, one quad / pixel per thread -- from_u8 58.1 -> 50.4 us, height_to_normal 56.8 -> 55.4 us at 4096^2
 // against 8192 workgroups looping twice (profiles/r02_kernel_times.txt); to_u8 does not care.
 static uint64_t grid_cap(uint64_t dflt)
 {
-    static long v = [] {
-        const char *e = std::getenv("KC_TUNE_CAP");
-        return e ? std::atol(e) : 0L;
-    }();
-    return v > 0 ? (uint64_t)v : dflt;
+    const int cap = options().tune_cap;
+    return cap > 0 ? (uint64_t)cap : dflt;
 }
 
 // Loads / stores with the launch's cache policy (ChainProgram::nt_mask; runtime.cpp, cache_policy_mask) as a compile-time
