@@ -1,14 +1,20 @@
 #!/usr/bin/env python3
 """Headline benchmark: node-Mpix/s of the 32-node linear mix/invert graph on 4096x4096 f32x4
 (BASELINE.json metric; SURVEY.md 8(d) config #3 at 4096^2) on one MI355X, plus the HBM roofline
-fraction of the dominant kernel and the CPU oracle timed on this box's host cores.
+fraction of the dominant kernel; with --full also the side measurements and the CPU oracle timed on the host's cores.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload ...] [--size 4096] [--nodes 32] [--dump-outputs DIR]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload ...] [--size 4096] [--nodes 32] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
 
 A "step" is one full evaluation of the graph (every node over every pixel) on inputs already
 resident in HBM.  Rank 0 prints ONE JSON line.
+
+A plain run does only what its line needs: it sets up, warms up, times the --steps steps, writes --dump-outputs and prints
+the line (the roofline figures of the timed region included).  --full adds everything that takes runs of its own, all after
+the timed region: the per-step spread, the cold rotation (roofline.frac_cold), the unfused and PCIe-inclusive legs, the CPU
+baselines, the parity checks against the oracle, e2e's PCIe probe, fanin's run without the gather and the N > 1 gather leg.
+--no-extras and --no-cpu-baseline leave out parts of that.
 
 Default workload:
     N = 1   chain32: the headline.  One launch per step (the 32 nodes are one fused chain), the kernel compiled for that
@@ -18,7 +24,8 @@ Default workload:
             row band of the result through the library's band path (kc_live_graph_evaluate_band, csrc/bands.cpp) and
             holding only those rows of the inputs.  A pointwise graph needs no halo and no exchange: "scaling": "strong"
             (fixed total work), time = max over ranks.  A side leg outside the timed region ("gather_to_rank0") then moves the
-            finished bands to rank 0 through the library's communicator, so that a multi-GPU run also measures a transfer.
+            finished bands to rank 0 through the library's communicator, so that a multi-GPU run also measures a transfer
+            (--full).
 
 Other workloads (parity-tested configs of BASELINE.json, reported in DESIGN.md):
     --workload mix1           config #1: one Mix(Add) node, two 4096^2 f32x4 inputs
@@ -34,10 +41,10 @@ Other workloads (parity-tested configs of BASELINE.json, reported in DESIGN.md):
     --workload e2e            the host boundary (row f-4): RGBA8 host images in (deconstruct_image) -> the 32-node graph -> RGBA8 out
                               (to_u8) through the pipelined u8 route (kc_u8_pipe: pinned buffers, copy streams; the upload of image
                               k + 1 and the download of image k - 1 overlap the evaluation of image k); images/s and the fraction of
-                              the box's measured PCIe rate ("pcie")
+                              the box's measured PCIe rate ("pcie", --full)
     --cold                    (chain32 / mix1 / resize_blend, N = 1) the timed region itself rotates over 4 instances on different
                               inputs: the run whose kernel trace reproduces roofline.frac_cold
-Every workload run with N = 1 also carries a "parity" object: the timed graph's result against the oracle.
+With --full a run also carries a "parity" object: the timed graph's result against the oracle.
 --dump-outputs DIR writes the timed path's result of the last timed step as .npy files (float32; a fixed, seeded sample
 of each array when the whole would exceed 64 MB), so that two builds can be compared output for output.
 """
@@ -150,8 +157,12 @@ def main():
                          "the Infinity Cache): what roofline.frac_cold measures, as the main region -- for profiling that case")
     ap.add_argument("--size", type=int, default=None, help="default 4096; 8192 for the multi-GPU default workload")
     ap.add_argument("--nodes", type=int, default=32)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="skip the unfused and PCIe-inclusive side measurements")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed region, also run the measurements and checks the line's headline does not need: per-step "
+                         "spread, cold rotation, unfused and PCIe-inclusive legs, CPU baselines, parity against the oracle, e2e's "
+                         "PCIe probe, fanin without the gather, the N > 1 gather leg")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baselines and the oracle's parity checks")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: skip the cold rotation and the unfused and PCIe-inclusive side measurements")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="after the timed steps, write what the timed path computed in its last step (the arrays its caller receives) "
                          "as DIR/<name>.npy in float32; arrays over the 64 MB budget are a fixed, seeded sample of their elements")
@@ -167,6 +178,9 @@ def main():
             args.size = 8192
     if args.size is None:
         args.size = 4096
+    # everything after the timed region that the line's headline does not need runs with --full only
+    extras = args.full and not args.no_extras
+    oracle_checks = args.full and not args.no_cpu_baseline
 
     import numpy as np
     import torch
@@ -640,7 +654,7 @@ def main():
                   "first sightings only)") if kc.specialize_stats()["specialized_launches"] else "upsample_chain_kernel<2,3,true>"
     elif kc.specialize_stats()["specialized_launches"] and "chain_kernel<" in kernel:
         kernel = "kc_chain_<hash> (the chain program compiled to straight-line code at run time, csrc/specialize.cpp; " + kernel + " = the interpreter, first sightings only)"
-    main_step_us = step_spread(main_step, max(20, min(args.steps, 100)))
+    main_step_us = step_spread(main_step, max(20, min(args.steps, 100))) if args.full else None
     total_px = node_px
     job_bytes, job_dev_s = alg_bytes, dev_s
     if world > 1:
@@ -692,7 +706,7 @@ def main():
         "data": "synthetic",
         "config": {
             "workload": desc, "graph_nodes": N if args.workload == "chain32" else None, "width": S, "height": S,
-            "channels": 4, "use_cache": False,
+            "channels": 4, "use_cache": False, "full": args.full,
             "series": ("%s at %dx%d: the line for --gpus N of this workload and size; N = 1 runs the same graph through the same path"
                        % ("chain32_rows (one graph split by row bands, strong scaling)" if band is not None else args.workload, S, S)),
             "cache_policy": kc.get_cache_policy(),
@@ -718,13 +732,14 @@ def main():
             "algorithmic_bytes_per_step": alg_bytes, "closed_form_bytes_per_step": formula_bytes,
             "kernel_us": round(per_step_s / max(launches_per_step, 1.0) * 1e6, 2),
             "launches_per_step": launches_per_step,
-            # separate pass, one HIP event after every step (>= 20 steps): spread of individual steps, event overhead included
-            "step_us_median": round(main_step_us[len(main_step_us) // 2], 2), "step_us_min": round(main_step_us[0], 2),
-            "step_us_max": round(main_step_us[-1], 2),
             "specialized_kernel": bool(kc.specialize_stats()["specialized_launches"]),
             "host_us_per_step_first5": [round(x, 1) for x in main_host_us[:5]], "host_us_per_step_median": round(sorted(main_host_us)[len(main_host_us) // 2], 1),
         },
     }
+    if main_step_us is not None:
+        # separate pass, one HIP event after every step (>= 20 steps): spread of individual steps, event overhead included
+        out["roofline"].update({"step_us_median": round(main_step_us[len(main_step_us) // 2], 2), "step_us_min": round(main_step_us[0], 2),
+                                "step_us_max": round(main_step_us[-1], 2)})
 
     if dumped is not None:
         out["dump_outputs"] = dumped
@@ -733,21 +748,24 @@ def main():
     if args.workload == "e2e":
         for sl in range(depth):
             pipe.wait_download(sl)
-        pcie = measure_pcie()
         per_image_s = wall / args.steps
         in_b, out_b = 4.0 * S * S, 4.0 * S * S
-        bound_s = max(in_b, out_b) / (pcie["duplex_GBps_per_direction"] * 1e9)  # both directions at once, each at its duplex rate
         out["metric"] = "images/s, RGBA8 %dx%d in -> %d-node graph -> RGBA8 out (host to host)" % (S, S, N)
         out["value"] = round(1.0 / per_image_s, 1)
         out["unit"] = "images/s"
-        out["roofline"] = {"bound": "pcie", "achieved": round(in_b / per_image_s / 1e9, 2), "peak": pcie["duplex_GBps_per_direction"],
-                           "unit": "GB/s", "frac": round(bound_s / per_image_s, 4),
-                           "frac_definition": "time the slower direction of one image needs at the measured full-duplex PCIe rate / measured time per image",
+        out["roofline"] = {"bound": "pcie", "achieved": round(in_b / per_image_s / 1e9, 2), "unit": "GB/s",
                            "gpu_side": {"algorithmic_bytes_per_image": alg_bytes, "hbm_time_us_at_6.1TBps": round(alg_bytes / 6.1e12 * 1e6, 1)},
                            "launches_per_step": launches_per_step, "traffic": None}
-        out["pcie"] = pcie
+        if args.full:
+            # the peak and the fraction need the box's PCIe rates: copies of their own
+            pcie = measure_pcie()
+            bound_s = max(in_b, out_b) / (pcie["duplex_GBps_per_direction"] * 1e9)  # both directions at once, each at its duplex rate
+            out["roofline"].update({"peak": pcie["duplex_GBps_per_direction"], "frac": round(bound_s / per_image_s, 4),
+                                    "frac_definition": "time the slower direction of one image needs at the measured full-duplex PCIe rate / "
+                                                       "measured time per image"})
+            out["pcie"] = pcie
         out["bytes_per_image"] = {"in": in_b, "out": out_b, "f32_route_would_move": 2 * 16.0 * S * S}
-        if not args.no_cpu_baseline:
+        if oracle_checks:
             # parity: what reached the host for the last image of every slot against the oracle's deconstruct -> graph -> to_u8 on
             # three 32-row crops (the graph is pointwise)
             from oracle import oracle as orc
@@ -764,7 +782,7 @@ def main():
             orc.set_threads(1)
             out["parity"] = {"checked_bytes": checked, "byte_mismatches": mism}
         pipe.close()
-    if rank == 0 and world == 1 and band is None and args.workload in ("chain32", "mix1", "resize_blend") and not args.no_extras and not args.cold:
+    if rank == 0 and world == 1 and band is None and args.workload in ("chain32", "mix1", "resize_blend") and extras and not args.cold:
         # ---- cold: nothing a step touches can still be in the 256 MB Infinity Cache ----
         # The timed region above re-evaluates ONE graph on the same inputs (what an editor does, and what the contract asks
         # for); with the cache policy (csrc/runtime.cpp, chain_cache_policy) one long-lived input of it stays in the Infinity
@@ -788,7 +806,7 @@ def main():
         }
         del cold_steps
 
-    if rank == 0 and args.workload == "chain32" and not args.no_extras and band is None:
+    if rank == 0 and args.workload == "chain32" and extras and band is None:
         # ---- the same graph with every node materialised (use_cache = true): N launches per step ----
         gu = make(True)
         k2 = max(5, args.steps // 10)
@@ -817,7 +835,7 @@ def main():
                                          "overlaps the directions: --workload e2e gives its rate and its fraction of the box's PCIe peak"}
         del res, lgp
 
-    if rank == 0 and world == 1 and args.workload == "chain32" and not args.no_cpu_baseline and band is None:
+    if rank == 0 and world == 1 and args.workload == "chain32" and oracle_checks and band is None:
         from oracle import oracle as orc
         orc.set_threads(1)
         reps, cpu_s, ref = 0, 0.0, None
@@ -888,7 +906,7 @@ def main():
         mism = int(sum((x.view(np.uint32) != y.view(np.uint32)).sum() for x, y in zip(got, ref)))
         out["parity"] = {"checked_pixels": S * rows * 4, "bit_mismatches": mism}
 
-    if rank == 0 and world == 1 and args.workload in ("mix1", "resize_blend", "fanin") and not args.no_cpu_baseline and g is not None:
+    if rank == 0 and world == 1 and args.workload in ("mix1", "resize_blend", "fanin") and oracle_checks and g is not None:
         # parity of the timed graph against the oracle on the same inputs (the oracle as checker, after the timed region)
         from oracle import oracle as orc
         orc.set_threads(usable_cores())
@@ -917,7 +935,7 @@ def main():
         mism = int(sum((~nan_ok(x, y)).sum() for x, y in zip(got, ref)))
         out["parity"] = {"checked_pixels": S * S * 4, "bit_mismatches": mism}
 
-    if band is not None and not args.no_cpu_baseline:
+    if band is not None and oracle_checks:
         # parity of the row-band path on every rank: three 32-row crops of this rank's band (its first, middle and last rows)
         # against the oracle on the same rows of the inputs -- the graph is pointwise, so a crop's result depends on nothing else
         from oracle import oracle as orc
@@ -935,7 +953,7 @@ def main():
         out["parity"] = {"checked_pixels": checked, "bit_mismatches": mism,
                          "how": "3 crops of 32 rows per rank against the oracle on the same rows, summed over the ranks"}
 
-    if args.workload == "fanin" and world > 1 and not args.no_cpu_baseline:
+    if args.workload == "fanin" and world > 1 and oracle_checks:
         # parity of the partitioned evaluation: the home rank's result against the oracle on three 32-row crops (the graph
         # is pointwise); every rank learns the verdict
         verdict = torch.zeros(2, device=red_dev, dtype=torch.float64)
@@ -972,7 +990,7 @@ def main():
         out["plan"] = {"kind": ("single", "branches", "bands")[ev.plan.kind], "policy": args.policy,
                        "estimates_in_units_of_one_fused_rgba_chain": ev.plan.estimates, "bands": ev.plan.bands or None,
                        "transfers": len(ev.plan.transfers), "transport": kc.comm_transport() or None}
-        if ev.plan.kind == kc.PlanKind.Bands and world > 1:
+        if ev.plan.kind == kc.PlanKind.Bands and world > 1 and args.full:
             # the same plan with the bands left where they are (a consumer that is row-parallel too): what the gather costs
             ev.plan.set_gather(False)
             wall_ng, dev_ng, _ = timed(step, max(5, args.steps // 2), 2)
@@ -982,10 +1000,10 @@ def main():
             out["plan"]["ms_per_step_without_gather"] = round(float(t[0].item()) / max(5, args.steps // 2) * 1e3, 4)
         out["multi_gpu_measured"] = world > 1 and args.dist_backend == "nccl"
 
-    if band is not None and world > 1:
+    if band is not None and world > 1 and args.full:
         # The default N > 1 workload moves no plane (a pointwise graph by rows needs no exchange).  This leg does: every rank's
         # finished band goes to rank 0's row offset through the library's communicator (kc_comm_gather_bands), so that a multi-GPU
-        # run also carries a measured transfer.  Outside the timed region above; never part of `value`.
+        # run with --full also carries a measured transfer.  Outside the timed region above; never part of `value`.
         leg = {}
         # This leg is the first thing in the run that makes the ranks wait for EACH OTHER'S GPUs (counters in shared memory that
         # streams wait on): if it ever stalls, the line measured above must still come out.  Every rank arms the same timer; when
@@ -1019,7 +1037,7 @@ def main():
             leg = {"ms_per_step": round(float(t[0].item()) / k_g * 1e3, 4), "steps": k_g, "transport": kc.comm_transport(),
                    "bytes_into_rank0_per_step": moved, "inbound_GBps": round(moved / (float(t[0].item()) / k_g) / 1e9, 1),
                    "what": "band evaluation + gather of the R, G, B rows of the other ranks' bands into rank 0's image (alpha is a constant)"}
-            if rank == 0 and not args.no_cpu_baseline:
+            if rank == 0 and oracle_checks:
                 from oracle import oracle as orc
                 got = band_keep[0].planes()
                 mism = 0

@@ -13,7 +13,7 @@ print("%-12s kernel_us=%.2f frac=%.3f median=%.2f min=%.2f parity=%s" % (sys.arg
 for rep in 1 2; do
   for v in "$@"; do
     if [ "$v" = base ]; then cp /tmp/base.so $R/kanter_core_amd/libkanter_core_amd.so; else cp $R/profiles/ab_libs/$v.so $R/kanter_core_amd/libkanter_core_amd.so; fi
-    python3 $R/bench.py --workload $W --steps 200 --warmup 20 --no-cpu-baseline ${BENCH_EXTRA:-} 2>/dev/null | python3 -c "$P" $v
+    python3 $R/bench.py --full --workload $W --steps 200 --warmup 20 --no-cpu-baseline ${BENCH_EXTRA:-} 2>/dev/null | python3 -c "$P" $v
   done
 done
 cp /tmp/base.so $R/kanter_core_amd/libkanter_core_amd.so

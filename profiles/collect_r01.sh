@@ -8,11 +8,11 @@ R=$GRAFT_REPO_ROOT
 OUT=$R/gpurun_out/r01
 mkdir -p $OUT
 cd $R
-python bench.py > $OUT/r01_bench_default.json 2> $OUT/bench_default.err
-python bench.py --workload mix1 --no-cpu-baseline --no-extras > $OUT/r01_bench_mix1.json 2>/dev/null
-python bench.py --workload resize_blend --no-cpu-baseline --no-extras > $OUT/r01_bench_resize_blend.json 2>/dev/null
-python bench.py --workload chain32 --size 8192 --steps 50 --no-cpu-baseline --no-extras > $OUT/r01_bench_chain32_8192.json 2>/dev/null
-python bench.py --workload fanin --steps 20 --warmup 3 --no-cpu-baseline --no-extras > $OUT/r01_bench_fanin.json 2>/dev/null
+python bench.py --full > $OUT/r01_bench_default.json 2> $OUT/bench_default.err
+python bench.py --full --workload mix1 --no-cpu-baseline --no-extras > $OUT/r01_bench_mix1.json 2>/dev/null
+python bench.py --full --workload resize_blend --no-cpu-baseline --no-extras > $OUT/r01_bench_resize_blend.json 2>/dev/null
+python bench.py --full --workload chain32 --size 8192 --steps 50 --no-cpu-baseline --no-extras > $OUT/r01_bench_chain32_8192.json 2>/dev/null
+python bench.py --full --workload fanin --steps 20 --warmup 3 --no-cpu-baseline --no-extras > $OUT/r01_bench_fanin.json 2>/dev/null
 python profiles/kernel_microbench.py --reps 50 > $OUT/r01_kernel_microbench.json 2>/dev/null
 cd /tmp && export TMPDIR=/tmp
 for w in chain32 resize_blend; do

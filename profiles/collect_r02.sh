@@ -8,14 +8,14 @@ R=$GRAFT_REPO_ROOT
 OUT=$R/gpurun_out/r02
 mkdir -p $OUT
 cd $R
-python bench.py > $OUT/r02_bench_default.json 2> $OUT/bench_default.err
+python bench.py --full > $OUT/r02_bench_default.json 2> $OUT/bench_default.err
 echo "default done"
-python bench.py --workload mix1 > $OUT/r02_bench_mix1.json 2>/dev/null
-python bench.py --workload resize_blend > $OUT/r02_bench_resize_blend.json 2>/dev/null
-python bench.py --workload fanin --steps 50 --warmup 5 > $OUT/r02_bench_fanin.json 2>/dev/null
-python bench.py --workload chain32 --size 8192 --steps 50 --no-cpu-baseline --no-extras > $OUT/r02_bench_chain32_8192.json 2>/dev/null
-python bench.py --workload chain32_rows --size 8192 --steps 50 --no-cpu-baseline > $OUT/r02_bench_chain32_rows_8192.json 2>/dev/null
-python bench.py --size 256 --steps 2000 --warmup 50 --no-cpu-baseline --no-extras > $OUT/r02_bench_chain32_256.json 2>/dev/null
+python bench.py --full --workload mix1 > $OUT/r02_bench_mix1.json 2>/dev/null
+python bench.py --full --workload resize_blend > $OUT/r02_bench_resize_blend.json 2>/dev/null
+python bench.py --full --workload fanin --steps 50 --warmup 5 > $OUT/r02_bench_fanin.json 2>/dev/null
+python bench.py --full --workload chain32 --size 8192 --steps 50 --no-cpu-baseline --no-extras > $OUT/r02_bench_chain32_8192.json 2>/dev/null
+python bench.py --full --workload chain32_rows --size 8192 --steps 50 --no-cpu-baseline > $OUT/r02_bench_chain32_rows_8192.json 2>/dev/null
+python bench.py --full --size 256 --steps 2000 --warmup 50 --no-cpu-baseline --no-extras > $OUT/r02_bench_chain32_256.json 2>/dev/null
 echo "benches done"
 python profiles/kernel_microbench.py --reps 50 > $OUT/r02_kernel_microbench.json 2>/dev/null
 cd /tmp && export TMPDIR=/tmp

@@ -10,21 +10,21 @@ R=$GRAFT_REPO_ROOT
 OUT=$R/gpurun_out/r04
 mkdir -p $OUT
 cd $R
-python bench.py > $OUT/r04_bench_default.json 2> $OUT/bench_default.err
+python bench.py --full > $OUT/r04_bench_default.json 2> $OUT/bench_default.err
 echo "default done"
-python bench.py --workload mix1 > $OUT/r04_bench_mix1.json 2>/dev/null
-python bench.py --workload resize_blend > $OUT/r04_bench_resize_blend.json 2>/dev/null
-python bench.py --workload fanin --steps 50 --warmup 5 > $OUT/r04_bench_fanin.json 2>/dev/null
-python bench.py --workload e2e --steps 100 --warmup 6 > $OUT/r04_bench_e2e.json 2>/dev/null
-python bench.py --workload chain32 --size 8192 --steps 50 --no-cpu-baseline --no-extras > $OUT/r04_bench_chain32_8192.json 2>/dev/null
-python bench.py --gpus 1 --workload chain32_rows --size 8192 --steps 50 > $OUT/r04_bench_chain32_rows_8192.json 2>/dev/null
-python bench.py --size 256 --steps 2000 --warmup 50 --no-cpu-baseline --no-extras > $OUT/r04_bench_chain32_256.json 2>/dev/null
-python bench.py --size 1024 --steps 1000 --warmup 50 --no-cpu-baseline --no-extras > $OUT/r04_bench_chain32_1024.json 2>/dev/null
-for s in 256 1024; do python bench.py --workload fanin --size $s --steps 300 --warmup 20 --no-cpu-baseline > $OUT/r04_bench_fanin_$s.json 2>/dev/null; done
+python bench.py --full --workload mix1 > $OUT/r04_bench_mix1.json 2>/dev/null
+python bench.py --full --workload resize_blend > $OUT/r04_bench_resize_blend.json 2>/dev/null
+python bench.py --full --workload fanin --steps 50 --warmup 5 > $OUT/r04_bench_fanin.json 2>/dev/null
+python bench.py --full --workload e2e --steps 100 --warmup 6 > $OUT/r04_bench_e2e.json 2>/dev/null
+python bench.py --full --workload chain32 --size 8192 --steps 50 --no-cpu-baseline --no-extras > $OUT/r04_bench_chain32_8192.json 2>/dev/null
+python bench.py --full --gpus 1 --workload chain32_rows --size 8192 --steps 50 > $OUT/r04_bench_chain32_rows_8192.json 2>/dev/null
+python bench.py --full --size 256 --steps 2000 --warmup 50 --no-cpu-baseline --no-extras > $OUT/r04_bench_chain32_256.json 2>/dev/null
+python bench.py --full --size 1024 --steps 1000 --warmup 50 --no-cpu-baseline --no-extras > $OUT/r04_bench_chain32_1024.json 2>/dev/null
+for s in 256 1024; do python bench.py --full --workload fanin --size $s --steps 300 --warmup 20 --no-cpu-baseline > $OUT/r04_bench_fanin_$s.json 2>/dev/null; done
 # a process that has to compile (empty cache, no packaged kernels): what the first sightings cost, what the driver would have seen
 d=$(mktemp -d); mv $R/kanter_core_amd/kernel_cache $d/packaged
-KC_KERNEL_CACHE_DIR=$d/user python bench.py --no-cpu-baseline --no-extras > $OUT/r04_bench_default_empty_cache.json 2>/dev/null
-KC_KERNEL_CACHE_DIR=$d/user python bench.py --no-cpu-baseline --no-extras > $OUT/r04_bench_default_second_process.json 2>/dev/null
+KC_KERNEL_CACHE_DIR=$d/user python bench.py --full --no-cpu-baseline --no-extras > $OUT/r04_bench_default_empty_cache.json 2>/dev/null
+KC_KERNEL_CACHE_DIR=$d/user python bench.py --full --no-cpu-baseline --no-extras > $OUT/r04_bench_default_second_process.json 2>/dev/null
 mv $d/packaged $R/kanter_core_amd/kernel_cache; rm -rf $d
 echo "benches done"
 cd /tmp && export TMPDIR=/tmp

@@ -12,7 +12,7 @@ for setting in "$@"; do
   i=$((i+1))
   echo "== setting $i: '$setting'"
   ( [ -n "$setting" ] && export $setting
-    python3 $R/bench.py --workload resize_blend --steps 200 --warmup 20 --no-cpu-baseline 2>/dev/null | python3 -c "
+    python3 $R/bench.py --full --workload resize_blend --steps 200 --warmup 20 --no-cpu-baseline 2>/dev/null | python3 -c "
 import json,sys
 d=json.loads(sys.stdin.readlines()[-1]); r=d['roofline']
 print('events: kernel_us=%.2f frac=%.3f median=%.2f min=%.2f parity=%s spec=%s' % (r['kernel_us'], r['frac'], r['step_us_median'], r['step_us_min'], d.get('parity'), r.get('specialized_kernel')))"

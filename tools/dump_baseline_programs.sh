@@ -11,7 +11,7 @@ rm -f "$out"
 export KC_KERNEL_CACHE_MANIFEST="$PWD/$out"
 run() {
     d=$(mktemp -d)
-    KC_KERNEL_CACHE_DIR="$d" python bench.py --steps 6 --warmup 4 --no-cpu-baseline "$@" > /dev/null
+    KC_KERNEL_CACHE_DIR="$d" python bench.py --full --steps 6 --warmup 4 --no-cpu-baseline "$@" > /dev/null
     rm -rf "$d"
 }
 run                                               # the headline (its cold rotation and the PCIe leg included)
