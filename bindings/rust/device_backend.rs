@@ -105,6 +105,15 @@ impl SlotImage {
     }
     pub fn to_u8(&self) -> Result<Vec<u8>> { self.to_u8_impl(false) }
     pub fn to_u8_srgb(&self) -> Result<Vec<u8>> { self.to_u8_impl(true) }
+    /// Per-channel min / max / NaN count, and with `histogram` the bins to_u8 (`srgb`: to_u8_srgb) writes, computed on the
+    /// device (kc_image_channel_stats); only the first `channels` entries of each array describe the image.
+    pub fn channel_stats(&self, histogram: bool, srgb: bool) -> Result<Box<KcChannelStats>> {
+        let flags = if histogram { KC_STATS_HISTOGRAM } else { 0 } | if srgb { KC_STATS_SRGB } else { 0 };
+        // about 8 KiB: on the heap; every field is plain data, so all-zero bytes are a valid value
+        let mut out: Box<KcChannelStats> = Box::new(unsafe { std::mem::zeroed() });
+        check(unsafe { kc_image_channel_stats(self.raw(), flags, &mut *out) })?;
+        Ok(out)
+    }
 }
 
 /// src/shared.rs:218-261 (decode with the `image` crate as before, then hand the u8 samples over).

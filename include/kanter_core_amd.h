@@ -349,6 +349,38 @@ typedef struct kc_device_image {
 KC_API int kc_device_image_validate(const kc_device_image *d, size_t *extent_bytes);
 KC_API int kc_image_from_device(const kc_device_image *src, uint32_t flags, void *hip_stream, kc_image **out);
 KC_API int kc_image_to_device(kc_image *img, const kc_device_image *dst, uint32_t flags, void *hip_stream);
+/* Per-channel statistics of an image, computed on the device: the value range and NaN count of every channel and, on request,
+ * the histogram of the 8-bit export -- without downloading the pixels (an editor's levels view, a range check before a u8
+ * export).  Not a node: a query like kc_image_to_device.
+ *   min / max     over the channel's non-NaN pixels in the total order of the floats: -0.0 < +0.0, infinities included,
+ *                 denormals as they are (compared through the key k = bits >> 31 ? ~bits : bits | 0x80000000, not fminf);
+ *                 NaN when the channel has no such pixel, and for channels >= `channels`.
+ *   nan_count     the channel's NaN pixels (any payload, either sign); 0 for channels >= `channels`.
+ *   histogram     with KC_STATS_HISTOGRAM: histogram[c][b] = the pixels that kc_image_to_u8 writes as b in channel c (the
+ *                 same quantiser functions); with KC_STATS_SRGB as well, as kc_image_to_u8 with srgb = 1 writes them: R, G, B of
+ *                 an RGBA image and the channel of a Gray image through to_u8_srgb, alpha linear.  Only the first `channels`
+ *                 rows are filled; all zero without the flag.
+ * `channels` is the image's own (1 Gray, 4 RGBA), not to_u8's (v, v, v, 1).  Bytes of a plane's rows past `width` (the
+ * padding kc_plane_wrap allows) are never read as pixels.  Errors: NULL img / lg / out KC_ERR_INVALID_ARG; flag bits other
+ * than the two KC_ERR_UNSUPPORTED; KC_STATS_SRGB without KC_STATS_HISTOGRAM KC_ERR_INVALID_ARG; then KC_ERR_NO_DEVICE before
+ * kc_init.  kc_live_graph_buffer_channel_stats returns KC_ERR_NO_SLOT_DATA where kc_live_graph_buffer_device does.  `*out` is
+ * written on KC_OK only.
+ * The call runs after the work already enqueued on the library's stream and blocks until the host values are there (an event of
+ * its own; other streams are not waited for).  A pending chain or resample is run first.  A constant channel is answered on the
+ * host; the distinct resident planes are read once, by one launch plus a small combining launch (kc_stats: two launches,
+ * width * height * 4 algorithmic bytes per plane read); an image of constant channels launches nothing. */
+#define KC_STATS_HISTOGRAM 1u /* also fill histogram[][] */
+#define KC_STATS_SRGB 2u      /* histogram bins as to_u8_srgb assigns them (R, G, B; alpha linear); needs KC_STATS_HISTOGRAM */
+typedef struct kc_channel_stats {
+    uint32_t channels;          /* 1: Gray, 4: Rgba -- the image's own channels, not to_u8's (v, v, v, 1) */
+    uint32_t flags;             /* the flags the call was given */
+    uint64_t pixels;            /* width * height */
+    float min[4], max[4];       /* over the non-NaN pixels; NaN when a channel has none; NaN for channels >= `channels` */
+    uint64_t nan_count[4];
+    uint64_t histogram[4][256]; /* KC_STATS_HISTOGRAM: histogram[c][b] = #pixels that kc_image_to_u8 (or _srgb) writes as b in
+                                   channel c; all zero without the flag */
+} kc_channel_stats;
+KC_API int kc_image_channel_stats(kc_image *img, uint32_t flags, kc_channel_stats *out);
 /* read_slot_image, src/shared.rs:218-261 (PNG only; decode on host, planes built on device). */
 KC_API int kc_image_read_png(const char *path, kc_image **out);
 KC_API int kc_image_write_png(kc_image *img, const char *path);        /* src/node/write.rs:5-21 */
@@ -447,6 +479,9 @@ KC_API int kc_live_graph_buffer_rgba(kc_live_graph *lg, uint32_t node_id, uint32
 /* buffer_rgba into device memory in any kc_device_image form (see kc_image_to_device) */
 KC_API int kc_live_graph_buffer_device(kc_live_graph *lg, uint32_t node_id, uint32_t slot_id, const kc_device_image *dst, uint32_t flags,
                                        void *hip_stream);
+/* kc_image_channel_stats of a slot's image */
+KC_API int kc_live_graph_buffer_channel_stats(kc_live_graph *lg, uint32_t node_id, uint32_t slot_id, uint32_t flags,
+                                              kc_channel_stats *out);
 KC_API int kc_live_graph_embed_slot_data_with_id(kc_live_graph *lg, kc_image *image, uint32_t slot_id, uint32_t embed_id); /* :324-341 */
 KC_API int kc_live_graph_add_input_slot_data(kc_live_graph *lg, uint32_t node_id, uint32_t slot_id, kc_image *image);     /* :347-350 */
 KC_API int kc_live_graph_changed_consume(kc_live_graph *lg, uint32_t *ids, uint32_t cap, uint32_t *count);               /* :156-160 */

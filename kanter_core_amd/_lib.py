@@ -52,6 +52,11 @@ class kc_device_image(C.Structure):
                 ("layout", C.c_int32), ("row_pitch_bytes", C.c_size_t), ("channel_pitch_bytes", C.c_size_t)]
 
 
+class kc_channel_stats(C.Structure):
+    _fields_ = [("channels", C.c_uint32), ("flags", C.c_uint32), ("pixels", C.c_uint64), ("min", C.c_float * 4), ("max", C.c_float * 4),
+                ("nan_count", C.c_uint64 * 4), ("histogram", (C.c_uint64 * 256) * 4)]
+
+
 # name -> (restype, argtypes); every symbol include/kanter_core_amd.h declares.
 SIGNATURES = {
     "kc_init": (C.c_int, [C.c_int]),
@@ -142,6 +147,7 @@ SIGNATURES = {
     "kc_device_image_validate": (C.c_int, [C.POINTER(kc_device_image), C.POINTER(C.c_size_t)]),
     "kc_image_from_device": (C.c_int, [C.POINTER(kc_device_image), C.c_uint32, c_vp, C.POINTER(c_vp)]),
     "kc_image_to_device": (C.c_int, [c_vp, C.POINTER(kc_device_image), C.c_uint32, c_vp]),
+    "kc_image_channel_stats": (C.c_int, [c_vp, C.c_uint32, C.POINTER(kc_channel_stats)]),
     "kc_image_from_f32": (C.c_int, [C.POINTER(c_vp), C.c_int, C.c_uint32, C.c_uint32, C.POINTER(c_vp)]),
     "kc_image_to_f32": (C.c_int, [c_vp, C.POINTER(c_vp), C.c_int]),
     "kc_image_read_png": (C.c_int, [C.c_char_p, C.POINTER(c_vp)]),
@@ -205,6 +211,7 @@ SIGNATURES = {
     "kc_live_graph_node_slot_ids": (C.c_int, [c_vp, C.c_uint32, c_u32p, C.c_uint32, c_u32p]),
     "kc_live_graph_buffer_rgba": (C.c_int, [c_vp, C.c_uint32, C.c_uint32, C.c_int, c_vp]),
     "kc_live_graph_buffer_device": (C.c_int, [c_vp, C.c_uint32, C.c_uint32, C.POINTER(kc_device_image), C.c_uint32, c_vp]),
+    "kc_live_graph_buffer_channel_stats": (C.c_int, [c_vp, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(kc_channel_stats)]),
     "kc_live_graph_embed_slot_data_with_id": (C.c_int, [c_vp, c_vp, C.c_uint32, C.c_uint32]),
     "kc_live_graph_add_input_slot_data": (C.c_int, [c_vp, C.c_uint32, C.c_uint32, c_vp]),
     "kc_live_graph_changed_consume": (C.c_int, [c_vp, c_u32p, C.c_uint32, c_u32p]),

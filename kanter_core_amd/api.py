@@ -12,6 +12,7 @@ handles around.
     SlotImage / SlotData / Size   src/slot_image.rs, src/slot_data.rs
     TexProError        src/error.rs:5-27
 """
+import collections
 import ctypes as C
 import os
 
@@ -622,6 +623,26 @@ def _device_export(call, size, dtype, layout, channels, srgb, out):
     return out
 
 
+STATS_HISTOGRAM = 1  # kc_image_channel_stats: also the u8 histograms
+STATS_SRGB = 2       # ... binned as to_u8_srgb (R, G, B; alpha linear)
+
+ChannelStats = collections.namedtuple("ChannelStats", "min max nan_count pixels histogram")
+ChannelStats.__doc__ = """Per-channel statistics (kc_image_channel_stats), one entry per channel of the image (1 Gray, 4 RGBA):
+min / max float32 over the non-NaN pixels (NaN where a channel has none), nan_count uint64, pixels = width * height, histogram
+uint64 (channels, 256) -- the pixels kc_image_to_u8 writes as each byte -- or None."""
+
+
+def _channel_stats(call, histogram, srgb):
+    if srgb and not histogram:
+        raise ValueError("srgb bins need histogram=True")
+    r = _lib.kc_channel_stats()
+    _check(call((STATS_HISTOGRAM if histogram else 0) | (STATS_SRGB if srgb else 0), C.byref(r)))
+    n = r.channels
+    hist = np.ctypeslib.as_array(r.histogram)[:n].astype(np.uint64) if histogram else None
+    return ChannelStats(np.array(r.min[:n], np.float32), np.array(r.max[:n], np.float32), np.array(r.nan_count[:n], np.uint64),
+                        int(r.pixels), hist)
+
+
 # ------------------------------------------------------------------ SlotImage / SlotData
 class SlotImage:
     """SlotImage (src/slot_image.rs:15-264) backed by device planes."""
@@ -715,6 +736,11 @@ class SlotImage:
         tensor) is written instead of a new tensor; its dtype and shape then decide.  Ready on torch's current stream."""
         return _device_export(lambda d, f, s: _lib.load().kc_image_to_device(self._h, d, f, s), self.size(), dtype, layout, channels,
                               srgb, out)
+
+    def channel_stats(self, histogram=False, srgb=False):
+        """-> ChannelStats of the image, computed on the device (kc_image_channel_stats): the range and NaN count of every
+        channel, with histogram=True the u8 bins to_u8 writes (srgb=True: to_u8_srgb's).  Blocks until the values are there."""
+        return _channel_stats(lambda f, out: _lib.load().kc_image_channel_stats(self._h, f, out), histogram, srgb)
 
     def planes(self):
         """Downloads the f32 planes: list of (h, w) arrays (1 or 4)."""
@@ -1061,6 +1087,11 @@ class LiveGraph:
         """buffer_rgba into a tensor in device memory (kc_live_graph_buffer_device); arguments as SlotImage.to_torch."""
         return _device_export(lambda d, f, s: _lib.load().kc_live_graph_buffer_device(self._h, node_id, slot_id, d, f, s),
                               self.slot_data_size(node_id, slot_id), dtype, layout, channels, srgb, out)
+
+    def buffer_channel_stats(self, node_id, slot_id, histogram=False, srgb=False):
+        """SlotImage.channel_stats of a slot's image (kc_live_graph_buffer_channel_stats)."""
+        return _channel_stats(lambda f, out: _lib.load().kc_live_graph_buffer_channel_stats(self._h, node_id, slot_id, f, out),
+                              histogram, srgb)
 
     @staticmethod
     def try_buffer_rgba(live_graph, node_id, slot_id, srgb=False):

@@ -173,6 +173,7 @@ try {
         us = Context::UploadSlot{};
     }
     c.upload_next = 0;
+    channel_stats_release();
     for (auto &kv : c.taps) (void)hipFree(kv.second.dev_block);
     c.taps.clear();
     for (auto &kv : c.band_taps) (void)hipFree(kv.second.dev_block);
@@ -736,6 +737,14 @@ try {
     Lock api_lock(ctx().mu);  // reference counts are plain integers, see kc_plane::refs
     KC_ARG(img && dst);
     return image_to_device(img, dst, flags, hip_stream);
+}
+KC_CATCH
+
+int kc_image_channel_stats(kc_image *img, uint32_t flags, kc_channel_stats *out)
+try {
+    Lock api_lock(ctx().mu);  // reference counts are plain integers, see kc_plane::refs
+    KC_ARG(img && out);
+    return image_channel_stats(img, flags, out);  // the flags, then need_init()
 }
 KC_CATCH
 
@@ -1378,6 +1387,16 @@ try {
     const SlotData *sd = lg->find_slot(node, slot);
     if (!sd) return KC_ERR_NO_SLOT_DATA;
     return image_to_device(sd->image, dst, flags, hip_stream);
+}
+KC_CATCH
+
+int kc_live_graph_buffer_channel_stats(kc_live_graph *lg, uint32_t node, uint32_t slot, uint32_t flags, kc_channel_stats *out)
+try {
+    LG_LOCK(lg);
+    KC_ARG(out);
+    const SlotData *sd = lg->find_slot(node, slot);
+    if (!sd) return KC_ERR_NO_SLOT_DATA;
+    return image_channel_stats(sd->image, flags, out);
 }
 KC_CATCH
 

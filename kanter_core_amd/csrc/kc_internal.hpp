@@ -222,6 +222,21 @@ hipError_t launch_image_import(int dtype, const DevImageArgs &a, float *const pl
 // image_export_kernel: channel c of the output is op[c]; gray != 0: op[0] stands for R, G and B (read once); nt_mask bits 0-7:
 // nontemporal plane loads; srgb: U8 only
 hipError_t launch_image_export(int dtype, int srgb, const Operand op[4], int gray, const DevImageArgs &a, uint32_t nt_mask, hipStream_t s);
+// Per-channel statistics (stats.hip / stats.cpp): the n distinct resident planes ("slots") of one image.  Bit s of srgb: slot
+// s bins with the sRGB quantiser.  partials: one record of rec_words u32 per workgroup (stats.hip has the layout); result:
+// rec_words u64, initialised by the launch itself.
+struct StatsArgs {
+    const float *ptr[4];
+    uint32_t pitch[4];  // floats
+    uint32_t w, h, n, srgb;
+    uint32_t *partials;
+    uint32_t rec_words;
+    unsigned long long *result;
+};
+// channel_stats_kernel<nt, hist, srgb> on `groups` workgroups, then channel_stats_combine_kernel: two launches
+hipError_t launch_channel_stats(const StatsArgs &a, bool hist, bool srgb, bool nt, uint32_t groups, hipStream_t s);
+// workgroups of that launch for a w x h image on a device of `cus` CUs (>= 1)
+uint32_t channel_stats_groups(uint32_t w, uint32_t h, bool hist, bool srgb, uint32_t cus);
 hipError_t launch_from_u8(const uint8_t *src, int channels, uint32_t w, uint32_t h, float *const planes[4],
                           uint32_t pitch, uint32_t nt_mask, hipStream_t s);
 

@@ -246,6 +246,16 @@ struct Context {
     static constexpr size_t kUploadSlotMax = (size_t)4 << 20;  // larger images keep the synchronous path
     UploadSlot upload_ring[kUploadSlots];
     int upload_next = 0;
+    // kc_image_channel_stats (stats.cpp): the workgroups' partial records and the result on the device, the result's pinned
+    // host copy and the event the call waits on -- allocated on first use, the partials grown when needed, freed at kc_shutdown
+    struct StatsBuffers {
+        void *partials = nullptr;
+        size_t partials_bytes = 0;
+        unsigned long long *result = nullptr, *host = nullptr;
+        hipEvent_t done = nullptr;
+        uint32_t cus = 0;
+    };
+    StatsBuffers stats;
 };
 
 // RAII scope for the resize memo (nested Graph nodes share the outermost scope).
@@ -329,6 +339,9 @@ int image_to_u8(kc_image *img, bool srgb, uint8_t *host);
 int device_image_validate(const kc_device_image *d, size_t *extent_bytes);
 int image_from_device(const kc_device_image *src, uint32_t flags, void *hip_stream, kc_image **out);
 int image_to_device(kc_image *img, const kc_device_image *dst, uint32_t flags, void *hip_stream);
+// per-channel statistics (stats.cpp): the body of kc_image_channel_stats; the context's buffers, released at kc_shutdown
+int image_channel_stats(kc_image *img, uint32_t flags, kc_channel_stats *out);
+void channel_stats_release();
 int calculate_size(int policy, const kc_size *sizes, int n, int slot_index, kc_size specific, kc_size *out);
 int mix_process(kc_image *left, kc_image *right, int mix_type, kc_image **out);
 int separate_process(kc_image *in, kc_image *out[4]);
