@@ -248,61 +248,18 @@ __global__ __launch_bounds__(256) void resize_down2_kernel(const ResizePlanes P,
     }
 }
 
-hipError_t launch_resize_down2(const ResizePlanes &p, int batch, const Down2Args &a, hipStream_t s, ResizeVariant *var)
+hipError_t launch_resize_down2(const ResizePlan &r, const ResizePlanes &p, const Down2Args &a, hipStream_t s)
 {
     if (a.dw == 0 || a.dh == 0) return hipSuccess;
-    if (batch < 1 || batch > 4) return hipErrorInvalidValue;
+    if (r.planes < 1 || r.planes > 4) return hipErrorInvalidValue;
     const uint32_t nw4 = a.hstride / 4u;
     if (a.hstride % 4u != 0 || nw4 < 1 || nw4 > 8 || a.nc < 1 || a.nc > KC_DOWN2_MAX_CHUNKS || a.tile_w == 0 || !a.strips)
         return hipErrorInvalidValue;
-    const uint32_t hc = down2_cols_per_lane(nw4);
-    if (a.tile_w > 64u * hc) return hipErrorInvalidValue;
-    dim3 grid((a.dw + a.tile_w - 1) / a.tile_w, (a.dh + 15u) / 16u, batch);
-    Down2Args a2 = a;
-    a2.by_rows = 0;
-    // KC_DOWN2_XCD=0 / 1: never / always (A/B); default: when the planes fit the Infinity Cache (a.xcd_per as the caller's hint).
-    // Measured (profiles/r03_down2_xcd.txt): one 4096^2 plane 27.9 -> 26.2 us, 3000^2 -> 700^2 17.9 -> 15.4; four 4096^2 planes
-    // (268 MB of source, past the cache) 114.6 -> 122.7: there the plain order, whole rows at a time, is kinder to HBM.
-    const int xcd_opt = options().down2_xcd;
-    const bool xcd = xcd_opt < 0 ? a.xcd_per != 0 : xcd_opt != 0;
-    a2.xcd_per = 0;
-    // Four strips of one row group per workgroup and the jobs dealt to the XCDs in eighths row by row (what resize_poly_kernel
-    // gained 8 - 20 % from): here it pays where the row groups' windows span several chunks (ratios from about 1.6: CatmullRom
-    // 4096^2 -> 1365^2 21.3 -> 19.3 us, RGBA 74.3 -> 63.9; Gaussian 3000^2 -> 700^2 14.6 -> 12.5, RGBA 52.4 -> 41.4; Lanczos3 2:1
-    // 24.8 -> 23.4) and costs 5 - 10 % on RGBA launches of single-chunk ratios (4096^2 -> 3000^2 111.5 -> 122.4), which keep the
-    // order above (profiles/r04_down2_by_rows.txt).
-    if (a.by_rows && grid.x >= 2) {  // (the caller's choice: resize.cpp, kc_set_option("down2_by_rows"); one strip: nothing to order,
-                                     // and the reciprocal of 1 does not fit 32 bits)
-        const uint32_t gx = grid.x, groups = (a.dh + 3u) / 4u;
-        const uint64_t jobs = (uint64_t)gx * groups, magic = ((1ull << 32) + gx - 1) / gx;
-        if (jobs < (1u << 24) && jobs * (magic * gx - (1ull << 32)) < (1ull << 32)) {
-            a2.by_rows = 1u;
-            a2.n_tiles = (uint32_t)jobs;
-            a2.gy = gx;
-            a2.gy_magic = (uint32_t)magic;
-            a2.xcd_per = (uint32_t)(((jobs + 3u) / 4u + 7u) / 8u);
-            grid = dim3(8u * a2.xcd_per, 1, batch);
-        }
-    } else
-    if (xcd && grid.y >= 2) {
-        const uint64_t n = (uint64_t)grid.x * grid.y, magic = ((1ull << 32) + grid.y - 1) / grid.y;
-        // tile / gy == (tile * magic) >> 32 for every tile < n when n * (magic * gy - 2^32) < 2^32
-        if (n < (1u << 24) && n * (magic * grid.y - (1ull << 32)) < (1ull << 32)) {
-            a2.n_tiles = (uint32_t)n;
-            a2.gy = grid.y;
-            a2.gy_magic = (uint32_t)magic;
-            a2.xcd_per = (uint32_t)((n + 7) / 8);
-            grid = dim3(8u * a2.xcd_per, 1, batch);
-        }
-    }
-    if (var) {
-        var->xcd = a2.xcd_per != 0 && !a2.by_rows;
-        var->by_rows = a2.by_rows != 0;
-    }
+    if (a.tile_w > 64u * down2_cols_per_lane(nw4)) return hipErrorInvalidValue;
 #define KC_D2(HC, NW4)                                                                     \
     do {                                                                                   \
-        if (a.nc == 1) resize_down2_kernel<HC, NW4, 0><<<grid, 256, 0, s>>>(p, a2);        \
-        else resize_down2_kernel<HC, NW4, 1><<<grid, 256, 0, s>>>(p, a2);                  \
+        if (a.nc == 1) resize_down2_kernel<HC, NW4, 0><<<r.grid, 256, 0, s>>>(p, a);       \
+        else resize_down2_kernel<HC, NW4, 1><<<r.grid, 256, 0, s>>>(p, a);                 \
     } while (0)
     switch (nw4) {
     case 1: KC_D2(3, 1); break;

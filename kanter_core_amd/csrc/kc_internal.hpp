@@ -107,21 +107,13 @@ struct ResizePlanes {
 //   strips   per strip of tile_w output columns: its first source column rounded down to a multiple of 4, and the width of its
 //            source window in column quads (<= 64: one per lane of the vertical pass)
 constexpr uint32_t KC_DOWN2_REC = 72, KC_DOWN2_MAX_CHUNKS = 4, KC_DOWN2_SLOTS = 256 + 32;
-// What a resize launcher chose from the launch size and its overrides, as it launched it (resize.cpp counts it: kc_stats_counter)
-struct ResizeVariant {
-    uint32_t rows = 0;     // band height (resize_poly_kernel, resize_poly2_kernel)
-    bool xcd = false;      // jobs dealt to the XCDs in eighths (resize_poly2_kernel, resize_down2_kernel)
-    bool by_rows = false;  // resize_down2_kernel: four strips of one row group per workgroup
-    bool wide = false;     // launch_resize_lds: resize_wide_kernel
-};
 struct Down2Args {
     const uint32_t *vrec;
     const uint32_t *hleft, *hcount, *strips;
     const float *hw;
     uint32_t nc, hstride;
     uint32_t tile_w, dw, dh;
-    // XCD-aware tile order (down2.hip).  The caller sets xcd_per != 0 to ask for it; the launcher fills in the rest (or clears
-    // xcd_per: plain 2-D grid).
+    // XCD-aware tile order (down2.hip): xcd_per != 0 makes the grid one-dimensional (xcd_per = 0: plain 2-D grid)
     uint32_t xcd_per, n_tiles, gy, gy_magic;
     // by_rows != 0: a workgroup's four waves are four neighbouring STRIPS of one row group and XCD k works through the k-th eighth
     // of the jobs row by row (xcd_per workgroups each; gy / gy_magic then divide by the number of strips): see resize_poly_kernel
@@ -129,11 +121,6 @@ struct Down2Args {
 };
 // output columns per lane of the horizontal pass: its weights live in registers (at most 9 quads per lane)
 inline uint32_t down2_cols_per_lane(uint32_t weight_quads) { return weight_quads <= 3 ? 3u : weight_quads == 4 ? 2u : 1u; }
-hipError_t launch_resize_down2(const ResizePlanes &p, int batch, const Down2Args &a, hipStream_t s, ResizeVariant *var);
-hipError_t launch_resize_lds(const ResizePlanes &p, int batch, uint32_t dw, uint32_t dh, TapsDev v, TapsDev h,
-                             uint32_t h_min_count, uint32_t tile_w, uint32_t tile_h, uint32_t ncp, hipStream_t s, ResizeVariant *var);
-hipError_t launch_resize_down(const ResizePlanes &p, int batch, uint32_t dw, uint32_t dh, TapsDev v, TapsDev h, uint32_t tile_w,
-                              uint32_t tile_h, uint32_t ncp, hipStream_t s);
 // Tiles in XCD order (as resize_down2_kernel's): with per != 0 the grid is one-dimensional, workgroup id % 8 is the XCD and XCD k
 // works through the k-th eighth of the gx x gy tiles in column-major order (tile = (id % 8) * per + id / 8; x = tile / gy), so
 // that vertically adjacent tiles, which share source rows, meet in one L2.
@@ -153,15 +140,66 @@ inline XcdOrder xcd_order(uint32_t gx, uint32_t gy, bool want)
     o.magic = (uint32_t)magic;
     return o;
 }
-hipError_t launch_resize_poly(const ResizePlanes &p, int batch, uint32_t dw, uint32_t dh, TapsDev v, TapsDev h, uint32_t tile_w,
-                              uint32_t ncp, uint32_t reg_a, uint32_t reg_b, uint32_t ages, uint32_t ratio, hipStream_t s, ResizeVariant *var);
+// LDS floats of one band wave of resize_poly_kernel (kernels.hip, resize_down_stage_wave)
+inline uint32_t resize_down_wave_floats(uint32_t tile_w, uint32_t hstride) { return (4u * KC_DOWN_ROW_FLOATS + 2u * tile_w + tile_w * (hstride | 1u) + 3u) / 4u * 4u; }
+// resize_poly_kernel's jobs (kernels.hip)
+struct PolyBands {
+    uint32_t ya, yb;    // regular rows handled as bands: [ya, yb), yb - ya a multiple of 4
+    uint32_t rows;      // rows per band (a multiple of 4; the last band may be shorter)
+    uint32_t n_bands;
+    uint32_t ty0[4], th[4];  // general tiles: first row, rows (<= 16)
+    // A workgroup's four waves are four neighbouring STRIPS of one band (each with its taps staged by itself); the grid is
+    // one-dimensional and XCD k (workgroup id % 8) works through the k-th eighth of the band workgroups band by band; the
+    // border tiles follow.  n_sq strip quads per band, n_band_wgs = n_bands * n_sq, xper = ceil(n_band_wgs / 8), gx strips,
+    // wave_floats of LDS per wave.
+    uint32_t n_sq, n_band_wgs, xper, gx, wave_floats;
+};
+// resize_poly2_kernel's jobs (kernels.hip)
+struct Poly2Bands {
+    uint32_t ya, yb, rows, n_bands;
+    uint32_t tw, n_strips;     // band path: output columns per strip (its source window is at most 256 columns), strips per row
+    uint32_t n_wgx;            // workgroups per band (two strips each)
+    uint32_t n_band_wgs;       // n_wgx * n_bands; the general tiles follow
+    uint32_t gen_tw, gen_gx, gen_ncp;  // general tiles: resize_down_kernel's strip width, strips per row, padded window
+    uint32_t n_gen;
+    uint32_t ty0[6], th[6];
+};
+#define KC_POLY2_RING_PITCH 265u  // 256 columns + one pad per 32, odd
+
+// How one resample runs, as plan_resample (resize.cpp) decides it on the host from the two tap tables, the sizes and the
+// options: the form, and everything its launcher needs besides the planes (or the chain program), the tables' device pointers
+// and the stream.
+// Form X runs X_kernel or resize_X_kernel; none: a fused request that is not eligible (the resample runs on its own); two_pass:
+// launch_resize_vertical, then launch_resize_horizontal through an HBM intermediate, plane by plane.
+enum class ResizeForm { none, upsample, upsample_chain, resize_chain, poly2, down2, poly, down, lds, wide, two_pass };
+struct ResizePlan {
+    ResizeForm form = ResizeForm::none;
+    uint32_t sw = 0, sh = 0, dw = 0, dh = 0;   // source and result size
+    int planes = 0;                            // planes (the chain's batch) of the launch: blockIdx.z
+    uint32_t tile_w = 0, tile_h = 0, ncp = 0;  // the tiled forms' tile (poly2: the border tiles')
+    uint32_t mint = 0, maxt = 0;               // lds: resize_lds_kernel<MINT, MAXT>
+    uint32_t ages = 0, ratio = 0;              // poly, poly2: <A, RT>
+    uint32_t n_border = 0;                     // poly, poly2: border tiles the rows take (more than the bands hold: refused)
+    PolyBands poly{};
+    Poly2Bands poly2{};
+    uint32_t pair_floats = 0;  // poly2: LDS floats of a pair of waves
+    XcdOrder xcd{};            // poly2: the job order
+    Down2Args d2{};            // down2: all but the table pointers
+    UpsampleArgs up{};         // upsample, upsample_chain
+    bool nt = false;           // upsample: nontemporal stores of the results (cache_policy_mask)
+    size_t lds = 0;            // dynamic LDS bytes
+    dim3 grid{};
+};
+// The launchers of the planned forms: they check the plan and pick the kernel template, nothing else.
+hipError_t launch_resize_lds(const ResizePlan &r, const ResizePlanes &p, TapsDev v, TapsDev h, hipStream_t s);  // lds, wide
+hipError_t launch_resize_down(const ResizePlan &r, const ResizePlanes &p, TapsDev v, TapsDev h, hipStream_t s);
+hipError_t launch_resize_poly(const ResizePlan &r, const ResizePlanes &p, TapsDev v, TapsDev h, hipStream_t s);
 // The same ranges with two waves to a band's strip (8-byte lanes, a shared ring, the horizontal pass split by pixels): kernels.hip
-hipError_t launch_resize_poly2(const ResizePlanes &p, int batch, uint32_t dw, uint32_t dh, TapsDev v, TapsDev h, uint32_t tw,
-                               uint32_t gen_tw, uint32_t gen_ncp, uint32_t reg_a, uint32_t reg_b, uint32_t ages, uint32_t ratio, bool xcd,
-                               hipStream_t s, ResizeVariant *var);
+hipError_t launch_resize_poly2(const ResizePlan &r, const ResizePlanes &p, TapsDev v, TapsDev h, hipStream_t s);
+// a: the plan's d2 with the tables' pointers
+hipError_t launch_resize_down2(const ResizePlan &r, const ResizePlanes &p, const Down2Args &a, hipStream_t s);
 // Fused resample + chain: input slot n_in - 1 of the program is produced by the resampler.
-hipError_t launch_resize_chain(const ChainProgram &p, int batch, uint32_t dw, uint32_t dh, TapsDev v, TapsDev h,
-                               uint32_t tile_w, uint32_t tile_h, uint32_t ncp, hipStream_t s);
+hipError_t launch_resize_chain(const ResizePlan &r, const ChainProgram &p, TapsDev v, TapsDev h, hipStream_t s);
 // Integer-ratio up-sampling (upsample.h).  A workgroup's tile: tile_w columns x KC_UPSAMPLE_ROWS * (1024 / tile_w) rows
 // (every thread 4 columns x KC_UPSAMPLE_ROWS rows, one trip).  LDS: the tile's intermediate, then the H quad classes.
 #ifdef KC_UP_RU  // tuning builds (tools/build_variant.sh)

@@ -365,8 +365,8 @@ int chain_resize_launch(const ChainProgram &P, int batch, int mode, kc_plane *co
 // ---- run-time specialisation of the chain kernel (specialize.cpp) ----
 hipError_t launch_chain_specialized(const ChainProgram &P, int batch, hipStream_t s, bool *launched, uint32_t *nt_mask);
 // Which streams of a launch are marked nontemporal: `in_bytes` / `out_bytes` = what the launch reads from its n_resident
-// full-size input planes / writes, summed over its channels.  Returns the ChainProgram::nt_mask bits.
-uint32_t cache_policy_mask(uint64_t in_bytes, uint64_t out_bytes, uint32_t n_resident);
+// full-size input planes / writes, summed over its channels, under the options o.  Returns the ChainProgram::nt_mask bits.
+uint32_t cache_policy_mask(uint64_t in_bytes, uint64_t out_bytes, uint32_t n_resident, const Options &o = options());
 uint32_t chain_cache_policy(const uint32_t *refs, uint32_t n, uint64_t stream_bytes, uint64_t out_bytes);
 hipError_t chain_dispatch(ChainProgram &P, int batch, int mode, uint32_t w, uint32_t h, size_t out_pitch_bytes);
 hipError_t launch_upsample_chain_specialized(const ChainProgram &P, int batch, const UpsampleArgs &U, hipStream_t s, bool *launched);

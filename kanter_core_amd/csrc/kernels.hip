@@ -872,8 +872,6 @@ static __device__ __forceinline__ DownStrip resize_down_stage_wave(float *lds, c
     }
     return S;
 }
-// floats of such an area
-static inline uint32_t resize_down_wave_floats(uint32_t tile_w, uint32_t hstride) { return (4u * KC_DOWN_ROW_FLOATS + 2u * tile_w + tile_w * (hstride | 1u) + 3u) / 4u * 4u; }
 
 // Horizontal pass of four intermediate rows (row, row + row_floats, ...) for this lane's output column.
 static __device__ __forceinline__ void resize_down_hrows(const DownStrip &S, const float *row, uint32_t lane, float *dst_row,
@@ -988,18 +986,7 @@ __global__ __launch_bounds__(256) void resize_down_kernel(const ResizePlanes P, 
 // share halo columns: one L1), each with its strip's taps staged in LDS by itself, and workgroup id % 8 -- the XCD -- works
 // through the k-th eighth of the bands one whole band after the other (a band and the next one share A - 1 trips of rows: one
 // L2; every XCD streams a contiguous eighth of the plane).  The bare access pattern takes 12.9 us like this against 18.8 with
-// four bands of one strip per workgroup (profiles/tile_read_bench.hip), the kernels 8 - 20 % less.
-struct PolyBands {
-    uint32_t ya, yb;    // regular rows handled as bands: [ya, yb), yb - ya a multiple of 4
-    uint32_t rows;      // rows per band (a multiple of 4; the last band may be shorter)
-    uint32_t n_bands;
-    uint32_t ty0[4], th[4];  // general tiles: first row, rows (<= 16)
-    // A workgroup's four waves are four neighbouring STRIPS of one band (each with its taps staged by itself); the grid is
-    // one-dimensional and XCD k (workgroup id % 8) works through the k-th eighth of the band workgroups band by band; the
-    // border tiles follow.  n_sq strip quads per band, n_band_wgs = n_bands * n_sq, xper = ceil(n_band_wgs / 8), gx strips,
-    // wave_floats of LDS per wave.
-    uint32_t n_sq, n_band_wgs, xper, gx, wave_floats;
-};
+// four bands of one strip per workgroup (profiles/tile_read_bench.hip), the kernels 8 - 20 % less.  (PolyBands: kc_internal.hpp)
 
 
 template <int A, int RT>
@@ -1210,46 +1197,39 @@ static void launch_resize_lds_t(dim3 grid, size_t lds, hipStream_t s, uint32_t m
 {
 #define KC_RESIZE_LAUNCH(MAXT) \
     resize_lds_kernel<(MINT <= MAXT ? MINT : MAXT), MAXT><<<grid, 256, lds, s>>>(p, dw, dh, v, h, tile_w, tile_h, ncp)
-    if (maxt <= 1) KC_RESIZE_LAUNCH(1);
+    if (maxt == 1) KC_RESIZE_LAUNCH(1);
     else if (maxt == 2) KC_RESIZE_LAUNCH(2);
     else if (maxt == 3) KC_RESIZE_LAUNCH(3);
     else if (maxt == 4) KC_RESIZE_LAUNCH(4);
-    else if (maxt <= 6) KC_RESIZE_LAUNCH(6);
+    else if (maxt == 6) KC_RESIZE_LAUNCH(6);
     else KC_RESIZE_LAUNCH(8);
 #undef KC_RESIZE_LAUNCH
 }
 
-hipError_t launch_resize_lds(const ResizePlanes &p, int batch, uint32_t dw, uint32_t dh, TapsDev v, TapsDev h,
-                             uint32_t h_min_count, uint32_t tile_w, uint32_t tile_h, uint32_t ncp, hipStream_t s, ResizeVariant *var)
+hipError_t launch_resize_lds(const ResizePlan &r, const ResizePlanes &p, TapsDev v, TapsDev h, hipStream_t s)
 {
-    if (dw == 0 || dh == 0) return hipSuccess;
-    if (batch < 1 || batch > 4) return hipErrorInvalidValue;
-    if (tile_w % 4 != 0 || tile_w > 1024 || 256u % (tile_w / 4) != 0 || tile_h > 64) return hipErrorInvalidValue;
-    const size_t lds = resize_lds_bytes(tile_h, ncp, v.stride, tile_w, h.stride);
-    dim3 grid((dw + tile_w - 1) / tile_w, (dh + tile_h - 1) / tile_h, batch);
-    if (var) var->wide = h.stride > KC_RESIZE_REG_TAPS;
-    if (h.stride > KC_RESIZE_REG_TAPS)
-        resize_wide_kernel<<<grid, 256, lds, s>>>(p, dw, dh, v, h, tile_w, tile_h, ncp,
-                                                  (uint32_t)(lds / sizeof(float) - (2u * tile_w + (size_t)tile_w * h.stride)));
-    else if (h_min_count >= 2)
-        launch_resize_lds_t<2>(grid, lds, s, h.stride, p, dw, dh, v, h, tile_w, tile_h, ncp);
+    if (r.dw == 0 || r.dh == 0) return hipSuccess;
+    if (r.planes < 1 || r.planes > 4) return hipErrorInvalidValue;
+    if (r.tile_w % 4 != 0 || r.tile_w > 1024 || 256u % (r.tile_w / 4) != 0 || r.tile_h > 64) return hipErrorInvalidValue;
+    if (r.form == ResizeForm::wide)
+        resize_wide_kernel<<<r.grid, 256, r.lds, s>>>(p, r.dw, r.dh, v, h, r.tile_w, r.tile_h, r.ncp,
+                                                      (uint32_t)(r.lds / sizeof(float) - (2u * r.tile_w + (size_t)r.tile_w * h.stride)));
+    else if (r.mint >= 2)
+        launch_resize_lds_t<2>(r.grid, r.lds, s, r.maxt, p, r.dw, r.dh, v, h, r.tile_w, r.tile_h, r.ncp);
     else
-        launch_resize_lds_t<1>(grid, lds, s, h.stride, p, dw, dh, v, h, tile_w, tile_h, ncp);
+        launch_resize_lds_t<1>(r.grid, r.lds, s, r.maxt, p, r.dw, r.dh, v, h, r.tile_w, r.tile_h, r.ncp);
     return hipGetLastError();
 }
 
-hipError_t launch_resize_down(const ResizePlanes &p, int batch, uint32_t dw, uint32_t dh, TapsDev v, TapsDev h, uint32_t tile_w,
-                              uint32_t tile_h, uint32_t ncp, hipStream_t s)
+hipError_t launch_resize_down(const ResizePlan &r, const ResizePlanes &p, TapsDev v, TapsDev h, hipStream_t s)
 {
-    if (dw == 0 || dh == 0) return hipSuccess;
-    if (batch < 1 || batch > 4) return hipErrorInvalidValue;
-    if (tile_w == 0 || tile_w > 64 || (tile_h != 16 && tile_h != 32) || ncp % 4 != 0 || ncp > 256) return hipErrorInvalidValue;
-    const size_t lds = resize_down_lds_bytes(tile_h, ncp, tile_w, h.stride);
-    dim3 grid((dw + tile_w - 1) / tile_w, (dh + tile_h - 1) / tile_h, batch);
-    if (tile_h == 16)
-        resize_down_kernel<4><<<grid, 256, lds, s>>>(p, dw, dh, v, h, tile_w, ncp);
+    if (r.dw == 0 || r.dh == 0) return hipSuccess;
+    if (r.planes < 1 || r.planes > 4) return hipErrorInvalidValue;
+    if (r.tile_w == 0 || r.tile_w > 64 || (r.tile_h != 16 && r.tile_h != 32) || r.ncp % 4 != 0 || r.ncp > 256) return hipErrorInvalidValue;
+    if (r.tile_h == 16)
+        resize_down_kernel<4><<<r.grid, 256, r.lds, s>>>(p, r.dw, r.dh, v, h, r.tile_w, r.ncp);
     else
-        resize_down_kernel<8><<<grid, 256, lds, s>>>(p, dw, dh, v, h, tile_w, ncp);
+        resize_down_kernel<8><<<r.grid, 256, r.lds, s>>>(p, r.dw, r.dh, v, h, r.tile_w, r.ncp);
     return hipGetLastError();
 }
 
@@ -1262,74 +1242,19 @@ static void launch_resize_poly_a(dim3 grid, size_t lds, hipStream_t s, uint32_t 
     else resize_poly_kernel<A, 8><<<grid, 256, lds, s>>>(p, dw, dh, v, h, tile_w, ncp, b);
 }
 
-// The poly_rows option (tuning): 0 (chosen by the launch) or rows per band, rounded down to a multiple of 4 and at least 4
-static uint32_t poly_rows_option() { return options().poly_rows ? std::max(4u, (uint32_t)options().poly_rows / 4u * 4u) : 0u; }
-
-// Rows [reg_a, reg_b) of the vertical table are regular: `ages` x `ratio` taps each, windows `ratio` apart, equal weights.
-hipError_t launch_resize_poly(const ResizePlanes &p, int batch, uint32_t dw, uint32_t dh, TapsDev v, TapsDev h, uint32_t tile_w,
-                              uint32_t ncp, uint32_t reg_a, uint32_t reg_b, uint32_t ages, uint32_t ratio, hipStream_t s, ResizeVariant *var)
+// resize_poly_kernel: bands of the vertical table's regular rows (`ages` x `ratio` taps each, windows `ratio` apart, equal
+// weights), the rows above and below them as border tiles
+hipError_t launch_resize_poly(const ResizePlan &r, const ResizePlanes &p, TapsDev v, TapsDev h, hipStream_t s)
 {
-    if (dw == 0 || dh == 0) return hipSuccess;
-    if (batch < 1 || batch > 4) return hipErrorInvalidValue;
-    if (tile_w == 0 || tile_w > 64 || ncp % 4 != 0 || ncp > 256 || reg_a > reg_b || reg_b > dh) return hipErrorInvalidValue;
-    if ((ages != 2 && ages != 4 && ages != 6) || (ratio != 2 && ratio != 4 && ratio != 8)) return hipErrorInvalidValue;
-    PolyBands b{};
-    b.ya = reg_a;
-    b.yb = reg_a + (reg_b - reg_a) / 4u * 4u;
-    // Band height: 12 rows for one plane, 24 for several planes of a long-windowed filter.  Measured on one box
-    // (profiles/r02_down_kernel.md): 8 / 12 / 16 rows give 28.7 / 24.5 / 27.7 us on Lanczos3 4:1 -- shorter bands re-read more
-    // of their neighbours' windows, taller ones leave too few waves to overlap one wave's arithmetic with another's loads
-    // (bands sized for one wave per SIMD, 20+ rows, were slower still); with four planes per launch the waves are there and
-    // 12 / 24 / 36 / 48 rows give 80.5 / 71.2 / 74.8 / 85.4 us.
-    // A launch whose waves are all resident at once lasts as long as ONE wave lives -- A - 1 + rows trips -- so images that do
-    // not fill the chip take SHORT bands: 2048^2 -> 512^2 19.3 / 15.3 / 11.5 us with 12 / 8 / 4 rows, 2048^2 -> 256^2
-    // 26.6 / 20.3 / 16.5, 1024^2 -> 256^2 16.7 / 13.2 / 9.6 (profiles/r04_poly_rows_small.txt); past about one wave per SIMD the
-    // windows short bands re-read cost more than their trips save (4096^2 -> 1024^2: 22.2 / 24.7 / 33.5 us).
-    // With four strips of a band per workgroup (round 4), same run, one plane, 8 / 12 / 16 / 24 rows: Lanczos3 4096^2 -> 1024^2
-    // 23.5 / 22.4 / 26.1 / 29.2 us; RGBA launches 12 / 16 / 24 / 32 rows: Lanczos3 4:1 68.1 / 65.8 / 70.8 / 63.5, CatmullRom 4:1
-    // 57.3 / 62.7 / 55.7 / 54.2, but 2048^2 -> 512^2 RGBA 26.4 / 26.3 / 34.2 / 34.4 (profiles/r04_poly_rows_by_band.txt): tall bands
-    // only where 12-row bands already give six waves per SIMD.
-    b.rows = 12u;
-    b.gx = (dw + tile_w - 1) / tile_w;
-    {
-        const uint64_t regular = (reg_b - reg_a) / 4u * 4u;
-        bool small = false;
-        for (uint32_t r : { 4u, 8u })
-            if (b.gx * ((regular + r - 1) / r) * (uint64_t)batch <= 1100u) {
-                b.rows = r;
-                small = true;
-                break;
-            }
-        if (!small && b.gx * ((regular + 11u) / 12u) * (uint64_t)batch >= 6000u) b.rows = 32u;
-    }
-    if (const uint32_t rows = poly_rows_option()) b.rows = rows;
-    b.n_bands = (b.yb - b.ya + b.rows - 1) / b.rows;
-    // what is left: rows above the first band and below the last one, as general tiles of at most 16 rows
-    uint32_t nt = 0;
-    auto add_tiles = [&](uint32_t y0, uint32_t y1) {
-        for (uint32_t y = y0; y < y1; y += 16u) {
-            if (nt == 4) return false;
-            b.ty0[nt] = y;
-            b.th[nt] = std::min(16u, y1 - y);
-            ++nt;
-        }
-        return true;
-    };
-    if (!add_tiles(0, b.ya) || !add_tiles(b.yb, dh)) return hipErrorInvalidValue;
-    // Band workgroups: four neighbouring strips of one band each, dealt to the XCDs in eighths of the band-major sequence (what
-    // this order is worth, same run, us: Gaussian 4096^2 -> 512^2 30.6 -> 25.2, Lanczos3 -> 1024^2 24.7 -> 22.4, Triangle -> 512^2
-    // 18.1 -> 16.0, 8192^2 -> 1024^2 83.9 -> 67.8; RGBA Triangle 57.1 -> 48.5 = 0.70 of the HBM peak: profiles/r04_poly_by_band.txt)
-    b.n_sq = (b.gx + 3u) / 4u;
-    b.n_band_wgs = b.n_bands * b.n_sq;
-    b.xper = (b.n_band_wgs + 7u) / 8u;
-    b.wave_floats = resize_down_wave_floats(tile_w, h.stride);
-    const size_t lds = std::max(resize_down_lds_bytes(16, ncp, tile_w, h.stride), (size_t)4 * b.wave_floats * sizeof(float));
-    if (lds > 64u * 1024u) return hipErrorInvalidValue;
-    const dim3 grid(8u * b.xper + nt * b.gx, 1, batch);
-    if (var) var->rows = b.rows;
-    if (ages == 2) launch_resize_poly_a<2>(grid, lds, s, ratio, p, dw, dh, v, h, tile_w, ncp, b);
-    else if (ages == 4) launch_resize_poly_a<4>(grid, lds, s, ratio, p, dw, dh, v, h, tile_w, ncp, b);
-    else launch_resize_poly_a<6>(grid, lds, s, ratio, p, dw, dh, v, h, tile_w, ncp, b);
+    const PolyBands &b = r.poly;
+    if (r.dw == 0 || r.dh == 0) return hipSuccess;
+    if (r.planes < 1 || r.planes > 4) return hipErrorInvalidValue;
+    if (r.tile_w == 0 || r.tile_w > 64 || r.ncp % 4 != 0 || r.ncp > 256 || b.ya > b.yb || b.yb > r.dh) return hipErrorInvalidValue;
+    if ((r.ages != 2 && r.ages != 4 && r.ages != 6) || (r.ratio != 2 && r.ratio != 4 && r.ratio != 8)) return hipErrorInvalidValue;
+    if (r.n_border > 4 || r.lds > 64u * 1024u) return hipErrorInvalidValue;
+    if (r.ages == 2) launch_resize_poly_a<2>(r.grid, r.lds, s, r.ratio, p, r.dw, r.dh, v, h, r.tile_w, r.ncp, b);
+    else if (r.ages == 4) launch_resize_poly_a<4>(r.grid, r.lds, s, r.ratio, p, r.dw, r.dh, v, h, r.tile_w, r.ncp, b);
+    else launch_resize_poly_a<6>(r.grid, r.lds, s, r.ratio, p, r.dw, r.dh, v, h, r.tile_w, r.ncp, b);
     return hipGetLastError();
 }
 
@@ -1346,17 +1271,8 @@ hipError_t launch_resize_poly(const ResizePlanes &p, int batch, uint32_t dw, uin
 // s_barrier (the ring holds eight rows, so nobody has to wait for the other's reads before writing on).  The barrier is a bare
 // s_waitcnt lgkmcnt(0) + s_barrier: the rows requested for the next trips stay in flight across it.  Both pairs of a workgroup
 // work on the same band (same number of trips and barriers).  Same taps in the same order: same roundings.
-// Rows outside the regular range run as resize_down_kernel tiles in the launch's last workgroups, as before.
-struct Poly2Bands {
-    uint32_t ya, yb, rows, n_bands;
-    uint32_t tw, n_strips;     // band path: output columns per strip (its source window is at most 256 columns), strips per row
-    uint32_t n_wgx;            // workgroups per band (two strips each)
-    uint32_t n_band_wgs;       // n_wgx * n_bands; the general tiles follow
-    uint32_t gen_tw, gen_gx, gen_ncp;  // general tiles: resize_down_kernel's strip width, strips per row, padded window
-    uint32_t n_gen;
-    uint32_t ty0[6], th[6];
-};
-#define KC_POLY2_RING_PITCH 265u  // 256 columns + one pad per 32, odd
+// Rows outside the regular range run as resize_down_kernel tiles in the launch's last workgroups, as before.  (Poly2Bands and
+// KC_POLY2_RING_PITCH: kc_internal.hpp)
 #ifndef KC_POLY2_NB
 #define KC_POLY2_NB 1  // trips of rows in flight beyond the one in use: 1 / 2 / 3 measure the same or worse (profiles/r04_poly2_sweep.txt)
 #endif
@@ -1557,74 +1473,20 @@ static void launch_resize_poly2_a(dim3 grid, size_t lds, hipStream_t s, uint32_t
     else resize_poly2_kernel<A, 8><<<grid, 256, lds, s>>>(p, dw, dh, v, h, b, pair_floats, x);
 }
 
-// tw: output columns per band strip (host-checked: every strip's source window, from its first column rounded down to a multiple
-// of 4, is at most 256 columns); gen_tw / gen_ncp: resize_down_kernel's tile for the border rows.
-hipError_t launch_resize_poly2(const ResizePlanes &p, int batch, uint32_t dw, uint32_t dh, TapsDev v, TapsDev h, uint32_t tw,
-                               uint32_t gen_tw, uint32_t gen_ncp, uint32_t reg_a, uint32_t reg_b, uint32_t ages, uint32_t ratio, bool xcd,
-                               hipStream_t s, ResizeVariant *var)
+// b.tw: output columns per band strip (host-checked: every strip's source window, from its first column rounded down to a multiple
+// of 4, is at most 256 columns); b.gen_tw / b.gen_ncp: resize_down_kernel's tile for the border rows.
+hipError_t launch_resize_poly2(const ResizePlan &r, const ResizePlanes &p, TapsDev v, TapsDev h, hipStream_t s)
 {
-    if (dw == 0 || dh == 0) return hipSuccess;
-    if (batch < 1 || batch > 4) return hipErrorInvalidValue;
-    if (tw == 0 || tw > 128 || gen_tw == 0 || gen_tw > 64 || gen_ncp % 4 != 0 || gen_ncp > 256 || reg_a > reg_b || reg_b > dh) return hipErrorInvalidValue;
-    if ((ages != 2 && ages != 4 && ages != 6) || (ratio != 2 && ratio != 4 && ratio != 8)) return hipErrorInvalidValue;
-    Poly2Bands b{};
-    b.ya = reg_a;
-    b.yb = reg_a + (reg_b - reg_a) / 4u * 4u;
-    if (b.yb == b.ya) return hipErrorInvalidValue;
-    b.tw = tw;
-    b.n_strips = (dw + tw - 1) / tw;
-    b.n_wgx = (b.n_strips + 1u) / 2u;
-    // band height as resize_poly_kernel chooses it (a launch lasts as long as one wave lives), for twice the waves per strip
-    b.rows = 12u;
-    {
-        // (2048^2 -> 256^2 Gaussian: 16.5 / 14.7 us with 4 / 8 rows = 1280 / 640 waves)
-        const uint64_t regular = b.yb - b.ya, waves4 = 4u * b.n_wgx * ((regular + 3u) / 4u) * (uint64_t)batch,
-                       waves8 = 4u * b.n_wgx * ((regular + 7u) / 8u) * (uint64_t)batch;
-        if (waves4 <= 1100u) b.rows = 4u;
-        else if (waves8 <= 2200u) b.rows = 8u;
-        // (and where 12-row bands give six waves per SIMD or more -- RGBA launches from 4096^2 on -- taller bands re-read less:
-        // 4096^2 -> 512^2 RGBA 68.0 -> 66.0 us, 8192^2 -> 1024^2 RGBA 286.6 -> 271.1; 2048^2 -> 256^2 RGBA 24.9 -> 38.2, one plane
-        // at 4096^2 25.3 -> 30.3: profiles/r04_poly2_rows_rgba.txt, r04_poly2_sweep.txt)
-        else if (4u * b.n_wgx * ((regular + 11u) / 12u) * (uint64_t)batch >= 6000u) b.rows = 24u;
-    }
-    if (const uint32_t rows = poly_rows_option()) b.rows = rows;
-    b.n_bands = (b.yb - b.ya + b.rows - 1) / b.rows;
-    b.n_band_wgs = b.n_wgx * b.n_bands;
-    b.gen_tw = gen_tw;
-    b.gen_ncp = gen_ncp;
-    b.gen_gx = (dw + gen_tw - 1) / gen_tw;
-    uint32_t nt = 0;
-    auto add_tiles = [&](uint32_t y0, uint32_t y1) {
-        for (uint32_t y = y0; y < y1; y += 16u) {
-            if (nt == 6) return false;
-            b.ty0[nt] = y;
-            b.th[nt] = std::min(16u, y1 - y);
-            ++nt;
-        }
-        return true;
-    };
-    if (!add_tiles(0, b.ya) || !add_tiles(b.yb, dh)) return hipErrorInvalidValue;
-    b.n_gen = nt;
-    const uint32_t pair_floats = (8u * KC_POLY2_RING_PITCH + 256u + tw * (h.stride | 1u) + 3u) / 4u * 4u;
-    const size_t lds = std::max((size_t)2 * pair_floats * sizeof(float), resize_down_lds_bytes(16, gen_ncp, gen_tw, h.stride));
-    if (lds > 64u * 1024u) return hipErrorInvalidValue;
-    const int xcd_opt = options().poly2_xcd;  // 0: plain order, 2: strip-major, else band-major eighths
-    (void)xcd;
-    XcdOrder x{ 0, 0, 0, 0 };
-    if (xcd_opt == 2) {
-        x = xcd_order(b.n_wgx, b.n_bands, true);
-    } else if (xcd_opt != 0 && b.n_band_wgs >= 16u) {
-        x.per = (b.n_band_wgs + 7u) / 8u;
-        x.n = b.n_band_wgs;
-    }
-    dim3 grid((x.per ? 8u * x.per : b.n_band_wgs) + nt * b.gen_gx, 1, batch);
-    if (var) {
-        var->rows = b.rows;
-        var->xcd = x.per != 0;
-    }
-    if (ages == 2) launch_resize_poly2_a<2>(grid, lds, s, ratio, p, dw, dh, v, h, b, pair_floats, x);
-    else if (ages == 4) launch_resize_poly2_a<4>(grid, lds, s, ratio, p, dw, dh, v, h, b, pair_floats, x);
-    else launch_resize_poly2_a<6>(grid, lds, s, ratio, p, dw, dh, v, h, b, pair_floats, x);
+    const Poly2Bands &b = r.poly2;
+    if (r.dw == 0 || r.dh == 0) return hipSuccess;
+    if (r.planes < 1 || r.planes > 4) return hipErrorInvalidValue;
+    if (b.tw == 0 || b.tw > 128 || b.gen_tw == 0 || b.gen_tw > 64 || b.gen_ncp % 4 != 0 || b.gen_ncp > 256 || b.ya >= b.yb || b.yb > r.dh)
+        return hipErrorInvalidValue;
+    if ((r.ages != 2 && r.ages != 4 && r.ages != 6) || (r.ratio != 2 && r.ratio != 4 && r.ratio != 8)) return hipErrorInvalidValue;
+    if (r.n_border > 6 || r.lds > 64u * 1024u) return hipErrorInvalidValue;
+    if (r.ages == 2) launch_resize_poly2_a<2>(r.grid, r.lds, s, r.ratio, p, r.dw, r.dh, v, h, b, r.pair_floats, r.xcd);
+    else if (r.ages == 4) launch_resize_poly2_a<4>(r.grid, r.lds, s, r.ratio, p, r.dw, r.dh, v, h, b, r.pair_floats, r.xcd);
+    else launch_resize_poly2_a<6>(r.grid, r.lds, s, r.ratio, p, r.dw, r.dh, v, h, b, r.pair_floats, r.xcd);
     return hipGetLastError();
 }
 
@@ -1642,19 +1504,16 @@ static hipError_t launch_resize_chain_k(const ChainProgram &p, dim3 grid, size_t
     return hipGetLastError();
 }
 
-hipError_t launch_resize_chain(const ChainProgram &p, int batch, uint32_t dw, uint32_t dh, TapsDev v, TapsDev h,
-                               uint32_t tile_w, uint32_t tile_h, uint32_t ncp, hipStream_t s)
+hipError_t launch_resize_chain(const ResizePlan &r, const ChainProgram &p, TapsDev v, TapsDev h, hipStream_t s)
 {
-    if (dw == 0 || dh == 0) return hipSuccess;
-    if (batch < 1 || batch > KC_CHAIN_MAX_BATCH || p.n_ops < 1 || p.n_ops > KC_CHAIN_MAX_OPS) return hipErrorInvalidValue;
-    if (tile_w % 4 != 0 || tile_w > 1024 || 256u % (tile_w / 4) != 0 || tile_h > 64) return hipErrorInvalidValue;
-    const size_t lds = resize_lds_bytes(tile_h, ncp, v.stride, tile_w, h.stride);
-    dim3 grid((dw + tile_w - 1) / tile_w, (dh + tile_h - 1) / tile_h, batch);
+    if (r.dw == 0 || r.dh == 0) return hipSuccess;
+    if (r.planes < 1 || r.planes > KC_CHAIN_MAX_BATCH || p.n_ops < 1 || p.n_ops > KC_CHAIN_MAX_OPS) return hipErrorInvalidValue;
+    if (r.tile_w % 4 != 0 || r.tile_w > 1024 || 256u % (r.tile_w / 4) != 0 || r.tile_h > 64) return hipErrorInvalidValue;
     switch (p.n_in) {
-    case 1: return launch_resize_chain_k<1>(p, grid, lds, s, dw, dh, v, h, tile_w, tile_h, ncp);
-    case 2: return launch_resize_chain_k<2>(p, grid, lds, s, dw, dh, v, h, tile_w, tile_h, ncp);
-    case 3: return launch_resize_chain_k<3>(p, grid, lds, s, dw, dh, v, h, tile_w, tile_h, ncp);
-    case 4: return launch_resize_chain_k<4>(p, grid, lds, s, dw, dh, v, h, tile_w, tile_h, ncp);
+    case 1: return launch_resize_chain_k<1>(p, r.grid, r.lds, s, r.dw, r.dh, v, h, r.tile_w, r.tile_h, r.ncp);
+    case 2: return launch_resize_chain_k<2>(p, r.grid, r.lds, s, r.dw, r.dh, v, h, r.tile_w, r.tile_h, r.ncp);
+    case 3: return launch_resize_chain_k<3>(p, r.grid, r.lds, s, r.dw, r.dh, v, h, r.tile_w, r.tile_h, r.ncp);
+    case 4: return launch_resize_chain_k<4>(p, r.grid, r.lds, s, r.dw, r.dh, v, h, r.tile_w, r.tile_h, r.ncp);
     default: return hipErrorInvalidValue;
     }
 }

@@ -121,6 +121,17 @@ static uint32_t tile_groups(const TapsHost &h, uint32_t out_n, uint32_t tile_w)
     return groups;
 }
 
+// The widest strip (up to `cap` columns) whose source window is at most 64 quads, then evened out over the strips it takes.
+static uint32_t strip_width(const TapsHost &h, uint32_t out_n, uint32_t cap)
+{
+    for (uint32_t tw = std::min(cap, out_n); tw >= 1; --tw)
+        if (tile_groups(h, out_n, tw) <= 64u) {
+            const uint32_t strips = (out_n + tw - 1) / tw, even = (out_n + strips - 1) / strips;
+            return tile_groups(h, out_n, even) <= 64u ? even : tw;
+        }
+    return 0;
+}
+
 // What resize_down2_kernel (down2.hip) reads instead of the plain table, for the tables of down-sampling axes (d2_want).
 // Vertical use: per group of four output rows the union of their windows in chunks of 16 source rows; record (group, chunk)
 // holds the weight of tap (source row u of the chunk, output row k of the group) at [8 + 4 u + k] -- +0.0 and a clear mask
@@ -134,13 +145,7 @@ void down2_build(uint32_t out_n, TapsHost &t)
     t.d2_strips.clear();
     t.d2_hw.clear();
     if (!t.d2_want || out_n == 0) return;
-    // resize_poly2_kernel's strips: the widest (up to 128 columns) whose source window is at most 64 quads, evened out
-    for (uint32_t tw = std::min(128u, out_n); tw >= 1; --tw)
-        if (tile_groups(t, out_n, tw) <= 64u) {
-            const uint32_t strips = (out_n + tw - 1) / tw, even = (out_n + strips - 1) / strips;
-            t.p2_tile_w = tile_groups(t, out_n, even) <= 64u ? even : tw;
-            break;
-        }
+    t.p2_tile_w = strip_width(t, out_n, 128u);  // resize_poly2_kernel's strips
     const uint32_t groups = (out_n + 3u) / 4u;
     uint32_t nc = 0;
     for (uint32_t g = 0; g < groups; ++g) {
@@ -190,15 +195,7 @@ void down2_build(uint32_t out_n, TapsHost &t)
     t.d2_hw.assign((size_t)out_n * hs, 0.0f);
     for (uint32_t x = 0; x < out_n; ++x)
         std::copy(t.w.begin() + (size_t)x * t.stride, t.w.begin() + (size_t)x * t.stride + t.count[x], t.d2_hw.begin() + (size_t)x * hs);
-    // the widest strip whose source window is at most 64 quads (one per lane of the vertical pass), then evened out over the
-    // strips it takes
-    const uint32_t cap = 64u * down2_cols_per_lane(hs / 4u);
-    for (uint32_t tw = std::min(cap, out_n); tw >= 1; --tw)
-        if (tile_groups(t, out_n, tw) <= 64u) {
-            const uint32_t strips = (out_n + tw - 1) / tw, even = (out_n + strips - 1) / strips;
-            t.d2_tile_w = tile_groups(t, out_n, even) <= 64u ? even : tw;
-            break;
-        }
+    t.d2_tile_w = strip_width(t, out_n, 64u * down2_cols_per_lane(hs / 4u));  // (64 quads: one per lane of the vertical pass)
     for (uint32_t x0 = 0; t.d2_tile_w && x0 < out_n; x0 += t.d2_tile_w) {
         const uint32_t x1 = std::min(out_n, x0 + t.d2_tile_w), c0 = t.left[x0] & ~3u;
         t.d2_strips.push_back(c0);
@@ -432,9 +429,6 @@ static int get_band_taps(uint32_t in_n, uint32_t out_n, int filter, int32_t a, i
     return KC_OK;
 }
 
-// LDS pitch in floats for such tiles; an odd group count staggers consecutive tile rows over the banks.
-static uint32_t tile_pitch(const TapsHost &h, uint32_t out_n, uint32_t tile_w) { return 4u * (tile_groups(h, out_n, tile_w) | 1u); }
-
 ResizeMemoScope::ResizeMemoScope()
 {
     Context &c = ctx();
@@ -482,54 +476,46 @@ static int resize_plane(kc_plane *src, kc_size size, int filter, kc_plane **out)
     return KC_OK;
 }
 
-// Picks the output tile for one resample: the first candidate whose vertical-pass intermediate
-// (tile_h rows of the tile's source-column window) fits the LDS budget.  Wide tiles make every tile
-// row one long run of 16-byte stores; the budget keeps several workgroups resident per CU.
-struct TileChoice {
-    uint32_t tile_w = 0, tile_h = 0, ncp = 0;
-    bool ok = false;
-    bool down = false;  // resize_down_kernel (both axes wider than the register-tap forms)
-    bool poly = false;  // ... and its vertical table is regular: resize_poly_kernel
-};
-
-static bool tile_fits(const TapsEntry &tv, const TapsEntry &th, kc_size size, uint32_t tw, uint32_t tht, size_t budget, TileChoice &t)
+// The tiled forms' output tile.  Wave-uniform forms aside, the first candidate whose vertical-pass intermediate (tile_h rows
+// of the tile's source-column window) fits the LDS budget.  Wide tiles make every tile row one long run of 16-byte stores;
+// the budget keeps several workgroups resident per CU.
+static bool tile_fits(const TapsHost &v, const TapsHost &h, uint32_t tw, uint32_t tht, size_t budget, ResizePlan &r)
 {
     if (tw % 4 != 0 || tw > 1024 || tw == 0 || tht == 0 || tht > 64 || 256u % (tw / 4) != 0) return false;
-    const uint32_t ncp = tile_pitch(th.host, size.width, tw);
-    if (resize_lds_bytes(tht, ncp, tv.dev.stride, tw, th.dev.stride) > budget) return false;
-    t.tile_w = tw;
-    t.tile_h = tht;
-    t.ncp = ncp;
-    t.ok = true;
+    const uint32_t ncp = 4u * (tile_groups(h, r.dw, tw) | 1u);  // an odd group count staggers consecutive tile rows over the banks
+    if (resize_lds_bytes(tht, ncp, v.stride, tw, h.stride) > budget) return false;
+    r.form = h.stride > KC_RESIZE_REG_TAPS ? ResizeForm::wide : ResizeForm::lds;
+    r.tile_w = tw;
+    r.tile_h = tht;
+    r.ncp = ncp;
     return true;
 }
 
-static TileChoice choose_tile(const TapsEntry &tv, const TapsEntry &th, kc_size size)
+// Sets r's tiled form (poly, down, wide or lds) and its tile, or returns false: no tile fits.
+static bool choose_tile(const TapsHost &v, const TapsHost &h, const Options &o, ResizePlan &r)
 {
-    const Options &o = options();
-    TileChoice t;
     // Both axes down-sampled: the wave-uniform form.  Its vertical pass deals 64 column quads to a wave, so the widest
     // tile whose source window is at most 64 quads wastes no lanes; a wave walks 4 (tile of 16) or 8 (tile of 32) rows.
-    if (th.dev.stride > KC_RESIZE_REG_TAPS && tv.dev.stride > KC_RESIZE_REG_TAPS && o.resize_mode != 2) {
+    if (h.stride > KC_RESIZE_REG_TAPS && v.stride > KC_RESIZE_REG_TAPS && o.resize_mode != 2) {
         const uint32_t rows = o.resize_tile_h == 32 ? 32u : 16u;  // KC_RESIZE_TILE_H=32: tuning
         for (uint32_t tw = 64; tw >= 4; tw -= 4) {
-            const uint32_t groups = tile_groups(th.host, size.width, tw);
+            const uint32_t groups = tile_groups(h, r.dw, tw);
             if (groups > 64) continue;  // the intermediate rows hold 256 floats
-            if (resize_down_lds_bytes(rows, 4u * groups, tw, th.dev.stride) > 64 * 1024) continue;
-            t.tile_w = tw;
-            t.tile_h = rows;
-            t.ncp = 4u * groups;
-            t.ok = t.down = true;
-            const TapsHost &hv = tv.host;
-            t.poly = rows == 16 && o.resize_mode != 1 && (hv.reg_ages == 2 || hv.reg_ages == 4 || hv.reg_ages == 6) &&
-                     (hv.reg_ratio == 2 || hv.reg_ratio == 4 || hv.reg_ratio == 8) && hv.reg_b - hv.reg_a >= 16 && hv.reg_a <= 16 &&
-                     size.height - (hv.reg_a + (hv.reg_b - hv.reg_a) / 4 * 4) <= 48;
-            return t;
+            if (resize_down_lds_bytes(rows, 4u * groups, tw, h.stride) > 64 * 1024) continue;
+            r.tile_w = tw;
+            r.tile_h = rows;
+            r.ncp = 4u * groups;
+            // ... and resize_poly_kernel where the vertical table is regular
+            const bool poly = rows == 16 && o.resize_mode != 1 && (v.reg_ages == 2 || v.reg_ages == 4 || v.reg_ages == 6) &&
+                              (v.reg_ratio == 2 || v.reg_ratio == 4 || v.reg_ratio == 8) && v.reg_b - v.reg_a >= 16 && v.reg_a <= 16 &&
+                              r.dh - (v.reg_a + (v.reg_b - v.reg_a) / 4 * 4) <= 48;
+            r.form = poly ? ResizeForm::poly : ResizeForm::down;
+            return true;
         }
     }
     if (o.resize_tile_w > 0 && o.resize_tile_h > 0 &&  // tuning override (KC_RESIZE_TILE_W / _H)
-        tile_fits(tv, th, size, (uint32_t)o.resize_tile_w, (uint32_t)o.resize_tile_h, 64 * 1024, t))
-        return t;
+        tile_fits(v, h, (uint32_t)o.resize_tile_w, (uint32_t)o.resize_tile_h, 64 * 1024, r))
+        return true;
     // Wide horizontal windows (down-sampling): the vertical pass re-reads window rows per output row, so small tiles --
     // many workgroups, short dependent chains -- win (profiles/resize_tile_sweep.py).  With the intermediate rows
     // swizzled (no LDS bank conflicts in the horizontal pass) 64 x 8 is the best all-rounder: Lanczos3 4x 37.9 -> 36.3 us,
@@ -538,23 +524,24 @@ static TileChoice choose_tile(const TapsEntry &tv, const TapsEntry &th, kc_size 
     static const uint32_t tiles[][2] = { { 1024, 16 }, { 1024, 8 }, { 512, 16 }, { 512, 8 }, { 256, 16 }, { 256, 8 },
                                          { 128, 16 },  { 128, 8 },  { 64, 8 },   { 32, 8 },  { 16, 8 },   { 16, 4 },
                                          { 8, 4 },     { 4, 4 } };
-    if (th.dev.stride > KC_RESIZE_REG_TAPS)
+    if (h.stride > KC_RESIZE_REG_TAPS)
         for (auto &tl : wide)
-            if (tile_fits(tv, th, size, tl[0], tl[1], 64 * 1024, t)) return t;
+            if (tile_fits(v, h, tl[0], tl[1], 64 * 1024, r)) return true;
     for (size_t budget : { (size_t)40 * 1024, (size_t)64 * 1024 })
         for (auto &tl : tiles)
-            if (tile_fits(tv, th, size, tl[0], tl[1], budget, t)) return t;
-    return t;
+            if (tile_fits(v, h, tl[0], tl[1], budget, r)) return true;
+    return false;
 }
 
-// Integer-ratio up-sampling on both axes (upsample.h): tile and LDS pitch for upsample_chain_tile, or false.
-static bool up_plan(const TapsEntry &tv, const TapsEntry &th, UpsampleArgs &u)
+// Integer-ratio up-sampling on both axes (upsample.h): tile and LDS pitch for upsample_chain_tile, or false.  The axes come
+// with their class rows' device pointers (taps_upload sets them exactly when up_rows / up_qrows are not empty); nothing here
+// reads them.
+static bool up_plan(const TapsHost &v, const TapsHost &h, const Options &o, UpsampleArgs &u)
 {
-    const Options &o = options();
-    if (o.resize_mode >= 3 || !tv.host.up_ok || !th.host.up_ok) return false;
-    u.H = th.host.up;
-    u.V = tv.host.up;
-    if (u.H.taps != u.V.taps || !u.H.qcls || !u.V.cls) return false;
+    if (o.resize_mode >= 3 || !v.up_ok || !h.up_ok) return false;
+    u.H = h.up;
+    u.V = v.up;
+    if (u.H.taps != u.V.taps || h.up_qrows.empty() || v.up_rows.empty()) return false;
     if (u.H.ratio % 4 != 0 && !(u.H.ratio == 2 && u.H.n_out % 4 == 0)) return false;  // (ratio 2: "half quads", upsample.h)
     const uint32_t dw = u.H.n_out, R = u.H.ratio, T = u.H.taps;
     // widest tile that wastes the fewest threads on columns past the image (narrower tiles are taller: a thread always
@@ -588,17 +575,248 @@ static bool up_plan(const TapsEntry &tv, const TapsEntry &th, UpsampleArgs &u)
     return upsample_lds_bytes(u) <= 64 * 1024;
 }
 
+// Rows [y0, y1) as border tiles of at most 16 rows: every one is counted in n, the first `cap` are kept.
+static void border_tiles(uint32_t y0, uint32_t y1, uint32_t *ty0, uint32_t *th, uint32_t cap, uint32_t &n)
+{
+    for (uint32_t y = y0; y < y1; y += 16u, ++n)
+        if (n < cap) {
+            ty0[n] = y;
+            th[n] = std::min(16u, y1 - y);
+        }
+}
+
+// resize_poly_kernel: rows [reg_a, reg_b) of the vertical table are regular -- reg_ages x reg_ratio taps each, windows reg_ratio
+// apart, equal weights -- and run as bands; the rows above and below them as border tiles.
+static void plan_poly(ResizePlan &r, const TapsHost &v, const TapsHost &h, uint32_t rows_opt)
+{
+    PolyBands &b = r.poly;
+    r.ages = v.reg_ages;
+    r.ratio = v.reg_ratio;
+    b.ya = v.reg_a;
+    b.yb = v.reg_a + (v.reg_b - v.reg_a) / 4u * 4u;
+    // Band height: 12 rows for one plane, 24 for several planes of a long-windowed filter.  Measured on one box
+    // (profiles/r02_down_kernel.md): 8 / 12 / 16 rows give 28.7 / 24.5 / 27.7 us on Lanczos3 4:1 -- shorter bands re-read more
+    // of their neighbours' windows, taller ones leave too few waves to overlap one wave's arithmetic with another's loads
+    // (bands sized for one wave per SIMD, 20+ rows, were slower still); with four planes per launch the waves are there and
+    // 12 / 24 / 36 / 48 rows give 80.5 / 71.2 / 74.8 / 85.4 us.
+    // A launch whose waves are all resident at once lasts as long as ONE wave lives -- A - 1 + rows trips -- so images that do
+    // not fill the chip take SHORT bands: 2048^2 -> 512^2 19.3 / 15.3 / 11.5 us with 12 / 8 / 4 rows, 2048^2 -> 256^2
+    // 26.6 / 20.3 / 16.5, 1024^2 -> 256^2 16.7 / 13.2 / 9.6 (profiles/r04_poly_rows_small.txt); past about one wave per SIMD the
+    // windows short bands re-read cost more than their trips save (4096^2 -> 1024^2: 22.2 / 24.7 / 33.5 us).
+    // With four strips of a band per workgroup (round 4), same run, one plane, 8 / 12 / 16 / 24 rows: Lanczos3 4096^2 -> 1024^2
+    // 23.5 / 22.4 / 26.1 / 29.2 us; RGBA launches 12 / 16 / 24 / 32 rows: Lanczos3 4:1 68.1 / 65.8 / 70.8 / 63.5, CatmullRom 4:1
+    // 57.3 / 62.7 / 55.7 / 54.2, but 2048^2 -> 512^2 RGBA 26.4 / 26.3 / 34.2 / 34.4 (profiles/r04_poly_rows_by_band.txt): tall bands
+    // only where 12-row bands already give six waves per SIMD.
+    b.gx = (r.dw + r.tile_w - 1) / r.tile_w;
+    const uint64_t regular = b.yb - b.ya, wgs = b.gx * (uint64_t)r.planes;  // band waves per row of bands
+    b.rows = wgs * ((regular + 3u) / 4u) <= 1100u   ? 4u
+             : wgs * ((regular + 7u) / 8u) <= 1100u ? 8u
+             : wgs * ((regular + 11u) / 12u) >= 6000u ? 32u : 12u;
+    if (rows_opt) b.rows = rows_opt;
+    b.n_bands = (b.yb - b.ya + b.rows - 1) / b.rows;
+    // what is left: rows above the first band and below the last one, as general tiles of at most 16 rows
+    border_tiles(0, b.ya, b.ty0, b.th, 4, r.n_border);
+    border_tiles(b.yb, r.dh, b.ty0, b.th, 4, r.n_border);
+    // Band workgroups: four neighbouring strips of one band each, dealt to the XCDs in eighths of the band-major sequence (what
+    // this order is worth, same run, us: Gaussian 4096^2 -> 512^2 30.6 -> 25.2, Lanczos3 -> 1024^2 24.7 -> 22.4, Triangle -> 512^2
+    // 18.1 -> 16.0, 8192^2 -> 1024^2 83.9 -> 67.8; RGBA Triangle 57.1 -> 48.5 = 0.70 of the HBM peak: profiles/r04_poly_by_band.txt)
+    b.n_sq = (b.gx + 3u) / 4u;
+    b.n_band_wgs = b.n_bands * b.n_sq;
+    b.xper = (b.n_band_wgs + 7u) / 8u;
+    b.wave_floats = resize_down_wave_floats(r.tile_w, h.stride);
+    r.lds = std::max(resize_down_lds_bytes(16, r.ncp, r.tile_w, h.stride), (size_t)4 * b.wave_floats * sizeof(float));
+    r.grid = dim3(8u * b.xper + r.n_border * b.gx, 1, r.planes);
+}
+
+// resize_poly2_kernel: the same bands with two waves to a band's strip of h.p2_tile_w columns; the border tiles are
+// resize_down_kernel's (the plan's tile).  xcd_opt: the poly2_xcd option.
+static void plan_poly2(ResizePlan &r, const TapsHost &v, const TapsHost &h, uint32_t rows_opt, int xcd_opt)
+{
+    Poly2Bands &b = r.poly2;
+    r.form = ResizeForm::poly2;
+    r.ages = v.reg_ages;
+    r.ratio = v.reg_ratio;
+    b.ya = v.reg_a;
+    b.yb = v.reg_a + (v.reg_b - v.reg_a) / 4u * 4u;
+    b.tw = h.p2_tile_w;
+    b.n_strips = (r.dw + b.tw - 1) / b.tw;
+    b.n_wgx = (b.n_strips + 1u) / 2u;
+    // band height as resize_poly_kernel chooses it (a launch lasts as long as one wave lives), for twice the waves per strip
+    // (2048^2 -> 256^2 Gaussian: 16.5 / 14.7 us with 4 / 8 rows = 1280 / 640 waves), and where 12-row bands give six waves per
+    // SIMD or more -- RGBA launches from 4096^2 on -- taller bands re-read less: 4096^2 -> 512^2 RGBA 68.0 -> 66.0 us, 8192^2 ->
+    // 1024^2 RGBA 286.6 -> 271.1; 2048^2 -> 256^2 RGBA 24.9 -> 38.2, one plane at 4096^2 25.3 -> 30.3:
+    // profiles/r04_poly2_rows_rgba.txt, r04_poly2_sweep.txt
+    const uint64_t regular = b.yb - b.ya, waves = 4u * b.n_wgx * (uint64_t)r.planes;  // waves per row of bands
+    b.rows = waves * ((regular + 3u) / 4u) <= 1100u   ? 4u
+             : waves * ((regular + 7u) / 8u) <= 2200u ? 8u
+             : waves * ((regular + 11u) / 12u) >= 6000u ? 24u : 12u;
+    if (rows_opt) b.rows = rows_opt;
+    b.n_bands = (b.yb - b.ya + b.rows - 1) / b.rows;
+    b.n_band_wgs = b.n_wgx * b.n_bands;
+    b.gen_tw = r.tile_w;
+    b.gen_ncp = r.ncp;
+    b.gen_gx = (r.dw + r.tile_w - 1) / r.tile_w;
+    border_tiles(0, b.ya, b.ty0, b.th, 6, r.n_border);
+    border_tiles(b.yb, r.dh, b.ty0, b.th, 6, r.n_border);
+    b.n_gen = r.n_border;
+    r.pair_floats = (8u * KC_POLY2_RING_PITCH + 256u + b.tw * (h.stride | 1u) + 3u) / 4u * 4u;
+    r.lds = std::max((size_t)2 * r.pair_floats * sizeof(float), resize_down_lds_bytes(16, b.gen_ncp, b.gen_tw, h.stride));
+    // the bands go to the XCDs at every size, whatever the cache budget: band-major eighths (poly2_xcd -1), strip-major (2), or
+    // the plain order (0, and launches of fewer than 16 band workgroups)
+    if (xcd_opt == 2) {
+        r.xcd = xcd_order(b.n_wgx, b.n_bands, true);
+    } else if (xcd_opt != 0 && b.n_band_wgs >= 16u) {
+        r.xcd.per = (b.n_band_wgs + 7u) / 8u;
+        r.xcd.n = b.n_band_wgs;
+    }
+    r.grid = dim3((r.xcd.per ? 8u * r.xcd.per : b.n_band_wgs) + r.n_border * b.gen_gx, 1, r.planes);
+}
+
+// resize_down2_kernel: strips of h.d2_tile_w columns by groups of 4 rows, 16 rows to a workgroup; fits_cache: source and result
+// stay in the Infinity Cache (the budget of the cache policy, kc_set_option("cache_budget_mb")).
+static void plan_down2(ResizePlan &r, const TapsHost &v, const TapsHost &h, bool fits_cache, const Options &o)
+{
+    Down2Args &a = r.d2;
+    r.form = ResizeForm::down2;
+    a.nc = v.d2_nc;
+    a.hstride = h.d2_hstride;
+    a.tile_w = h.d2_tile_w;
+    a.dw = r.dw;
+    a.dh = r.dh;
+    r.grid = dim3((r.dw + a.tile_w - 1) / a.tile_w, (r.dh + 15u) / 16u, r.planes);
+    // Four strips of one row group per workgroup and the jobs dealt to the XCDs in eighths row by row (what resize_poly_kernel
+    // gained 8 - 20 % from): here it pays where the row groups' windows span several chunks (ratios from about 1.6: CatmullRom
+    // 4096^2 -> 1365^2 21.3 -> 19.3 us, RGBA 74.3 -> 63.9; Gaussian 3000^2 -> 700^2 14.6 -> 12.5, RGBA 52.4 -> 41.4; Lanczos3 2:1
+    // 24.8 -> 23.4) and costs 5 - 10 % on RGBA launches of single-chunk ratios (4096^2 -> 3000^2 111.5 -> 122.4), which keep the
+    // order below (profiles/r04_down2_by_rows.txt).  kc_set_option("down2_by_rows") overrides; one strip: nothing to order, and
+    // the reciprocal of 1 does not fit 32 bits.
+    const bool by_rows = (o.down2_by_rows < 0 ? v.d2_nc > 1 : o.down2_by_rows != 0) && r.grid.x >= 2;
+    // Otherwise the tiles in XCD order while the planes fit the Infinity Cache (KC_DOWN2_XCD=0 / 1: never / always, A/B).
+    // Measured (profiles/r03_down2_xcd.txt): one 4096^2 plane 27.9 -> 26.2 us, 3000^2 -> 700^2 17.9 -> 15.4; four 4096^2 planes
+    // (268 MB of source, past the cache) 114.6 -> 122.7: there the plain order, whole rows at a time, is kinder to HBM.
+    const bool xcd = o.down2_xcd < 0 ? fits_cache : o.down2_xcd != 0;
+    // by rows the jobs are (row group, strip) pairs, the strips the inner index
+    const XcdOrder x = by_rows ? xcd_order((r.dh + 3u) / 4u, r.grid.x, true) : xcd_order(r.grid.x, r.grid.y, xcd);
+    if (x.per) {
+        a.by_rows = by_rows;
+        a.n_tiles = x.n;
+        a.gy = x.gy;
+        a.gy_magic = x.magic;
+        a.xcd_per = by_rows ? ((x.n + 3u) / 4u + 7u) / 8u : x.per;  // (by rows: four jobs to a workgroup)
+        r.grid = dim3(8u * a.xcd_per, 1, r.planes);
+    }
+}
+
+// Decides how the resample of `planes` planes src -> dst with the vertical table v and the horizontal table h runs, and its
+// launch shape: pure host work on the tables' host side and the options.  fused: inside a Mix chain's kernel (chain_resize_launch;
+// ResizeForm::none where that is not possible), otherwise on its own.
+static ResizePlan plan_resample(const TapsHost &v, const TapsHost &h, kc_size src, kc_size dst, int planes, bool fused, const Options &o)
+{
+    ResizePlan r;
+    r.sw = src.width;
+    r.sh = src.height;
+    r.dw = dst.width;
+    r.dh = dst.height;
+    r.planes = planes;
+    // Fused: every channel's resampled operand uses the same tap tables (same source size and filter, the caller's), at most 4
+    // horizontal taps (held in registers), and an LDS tile exists.
+    if (fused && (!o.fusion || o.resize_mode == 3)) return r;
+    if (up_plan(v, h, o, r.up) && (!fused || r.up.H.taps <= 3)) {
+        r.form = fused ? ResizeForm::upsample_chain : ResizeForm::upsample;
+        r.nt = !fused && (cache_policy_mask(0, (uint64_t)planes * 4 * r.dw * r.dh, 0, o) & 0x100u);  // the small source stays cacheable
+        return r;
+    }
+    // Tiled single pass when a tile's vertical-pass intermediate and tap tables fit in LDS; very wide
+    // windows fall back to two passes through an HBM intermediate (KC_RESIZE_MODE=3 forces them).
+    if ((fused ? h.stride > 4 : o.resize_mode == 3) || !choose_tile(v, h, o, r)) {
+        r.form = fused ? ResizeForm::none : ResizeForm::two_pass;
+        return r;
+    }
+    const bool poly = r.form == ResizeForm::poly;
+    if (!fused) {
+        const uint32_t rows_opt = o.poly_rows ? std::max(4u, (uint32_t)o.poly_rows / 4u * 4u) : 0u;  // tuning: rows per band
+        // integer ratios: two waves to a band's strip (resize_poly2_kernel)
+        // (where it measures faster than the forms below -- profiles/r04_poly2_sweep.txt: ratio 8 with windows of 4 or 6 ages,
+        // Gaussian 4096^2 -> 512^2 27.6 -> 25.3 us, 8192^2 -> 1024^2 82.5 -> 72.5; at ratio 4 and 2 it is behind resize_poly_kernel
+        // and resize_down2_kernel, 24.8 against 21.2 us and 34.3 against 24.5; kc_set_option("poly2_min_ratio") moves the line)
+        if (poly && o.poly2 && v.reg_ratio >= (uint32_t)o.poly2_min_ratio && v.reg_ages >= 4 && h.p2_tile_w) {
+            plan_poly2(r, v, h, rows_opt, o.poly2_xcd);
+            return r;
+        }
+        // both axes down-sampled: the wave-private form where its tables exist (down2_build fills d2_vrec with d2_nc, d2_hw and
+        // d2_strips with d2_tile_w) ... except where the streaming kernel of integer ratios is the faster one: ratios 4 and 8
+        // (Lanczos3 4096^2 -> 1024^2 23.5 against 26.7 us, CatmullRom 18.1 / 21.4; at ratio 2 down2 wins, 26.3 / 30.4 --
+        // profiles/r03_down2_ab.txt); kc_set_option("down2") 2 puts it first there too
+        if (o.down2 > (poly && v.reg_ratio >= 4 ? 1 : 0) && v.d2_nc && h.d2_tile_w) {
+            const uint64_t bytes = (uint64_t)planes * 4 * ((uint64_t)r.sw * r.sh + (uint64_t)r.dw * r.dh);
+            plan_down2(r, v, h, bytes <= ((uint64_t)o.cache_budget_mb << 20), o);
+            return r;
+        }
+        if (poly) {
+            plan_poly(r, v, h, rows_opt);
+            return r;
+        }
+    }
+    r.grid = dim3((r.dw + r.tile_w - 1) / r.tile_w, (r.dh + r.tile_h - 1) / r.tile_h, planes);
+    if (fused) r.form = ResizeForm::resize_chain;
+    r.lds = r.form == ResizeForm::down ? resize_down_lds_bytes(r.tile_h, r.ncp, r.tile_w, h.stride)
+                                       : resize_lds_bytes(r.tile_h, r.ncp, v.stride, r.tile_w, h.stride);
+    // resize_lds_kernel<MINT, MAXT>: MINT horizontal taps unconditional, up to MAXT
+    r.mint = h.min_count >= 2 ? 2u : 1u;
+    r.maxt = h.stride <= 4 ? std::max(h.stride, 1u) : h.stride <= 6 ? 6u : 8u;
+    return r;
+}
+
+// Counts a launched plan (kc_stats_counter): its form and the variant the plan chose; the plain forms' launches and algorithmic
+// bytes too (the fused forms' are the chain's: runtime.cpp, chain_launch).
+static void count_resize(const ResizePlan &r)
+{
+    Context &c = ctx();
+    const uint64_t n = (uint64_t)r.planes, src = (uint64_t)r.sw * r.sh, dst = (uint64_t)r.dw * r.dh;
+    switch (r.form) {
+    case ResizeForm::none: return;
+    case ResizeForm::upsample_chain: c.counters["upsample_chain_launches"]++; return;
+    case ResizeForm::resize_chain: c.counters["resize_chain_launches"]++; return;
+    case ResizeForm::two_pass:  // two launches per plane
+        c.launches += 2 * n;
+        c.counters["resize_two_pass_launches"] += n;
+        c.alg_bytes += n * 4 * (src + 2 * (uint64_t)r.sw * r.dh + dst);
+        return;
+    case ResizeForm::upsample:
+        c.counters["upsample_launches"]++;
+        if (r.nt) c.counters["upsample_nt_stores"]++;
+        if (r.up.H.ratio == 2) c.counters["upsample_half_quads"]++;
+        break;
+    case ResizeForm::poly2:
+        c.counters["poly2_launches"]++;
+        c.counters["poly2_rows_" + std::to_string(r.poly2.rows)]++;
+        if (r.xcd.per) c.counters["poly2_xcd_order"]++;
+        break;
+    case ResizeForm::down2:
+        c.counters["down2_launches"]++;
+        if (r.d2.by_rows) c.counters["down2_by_rows"]++;
+        else if (r.d2.xcd_per) c.counters["down2_xcd_order"]++;
+        break;
+    case ResizeForm::poly:
+        c.counters["resize_poly_launches"]++;
+        c.counters["poly_rows_" + std::to_string(r.poly.rows)]++;
+        break;
+    case ResizeForm::down: c.counters["resize_down_launches"]++; break;
+    case ResizeForm::lds: c.counters["resize_lds_launches"]++; break;
+    case ResizeForm::wide: c.counters["resize_wide_launches"]++; break;
+    }
+    c.launches++;
+    c.alg_bytes += n * 4 * (src + dst);
+}
+
 // Runs the resample srcs[i] -> dsts[i] (all resident; equal source sizes, equal target sizes) with the given tap
 // tables: one launch for the whole batch in the tiled form, two per plane in the two-pass form.
 static int resize_run_taps(kc_plane *const *srcs, kc_plane *const *dsts, int n, TapsEntry *tv, TapsEntry *th)
 {
     Context &c = ctx();
-    const kc_plane *s0 = srcs[0];
-    const kc_size size{ dsts[0]->w, dsts[0]->h };
-    // Tiled single pass when a tile's vertical-pass intermediate and tap tables fit in LDS; very wide
-    // windows fall back to two passes through an HBM intermediate (KC_RESIZE_MODE=3 forces them).
-    UpsampleArgs ua{};
-    if (up_plan(*tv, *th, ua)) {
+    const ResizePlan r = plan_resample(tv->host, th->host, { srcs[0]->w, srcs[0]->h }, { dsts[0]->w, dsts[0]->h }, n, false, c.opt);
+    hipError_t e = hipSuccess;
+    if (r.form == ResizeForm::upsample) {
         UpsamplePlanes up{};
         for (int i = 0; i < n; ++i) {
             up.samp_src[i] = srcs[i]->dptr;
@@ -606,117 +824,45 @@ static int resize_run_taps(kc_plane *const *srcs, kc_plane *const *dsts, int n, 
             up.out[i] = dsts[i]->dptr;
             up.out_pitch[i] = (uint32_t)(dsts[i]->pitch / 16);
         }
-        up.nt_mask = cache_policy_mask(0, (uint64_t)n * 4 * size.width * size.height, 0);  // the small source stays cacheable
-        hipError_t e = launch_upsample(up, n, ua, c.stream);
-        if (e != hipSuccess) return hip_fail(e, "launch_upsample");
-        c.launches++;
-        c.counters["upsample_launches"]++;
-        if (up.nt_mask & 0x100u) c.counters["upsample_nt_stores"]++;
-        if (ua.H.ratio == 2) c.counters["upsample_half_quads"]++;
-        c.alg_bytes += (uint64_t)n * 4 * ((uint64_t)s0->w * s0->h + (uint64_t)size.width * size.height);
-        return KC_OK;
-    }
-    if (c.opt.resize_mode != 3) {
-        const TileChoice t = choose_tile(*tv, *th, size);
-        if (t.ok) {
-            ResizePlanes rp{};
-            for (int i = 0; i < n; ++i) {
-                rp.src[i] = srcs[i]->dptr;
-                rp.dst[i] = dsts[i]->dptr;
-                rp.spitch[i] = (uint32_t)(srcs[i]->pitch / 4);
-                rp.dpitch[i] = (uint32_t)(dsts[i]->pitch / 4);
-            }
-            // both axes down-sampled: the wave-private form where its tables exist (down2.hip)
-            // ... except where the streaming kernel of integer ratios is the faster one: ratios 4 and 8 (Lanczos3 4096^2 -> 1024^2
-            // 23.5 against 26.7 us, CatmullRom 18.1 / 21.4; at ratio 2 down2 wins, 26.3 / 30.4 -- profiles/r03_down2_ab.txt)
-            // tiles in XCD order while source and result stay in the Infinity Cache (the budget of the cache policy,
-            // kc_set_option("cache_budget_mb")); resize_down2_kernel follows it, resize_poly2_kernel deals its bands to the XCDs
-            // at every size (launch_resize_poly2)
-            const bool fits_cache = (uint64_t)n * 4 * ((uint64_t)s0->w * s0->h + (uint64_t)size.width * size.height) <=
-                                    ((uint64_t)c.opt.cache_budget_mb << 20);
-            ResizeVariant var{};
-            // integer ratios: two waves to a band's strip (resize_poly2_kernel)
-            // (where it measures faster than the forms below -- profiles/r04_poly2_sweep.txt: ratio 8 with windows of 4 or 6 ages,
-            // Gaussian 4096^2 -> 512^2 27.6 -> 25.3 us, 8192^2 -> 1024^2 82.5 -> 72.5; at ratio 4 and 2 it is behind resize_poly_kernel
-            // and resize_down2_kernel, 24.8 against 21.2 us and 34.3 against 24.5; kc_set_option("poly2_min_ratio") moves the line)
-            if (t.poly && c.opt.poly2 && tv->host.reg_ratio >= (uint32_t)c.opt.poly2_min_ratio && tv->host.reg_ages >= 4 && th->host.p2_tile_w) {
-                hipError_t e2 = launch_resize_poly2(rp, n, size.width, size.height, tv->dev, th->dev, th->host.p2_tile_w, t.tile_w, t.ncp,
-                                                    tv->host.reg_a, tv->host.reg_b, tv->host.reg_ages, tv->host.reg_ratio, fits_cache, c.stream, &var);
-                if (e2 != hipSuccess) return hip_fail(e2, "launch_resize_poly2");
-                c.launches++;
-                c.counters["poly2_launches"]++;
-                c.counters["poly2_rows_" + std::to_string(var.rows)]++;
-                if (var.xcd) c.counters["poly2_xcd_order"]++;
-                c.alg_bytes += (uint64_t)n * 4 * ((uint64_t)s0->w * s0->h + (uint64_t)size.width * size.height);
-                return KC_OK;
-            }
-            const bool poly_first = t.poly && tv->host.reg_ratio >= 4;
-            if (c.opt.down2 > (poly_first ? 1 : 0) && tv->host.d2_nc && tv->host.d2_vrec_dev && th->host.d2_tile_w &&
-                th->host.d2_hw_dev && th->host.d2_strips_dev) {
-                Down2Args a{};
-                a.vrec = tv->host.d2_vrec_dev;
-                a.nc = tv->host.d2_nc;
-                a.hleft = th->dev.left;
-                a.hcount = th->dev.count;
-                a.hw = th->host.d2_hw_dev;
-                a.hstride = th->host.d2_hstride;
-                a.strips = th->host.d2_strips_dev;
-                a.tile_w = th->host.d2_tile_w;
-                a.dw = size.width;
-                a.dh = size.height;
-                a.xcd_per = fits_cache ? 1u : 0u;
-                a.by_rows = c.opt.down2_by_rows < 0 ? (tv->host.d2_nc > 1 ? 1u : 0u) : (c.opt.down2_by_rows ? 1u : 0u);
-                hipError_t e2 = launch_resize_down2(rp, n, a, c.stream, &var);
-                if (e2 != hipSuccess) return hip_fail(e2, "launch_resize_down2");
-                c.launches++;
-                c.counters["down2_launches"]++;
-                if (var.xcd) c.counters["down2_xcd_order"]++;
-                if (var.by_rows) c.counters["down2_by_rows"]++;
-                c.alg_bytes += (uint64_t)n * 4 * ((uint64_t)s0->w * s0->h + (uint64_t)size.width * size.height);
-                return KC_OK;
-            }
-            hipError_t e = t.poly ? launch_resize_poly(rp, n, size.width, size.height, tv->dev, th->dev, t.tile_w, t.ncp, tv->host.reg_a,
-                                                       tv->host.reg_b, tv->host.reg_ages, tv->host.reg_ratio, c.stream, &var)
-                           : t.down ? launch_resize_down(rp, n, size.width, size.height, tv->dev, th->dev, t.tile_w, t.tile_h, t.ncp, c.stream)
-                                  : launch_resize_lds(rp, n, size.width, size.height, tv->dev, th->dev, th->host.min_count, t.tile_w,
-                                                      t.tile_h, t.ncp, c.stream, &var);
-            if (e != hipSuccess) return hip_fail(e, "launch_resize_lds");
-            c.launches++;
-            if (t.poly) {
-                c.counters["resize_poly_launches"]++;
-                c.counters["poly_rows_" + std::to_string(var.rows)]++;
-            } else if (t.down)
-                c.counters["resize_down_launches"]++;
-            else
-                c.counters[var.wide ? "resize_wide_launches" : "resize_lds_launches"]++;
-            c.alg_bytes += (uint64_t)n * 4 * ((uint64_t)s0->w * s0->h + (uint64_t)size.width * size.height);
-            return KC_OK;
+        up.nt_mask = r.nt ? 0x100u : 0u;
+        e = launch_upsample(up, n, r.up, c.stream);
+    } else if (r.form == ResizeForm::two_pass) {
+        for (int i = 0; i < n && e == hipSuccess; ++i) {
+            kc_plane *tmp = nullptr;
+            KC_TRY(plane_new_mem(r.sw, r.dh, &tmp));
+            const uint32_t tpitch = (uint32_t)(tmp->pitch / 4);
+            e = launch_resize_vertical(srcs[i]->dptr, (uint32_t)(srcs[i]->pitch / 4), r.sw, tmp->dptr, tpitch, r.dh, tv->dev, c.stream);
+            if (e == hipSuccess)
+                e = launch_resize_horizontal(tmp->dptr, tpitch, dsts[i]->dptr, (uint32_t)(dsts[i]->pitch / 4), r.dw, r.dh, th->dev, c.stream);
+            plane_release(tmp);
+        }
+    } else {
+        ResizePlanes rp{};
+        for (int i = 0; i < n; ++i) {
+            rp.src[i] = srcs[i]->dptr;
+            rp.dst[i] = dsts[i]->dptr;
+            rp.spitch[i] = (uint32_t)(srcs[i]->pitch / 4);
+            rp.dpitch[i] = (uint32_t)(dsts[i]->pitch / 4);
+        }
+        Down2Args a = r.d2;
+        switch (r.form) {
+        case ResizeForm::poly2: e = launch_resize_poly2(r, rp, tv->dev, th->dev, c.stream); break;
+        case ResizeForm::down2:
+            a.vrec = tv->host.d2_vrec_dev;
+            a.hleft = th->dev.left;
+            a.hcount = th->dev.count;
+            a.hw = th->host.d2_hw_dev;
+            a.strips = th->host.d2_strips_dev;
+            e = launch_resize_down2(r, rp, a, c.stream);
+            break;
+        case ResizeForm::poly: e = launch_resize_poly(r, rp, tv->dev, th->dev, c.stream); break;
+        case ResizeForm::down: e = launch_resize_down(r, rp, tv->dev, th->dev, c.stream); break;
+        default: e = launch_resize_lds(r, rp, tv->dev, th->dev, c.stream); break;  // lds, wide
         }
     }
-    for (int i = 0; i < n; ++i) {
-        kc_plane *tmp = nullptr;
-        KC_TRY(plane_new_mem(s0->w, size.height, &tmp));
-        const uint32_t tpitch = (uint32_t)(tmp->pitch / 4);
-        hipError_t e = launch_resize_vertical(srcs[i]->dptr, (uint32_t)(srcs[i]->pitch / 4), s0->w, tmp->dptr, tpitch,
-                                              size.height, tv->dev, c.stream);
-        if (e == hipSuccess)
-            e = launch_resize_horizontal(tmp->dptr, tpitch, dsts[i]->dptr, (uint32_t)(dsts[i]->pitch / 4), size.width,
-                                         size.height, th->dev, c.stream);
-        plane_release(tmp);
-        if (e != hipSuccess) return hip_fail(e, "launch_resize two-pass");
-        c.launches += 2;
-        c.counters["resize_two_pass_launches"]++;
-        c.alg_bytes += 4 * ((uint64_t)s0->w * s0->h + 2 * (uint64_t)s0->w * size.height + (uint64_t)size.width * size.height);
-    }
+    if (e != hipSuccess) return hip_fail(e, "resize launch");
+    count_resize(r);
     return KC_OK;
-}
-
-static int resize_run(kc_plane *const *srcs, kc_plane *const *dsts, int n, int filter)
-{
-    TapsEntry *tv = nullptr, *th = nullptr;
-    KC_TRY(get_taps(srcs[0]->h, dsts[0]->h, filter, &tv));
-    KC_TRY(get_taps(srcs[0]->w, dsts[0]->w, filter, &th));
-    return resize_run_taps(srcs, dsts, n, tv, th);
 }
 
 // Row-band form of resize_image for resident planes (bands.cpp): srcs[i] holds rows src_y0 .. of a logical
@@ -777,7 +923,10 @@ int resize_force_many(kc_plane *const *planes, int n)
         }
         int s = KC_OK;
         for (int k = 0; k < g && s == KC_OK; ++k) s = plane_new_mem(group[k]->w, group[k]->h, &dsts[k]);
-        if (s == KC_OK) s = resize_run(srcs, dsts, g, group[0]->rz_filter);
+        TapsEntry *tv = nullptr, *th = nullptr;
+        if (s == KC_OK) s = get_taps(srcs[0]->h, group[0]->h, group[0]->rz_filter, &tv);
+        if (s == KC_OK) s = get_taps(srcs[0]->w, group[0]->w, group[0]->rz_filter, &th);
+        if (s == KC_OK) s = resize_run_taps(srcs, dsts, g, tv, th);
         if (s != KC_OK) {
             for (int k = 0; k < g; ++k) plane_release(dsts[k]);
             return s;
@@ -801,36 +950,30 @@ int resize_force_many(kc_plane *const *planes, int n)
 
 int resize_force(kc_plane *p) { return resize_force_many(&p, 1); }
 
-// Fused resample + chain (see kc_runtime.hpp).  Eligible: every channel's resampled operand uses
-// the same tap tables (same source size and filter), at most 4 horizontal taps (held in
-// registers), a {+,-,*} program of at most 16 steps, and an LDS tile exists.
+// Fused resample + chain (see kc_runtime.hpp).  Eligible: a {+,-,*} program of at most 16 steps, and what plan_resample
+// asks of a fused resample.
 int chain_resize_launch(const ChainProgram &P, int batch, int mode, kc_plane *const *sampled, bool *launched)
 {
     Context &c = ctx();
     *launched = false;
-    if (!c.opt.fusion || c.opt.resize_mode == 3 || mode != 0 || P.n_ops > 16 || P.n_in < 1 || P.n_in > 4) return KC_OK;
+    if (mode != 0 || P.n_ops > 16 || P.n_in < 1 || P.n_in > 4) return KC_OK;
     const kc_plane *s0 = sampled[0];
-    const kc_size size{ s0->w, s0->h };
     TapsEntry *tv = nullptr, *th = nullptr;
-    KC_TRY(get_taps(s0->rz_src->h, size.height, s0->rz_filter, &tv));
-    KC_TRY(get_taps(s0->rz_src->w, size.width, s0->rz_filter, &th));
-    UpsampleArgs ua{};
-    if (up_plan(*tv, *th, ua) && ua.H.taps <= 3) {
+    KC_TRY(get_taps(s0->rz_src->h, s0->h, s0->rz_filter, &tv));
+    KC_TRY(get_taps(s0->rz_src->w, s0->w, s0->rz_filter, &th));
+    const ResizePlan r = plan_resample(tv->host, th->host, { s0->rz_src->w, s0->rz_src->h }, { s0->w, s0->h }, batch, true, c.opt);
+    hipError_t e = hipSuccess;
+    if (r.form == ResizeForm::upsample_chain) {
         // the chain as straight-line code if that kernel has been compiled (specialize.cpp), otherwise the interpreter
         bool spec = false;
-        hipError_t e = launch_upsample_chain_specialized(P, batch, ua, c.stream, &spec);
-        if (e == hipSuccess && !spec) e = launch_upsample_chain(P, batch, ua, c.stream);
-        if (e != hipSuccess) return hip_fail(e, "launch_upsample_chain");
-        c.counters["upsample_chain_launches"]++;
-        *launched = true;
+        e = launch_upsample_chain_specialized(P, batch, r.up, c.stream, &spec);
+        if (e == hipSuccess && !spec) e = launch_upsample_chain(P, batch, r.up, c.stream);
+    } else if (r.form == ResizeForm::resize_chain) {
+        e = launch_resize_chain(r, P, tv->dev, th->dev, c.stream);
+    } else
         return KC_OK;
-    }
-    if (th->host.stride > 4) return KC_OK;
-    const TileChoice t = choose_tile(*tv, *th, size);
-    if (!t.ok) return KC_OK;
-    hipError_t e = launch_resize_chain(P, batch, size.width, size.height, tv->dev, th->dev, t.tile_w, t.tile_h, t.ncp, c.stream);
-    if (e != hipSuccess) return hip_fail(e, "launch_resize_chain");
-    c.counters["resize_chain_launches"]++;
+    if (e != hipSuccess) return hip_fail(e, "resize chain launch");
+    count_resize(r);
     *launched = true;
     return KC_OK;
 }

@@ -590,9 +590,8 @@ uint32_t chain_cache_policy(const uint32_t *refs, uint32_t n, uint64_t stream_by
     return mask;
 }
 
-uint32_t cache_policy_mask(uint64_t in_bytes, uint64_t out_bytes, uint32_t n_resident)
+uint32_t cache_policy_mask(uint64_t in_bytes, uint64_t out_bytes, uint32_t n_resident, const Options &o)
 {
-    const Options &o = options();
     if (!o.cache_policy) return 0;
     if (o.nt_force >= 0) return (uint32_t)o.nt_force & (((1u << n_resident) - 1u) | 0x100u);  // tuning: this mask for every launch
     const uint64_t budget = (uint64_t)o.cache_budget_mb << 20;

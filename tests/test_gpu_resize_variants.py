@@ -24,7 +24,7 @@ CASES = [
     # (id, filter, planes, source (w, h), destination (w, h), cache_budget_mb or None, counters that read 1)
     ("poly_rows_32", "Lanczos3", 4, (4096, 4096), (1024, 1024), None, ["resize_poly_launches", "poly_rows_32"]),
     ("poly_rows_12", "Lanczos3", 1, (4096, 4096), (1024, 1024), None, ["resize_poly_launches", "poly_rows_12"]),
-    # resize_poly2_kernel deals its bands to the XCDs whatever the budget (launch_resize_poly2): the order is the same
+    # resize_poly2_kernel deals its bands to the XCDs whatever the budget (resize.cpp, plan_poly2): the order is the same
     # at budget 0 and 208, and the plain order comes from a launch of fewer than 16 band workgroups
     ("poly2_rows_24", "Gaussian", 4, (4096, 4096), (512, 512), None, ["poly2_launches", "poly2_rows_24", "poly2_xcd_order"]),
     ("poly2_budget_0", "Gaussian", 1, (2048, 2048), (256, 256), 0, ["poly2_launches", "poly2_rows_8", "poly2_xcd_order"]),
