@@ -381,6 +381,52 @@ typedef struct kc_channel_stats {
                                    channel c; all zero without the flag */
 } kc_channel_stats;
 KC_API int kc_image_channel_stats(kc_image *img, uint32_t flags, kc_channel_stats *out);
+/* Block-compressed textures, encoded on the device: BC1 (colour), BC3 (colour and alpha), BC4 (one channel) and BC5 (two
+ * channels), the formats a GPU samples.  The blocks are a function of the RGBA8 bytes kc_image_to_u8(img, srgb) writes (Gray =
+ * (v, v, v, 1); KC_BC_SRGB: R, G, B as with srgb = 1, alpha always linear); everything after that quantisation is integer
+ * arithmetic, so the output is bit-exact.  The grid is bx = ceil(w / 4) by by = ceil(h / 4) blocks; texel t = 4y + x (x, y in
+ * 0..3) of block (i, j) is pixel (min(4i + x, w - 1), min(4j + y, h - 1)): edge blocks repeat the last column or row.
+ *   BC4 of values v_t: e0 = max, e1 = min, d = e0 - e1.  d == 0: bytes e0, e1, then six zero bytes.  Otherwise the ramp
+ *           position r = floor((14 (v - e1) + d) / (2 d)) (0..7) gives the index 0 for r == 7, 1 for r == 0 and 8 - r otherwise.
+ *           Bytes: e0, e1, then a 48-bit little-endian word with texel t's index at bits 3t..3t+2.
+ *   BC1 of texels p_t = (r, g, b): per channel lo = min, hi = max; the reference channel k has the largest hi - lo (ties: R, then
+ *           G, then B); s_c = sum_t (2 p_t,k - lo_k - hi_k)(2 p_t,c - lo_c - hi_c).  a_c = hi_c - m_c, b_c = lo_c + m_c with
+ *           m_c = (hi_c - lo_c) >> 4, swapped where s_c < 0 (the colour box's anti-diagonal).  c0 = pack(a), c1 = pack(b),
+ *           pack = q5(R) << 11 | q6(G) << 5 | q5(B), q5(x) = (31x + 127) div 255, q6(x) = (63x + 127) div 255; swapped when
+ *           c0 < c1.  E(c) expands by bit replication; the scaled palette is P0 = 3E(c0), P1 = 3E(c1), P2 = 2E(c0) + E(c1),
+ *           P3 = E(c0) + 2E(c1).  c0 == c1: every index 0; otherwise texel t's index is the j minimising
+ *           sum_c (3 p_t,c - P_j,c)^2, the lowest j on a tie.  Bytes: c0 and c1 as u16 LE, then a u32 LE with texel t's index at
+ *           bits 2t..2t+1.  A block with a non-zero index has c0 > c1: it decodes in four-colour mode, never transparent.
+ *   BC3     the BC4 block of alpha, then the BC1 block (16 bytes).  BC5: the BC4 block of R, then that of G (16 bytes).  BC1
+ *           ignores alpha; BC4 reads R only, BC5 R and G.
+ *   kc_bc_image           a caller's buffer of blocks: block (i, j) at ptr + j * row_pitch_bytes + i * block bytes.
+ *   kc_bc_image_validate  launches nothing; like kc_device_image_validate.  Arithmetic first (no kc_init needed): a known
+ *                         format, width and height > 0, bx * by <= 2^31, ptr and row_pitch_bytes multiples of the block
+ *                         bytes, row pitch >= bx * block bytes, no overflow; a failure is KC_ERR_INVALID_ARG.  Then
+ *                         `*extent_bytes` (optional) = (by - 1) * row_pitch_bytes + bx * block bytes.  Once initialised, the
+ *                         extent must lie in ONE device allocation of the library's device (KC_ERR_INVALID_ARG otherwise);
+ *                         before kc_init the call returns KC_ERR_NO_DEVICE after the arithmetic, with the extent written.
+ *   kc_image_to_bc        blocks into host memory, tightly packed rows (bx * by * block bytes; `host_bytes` at least that).
+ *                         Blocks until they are there, as kc_image_to_u8.
+ *   kc_image_to_bc_device blocks into `dst`, ordered against `hip_stream` by the two event edges of kc_image_to_device (the
+ *                         host does not wait).  kc_live_graph_buffer_bc: the same for a slot's image.
+ * Errors: flag bits other than KC_BC_SRGB, or KC_BC_SRGB with BC4 / BC5, KC_ERR_UNSUPPORTED; a NULL argument, an unknown
+ * format, a descriptor size that differs from the image's or `host_bytes` below the blocks' bytes KC_ERR_INVALID_ARG; then
+ * KC_ERR_NO_DEVICE before kc_init; kc_live_graph_buffer_bc returns KC_ERR_NO_SLOT_DATA where kc_live_graph_buffer_device does.
+ * A refused call launches nothing.  A pending chain or resample runs first; then one launch (kc_stats), constant channels
+ * included, with width * height * 4 algorithmic bytes per distinct resident plane the format reads plus the blocks' bytes.
+ * Bytes outside the blocks are never written. */
+typedef enum kc_bc_format { KC_BC1 = 1, KC_BC3 = 3, KC_BC4 = 4, KC_BC5 = 5 } kc_bc_format;
+typedef struct kc_bc_image {
+    void *ptr;               /* device memory of the library's device */
+    uint32_t width, height;  /* the image's pixels */
+    int32_t format;          /* kc_bc_format; block bytes 8 (BC1, BC4) or 16 (BC3, BC5) */
+    size_t row_pitch_bytes;  /* distance between block rows */
+} kc_bc_image;
+#define KC_BC_SRGB 1u        /* BC1 / BC3: R, G, B as kc_image_to_u8 with srgb = 1 writes them; alpha linear */
+KC_API int kc_bc_image_validate(const kc_bc_image *d, size_t *extent_bytes);
+KC_API int kc_image_to_bc(kc_image *img, int format, uint32_t flags, uint8_t *host, size_t host_bytes);
+KC_API int kc_image_to_bc_device(kc_image *img, const kc_bc_image *dst, uint32_t flags, void *hip_stream);
 /* read_slot_image, src/shared.rs:218-261 (PNG only; decode on host, planes built on device). */
 KC_API int kc_image_read_png(const char *path, kc_image **out);
 KC_API int kc_image_write_png(kc_image *img, const char *path);        /* src/node/write.rs:5-21 */
@@ -482,6 +528,8 @@ KC_API int kc_live_graph_buffer_device(kc_live_graph *lg, uint32_t node_id, uint
 /* kc_image_channel_stats of a slot's image */
 KC_API int kc_live_graph_buffer_channel_stats(kc_live_graph *lg, uint32_t node_id, uint32_t slot_id, uint32_t flags,
                                               kc_channel_stats *out);
+KC_API int kc_live_graph_buffer_bc(kc_live_graph *lg, uint32_t node_id, uint32_t slot_id, const kc_bc_image *dst,
+                                   uint32_t flags, void *hip_stream); /* kc_image_to_bc_device of a slot's image */
 KC_API int kc_live_graph_embed_slot_data_with_id(kc_live_graph *lg, kc_image *image, uint32_t slot_id, uint32_t embed_id); /* :324-341 */
 KC_API int kc_live_graph_add_input_slot_data(kc_live_graph *lg, uint32_t node_id, uint32_t slot_id, kc_image *image);     /* :347-350 */
 KC_API int kc_live_graph_changed_consume(kc_live_graph *lg, uint32_t *ids, uint32_t cap, uint32_t *count);               /* :156-160 */

@@ -57,6 +57,10 @@ class kc_channel_stats(C.Structure):
                 ("nan_count", C.c_uint64 * 4), ("histogram", (C.c_uint64 * 256) * 4)]
 
 
+class kc_bc_image(C.Structure):
+    _fields_ = [("ptr", c_vp), ("width", C.c_uint32), ("height", C.c_uint32), ("format", C.c_int32), ("row_pitch_bytes", C.c_size_t)]
+
+
 # name -> (restype, argtypes); every symbol include/kanter_core_amd.h declares.
 SIGNATURES = {
     "kc_init": (C.c_int, [C.c_int]),
@@ -148,6 +152,9 @@ SIGNATURES = {
     "kc_image_from_device": (C.c_int, [C.POINTER(kc_device_image), C.c_uint32, c_vp, C.POINTER(c_vp)]),
     "kc_image_to_device": (C.c_int, [c_vp, C.POINTER(kc_device_image), C.c_uint32, c_vp]),
     "kc_image_channel_stats": (C.c_int, [c_vp, C.c_uint32, C.POINTER(kc_channel_stats)]),
+    "kc_bc_image_validate": (C.c_int, [C.POINTER(kc_bc_image), C.POINTER(C.c_size_t)]),
+    "kc_image_to_bc": (C.c_int, [c_vp, C.c_int, C.c_uint32, c_vp, C.c_size_t]),
+    "kc_image_to_bc_device": (C.c_int, [c_vp, C.POINTER(kc_bc_image), C.c_uint32, c_vp]),
     "kc_image_from_f32": (C.c_int, [C.POINTER(c_vp), C.c_int, C.c_uint32, C.c_uint32, C.POINTER(c_vp)]),
     "kc_image_to_f32": (C.c_int, [c_vp, C.POINTER(c_vp), C.c_int]),
     "kc_image_read_png": (C.c_int, [C.c_char_p, C.POINTER(c_vp)]),
@@ -212,6 +219,7 @@ SIGNATURES = {
     "kc_live_graph_buffer_rgba": (C.c_int, [c_vp, C.c_uint32, C.c_uint32, C.c_int, c_vp]),
     "kc_live_graph_buffer_device": (C.c_int, [c_vp, C.c_uint32, C.c_uint32, C.POINTER(kc_device_image), C.c_uint32, c_vp]),
     "kc_live_graph_buffer_channel_stats": (C.c_int, [c_vp, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(kc_channel_stats)]),
+    "kc_live_graph_buffer_bc": (C.c_int, [c_vp, C.c_uint32, C.c_uint32, C.POINTER(kc_bc_image), C.c_uint32, c_vp]),
     "kc_live_graph_embed_slot_data_with_id": (C.c_int, [c_vp, c_vp, C.c_uint32, C.c_uint32]),
     "kc_live_graph_add_input_slot_data": (C.c_int, [c_vp, C.c_uint32, C.c_uint32, c_vp]),
     "kc_live_graph_changed_consume": (C.c_int, [c_vp, c_u32p, C.c_uint32, c_u32p]),

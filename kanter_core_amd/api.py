@@ -623,6 +623,37 @@ def _device_export(call, size, dtype, layout, channels, srgb, out):
     return out
 
 
+BC_SRGB = 1  # kc_image_to_bc: BC1 / BC3 colour as to_u8_srgb writes it (alpha linear)
+BC_BLOCK_BYTES = {1: 8, 3: 16, 4: 8, 5: 16}  # kc_bc_format -> bytes per 4 x 4 block
+
+
+def _bc_format(fmt):
+    """1, 3, 4, 5 or "bc1" / "BC3" / ... -> kc_bc_format"""
+    f = int(str(fmt).lower().lstrip("bc")) if isinstance(fmt, str) else int(fmt)
+    if f not in BC_BLOCK_BYTES:
+        raise ValueError("BC format must be 1, 3, 4 or 5, not %r" % (fmt,))
+    return f
+
+
+def _bc_export(call, size, fmt, srgb, out):
+    """Allocates (or takes) a uint8 (by, bx, block bytes) tensor and runs `call(desc, flags, stream)` into it.  `out` may be any
+    view whose last two dimensions are contiguous (rows of blocks anywhere, e.g. a slice of a larger tensor)."""
+    import torch
+    f = _bc_format(fmt)
+    bb = BC_BLOCK_BYTES[f]
+    bx, by = (size.width + 3) // 4, (size.height + 3) // 4
+    if out is None:
+        out = torch.empty((by, bx, bb), dtype=torch.uint8, device=torch.device("cuda", torch.cuda.current_device()))
+    if out.dtype != torch.uint8 or tuple(out.shape) != (by, bx, bb):
+        raise ValueError("out must be uint8 of shape %s, got %s %s" % ((by, bx, bb), out.dtype, tuple(out.shape)))
+    if (bx > 1 and out.stride(1) != bb) or out.stride(2) != 1:
+        raise ValueError("out needs each block row packed: strides (..., %d, 1), got %s" % (bb, out.stride()))
+    pitch = out.stride(0) if by > 1 else bx * bb
+    d = _lib.kc_bc_image(out.data_ptr(), size.width, size.height, f, pitch)
+    _check(_on_torch_stream(out, lambda stream: call(C.byref(d), BC_SRGB if srgb else 0, stream)))
+    return out
+
+
 STATS_HISTOGRAM = 1  # kc_image_channel_stats: also the u8 histograms
 STATS_SRGB = 2       # ... binned as to_u8_srgb (R, G, B; alpha linear)
 
@@ -736,6 +767,20 @@ class SlotImage:
         tensor) is written instead of a new tensor; its dtype and shape then decide.  Ready on torch's current stream."""
         return _device_export(lambda d, f, s: _lib.load().kc_image_to_device(self._h, d, f, s), self.size(), dtype, layout, channels,
                               srgb, out)
+
+    def to_bc(self, fmt, srgb=False):
+        """-> uint8 (ceil(h/4), ceil(w/4), block bytes): the image's BC1, BC3, BC4 or BC5 blocks (kc_image_to_bc), encoded on the
+        device from the RGBA8 bytes to_u8(srgb) writes; srgb is for BC1 and BC3 only."""
+        f = _bc_format(fmt)
+        s = self.size()
+        out = np.empty(((s.height + 3) // 4, (s.width + 3) // 4, BC_BLOCK_BYTES[f]), np.uint8)
+        _check(_lib.load().kc_image_to_bc(self._h, f, BC_SRGB if srgb else 0, out.ctypes.data, out.nbytes))
+        return out
+
+    def to_bc_torch(self, fmt, srgb=False, out=None):
+        """to_bc into a uint8 tensor (ceil(h/4), ceil(w/4), block bytes) in device memory (kc_image_to_bc_device); `out` (any view
+        whose last two dimensions are contiguous) is written instead of a new tensor.  Ready on torch's current stream."""
+        return _bc_export(lambda d, f, st: _lib.load().kc_image_to_bc_device(self._h, d, f, st), self.size(), fmt, srgb, out)
 
     def channel_stats(self, histogram=False, srgb=False):
         """-> ChannelStats of the image, computed on the device (kc_image_channel_stats): the range and NaN count of every
@@ -1087,6 +1132,11 @@ class LiveGraph:
         """buffer_rgba into a tensor in device memory (kc_live_graph_buffer_device); arguments as SlotImage.to_torch."""
         return _device_export(lambda d, f, s: _lib.load().kc_live_graph_buffer_device(self._h, node_id, slot_id, d, f, s),
                               self.slot_data_size(node_id, slot_id), dtype, layout, channels, srgb, out)
+
+    def buffer_bc_torch(self, node_id, slot_id, fmt, srgb=False, out=None):
+        """SlotImage.to_bc_torch of a slot's image (kc_live_graph_buffer_bc)."""
+        return _bc_export(lambda d, f, st: _lib.load().kc_live_graph_buffer_bc(self._h, node_id, slot_id, d, f, st),
+                          self.slot_data_size(node_id, slot_id), fmt, srgb, out)
 
     def buffer_channel_stats(self, node_id, slot_id, histogram=False, srgb=False):
         """SlotImage.channel_stats of a slot's image (kc_live_graph_buffer_channel_stats)."""

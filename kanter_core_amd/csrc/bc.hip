@@ -1,0 +1,315 @@
+// Block compression (kc_image_to_bc / kc_image_to_bc_device, bc.cpp): the image as kc_image_to_u8 writes it -> BC1, BC3, BC4 or
+// BC5 blocks, by the integer rules of include/kanter_core_amd.h (tests/bc_ref.py is the same rules in numpy).  An HBM-bound
+// stream in the form of to_u8_kernel: one thread per 4x4 block, a grid-stride loop over the blocks in row order, so the lanes of
+// a wave take consecutive blocks of a block row and each of the block's four pixel rows is one 16-byte load per plane and lane,
+// contiguous across the wave (the library's planes, kc_plane_wrap's included, are readable in whole float4 quads).  The texels
+// are quantised as they arrive and kept as RGBA8 words; the encoder is integer arithmetic on them; a block leaves in one 8- or
+// 16-byte store.
+#include "kc_internal.hpp"
+
+namespace kc {
+
+#include "streaming.h"  // grid_cap, ld_policy, quant_u8 / quant_u8_srgb: shared with kernels.hip
+
+typedef float bc_f4 __attribute__((ext_vector_type(4)));
+typedef uint32_t bc_u4 __attribute__((ext_vector_type(4)));
+typedef uint32_t bc_u2 __attribute__((ext_vector_type(2)));
+typedef int16_t bc_s2 __attribute__((ext_vector_type(2)));
+typedef uint16_t bc_h2 __attribute__((ext_vector_type(2)));
+
+// The channels a format reads: bit c = channel c (R, G, B, A)
+static constexpr uint32_t bc_channels(int fmt) { return fmt == 1 ? 0x7u : fmt == 3 ? 0xfu : fmt == 4 ? 0x1u : 0x3u; }
+
+template <bool NT>
+static __device__ __forceinline__ bc_f4 bc_load(const Operand &o, uint32_t row, uint32_t q)
+{
+    if (o.ptr == nullptr) return bc_f4{ o.c, o.c, o.c, o.c };  // a constant plane: no memory read
+    return ld_policy<NT>(reinterpret_cast<const bc_f4 *>(o.ptr + (size_t)row * o.pitch + 4 * q));
+}
+
+template <bool SRGB>
+static __device__ __forceinline__ uint32_t bc_quant(float v, int c, const uint32_t *srgb_tab)
+{
+    return (SRGB && c < 3) ? quant_u8_srgb(v, srgb_tab) : quant_u8(v);  // alpha stays linear
+}
+
+// BC4 of the 16-bit lane at bit `sh` (0 or 16) of the 16 texel words: e0 = max, e1 = min; ramp r = floor((14 (v - e1) + d) / 2d)
+// by the exact reciprocal m = ceil(2^21 / 2d) (x = 14 (v - e1) + d < 3826 and the rounding error of m below 2d keep x m >> 21
+// exact, and x m < 2^32 in a 24-bit multiply); index = 1, 7, 6, 5, 4, 3, 2, 0 for r = 0..7.
+static __device__ __forceinline__ bc_u2 encode_bc4(const uint32_t (&wd)[16], uint32_t sh)
+{
+    uint32_t e0 = 0u, e1 = 255u;
+#pragma unroll
+    for (int t = 0; t < 16; ++t) {
+        const uint32_t v = __builtin_amdgcn_ubfe(wd[t], sh, 16u);
+        e0 = max(e0, v);
+        e1 = min(e1, v);
+    }
+    const uint32_t d = e0 - e1;
+    uint32_t lo = e0 | (e1 << 8), hi = 0u;  // bytes 0..3 and 4..7 of the block
+    if (d != 0u) {
+        const uint32_t m = (0x200000u + 2u * d - 1u) / (2u * d);
+        constexpr uint32_t kIndex = 1u | 7u << 3 | 6u << 6 | 5u << 9 | 4u << 12 | 3u << 15 | 2u << 18;  // r = 7: 0
+#pragma unroll
+        for (int t = 0; t < 16; ++t) {
+            const uint32_t v = __builtin_amdgcn_ubfe(wd[t], sh, 16u);
+            const uint32_t x = __umul24(14u, v - e1) + d;
+            const uint32_t r = __umul24(x, m) >> 21;
+            const uint32_t idx = __builtin_amdgcn_ubfe(kIndex, 3u * r, 3u);
+            // the 48 index bits start at bit 16 of the block
+            const int b = 16 + 3 * t;
+            if (b + 3 <= 32) lo |= idx << b;
+            else if (b >= 32) hi |= idx << (b - 32);
+            else {
+                lo |= idx << b;
+                hi |= idx >> (32 - b);
+            }
+        }
+    }
+    return bc_u2{ lo, hi };
+}
+
+static __device__ __forceinline__ uint32_t pack565(uint32_t r, uint32_t g, uint32_t b)
+{
+    return ((31u * r + 127u) / 255u) << 11 | ((63u * g + 127u) / 255u) << 5 | ((31u * b + 127u) / 255u);
+}
+
+static __device__ __forceinline__ bc_s2 as_s2(uint32_t x) { return __builtin_bit_cast(bc_s2, x); }
+static __device__ __forceinline__ bc_h2 as_h2(uint32_t x) { return __builtin_bit_cast(bc_h2, x); }
+
+// BC1 of texels held as rb = R | B << 16 and ga = G | A << 16 (alpha ignored), so that the channel ranges are packed 16-bit
+// min / max and the sums over channels 16-bit dot products.  Endpoints: the colour box inset by 1/16 of each range, on the
+// diagonal the covariance signs against the channel of the largest range choose (s_c = 2 sum a p_c - S_c sum a with
+// a = 2 p_k - S_k, S = lo + hi).  Indices: the palette P_j = 3 E0 + k_j D (D = E1 - E0, k = 0, 3, 1, 2 for j = 0..3) lies on
+// one line, so |3p - P_j|^2 = |3p - 3E0|^2 - 6 k v + k^2 L with v = (p - E0).D and L = |D|^2, and the nearest k is the number of
+// thresholds 6v > L, 6v > 3L, 6v >= 5L that v passes (the last one >= : the tie of k = 2 and 3 goes to j = 1, the lower index)
+// -- the contract's arg-min, without computing the four distances.
+static __device__ __forceinline__ bc_u2 encode_bc1(const uint32_t (&rb)[16], const uint32_t (&ga)[16])
+{
+    bc_h2 lrb = as_h2(rb[0]), hrb = lrb, lga = as_h2(ga[0]), hga = lga;
+#pragma unroll
+    for (int t = 1; t < 16; ++t) {
+        lrb = __builtin_elementwise_min(lrb, as_h2(rb[t]));
+        hrb = __builtin_elementwise_max(hrb, as_h2(rb[t]));
+        lga = __builtin_elementwise_min(lga, as_h2(ga[t]));
+        hga = __builtin_elementwise_max(hga, as_h2(ga[t]));
+    }
+    const uint32_t lo[3] = { lrb.x, lga.x, lrb.y }, hi[3] = { hrb.x, hga.x, hrb.y };
+    const uint32_t rr = hi[0] - lo[0], rg = hi[1] - lo[1], rb_ = hi[2] - lo[2];
+    const uint32_t k = (rr >= rg && rr >= rb_) ? 0u : (rg >= rb_ ? 1u : 2u);
+    const int32_t sk = (int32_t)(k == 0u ? lo[0] + hi[0] : k == 1u ? lo[1] + hi[1] : lo[2] + hi[2]);
+    const uint32_t ksh = k == 2u ? 16u : 0u;
+    int32_t sa = 0, sr = 0, sg = 0, sb = 0;
+#pragma unroll
+    for (int t = 0; t < 16; ++t) {
+        const int32_t a = 2 * (int32_t)__builtin_amdgcn_ubfe(k == 1u ? ga[t] : rb[t], ksh, 16u) - sk;  // -510..510
+        sa += a;
+        const uint32_t alo = (uint32_t)a & 0xffffu, ahi = (uint32_t)a << 16;
+        sr = __builtin_amdgcn_sdot2(as_s2(rb[t]), as_s2(alo), sr, false);
+        sb = __builtin_amdgcn_sdot2(as_s2(rb[t]), as_s2(ahi), sb, false);
+        sg = __builtin_amdgcn_sdot2(as_s2(ga[t]), as_s2(alo), sg, false);
+    }
+    const int32_t s[3] = { 2 * sr - (int32_t)(lo[0] + hi[0]) * sa, 2 * sg - (int32_t)(lo[1] + hi[1]) * sa,
+                           2 * sb - (int32_t)(lo[2] + hi[2]) * sa };
+    uint32_t ea[3], eb[3];
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+        const uint32_t m = (hi[c] - lo[c]) >> 4;
+        const uint32_t a = hi[c] - m, b = lo[c] + m;
+        ea[c] = s[c] < 0 ? b : a;  // s_k >= 0: the reference channel keeps its direction
+        eb[c] = s[c] < 0 ? a : b;
+    }
+    uint32_t c0 = pack565(ea[0], ea[1], ea[2]), c1 = pack565(eb[0], eb[1], eb[2]);
+    if (c0 < c1) {
+        const uint32_t tmp = c0;
+        c0 = c1;
+        c1 = tmp;
+    }
+    uint32_t word = 0u;
+    if (c0 != c1) {
+        const int32_t r5 = (int32_t)(c0 >> 11), g6 = (int32_t)((c0 >> 5) & 63u), b5 = (int32_t)(c0 & 31u);
+        const int32_t s5 = (int32_t)(c1 >> 11), h6 = (int32_t)((c1 >> 5) & 63u), c5 = (int32_t)(c1 & 31u);
+        const int32_t E0[3] = { (r5 << 3) | (r5 >> 2), (g6 << 2) | (g6 >> 4), (b5 << 3) | (b5 >> 2) };
+        const int32_t E1[3] = { (s5 << 3) | (s5 >> 2), (h6 << 2) | (h6 >> 4), (c5 << 3) | (c5 >> 2) };
+        const int32_t D[3] = { E1[0] - E0[0], E1[1] - E0[1], E1[2] - E0[2] };
+        const int32_t L = D[0] * D[0] + D[1] * D[1] + D[2] * D[2];
+        const int32_t L3 = 3 * L, L5 = 5 * L;
+        const int32_t e0d = -(E0[0] * D[0] + E0[1] * D[1] + E0[2] * D[2]);
+        const bc_s2 drb = as_s2(((uint32_t)D[0] & 0xffffu) | ((uint32_t)D[2] << 16)), dg = as_s2((uint32_t)D[1] & 0xffffu);
+#pragma unroll
+        for (int t = 0; t < 16; ++t) {
+            const int32_t v = __builtin_amdgcn_sdot2(as_s2(ga[t]), dg, __builtin_amdgcn_sdot2(as_s2(rb[t]), drb, e0d, false), false);
+            const int32_t v6 = 6 * v;
+            const uint32_t kk = (uint32_t)(v6 > L) + (uint32_t)(v6 > L3) + (uint32_t)(v6 >= L5);
+            word |= __builtin_amdgcn_ubfe(0x78u, 2u * kk, 2u) << (2 * t);  // k = 0, 1, 2, 3 -> j = 0, 2, 3, 1
+        }
+    }
+    return bc_u2{ c0 | (c1 << 16), word };
+}
+
+struct BcBlockArgs {
+    char *dst;
+    uint64_t row_pitch;  // bytes between block rows
+    uint32_t w, h, bx, by;
+};
+
+// Row y of a block's texels, raw: a 16-byte load per channel the format reads (Gray: the plane once, for R; a constant: none)
+template <int FMT, bool NT>
+static __device__ __forceinline__ void bc_load_row(const Operand (&op)[4], int gray, const BcBlockArgs &a, uint32_t i, uint32_t j, int y,
+                                                   bool wave_edge, bc_f4 (&v)[4])
+{
+    constexpr uint32_t CH = bc_channels(FMT);
+    uint32_t row = 4 * j + y;
+    if (wave_edge) row = min(row, a.h - 1);  // bottom edge blocks repeat the last row
+#pragma unroll
+    for (int c = 0; c < 4; ++c) {
+        if (!((CH >> c) & 1u)) continue;
+        if (gray && c > 0 && c < 3) continue;
+        v[c] = bc_load<NT>(op[c], row, i);
+    }
+}
+
+// ... quantised to 8 bits and packed as rb = R | B << 16, ga = G | A << 16 (Gray: (v, v, v, A))
+template <int FMT, bool SRGB>
+static __device__ __forceinline__ void bc_quantise_row(const bc_f4 (&v)[4], int gray, int y, const uint32_t *srgb_tab, uint32_t (&rb)[16],
+                                                       uint32_t (&ga)[16])
+{
+    constexpr uint32_t CH = bc_channels(FMT);
+#pragma unroll
+    for (int x = 0; x < 4; ++x) {
+        const uint32_t r = bc_quant<SRGB>(v[0][x], 0, srgb_tab);
+        uint32_t g = 0u, b = 0u, al = 0u;
+        if constexpr ((CH & 2u) != 0) g = gray ? r : bc_quant<SRGB>(v[1][x], 1, srgb_tab);
+        if constexpr ((CH & 4u) != 0) b = gray ? r : bc_quant<SRGB>(v[2][x], 2, srgb_tab);
+        if constexpr ((CH & 8u) != 0) al = quant_u8(v[3][x]);
+        rb[4 * y + x] = r | (b << 16);
+        ga[4 * y + x] = g | (al << 16);
+    }
+}
+
+// Right edge blocks: the columns past the width repeat the last one
+static __device__ __forceinline__ void bc_clamp_columns(const BcBlockArgs &a, uint32_t i, uint32_t (&rb)[16], uint32_t (&ga)[16])
+{
+    const uint32_t last = min(a.w - 1 - 4 * i, 3u);
+#pragma unroll
+    for (int y = 0; y < 4; ++y)
+#pragma unroll
+        for (int x = 1; x < 4; ++x)
+            if ((uint32_t)x > last) {
+                rb[4 * y + x] = rb[4 * y + x - 1];
+                ga[4 * y + x] = ga[4 * y + x - 1];
+            }
+}
+
+template <int FMT>
+static __device__ __forceinline__ void bc_encode_store(const uint32_t (&rb)[16], const uint32_t (&ga)[16], const BcBlockArgs &a, uint32_t i,
+                                                       uint32_t j)
+{
+    char *p = a.dst + (size_t)j * a.row_pitch;
+    if constexpr (FMT == 1) {
+        *reinterpret_cast<bc_u2 *>(p + (size_t)i * 8) = encode_bc1(rb, ga);
+    } else if constexpr (FMT == 4) {
+        *reinterpret_cast<bc_u2 *>(p + (size_t)i * 8) = encode_bc4(rb, 0u);
+    } else {
+        const bc_u2 x = FMT == 3 ? encode_bc4(ga, 16u) : encode_bc4(rb, 0u);
+        const bc_u2 y = FMT == 3 ? encode_bc1(rb, ga) : encode_bc4(ga, 0u);
+        *reinterpret_cast<bc_u4 *>(p + (size_t)i * 16) = bc_u4{ x.x, x.y, y.x, y.y };
+    }
+}
+
+template <int FMT, bool SRGB, bool NT>  // NT: the planes are read once and do not fit the Infinity Cache (cache_policy_mask)
+__global__ __launch_bounds__(256) void bc_encode_kernel(Operand r, Operand g, Operand b, Operand al, int gray, const BcBlockArgs a)
+{
+    __shared__ uint32_t srgb_t[SRGB ? 257 : 1];
+    const Operand op[4] = { r, g, b, al };
+    const uint32_t total = a.bx * a.by;
+    // edge blocks: the last block column when the width is not a multiple of 4, the last block row likewise
+    const uint32_t edge_i = (a.w & 3u) ? a.bx - 1 : 0xffffffffu, edge_j = (a.h & 3u) ? a.by - 1 : 0xffffffffu;
+    uint32_t idx = blockIdx.x * 256u + threadIdx.x;
+    auto block_of = [&](uint32_t n, uint32_t &i, uint32_t &j, bool &wave_edge) {
+        j = n / a.bx;
+        i = n - j * a.bx;
+        // wave-uniform: a wave that holds no edge block skips the clamps
+        wave_edge = __any(n < total && (i == edge_i || j == edge_j)) != 0;
+    };
+    if constexpr (SRGB) {
+        // The first block's first row of loads goes out BEFORE the threshold table is staged (a global read and a barrier that
+        // every thread of the workgroup takes, in range or not), as in to_u8_kernel: the table arrives while they are in flight.
+        const bool in_range = idx < total;
+        uint32_t i = 0u, j = 0u;
+        bool we = false;
+        block_of(in_range ? idx : 0u, i, j, we);
+        bc_f4 v[4];
+        if (in_range) bc_load_row<FMT, NT>(op, gray, a, i, j, 0, we, v);
+        srgb_t[threadIdx.x] = kSrgbThresholdBits[threadIdx.x];  // 256 threads
+        if (threadIdx.x == 0) srgb_t[256] = 0xffffffffu;         // sentinel: nothing is >= it
+        __syncthreads();
+        if (!in_range) return;
+        uint32_t rb[16], ga[16];
+        bc_quantise_row<FMT, SRGB>(v, gray, 0, srgb_t, rb, ga);
+#pragma unroll
+        for (int y = 1; y < 4; ++y) {
+            bc_load_row<FMT, NT>(op, gray, a, i, j, y, we, v);
+            bc_quantise_row<FMT, SRGB>(v, gray, y, srgb_t, rb, ga);
+        }
+        if (we) bc_clamp_columns(a, i, rb, ga);
+        bc_encode_store<FMT>(rb, ga, a, i, j);
+        idx += gridDim.x * 256u;
+    }
+    for (; idx < total; idx += gridDim.x * 256u) {
+        uint32_t i, j;
+        bool we;
+        block_of(idx, i, j, we);
+        uint32_t rb[16], ga[16];
+#pragma unroll
+        for (int y = 0; y < 4; ++y) {
+            bc_f4 v[4];
+            bc_load_row<FMT, NT>(op, gray, a, i, j, y, we, v);
+            bc_quantise_row<FMT, SRGB>(v, gray, y, srgb_t, rb, ga);
+        }
+        if (we) bc_clamp_columns(a, i, rb, ga);
+        bc_encode_store<FMT>(rb, ga, a, i, j);
+    }
+}
+
+hipError_t launch_bc_encode(int fmt, int srgb, const Operand op[4], int gray, char *dst, uint64_t row_pitch, uint32_t w, uint32_t h,
+                            uint32_t nt_mask, hipStream_t s)
+{
+    BcBlockArgs a;
+    a.dst = dst;
+    a.row_pitch = row_pitch;
+    a.w = w;
+    a.h = h;
+    a.bx = (w + 3) / 4;
+    a.by = (h + 3) / 4;
+    const uint64_t total = (uint64_t)a.bx * a.by;
+    if (total == 0) return hipSuccess;
+    uint64_t blocks = (total + 255) / 256;
+    if (blocks > grid_cap(1u << 30)) blocks = grid_cap(1u << 30);
+    const bool nt = (nt_mask & 0xffu) != 0;
+    if (srgb && fmt != 1 && fmt != 3) return hipErrorInvalidValue;
+#define KC_BC(F, SR, NTL) bc_encode_kernel<F, SR, NTL><<<dim3((unsigned)blocks), 256, 0, s>>>(op[0], op[1], op[2], op[3], gray, a)
+#define KC_BC_NT(F, SR)                                                                                                               \
+    do {                                                                                                                             \
+        if (nt) KC_BC(F, SR, true);                                                                                                  \
+        else KC_BC(F, SR, false);                                                                                                    \
+    } while (0)
+    switch (fmt) {
+    case KC_BC1:
+        if (srgb) KC_BC_NT(KC_BC1, true);
+        else KC_BC_NT(KC_BC1, false);
+        break;
+    case KC_BC3:
+        if (srgb) KC_BC_NT(KC_BC3, true);
+        else KC_BC_NT(KC_BC3, false);
+        break;
+    case KC_BC4: KC_BC_NT(KC_BC4, false); break;
+    case KC_BC5: KC_BC_NT(KC_BC5, false); break;
+    default: return hipErrorInvalidValue;
+    }
+#undef KC_BC_NT
+#undef KC_BC
+    return hipGetLastError();
+}
+
+}  // namespace kc

@@ -740,6 +740,28 @@ try {
 }
 KC_CATCH
 
+int kc_bc_image_validate(const kc_bc_image *d, size_t *extent_bytes)
+try {
+    KC_ARG(d);
+    return bc_image_validate(d, extent_bytes);
+}
+KC_CATCH
+
+int kc_image_to_bc(kc_image *img, int format, uint32_t flags, uint8_t *host, size_t host_bytes)
+try {
+    Lock api_lock(ctx().mu);  // reference counts are plain integers, see kc_plane::refs
+    return image_to_bc(img, format, flags, host, host_bytes);  // the flags, the arguments, then need_init()
+}
+KC_CATCH
+
+int kc_image_to_bc_device(kc_image *img, const kc_bc_image *dst, uint32_t flags, void *hip_stream)
+try {
+    Lock api_lock(ctx().mu);  // reference counts are plain integers, see kc_plane::refs
+    KC_ARG(img && dst);
+    return image_to_bc_device(img, dst, flags, hip_stream);
+}
+KC_CATCH
+
 int kc_image_channel_stats(kc_image *img, uint32_t flags, kc_channel_stats *out)
 try {
     Lock api_lock(ctx().mu);  // reference counts are plain integers, see kc_plane::refs
@@ -1387,6 +1409,16 @@ try {
     const SlotData *sd = lg->find_slot(node, slot);
     if (!sd) return KC_ERR_NO_SLOT_DATA;
     return image_to_device(sd->image, dst, flags, hip_stream);
+}
+KC_CATCH
+
+int kc_live_graph_buffer_bc(kc_live_graph *lg, uint32_t node, uint32_t slot, const kc_bc_image *dst, uint32_t flags, void *hip_stream)
+try {
+    LG_LOCK(lg);
+    KC_ARG(dst);
+    const SlotData *sd = lg->find_slot(node, slot);
+    if (!sd) return KC_ERR_NO_SLOT_DATA;
+    return image_to_bc_device(sd->image, dst, flags, hip_stream);
 }
 KC_CATCH
 

@@ -47,30 +47,40 @@ static int devimage_check_arith(const kc_device_image *d, size_t *extent)
     return KC_OK;
 }
 
+// [ptr, ptr + extent) lies in one device allocation of the library's device (needs kc_init); `who` prefixes the error text
+int device_extent_check(const void *ptr, size_t ext, const char *who)
+{
+    KC_TRY(need_init());
+    Context &c = ctx();
+    auto refuse = [&](const char *what) {
+        set_error(std::string(who) + ": " + what);
+        return KC_ERR_INVALID_ARG;
+    };
+    hipPointerAttribute_t attr;
+    hipError_t e = hipPointerGetAttributes(&attr, ptr);
+    if (e != hipSuccess) {
+        (void)hipGetLastError();
+        return refuse("ptr is not memory the HIP runtime knows (a host pointer?)");
+    }
+    if (attr.type != hipMemoryTypeDevice || attr.device != c.device) return refuse("ptr is not device memory of the library's device");
+    hipDeviceptr_t base = nullptr;
+    size_t size = 0;
+    e = hipMemGetAddressRange(&base, &size, (hipDeviceptr_t)ptr);
+    if (e != hipSuccess) {
+        (void)hipGetLastError();
+        return refuse("no device allocation contains ptr");
+    }
+    const uintptr_t lo = (uintptr_t)base, p = (uintptr_t)ptr;
+    if (p < lo || p - lo > size || ext > size - (p - lo)) return refuse("the described extent runs past the end of its allocation");
+    return KC_OK;
+}
+
 int device_image_validate(const kc_device_image *d, size_t *extent_bytes)
 {
     size_t ext = 0;
     KC_TRY(devimage_check_arith(d, &ext));
     if (extent_bytes) *extent_bytes = ext;
-    KC_TRY(need_init());
-    Context &c = ctx();
-    hipPointerAttribute_t attr;
-    hipError_t e = hipPointerGetAttributes(&attr, d->ptr);
-    if (e != hipSuccess) {
-        (void)hipGetLastError();
-        return devimage_refuse("ptr is not memory the HIP runtime knows (a host pointer?)");
-    }
-    if (attr.type != hipMemoryTypeDevice || attr.device != c.device) return devimage_refuse("ptr is not device memory of the library's device");
-    hipDeviceptr_t base = nullptr;
-    size_t size = 0;
-    e = hipMemGetAddressRange(&base, &size, (hipDeviceptr_t)d->ptr);
-    if (e != hipSuccess) {
-        (void)hipGetLastError();
-        return devimage_refuse("no device allocation contains ptr");
-    }
-    const uintptr_t lo = (uintptr_t)base, p = (uintptr_t)d->ptr;
-    if (p < lo || p - lo > size || ext > size - (p - lo)) return devimage_refuse("the described extent runs past the end of its allocation");
-    return KC_OK;
+    return device_extent_check(d->ptr, ext, "kc_device_image");
 }
 
 // vec: the pointer and the pitches allow the widest access of a whole pixel quad (devimage.hip: 16, 8 or 4 bytes for a
@@ -101,7 +111,7 @@ static DevImageArgs devimage_args(const kc_device_image *d)
 
 // The library's stream waits for what `hip_stream` holds now (before the conversion) / `hip_stream` waits for the conversion
 // (after it).  The events are released at once; the runtime keeps them until they have fired.
-static int stream_edge(hipStream_t from, hipStream_t to)
+int stream_edge(hipStream_t from, hipStream_t to)
 {
     hipEvent_t ev = nullptr;
     KC_HIP(hipEventCreateWithFlags(&ev, hipEventDisableTiming));

@@ -275,6 +275,11 @@ struct StatsArgs {
 hipError_t launch_channel_stats(const StatsArgs &a, bool hist, bool srgb, bool nt, uint32_t groups, hipStream_t s);
 // workgroups of that launch for a w x h image on a device of `cus` CUs (>= 1)
 uint32_t channel_stats_groups(uint32_t w, uint32_t h, bool hist, bool srgb, uint32_t cus);
+// Block compression (bc.hip / bc.cpp): bc_encode_kernel<fmt, srgb, nt> writes the ceil(w/4) x ceil(h/4) blocks of format `fmt`
+// (kc_bc_format) at dst, block rows row_pitch bytes apart; channel c is op[c]; gray != 0: op[0] stands for R, G and B (read
+// once); nt_mask bits 0-7: nontemporal plane loads; srgb: BC1 and BC3 only
+hipError_t launch_bc_encode(int fmt, int srgb, const Operand op[4], int gray, char *dst, uint64_t row_pitch, uint32_t w, uint32_t h,
+                            uint32_t nt_mask, hipStream_t s);
 hipError_t launch_from_u8(const uint8_t *src, int channels, uint32_t w, uint32_t h, float *const planes[4],
                           uint32_t pitch, uint32_t nt_mask, hipStream_t s);
 

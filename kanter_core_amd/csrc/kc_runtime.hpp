@@ -339,6 +339,14 @@ int image_to_u8(kc_image *img, bool srgb, uint8_t *host);
 int device_image_validate(const kc_device_image *d, size_t *extent_bytes);
 int image_from_device(const kc_device_image *src, uint32_t flags, void *hip_stream, kc_image **out);
 int image_to_device(kc_image *img, const kc_device_image *dst, uint32_t flags, void *hip_stream);
+// [ptr, ptr + ext) lies in one device allocation of the library's device (KC_ERR_NO_DEVICE before kc_init, KC_ERR_INVALID_ARG
+// otherwise, with `who` in the error text); stream_edge: `to` waits for the work already enqueued on `from`
+int device_extent_check(const void *ptr, size_t ext, const char *who);
+int stream_edge(hipStream_t from, hipStream_t to);
+// block compression (bc.cpp): the bodies of kc_bc_image_validate / kc_image_to_bc / kc_image_to_bc_device
+int bc_image_validate(const kc_bc_image *d, size_t *extent_bytes);
+int image_to_bc(kc_image *img, int format, uint32_t flags, uint8_t *host, size_t host_bytes);
+int image_to_bc_device(kc_image *img, const kc_bc_image *dst, uint32_t flags, void *hip_stream);
 // per-channel statistics (stats.cpp): the body of kc_image_channel_stats; the context's buffers, released at kc_shutdown
 int image_channel_stats(kc_image *img, uint32_t flags, kc_channel_stats *out);
 void channel_stats_release();

@@ -1,0 +1,125 @@
+"""Block compression at 4096^2 (csrc/bc.hip): kernel time, algorithmic bytes and the fraction of 8 TB/s per case -- Gray BC4;
+RGBA BC1, BC1 sRGB, BC3, BC3 sRGB, BC4 and BC5; random data and a uniform image (every block takes the d == 0 / c0 == c1 path)
+-- with kc_image_to_device U8 of the same images beside them as the yardstick, and the wall-clock of kc_image_to_bc against
+kc_image_to_u8 plus the numpy reference encoder (tests/bc_ref.py) for the same blocks.
+
+    python profiles/bc_times.py run [reps]          (on the GPU box; wall-clock, bytes per call)
+    rocprofv3 --kernel-trace --output-format csv -d DIR -- python profiles/bc_times.py run [reps]
+    python profiles/bc_times.py report DIR/.../*_kernel_trace.csv run.log    -> the table (bc_times.txt)
+
+The cases run in a fixed order, each as one warm-up call and `reps` timed calls, so the report assigns the trace's dispatches to
+the cases by their order.
+"""
+import csv
+import os
+import statistics
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+N = 4096
+PEAK_TBS = 8.0
+PX = N * N
+BLOCK_BYTES = {1: 8, 3: 16, 4: 8, 5: 16}
+PLANES = {1: 3, 3: 4, 4: 1, 5: 2}  # RGBA planes each format reads
+# (name, channels, data, kind, fmt, srgb); kind "bc" or "u8" (kc_image_to_device U8, the yardstick)
+CASES = []
+for _data in ("random", "uniform"):
+    CASES.append(("Gray BC4 %s" % _data, 1, _data, "bc", 4, False))
+    for _fmt, _srgb in ((1, False), (1, True), (3, False), (3, True), (4, False), (5, False)):
+        CASES.append(("RGBA BC%d%s %s" % (_fmt, " sRGB" if _srgb else "", _data), 4, _data, "bc", _fmt, _srgb))
+    CASES.append(("RGBA to_device U8 %s" % _data, 4, _data, "u8", 0, False))
+
+
+def planes_for(ch, data):
+    import numpy as np
+    rng = np.random.default_rng(ch)
+    if data == "random":
+        return [rng.random((N, N), dtype=np.float32) for _ in range(ch)]
+    return [np.full((N, N), 0.4 + 0.1 * c, np.float32) for c in range(ch)]  # resident planes of one value each
+
+
+def case_bytes(ch, kind, fmt):
+    if kind == "u8":
+        return 4 * ch * PX + 4 * PX
+    return 4 * (1 if ch == 1 else PLANES[fmt]) * PX + (N // 4) * (N // 4) * BLOCK_BYTES[fmt]
+
+
+def run(reps):
+    import numpy as np
+    import torch
+
+    import kanter_core_amd as kc
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import bc_ref
+    kc.init(0)
+    imgs = {}
+    for ch in (1, 4):
+        for data in ("random", "uniform"):
+            imgs[ch, data] = kc.SlotImage.from_planes(planes_for(ch, data)).materialize()
+    outs = {f: torch.empty((N // 4, N // 4, BLOCK_BYTES[f]), dtype=torch.uint8, device="cuda") for f in BLOCK_BYTES}
+    u8 = torch.empty((N, N, 4), dtype=torch.uint8, device="cuda")
+    kc.sync()
+    torch.cuda.synchronize()
+    for name, ch, data, kind, fmt, srgb in CASES:
+        img = imgs[ch, data]
+        call = (lambda: img.to_torch(out=u8)) if kind == "u8" else (lambda: img.to_bc_torch(fmt, srgb, out=outs[fmt]))
+        call()  # warm-up
+        torch.cuda.synchronize()
+        b0 = kc.stats()["algorithmic_bytes"]
+        for _ in range(reps):
+            call()
+        torch.cuda.synchronize()
+        print("bytes %-28s %d per call" % (name, (kc.stats()["algorithmic_bytes"] - b0) // reps))
+    # the same blocks through the host: kc_image_to_u8 + the numpy reference encoder
+    img = imgs[4, "random"]
+    for fmt in (1, 3):
+        dev_ms, host_ms = [], []
+        for _ in range(5):
+            t0 = time.perf_counter()
+            a = img.to_bc(fmt)
+            dev_ms.append((time.perf_counter() - t0) * 1e3)
+        t0 = time.perf_counter()  # once: the numpy encoder takes seconds
+        b = bc_ref.encode(img.to_u8(), fmt)
+        host_ms.append((time.perf_counter() - t0) * 1e3)
+        assert np.array_equal(a, b)
+        print("wall RGBA BC%d kc_image_to_bc:                 median %.2f ms" % (fmt, statistics.median(dev_ms)))
+        print("wall RGBA BC%d kc_image_to_u8 + numpy encoder: median %.2f ms" % (fmt, statistics.median(host_ms)))
+    print("reps %d" % reps)
+
+
+def report(trace_csv, log):
+    lines = open(log).read().splitlines()
+    reps = int(next(x.split()[1] for x in lines if x.startswith("reps ")))
+    rows = list(csv.DictReader(open(trace_csv)))
+    col = lambda key: next(k for k in rows[0] if key in k)  # noqa: E731
+    kn, ks, ke = col("Kernel_Name"), col("Start_Timestamp"), col("End_Timestamp")
+    rows.sort(key=lambda r: int(r[ks]))
+    ours = [r for r in rows if "bc_encode_kernel" in r[kn] or "image_export_kernel" in r[kn]]
+    per = reps + 1
+    # the cases' dispatches come first; the wall-clock comparison's calls follow them
+    assert len(ours) >= len(CASES) * per, (len(ours), len(CASES) * per)
+    out = ["Block compression, %d x %d, MI355X; kernel times from rocprofv3 --kernel-trace (median of %d calls after a warm-up), "
+           "fraction of %.0f TB/s = algorithmic bytes (planes read + blocks or pixels written) / time / peak" % (N, N, reps, PEAK_TBS),
+           ""]
+    out.append("%-30s %10s %10s %9s" % ("case", "median us", "alg MB", "of 8TB/s"))
+    for i, (name, ch, _, kind, fmt, _) in enumerate(CASES):
+        seg = ours[i * per:(i + 1) * per]
+        want = "image_export_kernel" if kind == "u8" else "bc_encode_kernel"
+        assert all(want in r[kn] for r in seg), name
+        ns = statistics.median([int(r[ke]) - int(r[ks]) for r in seg[1:]])
+        b = case_bytes(ch, kind, fmt)
+        out.append("%-30s %10.1f %10.1f %9.3f" % (name, ns / 1e3, b / 1e6, b / ns / 1e3 / PEAK_TBS))
+    out.append("")
+    out.append("Algorithmic bytes per call (kc_stats_algorithmic_bytes) and wall-clock (a run of its own, without the tracer):")
+    out += ["  " + x.rstrip() for x in lines if x.startswith(("bytes ", "wall "))]
+    print("\n".join(out))
+
+
+if __name__ == "__main__":
+    if sys.argv[1] == "run":
+        run(int(sys.argv[2]) if len(sys.argv) > 2 else 20)
+    else:
+        report(sys.argv[2], sys.argv[3])
