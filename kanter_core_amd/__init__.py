@@ -1,6 +1,6 @@
 """kanter_core_amd -- MI355X (gfx950) per-pixel evaluation backend for kanter_core / vismut_core
 graphs.  The product is libkanter_core_amd.so (C ABI: include/kanter_core_amd.h, hand-written HIP
-kernels in csrc/kernels.hip); this package mirrors the reference's host API on top of it.
+kernels in csrc/*.hip); this package mirrors the reference's host API on top of it.
 Build the library with `python -m kanter_core_amd.build`; importing `api` symbols that touch the
 device fails loudly when it is missing -- there is no CPU fallback.
 """

@@ -9,7 +9,7 @@
 
 namespace kc {
 
-#include "streaming.h"  // grid_cap, ld_policy, quant_u8 / quant_u8_srgb: shared with kernels.hip
+#include "streaming.h"  // grid_cap, ld_policy, quant_u8 / quant_u8_srgb: shared with u8.hip
 
 typedef float bc_f4 __attribute__((ext_vector_type(4)));
 typedef uint32_t bc_u4 __attribute__((ext_vector_type(4)));

@@ -1,4 +1,5 @@
-// Per-sample operations of a Mix step (src/node/mix.rs:136-192) shared by the kernels of kernels.hip and chain1.hip.
+// Per-sample operations of a Mix step (src/node/mix.rs:136-192) shared by the step interpreter (chain_interp.inc) and chain1.hip;
+// u8.hip and chain.hip's fill_kernel take splat4 from here, and f4.
 // Included inside namespace kc (chain1.hip: inside an unnamed namespace as well, pow_positive.inc defines a __constant__ table).
 static __device__ __forceinline__ float4 splat4(float v) { return make_float4(v, v, v, v); }
 

@@ -8,7 +8,7 @@
 
 namespace kc {
 
-#include "streaming.h"  // grid_cap, ld_policy / st_policy, quant_u8 / quant_u8_srgb: shared with kernels.hip
+#include "streaming.h"  // grid_cap, ld_policy / st_policy, quant_u8 / quant_u8_srgb: shared with u8.hip
 
 typedef float dv_f4 __attribute__((ext_vector_type(4)));
 typedef uint32_t dv_u4 __attribute__((ext_vector_type(4)));

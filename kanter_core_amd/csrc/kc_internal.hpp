@@ -1,5 +1,14 @@
-// Internal declarations shared by the HIP kernels (kernels.hip) and the host runtime.
+// Internal declarations shared by the HIP kernels (the .hip files, one per kernel family) and the host runtime.
 // Not part of the C ABI (include/kanter_core_amd.h).
+//
+// The kernels are hand-written CDNA4 (gfx950) code for the kanter_core per-pixel hot path.
+// All of these are HBM-bandwidth-bound pointwise / small-stencil kernels: 16-byte (dwordx4)
+// coalesced row-major accesses on 256-byte-pitched f32 planes, 64-wide wavefronts, no MFMA.
+// Build flags that matter for parity with the reference's scalar Rust loops:
+//   -ffp-contract=off                         no FMA contraction (Rust never fuses a*b+c)
+//   -fhip-fp32-correctly-rounded-divide-sqrt  IEEE f32 divide / sqrt
+//   f32 denormals are not flushed (gfx9 default)
+// Reference paths are relative to the reference checkout.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -44,7 +53,8 @@ struct Operand {
     float c;
 };
 
-// ---- kernel launchers (kernels.hip).  All enqueue on `s` and return hipGetLastError(). ----
+// ---- kernel launchers, by the unit that defines them.  All enqueue on `s` and return hipGetLastError(). ----
+// -- chain.hip --
 // What launch_chain launched (runtime.cpp counts it: kc_stats_counter): chain_kernel<k, u, mode, nt>, or
 // chain_kernel_k0<mode> for k = 0; k < 0: nothing (an empty plane)
 struct ChainVariant {
@@ -53,6 +63,9 @@ struct ChainVariant {
 };
 // mode: 0 = {+, -, *} only, 1 = + divide, 2 = + pow
 hipError_t launch_chain(const ChainProgram &p, int batch, int mode, int max_blocks, int unroll, hipStream_t s, ChainVariant *var);
+inline uint32_t chain_op_word(uint8_t code, int src) { return (uint32_t)code | ((uint32_t)(src + 1) << 8); }
+hipError_t launch_fill(float *dst, uint32_t pitch_floats, uint32_t w, uint32_t h, float v, hipStream_t s);
+// -- chain1.hip --
 // A one-step program for the ahead-of-time kernels of chain1.hip: result = op(start, operand), each a plane (pointer,
 // pitch in float4) or a broadcast constant (pointer null); c = the constant of the fused "c - ..." codes.
 struct Chain1Args {
@@ -65,12 +78,8 @@ struct Chain1Args {
 // nt: bit 0 = the start plane, bit 1 = the operand plane, bit 2 = the result carry the nontemporal hint.
 // *launched_nt: the bits of the instantiation launched (left alone when nothing is launched: an empty plane)
 hipError_t launch_chain1(const Chain1Args &a, int batch, int code, unsigned nt, hipStream_t s, unsigned *launched_nt);
-inline uint32_t chain_op_word(uint8_t code, int src) { return (uint32_t)code | ((uint32_t)(src + 1) << 8); }
-hipError_t launch_fill(float *dst, uint32_t pitch_floats, uint32_t w, uint32_t h, float v, hipStream_t s);
-hipError_t launch_resize_vertical(const float *src, uint32_t spitch, uint32_t sw, float *tmp, uint32_t tpitch,
-                                  uint32_t dh, TapsDev v, hipStream_t s);
-hipError_t launch_resize_horizontal(const float *tmp, uint32_t tpitch, float *dst, uint32_t dpitch, uint32_t dw,
-                                    uint32_t dh, TapsDev h, hipStream_t s);
+// -- the resamplers: LDS sizes, the kernels' job tables and the plan that the launchers of resize_tile.hip, resize_down.hip,
+// down2.hip and upsample.hip take --
 // Tiled single-pass resample.  ncp = LDS pitch in floats of the vertical-pass intermediate: a multiple
 // of 4 that covers the widest 4-aligned source window any tile needs (from the host).  The 8 spare
 // floats absorb the register-tap form's reads past a short window (discarded, see resize_out_row);
@@ -140,9 +149,9 @@ inline XcdOrder xcd_order(uint32_t gx, uint32_t gy, bool want)
     o.magic = (uint32_t)magic;
     return o;
 }
-// LDS floats of one band wave of resize_poly_kernel (kernels.hip, resize_down_stage_wave)
+// LDS floats of one band wave of resize_poly_kernel (resize_down.hip, resize_down_stage_wave)
 inline uint32_t resize_down_wave_floats(uint32_t tile_w, uint32_t hstride) { return (4u * KC_DOWN_ROW_FLOATS + 2u * tile_w + tile_w * (hstride | 1u) + 3u) / 4u * 4u; }
-// resize_poly_kernel's jobs (kernels.hip)
+// resize_poly_kernel's jobs (resize_down.hip)
 struct PolyBands {
     uint32_t ya, yb;    // regular rows handled as bands: [ya, yb), yb - ya a multiple of 4
     uint32_t rows;      // rows per band (a multiple of 4; the last band may be shorter)
@@ -154,7 +163,7 @@ struct PolyBands {
     // wave_floats of LDS per wave.
     uint32_t n_sq, n_band_wgs, xper, gx, wave_floats;
 };
-// resize_poly2_kernel's jobs (kernels.hip)
+// resize_poly2_kernel's jobs (resize_down.hip)
 struct Poly2Bands {
     uint32_t ya, yb, rows, n_bands;
     uint32_t tw, n_strips;     // band path: output columns per strip (its source window is at most 256 columns), strips per row
@@ -191,15 +200,24 @@ struct ResizePlan {
     dim3 grid{};
 };
 // The launchers of the planned forms: they check the plan and pick the kernel template, nothing else.
+// -- resize_tile.hip --
 hipError_t launch_resize_lds(const ResizePlan &r, const ResizePlanes &p, TapsDev v, TapsDev h, hipStream_t s);  // lds, wide
-hipError_t launch_resize_down(const ResizePlan &r, const ResizePlanes &p, TapsDev v, TapsDev h, hipStream_t s);
-hipError_t launch_resize_poly(const ResizePlan &r, const ResizePlanes &p, TapsDev v, TapsDev h, hipStream_t s);
-// The same ranges with two waves to a band's strip (8-byte lanes, a shared ring, the horizontal pass split by pixels): kernels.hip
-hipError_t launch_resize_poly2(const ResizePlan &r, const ResizePlanes &p, TapsDev v, TapsDev h, hipStream_t s);
-// a: the plan's d2 with the tables' pointers
-hipError_t launch_resize_down2(const ResizePlan &r, const ResizePlanes &p, const Down2Args &a, hipStream_t s);
 // Fused resample + chain: input slot n_in - 1 of the program is produced by the resampler.
 hipError_t launch_resize_chain(const ResizePlan &r, const ChainProgram &p, TapsDev v, TapsDev h, hipStream_t s);
+// The two-pass form, one plane per call.
+hipError_t launch_resize_vertical(const float *src, uint32_t spitch, uint32_t sw, float *tmp, uint32_t tpitch,
+                                  uint32_t dh, TapsDev v, hipStream_t s);
+hipError_t launch_resize_horizontal(const float *tmp, uint32_t tpitch, float *dst, uint32_t dpitch, uint32_t dw,
+                                    uint32_t dh, TapsDev h, hipStream_t s);
+// -- resize_down.hip --
+hipError_t launch_resize_down(const ResizePlan &r, const ResizePlanes &p, TapsDev v, TapsDev h, hipStream_t s);
+hipError_t launch_resize_poly(const ResizePlan &r, const ResizePlanes &p, TapsDev v, TapsDev h, hipStream_t s);
+// The same ranges with two waves to a band's strip (8-byte lanes, a shared ring, the horizontal pass split by pixels)
+hipError_t launch_resize_poly2(const ResizePlan &r, const ResizePlanes &p, TapsDev v, TapsDev h, hipStream_t s);
+// -- down2.hip --
+// a: the plan's d2 with the tables' pointers
+hipError_t launch_resize_down2(const ResizePlan &r, const ResizePlanes &p, const Down2Args &a, hipStream_t s);
+// -- upsample.hip --
 // Integer-ratio up-sampling (upsample.h).  A workgroup's tile: tile_w columns x KC_UPSAMPLE_ROWS * (1024 / tile_w) rows
 // (every thread 4 columns x KC_UPSAMPLE_ROWS rows, one trip).  LDS: the tile's intermediate, then the H quad classes.
 #ifdef KC_UP_RU  // tuning builds (tools/build_variant.sh)
@@ -241,11 +259,16 @@ struct UpsamplePlanes {
 };
 hipError_t launch_upsample_chain(const ChainProgram &p, int batch, const UpsampleArgs &u, hipStream_t s);
 hipError_t launch_upsample(const UpsamplePlanes &p, int batch, const UpsampleArgs &u, hipStream_t s);
+// -- h2n.hip --
 // nt_mask: the launch's cache policy as cache_policy_mask() returns it (bits 0-7: inputs, bit 8: results)
 hipError_t launch_height_to_normal(const float *hgt, uint32_t hpitch, uint32_t w, uint32_t h, uint32_t full_h, int band,
                                    float *nx, float *ny, float *nz, uint32_t opitch, uint32_t nt_mask, hipStream_t s);
+// -- u8.hip --
 hipError_t launch_to_u8(Operand r, Operand g, Operand b, Operand a, int gray, int srgb, uint32_t w, uint32_t h,
                         uint8_t *dst, uint32_t nt_mask, hipStream_t s);
+hipError_t launch_from_u8(const uint8_t *src, int channels, uint32_t w, uint32_t h, float *const planes[4],
+                          uint32_t pitch, uint32_t nt_mask, hipStream_t s);
+// -- devimage.hip --
 // Device-memory images (devimage.hip / devimage.cpp): a validated kc_device_image as the kernels take it.  vec != 0: the pointer
 // and the pitches are aligned for the widest access of a whole pixel quad (devimage.cpp, devimage_vec).
 struct DevImageArgs {
@@ -260,6 +283,7 @@ hipError_t launch_image_import(int dtype, const DevImageArgs &a, float *const pl
 // image_export_kernel: channel c of the output is op[c]; gray != 0: op[0] stands for R, G and B (read once); nt_mask bits 0-7:
 // nontemporal plane loads; srgb: U8 only
 hipError_t launch_image_export(int dtype, int srgb, const Operand op[4], int gray, const DevImageArgs &a, uint32_t nt_mask, hipStream_t s);
+// -- stats.hip --
 // Per-channel statistics (stats.hip / stats.cpp): the n distinct resident planes ("slots") of one image.  Bit s of srgb: slot
 // s bins with the sRGB quantiser.  partials: one record of rec_words u32 per workgroup (stats.hip has the layout); result:
 // rec_words u64, initialised by the launch itself.
@@ -275,12 +299,11 @@ struct StatsArgs {
 hipError_t launch_channel_stats(const StatsArgs &a, bool hist, bool srgb, bool nt, uint32_t groups, hipStream_t s);
 // workgroups of that launch for a w x h image on a device of `cus` CUs (>= 1)
 uint32_t channel_stats_groups(uint32_t w, uint32_t h, bool hist, bool srgb, uint32_t cus);
+// -- bc.hip --
 // Block compression (bc.hip / bc.cpp): bc_encode_kernel<fmt, srgb, nt> writes the ceil(w/4) x ceil(h/4) blocks of format `fmt`
 // (kc_bc_format) at dst, block rows row_pitch bytes apart; channel c is op[c]; gray != 0: op[0] stands for R, G and B (read
 // once); nt_mask bits 0-7: nontemporal plane loads; srgb: BC1 and BC3 only
 hipError_t launch_bc_encode(int fmt, int srgb, const Operand op[4], int gray, char *dst, uint64_t row_pitch, uint32_t w, uint32_t h,
                             uint32_t nt_mask, hipStream_t s);
-hipError_t launch_from_u8(const uint8_t *src, int channels, uint32_t w, uint32_t h, float *const planes[4],
-                          uint32_t pitch, uint32_t nt_mask, hipStream_t s);
 
 }  // namespace kc

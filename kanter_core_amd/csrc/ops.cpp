@@ -1,6 +1,6 @@
 // Node operators: the bodies behind process_node_internal (src/node/node_type.rs:98-138) and the
 // SlotImage conversions they use.  Host logic only decides WHICH planes feed which kernel; every
-// pixel is produced by a kernel in kernels.hip.
+// pixel is produced by a kernel of one of the .hip files.
 #include <cstdlib>
 #include <cstring>
 

@@ -1,12 +1,13 @@
-// What the streaming kernels of kernels.hip (to_u8, from_u8, height_to_normal, ...) and devimage.hip (device-memory images)
-// share: the grid cap of their grid-stride loops, loads / stores with a launch's cache policy and the two 8-bit quantisers.
-// Included inside namespace kc by both units; every definition is static, each unit keeps its own copy.
+// What the streaming kernels share -- u8.hip (to_u8, from_u8), h2n.hip (height_to_normal), devimage.hip (device-memory images),
+// stats.hip, bc.hip, and chain.hip for the policy loads / stores: the grid cap of their grid-stride loops, loads / stores with a
+// launch's cache policy and the two 8-bit quantisers.
+// Included inside namespace kc by each unit; every definition is static, each unit keeps its own copy.
 #pragma once
 
 // Grid cap of the grid-stride streaming kernels (to_u8, from_u8, height_to_normal); the tune_cap option overrides (tuning).
 // Default: no cap, one quad / pixel per thread -- from_u8 58.1 -> 50.4 us, height_to_normal 56.8 -> 55.4 us at 4096^2
 // against 8192 workgroups looping twice (profiles/r02_kernel_times.txt); to_u8 does not care.
-static uint64_t grid_cap(uint64_t dflt)
+[[maybe_unused]] static uint64_t grid_cap(uint64_t dflt)  // (chain.hip takes its grid from the caller)
 {
     const int cap = options().tune_cap;
     return cap > 0 ? (uint64_t)cap : dflt;

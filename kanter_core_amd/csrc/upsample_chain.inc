@@ -1,5 +1,5 @@
 // Device body of the integer-ratio up-sampling kernels (see upsample.h for what the host has checked).
-// Included inside namespace kc by kernels.hip (the interpreter-driven and the plain instantiations) and, as text, by
+// Included inside namespace kc by upsample.hip (the interpreter-driven and the plain instantiations) and, as text, by
 // the run-time specialiser (specialize.cpp: the Mix chain as straight-line code).  Needs f4, ChainProgram, UpAxis /
 // UpsampleArgs.  Arithmetic per output sample is the reference's: vertical pass first, unclamped, every sum sequential
 // from 0.0 and unfused; horizontal pass clamped to [0, 1] with NaN passing through (image::math::utils::clamp).

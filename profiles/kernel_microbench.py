@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
-"""Per-kernel HBM bandwidth on one MI355X (4096x4096 planes): every kernel of csrc/kernels.hip
-through the C-ABI operator entry points, HIP-event timed on the shared stream.
+"""Per-kernel HBM bandwidth on one MI355X (4096x4096 planes): the kernels of csrc/chain.hip, resize_tile.hip, resize_down.hip,
+h2n.hip and u8.hip through the C-ABI operator entry points, HIP-event timed on the shared stream.
     python profiles/kernel_microbench.py [--size 4096] [--reps 50]
 Prints one JSON object: kernel -> {us, GB/s, frac of 8 TB/s, algorithmic bytes}."""
 import argparse

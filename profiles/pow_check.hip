@@ -2,7 +2,7 @@
 // f64 pow routine rounded to f32 (the correctly rounded power in all but ~2^-28 of cases).
 //   hipcc --offload-arch=gfx950 -O3 -ffp-contract=off profiles/pow_check.hip -o /tmp/powc && /tmp/powc
 // Reports, per sampled region, how many of 2^32 random (a, b) pairs differ and by how many ulp at most.
-// The function under test is a verbatim copy of pow_positive() in kanter_core_amd/csrc/kernels.hip.
+// The function under test is a verbatim copy of pow_positive() in kanter_core_amd/csrc/pow_positive.inc.
 #include <hip/hip_runtime.h>
 
 #include <cstdint>

@@ -22,7 +22,7 @@ Forms no graph reaches:
   with a cacheable result need an input with a single reference (above).
   chain_k0_m0 / chain_k0_m1: the host folds a Mix of two constants except Pow (runtime.cpp plane_mix), so a program without
   an input plane always starts with Pow: MODE 2.
-  the nontemporal interpreter at a tuning unroll (U != 4 in MODE 0) does not exist (kernels.hip launch_chain_k), nor a
+  the nontemporal interpreter at a tuning unroll (U != 4 in MODE 0) does not exist (chain.hip launch_chain_k), nor a
   nontemporal chain_kernel_k0.
 A one-record program with a step code that puts the running value on the right (x - acc, x / acc, x ^ acc, c - (x - acc))
 comes from a Mix whose right input is a chain that has not run, and that chain then running on its own first: the case

@@ -1,4 +1,4 @@
-"""GPU parity of resize_poly2_kernel (csrc/kernels.hip) -- down-sampling whose VERTICAL axis has an integer ratio (2, 4, 8), two
+"""GPU parity of resize_poly2_kernel (csrc/resize_down.hip) -- down-sampling whose VERTICAL axis has an integer ratio (2, 4, 8), two
 waves to a band's strip behind one s_barrier per four rows -- against the CPU oracle and against the kernels it replaces
 (kc.set_option("poly2", 0): resize_poly_kernel / resize_down2_kernel), bit for bit, through the C ABI.
 Reference: image::imageops::resize (crate image 0.24.0) as called from src/shared.rs:159-199.

@@ -20,7 +20,7 @@ def usage(tmp_path_factory):
         pytest.skip("hipcc not available")
     table = {}
     tmp = tmp_path_factory.mktemp("res")
-    for unit in ("kernels.hip", "chain1.hip", "down2.hip"):
+    for unit in ("chain.hip", "resize_tile.hip", "resize_down.hip", "upsample.hip", "h2n.hip", "u8.hip", "chain1.hip", "down2.hip"):
         src = os.path.join(ROOT, "kanter_core_amd", "csrc", unit)
         cmd = [hipcc] + kbuild.FLAGS + kbuild.DEVICE_FLAGS + ["-x", "hip", "-Rpass-analysis=kernel-resource-usage", "-c", src,
                                                               "-o", str(tmp / (unit + ".o"))]

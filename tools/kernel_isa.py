@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Instruction histogram / register use of one kernel in an AMDGPU assembly listing.
-    hipcc --offload-arch=gfx950 ... -S --cuda-device-only -o k.s kernels.hip;  python tools/kernel_isa.py k.s height_to_normal_kernelILb0"""
+    hipcc --offload-arch=gfx950 ... -S --cuda-device-only -o k.s h2n.hip;  python tools/kernel_isa.py k.s height_to_normal_kernelILb0"""
 import collections
 import re
 import sys

@@ -12,14 +12,17 @@ SAN=${KC_SANITIZER:-address,undefined}   # or: thread
 OUT=/tmp/kc_asan
 mkdir -p $OUT
 python -m kanter_core_amd.build >/dev/null
-for f in runtime ops resize graph json png specialize partition bands comm replay u8pipe devimage c_api; do
+# kanter_core_amd/build.py's sources: the .cpp files are compiled here, the device units' objects are the regular build's
+ask() { python -c "from kanter_core_amd import build as b; print(' '.join($1))"; }
+HOST=$(ask 's[:-4] for s in b.SOURCES if s.endswith(".cpp")')
+DEVICE=$(ask '"kanter_core_amd/csrc/build/" + b.object_name(s) for s in b.SOURCES if s.endswith(".hip")')
+for f in $HOST; do
   $CL -x c++ -O1 -g -std=c++17 -fPIC -fno-fast-math -ffp-contract=off -fsanitize=$SAN -fno-omit-frame-pointer \
       -D__HIP_PLATFORM_AMD__ -I/opt/rocm/include -Iinclude -Ikanter_core_amd/csrc -c kanter_core_amd/csrc/$f.cpp -o $OUT/$f.o &
 done
 wait
-$CL -shared -fPIC -fsanitize=$SAN -shared-libsan -o $OUT/libkanter_core_amd.so kanter_core_amd/csrc/build/kernels.o \
-    kanter_core_amd/csrc/build/chain1.o kanter_core_amd/csrc/build/down2.o kanter_core_amd/csrc/build/devimage_kernels.o \
-    kanter_core_amd/csrc/build/jit_texts.o $OUT/{runtime,ops,resize,graph,json,png,specialize,partition,bands,comm,replay,u8pipe,devimage,c_api}.o -L/opt/rocm/lib -lamdhip64 -lz -ldl -Wl,-rpath,/opt/rocm/lib
+$CL -shared -fPIC -fsanitize=$SAN -shared-libsan -o $OUT/libkanter_core_amd.so $DEVICE kanter_core_amd/csrc/build/jit_texts.o \
+    $(for f in $HOST; do echo $OUT/$f.o; done) -L/opt/rocm/lib -lamdhip64 -lz -ldl -Wl,-rpath,/opt/rocm/lib
 cp kanter_core_amd/libkanter_core_amd.so $OUT/regular.so
 cp $OUT/libkanter_core_amd.so kanter_core_amd/libkanter_core_amd.so
 trap 'cp $OUT/regular.so kanter_core_amd/libkanter_core_amd.so' EXIT
