@@ -58,13 +58,14 @@ struct BandSlot {
 };
 
 struct Walk {
+    std::unique_ptr<kc_live_graph> flat;  // the graph with its Graph nodes expanded, if it had any above the root
     kc_live_graph &lg;
     std::vector<uint32_t> topo;
     std::map<uint32_t, kc_size> size;
     std::map<uint32_t, bool> rgba;  // type of the node's output(s): some operators' output SIZE depends on it (Separate of a gray image)
     std::map<uint32_t, Need> need;
     std::map<uint32_t, std::vector<BandSlot>> data;
-    explicit Walk(kc_live_graph &g) : lg(g) {}
+    explicit Walk(kc_live_graph &g, std::unique_ptr<kc_live_graph> f = nullptr) : flat(std::move(f)), lg(flat ? *flat : g) {}
     ~Walk()
     {
         for (auto &kv : data)
@@ -72,91 +73,38 @@ struct Walk {
     }
 };
 
-int topo_order(const NodeGraph &g, uint32_t root, std::vector<uint32_t> &topo)
+// ---- (2) sizes -------------------------------------------------------------------------------------------
+// size and type of a source node's image (Image nodes are RGBA: image_from_u8 always builds four planes)
+int source_info(Walk &W, const Node &n, kc_size *out, bool *rgba)
 {
-    std::map<uint32_t, int> mark;
-    struct Frame {
-        uint32_t id;
-        std::vector<uint32_t> parents;
-        size_t next;
-    };
-    std::vector<Frame> st;
-    st.push_back(Frame{ root, g.get_parents(root), 0 });
-    mark[root] = 1;
-    while (!st.empty()) {
-        Frame &f = st.back();
-        if (f.next == f.parents.size()) {
-            mark[f.id] = 2;
-            topo.push_back(f.id);
-            st.pop_back();
-            continue;
-        }
-        const uint32_t p = f.parents[f.next++];
-        if (!g.find(p) || mark[p] == 2) continue;
-        if (mark[p] == 1) {
-            set_error("graph has a cycle through node " + std::to_string(p));
+    kc_live_graph &lg = W.lg;
+    if (n.type == KC_NODE_EMBED) {
+        const EmbeddedSlotData *e = lg.find_embedded(n.embed_id);
+        if (!e) {
+            set_error("embedded slot data not found");
             return KC_ERR_NODE_PROCESSING;
         }
-        mark[p] = 1;
-        st.push_back(Frame{ p, g.get_parents(p), 0 });
-    }
-    return KC_OK;
-}
-
-bool is_source(const Node &n) { return n.type == KC_NODE_EMBED || n.type == KC_NODE_IMAGE || n.is_input(); }
-
-// Is a source node's image RGBA?  (Image nodes are: image_from_u8 always builds four planes.)
-bool source_is_rgba(Walk &W, const Node &n)
-{
-    kc_live_graph &lg = W.lg;
-    if (n.type == KC_NODE_EMBED) {
-        for (auto &e : lg.embedded)
-            if (e.slot_data_id == n.embed_id) return e.image->is_rgba();
-        return false;
-    }
-    if (n.type == KC_NODE_IMAGE) return true;
-    if (n.type == KC_NODE_INPUT_RGBA) return !lg.input_slot_datas.empty() && lg.input_slot_datas[0].image->is_rgba();
-    for (auto &in : lg.input_slot_datas)
-        if (in.node_id == n.node_id) return in.image->is_rgba();
-    return false;
-}
-
-// ---- (2) sizes -------------------------------------------------------------------------------------------
-int source_size(Walk &W, const Node &n, kc_size *out)
-{
-    kc_live_graph &lg = W.lg;
-    if (n.type == KC_NODE_EMBED) {
-        for (auto &e : lg.embedded)
-            if (e.slot_data_id == n.embed_id) {
-                *out = kc_size{ e.image->w(), e.full_h ? e.full_h : e.image->h() };
-                return KC_OK;
-            }
-        set_error("embedded slot data not found");
-        return KC_ERR_NODE_PROCESSING;
+        *out = kc_size{ e->image->w(), e->full_h ? e->full_h : e->image->h() };
+        *rgba = e->image->is_rgba();
+        return KC_OK;
     }
     if (n.type == KC_NODE_IMAGE) {
         std::vector<uint8_t> px;
         uint32_t w = 0, h = 0;
         int ch = 0;
-        const std::string path = (n.text.empty() || n.text[0] == '/' || lg.base_dir.empty()) ? n.text : lg.base_dir + "/" + n.text;
-        *out = png_read(path, px, w, h, ch) == KC_OK ? kc_size{ w, h } : kc_size{ 1, 1 };  // unreadable -> 1x1 magenta
+        *out = png_read(lg.resolve_path(n.text), px, w, h, ch) == KC_OK ? kc_size{ w, h } : kc_size{ 1, 1 };  // unreadable -> 1x1 magenta
+        *rgba = true;
         return KC_OK;
     }
-    if (n.type == KC_NODE_INPUT_RGBA) {
-        if (lg.input_slot_datas.empty()) {
-            set_error("InputRgba without input slot data");
-            return KC_ERR_NODE_PROCESSING;
-        }
-        *out = kc_size{ lg.input_slot_datas[0].image->w(), lg.input_slot_datas[0].image->h() };
-        return KC_OK;
+    const SlotData *in = lg.find_input(n);
+    if (!in) {
+        const bool gray = n.type == KC_NODE_INPUT_GRAY;
+        set_error(gray ? "InputGray without input slot data" : "InputRgba without input slot data");
+        return gray ? KC_ERR_NO_SLOT_DATA : KC_ERR_NODE_PROCESSING;
     }
-    for (auto &in : lg.input_slot_datas)
-        if (in.node_id == n.node_id) {
-            *out = kc_size{ in.image->w(), in.image->h() };
-            return KC_OK;
-        }
-    set_error("InputGray without input slot data");
-    return KC_ERR_NO_SLOT_DATA;
+    *out = kc_size{ in->image->w(), in->image->h() };
+    *rgba = in->image->is_rgba();
+    return KC_OK;
 }
 
 // calculate_size of one node from its parents' logical sizes, as process_node does (graph.cpp)
@@ -164,24 +112,8 @@ int target_size(Walk &W, const Node &n, const std::vector<kc_edge> &edges, kc_si
 {
     std::vector<kc_size> sizes;
     for (auto &e : edges) sizes.push_back(W.size[e.output_id]);
-    int slot_index = -1;
-    if (n.policy == KC_POLICY_SPECIFIC_SLOT) {
-        std::vector<kc_edge> sorted = edges;
-        std::stable_sort(sorted.begin(), sorted.end(), [](const kc_edge &x, const kc_edge &y) { return x.input_slot < y.input_slot; });
-        const kc_edge *edge = nullptr;
-        for (auto &e : sorted)
-            if (e.input_slot == n.policy_slot) {
-                edge = &e;
-                break;
-            }
-        if (!edge && !sorted.empty()) edge = &sorted[0];
-        if (edge)
-            for (size_t i = 0; i < edges.size(); ++i)
-                if (edges[i].output_slot == edge->output_slot && edges[i].output_id == edge->output_id) {
-                    slot_index = (int)i;
-                    break;
-                }
-    }
+    const EdgeList sorted = edges_by_input_slot(edges.data(), edges.size());
+    const int slot_index = policy_slot_index(n.policy, n.policy_slot, sorted.data(), sorted.size(), edges.data(), edges.size());
     return calculate_size(n.policy, sizes.data(), (int)sizes.size(), slot_index, n.policy_size, out);
 }
 
@@ -193,9 +125,8 @@ int infer_sizes(Walk &W, const uint32_t *skip = nullptr)
         const Node &n = *g.find(id);
         kc_size s{ 1, 1 };
         bool rgba = false;
-        if (is_source(n)) {
-            KC_TRY(source_size(W, n, &s));
-            rgba = source_is_rgba(W, n);
+        if (n.is_source()) {
+            KC_TRY(source_info(W, n, &s, &rgba));
         } else if (n.type == KC_NODE_VALUE) {
             s = kc_size{ 1, 1 };
         } else if (n.type == KC_NODE_GRAPH || n.type == KC_NODE_WRITE) {
@@ -301,7 +232,7 @@ int propagate_needs(Walk &W, uint32_t root, int32_t y0, int32_t y1)
         const Node &n = *g.find(id);
         const kc_size T = W.size[id];
         normalise(nd, T.height);
-        if (is_source(n) || n.type == KC_NODE_VALUE) continue;
+        if (n.is_source() || n.type == KC_NODE_VALUE) continue;
         Need in = nd;
         if (n.type == KC_NODE_HEIGHT_TO_NORMAL && T.height > 1) in.a -= 1;  // the row above; row -1 wraps to the last row
         if (n.type == KC_NODE_HEIGHT_TO_NORMAL && T.height == 1) in = Need{ 0, 1, true };
@@ -465,15 +396,15 @@ int evaluate_source(Walk &W, const Node &n)
     const Need nd = W.need[n.node_id];
     const kc_size sz = W.size[n.node_id];
     if (n.type == KC_NODE_EMBED) {
-        for (auto &e : lg.embedded)
-            if (e.slot_data_id == n.embed_id) {
-                kc_image *img = nullptr;
-                KC_TRY(crop_rows(e.image, e.full_h ? e.band_y0 : 0, sz.height, nd.a, nd.b, &img));
-                W.data[n.node_id].push_back(BandSlot{ 0, img, sz.height == 1 ? 0 : nd.a });
-                return KC_OK;
-            }
-        set_error("embedded slot data not found");
-        return KC_ERR_NODE_PROCESSING;
+        const EmbeddedSlotData *e = lg.find_embedded(n.embed_id);
+        if (!e) {
+            set_error("embedded slot data not found");
+            return KC_ERR_NODE_PROCESSING;
+        }
+        kc_image *img = nullptr;
+        KC_TRY(crop_rows(e->image, e->full_h ? e->band_y0 : 0, sz.height, nd.a, nd.b, &img));
+        W.data[n.node_id].push_back(BandSlot{ 0, img, sz.height == 1 ? 0 : nd.a });
+        return KC_OK;
     }
     // Image / Input*: through the ordinary evaluator (whole image), then the needed rows
     KC_TRY(lg.ensure_clean(n.node_id));
@@ -487,19 +418,22 @@ int evaluate_source(Walk &W, const Node &n)
 
 int evaluate_node(Walk &W, const Node &n)
 {
-    const NodeGraph &g = W.lg.g;
+    const bool taken = n.type == KC_NODE_MIX || n.type == KC_NODE_HEIGHT_TO_NORMAL || n.type == KC_NODE_SEPARATE_RGBA ||
+                       n.type == KC_NODE_COMBINE_RGBA || n.is_output();
+    if (!taken) {
+        set_error("row-band evaluation: unsupported node type");
+        return KC_ERR_UNSUPPORTED;
+    }
     const uint32_t id = n.node_id;
     const kc_size T = W.size[id];
     const Need nd = W.need[id];
     Need in = nd;
     if (n.type == KC_NODE_HEIGHT_TO_NORMAL) in = T.height > 1 ? Need{ nd.a - 1, nd.b, true } : Need{ 0, 1, true };
-    std::vector<kc_edge> edges = g.edges_into(id);
-    std::vector<kc_edge> sorted = edges;
-    std::stable_sort(sorted.begin(), sorted.end(), [](const kc_edge &x, const kc_edge &y) { return x.input_slot < y.input_slot; });
+    const std::vector<kc_edge> &edges = W.lg.g.edges_into(id);
     // resize_buffers on bands, then assign_slot_ids (node_type.rs:229-267): one image per sorted edge
-    std::vector<SlotData> assigned;
+    SlotList assigned, result;
     int s = KC_OK;
-    for (auto &e : sorted) {
+    for (auto &e : edges_by_input_slot(edges.data(), edges.size())) {
         const BandSlot *bs = find_band_slot(W, e.output_id, e.output_slot);
         if (!bs) {
             set_error("a parent produced no data for a connected slot");
@@ -515,57 +449,13 @@ int evaluate_node(Walk &W, const Node &n)
         if (s != KC_OK) break;
         assigned.push_back(SlotData{ e.input_id, e.input_slot, img });
     }
-    auto with = [&](uint32_t slot) -> kc_image * {
-        for (auto &sd : assigned)
-            if (sd.slot_id == slot) return sd.image;
-        return nullptr;
-    };
-    std::vector<BandSlot> &out = W.data[id];
-    const int32_t oy = T.height == 1 ? 0 : nd.a;
-    if (s == KC_OK) switch (n.type) {
-        case KC_NODE_MIX: {
-            kc_image *img = nullptr;
-            s = mix_process(with(0), with(1), n.mix_type, &img);
-            if (s == KC_OK && img) out.push_back(BandSlot{ 0, img, oy });
-            break;
-        }
-        case KC_NODE_HEIGHT_TO_NORMAL: {
-            kc_image *img = nullptr;
-            kc_image *src = with(0);
-            if (T.height > 1) s = height_to_normal_band(src, T.height, &img);
-            else s = height_to_normal_process(src, &img);
-            if (s == KC_OK && img) out.push_back(BandSlot{ 0, img, oy });
-            break;
-        }
-        case KC_NODE_SEPARATE_RGBA: {
-            kc_image *o[4];
-            s = separate_process(assigned.empty() ? nullptr : assigned[0].image, o);
-            if (s == KC_OK)
-                for (uint32_t i = 0; i < 4; ++i) out.push_back(BandSlot{ i, o[i], oy });
-            break;
-        }
-        case KC_NODE_COMBINE_RGBA: {
-            kc_image *inp[4] = { with(0), with(1), with(2), with(3) };
-            kc_image *img = nullptr;
-            s = combine_process(inp, &img);
-            if (s == KC_OK) out.push_back(BandSlot{ 0, img, oy });
-            break;
-        }
-        case KC_NODE_OUTPUT_GRAY:
-        case KC_NODE_OUTPUT_RGBA: {
-            if (!assigned.empty()) {
-                image_retain(assigned[0].image);
-                out.push_back(BandSlot{ 0, assigned[0].image, oy });
-            } else {
-                kc_image *img = nullptr;
-                s = image_from_value(kc_size{ 1, 1 }, 0.0f, n.type == KC_NODE_OUTPUT_RGBA, &img);  // output.rs:20-31
-                if (s == KC_OK) out.push_back(BandSlot{ 0, img, 0 });
-            }
-            break;
-        }
-        default: set_error("row-band evaluation: unsupported node type"); s = KC_ERR_UNSUPPORTED;
-        }
+    // the operator itself: the whole-image evaluator's (graph.cpp), on the bands
+    if (s == KC_OK) s = dispatch(W.lg, n, assigned, T.height, result);
     for (auto &sd : assigned) image_release(sd.image);
+    for (auto &sd : result) {
+        if (s == KC_OK) W.data[id].push_back(BandSlot{ sd.slot_id, sd.image, T.height == 1 ? 0 : nd.a });
+        else image_release(sd.image);
+    }
     return s;
 }
 
@@ -585,7 +475,7 @@ int expand_graph_nodes(kc_live_graph &lg, uint32_t *root, uint32_t *slot, std::u
 {
     auto has_graph_ancestor = [](const NodeGraph &g, uint32_t r, uint32_t *which) {
         std::vector<uint32_t> topo;
-        if (topo_order(g, r, topo) != KC_OK) return false;
+        if (ancestors_topological(g, r, topo) != KC_OK) return false;
         for (uint32_t id : topo)
             if (g.find(id)->type == KC_NODE_GRAPH) {
                 *which = id;  // topological order: the first one has no Graph node above it
@@ -621,7 +511,7 @@ int expand_graph_nodes(kc_live_graph &lg, uint32_t *root, uint32_t *slot, std::u
         }
         // T: the Graph node's resize target, from the inferred sizes of its parents
         Walk W(F);
-        KC_TRY(topo_order(F.g, gid, W.topo));
+        KC_TRY(ancestors_topological(F.g, gid, W.topo));
         KC_TRY(infer_sizes(W, &gid));
         const std::vector<kc_edge> in_edges = F.g.edges_into(gid);
         kc_size T{ 1, 1 };
@@ -695,35 +585,31 @@ int expand_graph_nodes(kc_live_graph &lg, uint32_t *root, uint32_t *slot, std::u
     return KC_OK;
 }
 
-int build_walk(Walk &W, uint32_t root, int32_t y0, int32_t y1)
+// Opens the walk every entry point starts with: the Graph nodes above `root` expanded (root and slot then name the node that
+// took the root's place), the ancestors in order and their sizes.
+int open_walk(kc_live_graph &lg0, uint32_t *root, uint32_t *slot, std::unique_ptr<Walk> &W)
 {
-    if (!W.lg.g.find(root)) return KC_ERR_INVALID_NODE_ID;
-    KC_TRY(topo_order(W.lg.g, root, W.topo));
-    KC_TRY(infer_sizes(W));
-    return propagate_needs(W, root, y0, y1);
+    if (!lg0.g.find(*root)) return KC_ERR_INVALID_NODE_ID;
+    std::unique_ptr<kc_live_graph> flat;
+    KC_TRY(expand_graph_nodes(lg0, root, slot, flat));
+    W.reset(new Walk(lg0, std::move(flat)));
+    KC_TRY(ancestors_topological(W->lg.g, *root, W->topo));
+    return infer_sizes(*W);
 }
 
 }  // namespace
 
 int band_source_rows(kc_live_graph &lg0, uint32_t root, int32_t y0, int32_t y1, std::vector<kc_band_rows> &out)
 {
-    if (!lg0.g.find(root)) return KC_ERR_INVALID_NODE_ID;
-    std::unique_ptr<kc_live_graph> flat;
+    // any output of a Graph node: the sources' rows are asked for per node, the first Output node stands for it
     uint32_t slot = 0;
-    if (lg0.g.find(root)->type == KC_NODE_GRAPH) {
-        // any output of the Graph node: the sources' rows are asked for per node, the first Output node stands for it
-        const std::vector<uint32_t> outs = lg0.g.find(root)->graph ? lg0.g.find(root)->graph->output_ids() : std::vector<uint32_t>{};
-        if (outs.empty()) return KC_ERR_NO_SLOT_DATA;
-        slot = outs[0];
-    }
-    KC_TRY(expand_graph_nodes(lg0, &root, &slot, flat));
-    kc_live_graph &lg = flat ? *flat : lg0;
-    Walk W(lg);
-    KC_TRY(build_walk(W, root, y0, y1));
-    for (uint32_t id : W.topo) {
-        const Node &n = *lg.g.find(id);
-        if (!is_source(n) || !W.need[id].set) continue;
-        out.push_back(kc_band_rows{ id, W.need[id].a, W.need[id].b, W.size[id].width, W.size[id].height });
+    KC_TRY(root_output_slot(lg0.g, root, &slot));
+    std::unique_ptr<Walk> W;
+    KC_TRY(open_walk(lg0, &root, &slot, W));
+    KC_TRY(propagate_needs(*W, root, y0, y1));
+    for (uint32_t id : W->topo) {
+        if (!W->lg.g.find(id)->is_source() || !W->need[id].set) continue;
+        out.push_back(kc_band_rows{ id, W->need[id].a, W->need[id].b, W->size[id].width, W->size[id].height });
     }
     return KC_OK;
 }
@@ -731,21 +617,12 @@ int band_source_rows(kc_live_graph &lg0, uint32_t root, int32_t y0, int32_t y1, 
 // What a row-band PLAN needs (partition.cpp): is the graph one the band walk takes, and how large is the requested node's image?
 int band_plan_info(kc_live_graph &lg0, uint32_t root, kc_size *size, bool *rgba)
 {
-    if (!lg0.g.find(root)) return KC_ERR_INVALID_NODE_ID;
-    std::unique_ptr<kc_live_graph> flat;
     uint32_t slot = 0;
-    if (lg0.g.find(root)->type == KC_NODE_GRAPH) {
-        const std::vector<uint32_t> outs = lg0.g.find(root)->graph ? lg0.g.find(root)->graph->output_ids() : std::vector<uint32_t>{};
-        if (outs.empty()) return KC_ERR_NO_SLOT_DATA;
-        slot = outs[0];
-    }
-    KC_TRY(expand_graph_nodes(lg0, &root, &slot, flat));
-    kc_live_graph &lg = flat ? *flat : lg0;
-    Walk W(lg);
-    KC_TRY(topo_order(lg.g, root, W.topo));
-    KC_TRY(infer_sizes(W));
-    *size = W.size[root];
-    *rgba = W.rgba[root];
+    KC_TRY(root_output_slot(lg0.g, root, &slot));
+    std::unique_ptr<Walk> W;
+    KC_TRY(open_walk(lg0, &root, &slot, W));
+    *size = W->size[root];
+    *rgba = W->rgba[root];
     return KC_OK;
 }
 
@@ -753,17 +630,15 @@ int band_evaluate(kc_live_graph &lg0, uint32_t root, uint32_t slot, int32_t y0, 
 {
     *out = nullptr;
     KC_TRY(need_init());
-    if (!lg0.g.find(root)) return KC_ERR_INVALID_NODE_ID;
-    std::unique_ptr<kc_live_graph> flat;  // the graph with its Graph nodes expanded, if it has any above the root
-    KC_TRY(expand_graph_nodes(lg0, &root, &slot, flat));
-    kc_live_graph &lg = flat ? *flat : lg0;
-    Walk W(lg);
-    KC_TRY(build_walk(W, root, y0, y1));
+    std::unique_ptr<Walk> Wp;
+    KC_TRY(open_walk(lg0, &root, &slot, Wp));
+    Walk &W = *Wp;
+    KC_TRY(propagate_needs(W, root, y0, y1));
     ResizeMemoScope memo;
     for (uint32_t id : W.topo) {
         if (!W.need[id].set) continue;
-        const Node &n = *lg.g.find(id);
-        if (is_source(n)) {
+        const Node &n = *W.lg.g.find(id);
+        if (n.is_source()) {
             KC_TRY(evaluate_source(W, n));
         } else if (n.type == KC_NODE_VALUE) {
             kc_image *img = nullptr;

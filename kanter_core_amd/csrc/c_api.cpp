@@ -842,21 +842,7 @@ try {
     if (n == 0) return KC_OK;  // shared.rs:147-149
     std::vector<kc_size> sizes;
     for (int i = 0; i < n; ++i) sizes.push_back(kc_size{ images[i]->w(), images[i]->h() });
-    int slot_index = -1;
-    if (policy == KC_POLICY_SPECIFIC_SLOT && edges_sorted && n_edges > 0) {
-        const kc_edge *edge = nullptr;
-        for (int i = 0; i < n_edges; ++i)
-            if (edges_sorted[i].input_slot == policy_slot) {
-                edge = &edges_sorted[i];
-                break;
-            }
-        if (!edge) edge = &edges_sorted[0];
-        for (int i = 0; i < n; ++i)
-            if (keys[i].output_slot == edge->output_slot && keys[i].output_id == edge->output_id) {
-                slot_index = i;
-                break;
-            }
-    }
+    const int slot_index = policy_slot_index(policy, policy_slot, edges_sorted, n_edges > 0 ? (size_t)n_edges : 0, keys, (size_t)n);
     kc_size size;
     KC_TRY(calculate_size(policy, sizes.data(), n, slot_index, policy_size, &size));
     for (int i = 0; i < n; ++i) out[i] = nullptr;
@@ -1436,8 +1422,7 @@ int kc_live_graph_embed_slot_data_with_id(kc_live_graph *lg, kc_image *image, ui
 try {
     LG_LOCK(lg);
     KC_ARG(image);
-    for (auto &e : lg->embedded)
-        if (e.slot_data_id == embed_id) return KC_ERR_INVALID_SLOT_ID;  // :329-340
+    if (lg->find_embedded(embed_id)) return KC_ERR_INVALID_SLOT_ID;  // :329-340
     image_retain(image);
     lg->embedded.push_back(EmbeddedSlotData{ embed_id, slot_id, image });
     return KC_OK;
@@ -1450,8 +1435,7 @@ int kc_live_graph_embed_slot_data_band(kc_live_graph *lg, kc_image *image, uint3
 try {
     LG_LOCK(lg);
     KC_ARG(image && full_height > 0);
-    for (auto &e : lg->embedded)
-        if (e.slot_data_id == embed_id) return KC_ERR_INVALID_SLOT_ID;
+    if (lg->find_embedded(embed_id)) return KC_ERR_INVALID_SLOT_ID;
     image_retain(image);
     EmbeddedSlotData e{ embed_id, slot_id, image };
     e.band_y0 = band_y0;

@@ -1028,17 +1028,8 @@ int comm_evaluate_partitioned(kc_live_graph &lg, const kc_partition &plan, uint3
         return KC_ERR_INVALID_ARG;
     }
     if (plan.kind == KC_PLAN_BANDS) {
-        const Node *rn = lg.g.find(root);
-        if (!rn) return KC_ERR_INVALID_NODE_ID;
         uint32_t slot = 0;
-        if (rn->type == KC_NODE_GRAPH) {
-            const std::vector<uint32_t> outs = rn->graph ? rn->graph->output_ids() : std::vector<uint32_t>{};
-            if (outs.empty()) return KC_ERR_NO_SLOT_DATA;
-            slot = outs[0];
-        } else {
-            const std::vector<Slot> slots = node_output_slots(*rn);
-            if (!slots.empty()) slot = slots[0].slot_id;
-        }
+        KC_TRY(root_output_slot(lg.g, root, &slot));
         const kc_band_range b = plan.bands[(size_t)rank];
         kc_image *band = nullptr;
         int s = band_evaluate(lg, root, slot, b.y0, b.y1, &band);

@@ -468,19 +468,84 @@ std::vector<uint32_t> NodeGraph::output_ids() const
     return out;
 }
 
+// iterative post-order over get_parents; an edge back into the stack is a cycle
+int ancestors_topological(const NodeGraph &g, uint32_t root, std::vector<uint32_t> &topo)
+{
+    std::map<uint32_t, int> mark;  // 1 = on the stack, 2 = done
+    struct Frame {
+        uint32_t id;
+        std::vector<uint32_t> parents;
+        size_t next;
+    };
+    std::vector<Frame> st;
+    st.push_back(Frame{ root, g.get_parents(root), 0 });
+    mark[root] = 1;
+    while (!st.empty()) {
+        Frame &f = st.back();
+        if (f.next == f.parents.size()) {
+            mark[f.id] = 2;
+            topo.push_back(f.id);
+            st.pop_back();
+            continue;
+        }
+        const uint32_t p = f.parents[f.next++];
+        if (!g.find(p) || mark[p] == 2) continue;
+        if (mark[p] == 1) {
+            set_error("graph has a cycle through node " + std::to_string(p));
+            return KC_ERR_NODE_PROCESSING;
+        }
+        mark[p] = 1;
+        st.push_back(Frame{ p, g.get_parents(p), 0 });
+    }
+    return KC_OK;
+}
+
+int root_output_slot(const NodeGraph &g, uint32_t root, uint32_t *slot)
+{
+    const Node *n = g.find(root);
+    if (!n) return KC_ERR_INVALID_NODE_ID;
+    *slot = 0;
+    if (n->type != KC_NODE_GRAPH) return KC_OK;
+    const std::vector<uint32_t> outs = n->graph ? n->graph->output_ids() : std::vector<uint32_t>{};
+    if (outs.empty()) return KC_ERR_NO_SLOT_DATA;
+    *slot = outs[0];
+    return KC_OK;
+}
+
 // ------------------------------------------------------------------------------------------
 // process_node, src/node/node_type.rs:213-267 (+ resize_buffers, src/shared.rs:141-216)
 // ------------------------------------------------------------------------------------------
+// (a stable insertion sort: a node has a handful of edges, and std::stable_sort takes a heap buffer)
+EdgeList edges_by_input_slot(const kc_edge *edges, size_t n)
+{
+    EdgeList sorted(edges, n);
+    for (size_t i = 1; i < sorted.size(); ++i) {
+        const kc_edge e = sorted[i];
+        size_t j = i;
+        for (; j > 0 && sorted[j - 1].input_slot > e.input_slot; --j) sorted[j] = sorted[j - 1];
+        sorted[j] = e;
+    }
+    return sorted;
+}
+
+int policy_slot_index(int policy, uint32_t policy_slot, const kc_edge *sorted, size_t n_sorted, const kc_edge *producers, size_t n)
+{
+    if (policy != KC_POLICY_SPECIFIC_SLOT || !sorted || n_sorted == 0) return -1;
+    const kc_edge *edge = &sorted[0];
+    for (size_t i = 0; i < n_sorted; ++i)
+        if (sorted[i].input_slot == policy_slot) {
+            edge = &sorted[i];
+            break;
+        }
+    for (size_t i = 0; i < n; ++i)
+        if (producers[i].output_slot == edge->output_slot && producers[i].output_id == edge->output_id) return (int)i;
+    return -1;
+}
+
 static void release_all(SlotList &v)
 {
     for (auto &sd : v) image_release(sd.image);
     v.clear();
-}
-
-static std::string resolve_path(const kc_live_graph &lg, const std::string &p)
-{
-    if (p.empty() || p[0] == '/' || lg.base_dir.empty()) return p;
-    return lg.base_dir + "/" + p;
 }
 
 static kc_image *pixel_image(float v)
@@ -533,29 +598,27 @@ static int process_graph_node(kc_live_graph &parent, const Node &node, const Slo
     return KC_OK;
 }
 
-static int dispatch(kc_live_graph &lg, const Node &node, const SlotList &sd, SlotList &out)
+int dispatch(kc_live_graph &lg, const Node &node, const SlotList &sd, uint32_t full_h, SlotList &out)
 {
-    // process_node_internal, src/node/node_type.rs:98-138
     const uint32_t nid = node.node_id;
     switch (node.type) {
     case KC_NODE_INPUT_RGBA: {
         // input_rgba::process, src/node/input_rgba.rs:7-13: takes input_node_datas[0]
-        if (lg.input_slot_datas.empty()) {
+        const SlotData *in = lg.find_input(node);
+        if (!in) {
             set_error("InputRgba without input slot data (index out of bounds in the reference)");
             return KC_ERR_NODE_PROCESSING;
         }
-        image_retain(lg.input_slot_datas[0].image);
-        out.push_back(SlotData{ nid, 0, lg.input_slot_datas[0].image });
+        image_retain(in->image);
+        out.push_back(SlotData{ nid, 0, in->image });
         return KC_OK;
     }
     case KC_NODE_INPUT_GRAY:
         // input_gray::process, src/node/input_gray.rs:7-16
-        for (auto &in : lg.input_slot_datas)
-            if (in.node_id == nid) {
-                image_retain(in.image);
-                out.push_back(SlotData{ in.node_id, in.slot_id, in.image });
-                break;
-            }
+        if (const SlotData *in = lg.find_input(node)) {
+            image_retain(in->image);
+            out.push_back(*in);
+        }
         return KC_OK;
     case KC_NODE_OUTPUT_GRAY:
     case KC_NODE_OUTPUT_RGBA:
@@ -576,7 +639,7 @@ static int dispatch(kc_live_graph &lg, const Node &node, const SlotList &sd, Slo
         std::vector<uint8_t> px;
         uint32_t w = 0, h = 0;
         int ch = 0;
-        if (png_read(resolve_path(lg, node.text), px, w, h, ch) == KC_OK) {
+        if (png_read(lg.resolve_path(node.text), px, w, h, ch) == KC_OK) {
             KC_TRY(image_from_u8(px.data(), w, h, ch, &img));
         } else {
             img = pixel_image_rgba(1.0f, 0.0f, 1.0f, 1.0f);
@@ -586,12 +649,11 @@ static int dispatch(kc_live_graph &lg, const Node &node, const SlotList &sd, Slo
     }
     case KC_NODE_EMBED:
         // embed::process, src/node/embed.rs:33-50
-        for (auto &e : lg.embedded)
-            if (e.slot_data_id == node.embed_id) {
-                image_retain(e.image);
-                out.push_back(SlotData{ nid, 0, e.image });
-                return KC_OK;
-            }
+        if (const EmbeddedSlotData *e = lg.find_embedded(node.embed_id)) {
+            image_retain(e->image);
+            out.push_back(SlotData{ nid, 0, e->image });
+            return KC_OK;
+        }
         set_error("embedded slot data not found");
         return KC_ERR_NODE_PROCESSING;
     case KC_NODE_WRITE: {
@@ -600,7 +662,7 @@ static int dispatch(kc_live_graph &lg, const Node &node, const SlotList &sd, Slo
             kc_image *img = sd[0].image;
             std::vector<uint8_t> px((size_t)img->w() * img->h() * 4);
             KC_TRY(image_to_u8(img, false, px.data()));
-            KC_TRY(png_write_rgba8(resolve_path(lg, node.text), px.data(), img->w(), img->h()));
+            KC_TRY(png_write_rgba8(lg.resolve_path(node.text), px.data(), img->w(), img->h()));
         }
         return KC_OK;
     }
@@ -620,7 +682,8 @@ static int dispatch(kc_live_graph &lg, const Node &node, const SlotList &sd, Slo
     case KC_NODE_HEIGHT_TO_NORMAL: {
         const SlotData *in = with_slot(sd, 0);
         kc_image *img = nullptr;
-        KC_TRY(height_to_normal_process(in ? in->image : nullptr, &img));
+        if (full_h > 1) KC_TRY(height_to_normal_band(in ? in->image : nullptr, full_h, &img));
+        else KC_TRY(height_to_normal_process(in ? in->image : nullptr, &img));
         if (img) out.push_back(SlotData{ nid, 0, img });
         return KC_OK;
     }
@@ -654,14 +717,7 @@ int process_node(kc_live_graph &lg, const Node &node, const SlotList &inputs, co
         return KC_ERR_INVALID_BUFFER_COUNT;
     }
     // node_type.rs:229-231: edges sorted by input slot (slot datas stay in edge insertion order)
-    // (a stable insertion sort: a node has a handful of edges, and std::stable_sort takes a heap buffer)
-    EdgeList sorted(edges.data(), edges.size());
-    for (size_t i = 1; i < sorted.size(); ++i) {
-        const kc_edge e = sorted[i];
-        size_t j = i;
-        for (; j > 0 && sorted[j - 1].input_slot > e.input_slot; --j) sorted[j] = sorted[j - 1];
-        sorted[j] = e;
-    }
+    const EdgeList sorted = edges_by_input_slot(edges.data(), edges.size());
 
     // resize_buffers, src/shared.rs:141-216
     SlotList resized;
@@ -669,23 +725,8 @@ int process_node(kc_live_graph &lg, const Node &node, const SlotList &inputs, co
     if (!inputs.empty()) {
         SmallVec<kc_size, 8> sizes;
         for (auto &sd : inputs) sizes.push_back(kc_size{ sd.image->w(), sd.image->h() });
-        int slot_index = -1;
-        if (node.policy == KC_POLICY_SPECIFIC_SLOT) {
-            // shared.rs:113-131
-            const kc_edge *edge = nullptr;
-            for (auto &e : sorted)
-                if (e.input_slot == node.policy_slot) {
-                    edge = &e;
-                    break;
-                }
-            if (!edge && !sorted.empty()) edge = &sorted[0];
-            if (edge)
-                for (size_t i = 0; i < inputs.size(); ++i)
-                    if (inputs[i].slot_id == edge->output_slot && inputs[i].node_id == edge->output_id) {
-                        slot_index = (int)i;
-                        break;
-                    }
-        }
+        // inputs[i] is what edges[i] names (process_one), so the edges stand for the producers
+        const int slot_index = policy_slot_index(node.policy, node.policy_slot, sorted.data(), sorted.size(), edges.data(), edges.size());
         kc_size size;
         KC_TRY(calculate_size(node.policy, sizes.data(), (int)sizes.size(), slot_index, node.policy_size, &size));
         for (auto &sd : inputs) {
@@ -719,7 +760,7 @@ int process_node(kc_live_graph &lg, const Node &node, const SlotList &inputs, co
     int s;
     {
         KC_PROF("dispatch");
-        s = dispatch(lg, node, assigned, result);
+        s = dispatch(lg, node, assigned, 0, result);
     }
     release_all(assigned);
     if (s != KC_OK) {
@@ -778,6 +819,27 @@ const SlotData *kc_live_graph::find_slot(uint32_t node, uint32_t slot) const
     for (auto &sd : slots_of(node))
         if (sd.slot_id == slot) return &sd;
     return nullptr;
+}
+
+const EmbeddedSlotData *kc_live_graph::find_embedded(uint32_t embed_id) const
+{
+    for (auto &e : embedded)
+        if (e.slot_data_id == embed_id) return &e;
+    return nullptr;
+}
+
+const SlotData *kc_live_graph::find_input(const Node &n) const
+{
+    if (n.type == KC_NODE_INPUT_RGBA) return input_slot_datas.empty() ? nullptr : &input_slot_datas[0];
+    for (auto &in : input_slot_datas)
+        if (in.node_id == n.node_id) return &in;
+    return nullptr;
+}
+
+std::string kc_live_graph::resolve_path(const std::string &p) const
+{
+    if (p.empty() || p[0] == '/' || base_dir.empty()) return p;
+    return base_dir + "/" + p;
 }
 
 int kc_live_graph::state_of(uint32_t id, int *st) const

@@ -425,6 +425,7 @@ struct Node {
 
     bool is_input() const { return type == KC_NODE_INPUT_GRAY || type == KC_NODE_INPUT_RGBA; }
     bool is_output() const { return type == KC_NODE_OUTPUT_GRAY || type == KC_NODE_OUTPUT_RGBA; }
+    bool is_source() const { return type == KC_NODE_EMBED || type == KC_NODE_IMAGE || is_input(); }  // holds data somebody provided
 };
 
 enum SlotType { SLOT_GRAY = 0, SLOT_RGBA = 1, SLOT_GRAY_OR_RGBA = 2 };
@@ -483,6 +484,10 @@ struct NodeGraph {
 std::vector<Slot> node_input_slots(const Node &n, bool *unimplemented = nullptr);
 std::vector<Slot> node_output_slots(const Node &n, bool *unimplemented = nullptr);
 Node node_from_desc(const kc_node_desc &d);
+// the ancestors of `root` (itself last) in topological order; "graph has a cycle through node N" otherwise
+int ancestors_topological(const NodeGraph &g, uint32_t root, std::vector<uint32_t> &topo);
+// the slot that stands for a requested node: a Graph node's first Output id; slot 0 otherwise (every other node's first output slot)
+int root_output_slot(const NodeGraph &g, uint32_t root, uint32_t *slot);
 
 int graph_from_json(const std::string &text, NodeGraph &g);
 std::string graph_to_json(const NodeGraph &g);
@@ -568,6 +573,11 @@ public:
 };
 using SlotList = SmallVec<SlotData, 8>;
 using EdgeList = SmallVec<kc_edge, 8>;
+// node_type.rs:229-231: a node's edges sorted stably by input slot
+EdgeList edges_by_input_slot(const kc_edge *edges, size_t n);
+// shared.rs:113-131: which of `producers` (the inputs, in input order) a SpecificSlot policy means -- the edge on the named
+// slot, else the one on the lowest connected slot; -1 for every other policy and when nothing is connected
+int policy_slot_index(int policy, uint32_t policy_slot, const kc_edge *sorted, size_t n_sorted, const kc_edge *producers, size_t n);
 
 struct EmbeddedSlotData {
     uint32_t slot_data_id, slot_id;
@@ -608,6 +618,9 @@ struct kc_live_graph {
     void clear_data();
     void remove_nodes_data(uint32_t id);
     const kc::SlotData *find_slot(uint32_t node, uint32_t slot) const;
+    const kc::EmbeddedSlotData *find_embedded(uint32_t embed_id) const;
+    const kc::SlotData *find_input(const kc::Node &n) const;  // InputRgba: the first entry (input_rgba.rs:7-13); InputGray: the node's own
+    std::string resolve_path(const std::string &p) const;     // an Image / Write node's path, relative to base_dir
     int state_of(uint32_t id, int *st) const;
     int set_state(uint32_t id, int st);
     int force_state(uint32_t id, int st);
@@ -665,4 +678,7 @@ void comm_sync();
 // process_node, src/node/node_type.rs:213-248: inputs in edge insertion order.
 int process_node(kc_live_graph &lg, const Node &node, const SlotList &inputs, const std::vector<kc_edge> &edges,
                  SlotList &out);
+// process_node_internal, src/node/node_type.rs:98-138, on assigned inputs.  full_h > 1: `sd` holds row bands of images
+// full_h rows high (bands.cpp), HeightToNormal's with the halo row first; 0: whole images.
+int dispatch(kc_live_graph &lg, const Node &node, const SlotList &sd, uint32_t full_h, SlotList &out);
 }  // namespace kc

@@ -52,8 +52,6 @@ namespace {
 
 enum Kind { SOURCE = 0, REPLICATED = 1, COMPUTE = 2 };
 
-bool is_source(const Node &n) { return n.type == KC_NODE_EMBED || n.type == KC_NODE_IMAGE || n.is_input(); }
-
 // relative cost of evaluating a node (one fused Mix chain ~ 1 whatever its length when nothing is cached)
 double node_weight(const Node &n, bool use_cache)
 {
@@ -85,38 +83,9 @@ int partition_plan(kc_live_graph &lg, uint32_t root, int world, int policy, kc_p
         return KC_ERR_INVALID_ARG;
     }
     const double kTransferCost = transfer_cost();
-    // ---- 1. ancestors in topological order (iterative post-order; an edge into the stack is a cycle)
+    // ---- 1. ancestors in topological order
     std::vector<uint32_t> topo;
-    std::map<uint32_t, int> mark;  // 1 = on the stack, 2 = done
-    {
-        struct Frame {
-            uint32_t id;
-            std::vector<uint32_t> parents;
-            size_t next;
-        };
-        std::vector<Frame> st;
-        st.push_back(Frame{ root, g.get_parents(root), 0 });
-        mark[root] = 1;
-        while (!st.empty()) {
-            Frame &f = st.back();
-            if (f.next == f.parents.size()) {
-                mark[f.id] = 2;
-                topo.push_back(f.id);
-                st.pop_back();
-                continue;
-            }
-            const uint32_t p = f.parents[f.next++];
-            if (!g.find(p)) continue;
-            const int m = mark[p];
-            if (m == 2) continue;
-            if (m == 1) {
-                set_error("graph has a cycle through node " + std::to_string(p));
-                return KC_ERR_NODE_PROCESSING;
-            }
-            mark[p] = 1;
-            st.push_back(Frame{ p, g.get_parents(p), 0 });
-        }
-    }
+    KC_TRY(ancestors_topological(g, root, topo));
     const size_t n = topo.size();
     std::map<uint32_t, size_t> pos;
     for (size_t i = 0; i < n; ++i) pos[topo[i]] = i;
@@ -126,7 +95,7 @@ int partition_plan(kc_live_graph &lg, uint32_t root, int world, int policy, kc_p
     std::vector<int> kind(n, COMPUTE);
     for (size_t i = 0; i < n; ++i) {
         const Node &nd = *g.find(topo[i]);
-        if (is_source(nd)) {
+        if (nd.is_source()) {
             kind[i] = SOURCE;
         } else if (nd.type == KC_NODE_GRAPH || nd.type == KC_NODE_WRITE) {
             kind[i] = COMPUTE;  // a nested graph may read files; a Write has a side effect: exactly one rank runs it

@@ -380,3 +380,128 @@ def test_bands_through_nested_graph_nodes(kc):
     want = orc.RefGraph(g.dict(), embedded={0: orc.Image(planes)}).slot_data(out, 0).image.planes
     assert_planes(whole, want, what="nested Graph nodes vs oracle")
     assert_planes(whole, [(np.float32(1.0) - planes[2]) * planes[2]], what="closed form (1 - b) * b")
+
+
+# ---- the rules the whole-image evaluator, the band walk and kc_resize_buffers share (csrc/graph.cpp) ----
+def _rule_images():
+    from test_graph_rules_host import SIZES
+    return {i: [splitmix_plane(SEED_A + i, c, h, w) for c in range(4)] for i, (w, h) in SIZES.items()}
+
+
+RULE_IMAGES = _rule_images()
+
+
+def whole_bands_oracle(kc, graph, images, root, bands, what):
+    """The node evaluated whole and as `bands`, stacked: both the oracle's result, bit for bit.  Returns the oracle's planes."""
+    from oracle import oracle as orc
+    want = orc.RefGraph(graph, embedded={i: orc.Image(p) for i, p in images.items()}).slot_data(root, 0).image.planes
+    _, lg = build(kc, graph, images)
+    whole = lg.await_clean(root).slot_data(root, 0).image.planes()
+    assert [p.shape for p in whole] == [p.shape for p in want], what
+    assert_planes(whole, want, what=what + ", whole")
+    _, lg2 = build(kc, graph, images)
+    parts = [lg2.evaluate_band(root, y0, y1).planes() for (y0, y1) in bands]
+    assert all(p[0].shape[0] == y1 - y0 for p, (y0, y1) in zip(parts, bands))
+    assert_planes([np.concatenate([p[c] for p in parts], axis=0) for c in range(len(want))], want, what=what + ", bands")
+    return want
+
+
+def resize_buffers_then_mix(kc, graph, mix, images):
+    """kc_resize_buffers on the Mix node's inputs (images and keys in edge insertion order, the edges sorted by input slot,
+    the node's policy), then kc_mix_process on what comes back for slots 0 and 1."""
+    import ctypes as C
+    from kanter_core_amd import _lib
+    node = graph["nodes"][mix]
+    edges = [e for e in graph["edges"] if e["input_id"] == mix]
+    embed_of = {n["node_id"]: n["node_type"]["Embed"] for n in graph["nodes"] if isinstance(n["node_type"], dict) and "Embed" in n["node_type"]}
+    imgs = [kc.SlotImage.from_planes(images[embed_of[e["output_id"]]]) for e in edges]
+    as_c = lambda es: (_lib.kc_edge * len(es))(*[_lib.kc_edge(e["output_id"], e["input_id"], e["output_slot"], e["input_slot"]) for e in es])  # noqa: E731
+    policy = node["resize_policy"]
+    kind = ["MostPixels", "LeastPixels", "LargestAxes", "SmallestAxes", "SpecificSlot", "SpecificSize"].index(policy if isinstance(policy, str) else next(iter(policy)))
+    slot = policy["SpecificSlot"] if kind == 4 else 0
+    size = _lib.kc_size(policy["SpecificSize"]["width"], policy["SpecificSize"]["height"]) if kind == 5 else _lib.kc_size(0, 0)
+    out = (C.c_void_p * len(imgs))()
+    rc = _lib.load().kc_resize_buffers((C.c_void_p * len(imgs))(*[i._h.value for i in imgs]), as_c(edges), len(imgs),
+                                       as_c(sorted(edges, key=lambda e: e["input_slot"])), len(edges), kind, slot, size,
+                                       getattr(kc.ResizeFilter, node["resize_filter"]), out)
+    assert rc == 0
+    resized = {e["input_slot"]: kc.SlotImage(o) for e, o in zip(edges, out)}
+    return kc.mix_process(resized[0], resized[1], kc.MixType.Add).planes()
+
+
+def _policy_cases():
+    from test_graph_rules_host import POLICY_CASES
+    return POLICY_CASES
+
+
+@pytest.mark.parametrize("make,policy", _policy_cases())
+def test_policy_graphs_whole_bands_and_resize_buffers_equal_the_oracle(kc, make, policy):
+    """Edge insertion order that differs from slot order, under every resize policy: the whole-image evaluator, two uneven
+    bands and (for the Mix) the C entry point kc_resize_buffers pick the same input and give the oracle's size and bits."""
+    from test_graph_rules_host import mix_right_first, oracle_size
+    graph, root = make(policy)
+    h = oracle_size(graph, root)[1]
+    bands = [(0, 5), (5, h)] if h > 5 else [(0, h)]  # (a 5-row result is the first band alone)
+    want = whole_bands_oracle(kc, graph, RULE_IMAGES, root, bands, "%s %s" % (make.__name__, policy))
+    if make is mix_right_first:
+        got = resize_buffers_then_mix(kc, graph, root, RULE_IMAGES)
+        assert [p.shape for p in got] == [p.shape for p in want]
+        assert_planes(got, want, what="kc_resize_buffers + mix, %s" % (policy,))
+
+
+def _mix_right_only():
+    g = G()
+    e = g.add({"Embed": 1})
+    mix = g.add({"Mix": "Subtract"})
+    g.connect(e, mix, 0, 1)
+    return g.dict(), mix, [(0, 5), (5, 20)]
+
+
+def _combine_1_and_3():
+    g = G()
+    e0, e1 = g.add({"Embed": 0}), g.add({"Embed": 1})
+    s0, s1 = g.add("SeparateRgba"), g.add("SeparateRgba")
+    g.connect(e0, s0, 0, 0)
+    g.connect(e1, s1, 0, 0)
+    comb = g.add("CombineRgba")
+    g.connect(s1, comb, 2, 3)
+    g.connect(s0, comb, 0, 1)
+    return g.dict(), comb, [(0, 5), (5, 16)]
+
+
+def _h2n_of_rows(rows):
+    g = G()
+    e = g.add({"Embed": 7})
+    sep = g.add("SeparateRgba")
+    g.connect(e, sep, 0, 0)
+    h2n = g.add("HeightToNormal")
+    g.connect(sep, h2n, 1, 0)
+    return g.dict(), h2n, [(y, y + 1) for y in range(rows)]
+
+
+def _output_alone(kind):
+    g = G()
+    out = g.add({kind: "out"})
+    return g.dict(), out, [(0, 1)]
+
+
+OPERATOR_EDGE_CASES = {
+    "mix_right_only": (_mix_right_only, None),
+    "combine_slots_1_and_3": (_combine_1_and_3, None),
+    "output_rgba_unconnected": (lambda: _output_alone("OutputRgba"), None),
+    "output_gray_unconnected": (lambda: _output_alone("OutputGray"), None),
+    "height_to_normal_1_row": (lambda: _h2n_of_rows(1), (1, 9)),
+    "height_to_normal_2_rows_2_bands": (lambda: _h2n_of_rows(2), (2, 9)),
+}
+
+
+@pytest.mark.parametrize("case", sorted(OPERATOR_EDGE_CASES))
+def test_operator_edge_cases_whole_bands_and_oracle(kc, case):
+    """What an operator does with missing inputs and with one-row images, through the one operator switch: whole image ==
+    stacked bands == oracle."""
+    make, h2n_shape = OPERATOR_EDGE_CASES[case]
+    graph, root, bands = make()
+    images = dict(RULE_IMAGES)
+    if h2n_shape:
+        images[7] = [splitmix_plane(SEED_B, c, *h2n_shape) for c in range(4)]
+    whole_bands_oracle(kc, graph, images, root, bands, case)
