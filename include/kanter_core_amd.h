@@ -206,7 +206,8 @@ KC_API int kc_stats_algorithmic_bytes(uint64_t *bytes);
  * lane, op set MODE 0 {+, -, *}, 1 + divide, 2 + pow, and its nontemporal form), "chain_k0_m<MODE>" (no input plane),
  * "chain1_nt<0-7>" (a one-step kernel with its nontemporal bits: 1 the start plane, 2 the operand, 4 the result),
  * "specialized_nt_<3 hex digits>" (a kernel compiled at run time and its cache-policy bits: 0x001 << k input plane k < 8,
- * 0x100 the result). */
+ * 0x100 the result), "specialized_nt_<3 hex digits>_q2" / "_q4" when that kernel handles 2 / 4 float4 per lane instead of one
+ * (kc_set_chain_quads). */
 KC_API int kc_stats_counter(const char *name, uint64_t *value);
 KC_API int kc_pool_trim(void);
 /* Run-time specialisation of the fused Mix-chain kernel.  A chain of N Mix nodes (src/node/mix.rs:136-192
@@ -227,6 +228,15 @@ KC_API int kc_specialize_stats(uint64_t *kernels_compiled, uint64_t *compiles_fa
  * without a device.  The generated source is copied to `source` (NUL-terminated, truncated to `cap`) when given. */
 KC_API int kc_specialize_compile_check(const uint32_t *words, uint32_t n_ops, uint32_t n_in, int start_src, int flat,
                                        char *source, size_t cap);
+/* The same for the plain chain kernel under the cache-policy mask `nt_mask` (bits as in "specialized_nt_<hex>"). */
+KC_API int kc_specialize_compile_check_mask(const uint32_t *words, uint32_t n_ops, uint32_t n_in, int start_src, int flat,
+                                            uint32_t nt_mask, char *source, size_t cap);
+/* float4 per lane of the compiled plain chain kernels, for A/B runs only.  0 (default): the generator's rule -- two where a
+ * flat {+, -, *} program of at most 16 records leaves at least one input plain (cache resident) beside a nontemporal input or result, so that the
+ * body of one quad runs under the outstanding loads of the next; one everywhere else.  1, 2, 4: that many where the rule
+ * allows more than one.  Part of a kernel's signature: changing it never launches a kernel with another form's grid. */
+KC_API int kc_set_chain_quads(int quads);
+KC_API int kc_get_chain_quads(void);
 /* The same for a program that runs inside the integer-ratio up-sampling kernel (the resampled operand is input slot
  * n_in - 1; `taps` = 1 or 3 per axis, `wide` = the 1024-column tile form): src/shared.rs:159-199 feeding
  * src/node/mix.rs:136-192 in one launch. */

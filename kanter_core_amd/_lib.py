@@ -109,6 +109,9 @@ SIGNATURES = {
     "kc_specialize_wait": (C.c_int, []),
     "kc_specialize_stats": (C.c_int, [C.POINTER(C.c_uint64)] * 4),
     "kc_specialize_compile_check": (C.c_int, [c_u32p, C.c_uint32, C.c_uint32, C.c_int, C.c_int, C.c_char_p, C.c_size_t]),
+    "kc_specialize_compile_check_mask": (C.c_int, [c_u32p, C.c_uint32, C.c_uint32, C.c_int, C.c_int, C.c_uint32, C.c_char_p, C.c_size_t]),
+    "kc_set_chain_quads": (C.c_int, [C.c_int]),
+    "kc_get_chain_quads": (C.c_int, []),
     "kc_specialize_compile_check_upsample": (C.c_int, [c_u32p, C.c_uint32, C.c_uint32, C.c_int, C.c_uint32, C.c_int, C.c_char_p,
                                                        C.c_size_t]),
     "kc_stats_algorithmic_bytes": (C.c_int, [C.POINTER(C.c_uint64)]),

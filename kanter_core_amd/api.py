@@ -237,6 +237,25 @@ def specialize_compile_check(words, n_in, start_src=0, flat=True):
     return buf.value.decode()
 
 
+def specialize_compile_check_mask(words, n_in, nt_mask, start_src=0, flat=True):
+    """The same for the plain chain kernel under a cache-policy mask (and the current chain_quads setting)."""
+    arr = (C.c_uint32 * len(words))(*words)
+    buf = C.create_string_buffer(1 << 17)
+    _check(_lib.load().kc_specialize_compile_check_mask(arr, len(words), int(n_in), int(start_src), int(bool(flat)), int(nt_mask),
+                                                        buf, len(buf)))
+    return buf.value.decode()
+
+
+def set_chain_quads(quads):
+    """float4 per lane of the compiled chain kernels where the generator's rule allows more than one: 0 the rule's own choice,
+    1 / 2 / 4 forced (A/B runs)."""
+    _check(_lib.load().kc_set_chain_quads(int(quads)))
+
+
+def get_chain_quads():
+    return _lib.load().kc_get_chain_quads()
+
+
 def specialize_compile_check_upsample(words, n_in, start_src=0, taps=3, wide=True):
     """The same for a program that runs inside the integer-ratio up-sampling kernel (input n_in - 1 = the resampled
     operand).  Returns the generated source."""

@@ -379,6 +379,52 @@ try {
 }
 KC_CATCH
 
+int kc_specialize_compile_check_mask(const uint32_t *words, uint32_t n_ops, uint32_t n_in, int start_src, int flat, uint32_t nt_mask,
+                                     char *source, size_t cap)
+try {
+    KC_ARG(words && n_ops >= 1 && n_ops <= (uint32_t)KC_CHAIN_MAX_OPS && n_in <= (uint32_t)KC_CHAIN_MAX_IN);
+    KC_ARG(start_src >= -1 && start_src < (int)n_in);
+    ChainProgram P;
+    std::memset(&P, 0, sizeof P);
+    P.n_ops = n_ops;
+    P.n_in = n_in;
+    P.start_src = start_src;
+    P.rows = flat ? 1u : 2u;
+    P.row_units = 1;
+    P.nt_mask = nt_mask;
+    for (uint32_t i = 0; i < n_ops; ++i) {
+        const uint32_t from = (words[i] >> 8) & 0xffu, level = words[i] >> 16;
+        KC_ARG((words[i] & 0xffu) <= CH_SAVE_LOAD && (from <= n_in || (from == (uint32_t)KC_CHAIN_SRC_SAVED && (words[i] & 0xffu) != CH_SAVE_LOAD)));
+        KC_ARG(level < (uint32_t)KC_CHAIN_MAX_SAVED && (level == 0 || from == (uint32_t)KC_CHAIN_SRC_SAVED || (words[i] & 0xffu) == CH_SAVE_LOAD));
+        ((i & 1u) ? P.step[0][i / 2].b : P.step[0][i / 2].a).word = words[i];
+    }
+    if (source && cap) {
+        const std::string src = specialize_source(P);
+        std::snprintf(source, cap, "%s", src.c_str());
+    }
+    std::string log;
+    int s = specialize_compile_only(P, &log);
+    if (s != KC_OK) set_error("specialised chain kernel did not compile: " + log);
+    return s;
+}
+KC_CATCH
+
+int kc_set_chain_quads(int quads)
+try {
+    const int s = specialize_set_chain_quads(quads);
+    if (s != KC_OK) set_error("kc_set_chain_quads accepts 0, 1, 2 or 4");
+    return s;
+}
+KC_CATCH
+
+int kc_get_chain_quads(void)
+try {
+    return specialize_get_chain_quads();
+}
+catch (...) {
+    return 0;
+}
+
 int kc_kernel_cache_set_dir(const char *dir)
 try {
     Lock lk(ctx().mu);

@@ -371,7 +371,8 @@ int resize_force_many(kc_plane *const *planes, int n);  // same; equal resamples
 int chain_resize_launch(const ChainProgram &P, int batch, int mode, kc_plane *const *sampled, bool *launched);
 
 // ---- run-time specialisation of the chain kernel (specialize.cpp) ----
-hipError_t launch_chain_specialized(const ChainProgram &P, int batch, hipStream_t s, bool *launched, uint32_t *nt_mask);
+// *nt_mask, *quads (optional): the cache-policy bits and the float4 per lane of the kernel that was launched
+hipError_t launch_chain_specialized(const ChainProgram &P, int batch, hipStream_t s, bool *launched, uint32_t *nt_mask, uint32_t *quads = nullptr);
 // Which streams of a launch are marked nontemporal: `in_bytes` / `out_bytes` = what the launch reads from its n_resident
 // full-size input planes / writes, summed over its channels, under the options o.  Returns the ChainProgram::nt_mask bits.
 uint32_t cache_policy_mask(uint64_t in_bytes, uint64_t out_bytes, uint32_t n_resident, const Options &o = options());
@@ -380,6 +381,8 @@ hipError_t chain_dispatch(ChainProgram &P, int batch, int mode, uint32_t w, uint
 hipError_t launch_upsample_chain_specialized(const ChainProgram &P, int batch, const UpsampleArgs &U, hipStream_t s, bool *launched);
 int specialize_set_mode(int mode, int after);  // 0 off, 1 background compile after `after` sightings, 2 compile at once
 int specialize_get_mode();
+int specialize_set_chain_quads(int quads);  // 0 the generator's rule, 1 / 2 / 4 forced where the rule allows more than one
+int specialize_get_chain_quads();
 void specialize_wait();
 void specialize_stats(uint64_t *compiled, uint64_t *failed, uint64_t *launches, uint64_t *pending);
 std::string specialize_last_log();

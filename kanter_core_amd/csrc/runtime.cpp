@@ -604,13 +604,14 @@ uint32_t cache_policy_mask(uint64_t in_bytes, uint64_t out_bytes, uint32_t n_res
 // kc_stats_counter names of the chain forms chain_dispatch launches, built once.
 // chain_interp_k<K>_u<U>_m<MODE>[_nt]: chain_kernel<K, U, MODE, NT>; chain_k0_m<MODE>: chain_kernel_k0<MODE>;
 // chain1_nt<bits>: chain1_kernel's nontemporal bits (1 start, 2 operand, 4 result); specialized_nt_<hex>: the cache-policy
-// bits a compiled kernel carries (bits 0-7 inputs 0-7, 0x100 the result; the bits of inputs 8-15 are not part of the name).
+// bits a compiled kernel carries (bits 0-7 inputs 0-7, 0x100 the result; the bits of inputs 8-15 are not part of the name),
+// with "_q2" / "_q4" behind it when the kernel handles that many float4 per lane (specialize.cpp, chain_quads_for).
 namespace {
 struct ChainCounterNames {
     std::string interp[5][9][3][2];  // [K][U][MODE][NT]; U in {1, 2, 4, 6, 8}
     std::string k0[3];
     std::string chain1[8];
-    std::string spec[0x200];
+    std::string spec[0x200], spec_q2[0x200], spec_q4[0x200];
     ChainCounterNames()
     {
         char buf[64];
@@ -626,6 +627,8 @@ struct ChainCounterNames {
         for (int b = 0; b < 0x200; ++b) {
             std::snprintf(buf, sizeof buf, "specialized_nt_%03x", b);
             spec[b] = buf;
+            spec_q2[b] = spec[b] + "_q2";
+            spec_q4[b] = spec[b] + "_q4";
         }
     }
 };
@@ -687,9 +690,12 @@ hipError_t chain_dispatch(ChainProgram &P, int batch, int mode, uint32_t w, uint
     }
     if (!launched) {
         // a program-specialised straight-line kernel if one has been compiled (specialize.cpp) ...
-        uint32_t spec_nt = 0;
-        hipError_t e = launch_chain_specialized(P, batch, c.stream, &launched, &spec_nt);
-        if (e == hipSuccess && launched) c.counters[chain_counter_names().spec[spec_nt & 0x1ffu]]++;
+        uint32_t spec_nt = 0, spec_quads = 1;
+        hipError_t e = launch_chain_specialized(P, batch, c.stream, &launched, &spec_nt, &spec_quads);
+        if (e == hipSuccess && launched) {
+            const ChainCounterNames &names = chain_counter_names();
+            c.counters[(spec_quads == 2 ? names.spec_q2 : spec_quads == 4 ? names.spec_q4 : names.spec)[spec_nt & 0x1ffu]]++;
+        }
         // ... otherwise the interpreter -- which does not know the codes of a program that joins two chains (chain_launch
         // never sends it one; a replay of such a launch after kc_set_specialize(0) can)
         if (e == hipSuccess && !launched) {
