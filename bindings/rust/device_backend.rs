@@ -124,6 +124,20 @@ impl SlotImage {
         check(unsafe { kc_image_to_bc(self.raw(), format, flags, out.as_mut_ptr(), out.len()) })?;
         Ok(out)
     }
+    /// The BC blocks of the whole mip chain (kc_image_to_bc_mips): level k is max(1, w >> k) by max(1, h >> k), the 2 x 2 box of
+    /// the level above it in f32, built on the device; the levels follow one another, tightly packed, down to 1 x 1.  Returns the
+    /// bytes and the offset of every level (kc_bc_mip_layout).
+    pub fn to_bc_mips(&self, format: i32, srgb: bool) -> Result<(Vec<u8>, Vec<usize>)> {
+        let s = self.size()?;
+        let (mut levels, mut total) = (0u32, 0usize);
+        check(unsafe { kc_bc_mip_layout(s.width, s.height, format, &mut levels, ptr::null_mut(), 0, &mut total) })?;
+        let mut offsets = vec![0usize; levels as usize];
+        check(unsafe { kc_bc_mip_layout(s.width, s.height, format, &mut levels, offsets.as_mut_ptr(), levels, &mut total) })?;
+        let mut out = vec![0u8; total];
+        let flags = if srgb { KC_BC_SRGB } else { 0 };
+        check(unsafe { kc_image_to_bc_mips(self.raw(), format, flags, out.as_mut_ptr(), out.len()) })?;
+        Ok((out, offsets))
+    }
 }
 
 /// src/shared.rs:218-261 (decode with the `image` crate as before, then hand the u8 samples over).

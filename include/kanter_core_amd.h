@@ -207,7 +207,7 @@ KC_API int kc_stats_algorithmic_bytes(uint64_t *bytes);
  * "chain1_nt<0-7>" (a one-step kernel with its nontemporal bits: 1 the start plane, 2 the operand, 4 the result),
  * "specialized_nt_<3 hex digits>" (a kernel compiled at run time and its cache-policy bits: 0x001 << k input plane k < 8,
  * 0x100 the result), "specialized_nt_<3 hex digits>_q2" / "_q4" when that kernel handles 2 / 4 float4 per lane instead of one
- * (kc_set_chain_quads). */
+ * (kc_set_chain_quads).  The mip kernels (one per launch): "mip_pyramid", "mip_level". */
 KC_API int kc_stats_counter(const char *name, uint64_t *value);
 KC_API int kc_pool_trim(void);
 /* Run-time specialisation of the fused Mix-chain kernel.  A chain of N Mix nodes (src/node/mix.rs:136-192
@@ -437,6 +437,62 @@ typedef struct kc_bc_image {
 KC_API int kc_bc_image_validate(const kc_bc_image *d, size_t *extent_bytes);
 KC_API int kc_image_to_bc(kc_image *img, int format, uint32_t flags, uint8_t *host, size_t host_bytes);
 KC_API int kc_image_to_bc_device(kc_image *img, const kc_bc_image *dst, uint32_t flags, void *hip_stream);
+/* Mip chains, built on the device, and their export as BC textures and DDS files: what a renderer samples is a chain, not one
+ * level.  The rule is f32 throughout and bit-exact (tests/mip_ref.py is the same rule in numpy).
+ *   Levels.   Level 0 is the image; level k is max(1, w >> k) by max(1, h >> k); there are L = 1 + floor(log2(max(w, h)))
+ *             levels, the last 1 x 1.
+ *   A texel.  For a level made from the source level s of size (w, h), every plane on its own:
+ *                 x0 = 2x, x1 = min(2x + 1, w - 1), y0 = 2y, y1 = min(2y + 1, h - 1)
+ *                 d(x, y) = ((s(x0, y0) + s(x1, y0)) + (s(x0, y1) + s(x1, y1))) * 0.25f
+ *             three f32 additions in exactly that order and one multiplication.  Nothing is fused, denormals are kept, nothing
+ *             is clamped; NaN and the infinities follow IEEE (inf + -inf = NaN; a source of only -0.0 gives -0.0); NaN payload
+ *             and sign are not part of the contract.  x1 and y1 clamp only when that extent of the source is already 1.  With
+ *             an odd source extent the last column or row does not contribute: this is the usual 2 x 2 box, not a filter over
+ *             the whole footprint -- kc_resize_image is the filtered minification of odd sizes.
+ *   Level k depends only on level k - 1 as stored: each level is rounded to f32 before the next is made, so the fused kernel
+ *             (up to six levels per launch from one read of a 64 x 64 tile) and the level-by-level one give the same bits.
+ *   Planes.   A constant plane stays a constant plane at every level, its value the same expression in f32 on the host,
+ *             ((c + c) + (c + c)) * 0.25f once per level (not c for very large or denormal c).  Planes that alias
+ *             (kc_image_as_type's [p, p, p, ones]) are reduced once and the level images alias the same way.  Pending chains and
+ *             deferred resizes run first.  Planes are linear f32 and sRGB is applied at export (KC_BC_SRGB, kc_image_to_u8 with
+ *             srgb), so the average is taken in linear light.
+ *   kc_mip_level_count   L for a size; arithmetic, no kc_init needed.
+ *   kc_image_build_mips  levels[0] = img itself (+1 reference), levels[k] a new image of the same kind (+1 reference each);
+ *                        `*count` = L whenever the image is known; cap < L is KC_ERR_INVALID_ARG with nothing launched and nothing
+ *                        allocated.  Enqueued on the library's stream; the call does not wait.  A failure part-way releases what
+ *                        it made.  KC_MIP_PER_LEVEL: one launch per level (A/B runs and tests; the same bits).
+ *                        kc_stats: one launch per up to six levels while both extents still halve, one per level after that
+ *                        (4096 x 4096: two; counters "mip_pyramid", "mip_level"); 4 w h algorithmic bytes per distinct resident
+ *                        plane read plus 4 sum_{k >= 1} W_k H_k per plane written; constant planes launch nothing.
+ *   kc_bc_mip_layout     the BC chain of a size: level k's blocks are tightly packed rows, ceil(W_k / 4) x ceil(H_k / 4) blocks
+ *                        (the 2 x 2 and 1 x 1 levels are one edge block), exactly what kc_image_to_bc writes for that level;
+ *                        levels 0 .. L - 1 follow one another.  `*levels` = L, offsets[k] = level k's first byte (`offsets` may be
+ *                        NULL; otherwise cap < L is KC_ERR_INVALID_ARG), `*total_bytes` = the chain's bytes.  Arithmetic, no kc_init.
+ *   kc_image_to_bc_mips  kc_image_build_mips, then the encoder of kc_image_to_bc once per level, into host memory (`host_bytes`
+ *                        at least the total); blocks until the bytes are there.  flags: KC_BC_SRGB (BC1 / BC3) | KC_MIP_PER_LEVEL.
+ *   kc_image_to_bc_mips_device  the same into device memory (a multiple of the block bytes; `bytes` at least the total, the
+ *                        total's extent in one allocation of the library's device), ordered against `hip_stream` by the two event
+ *                        edges of kc_image_to_bc_device.  Bytes past the total are never written.
+ *                        kc_live_graph_buffer_bc_mips: the same for a slot's image.
+ *   kc_dds_header        the 148 bytes in front of the blocks in a .dds file, DX10 form: "DDS ", DDS_HEADER (dwSize 124, flags
+ *                        0x81007 plus 0x20000 with levels > 1, height, width, level 0's block bytes as the linear size, depth 0,
+ *                        `levels` as the mip count, pixel format {32, DDPF_FOURCC, "DX10"}, caps 0x1000 plus 0x400008 with
+ *                        levels > 1), DDS_HEADER_DXT10 {dxgiFormat, TEXTURE2D, 0, 1, 0}; dxgiFormat BC1 71, BC3 77, BC4 80,
+ *                        BC5 83, with KC_BC_SRGB BC1 72, BC3 78.  1 <= levels <= L.  `*bytes` (optional) = 148.  No kc_init.
+ *   kc_image_write_dds   the header, then the chain (with_mips != 0) or level 0 alone.
+ * Errors, in this order: unknown flag bits, or KC_BC_SRGB with BC4 / BC5, KC_ERR_UNSUPPORTED; a NULL argument, a zero size, an
+ * unknown format, a size below the total KC_ERR_INVALID_ARG; KC_ERR_NO_DEVICE before kc_init; KC_ERR_NO_SLOT_DATA where
+ * kc_live_graph_buffer_bc returns it; KC_ERR_IO for a file that cannot be written. */
+#define KC_MIP_PER_LEVEL 2u  /* one launch of the one-level kernel per level instead of the fused pyramid kernel; a bit of its
+                                own beside KC_BC_SRGB, since the chain exporters take both in one flags word */
+KC_API int kc_mip_level_count(uint32_t width, uint32_t height, uint32_t *levels);
+KC_API int kc_image_build_mips(kc_image *img, uint32_t flags, kc_image **levels, uint32_t cap, uint32_t *count);
+KC_API int kc_bc_mip_layout(uint32_t width, uint32_t height, int format, uint32_t *levels, size_t *offsets, uint32_t cap,
+                            size_t *total_bytes);
+KC_API int kc_image_to_bc_mips(kc_image *img, int format, uint32_t flags, uint8_t *host, size_t host_bytes);
+KC_API int kc_image_to_bc_mips_device(kc_image *img, int format, uint32_t flags, void *device_ptr, size_t bytes, void *hip_stream);
+KC_API int kc_dds_header(uint32_t width, uint32_t height, int format, uint32_t flags, uint32_t levels, uint8_t out[148], size_t *bytes);
+KC_API int kc_image_write_dds(kc_image *img, const char *path, int format, uint32_t flags, int with_mips);
 /* read_slot_image, src/shared.rs:218-261 (PNG only; decode on host, planes built on device). */
 KC_API int kc_image_read_png(const char *path, kc_image **out);
 KC_API int kc_image_write_png(kc_image *img, const char *path);        /* src/node/write.rs:5-21 */
@@ -540,6 +596,8 @@ KC_API int kc_live_graph_buffer_channel_stats(kc_live_graph *lg, uint32_t node_i
                                               kc_channel_stats *out);
 KC_API int kc_live_graph_buffer_bc(kc_live_graph *lg, uint32_t node_id, uint32_t slot_id, const kc_bc_image *dst,
                                    uint32_t flags, void *hip_stream); /* kc_image_to_bc_device of a slot's image */
+KC_API int kc_live_graph_buffer_bc_mips(kc_live_graph *lg, uint32_t node_id, uint32_t slot_id, int format, uint32_t flags,
+                                        void *device_ptr, size_t bytes, void *hip_stream); /* kc_image_to_bc_mips_device likewise */
 KC_API int kc_live_graph_embed_slot_data_with_id(kc_live_graph *lg, kc_image *image, uint32_t slot_id, uint32_t embed_id); /* :324-341 */
 KC_API int kc_live_graph_add_input_slot_data(kc_live_graph *lg, uint32_t node_id, uint32_t slot_id, kc_image *image);     /* :347-350 */
 KC_API int kc_live_graph_changed_consume(kc_live_graph *lg, uint32_t *ids, uint32_t cap, uint32_t *count);               /* :156-160 */

@@ -158,6 +158,14 @@ SIGNATURES = {
     "kc_bc_image_validate": (C.c_int, [C.POINTER(kc_bc_image), C.POINTER(C.c_size_t)]),
     "kc_image_to_bc": (C.c_int, [c_vp, C.c_int, C.c_uint32, c_vp, C.c_size_t]),
     "kc_image_to_bc_device": (C.c_int, [c_vp, C.POINTER(kc_bc_image), C.c_uint32, c_vp]),
+    "kc_mip_level_count": (C.c_int, [C.c_uint32, C.c_uint32, C.POINTER(C.c_uint32)]),
+    "kc_image_build_mips": (C.c_int, [c_vp, C.c_uint32, C.POINTER(c_vp), C.c_uint32, C.POINTER(C.c_uint32)]),
+    "kc_bc_mip_layout": (C.c_int, [C.c_uint32, C.c_uint32, C.c_int, C.POINTER(C.c_uint32), C.POINTER(C.c_size_t), C.c_uint32,
+                                   C.POINTER(C.c_size_t)]),
+    "kc_image_to_bc_mips": (C.c_int, [c_vp, C.c_int, C.c_uint32, c_vp, C.c_size_t]),
+    "kc_image_to_bc_mips_device": (C.c_int, [c_vp, C.c_int, C.c_uint32, c_vp, C.c_size_t, c_vp]),
+    "kc_dds_header": (C.c_int, [C.c_uint32, C.c_uint32, C.c_int, C.c_uint32, C.c_uint32, c_vp, C.POINTER(C.c_size_t)]),
+    "kc_image_write_dds": (C.c_int, [c_vp, C.c_char_p, C.c_int, C.c_uint32, C.c_int]),
     "kc_image_from_f32": (C.c_int, [C.POINTER(c_vp), C.c_int, C.c_uint32, C.c_uint32, C.POINTER(c_vp)]),
     "kc_image_to_f32": (C.c_int, [c_vp, C.POINTER(c_vp), C.c_int]),
     "kc_image_read_png": (C.c_int, [C.c_char_p, C.POINTER(c_vp)]),
@@ -223,6 +231,7 @@ SIGNATURES = {
     "kc_live_graph_buffer_device": (C.c_int, [c_vp, C.c_uint32, C.c_uint32, C.POINTER(kc_device_image), C.c_uint32, c_vp]),
     "kc_live_graph_buffer_channel_stats": (C.c_int, [c_vp, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(kc_channel_stats)]),
     "kc_live_graph_buffer_bc": (C.c_int, [c_vp, C.c_uint32, C.c_uint32, C.POINTER(kc_bc_image), C.c_uint32, c_vp]),
+    "kc_live_graph_buffer_bc_mips": (C.c_int, [c_vp, C.c_uint32, C.c_uint32, C.c_int, C.c_uint32, c_vp, C.c_size_t, c_vp]),
     "kc_live_graph_embed_slot_data_with_id": (C.c_int, [c_vp, c_vp, C.c_uint32, C.c_uint32]),
     "kc_live_graph_add_input_slot_data": (C.c_int, [c_vp, C.c_uint32, C.c_uint32, c_vp]),
     "kc_live_graph_changed_consume": (C.c_int, [c_vp, c_u32p, C.c_uint32, c_u32p]),

@@ -673,6 +673,62 @@ def _bc_export(call, size, fmt, srgb, out):
     return out
 
 
+MIP_PER_LEVEL = 2  # kc_image_build_mips and the chain exporters: one launch of the one-level kernel per level
+
+
+def mip_level_count(width, height):
+    """Levels of the mip chain of a width x height image: 1 + floor(log2(max(width, height))) (kc_mip_level_count; no device)."""
+    n = C.c_uint32()
+    _check(_lib.load().kc_mip_level_count(width, height, C.byref(n)))
+    return n.value
+
+
+def bc_mip_layout(width, height, fmt):
+    """-> (offsets, total_bytes) of the BC mip chain of a width x height image (kc_bc_mip_layout; no device): level k's tightly
+    packed blocks start at offsets[k], the chain is total_bytes long."""
+    f = _bc_format(fmt)
+    n = mip_level_count(width, height)
+    offs = (C.c_size_t * n)()
+    total = C.c_size_t()
+    _check(_lib.load().kc_bc_mip_layout(width, height, f, None, offs, n, C.byref(total)))
+    return list(offs), total.value
+
+
+def dds_header(width, height, fmt, srgb=False, levels=None):
+    """-> the 148 bytes in front of the blocks of a .dds file (kc_dds_header; no device); levels: the whole chain by default."""
+    f = _bc_format(fmt)
+    out = (C.c_uint8 * 148)()
+    _check(_lib.load().kc_dds_header(width, height, f, BC_SRGB if srgb else 0, mip_level_count(width, height) if levels is None else levels,
+                                     out, None))
+    return bytes(out)
+
+
+def _bc_mip_views(buf, size, fmt):
+    """One (by, bx, block bytes) view per level of a flat chain buffer (numpy array or tensor)."""
+    f = _bc_format(fmt)
+    offs, total = bc_mip_layout(size.width, size.height, f)
+    bb = BC_BLOCK_BYTES[f]
+    views = []
+    for k, o in enumerate(offs):
+        bx, by = (max(1, size.width >> k) + 3) // 4, (max(1, size.height >> k) + 3) // 4
+        views.append(buf[o:o + bx * by * bb].reshape(by, bx, bb))
+    return views
+
+
+def _bc_mips_export(call, size, fmt, srgb, per_level, out):
+    """Allocates (or takes) a flat uint8 tensor of at least the chain's bytes and runs `call(fmt, flags, ptr, bytes, stream)`."""
+    import torch
+    f = _bc_format(fmt)
+    offs, total = bc_mip_layout(size.width, size.height, f)
+    if out is None:
+        out = torch.empty((total,), dtype=torch.uint8, device=torch.device("cuda", torch.cuda.current_device()))
+    if out.dtype != torch.uint8 or out.dim() != 1 or not out.is_contiguous() or out.numel() < total:
+        raise ValueError("out must be a contiguous 1-D uint8 tensor of at least %d bytes" % total)
+    flags = (BC_SRGB if srgb else 0) | (MIP_PER_LEVEL if per_level else 0)
+    _check(_on_torch_stream(out, lambda stream: call(f, flags, C.c_void_p(out.data_ptr()), out.numel(), stream)))
+    return out, offs
+
+
 STATS_HISTOGRAM = 1  # kc_image_channel_stats: also the u8 histograms
 STATS_SRGB = 2       # ... binned as to_u8_srgb (R, G, B; alpha linear)
 
@@ -800,6 +856,39 @@ class SlotImage:
         """to_bc into a uint8 tensor (ceil(h/4), ceil(w/4), block bytes) in device memory (kc_image_to_bc_device); `out` (any view
         whose last two dimensions are contiguous) is written instead of a new tensor.  Ready on torch's current stream."""
         return _bc_export(lambda d, f, st: _lib.load().kc_image_to_bc_device(self._h, d, f, st), self.size(), fmt, srgb, out)
+
+    def mips(self, per_level=False):
+        """-> the mip chain as a list of SlotImage (kc_image_build_mips): entry 0 is this image, entry k is max(1, w >> k) by
+        max(1, h >> k), the 2 x 2 box of the level above it in f32, down to 1 x 1.  per_level=True runs one launch per level
+        instead of the fused kernel (the same bits)."""
+        s = self.size()
+        n = mip_level_count(s.width, s.height)
+        arr = (C.c_void_p * n)()
+        count = C.c_uint32()
+        _check(_lib.load().kc_image_build_mips(self._h, MIP_PER_LEVEL if per_level else 0, arr, n, C.byref(count)))
+        return [SlotImage(arr[k]) for k in range(count.value)]
+
+    def to_bc_mips(self, fmt, srgb=False, per_level=False):
+        """-> one uint8 (ceil(H_k/4), ceil(W_k/4), block bytes) array per level, shaped like to_bc's and views of one buffer
+        that holds the chain as a texture file stores it (kc_image_to_bc_mips)."""
+        f = _bc_format(fmt)
+        s = self.size()
+        offs, total = bc_mip_layout(s.width, s.height, f)
+        buf = np.empty((total,), np.uint8)
+        flags = (BC_SRGB if srgb else 0) | (MIP_PER_LEVEL if per_level else 0)
+        _check(_lib.load().kc_image_to_bc_mips(self._h, f, flags, buf.ctypes.data, buf.nbytes))
+        return _bc_mip_views(buf, s, f)
+
+    def to_bc_mips_torch(self, fmt, srgb=False, out=None, per_level=False):
+        """-> (flat uint8 tensor in device memory holding the chain, offsets of the levels) (kc_image_to_bc_mips_device); `out`
+        (contiguous, 1-D, at least the chain's bytes) is written instead of a new tensor, bytes past the chain are not touched.
+        Ready on torch's current stream."""
+        return _bc_mips_export(lambda f, fl, p, n, st: _lib.load().kc_image_to_bc_mips_device(self._h, f, fl, p, n, st), self.size(), fmt,
+                               srgb, per_level, out)
+
+    def write_dds(self, path, fmt, srgb=False, mips=True):
+        """Writes a .dds file (DX10 header) with the image's BC blocks: the whole mip chain, or level 0 alone (kc_image_write_dds)."""
+        _check(_lib.load().kc_image_write_dds(self._h, os.fspath(path).encode(), _bc_format(fmt), BC_SRGB if srgb else 0, int(mips)))
 
     def channel_stats(self, histogram=False, srgb=False):
         """-> ChannelStats of the image, computed on the device (kc_image_channel_stats): the range and NaN count of every
@@ -1156,6 +1245,11 @@ class LiveGraph:
         """SlotImage.to_bc_torch of a slot's image (kc_live_graph_buffer_bc)."""
         return _bc_export(lambda d, f, st: _lib.load().kc_live_graph_buffer_bc(self._h, node_id, slot_id, d, f, st),
                           self.slot_data_size(node_id, slot_id), fmt, srgb, out)
+
+    def buffer_bc_mips_torch(self, node_id, slot_id, fmt, srgb=False, out=None, per_level=False):
+        """SlotImage.to_bc_mips_torch of a slot's image (kc_live_graph_buffer_bc_mips)."""
+        return _bc_mips_export(lambda f, fl, p, n, st: _lib.load().kc_live_graph_buffer_bc_mips(self._h, node_id, slot_id, f, fl, p, n, st),
+                               self.slot_data_size(node_id, slot_id), fmt, srgb, per_level, out)
 
     def buffer_channel_stats(self, node_id, slot_id, histogram=False, srgb=False):
         """SlotImage.channel_stats of a slot's image (kc_live_graph_buffer_channel_stats)."""

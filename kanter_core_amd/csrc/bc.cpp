@@ -6,7 +6,7 @@
 
 namespace kc {
 
-static size_t bc_block_bytes(int format)
+size_t bc_block_bytes(int format)
 {
     return format == KC_BC1 || format == KC_BC4 ? 8 : format == KC_BC3 || format == KC_BC5 ? 16 : 0;
 }
@@ -62,7 +62,7 @@ int bc_image_validate(const kc_bc_image *d, size_t *extent_bytes)
 
 // One launch of the encoder for `img` (forced already) into `dst`, block rows `row_pitch` bytes apart.  The channels the format
 // reads come from the image as to_u8 sees it (Gray: (v, v, v, 1)); constants cost no loads.
-static int bc_encode(kc_image *img, int format, bool srgb, char *dst, size_t row_pitch, hipStream_t s)
+int bc_encode(kc_image *img, int format, bool srgb, char *dst, size_t row_pitch, hipStream_t s)
 {
     Context &c = ctx();
     const bool rgba = img->is_rgba();

@@ -808,6 +808,52 @@ try {
 }
 KC_CATCH
 
+int kc_mip_level_count(uint32_t width, uint32_t height, uint32_t *levels)
+try {
+    return mip_level_count(width, height, levels);
+}
+KC_CATCH
+
+int kc_image_build_mips(kc_image *img, uint32_t flags, kc_image **levels, uint32_t cap, uint32_t *count)
+try {
+    Lock api_lock(ctx().mu);  // reference counts are plain integers, see kc_plane::refs
+    return image_build_mips(img, flags, levels, cap, count);  // the flags, the arguments, then need_init()
+}
+KC_CATCH
+
+int kc_bc_mip_layout(uint32_t width, uint32_t height, int format, uint32_t *levels, size_t *offsets, uint32_t cap, size_t *total_bytes)
+try {
+    return bc_mip_layout(width, height, format, levels, offsets, cap, total_bytes);
+}
+KC_CATCH
+
+int kc_image_to_bc_mips(kc_image *img, int format, uint32_t flags, uint8_t *host, size_t host_bytes)
+try {
+    Lock api_lock(ctx().mu);  // reference counts are plain integers, see kc_plane::refs
+    return image_to_bc_mips(img, format, flags, host, host_bytes);
+}
+KC_CATCH
+
+int kc_image_to_bc_mips_device(kc_image *img, int format, uint32_t flags, void *device_ptr, size_t bytes, void *hip_stream)
+try {
+    Lock api_lock(ctx().mu);  // reference counts are plain integers, see kc_plane::refs
+    return image_to_bc_mips_device(img, format, flags, device_ptr, bytes, hip_stream);
+}
+KC_CATCH
+
+int kc_dds_header(uint32_t width, uint32_t height, int format, uint32_t flags, uint32_t levels, uint8_t out[148], size_t *bytes)
+try {
+    return dds_header(width, height, format, flags, levels, out, bytes);
+}
+KC_CATCH
+
+int kc_image_write_dds(kc_image *img, const char *path, int format, uint32_t flags, int with_mips)
+try {
+    Lock api_lock(ctx().mu);  // reference counts are plain integers, see kc_plane::refs
+    return image_write_dds(img, path, format, flags, with_mips);
+}
+KC_CATCH
+
 int kc_image_channel_stats(kc_image *img, uint32_t flags, kc_channel_stats *out)
 try {
     Lock api_lock(ctx().mu);  // reference counts are plain integers, see kc_plane::refs
@@ -1451,6 +1497,22 @@ try {
     const SlotData *sd = lg->find_slot(node, slot);
     if (!sd) return KC_ERR_NO_SLOT_DATA;
     return image_to_bc_device(sd->image, dst, flags, hip_stream);
+}
+KC_CATCH
+
+int kc_live_graph_buffer_bc_mips(kc_live_graph *lg, uint32_t node, uint32_t slot, int format, uint32_t flags, void *device_ptr,
+                                 size_t bytes, void *hip_stream)
+try {
+    if (flags & ~(uint32_t)(KC_BC_SRGB | KC_MIP_PER_LEVEL)) {
+        set_error("kc_live_graph_buffer_bc_mips: unknown flag bits");
+        return KC_ERR_UNSUPPORTED;
+    }
+    LG_LOCK(lg);
+    KC_ARG(device_ptr && bytes > 0);
+    KC_TRY(need_init());
+    const SlotData *sd = lg->find_slot(node, slot);
+    if (!sd) return KC_ERR_NO_SLOT_DATA;
+    return image_to_bc_mips_device(sd->image, format, flags, device_ptr, bytes, hip_stream);
 }
 KC_CATCH
 

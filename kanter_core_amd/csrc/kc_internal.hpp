@@ -305,5 +305,27 @@ uint32_t channel_stats_groups(uint32_t w, uint32_t h, bool hist, bool srgb, uint
 // once); nt_mask bits 0-7: nontemporal plane loads; srgb: BC1 and BC3 only
 hipError_t launch_bc_encode(int fmt, int srgb, const Operand op[4], int gray, char *dst, uint64_t row_pitch, uint32_t w, uint32_t h,
                             uint32_t nt_mask, hipStream_t s);
+// -- mip.hip --
+// Mip chains (mip.hip / mip.cpp): the 2 x 2 box of the header on the n_planes distinct resident planes of one image.
+// mip_pyramid_kernel<nt>: levels 1..n (1 <= n <= 6, both of w >> n and h >> n still >= 1) of the w x h source planes, one
+// workgroup per 64 x 64 tile; dst[p][k - 1] is level k of plane p, dst_pitch[k - 1] floats between its rows.
+struct MipPyramidArgs {
+    const float *src[4];
+    uint32_t src_pitch[4];  // floats
+    float *dst[4][6];
+    uint32_t dst_pitch[6];  // floats
+    uint32_t w, h, n;
+};
+hipError_t launch_mip_pyramid(const MipPyramidArgs &a, uint32_t n_planes, bool nt, hipStream_t s);
+// mip_level_kernel<nt>: the one level below a w x h source (not 1 x 1), max(1, w >> 1) x max(1, h >> 1), with the clamps; dst rows
+// start 16-byte aligned
+struct MipLevelArgs {
+    const float *src[4];
+    uint32_t src_pitch[4];  // floats
+    float *dst[4];
+    uint32_t dst_pitch;  // floats
+    uint32_t w, h;
+};
+hipError_t launch_mip_level(const MipLevelArgs &a, uint32_t n_planes, bool nt, hipStream_t s);
 
 }  // namespace kc

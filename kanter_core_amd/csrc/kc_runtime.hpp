@@ -347,6 +347,19 @@ int stream_edge(hipStream_t from, hipStream_t to);
 int bc_image_validate(const kc_bc_image *d, size_t *extent_bytes);
 int image_to_bc(kc_image *img, int format, uint32_t flags, uint8_t *host, size_t host_bytes);
 int image_to_bc_device(kc_image *img, const kc_bc_image *dst, uint32_t flags, void *hip_stream);
+size_t bc_block_bytes(int format);  // 8, 16, or 0 for an unknown format
+// one launch of the encoder for `img` (forced already) into `dst`, block rows `row_pitch` bytes apart, on `s`
+int bc_encode(kc_image *img, int format, bool srgb, char *dst, size_t row_pitch, hipStream_t s);
+// mip chains and their export (mip.cpp): the bodies of kc_mip_level_count, kc_image_build_mips, kc_bc_mip_layout,
+// kc_image_to_bc_mips, kc_image_to_bc_mips_device, kc_dds_header, kc_image_write_dds
+int mip_level_count(uint32_t w, uint32_t h, uint32_t *levels);
+float mip_const_fold(float c);  // ((c + c) + (c + c)) * 0.25f, as the device computes it
+int image_build_mips(kc_image *img, uint32_t flags, kc_image **levels, uint32_t cap, uint32_t *count);
+int bc_mip_layout(uint32_t w, uint32_t h, int format, uint32_t *levels, size_t *offsets, uint32_t cap, size_t *total_bytes);
+int image_to_bc_mips(kc_image *img, int format, uint32_t flags, uint8_t *host, size_t host_bytes);
+int image_to_bc_mips_device(kc_image *img, int format, uint32_t flags, void *device_ptr, size_t bytes, void *hip_stream);
+int dds_header(uint32_t w, uint32_t h, int format, uint32_t flags, uint32_t levels, uint8_t *out, size_t *bytes);
+int image_write_dds(kc_image *img, const char *path, int format, uint32_t flags, int with_mips);
 // per-channel statistics (stats.cpp): the body of kc_image_channel_stats; the context's buffers, released at kc_shutdown
 int image_channel_stats(kc_image *img, uint32_t flags, kc_channel_stats *out);
 void channel_stats_release();

@@ -1,0 +1,343 @@
+// Mip chains and their export (include/kanter_core_amd.h): kc_mip_level_count, kc_image_build_mips, kc_bc_mip_layout,
+// kc_image_to_bc_mips, kc_image_to_bc_mips_device, kc_dds_header, kc_image_write_dds.  The host side does the level arithmetic,
+// folds constant planes with the device's expression, allocates the level planes and enqueues mip.hip's kernels on the library's
+// stream: the pyramid kernel while both extents still halve (up to six levels per launch), the one-level kernel for the rest and
+// for every level under KC_MIP_PER_LEVEL.  The BC chain is bc.cpp's encoder launch once per level; the DDS writer is host code.
+#include <cstdio>
+
+#include "kc_runtime.hpp"
+
+namespace kc {
+
+static int mip_refuse(const char *who, const char *what)
+{
+    set_error(std::string(who) + ": " + what);
+    return KC_ERR_INVALID_ARG;
+}
+
+static uint32_t floor_log2(uint32_t v) { return 31u - (uint32_t)__builtin_clz(v); }  // v > 0
+
+int mip_level_count(uint32_t w, uint32_t h, uint32_t *levels)
+{
+    if (!levels || w == 0 || h == 0) return mip_refuse("kc_mip_level_count", "NULL output or zero extent");
+    *levels = 1u + floor_log2(w > h ? w : h);
+    return KC_OK;
+}
+
+static uint32_t level_extent(uint32_t v, uint32_t k) { return k < 32 && (v >> k) ? v >> k : 1u; }
+
+// The contract's expression on a constant plane, once per level: ((c + c) + (c + c)) * 0.25f in f32.  It is not c for very
+// large c (c + c overflows) or denormal c (the product rounds), so nothing is shortcut; the volatile temporaries keep the
+// compiler from folding or contracting the four operations differently from the device.
+float mip_const_fold(float c)
+{
+    volatile float a = c;
+    volatile float s = a + a;
+    volatile float t = s + s;
+    volatile float q = 0.25f;
+    volatile float r = t * q;
+    return r;
+}
+
+namespace {
+// The distinct resident planes of an image: slot s reads src[s]; slot_of[ch] = the slot of channel ch, -1 for a constant
+struct MipSlots {
+    const kc_plane *src[4];
+    int n = 0;
+    int slot_of[4] = { -1, -1, -1, -1 };
+};
+
+struct MipChain {
+    std::vector<kc_plane *> planes;  // [level - 1][channel], one reference each held here until the images exist
+    ~MipChain()
+    {
+        for (kc_plane *p : planes) plane_release(p);
+    }
+};
+}  // namespace
+
+int image_build_mips(kc_image *img, uint32_t flags, kc_image **levels, uint32_t cap, uint32_t *count)
+{
+    if (flags & ~(uint32_t)KC_MIP_PER_LEVEL) {
+        set_error("kc_image_build_mips: flags other than KC_MIP_PER_LEVEL");
+        return KC_ERR_UNSUPPORTED;
+    }
+    if (!img || !levels || !count) return mip_refuse("kc_image_build_mips", "NULL image, level array or count");
+    KC_TRY(need_init());
+    Context &c = ctx();
+    std::lock_guard<std::recursive_mutex> lk(c.mu);
+    const uint32_t w = img->w(), h = img->h(), L = 1u + floor_log2(w > h ? w : h);
+    *count = L;
+    if (cap < L) return mip_refuse("kc_image_build_mips", "cap is below the level count");
+    // the kernels' indices are 32-bit and the pyramid's tile rows a grid dimension
+    if (w > (1u << 30) || ((uint64_t)h + 63) / 64 > 65535ull || (((uint64_t)w + 3) / 4) * h > (1ull << 31))
+        return mip_refuse("kc_image_build_mips", "image too large");
+    KC_TRY(image_force(img));  // pending chains and deferred resizes run first
+    const int n = img->n;
+    MipSlots sl;
+    for (int ch = 0; ch < n; ++ch) {
+        const kc_plane *p = img->planes[ch];
+        if (p->kind == kc_plane::CONST) continue;
+        int s = 0;
+        while (s < sl.n && !(sl.src[s] == p || (sl.src[s]->dptr == p->dptr && sl.src[s]->pitch == p->pitch))) ++s;
+        if (s == sl.n) sl.src[sl.n++] = p;
+        sl.slot_of[ch] = s;
+    }
+    // the planes of every level: one new resident plane per slot, shared by the channels that alias it, one constant per
+    // constant channel
+    MipChain mc;
+    mc.planes.reserve((size_t)(L - 1) * n);
+    std::vector<kc_plane *> slot_planes((size_t)(L - 1) * 4, nullptr);  // [level - 1][slot], owned through mc.planes
+    float cv[4] = { 0.0f, 0.0f, 0.0f, 0.0f };
+    for (int ch = 0; ch < n; ++ch) cv[ch] = img->planes[ch]->cval;
+    for (uint32_t k = 1; k < L; ++k) {
+        const uint32_t W = level_extent(w, k), H = level_extent(h, k);
+        for (int ch = 0; ch < n; ++ch) {
+            const int s = sl.slot_of[ch];
+            kc_plane *p = nullptr;
+            if (s < 0) {
+                cv[ch] = mip_const_fold(cv[ch]);
+                p = plane_new_const(W, H, cv[ch]);
+            } else if (slot_planes[(size_t)(k - 1) * 4 + s]) {
+                p = slot_planes[(size_t)(k - 1) * 4 + s];
+                plane_retain(p);
+            } else {
+                KC_TRY(plane_new_mem(W, H, &p));
+                slot_planes[(size_t)(k - 1) * 4 + s] = p;
+            }
+            mc.planes.push_back(p);
+        }
+    }
+    if (sl.n > 0 && L > 1) {
+        const bool per_level = (flags & KC_MIP_PER_LEVEL) != 0;
+        auto plane_at = [&](uint32_t k, int s) -> const kc_plane * { return k == 0 ? sl.src[s] : slot_planes[(size_t)(k - 1) * 4 + s]; };
+        uint32_t k = 0;  // the level the next launch reads
+        while (k + 1 < L) {
+            const uint32_t sw = level_extent(w, k), sh = level_extent(h, k);
+            const uint32_t small = sw < sh ? sw : sh;
+            const uint32_t fused = per_level || small < 2 ? 0u : floor_log2(small) < 6u ? floor_log2(small) : 6u;
+            const uint64_t in_bytes = (uint64_t)sw * sh * 4 * sl.n;
+            const uint64_t out_bytes = (uint64_t)level_extent(w, k + 1) * level_extent(h, k + 1) * 4 * sl.n;
+            const bool nt = (cache_policy_mask(in_bytes, out_bytes, (uint32_t)sl.n) & 0xffu) != 0;
+            if (fused) {
+                MipPyramidArgs a{};
+                a.w = sw;
+                a.h = sh;
+                a.n = fused;
+                for (int s = 0; s < sl.n; ++s) {
+                    a.src[s] = plane_at(k, s)->dptr;
+                    a.src_pitch[s] = (uint32_t)(plane_at(k, s)->pitch / sizeof(float));
+                    for (uint32_t j = 0; j < fused; ++j) a.dst[s][j] = plane_at(k + 1 + j, s)->dptr;
+                }
+                for (uint32_t j = 0; j < fused; ++j) a.dst_pitch[j] = (uint32_t)(plane_at(k + 1 + j, 0)->pitch / sizeof(float));
+                hipError_t e = launch_mip_pyramid(a, (uint32_t)sl.n, nt, c.stream);
+                if (e != hipSuccess) return hip_fail(e, "launch_mip_pyramid");
+                c.counters["mip_pyramid"]++;
+                k += fused;
+            } else {
+                MipLevelArgs a{};
+                a.w = sw;
+                a.h = sh;
+                for (int s = 0; s < sl.n; ++s) {
+                    a.src[s] = plane_at(k, s)->dptr;
+                    a.src_pitch[s] = (uint32_t)(plane_at(k, s)->pitch / sizeof(float));
+                    a.dst[s] = plane_at(k + 1, s)->dptr;
+                }
+                a.dst_pitch = (uint32_t)(plane_at(k + 1, 0)->pitch / sizeof(float));
+                hipError_t e = launch_mip_level(a, (uint32_t)sl.n, nt, c.stream);
+                if (e != hipSuccess) return hip_fail(e, "launch_mip_level");
+                c.counters["mip_level"]++;
+                k += 1;
+            }
+            c.launches++;
+        }
+        uint64_t texels = (uint64_t)w * h;  // level 0 read once, every further level written once
+        for (uint32_t j = 1; j < L; ++j) texels += (uint64_t)level_extent(w, j) * level_extent(h, j);
+        c.alg_bytes += 4 * texels * sl.n;
+    }
+    image_retain(img);
+    levels[0] = img;
+    for (uint32_t k = 1; k < L; ++k) levels[k] = image_new(n, mc.planes.data() + (size_t)(k - 1) * n);  // retains; mc drops its own
+    return KC_OK;
+}
+
+// ---------------------------------------------------------------- the BC chain
+// flags of the chain exporters: KC_BC_SRGB under kc_image_to_bc's rule, plus KC_MIP_PER_LEVEL
+static int bc_mips_check_flags(int format, uint32_t flags, uint32_t allowed, const char *who)
+{
+    if (flags & ~allowed) {
+        set_error(std::string(who) + ": unknown flag bits");
+        return KC_ERR_UNSUPPORTED;
+    }
+    if ((flags & KC_BC_SRGB) && (format == KC_BC4 || format == KC_BC5)) {
+        set_error(std::string(who) + ": KC_BC_SRGB is for BC1 and BC3 only");
+        return KC_ERR_UNSUPPORTED;
+    }
+    return KC_OK;
+}
+
+static size_t bc_level_bytes(uint32_t W, uint32_t H, size_t bb) { return (((size_t)W + 3) / 4) * (((size_t)H + 3) / 4) * bb; }
+
+int bc_mip_layout(uint32_t w, uint32_t h, int format, uint32_t *levels, size_t *offsets, uint32_t cap, size_t *total_bytes)
+{
+    const size_t bb = bc_block_bytes(format);
+    if (bb == 0) return mip_refuse("kc_bc_mip_layout", "unknown format");
+    if (w == 0 || h == 0) return mip_refuse("kc_bc_mip_layout", "zero extent");
+    const uint32_t L = 1u + floor_log2(w > h ? w : h);
+    if (levels) *levels = L;
+    if (offsets && cap < L) return mip_refuse("kc_bc_mip_layout", "cap is below the level count");
+    if ((((uint64_t)w + 3) / 4) * (((uint64_t)h + 3) / 4) > (1ull << 31)) return mip_refuse("kc_bc_mip_layout", "image too large: more than 2^31 blocks");
+    size_t at = 0;
+    for (uint32_t k = 0; k < L; ++k) {
+        if (offsets) offsets[k] = at;
+        at += bc_level_bytes(level_extent(w, k), level_extent(h, k), bb);
+    }
+    if (total_bytes) *total_bytes = at;
+    return KC_OK;
+}
+
+// The chain of `img` (forced by image_build_mips) as blocks at dst, level k at its kc_bc_mip_layout offset; on the library's stream
+static int bc_mips_encode(kc_image *img, int format, uint32_t flags, char *dst)
+{
+    Context &c = ctx();
+    uint32_t L = 0;
+    KC_TRY(mip_level_count(img->w(), img->h(), &L));
+    std::vector<kc_image *> lv(L, nullptr);
+    uint32_t count = 0;
+    KC_TRY(image_build_mips(img, flags & KC_MIP_PER_LEVEL, lv.data(), L, &count));
+    const size_t bb = bc_block_bytes(format);
+    size_t at = 0;
+    int s = KC_OK;
+    for (uint32_t k = 0; k < L && s == KC_OK; ++k) {
+        const uint32_t W = lv[k]->w(), H = lv[k]->h();
+        s = bc_encode(lv[k], format, (flags & KC_BC_SRGB) != 0, dst + at, (((size_t)W + 3) / 4) * bb, c.stream);
+        at += bc_level_bytes(W, H, bb);
+    }
+    // the level planes go back to the pool here; the pool hands a block out again only to work enqueued on the same stream
+    for (kc_image *i : lv) image_release(i);
+    return s;
+}
+
+int image_to_bc_mips(kc_image *img, int format, uint32_t flags, uint8_t *host, size_t host_bytes)
+{
+    KC_TRY(bc_mips_check_flags(format, flags, KC_BC_SRGB | KC_MIP_PER_LEVEL, "kc_image_to_bc_mips"));
+    if (bc_block_bytes(format) == 0) return mip_refuse("kc_image_to_bc_mips", "unknown format");
+    if (!img || !host) return mip_refuse("kc_image_to_bc_mips", "NULL image or host buffer");
+    KC_TRY(need_init());
+    Context &c = ctx();
+    std::lock_guard<std::recursive_mutex> lk(c.mu);
+    size_t total = 0;
+    KC_TRY(bc_mip_layout(img->w(), img->h(), format, nullptr, nullptr, 0, &total));
+    if (host_bytes < total) return mip_refuse("kc_image_to_bc_mips", "host_bytes is below the chain's bytes");
+    const size_t block = (total + 255) / 256 * 256;
+    void *staging = nullptr;
+    KC_TRY(pool_alloc(block, &staging));
+    int s = bc_mips_encode(img, format, flags, (char *)staging);
+    hipError_t e = hipSuccess;
+    if (s == KC_OK) e = hipMemcpyAsync(host, staging, total, hipMemcpyDeviceToHost, c.stream);
+    if (s == KC_OK && e == hipSuccess) e = hipStreamSynchronize(c.stream);
+    pool_free(staging, block);
+    if (s != KC_OK) return s;
+    if (e != hipSuccess) return hip_fail(e, "image_to_bc_mips");
+    return KC_OK;
+}
+
+int image_to_bc_mips_device(kc_image *img, int format, uint32_t flags, void *device_ptr, size_t bytes, void *hip_stream)
+{
+    KC_TRY(bc_mips_check_flags(format, flags, KC_BC_SRGB | KC_MIP_PER_LEVEL, "kc_image_to_bc_mips_device"));
+    const size_t bb = bc_block_bytes(format);
+    if (bb == 0) return mip_refuse("kc_image_to_bc_mips_device", "unknown format");
+    if (!img || !device_ptr) return mip_refuse("kc_image_to_bc_mips_device", "NULL image or device pointer");
+    if ((uintptr_t)device_ptr % bb) return mip_refuse("kc_image_to_bc_mips_device", "the pointer must be a multiple of the block bytes");
+    KC_TRY(need_init());  // an image exists only after kc_init: it is not looked at before
+    Context &c = ctx();
+    std::lock_guard<std::recursive_mutex> lk(c.mu);
+    size_t total = 0;
+    KC_TRY(bc_mip_layout(img->w(), img->h(), format, nullptr, nullptr, 0, &total));
+    if (bytes < total) return mip_refuse("kc_image_to_bc_mips_device", "bytes is below the chain's bytes");
+    KC_TRY(device_extent_check(device_ptr, total, "kc_image_to_bc_mips_device"));
+    hipStream_t hs = (hipStream_t)hip_stream;
+    const bool edges = hs && hs != c.stream;
+    if (edges) KC_TRY(stream_edge(hs, c.stream));
+    KC_TRY(bc_mips_encode(img, format, flags, (char *)device_ptr));
+    if (edges) KC_TRY(stream_edge(c.stream, hs));
+    return KC_OK;
+}
+
+// ---------------------------------------------------------------- DDS
+static uint32_t dxgi_format(int format, bool srgb)
+{
+    switch (format) {
+    case KC_BC1: return srgb ? 72u : 71u;
+    case KC_BC3: return srgb ? 78u : 77u;
+    case KC_BC4: return 80u;
+    default: return 83u;  // KC_BC5
+    }
+}
+
+int dds_header(uint32_t w, uint32_t h, int format, uint32_t flags, uint32_t levels, uint8_t *out, size_t *bytes)
+{
+    KC_TRY(bc_mips_check_flags(format, flags, KC_BC_SRGB, "kc_dds_header"));
+    const size_t bb = bc_block_bytes(format);
+    if (bb == 0) return mip_refuse("kc_dds_header", "unknown format");
+    if (!out || w == 0 || h == 0) return mip_refuse("kc_dds_header", "NULL output or zero extent");
+    if (levels == 0 || levels > 1u + floor_log2(w > h ? w : h)) return mip_refuse("kc_dds_header", "levels is 0 or above the chain's level count");
+    const uint64_t linear = (((uint64_t)w + 3) / 4) * (((uint64_t)h + 3) / 4) * bb;
+    if (linear > 0xffffffffull) return mip_refuse("kc_dds_header", "level 0 is larger than the header can say");
+    const bool mips = levels > 1;
+    uint32_t d[37] = { 0 };
+    d[0] = 0x20534444u;  // "DDS "
+    d[1] = 124;          // DDS_HEADER: dwSize
+    d[2] = 0x1u | 0x2u | 0x4u | 0x1000u | 0x80000u | (mips ? 0x20000u : 0u);  // CAPS, HEIGHT, WIDTH, PIXELFORMAT, LINEARSIZE, MIPMAPCOUNT
+    d[3] = h;
+    d[4] = w;
+    d[5] = (uint32_t)linear;  // dwPitchOrLinearSize
+    d[6] = 0;                 // dwDepth
+    d[7] = levels;            // dwMipMapCount; d[8..18]: reserved
+    d[19] = 32;               // DDS_PIXELFORMAT: dwSize
+    d[20] = 0x4;              // DDPF_FOURCC
+    d[21] = 0x30315844u;      // "DX10"; d[22..26]: bit count and masks, 0
+    d[27] = 0x1000u | (mips ? 0x8u | 0x400000u : 0u);  // dwCaps: TEXTURE (, COMPLEX, MIPMAP); d[28..31]: 0
+    d[32] = dxgi_format(format, (flags & KC_BC_SRGB) != 0);  // DDS_HEADER_DXT10
+    d[33] = 3;                // D3D10_RESOURCE_DIMENSION_TEXTURE2D
+    d[34] = 0;                // miscFlag
+    d[35] = 1;                // arraySize
+    d[36] = 0;                // miscFlags2
+    for (int i = 0; i < 37; ++i)  // little-endian, whatever the host's order
+        for (int b = 0; b < 4; ++b) out[4 * i + b] = (uint8_t)(d[i] >> (8 * b));
+    if (bytes) *bytes = 148;
+    return KC_OK;
+}
+
+int image_write_dds(kc_image *img, const char *path, int format, uint32_t flags, int with_mips)
+{
+    KC_TRY(bc_mips_check_flags(format, flags, KC_BC_SRGB | KC_MIP_PER_LEVEL, "kc_image_write_dds"));
+    if (bc_block_bytes(format) == 0) return mip_refuse("kc_image_write_dds", "unknown format");
+    if (!img || !path) return mip_refuse("kc_image_write_dds", "NULL image or path");
+    KC_TRY(need_init());
+    const uint32_t w = img->w(), h = img->h();
+    uint32_t L = 1;
+    size_t total = 0;
+    KC_TRY(bc_mip_layout(w, h, format, &L, nullptr, 0, &total));
+    if (!with_mips) {
+        L = 1;
+        total = bc_level_bytes(w, h, bc_block_bytes(format));
+    }
+    std::vector<uint8_t> file(148 + total);
+    KC_TRY(dds_header(w, h, format, flags & KC_BC_SRGB, L, file.data(), nullptr));
+    if (with_mips) KC_TRY(image_to_bc_mips(img, format, flags, file.data() + 148, total));
+    else KC_TRY(image_to_bc(img, format, flags & KC_BC_SRGB, file.data() + 148, total));
+    FILE *f = std::fopen(path, "wb");
+    if (!f) {
+        set_error(std::string("kc_image_write_dds: cannot open ") + path);
+        return KC_ERR_IO;
+    }
+    const bool ok = std::fwrite(file.data(), 1, file.size(), f) == file.size();
+    if (std::fclose(f) != 0 || !ok) {
+        set_error(std::string("kc_image_write_dds: cannot write ") + path);
+        return KC_ERR_IO;
+    }
+    return KC_OK;
+}
+
+}  // namespace kc
