@@ -114,11 +114,12 @@ impl SlotImage {
         check(unsafe { kc_image_channel_stats(self.raw(), flags, &mut *out) })?;
         Ok(out)
     }
-    /// The image's BC1, BC3, BC4 or BC5 blocks (kc_image_to_bc), encoded on the device from the bytes to_u8 (`srgb`: to_u8_srgb,
-    /// BC1 and BC3 only) writes: ceil(h/4) rows of ceil(w/4) blocks of 8 (BC1, BC4) or 16 (BC3, BC5) bytes, tightly packed.
+    /// The image's BC1, BC3, BC4, BC5 or BC7 blocks (kc_image_to_bc), encoded on the device from the bytes to_u8 (`srgb`:
+    /// to_u8_srgb, BC1, BC3 and BC7 only) writes: ceil(h/4) rows of ceil(w/4) blocks of 8 (BC1, BC4) or 16 (BC3, BC5, BC7) bytes,
+    /// tightly packed.
     pub fn to_bc(&self, format: i32, srgb: bool) -> Result<Vec<u8>> {
         let s = self.size()?;
-        let block = if format == KC_BC3 || format == KC_BC5 { 16 } else { 8 };
+        let block = if format == KC_BC1 || format == KC_BC4 { 8 } else { 16 };
         let mut out = vec![0u8; ((s.width as usize + 3) / 4) * ((s.height as usize + 3) / 4) * block];
         let flags = if srgb { KC_BC_SRGB } else { 0 };
         check(unsafe { kc_image_to_bc(self.raw(), format, flags, out.as_mut_ptr(), out.len()) })?;

@@ -391,8 +391,8 @@ typedef struct kc_channel_stats {
                                    channel c; all zero without the flag */
 } kc_channel_stats;
 KC_API int kc_image_channel_stats(kc_image *img, uint32_t flags, kc_channel_stats *out);
-/* Block-compressed textures, encoded on the device: BC1 (colour), BC3 (colour and alpha), BC4 (one channel) and BC5 (two
- * channels), the formats a GPU samples.  The blocks are a function of the RGBA8 bytes kc_image_to_u8(img, srgb) writes (Gray =
+/* Block-compressed textures, encoded on the device: BC1 (colour), BC3 (colour and alpha), BC4 (one channel), BC5 (two
+ * channels) and BC7 (colour and alpha at 8 bits an endpoint), the formats a GPU samples.  The blocks are a function of the RGBA8 bytes kc_image_to_u8(img, srgb) writes (Gray =
  * (v, v, v, 1); KC_BC_SRGB: R, G, B as with srgb = 1, alpha always linear); everything after that quantisation is integer
  * arithmetic, so the output is bit-exact.  The grid is bx = ceil(w / 4) by by = ceil(h / 4) blocks; texel t = 4y + x (x, y in
  * 0..3) of block (i, j) is pixel (min(4i + x, w - 1), min(4j + y, h - 1)): edge blocks repeat the last column or row.
@@ -409,6 +409,26 @@ KC_API int kc_image_channel_stats(kc_image *img, uint32_t flags, kc_channel_stat
  *           bits 2t..2t+1.  A block with a non-zero index has c0 > c1: it decodes in four-colour mode, never transparent.
  *   BC3     the BC4 block of alpha, then the BC1 block (16 bytes).  BC5: the BC4 block of R, then that of G (16 bytes).  BC1
  *           ignores alpha; BC4 reads R only, BC5 R and G.
+ *   BC7 of texels p_t = (r, g, b, a), 16 bytes: the two single-subset modes 6 and 5 (rotation 0) only.
+ *           interp(e0, e1, w) = ((64 - w) e0 + w e1 + 32) >> 6; W4 = 0, 4, 9, 13, 17, 21, 26, 30, 34, 38, 43, 47, 51, 55, 60, 64;
+ *           W2 = 0, 21, 43, 64.  axis(p over channels C): per channel lo = min, hi = max; k the first channel (order R, G, B, A)
+ *           of the largest hi - lo; a_t = 2 p_t,k - lo_k - hi_k; s_c = sum_t a_t (2 p_t,c - lo_c - hi_c); e0_c = hi_c if
+ *           s_c < 0 else lo_c, e1_c the other one (BC1's covariance-sign diagonal, without the inset).  An index is the arg-min
+ *           of the squared distance summed over the channels of its palette, the lowest index on a tie; a mode's error is the
+ *           sum of those minima.
+ *           Mode 6: (e0, e1) = axis(p over R, G, B, A).  Each endpoint on its own: for pb in 0, 1,
+ *           q_c = clamp((e_c - pb + 1) >> 1, 0, 127), v_c = 2 q_c + pb, cost sum_c (v_c - e_c)^2; pb = 1 only if its cost is
+ *           strictly lower.  Palette i = interp(v0, v1, W4[i]) per channel.  If texel 0's index is >= 8 the endpoints swap
+ *           together with their p-bits and every index becomes 15 - index (the weights are symmetric).
+ *           Mode 5: (e0, e1) = axis(p over R, G, B); q_c = (127 e_c + 127) div 255 decodes to v_c = (q_c << 1) | (q_c >> 6);
+ *           colour palette interp(v0, v1, W2[i]); alpha endpoints a0 = min, a1 = max, palette interp(a0, a1, W2[i]); err5 = the
+ *           colour error plus the alpha error.  The two index sets are anchored independently: a texel-0 index >= 2 swaps that
+ *           set's endpoints and turns its indices into 3 - index.
+ *           Mode 5 if and only if err5 < err6.  Bit n of the block is bit n % 8 of byte n / 8; fields are LSB first.
+ *           Mode 6: bits 0-6 the value 64; R0, R1, G0, G1, B0, B1, A0, A1 of 7 bits each (7-62); P0 bit 63, P1 bit 64; texel 0's
+ *           index in 3 bits (65-67), texels 1-15 in 4 bits each (68-127).  Mode 5: bits 0-5 the value 32; rotation (6-7) 0; R0,
+ *           R1, G0, G1, B0, B1 of 7 bits each (8-49); A0, A1 of 8 bits each (50-65); colour indices, texel 0 in 1 bit (66),
+ *           texels 1-15 in 2 bits each (67-96); alpha indices likewise (97, 98-127).
  *   kc_bc_image           a caller's buffer of blocks: block (i, j) at ptr + j * row_pitch_bytes + i * block bytes.
  *   kc_bc_image_validate  launches nothing; like kc_device_image_validate.  Arithmetic first (no kc_init needed): a known
  *                         format, width and height > 0, bx * by <= 2^31, ptr and row_pitch_bytes multiples of the block
@@ -425,15 +445,17 @@ KC_API int kc_image_channel_stats(kc_image *img, uint32_t flags, kc_channel_stat
  * KC_ERR_NO_DEVICE before kc_init; kc_live_graph_buffer_bc returns KC_ERR_NO_SLOT_DATA where kc_live_graph_buffer_device does.
  * A refused call launches nothing.  A pending chain or resample runs first; then one launch (kc_stats), constant channels
  * included, with width * height * 4 algorithmic bytes per distinct resident plane the format reads plus the blocks' bytes.
- * Bytes outside the blocks are never written. */
-typedef enum kc_bc_format { KC_BC1 = 1, KC_BC3 = 3, KC_BC4 = 4, KC_BC5 = 5 } kc_bc_format;
+ * Bytes outside the blocks are never written.
+ * KC_BC7 is 98, DXGI_FORMAT_BC7_UNORM's own number, not 7: the value 7 has always been refused as an unknown format and stays
+ * refused. */
+typedef enum kc_bc_format { KC_BC1 = 1, KC_BC3 = 3, KC_BC4 = 4, KC_BC5 = 5, KC_BC7 = 98 } kc_bc_format;
 typedef struct kc_bc_image {
     void *ptr;               /* device memory of the library's device */
     uint32_t width, height;  /* the image's pixels */
-    int32_t format;          /* kc_bc_format; block bytes 8 (BC1, BC4) or 16 (BC3, BC5) */
+    int32_t format;          /* kc_bc_format; block bytes 8 (BC1, BC4) or 16 (BC3, BC5, BC7) */
     size_t row_pitch_bytes;  /* distance between block rows */
 } kc_bc_image;
-#define KC_BC_SRGB 1u        /* BC1 / BC3: R, G, B as kc_image_to_u8 with srgb = 1 writes them; alpha linear */
+#define KC_BC_SRGB 1u        /* BC1 / BC3 / BC7: R, G, B as kc_image_to_u8 with srgb = 1 writes them; alpha linear */
 KC_API int kc_bc_image_validate(const kc_bc_image *d, size_t *extent_bytes);
 KC_API int kc_image_to_bc(kc_image *img, int format, uint32_t flags, uint8_t *host, size_t host_bytes);
 KC_API int kc_image_to_bc_device(kc_image *img, const kc_bc_image *dst, uint32_t flags, void *hip_stream);
@@ -469,7 +491,7 @@ KC_API int kc_image_to_bc_device(kc_image *img, const kc_bc_image *dst, uint32_t
  *                        levels 0 .. L - 1 follow one another.  `*levels` = L, offsets[k] = level k's first byte (`offsets` may be
  *                        NULL; otherwise cap < L is KC_ERR_INVALID_ARG), `*total_bytes` = the chain's bytes.  Arithmetic, no kc_init.
  *   kc_image_to_bc_mips  kc_image_build_mips, then the encoder of kc_image_to_bc once per level, into host memory (`host_bytes`
- *                        at least the total); blocks until the bytes are there.  flags: KC_BC_SRGB (BC1 / BC3) | KC_MIP_PER_LEVEL.
+ *                        at least the total); blocks until the bytes are there.  flags: KC_BC_SRGB (BC1 / BC3 / BC7) | KC_MIP_PER_LEVEL.
  *   kc_image_to_bc_mips_device  the same into device memory (a multiple of the block bytes; `bytes` at least the total, the
  *                        total's extent in one allocation of the library's device), ordered against `hip_stream` by the two event
  *                        edges of kc_image_to_bc_device.  Bytes past the total are never written.
@@ -478,7 +500,8 @@ KC_API int kc_image_to_bc_device(kc_image *img, const kc_bc_image *dst, uint32_t
  *                        0x81007 plus 0x20000 with levels > 1, height, width, level 0's block bytes as the linear size, depth 0,
  *                        `levels` as the mip count, pixel format {32, DDPF_FOURCC, "DX10"}, caps 0x1000 plus 0x400008 with
  *                        levels > 1), DDS_HEADER_DXT10 {dxgiFormat, TEXTURE2D, 0, 1, 0}; dxgiFormat BC1 71, BC3 77, BC4 80,
- *                        BC5 83, with KC_BC_SRGB BC1 72, BC3 78.  1 <= levels <= L.  `*bytes` (optional) = 148.  No kc_init.
+ *                        BC5 83, BC7 98, with KC_BC_SRGB BC1 72, BC3 78, BC7 99.  1 <= levels <= L.  `*bytes` (optional) = 148.
+ *                        No kc_init.
  *   kc_image_write_dds   the header, then the chain (with_mips != 0) or level 0 alone.
  * Errors, in this order: unknown flag bits, or KC_BC_SRGB with BC4 / BC5, KC_ERR_UNSUPPORTED; a NULL argument, a zero size, an
  * unknown format, a size below the total KC_ERR_INVALID_ARG; KC_ERR_NO_DEVICE before kc_init; KC_ERR_NO_SLOT_DATA where

@@ -642,15 +642,19 @@ def _device_export(call, size, dtype, layout, channels, srgb, out):
     return out
 
 
-BC_SRGB = 1  # kc_image_to_bc: BC1 / BC3 colour as to_u8_srgb writes it (alpha linear)
-BC_BLOCK_BYTES = {1: 8, 3: 16, 4: 8, 5: 16}  # kc_bc_format -> bytes per 4 x 4 block
+BC_SRGB = 1  # kc_image_to_bc: BC1 / BC3 / BC7 colour as to_u8_srgb writes it (alpha linear)
+BC7 = 98     # KC_BC7: DXGI_FORMAT_BC7_UNORM's number (7 is not a format and stays refused)
+BC_BLOCK_BYTES = {1: 8, 3: 16, 4: 8, 5: 16, BC7: 16}  # kc_bc_format -> bytes per 4 x 4 block
 
 
 def _bc_format(fmt):
-    """1, 3, 4, 5 or "bc1" / "BC3" / ... -> kc_bc_format"""
-    f = int(str(fmt).lower().lstrip("bc")) if isinstance(fmt, str) else int(fmt)
+    """1, 3, 4, 5, BC7 (98) or "bc1" / "BC3" / ... / "bc7" -> kc_bc_format"""
+    if isinstance(fmt, str):
+        f = BC7 if fmt.lower() == "bc7" else int(fmt.lower().lstrip("bc"))
+    else:
+        f = int(fmt)
     if f not in BC_BLOCK_BYTES:
-        raise ValueError("BC format must be 1, 3, 4 or 5, not %r" % (fmt,))
+        raise ValueError("BC format must be 1, 3, 4, 5 or BC7 (98), not %r" % (fmt,))
     return f
 
 
@@ -844,8 +848,8 @@ class SlotImage:
                               srgb, out)
 
     def to_bc(self, fmt, srgb=False):
-        """-> uint8 (ceil(h/4), ceil(w/4), block bytes): the image's BC1, BC3, BC4 or BC5 blocks (kc_image_to_bc), encoded on the
-        device from the RGBA8 bytes to_u8(srgb) writes; srgb is for BC1 and BC3 only."""
+        """-> uint8 (ceil(h/4), ceil(w/4), block bytes): the image's BC1, BC3, BC4, BC5 or BC7 (fmt = BC7) blocks (kc_image_to_bc),
+        encoded on the device from the RGBA8 bytes to_u8(srgb) writes; srgb is for BC1, BC3 and BC7 only."""
         f = _bc_format(fmt)
         s = self.size()
         out = np.empty(((s.height + 3) // 4, (s.width + 3) // 4, BC_BLOCK_BYTES[f]), np.uint8)

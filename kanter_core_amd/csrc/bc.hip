@@ -4,34 +4,16 @@
 // a wave take consecutive blocks of a block row and each of the block's four pixel rows is one 16-byte load per plane and lane,
 // contiguous across the wave (the library's planes, kc_plane_wrap's included, are readable in whole float4 quads).  The texels
 // are quantised as they arrive and kept as RGBA8 words; the encoder is integer arithmetic on them; a block leaves in one 8- or
-// 16-byte store.
+// 16-byte store.  bc7.hip is the same stream with the BC7 encoder.
 #include "kc_internal.hpp"
 
 namespace kc {
 
 #include "streaming.h"  // grid_cap, ld_policy, quant_u8 / quant_u8_srgb: shared with u8.hip
-
-typedef float bc_f4 __attribute__((ext_vector_type(4)));
-typedef uint32_t bc_u4 __attribute__((ext_vector_type(4)));
-typedef uint32_t bc_u2 __attribute__((ext_vector_type(2)));
-typedef int16_t bc_s2 __attribute__((ext_vector_type(2)));
-typedef uint16_t bc_h2 __attribute__((ext_vector_type(2)));
+#include "bc_blocks.h"  // the row loaders, the quantiser, the column clamp and BcBlockArgs: shared with bc7.hip
 
 // The channels a format reads: bit c = channel c (R, G, B, A)
 static constexpr uint32_t bc_channels(int fmt) { return fmt == 1 ? 0x7u : fmt == 3 ? 0xfu : fmt == 4 ? 0x1u : 0x3u; }
-
-template <bool NT>
-static __device__ __forceinline__ bc_f4 bc_load(const Operand &o, uint32_t row, uint32_t q)
-{
-    if (o.ptr == nullptr) return bc_f4{ o.c, o.c, o.c, o.c };  // a constant plane: no memory read
-    return ld_policy<NT>(reinterpret_cast<const bc_f4 *>(o.ptr + (size_t)row * o.pitch + 4 * q));
-}
-
-template <bool SRGB>
-static __device__ __forceinline__ uint32_t bc_quant(float v, int c, const uint32_t *srgb_tab)
-{
-    return (SRGB && c < 3) ? quant_u8_srgb(v, srgb_tab) : quant_u8(v);  // alpha stays linear
-}
 
 // BC4 of the 16-bit lane at bit `sh` (0 or 16) of the 16 texel words: e0 = max, e1 = min; ramp r = floor((14 (v - e1) + d) / 2d)
 // by the exact reciprocal m = ceil(2^21 / 2d) (x = 14 (v - e1) + d < 3826 and the rounding error of m below 2d keep x m >> 21
@@ -73,9 +55,6 @@ static __device__ __forceinline__ uint32_t pack565(uint32_t r, uint32_t g, uint3
 {
     return ((31u * r + 127u) / 255u) << 11 | ((63u * g + 127u) / 255u) << 5 | ((31u * b + 127u) / 255u);
 }
-
-static __device__ __forceinline__ bc_s2 as_s2(uint32_t x) { return __builtin_bit_cast(bc_s2, x); }
-static __device__ __forceinline__ bc_h2 as_h2(uint32_t x) { return __builtin_bit_cast(bc_h2, x); }
 
 // BC1 of texels held as rb = R | B << 16 and ga = G | A << 16 (alpha ignored), so that the channel ranges are packed 16-bit
 // min / max and the sums over channels 16-bit dot products.  Endpoints: the colour box inset by 1/16 of each range, on the
@@ -147,60 +126,6 @@ static __device__ __forceinline__ bc_u2 encode_bc1(const uint32_t (&rb)[16], con
     return bc_u2{ c0 | (c1 << 16), word };
 }
 
-struct BcBlockArgs {
-    char *dst;
-    uint64_t row_pitch;  // bytes between block rows
-    uint32_t w, h, bx, by;
-};
-
-// Row y of a block's texels, raw: a 16-byte load per channel the format reads (Gray: the plane once, for R; a constant: none)
-template <int FMT, bool NT>
-static __device__ __forceinline__ void bc_load_row(const Operand (&op)[4], int gray, const BcBlockArgs &a, uint32_t i, uint32_t j, int y,
-                                                   bool wave_edge, bc_f4 (&v)[4])
-{
-    constexpr uint32_t CH = bc_channels(FMT);
-    uint32_t row = 4 * j + y;
-    if (wave_edge) row = min(row, a.h - 1);  // bottom edge blocks repeat the last row
-#pragma unroll
-    for (int c = 0; c < 4; ++c) {
-        if (!((CH >> c) & 1u)) continue;
-        if (gray && c > 0 && c < 3) continue;
-        v[c] = bc_load<NT>(op[c], row, i);
-    }
-}
-
-// ... quantised to 8 bits and packed as rb = R | B << 16, ga = G | A << 16 (Gray: (v, v, v, A))
-template <int FMT, bool SRGB>
-static __device__ __forceinline__ void bc_quantise_row(const bc_f4 (&v)[4], int gray, int y, const uint32_t *srgb_tab, uint32_t (&rb)[16],
-                                                       uint32_t (&ga)[16])
-{
-    constexpr uint32_t CH = bc_channels(FMT);
-#pragma unroll
-    for (int x = 0; x < 4; ++x) {
-        const uint32_t r = bc_quant<SRGB>(v[0][x], 0, srgb_tab);
-        uint32_t g = 0u, b = 0u, al = 0u;
-        if constexpr ((CH & 2u) != 0) g = gray ? r : bc_quant<SRGB>(v[1][x], 1, srgb_tab);
-        if constexpr ((CH & 4u) != 0) b = gray ? r : bc_quant<SRGB>(v[2][x], 2, srgb_tab);
-        if constexpr ((CH & 8u) != 0) al = quant_u8(v[3][x]);
-        rb[4 * y + x] = r | (b << 16);
-        ga[4 * y + x] = g | (al << 16);
-    }
-}
-
-// Right edge blocks: the columns past the width repeat the last one
-static __device__ __forceinline__ void bc_clamp_columns(const BcBlockArgs &a, uint32_t i, uint32_t (&rb)[16], uint32_t (&ga)[16])
-{
-    const uint32_t last = min(a.w - 1 - 4 * i, 3u);
-#pragma unroll
-    for (int y = 0; y < 4; ++y)
-#pragma unroll
-        for (int x = 1; x < 4; ++x)
-            if ((uint32_t)x > last) {
-                rb[4 * y + x] = rb[4 * y + x - 1];
-                ga[4 * y + x] = ga[4 * y + x - 1];
-            }
-}
-
 template <int FMT>
 static __device__ __forceinline__ void bc_encode_store(const uint32_t (&rb)[16], const uint32_t (&ga)[16], const BcBlockArgs &a, uint32_t i,
                                                        uint32_t j)
@@ -240,17 +165,17 @@ __global__ __launch_bounds__(256) void bc_encode_kernel(Operand r, Operand g, Op
         bool we = false;
         block_of(in_range ? idx : 0u, i, j, we);
         bc_f4 v[4];
-        if (in_range) bc_load_row<FMT, NT>(op, gray, a, i, j, 0, we, v);
+        if (in_range) bc_load_row<bc_channels(FMT), NT>(op, gray, a, i, j, 0, we, v);
         srgb_t[threadIdx.x] = kSrgbThresholdBits[threadIdx.x];  // 256 threads
         if (threadIdx.x == 0) srgb_t[256] = 0xffffffffu;         // sentinel: nothing is >= it
         __syncthreads();
         if (!in_range) return;
         uint32_t rb[16], ga[16];
-        bc_quantise_row<FMT, SRGB>(v, gray, 0, srgb_t, rb, ga);
+        bc_quantise_row<bc_channels(FMT), SRGB>(v, gray, 0, srgb_t, rb, ga);
 #pragma unroll
         for (int y = 1; y < 4; ++y) {
-            bc_load_row<FMT, NT>(op, gray, a, i, j, y, we, v);
-            bc_quantise_row<FMT, SRGB>(v, gray, y, srgb_t, rb, ga);
+            bc_load_row<bc_channels(FMT), NT>(op, gray, a, i, j, y, we, v);
+            bc_quantise_row<bc_channels(FMT), SRGB>(v, gray, y, srgb_t, rb, ga);
         }
         if (we) bc_clamp_columns(a, i, rb, ga);
         bc_encode_store<FMT>(rb, ga, a, i, j);
@@ -264,8 +189,8 @@ __global__ __launch_bounds__(256) void bc_encode_kernel(Operand r, Operand g, Op
 #pragma unroll
         for (int y = 0; y < 4; ++y) {
             bc_f4 v[4];
-            bc_load_row<FMT, NT>(op, gray, a, i, j, y, we, v);
-            bc_quantise_row<FMT, SRGB>(v, gray, y, srgb_t, rb, ga);
+            bc_load_row<bc_channels(FMT), NT>(op, gray, a, i, j, y, we, v);
+            bc_quantise_row<bc_channels(FMT), SRGB>(v, gray, y, srgb_t, rb, ga);
         }
         if (we) bc_clamp_columns(a, i, rb, ga);
         bc_encode_store<FMT>(rb, ga, a, i, j);

@@ -305,6 +305,10 @@ uint32_t channel_stats_groups(uint32_t w, uint32_t h, bool hist, bool srgb, uint
 // once); nt_mask bits 0-7: nontemporal plane loads; srgb: BC1 and BC3 only
 hipError_t launch_bc_encode(int fmt, int srgb, const Operand op[4], int gray, char *dst, uint64_t row_pitch, uint32_t w, uint32_t h,
                             uint32_t nt_mask, hipStream_t s);
+// -- bc7.hip --
+// bc7_encode_kernel<srgb, nt>: the same for KC_BC7 (16-byte blocks, all four channels)
+hipError_t launch_bc7_encode(int srgb, const Operand op[4], int gray, char *dst, uint64_t row_pitch, uint32_t w, uint32_t h, uint32_t nt_mask,
+                             hipStream_t s);
 // -- mip.hip --
 // Mip chains (mip.hip / mip.cpp): the 2 x 2 box of the header on the n_planes distinct resident planes of one image.
 // mip_pyramid_kernel<nt>: levels 1..n (1 <= n <= 6, both of w >> n and h >> n still >= 1) of the w x h source planes, one

@@ -1,5 +1,6 @@
-"""Block compression at 4096^2 (csrc/bc.hip): kernel time, algorithmic bytes and the fraction of 8 TB/s per case -- Gray BC4;
-RGBA BC1, BC1 sRGB, BC3, BC3 sRGB, BC4 and BC5; random data and a uniform image (every block takes the d == 0 / c0 == c1 path)
+"""Block compression at 4096^2 (csrc/bc.hip, csrc/bc7.hip): kernel time, algorithmic bytes and the fraction of 8 TB/s per case --
+Gray BC4; RGBA BC1, BC1 sRGB, BC3, BC3 sRGB, BC4, BC5, BC7 and BC7 sRGB; random data and a uniform image (every block takes the
+d == 0 / c0 == c1 path; BC7 searches its palettes all the same)
 -- with kc_image_to_device U8 of the same images beside them as the yardstick, and the wall-clock of kc_image_to_bc against
 kc_image_to_u8 plus the numpy reference encoder (tests/bc_ref.py) for the same blocks.
 
@@ -22,14 +23,15 @@ sys.path.insert(0, ROOT)
 N = 4096
 PEAK_TBS = 8.0
 PX = N * N
-BLOCK_BYTES = {1: 8, 3: 16, 4: 8, 5: 16}
-PLANES = {1: 3, 3: 4, 4: 1, 5: 2}  # RGBA planes each format reads
+BC7 = 98  # KC_BC7
+BLOCK_BYTES = {1: 8, 3: 16, 4: 8, 5: 16, BC7: 16}
+PLANES = {1: 3, 3: 4, 4: 1, 5: 2, BC7: 4}  # RGBA planes each format reads
 # (name, channels, data, kind, fmt, srgb); kind "bc" or "u8" (kc_image_to_device U8, the yardstick)
 CASES = []
 for _data in ("random", "uniform"):
     CASES.append(("Gray BC4 %s" % _data, 1, _data, "bc", 4, False))
-    for _fmt, _srgb in ((1, False), (1, True), (3, False), (3, True), (4, False), (5, False)):
-        CASES.append(("RGBA BC%d%s %s" % (_fmt, " sRGB" if _srgb else "", _data), 4, _data, "bc", _fmt, _srgb))
+    for _fmt, _srgb in ((1, False), (1, True), (3, False), (3, True), (4, False), (5, False), (BC7, False), (BC7, True)):
+        CASES.append(("RGBA BC%d%s %s" % (7 if _fmt == BC7 else _fmt, " sRGB" if _srgb else "", _data), 4, _data, "bc", _fmt, _srgb))
     CASES.append(("RGBA to_device U8 %s" % _data, 4, _data, "u8", 0, False))
 
 
@@ -97,7 +99,7 @@ def report(trace_csv, log):
     col = lambda key: next(k for k in rows[0] if key in k)  # noqa: E731
     kn, ks, ke = col("Kernel_Name"), col("Start_Timestamp"), col("End_Timestamp")
     rows.sort(key=lambda r: int(r[ks]))
-    ours = [r for r in rows if "bc_encode_kernel" in r[kn] or "image_export_kernel" in r[kn]]
+    ours = [r for r in rows if "bc_encode_kernel" in r[kn] or "bc7_encode_kernel" in r[kn] or "image_export_kernel" in r[kn]]
     per = reps + 1
     # the cases' dispatches come first; the wall-clock comparison's calls follow them
     assert len(ours) >= len(CASES) * per, (len(ours), len(CASES) * per)
@@ -107,7 +109,7 @@ def report(trace_csv, log):
     out.append("%-30s %10s %10s %9s" % ("case", "median us", "alg MB", "of 8TB/s"))
     for i, (name, ch, _, kind, fmt, _) in enumerate(CASES):
         seg = ours[i * per:(i + 1) * per]
-        want = "image_export_kernel" if kind == "u8" else "bc_encode_kernel"
+        want = "image_export_kernel" if kind == "u8" else "bc7_encode_kernel" if fmt == BC7 else "bc_encode_kernel"
         assert all(want in r[kn] for r in seg), name
         ns = statistics.median([int(r[ke]) - int(r[ks]) for r in seg[1:]])
         b = case_bytes(ch, kind, fmt)

@@ -36,7 +36,7 @@ static uint32_t bits(float f)
 int main()
 {
     const uint32_t sizes[] = { 1, 2, 3, 4, 5, 63, 64, 65, 70, 130, 4096, 65535, 65536, 1u << 20, 0x7fffffffu, 0x80000000u, 0xffffffffu };
-    const int formats[] = { KC_BC1, KC_BC3, KC_BC4, KC_BC5 };
+    const int formats[] = { KC_BC1, KC_BC3, KC_BC4, KC_BC5, KC_BC7 };
     for (uint32_t w : sizes)
         for (uint32_t h : sizes) {
             uint32_t L = 0;
@@ -59,7 +59,7 @@ int main()
                 if (L > 1) CHECK(kc_bc_mip_layout(w, h, f, &n, offs.data(), L - 1, &total) == KC_ERR_INVALID_ARG);
                 std::vector<uint8_t> hdr(148);  // exactly 148 bytes
                 size_t hb = 0;
-                const int hs = kc_dds_header(w, h, f, f == KC_BC1 || f == KC_BC3 ? KC_BC_SRGB : 0u, L, hdr.data(), &hb);
+                const int hs = kc_dds_header(w, h, f, f == KC_BC1 || f == KC_BC3 || f == KC_BC7 ? KC_BC_SRGB : 0u, L, hdr.data(), &hb);
                 const bool says = (((uint64_t)w + 3) / 4) * (((uint64_t)h + 3) / 4) * (f == KC_BC1 || f == KC_BC4 ? 8 : 16) <= 0xffffffffull;
                 CHECK(hs == (says ? KC_OK : KC_ERR_INVALID_ARG));
                 if (says) CHECK(hb == 148 && std::memcmp(hdr.data(), "DDS ", 4) == 0);
