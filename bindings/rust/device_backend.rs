@@ -139,6 +139,29 @@ impl SlotImage {
         check(unsafe { kc_image_to_bc_mips(self.raw(), format, flags, out.as_mut_ptr(), out.len()) })?;
         Ok((out, offsets))
     }
+    /// The image that tightly packed BC blocks decode to (kc_image_from_bc), decoded on the device: to_u8 of the result is exactly
+    /// the decoded bytes.  `gray` (BC4 only): a Gray image of the channel.  Also returns the BC7 blocks of partitioned modes,
+    /// which are not decoded and give (0, 0, 0, 0).
+    pub fn from_bc(blocks: &[u8], size: Size, format: i32, gray: bool) -> Result<(Self, u64)> {
+        let (mut out, mut undecoded) = (ptr::null_mut(), 0u64);
+        let flags = if gray { KC_BC_GRAY } else { 0 };
+        check(unsafe { kc_image_from_bc(blocks.as_ptr(), blocks.len(), size.width, size.height, format, flags, &mut out, &mut undecoded) })?;
+        Ok((wrap(out), undecoded))
+    }
+    /// How far the image's BC encoding is from the image (kc_image_bc_error): the decoded bytes against the bytes to_u8 (`srgb`:
+    /// to_u8_srgb) writes, summed over the image's pixels on the device.
+    pub fn bc_error(&self, format: i32, srgb: bool) -> Result<KcBcError> {
+        let mut out: KcBcError = unsafe { std::mem::zeroed() };
+        check(unsafe { kc_image_bc_error(self.raw(), format, if srgb { KC_BC_SRGB } else { 0 }, &mut out) })?;
+        Ok(out)
+    }
+    /// Level `level` of a .dds file of BC blocks, decoded as from_bc (kc_image_read_dds), and what its header says.
+    pub fn read_dds(path: &std::path::Path, level: u32, gray: bool) -> Result<(Self, KcDdsInfo)> {
+        let c = std::ffi::CString::new(path.to_string_lossy().as_bytes()).map_err(|_| TexProError::Generic)?;
+        let (mut out, mut info): (*mut KcImage, KcDdsInfo) = (ptr::null_mut(), unsafe { std::mem::zeroed() });
+        check(unsafe { kc_image_read_dds(c.as_ptr(), level, if gray { KC_BC_GRAY } else { 0 }, &mut out, &mut info) })?;
+        Ok((wrap(out), info))
+    }
 }
 
 /// src/shared.rs:218-261 (decode with the `image` crate as before, then hand the u8 samples over).

@@ -516,6 +516,102 @@ KC_API int kc_image_to_bc_mips(kc_image *img, int format, uint32_t flags, uint8_
 KC_API int kc_image_to_bc_mips_device(kc_image *img, int format, uint32_t flags, void *device_ptr, size_t bytes, void *hip_stream);
 KC_API int kc_dds_header(uint32_t width, uint32_t height, int format, uint32_t flags, uint32_t levels, uint8_t out[148], size_t *bytes);
 KC_API int kc_image_write_dds(kc_image *img, const char *path, int format, uint32_t flags, int with_mips);
+/* The way back: BC blocks decoded on the device, the error of an encoding measured on the device, and .dds files read.
+ * Decoding is integer arithmetic on the block's bytes, so the pixels are exact (tests/bc_decode_ref.py is the same rules in
+ * numpy).  Pixel (x, y) is texel 4 (y % 4) + x % 4 of block (x / 4, y / 4); texels of edge blocks outside the image are dropped.
+ *   BC1     c0, c1 u16 LE, then a u32 LE with texel t's index at bits 2t..2t+1; E() expands 5:6:5 by bit replication.  c0 > c1:
+ *           palette E0, E1, (2 E0 + E1 + 1) div 3, (E0 + 2 E1 + 1) div 3, alpha 255.  Otherwise E0, E1, (E0 + E1) div 2 with alpha
+ *           255, and index 3 is (0, 0, 0) with alpha 0.
+ *   BC4     bytes e0, e1, then a 48-bit LE word with texel t's index at bits 3t..3t+2.  Indices 0 and 1 are e0 and e1.  e0 > e1:
+ *           index i >= 2 is ((8 - i) e0 + (i - 1) e1 + 3) div 7.  Otherwise i in 2..5 is ((6 - i) e0 + (i - 1) e1 + 2) div 5,
+ *           i = 6 is 0 and i = 7 is 255.
+ *   BC3     the BC4 block is alpha; the BC1 block after it always decodes in four-colour mode, whatever the order of c0 and c1.
+ *   BC5     the BC4 block of R, then that of G.
+ *   BC7     the three single-subset modes 4, 5 and 6, in full: everything kc_image_to_bc writes and everything else that needs
+ *           no partition table.  The mode is the position of the lowest set bit of byte 0; bit order, interp, W2 and W4 as for
+ *           the encoder above; W3 = 0, 9, 18, 27, 37, 46, 55, 64.  Modes 6 and 5 have the layouts given above, mode 5 with any
+ *           rotation.  Mode 4: bits 0-4 the value 16; rotation (5-6); index selection (7); R0, R1, G0, G1, B0, B1 of 5 bits
+ *           each (8-37), decoded (q << 3) | (q >> 2); A0, A1 of 6 bits each (38-49), decoded (q << 2) | (q >> 4); the 2-bit
+ *           index set, texel 0 in 1 bit (50), texels 1-15 in 2 bits each (51-80); the 3-bit set, texel 0 in 2 bits (81-82),
+ *           texels 1-15 in 3 bits each (83-127).  Index selection 0: colour takes the 2-bit set with W2, alpha the 3-bit set with
+ *           W3; 1: colour the 3-bit set with W3, alpha the 2-bit set with W2.  Rotation r in 1..3 (modes 4 and 5) swaps alpha
+ *           with channel r - 1 after the interpolation.  Byte 0 == 0 is the reserved mode: (0, 0, 0, 0), as the format defines.
+ *           Blocks of the partitioned modes 0, 1, 2, 3 and 7 are NOT decoded: they give (0, 0, 0, 0) and are counted in
+ *           `*undecoded_blocks`.  The other formats always count 0.
+ *   kc_image_from_bc         `host`: tightly packed block rows, exactly what kc_image_to_bc writes (`host_bytes` at least
+ *                            bx * by * block bytes).  `*out` (+1 reference) owns new planes; a decoded byte b is the f32
+ *                            b / 255.f with the IEEE divide, as kc_image_from_u8 makes it, so kc_image_to_u8(*out, 0) returns
+ *                            exactly the decoded bytes.  No transfer function is applied.  The image is RGBA: BC1 / BC3 / BC7
+ *                            four resident planes (BC1's alpha 0 or 1); BC4 R resident, G = B = 0 and A = 1 constant planes;
+ *                            BC5 R and G resident, B = 0 and A = 1 constant (the sampling convention; constant planes cost no
+ *                            stores).  KC_BC_GRAY (BC4 only): a Gray image of the channel.  The call waits for its upload.
+ *   kc_image_from_bc_device  the same from a kc_bc_image (kc_bc_image_validate's rules), ordered against `hip_stream` by the two
+ *                            event edges of kc_image_to_bc_device; nothing aliases the caller's blocks.  With a non-NULL
+ *                            `undecoded_blocks` and KC_BC7 the call blocks until the count is on the host, as
+ *                            kc_image_channel_stats does; with NULL, or another format (count 0), it does not wait.
+ *                            Errors, in this order: flag bits other than KC_BC_GRAY (KC_BC_SRGB included), or KC_BC_GRAY with a
+ *                            format other than KC_BC4, KC_ERR_UNSUPPORTED; a NULL argument (`undecoded_blocks` may be NULL), an
+ *                            unknown format, a zero size, more than 2^31 blocks, `host_bytes` below the blocks' bytes or a
+ *                            descriptor kc_bc_image_validate refuses KC_ERR_INVALID_ARG; KC_ERR_NO_DEVICE before kc_init.
+ *                            kc_stats: one launch (KC_BC7 with a count: two, the second sums the workgroups' counts), the
+ *                            blocks' bytes plus 4 w h algorithmic bytes per resident plane written; a refused call launches nothing.
+ *   kc_bc_error              the error of blocks against an image.  The source bytes are what kc_image_to_u8(img, srgb) writes
+ *                            with srgb = flags & KC_BC_SRGB (Gray = (v, v, v, 1); the encoders' quantiser functions); the
+ *                            decoded bytes are those above.  Only the image's pixels count, not the replicated texels of edge
+ *                            blocks; undecoded blocks contribute their (0, 0, 0, 0).  The mask holds the channels the format
+ *                            encodes (BC1: not alpha, which its encoder ignores).
+ *   kc_image_bc_compare      any blocks of the image's size, the library's own or another encoder's.
+ *   kc_image_bc_error        encodes into pool staging with kc_image_to_bc's encoder, then compares.
+ *                            kc_live_graph_buffer_bc_error: the same for a slot's image.
+ *                            Both block until the host values are there (kc_image_channel_stats' event).  Flags: kc_image_to_bc's
+ *                            rule.  Errors, in this order: that rule's KC_ERR_UNSUPPORTED; a NULL argument, an unknown format, a
+ *                            descriptor kc_bc_image_validate refuses KC_ERR_INVALID_ARG; KC_ERR_NO_DEVICE before kc_init; a
+ *                            descriptor size that differs from the image's KC_ERR_INVALID_ARG; KC_ERR_NO_SLOT_DATA where
+ *                            kc_live_graph_buffer_bc returns it.  `*out` is written on KC_OK only.  A pending chain or resample
+ *                            runs first.  kc_stats: kc_image_bc_compare two launches (the comparison, whose workgroups each
+ *                            leave one record of integer sums, and a small combining launch), 4 w h
+ *                            algorithmic bytes per distinct resident plane the format reads plus the blocks' bytes;
+ *                            kc_image_bc_error three launches, the encoder's launch and bytes first.  Constant planes cost no
+ *                            loads.
+ *   kc_dds_parse             arithmetic on a buffer that holds a whole .dds file; no kc_init.  Accepted: the
+ *                            DX10 form kc_dds_header writes (dxgiFormat 71, 72, 77, 78, 80, 83, 98 or 99, TEXTURE2D, array size
+ *                            1, no cube flag; data at byte 148) and the legacy FourCCs DXT1, DXT5, ATI1 / BC4U, ATI2 / BC5U (data
+ *                            at byte 128).  `levels` = dwMipMapCount when DDSD_MIPMAPCOUNT is set and the count non-zero, else 1;
+ *                            at most kc_mip_level_count.  `data_bytes` = what kc_bc_mip_layout gives for those levels.  Errors, in
+ *                            this order: a NULL argument, fewer than 128 bytes (148: DX10), a bad magic, dwSize != 124, a pixel
+ *                            format size != 32 or a zero extent KC_ERR_INVALID_ARG; a well-formed header of anything else
+ *                            (uncompressed, BC2, BC6H, signed, typeless, arrays, cube maps, volumes) KC_ERR_UNSUPPORTED; `levels`
+ *                            above the level count, or a buffer shorter than data_offset + data_bytes, KC_ERR_INVALID_ARG.
+ *   kc_image_read_dds        kc_image_from_bc of level `level` of the file (kc_bc_mip_layout's offsets).  flags: KC_BC_GRAY only.
+ *                            `info` (optional) is written once the header has parsed.  Errors, in this order: flag bits other
+ *                            than KC_BC_GRAY KC_ERR_UNSUPPORTED; a NULL path or `out` KC_ERR_INVALID_ARG; a file that cannot be
+ *                            opened or read KC_ERR_IO; kc_dds_parse's errors (a file shorter than its header says is
+ *                            KC_ERR_INVALID_ARG); level >= levels KC_ERR_INVALID_ARG; then kc_image_from_bc's. */
+#define KC_BC_GRAY 4u  /* decode, BC4 only: a Gray image of the channel instead of the RGBA rule */
+typedef struct kc_bc_error {
+    int32_t format;              /* kc_bc_format of the blocks */
+    uint32_t flags;              /* the flags the call was given */
+    uint32_t channel_mask;       /* bit c: channel c is compared: BC1 0x7, BC3 / BC7 0xF, BC4 0x1, BC5 0x3 */
+    uint64_t pixels;             /* width * height: the image's pixels, not the blocks' texels */
+    uint64_t sse[4];             /* sum over the pixels of (decoded byte - source byte)^2; 0 outside the mask */
+    uint32_t max_abs[4];         /* largest |decoded byte - source byte|; 0 outside the mask */
+    uint64_t undecoded_blocks;   /* as kc_image_from_bc_device counts them */
+    uint64_t bc7_mode_blocks[8]; /* BC7: blocks per mode 0..7 (reserved blocks in none); zero for the other formats */
+} kc_bc_error;
+typedef struct kc_dds_info {
+    uint32_t width, height;
+    int32_t format;              /* kc_bc_format */
+    uint32_t flags;              /* KC_BC_SRGB for dxgiFormat 72 / 78 / 99 */
+    uint32_t levels;
+    size_t data_offset, data_bytes;
+} kc_dds_info;
+KC_API int kc_image_from_bc(const uint8_t *host, size_t host_bytes, uint32_t width, uint32_t height, int format, uint32_t flags,
+                            kc_image **out, uint64_t *undecoded_blocks);
+KC_API int kc_image_from_bc_device(const kc_bc_image *src, uint32_t flags, void *hip_stream, kc_image **out, uint64_t *undecoded_blocks);
+KC_API int kc_image_bc_compare(kc_image *img, const kc_bc_image *blocks, uint32_t flags, kc_bc_error *out);
+KC_API int kc_image_bc_error(kc_image *img, int format, uint32_t flags, kc_bc_error *out);
+KC_API int kc_dds_parse(const uint8_t *data, size_t bytes, kc_dds_info *info);
+KC_API int kc_image_read_dds(const char *path, uint32_t level, uint32_t flags, kc_image **out, kc_dds_info *info);
 /* read_slot_image, src/shared.rs:218-261 (PNG only; decode on host, planes built on device). */
 KC_API int kc_image_read_png(const char *path, kc_image **out);
 KC_API int kc_image_write_png(kc_image *img, const char *path);        /* src/node/write.rs:5-21 */
@@ -621,6 +717,8 @@ KC_API int kc_live_graph_buffer_bc(kc_live_graph *lg, uint32_t node_id, uint32_t
                                    uint32_t flags, void *hip_stream); /* kc_image_to_bc_device of a slot's image */
 KC_API int kc_live_graph_buffer_bc_mips(kc_live_graph *lg, uint32_t node_id, uint32_t slot_id, int format, uint32_t flags,
                                         void *device_ptr, size_t bytes, void *hip_stream); /* kc_image_to_bc_mips_device likewise */
+KC_API int kc_live_graph_buffer_bc_error(kc_live_graph *lg, uint32_t node_id, uint32_t slot_id, int format, uint32_t flags,
+                                         kc_bc_error *out); /* kc_image_bc_error of a slot's image */
 KC_API int kc_live_graph_embed_slot_data_with_id(kc_live_graph *lg, kc_image *image, uint32_t slot_id, uint32_t embed_id); /* :324-341 */
 KC_API int kc_live_graph_add_input_slot_data(kc_live_graph *lg, uint32_t node_id, uint32_t slot_id, kc_image *image);     /* :347-350 */
 KC_API int kc_live_graph_changed_consume(kc_live_graph *lg, uint32_t *ids, uint32_t cap, uint32_t *count);               /* :156-160 */

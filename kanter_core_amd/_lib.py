@@ -61,6 +61,16 @@ class kc_bc_image(C.Structure):
     _fields_ = [("ptr", c_vp), ("width", C.c_uint32), ("height", C.c_uint32), ("format", C.c_int32), ("row_pitch_bytes", C.c_size_t)]
 
 
+class kc_bc_error(C.Structure):
+    _fields_ = [("format", C.c_int32), ("flags", C.c_uint32), ("channel_mask", C.c_uint32), ("pixels", C.c_uint64), ("sse", C.c_uint64 * 4),
+                ("max_abs", C.c_uint32 * 4), ("undecoded_blocks", C.c_uint64), ("bc7_mode_blocks", C.c_uint64 * 8)]
+
+
+class kc_dds_info(C.Structure):
+    _fields_ = [("width", C.c_uint32), ("height", C.c_uint32), ("format", C.c_int32), ("flags", C.c_uint32), ("levels", C.c_uint32),
+                ("data_offset", C.c_size_t), ("data_bytes", C.c_size_t)]
+
+
 # name -> (restype, argtypes); every symbol include/kanter_core_amd.h declares.
 SIGNATURES = {
     "kc_init": (C.c_int, [C.c_int]),
@@ -166,6 +176,12 @@ SIGNATURES = {
     "kc_image_to_bc_mips_device": (C.c_int, [c_vp, C.c_int, C.c_uint32, c_vp, C.c_size_t, c_vp]),
     "kc_dds_header": (C.c_int, [C.c_uint32, C.c_uint32, C.c_int, C.c_uint32, C.c_uint32, c_vp, C.POINTER(C.c_size_t)]),
     "kc_image_write_dds": (C.c_int, [c_vp, C.c_char_p, C.c_int, C.c_uint32, C.c_int]),
+    "kc_image_from_bc": (C.c_int, [c_vp, C.c_size_t, C.c_uint32, C.c_uint32, C.c_int, C.c_uint32, C.POINTER(c_vp), C.POINTER(C.c_uint64)]),
+    "kc_image_from_bc_device": (C.c_int, [C.POINTER(kc_bc_image), C.c_uint32, c_vp, C.POINTER(c_vp), C.POINTER(C.c_uint64)]),
+    "kc_image_bc_compare": (C.c_int, [c_vp, C.POINTER(kc_bc_image), C.c_uint32, C.POINTER(kc_bc_error)]),
+    "kc_image_bc_error": (C.c_int, [c_vp, C.c_int, C.c_uint32, C.POINTER(kc_bc_error)]),
+    "kc_dds_parse": (C.c_int, [c_vp, C.c_size_t, C.POINTER(kc_dds_info)]),
+    "kc_image_read_dds": (C.c_int, [C.c_char_p, C.c_uint32, C.c_uint32, C.POINTER(c_vp), C.POINTER(kc_dds_info)]),
     "kc_image_from_f32": (C.c_int, [C.POINTER(c_vp), C.c_int, C.c_uint32, C.c_uint32, C.POINTER(c_vp)]),
     "kc_image_to_f32": (C.c_int, [c_vp, C.POINTER(c_vp), C.c_int]),
     "kc_image_read_png": (C.c_int, [C.c_char_p, C.POINTER(c_vp)]),
@@ -232,6 +248,7 @@ SIGNATURES = {
     "kc_live_graph_buffer_channel_stats": (C.c_int, [c_vp, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(kc_channel_stats)]),
     "kc_live_graph_buffer_bc": (C.c_int, [c_vp, C.c_uint32, C.c_uint32, C.POINTER(kc_bc_image), C.c_uint32, c_vp]),
     "kc_live_graph_buffer_bc_mips": (C.c_int, [c_vp, C.c_uint32, C.c_uint32, C.c_int, C.c_uint32, c_vp, C.c_size_t, c_vp]),
+    "kc_live_graph_buffer_bc_error": (C.c_int, [c_vp, C.c_uint32, C.c_uint32, C.c_int, C.c_uint32, C.POINTER(kc_bc_error)]),
     "kc_live_graph_embed_slot_data_with_id": (C.c_int, [c_vp, c_vp, C.c_uint32, C.c_uint32]),
     "kc_live_graph_add_input_slot_data": (C.c_int, [c_vp, C.c_uint32, C.c_uint32, c_vp]),
     "kc_live_graph_changed_consume": (C.c_int, [c_vp, c_u32p, C.c_uint32, c_u32p]),

@@ -753,6 +753,64 @@ def _channel_stats(call, histogram, srgb):
                         int(r.pixels), hist)
 
 
+BC_GRAY = 4  # kc_image_from_bc, BC4 only: a Gray image of the channel instead of the RGBA rule
+
+
+class BcError(collections.namedtuple("BcError", "format flags channel_mask pixels sse max_abs undecoded_blocks bc7_mode_blocks")):
+    """The error of BC blocks against an image (kc_bc_error): over the image's pixels, of the decoded bytes against the bytes
+    to_u8(srgb) writes.  channel_mask: bit c = channel c is compared (BC1 0x7, BC3 / BC7 0xF, BC4 0x1, BC5 0x3); sse uint64 (4,)
+    the sums of squared differences and max_abs uint32 (4,) the largest differences, 0 outside the mask; undecoded_blocks the
+    BC7 blocks of partitioned modes (they count as (0, 0, 0, 0)); bc7_mode_blocks uint64 (8,) the BC7 blocks per mode."""
+    __slots__ = ()
+
+    def psnr(self, channels=None):
+        """10 log10(255^2 pixels n / sum sse) in dB over the n masked channels (of `channels`, indices 0..3, when given); inf
+        for zero error"""
+        chans = [c for c in range(4) if (self.channel_mask >> c) & 1 and (channels is None or c in channels)]
+        if not chans:
+            raise ValueError("none of the channels %r is in the mask 0x%x" % (channels, self.channel_mask))
+        sse = sum(int(self.sse[c]) for c in chans)
+        return float("inf") if sse == 0 else float(10 * np.log10(255.0 ** 2 * self.pixels * len(chans) / sse))
+
+
+def _bc_error(call, srgb):
+    r = _lib.kc_bc_error()
+    _check(call(BC_SRGB if srgb else 0, C.byref(r)))
+    return BcError(int(r.format), int(r.flags), int(r.channel_mask), int(r.pixels), np.array(r.sse[:], np.uint64), np.array(r.max_abs[:], np.uint32),
+                   int(r.undecoded_blocks), np.array(r.bc7_mode_blocks[:], np.uint64))
+
+
+def _bc_desc(t, width, height, fmt):
+    """kc_bc_image of a uint8 (by, bx, block bytes) tensor whose last two dimensions are contiguous"""
+    import torch
+    f = _bc_format(fmt)
+    bb = BC_BLOCK_BYTES[f]
+    bx, by = (width + 3) // 4, (height + 3) // 4
+    if t.dtype != torch.uint8 or tuple(t.shape) != (by, bx, bb):
+        raise ValueError("blocks must be uint8 of shape %s, got %s %s" % ((by, bx, bb), t.dtype, tuple(t.shape)))
+    if (bx > 1 and t.stride(1) != bb) or t.stride(2) != 1:
+        raise ValueError("blocks need each block row packed: strides (..., %d, 1), got %s" % (bb, t.stride()))
+    return _lib.kc_bc_image(t.data_ptr(), width, height, f, t.stride(0) if by > 1 else bx * bb)
+
+
+DdsInfo = collections.namedtuple("DdsInfo", "width height format srgb levels data_offset data_bytes")
+DdsInfo.__doc__ = """What a .dds header says (kc_dds_info): the size of level 0, the kc_bc_format, whether the dxgiFormat is an
+sRGB one, the levels in the file, and where their blocks lie."""
+
+
+def _dds_info(d):
+    return DdsInfo(d.width, d.height, d.format, bool(d.flags & BC_SRGB), d.levels, d.data_offset, d.data_bytes)
+
+
+def dds_parse(data):
+    """-> DdsInfo of the bytes of a .dds file (kc_dds_parse; no device): the DX10 form dds_header writes and the legacy FourCCs
+    DXT1, DXT5, ATI1 / BC4U, ATI2 / BC5U.  Anything else well-formed raises Unsupported, a malformed or short buffer InvalidArg."""
+    data = bytes(data)
+    d = _lib.kc_dds_info()
+    _check(_lib.load().kc_dds_parse(data, len(data), C.byref(d)))
+    return _dds_info(d)
+
+
 # ------------------------------------------------------------------ SlotImage / SlotData
 class SlotImage:
     """SlotImage (src/slot_image.rs:15-264) backed by device planes."""
@@ -807,6 +865,41 @@ class SlotImage:
         _check(_on_torch_stream(t, lambda stream: _lib.load().kc_image_from_device(C.byref(d), DEVICE_GRAY if gray else 0, stream,
                                                                                     C.byref(out))))
         return SlotImage(out.value)
+
+    @staticmethod
+    def from_bc(blocks, width, height, fmt, gray=False, return_undecoded=False):
+        """The image BC blocks decode to (kc_image_from_bc): uint8 (ceil(h/4), ceil(w/4), block bytes) as to_bc returns them,
+        decoded on the device by the header's integer rules; to_u8() of the result is exactly the decoded bytes.  RGBA (BC4:
+        (r, 0, 0, 1), BC5: (r, g, 0, 1), the missing channels constant planes); gray=True, BC4 only: a Gray image.  BC7: modes
+        4, 5 and 6; blocks of the partitioned modes give (0, 0, 0, 0) and return_undecoded=True returns (image, their count)."""
+        f = _bc_format(fmt)
+        blocks = np.ascontiguousarray(blocks, np.uint8)
+        out, n = C.c_void_p(), C.c_uint64()
+        _check(_lib.load().kc_image_from_bc(blocks.ctypes.data, blocks.nbytes, width, height, f, BC_GRAY if gray else 0, C.byref(out),
+                                            C.byref(n) if return_undecoded else None))
+        img = SlotImage(out.value)
+        return (img, n.value) if return_undecoded else img
+
+    @staticmethod
+    def from_bc_torch(t, width, height, fmt, gray=False, return_undecoded=False):
+        """from_bc of a uint8 (ceil(h/4), ceil(w/4), block bytes) tensor in device memory (kc_image_from_bc_device); any view
+        whose last two dimensions are contiguous.  Ordered on torch's current stream: the image owns its pixels, the tensor may be
+        freed or overwritten by torch as soon as this returns.  return_undecoded=True waits for the count (BC7)."""
+        d = _bc_desc(t, width, height, fmt)
+        out, n = C.c_void_p(), C.c_uint64()
+        _check(_on_torch_stream(t, lambda stream: _lib.load().kc_image_from_bc_device(C.byref(d), BC_GRAY if gray else 0, stream, C.byref(out),
+                                                                                       C.byref(n) if return_undecoded else None)))
+        img = SlotImage(out.value)
+        return (img, n.value) if return_undecoded else img
+
+    @staticmethod
+    def read_dds(path, level=0, gray=False, return_info=False):
+        """Level `level` of a .dds file of BC1, BC3, BC4, BC5 or BC7 blocks, decoded as from_bc (kc_image_read_dds);
+        return_info=True returns (image, DdsInfo)."""
+        out, d = C.c_void_p(), _lib.kc_dds_info()
+        _check(_lib.load().kc_image_read_dds(os.fspath(path).encode(), level, BC_GRAY if gray else 0, C.byref(out), C.byref(d)))
+        img = SlotImage(out.value)
+        return (img, _dds_info(d)) if return_info else img
 
     @staticmethod
     def read_png(path):
@@ -893,6 +986,20 @@ class SlotImage:
     def write_dds(self, path, fmt, srgb=False, mips=True):
         """Writes a .dds file (DX10 header) with the image's BC blocks: the whole mip chain, or level 0 alone (kc_image_write_dds)."""
         _check(_lib.load().kc_image_write_dds(self._h, os.fspath(path).encode(), _bc_format(fmt), BC_SRGB if srgb else 0, int(mips)))
+
+    def bc_error(self, fmt, srgb=False, blocks=None):
+        """-> BcError: how far the image's BC encoding is from the image, measured on the device (kc_image_bc_error): the bytes
+        the blocks decode to against the bytes to_u8(srgb) writes, over the image's pixels.  blocks: a uint8 (ceil(h/4), ceil(w/4),
+        block bytes) tensor in device memory to compare instead of the library's own encoding (kc_image_bc_compare), e.g.
+        another encoder's.  Blocks until the values are there."""
+        f = _bc_format(fmt)
+        if blocks is None:
+            return _bc_error(lambda fl, out: _lib.load().kc_image_bc_error(self._h, f, fl, out), srgb)
+        s = self.size()
+        d = _bc_desc(blocks, s.width, s.height, f)
+        import torch
+        torch.cuda.current_stream(blocks.device).synchronize()  # the call runs on the library's stream: the blocks must be there
+        return _bc_error(lambda fl, out: _lib.load().kc_image_bc_compare(self._h, C.byref(d), fl, out), srgb)
 
     def channel_stats(self, histogram=False, srgb=False):
         """-> ChannelStats of the image, computed on the device (kc_image_channel_stats): the range and NaN count of every
@@ -1254,6 +1361,11 @@ class LiveGraph:
         """SlotImage.to_bc_mips_torch of a slot's image (kc_live_graph_buffer_bc_mips)."""
         return _bc_mips_export(lambda f, fl, p, n, st: _lib.load().kc_live_graph_buffer_bc_mips(self._h, node_id, slot_id, f, fl, p, n, st),
                                self.slot_data_size(node_id, slot_id), fmt, srgb, per_level, out)
+
+    def buffer_bc_error(self, node_id, slot_id, fmt, srgb=False):
+        """SlotImage.bc_error of a slot's image (kc_live_graph_buffer_bc_error)."""
+        f = _bc_format(fmt)
+        return _bc_error(lambda fl, out: _lib.load().kc_live_graph_buffer_bc_error(self._h, node_id, slot_id, f, fl, out), srgb)
 
     def buffer_channel_stats(self, node_id, slot_id, histogram=False, srgb=False):
         """SlotImage.channel_stats of a slot's image (kc_live_graph_buffer_channel_stats)."""

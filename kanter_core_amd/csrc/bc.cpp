@@ -19,7 +19,7 @@ static int bc_refuse(const char *what)
 }
 
 // Flag bits other than KC_BC_SRGB, or KC_BC_SRGB with a format without colour, are KC_ERR_UNSUPPORTED
-static int bc_check_flags(int format, uint32_t flags, const char *who)
+int bc_check_flags(int format, uint32_t flags, const char *who)
 {
     if (flags & ~(uint32_t)KC_BC_SRGB) {
         set_error(std::string(who) + ": flags other than KC_BC_SRGB");

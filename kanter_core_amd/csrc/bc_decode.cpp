@@ -1,0 +1,343 @@
+// Block decode, the error of an encoding and .dds input: kc_image_from_bc, kc_image_from_bc_device, kc_image_bc_compare,
+// kc_image_bc_error, kc_dds_parse, kc_image_read_dds (include/kanter_core_amd.h).  The host side checks the arguments in the
+// header's order, allocates the planes a format holds (constant planes for the channels it does not), and launches
+// bc_decode.hip's kernels on the library's stream: ordered against the caller's stream by the two event edges of
+// kc_image_to_bc_device, or after an upload into pool staging.  The counts and the error record come back through the
+// context's StatsBuffers (stats.cpp): pinned host memory and an event of the call's own.  The .dds parser is arithmetic on
+// bytes, with no device call.
+#include <cstdio>
+
+#include "kc_runtime.hpp"
+
+namespace kc {
+
+static int bcd_refuse(const char *who, const char *what)
+{
+    set_error(std::string(who) + ": " + what);
+    return KC_ERR_INVALID_ARG;
+}
+
+// Flag bits other than KC_BC_GRAY, or KC_BC_GRAY with a format other than BC4, are KC_ERR_UNSUPPORTED
+static int bcd_check_flags(int format, uint32_t flags, const char *who)
+{
+    if (flags & ~(uint32_t)KC_BC_GRAY) {
+        set_error(std::string(who) + ": flags other than KC_BC_GRAY (no transfer function is applied on decode)");
+        return KC_ERR_UNSUPPORTED;
+    }
+    if ((flags & KC_BC_GRAY) && format != KC_BC4) {
+        set_error(std::string(who) + ": KC_BC_GRAY is for BC4 only");
+        return KC_ERR_UNSUPPORTED;
+    }
+    return KC_OK;
+}
+
+// The result words of a reduction, on the host once the call's event has fired
+static int bcd_fetch(uint32_t words)
+{
+    Context &c = ctx();
+    KC_HIP(hipMemcpyAsync(c.stats.host, c.stats.result, words * sizeof(unsigned long long), hipMemcpyDeviceToHost, c.stream));
+    KC_HIP(hipEventRecord(c.stats.done, c.stream));
+    KC_HIP(hipEventSynchronize(c.stats.done));
+    return KC_OK;
+}
+
+// One launch of the decoder (two with a count) on the library's stream: the blocks at `src`, block rows `row_pitch` bytes apart,
+// into a new image.  *counted: the count is in flight and bcd_fetch brings it.
+static int bc_decode(const char *src, size_t row_pitch, uint32_t w, uint32_t h, int format, bool gray, bool want_count, kc_image **out,
+                     bool *counted)
+{
+    Context &c = ctx();
+    const int n_res = format == KC_BC4 ? 1 : format == KC_BC5 ? 2 : 4;
+    const int n = gray ? 1 : 4;
+    kc_plane *p[4] = { nullptr, nullptr, nullptr, nullptr };
+    int s = KC_OK;
+    for (int i = 0; i < n && s == KC_OK; ++i) {
+        if (i < n_res) s = plane_new_mem(w, h, &p[i]);
+        else p[i] = plane_new_const(w, h, i == 3 ? 1.0f : 0.0f);  // the sampling convention: missing G, B = 0, A = 1
+    }
+    const bool count = want_count && format == KC_BC7;
+    BcDecodeArgs a{};
+    uint32_t groups = 0;
+    if (s == KC_OK) {
+        a.src = src;
+        a.row_pitch = row_pitch;
+        a.w = w;
+        a.h = h;
+        a.bx = (w + 3) / 4;
+        a.by = (h + 3) / 4;
+        a.dst_pitch = (uint32_t)(p[0]->pitch / sizeof(float));
+        for (int i = 0; i < n_res; ++i) a.dst[i] = p[i]->dptr;
+        groups = bc_decode_groups(w, h, count);
+        if (count) {
+            s = stats_buffers((size_t)groups * sizeof(unsigned long long));
+            a.partials = (unsigned long long *)c.stats.partials;
+            a.result = c.stats.result;
+        }
+    }
+    if (s == KC_OK) {
+        const uint64_t in_bytes = (uint64_t)a.bx * a.by * bc_block_bytes(format), out_bytes = (uint64_t)w * h * 4 * n_res;
+        hipError_t e = launch_bc_decode(format, a, count, cache_policy_mask(in_bytes, out_bytes, 1), groups, c.stream);
+        if (e != hipSuccess) s = hip_fail(e, "launch_bc_decode");
+        else {
+            c.launches += count ? 2 : 1;
+            c.alg_bytes += in_bytes + out_bytes;
+        }
+    }
+    if (s == KC_OK) *out = image_new(n, p);
+    for (int i = 0; i < 4; ++i) plane_release(p[i]);
+    *counted = s == KC_OK && count;
+    return s;
+}
+
+int image_from_bc(const uint8_t *host, size_t host_bytes, uint32_t w, uint32_t h, int format, uint32_t flags, kc_image **out,
+                  uint64_t *undecoded_blocks)
+{
+    KC_TRY(bcd_check_flags(format, flags, "kc_image_from_bc"));
+    const size_t bb = bc_block_bytes(format);
+    if (bb == 0) return bcd_refuse("kc_image_from_bc", "unknown format");
+    if (!host || !out) return bcd_refuse("kc_image_from_bc", "NULL host buffer or output");
+    if (w == 0 || h == 0) return bcd_refuse("kc_image_from_bc", "zero extent");
+    const uint64_t bx = ((uint64_t)w + 3) / 4, by = ((uint64_t)h + 3) / 4;
+    if (bx * by > (1ull << 31)) return bcd_refuse("kc_image_from_bc", "image too large: more than 2^31 blocks");
+    const size_t nbytes = (size_t)(bx * by) * bb;
+    if (host_bytes < nbytes) return bcd_refuse("kc_image_from_bc", "host_bytes < blocks * block bytes");
+    KC_TRY(need_init());
+    Context &c = ctx();
+    std::lock_guard<std::recursive_mutex> lk(c.mu);
+    const size_t block = (nbytes + 255) / 256 * 256;
+    void *staging = nullptr;
+    KC_TRY(pool_alloc(block, &staging));
+    kc_image *img = nullptr;
+    bool counted = false;
+    hipError_t e = hipMemcpyAsync(staging, host, nbytes, hipMemcpyHostToDevice, c.stream);
+    int s = e == hipSuccess ? bc_decode((const char *)staging, (size_t)bx * bb, w, h, format, (flags & KC_BC_GRAY) != 0, undecoded_blocks != nullptr,
+                                        &img, &counted)
+                            : KC_OK;
+    if (s == KC_OK && e == hipSuccess && counted) s = bcd_fetch(1);
+    if (e == hipSuccess) e = hipStreamSynchronize(c.stream);  // the caller's bytes have been read
+    pool_free(staging, block);
+    if (s == KC_OK && e != hipSuccess) s = hip_fail(e, "image_from_bc");
+    if (s != KC_OK) {
+        image_release(img);
+        return s;
+    }
+    if (undecoded_blocks) *undecoded_blocks = counted ? c.stats.host[0] : 0;
+    *out = img;
+    return KC_OK;
+}
+
+int image_from_bc_device(const kc_bc_image *src, uint32_t flags, void *hip_stream, kc_image **out, uint64_t *undecoded_blocks)
+{
+    KC_TRY(bcd_check_flags(src ? src->format : 0, flags, "kc_image_from_bc_device"));
+    if (!out) return bcd_refuse("kc_image_from_bc_device", "NULL output");
+    KC_TRY(bc_image_validate(src, nullptr));
+    Context &c = ctx();
+    std::lock_guard<std::recursive_mutex> lk(c.mu);
+    hipStream_t hs = (hipStream_t)hip_stream;
+    const bool edges = hs && hs != c.stream;
+    if (edges) KC_TRY(stream_edge(hs, c.stream));
+    kc_image *img = nullptr;
+    bool counted = false;
+    int s = bc_decode((const char *)src->ptr, src->row_pitch_bytes, src->width, src->height, src->format, (flags & KC_BC_GRAY) != 0,
+                      undecoded_blocks != nullptr, &img, &counted);
+    if (s == KC_OK && edges) s = stream_edge(c.stream, hs);
+    if (s == KC_OK && counted) s = bcd_fetch(1);
+    if (s != KC_OK) {
+        image_release(img);
+        return s;
+    }
+    if (undecoded_blocks) *undecoded_blocks = counted ? c.stats.host[0] : 0;
+    *out = img;
+    return KC_OK;
+}
+
+// ---------------------------------------------------------------- the error of an encoding
+// The comparison of `img` (forced already) with the blocks at `blocks`, block rows `row_pitch` bytes apart, on the library's
+// stream; waits for the record.
+static int bc_compare(kc_image *img, int format, uint32_t flags, const char *blocks, size_t row_pitch, kc_bc_error *out)
+{
+    Context &c = ctx();
+    const bool rgba = img->is_rgba();
+    Operand o[4];
+    for (int i = 0; i < 4; ++i) o[i] = rgba ? plane_operand(img->planes[i]) : i < 3 ? plane_operand(img->planes[0]) : Operand{ nullptr, 0, 1.0f };
+    const uint32_t mask = format == KC_BC1 ? 0x7u : format == KC_BC4 ? 0x1u : format == KC_BC5 ? 0x3u : 0xfu;
+    const float *seen[4] = { nullptr, nullptr, nullptr, nullptr };
+    uint32_t n_res = 0;  // distinct resident planes the launch reads
+    for (int i = 0; i < 4; ++i) {
+        if (!((mask >> i) & 1u) || !o[i].ptr) continue;
+        bool dup = false;
+        for (uint32_t k = 0; k < n_res; ++k) dup |= seen[k] == o[i].ptr;
+        if (!dup) seen[n_res++] = o[i].ptr;
+    }
+    const uint32_t w = img->w(), h = img->h();
+    const uint32_t groups = bc_compare_groups(w, h);
+    KC_TRY(stats_buffers((size_t)groups * KC_BC_REC_WORDS * sizeof(unsigned long long)));
+    const uint64_t in_bytes = (uint64_t)w * h * 4 * n_res;
+    const uint64_t blk_bytes = (uint64_t)((w + 3) / 4) * ((h + 3) / 4) * bc_block_bytes(format);
+    const uint32_t nt_mask = cache_policy_mask(in_bytes + blk_bytes, 0, n_res ? n_res : 1);
+    hipError_t e = launch_bc_compare(format, (flags & KC_BC_SRGB) ? 1 : 0, o, rgba ? 0 : 1, blocks, row_pitch, w, h, nt_mask, groups,
+                                     (unsigned long long *)c.stats.partials, c.stats.result, c.stream);
+    if (e != hipSuccess) return hip_fail(e, "launch_bc_compare");
+    c.launches += 2;
+    c.alg_bytes += in_bytes + blk_bytes;
+    KC_TRY(bcd_fetch(KC_BC_REC_WORDS));
+    const unsigned long long *res = c.stats.host;
+    kc_bc_error r;
+    std::memset(&r, 0, sizeof r);
+    r.format = format;
+    r.flags = flags;
+    r.channel_mask = mask;
+    r.pixels = (uint64_t)w * h;
+    for (int ch = 0; ch < 4; ++ch) {
+        r.sse[ch] = res[ch];
+        r.max_abs[ch] = (uint32_t)res[4 + ch];
+    }
+    r.undecoded_blocks = res[8];
+    for (int k = 0; k < 8; ++k) r.bc7_mode_blocks[k] = res[9 + k];
+    *out = r;
+    return KC_OK;
+}
+
+int image_bc_compare(kc_image *img, const kc_bc_image *blocks, uint32_t flags, kc_bc_error *out)
+{
+    KC_TRY(bc_check_flags(blocks ? blocks->format : 0, flags, "kc_image_bc_compare"));
+    if (!img || !out) return bcd_refuse("kc_image_bc_compare", "NULL image or output");
+    KC_TRY(bc_image_validate(blocks, nullptr));
+    if (img->w() != blocks->width || img->h() != blocks->height) return bcd_refuse("kc_image_bc_compare", "descriptor size differs from the image's");
+    Context &c = ctx();
+    std::lock_guard<std::recursive_mutex> lk(c.mu);
+    KC_TRY(image_force(img));  // a pending fused chain runs first
+    return bc_compare(img, blocks->format, flags, (const char *)blocks->ptr, blocks->row_pitch_bytes, out);
+}
+
+int image_bc_error(kc_image *img, int format, uint32_t flags, kc_bc_error *out)
+{
+    KC_TRY(bc_check_flags(format, flags, "kc_image_bc_error"));
+    const size_t bb = bc_block_bytes(format);
+    if (bb == 0) return bcd_refuse("kc_image_bc_error", "unknown format");
+    if (!img || !out) return bcd_refuse("kc_image_bc_error", "NULL image or output");
+    KC_TRY(need_init());
+    Context &c = ctx();
+    std::lock_guard<std::recursive_mutex> lk(c.mu);
+    const uint64_t bx = ((uint64_t)img->w() + 3) / 4, by = ((uint64_t)img->h() + 3) / 4;
+    if (bx * by > (1ull << 31)) return bcd_refuse("kc_image_bc_error", "image too large: more than 2^31 blocks");
+    KC_TRY(image_force(img));  // a pending fused chain runs first
+    const size_t nbytes = (size_t)(bx * by) * bb, block = (nbytes + 255) / 256 * 256;
+    void *staging = nullptr;
+    KC_TRY(pool_alloc(block, &staging));
+    int s = bc_encode(img, format, (flags & KC_BC_SRGB) != 0, (char *)staging, (size_t)bx * bb, c.stream);
+    if (s == KC_OK) s = bc_compare(img, format, flags, (const char *)staging, (size_t)bx * bb, out);  // waits: the staging is free after it
+    pool_free(staging, block);
+    return s;
+}
+
+// ---------------------------------------------------------------- DDS input
+static uint32_t le32(const uint8_t *p) { return (uint32_t)p[0] | (uint32_t)p[1] << 8 | (uint32_t)p[2] << 16 | (uint32_t)p[3] << 24; }
+
+static constexpr uint32_t fourcc(char a, char b, char c, char d)
+{
+    return (uint32_t)(uint8_t)a | (uint32_t)(uint8_t)b << 8 | (uint32_t)(uint8_t)c << 16 | (uint32_t)(uint8_t)d << 24;
+}
+
+int dds_parse(const uint8_t *data, size_t bytes, kc_dds_info *info)
+{
+    auto unsupported = [](const char *what) {
+        set_error(std::string("kc_dds_parse: ") + what);
+        return KC_ERR_UNSUPPORTED;
+    };
+    if (!data || !info) return bcd_refuse("kc_dds_parse", "NULL buffer or output");
+    if (bytes < 128) return bcd_refuse("kc_dds_parse", "fewer than the 128 bytes of a header");
+    uint32_t d[37] = { 0 };
+    const size_t words = bytes >= 148 ? 37 : 32;
+    for (size_t i = 0; i < words; ++i) d[i] = le32(data + 4 * i);
+    if (d[0] != fourcc('D', 'D', 'S', ' ')) return bcd_refuse("kc_dds_parse", "no DDS magic");
+    if (d[1] != 124 || d[19] != 32) return bcd_refuse("kc_dds_parse", "dwSize is not 124 or the pixel format's is not 32");
+    const uint32_t h = d[3], w = d[4];
+    if (w == 0 || h == 0) return bcd_refuse("kc_dds_parse", "zero extent");
+    const bool dx10 = (d[20] & 0x4u) && d[21] == fourcc('D', 'X', '1', '0');
+    if (dx10 && bytes < 148) return bcd_refuse("kc_dds_parse", "fewer than the 148 bytes of a DX10 header");
+    // well-formed from here on: what is not a BC texture this library decodes is unsupported
+    if (!(d[20] & 0x4u)) return unsupported("not a FourCC format (uncompressed)");
+    if ((d[28] & 0x200u) || (d[28] & 0x200000u) || ((d[2] & 0x800000u) && d[6] > 1)) return unsupported("cube maps and volumes");
+    int format = 0;
+    uint32_t flags = 0;
+    if (dx10) {
+        switch (d[32]) {
+        case 71: format = KC_BC1; break;
+        case 72: format = KC_BC1, flags = KC_BC_SRGB; break;
+        case 77: format = KC_BC3; break;
+        case 78: format = KC_BC3, flags = KC_BC_SRGB; break;
+        case 80: format = KC_BC4; break;
+        case 83: format = KC_BC5; break;
+        case 98: format = KC_BC7; break;
+        case 99: format = KC_BC7, flags = KC_BC_SRGB; break;
+        default: return unsupported("a dxgiFormat other than BC1, BC3, BC4, BC5 and BC7 UNORM");
+        }
+        if (d[33] != 3) return unsupported("a resource dimension other than TEXTURE2D");
+        if (d[34] & 0x4u) return unsupported("cube maps");
+        if (d[35] != 1) return unsupported("texture arrays");
+    } else {
+        const uint32_t cc = d[21];
+        if (cc == fourcc('D', 'X', 'T', '1')) format = KC_BC1;
+        else if (cc == fourcc('D', 'X', 'T', '5')) format = KC_BC3;
+        else if (cc == fourcc('A', 'T', 'I', '1') || cc == fourcc('B', 'C', '4', 'U')) format = KC_BC4;
+        else if (cc == fourcc('A', 'T', 'I', '2') || cc == fourcc('B', 'C', '5', 'U')) format = KC_BC5;
+        else return unsupported("a FourCC other than DXT1, DXT5, ATI1 / BC4U, ATI2 / BC5U and DX10");
+    }
+    const uint32_t levels = ((d[2] & 0x20000u) && d[7]) ? d[7] : 1u;
+    uint32_t L = 0;
+    KC_TRY(mip_level_count(w, h, &L));
+    if (levels > L) return bcd_refuse("kc_dds_parse", "more levels than the chain of this size has");
+    std::vector<size_t> offs(L);
+    size_t total = 0;
+    KC_TRY(bc_mip_layout(w, h, format, nullptr, offs.data(), L, &total));
+    const size_t data_offset = dx10 ? 148 : 128, data_bytes = levels == L ? total : offs[levels];
+    if (bytes - data_offset < data_bytes) return bcd_refuse("kc_dds_parse", "shorter than the header's levels need");
+    info->width = w;
+    info->height = h;
+    info->format = format;
+    info->flags = flags;
+    info->levels = levels;
+    info->data_offset = data_offset;
+    info->data_bytes = data_bytes;
+    return KC_OK;
+}
+
+int image_read_dds(const char *path, uint32_t level, uint32_t flags, kc_image **out, kc_dds_info *info)
+{
+    if (flags & ~(uint32_t)KC_BC_GRAY) {
+        set_error("kc_image_read_dds: flags other than KC_BC_GRAY");
+        return KC_ERR_UNSUPPORTED;
+    }
+    if (!path || !out) return bcd_refuse("kc_image_read_dds", "NULL path or output");
+    std::vector<uint8_t> file;
+    {
+        FILE *f = std::fopen(path, "rb");
+        if (!f) {
+            set_error(std::string("kc_image_read_dds: cannot open ") + path);
+            return KC_ERR_IO;
+        }
+        uint8_t buf[1 << 16];
+        size_t n;
+        while ((n = std::fread(buf, 1, sizeof buf, f)) > 0) file.insert(file.end(), buf, buf + n);
+        const bool bad = std::ferror(f) != 0;
+        std::fclose(f);
+        if (bad) {
+            set_error(std::string("kc_image_read_dds: cannot read ") + path);
+            return KC_ERR_IO;
+        }
+    }
+    kc_dds_info di;
+    KC_TRY(dds_parse(file.data(), file.size(), &di));
+    if (info) *info = di;
+    if (level >= di.levels) return bcd_refuse("kc_image_read_dds", "level is not below the file's level count");
+    uint32_t L = 0;
+    KC_TRY(mip_level_count(di.width, di.height, &L));
+    std::vector<size_t> offs(L);
+    KC_TRY(bc_mip_layout(di.width, di.height, di.format, nullptr, offs.data(), L, nullptr));
+    const uint32_t W = (di.width >> level) ? di.width >> level : 1u, H = (di.height >> level) ? di.height >> level : 1u;
+    const size_t end = level + 1 < di.levels ? offs[level + 1] : di.data_bytes;
+    return image_from_bc(file.data() + di.data_offset + offs[level], end - offs[level], W, H, di.format, flags, out, nullptr);
+}
+
+}  // namespace kc

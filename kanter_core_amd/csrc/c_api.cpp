@@ -854,6 +854,48 @@ try {
 }
 KC_CATCH
 
+int kc_image_from_bc(const uint8_t *host, size_t host_bytes, uint32_t width, uint32_t height, int format, uint32_t flags, kc_image **out,
+                     uint64_t *undecoded_blocks)
+try {
+    Lock api_lock(ctx().mu);  // reference counts are plain integers, see kc_plane::refs
+    return image_from_bc(host, host_bytes, width, height, format, flags, out, undecoded_blocks);  // the flags, the arguments, then need_init()
+}
+KC_CATCH
+
+int kc_image_from_bc_device(const kc_bc_image *src, uint32_t flags, void *hip_stream, kc_image **out, uint64_t *undecoded_blocks)
+try {
+    Lock api_lock(ctx().mu);  // reference counts are plain integers, see kc_plane::refs
+    return image_from_bc_device(src, flags, hip_stream, out, undecoded_blocks);
+}
+KC_CATCH
+
+int kc_image_bc_compare(kc_image *img, const kc_bc_image *blocks, uint32_t flags, kc_bc_error *out)
+try {
+    Lock api_lock(ctx().mu);  // reference counts are plain integers, see kc_plane::refs
+    return image_bc_compare(img, blocks, flags, out);
+}
+KC_CATCH
+
+int kc_image_bc_error(kc_image *img, int format, uint32_t flags, kc_bc_error *out)
+try {
+    Lock api_lock(ctx().mu);  // reference counts are plain integers, see kc_plane::refs
+    return image_bc_error(img, format, flags, out);
+}
+KC_CATCH
+
+int kc_dds_parse(const uint8_t *data, size_t bytes, kc_dds_info *info)
+try {
+    return dds_parse(data, bytes, info);
+}
+KC_CATCH
+
+int kc_image_read_dds(const char *path, uint32_t level, uint32_t flags, kc_image **out, kc_dds_info *info)
+try {
+    Lock api_lock(ctx().mu);  // reference counts are plain integers, see kc_plane::refs
+    return image_read_dds(path, level, flags, out, info);
+}
+KC_CATCH
+
 int kc_image_channel_stats(kc_image *img, uint32_t flags, kc_channel_stats *out)
 try {
     Lock api_lock(ctx().mu);  // reference counts are plain integers, see kc_plane::refs
@@ -1513,6 +1555,18 @@ try {
     const SlotData *sd = lg->find_slot(node, slot);
     if (!sd) return KC_ERR_NO_SLOT_DATA;
     return image_to_bc_mips_device(sd->image, format, flags, device_ptr, bytes, hip_stream);
+}
+KC_CATCH
+
+int kc_live_graph_buffer_bc_error(kc_live_graph *lg, uint32_t node, uint32_t slot, int format, uint32_t flags, kc_bc_error *out)
+try {
+    KC_TRY(bc_check_flags(format, flags, "kc_live_graph_buffer_bc_error"));
+    LG_LOCK(lg);
+    KC_ARG(out && bc_block_bytes(format) != 0);
+    KC_TRY(need_init());
+    const SlotData *sd = lg->find_slot(node, slot);
+    if (!sd) return KC_ERR_NO_SLOT_DATA;
+    return image_bc_error(sd->image, format, flags, out);
 }
 KC_CATCH
 

@@ -309,6 +309,28 @@ hipError_t launch_bc_encode(int fmt, int srgb, const Operand op[4], int gray, ch
 // bc7_encode_kernel<srgb, nt>: the same for KC_BC7 (16-byte blocks, all four channels)
 hipError_t launch_bc7_encode(int srgb, const Operand op[4], int gray, char *dst, uint64_t row_pitch, uint32_t w, uint32_t h, uint32_t nt_mask,
                              hipStream_t s);
+// -- bc_decode.hip --
+// Block decode and the error of an encoding (bc_decode.hip / bc_decode.cpp).  bc_decode_kernel<fmt, nt, count> reads the
+// ceil(w/4) x ceil(h/4) blocks at src, block rows row_pitch bytes apart, and writes the planes the format holds (BC4: dst[0];
+// BC5: dst[0..1]; the others dst[0..3]), dst_pitch floats between their rows, rows 16-byte aligned; nt_mask bit 8: nontemporal.
+struct BcDecodeArgs {
+    const char *src;
+    uint64_t row_pitch;  // bytes between block rows
+    float *dst[4];
+    uint32_t dst_pitch;  // floats
+    uint32_t w, h, bx, by;
+    unsigned long long *partials, *result;  // count: one word per workgroup, and the sum (bc_combine_kernel: a second launch)
+};
+// count (KC_BC7 only): result[0] = the blocks of the partitioned modes, which are not decoded
+hipError_t launch_bc_decode(int fmt, const BcDecodeArgs &a, bool count, uint32_t nt_mask, uint32_t groups, hipStream_t s);
+uint32_t bc_decode_groups(uint32_t w, uint32_t h, bool count);
+// bc_compare_kernel<fmt, srgb, nt> on `groups` workgroups, then bc_combine_kernel: two launches.  The image's channels as
+// launch_bc_encode takes them against the blocks at `blocks`; partials: groups records of KC_BC_REC_WORDS u64 (bc_decode.hip has
+// the layout); result: one record, every word written.
+constexpr uint32_t KC_BC_REC_WORDS = 17;
+hipError_t launch_bc_compare(int fmt, int srgb, const Operand op[4], int gray, const char *blocks, uint64_t row_pitch, uint32_t w, uint32_t h,
+                             uint32_t nt_mask, uint32_t groups, unsigned long long *partials, unsigned long long *result, hipStream_t s);
+uint32_t bc_compare_groups(uint32_t w, uint32_t h);
 // -- mip.hip --
 // Mip chains (mip.hip / mip.cpp): the 2 x 2 box of the header on the n_planes distinct resident planes of one image.
 // mip_pyramid_kernel<nt>: levels 1..n (1 <= n <= 6, both of w >> n and h >> n still >= 1) of the w x h source planes, one

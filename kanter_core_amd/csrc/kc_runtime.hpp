@@ -350,6 +350,17 @@ int image_to_bc_device(kc_image *img, const kc_bc_image *dst, uint32_t flags, vo
 size_t bc_block_bytes(int format);  // 8, 16, or 0 for an unknown format
 // one launch of the encoder for `img` (forced already) into `dst`, block rows `row_pitch` bytes apart, on `s`
 int bc_encode(kc_image *img, int format, bool srgb, char *dst, size_t row_pitch, hipStream_t s);
+// kc_image_to_bc's flag rule: bits other than KC_BC_SRGB, or KC_BC_SRGB with BC4 / BC5, are KC_ERR_UNSUPPORTED
+int bc_check_flags(int format, uint32_t flags, const char *who);
+// block decode, the error of an encoding and .dds input (bc_decode.cpp): the bodies of kc_image_from_bc, kc_image_from_bc_device,
+// kc_image_bc_compare, kc_image_bc_error, kc_dds_parse and kc_image_read_dds
+int image_from_bc(const uint8_t *host, size_t host_bytes, uint32_t w, uint32_t h, int format, uint32_t flags, kc_image **out,
+                  uint64_t *undecoded_blocks);
+int image_from_bc_device(const kc_bc_image *src, uint32_t flags, void *hip_stream, kc_image **out, uint64_t *undecoded_blocks);
+int image_bc_compare(kc_image *img, const kc_bc_image *blocks, uint32_t flags, kc_bc_error *out);
+int image_bc_error(kc_image *img, int format, uint32_t flags, kc_bc_error *out);
+int dds_parse(const uint8_t *data, size_t bytes, kc_dds_info *info);
+int image_read_dds(const char *path, uint32_t level, uint32_t flags, kc_image **out, kc_dds_info *info);
 // mip chains and their export (mip.cpp): the bodies of kc_mip_level_count, kc_image_build_mips, kc_bc_mip_layout,
 // kc_image_to_bc_mips, kc_image_to_bc_mips_device, kc_dds_header, kc_image_write_dds
 int mip_level_count(uint32_t w, uint32_t h, uint32_t *levels);
@@ -362,6 +373,7 @@ int dds_header(uint32_t w, uint32_t h, int format, uint32_t flags, uint32_t leve
 int image_write_dds(kc_image *img, const char *path, int format, uint32_t flags, int with_mips);
 // per-channel statistics (stats.cpp): the body of kc_image_channel_stats; the context's buffers, released at kc_shutdown
 int image_channel_stats(kc_image *img, uint32_t flags, kc_channel_stats *out);
+int stats_buffers(size_t partials_bytes);  // the context's StatsBuffers, with room for that many bytes of partial records
 void channel_stats_release();
 int calculate_size(int policy, const kc_size *sizes, int n, int slot_index, kc_size specific, kc_size *out);
 int mix_process(kc_image *left, kc_image *right, int mix_type, kc_image **out);

@@ -63,8 +63,8 @@ void channel_stats_release()
 
 static constexpr uint32_t kStatsMaxWords = 16 + 4 * 256;  // a record / the result with four histograms
 
-// The context's buffers, with room for `partials_bytes` of partial records
-static int stats_buffers(size_t partials_bytes)
+// The context's buffers, with room for `partials_bytes` of partial records (bc_decode.cpp's reductions use them too)
+int stats_buffers(size_t partials_bytes)
 {
     Context::StatsBuffers &b = ctx().stats;
     if (!b.done) {
