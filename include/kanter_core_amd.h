@@ -392,7 +392,8 @@ typedef struct kc_channel_stats {
 } kc_channel_stats;
 KC_API int kc_image_channel_stats(kc_image *img, uint32_t flags, kc_channel_stats *out);
 /* Block-compressed textures, encoded on the device: BC1 (colour), BC3 (colour and alpha), BC4 (one channel), BC5 (two
- * channels) and BC7 (colour and alpha at 8 bits an endpoint), the formats a GPU samples.  The blocks are a function of the RGBA8 bytes kc_image_to_u8(img, srgb) writes (Gray =
+ * channels), BC7 (colour and alpha at 8 bits an endpoint) and BC6H (HDR colour as half floats, see its paragraph), the formats
+ * a GPU samples.  BC6H apart, the blocks are a function of the RGBA8 bytes kc_image_to_u8(img, srgb) writes (Gray =
  * (v, v, v, 1); KC_BC_SRGB: R, G, B as with srgb = 1, alpha always linear); everything after that quantisation is integer
  * arithmetic, so the output is bit-exact.  The grid is bx = ceil(w / 4) by by = ceil(h / 4) blocks; texel t = 4y + x (x, y in
  * 0..3) of block (i, j) is pixel (min(4i + x, w - 1), min(4j + y, h - 1)): edge blocks repeat the last column or row.
@@ -429,6 +430,18 @@ KC_API int kc_image_channel_stats(kc_image *img, uint32_t flags, kc_channel_stat
  *           index in 3 bits (65-67), texels 1-15 in 4 bits each (68-127).  Mode 5: bits 0-5 the value 32; rotation (6-7) 0; R0,
  *           R1, G0, G1, B0, B1 of 7 bits each (8-49); A0, A1 of 8 bits each (50-65); colour indices, texel 0 in 1 bit (66),
  *           texels 1-15 in 2 bits each (67-96); alpha indices likewise (97, 98-127).
+ *   BC6H (KC_BC6H, unsigned, DXGI_FORMAT_BC6H_UF16), 16 bytes: the HDR format, sampled as half floats.  It does NOT start from
+ *           kc_image_to_u8's bytes: a plane value v is quantised to h(v) = f16(min(max(v, 0), 65504)) as a 16-bit pattern,
+ *           rounded to nearest even, denormal halves kept; NaN, the negatives, -0 and -inf give 0, +inf and everything >= 65504
+ *           give 0x7BFF.  Texels are p_t = (h(R), h(G), h(B)), integers 0..31743 (Gray: (v, v, v)); alpha is never read; nothing
+ *           is clamped to 1.  After that everything is integer arithmetic on the patterns (tests/bc6h_ref.py is the same rules
+ *           in numpy).  unq10(q) = 0 for q = 0, 0xFFFF for q = 1023, else 64 q + 32; fin(x) = (31 x) >> 6; E(q) = fin(unq10(q)).
+ *           Only mode 11 is written (one subset, 10-bit endpoints).  (e0, e1) = axis(p over R, G, B) as for BC7, the sums s_c in
+ *           64 bits.  Each endpoint channel is the smallest q in 0..1023 minimising |E(q) - e|.  Palette i =
+ *           fin(interp(unq10(q0), unq10(q1), W4[i])) per channel; texel t takes the i minimising sum_c (p_t,c - P_i,c)^2, the
+ *           lowest i on a tie.  If texel 0's index is >= 8 the endpoints swap and every index becomes 15 - index.  Bits 0-4
+ *           the value 3; R0, G0, B0 of 10 bits each (5-34); R1, G1, B1 (35-64); texel 0's index in 3 bits (65-67), texels 1-15
+ *           in 4 bits each (68-127).  KC_BC_SRGB with KC_BC6H is KC_ERR_UNSUPPORTED.
  *   kc_bc_image           a caller's buffer of blocks: block (i, j) at ptr + j * row_pitch_bytes + i * block bytes.
  *   kc_bc_image_validate  launches nothing; like kc_device_image_validate.  Arithmetic first (no kc_init needed): a known
  *                         format, width and height > 0, bx * by <= 2^31, ptr and row_pitch_bytes multiples of the block
@@ -440,19 +453,19 @@ KC_API int kc_image_channel_stats(kc_image *img, uint32_t flags, kc_channel_stat
  *                         Blocks until they are there, as kc_image_to_u8.
  *   kc_image_to_bc_device blocks into `dst`, ordered against `hip_stream` by the two event edges of kc_image_to_device (the
  *                         host does not wait).  kc_live_graph_buffer_bc: the same for a slot's image.
- * Errors: flag bits other than KC_BC_SRGB, or KC_BC_SRGB with BC4 / BC5, KC_ERR_UNSUPPORTED; a NULL argument, an unknown
+ * Errors: flag bits other than KC_BC_SRGB, or KC_BC_SRGB with BC4 / BC5 / BC6H, KC_ERR_UNSUPPORTED; a NULL argument, an unknown
  * format, a descriptor size that differs from the image's or `host_bytes` below the blocks' bytes KC_ERR_INVALID_ARG; then
  * KC_ERR_NO_DEVICE before kc_init; kc_live_graph_buffer_bc returns KC_ERR_NO_SLOT_DATA where kc_live_graph_buffer_device does.
  * A refused call launches nothing.  A pending chain or resample runs first; then one launch (kc_stats), constant channels
  * included, with width * height * 4 algorithmic bytes per distinct resident plane the format reads plus the blocks' bytes.
  * Bytes outside the blocks are never written.
  * KC_BC7 is 98, DXGI_FORMAT_BC7_UNORM's own number, not 7: the value 7 has always been refused as an unknown format and stays
- * refused. */
-typedef enum kc_bc_format { KC_BC1 = 1, KC_BC3 = 3, KC_BC4 = 4, KC_BC5 = 5, KC_BC7 = 98 } kc_bc_format;
+ * refused.  KC_BC6H is 95, DXGI_FORMAT_BC6H_UF16's number, likewise; 6 and the signed form's 96 are refused. */
+typedef enum kc_bc_format { KC_BC1 = 1, KC_BC3 = 3, KC_BC4 = 4, KC_BC5 = 5, KC_BC6H = 95, KC_BC7 = 98 } kc_bc_format;
 typedef struct kc_bc_image {
     void *ptr;               /* device memory of the library's device */
     uint32_t width, height;  /* the image's pixels */
-    int32_t format;          /* kc_bc_format; block bytes 8 (BC1, BC4) or 16 (BC3, BC5, BC7) */
+    int32_t format;          /* kc_bc_format; block bytes 8 (BC1, BC4) or 16 (BC3, BC5, BC6H, BC7) */
     size_t row_pitch_bytes;  /* distance between block rows */
 } kc_bc_image;
 #define KC_BC_SRGB 1u        /* BC1 / BC3 / BC7: R, G, B as kc_image_to_u8 with srgb = 1 writes them; alpha linear */
@@ -492,6 +505,7 @@ KC_API int kc_image_to_bc_device(kc_image *img, const kc_bc_image *dst, uint32_t
  *                        NULL; otherwise cap < L is KC_ERR_INVALID_ARG), `*total_bytes` = the chain's bytes.  Arithmetic, no kc_init.
  *   kc_image_to_bc_mips  kc_image_build_mips, then the encoder of kc_image_to_bc once per level, into host memory (`host_bytes`
  *                        at least the total); blocks until the bytes are there.  flags: KC_BC_SRGB (BC1 / BC3 / BC7) | KC_MIP_PER_LEVEL.
+ *                        KC_BC6H quantises every level's own f32 values, so the chain keeps the range of the planes.
  *   kc_image_to_bc_mips_device  the same into device memory (a multiple of the block bytes; `bytes` at least the total, the
  *                        total's extent in one allocation of the library's device), ordered against `hip_stream` by the two event
  *                        edges of kc_image_to_bc_device.  Bytes past the total are never written.
@@ -500,10 +514,10 @@ KC_API int kc_image_to_bc_device(kc_image *img, const kc_bc_image *dst, uint32_t
  *                        0x81007 plus 0x20000 with levels > 1, height, width, level 0's block bytes as the linear size, depth 0,
  *                        `levels` as the mip count, pixel format {32, DDPF_FOURCC, "DX10"}, caps 0x1000 plus 0x400008 with
  *                        levels > 1), DDS_HEADER_DXT10 {dxgiFormat, TEXTURE2D, 0, 1, 0}; dxgiFormat BC1 71, BC3 77, BC4 80,
- *                        BC5 83, BC7 98, with KC_BC_SRGB BC1 72, BC3 78, BC7 99.  1 <= levels <= L.  `*bytes` (optional) = 148.
+ *                        BC5 83, BC6H 95, BC7 98, with KC_BC_SRGB BC1 72, BC3 78, BC7 99.  1 <= levels <= L.  `*bytes` (optional) = 148.
  *                        No kc_init.
  *   kc_image_write_dds   the header, then the chain (with_mips != 0) or level 0 alone.
- * Errors, in this order: unknown flag bits, or KC_BC_SRGB with BC4 / BC5, KC_ERR_UNSUPPORTED; a NULL argument, a zero size, an
+ * Errors, in this order: unknown flag bits, or KC_BC_SRGB with BC4 / BC5 / BC6H, KC_ERR_UNSUPPORTED; a NULL argument, a zero size, an
  * unknown format, a size below the total KC_ERR_INVALID_ARG; KC_ERR_NO_DEVICE before kc_init; KC_ERR_NO_SLOT_DATA where
  * kc_live_graph_buffer_bc returns it; KC_ERR_IO for a file that cannot be written. */
 #define KC_MIP_PER_LEVEL 2u  /* one launch of the one-level kernel per level instead of the fused pyramid kernel; a bit of its
@@ -537,7 +551,19 @@ KC_API int kc_image_write_dds(kc_image *img, const char *path, int format, uint3
  *           W3; 1: colour the 3-bit set with W3, alpha the 2-bit set with W2.  Rotation r in 1..3 (modes 4 and 5) swaps alpha
  *           with channel r - 1 after the interpolation.  Byte 0 == 0 is the reserved mode: (0, 0, 0, 0), as the format defines.
  *           Blocks of the partitioned modes 0, 1, 2, 3 and 7 are NOT decoded: they give (0, 0, 0, 0) and are counted in
- *           `*undecoded_blocks`.  The other formats always count 0.
+ *           `*undecoded_blocks`.  BC1, BC3, BC4 and BC5 always count 0.
+ *   BC6H    the four single-subset modes 11, 12, 13 and 14, in full: everything kc_image_to_bc writes and everything else that
+ *           needs no partition table.  The mode field: bit 1 of byte 0 clear, 2 bits, 0 is mode 1 and 1 is mode 2; otherwise 5
+ *           bits: 2, 6, 10, 14, 18, 22, 26, 30 are modes 3-10, 3, 7, 11, 15 are modes 11-14, and 19, 23, 27, 31 are reserved.
+ *           Mode 11 has the layout given above.  Modes 12, 13, 14 store endpoint 0 in n = 11, 12, 16 bits and endpoint 1 as a
+ *           signed delta of 9, 8, 4 bits: bits 5-34 are the low 10 bits of R0, G0, B0; then for R, G, B in turn a group of 10
+ *           bits, LSB first: mode 12 delta[0..8], e0[10]; mode 13 delta[0..7], e0[11], e0[10]; mode 14 delta[0..3], e0[15],
+ *           e0[14], e0[13], e0[12], e0[11], e0[10].  e1 = (e0 + sign_extend(delta)) mod 2^n.  unq_n(x) = x for n = 16, otherwise 0
+ *           for x = 0, 0xFFFF for x = 2^n - 1 and ((x << 16) + 0x8000) >> n else.  The indices lie as in mode 11.  A texel channel
+ *           is fin(interp(unq_n(e0), unq_n(e1), W4[index])), a half bit pattern <= 0x7BFF: never infinite, never NaN.  The image
+ *           is RGBA: R, G and B resident planes that hold the halves' exact f32 values (not bytes / 255: up to 65504), A a
+ *           constant plane of 1.  A block with a reserved mode field gives (0, 0, 0), as the format defines, and is not counted.
+ *           Blocks of the two-subset modes 1-10 are NOT decoded: they give (0, 0, 0) and are counted in `*undecoded_blocks`.
  *   kc_image_from_bc         `host`: tightly packed block rows, exactly what kc_image_to_bc writes (`host_bytes` at least
  *                            bx * by * block bytes).  `*out` (+1 reference) owns new planes; a decoded byte b is the f32
  *                            b / 255.f with the IEEE divide, as kc_image_from_u8 makes it, so kc_image_to_u8(*out, 0) returns
@@ -547,19 +573,22 @@ KC_API int kc_image_write_dds(kc_image *img, const char *path, int format, uint3
  *                            stores).  KC_BC_GRAY (BC4 only): a Gray image of the channel.  The call waits for its upload.
  *   kc_image_from_bc_device  the same from a kc_bc_image (kc_bc_image_validate's rules), ordered against `hip_stream` by the two
  *                            event edges of kc_image_to_bc_device; nothing aliases the caller's blocks.  With a non-NULL
- *                            `undecoded_blocks` and KC_BC7 the call blocks until the count is on the host, as
+ *                            `undecoded_blocks` and KC_BC7 or KC_BC6H the call blocks until the count is on the host, as
  *                            kc_image_channel_stats does; with NULL, or another format (count 0), it does not wait.
  *                            Errors, in this order: flag bits other than KC_BC_GRAY (KC_BC_SRGB included), or KC_BC_GRAY with a
  *                            format other than KC_BC4, KC_ERR_UNSUPPORTED; a NULL argument (`undecoded_blocks` may be NULL), an
  *                            unknown format, a zero size, more than 2^31 blocks, `host_bytes` below the blocks' bytes or a
  *                            descriptor kc_bc_image_validate refuses KC_ERR_INVALID_ARG; KC_ERR_NO_DEVICE before kc_init.
- *                            kc_stats: one launch (KC_BC7 with a count: two, the second sums the workgroups' counts), the
+ *                            kc_stats: one launch (KC_BC7 / KC_BC6H with a count: two, the second sums the workgroups' counts), the
  *                            blocks' bytes plus 4 w h algorithmic bytes per resident plane written; a refused call launches nothing.
  *   kc_bc_error              the error of blocks against an image.  The source bytes are what kc_image_to_u8(img, srgb) writes
  *                            with srgb = flags & KC_BC_SRGB (Gray = (v, v, v, 1); the encoders' quantiser functions); the
  *                            decoded bytes are those above.  Only the image's pixels count, not the replicated texels of edge
  *                            blocks; undecoded blocks contribute their (0, 0, 0, 0).  The mask holds the channels the format
- *                            encodes (BC1: not alpha, which its encoder ignores).
+ *                            encodes (BC1: not alpha, which its encoder ignores).  KC_BC6H: the differences are taken
+ *                            between half bit patterns, decoded minus h(source), as integers -- exact and independent of the
+ *                            order like the byte formats; a log-like measure, since a half's pattern grows like the logarithm
+ *                            of its value.  The mask is 0x7 and bc7_mode_blocks is zero.
  *   kc_image_bc_compare      any blocks of the image's size, the library's own or another encoder's.
  *   kc_image_bc_error        encodes into pool staging with kc_image_to_bc's encoder, then compares.
  *                            kc_live_graph_buffer_bc_error: the same for a slot's image.
@@ -580,7 +609,9 @@ KC_API int kc_image_write_dds(kc_image *img, const char *path, int format, uint3
  *                            at most kc_mip_level_count.  `data_bytes` = what kc_bc_mip_layout gives for those levels.  Errors, in
  *                            this order: a NULL argument, fewer than 128 bytes (148: DX10), a bad magic, dwSize != 124, a pixel
  *                            format size != 32 or a zero extent KC_ERR_INVALID_ARG; a well-formed header of anything else
- *                            (uncompressed, BC2, BC6H, signed, typeless, arrays, cube maps, volumes) KC_ERR_UNSUPPORTED; `levels`
+ *                            (uncompressed, BC2, BC6H, signed, typeless, arrays, cube maps, volumes) KC_ERR_UNSUPPORTED (so the
+ *                            dxgiFormat 95 file kc_image_write_dds writes for KC_BC6H is not read back: pass its blocks, from
+ *                            byte 148 on, to kc_image_from_bc); `levels`
  *                            above the level count, or a buffer shorter than data_offset + data_bytes, KC_ERR_INVALID_ARG.
  *   kc_image_read_dds        kc_image_from_bc of level `level` of the file (kc_bc_mip_layout's offsets).  flags: KC_BC_GRAY only.
  *                            `info` (optional) is written once the header has parsed.  Errors, in this order: flag bits other
@@ -591,11 +622,11 @@ KC_API int kc_image_write_dds(kc_image *img, const char *path, int format, uint3
 typedef struct kc_bc_error {
     int32_t format;              /* kc_bc_format of the blocks */
     uint32_t flags;              /* the flags the call was given */
-    uint32_t channel_mask;       /* bit c: channel c is compared: BC1 0x7, BC3 / BC7 0xF, BC4 0x1, BC5 0x3 */
+    uint32_t channel_mask;       /* bit c: channel c is compared: BC1 / BC6H 0x7, BC3 / BC7 0xF, BC4 0x1, BC5 0x3 */
     uint64_t pixels;             /* width * height: the image's pixels, not the blocks' texels */
-    uint64_t sse[4];             /* sum over the pixels of (decoded byte - source byte)^2; 0 outside the mask */
-    uint32_t max_abs[4];         /* largest |decoded byte - source byte|; 0 outside the mask */
-    uint64_t undecoded_blocks;   /* as kc_image_from_bc_device counts them */
+    uint64_t sse[4];             /* sum over the pixels of (decoded byte - source byte)^2; 0 outside the mask; BC6H: half bit patterns */
+    uint32_t max_abs[4];         /* largest |decoded byte - source byte|; 0 outside the mask; BC6H: of half bit patterns, <= 31743 */
+    uint64_t undecoded_blocks;   /* as kc_image_from_bc_device counts them (BC7's partitioned modes, BC6H's two-subset modes) */
     uint64_t bc7_mode_blocks[8]; /* BC7: blocks per mode 0..7 (reserved blocks in none); zero for the other formats */
 } kc_bc_error;
 typedef struct kc_dds_info {

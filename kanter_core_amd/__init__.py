@@ -13,7 +13,7 @@ from .api import (Edge, EmbeddedSlotDataId, LiveGraph, MixType, Node, NodeGraph,
                   get_resize_mode, resize_upsample_plan, resize_down2_plan, stats_counter, specialize_compile_check_upsample, specialize_compile_check_mask, set_chain_quads, get_chain_quads, set_cache_policy, get_cache_policy, set_option, get_option, comm_unique_id, comm_init,
                   comm_destroy, comm_info, comm_stats, comm_transport, comm_gather_bands, PlanKind, pool_trim, kernel_cache_set_dir, kernel_cache_stats,
                   kernel_cache_precompile, specialize_reset, U8Pipe, device_image_desc, DEVICE_SRGB, DEVICE_GRAY,
-                  ChannelStats, STATS_HISTOGRAM, STATS_SRGB, BC_SRGB, BC7, BC_BLOCK_BYTES,
+                  ChannelStats, STATS_HISTOGRAM, STATS_SRGB, BC_SRGB, BC6H, BC7, BC_BLOCK_BYTES,
                   MIP_PER_LEVEL, mip_level_count, bc_mip_layout, dds_header, BC_GRAY, BcError, DdsInfo, dds_parse)
 
 __all__ = [n for n in dir() if not n.startswith("_")]

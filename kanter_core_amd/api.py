@@ -644,17 +644,20 @@ def _device_export(call, size, dtype, layout, channels, srgb, out):
 
 BC_SRGB = 1  # kc_image_to_bc: BC1 / BC3 / BC7 colour as to_u8_srgb writes it (alpha linear)
 BC7 = 98     # KC_BC7: DXGI_FORMAT_BC7_UNORM's number (7 is not a format and stays refused)
-BC_BLOCK_BYTES = {1: 8, 3: 16, 4: 8, 5: 16, BC7: 16}  # kc_bc_format -> bytes per 4 x 4 block
+BC6H = 95    # KC_BC6H: DXGI_FORMAT_BC6H_UF16's number; HDR blocks of the planes' values as half floats, never sRGB
+BC_BLOCK_BYTES = {1: 8, 3: 16, 4: 8, 5: 16, BC6H: 16, BC7: 16}  # kc_bc_format -> bytes per 4 x 4 block
+BC6H_PEAK = 31743  # 0x7BFF, the bit pattern of 65504: the largest texel of a BC6H image, as an integer
 
 
 def _bc_format(fmt):
-    """1, 3, 4, 5, BC7 (98) or "bc1" / "BC3" / ... / "bc7" -> kc_bc_format"""
+    """1, 3, 4, 5, BC6H (95), BC7 (98) or "bc1" / "BC3" / ... / "bc6h" / "bc7" -> kc_bc_format"""
     if isinstance(fmt, str):
-        f = BC7 if fmt.lower() == "bc7" else int(fmt.lower().lstrip("bc"))
+        name = fmt.lower()
+        f = BC7 if name == "bc7" else BC6H if name == "bc6h" else int(name.lstrip("bc"))
     else:
         f = int(fmt)
     if f not in BC_BLOCK_BYTES:
-        raise ValueError("BC format must be 1, 3, 4, 5 or BC7 (98), not %r" % (fmt,))
+        raise ValueError("BC format must be 1, 3, 4, 5, BC6H (95) or BC7 (98), not %r" % (fmt,))
     return f
 
 
@@ -760,17 +763,21 @@ class BcError(collections.namedtuple("BcError", "format flags channel_mask pixel
     """The error of BC blocks against an image (kc_bc_error): over the image's pixels, of the decoded bytes against the bytes
     to_u8(srgb) writes.  channel_mask: bit c = channel c is compared (BC1 0x7, BC3 / BC7 0xF, BC4 0x1, BC5 0x3); sse uint64 (4,)
     the sums of squared differences and max_abs uint32 (4,) the largest differences, 0 outside the mask; undecoded_blocks the
-    BC7 blocks of partitioned modes (they count as (0, 0, 0, 0)); bc7_mode_blocks uint64 (8,) the BC7 blocks per mode."""
+    BC7 blocks of partitioned modes (they count as (0, 0, 0, 0)); bc7_mode_blocks uint64 (8,) the BC7 blocks per mode.
+    BC6H: the differences are taken between half bit patterns (integers 0..31743), decoded against the quantised source, over
+    R, G and B (mask 0x7); undecoded_blocks counts the two-subset modes 1-10; bc7_mode_blocks is zero."""
     __slots__ = ()
 
     def psnr(self, channels=None):
-        """10 log10(255^2 pixels n / sum sse) in dB over the n masked channels (of `channels`, indices 0..3, when given); inf
-        for zero error"""
+        """10 log10(peak^2 pixels n / sum sse) in dB over the n masked channels (of `channels`, indices 0..3, when given); inf
+        for zero error.  peak is 255, and for BC6H 31743 (BC6H_PEAK), the largest half bit pattern: half bit patterns grow
+        like the logarithm of the value, so BC6H's figure is a log-like measure, not a PSNR of radiance."""
         chans = [c for c in range(4) if (self.channel_mask >> c) & 1 and (channels is None or c in channels)]
         if not chans:
             raise ValueError("none of the channels %r is in the mask 0x%x" % (channels, self.channel_mask))
         sse = sum(int(self.sse[c]) for c in chans)
-        return float("inf") if sse == 0 else float(10 * np.log10(255.0 ** 2 * self.pixels * len(chans) / sse))
+        peak = float(BC6H_PEAK) if self.format == BC6H else 255.0
+        return float("inf") if sse == 0 else float(10 * np.log10(peak ** 2 * self.pixels * len(chans) / sse))
 
 
 def _bc_error(call, srgb):
@@ -871,7 +878,9 @@ class SlotImage:
         """The image BC blocks decode to (kc_image_from_bc): uint8 (ceil(h/4), ceil(w/4), block bytes) as to_bc returns them,
         decoded on the device by the header's integer rules; to_u8() of the result is exactly the decoded bytes.  RGBA (BC4:
         (r, 0, 0, 1), BC5: (r, g, 0, 1), the missing channels constant planes); gray=True, BC4 only: a Gray image.  BC7: modes
-        4, 5 and 6; blocks of the partitioned modes give (0, 0, 0, 0) and return_undecoded=True returns (image, their count)."""
+        4, 5 and 6; blocks of the partitioned modes give (0, 0, 0, 0) and return_undecoded=True returns (image, their count).
+        BC6H: the single-subset modes 11-14; R, G and B hold the decoded halves' exact values (up to 65504, not bytes / 255), A
+        is a constant 1; blocks of the two-subset modes 1-10 give (0, 0, 0) and are counted likewise."""
         f = _bc_format(fmt)
         blocks = np.ascontiguousarray(blocks, np.uint8)
         out, n = C.c_void_p(), C.c_uint64()
@@ -884,7 +893,7 @@ class SlotImage:
     def from_bc_torch(t, width, height, fmt, gray=False, return_undecoded=False):
         """from_bc of a uint8 (ceil(h/4), ceil(w/4), block bytes) tensor in device memory (kc_image_from_bc_device); any view
         whose last two dimensions are contiguous.  Ordered on torch's current stream: the image owns its pixels, the tensor may be
-        freed or overwritten by torch as soon as this returns.  return_undecoded=True waits for the count (BC7)."""
+        freed or overwritten by torch as soon as this returns.  return_undecoded=True waits for the count (BC7, BC6H)."""
         d = _bc_desc(t, width, height, fmt)
         out, n = C.c_void_p(), C.c_uint64()
         _check(_on_torch_stream(t, lambda stream: _lib.load().kc_image_from_bc_device(C.byref(d), BC_GRAY if gray else 0, stream, C.byref(out),
@@ -895,7 +904,8 @@ class SlotImage:
     @staticmethod
     def read_dds(path, level=0, gray=False, return_info=False):
         """Level `level` of a .dds file of BC1, BC3, BC4, BC5 or BC7 blocks, decoded as from_bc (kc_image_read_dds);
-        return_info=True returns (image, DdsInfo)."""
+        return_info=True returns (image, DdsInfo).  A BC6H file (dxgiFormat 95), which write_dds can write, is refused as
+        Unsupported here: pass its blocks to from_bc."""
         out, d = C.c_void_p(), _lib.kc_dds_info()
         _check(_lib.load().kc_image_read_dds(os.fspath(path).encode(), level, BC_GRAY if gray else 0, C.byref(out), C.byref(d)))
         img = SlotImage(out.value)
@@ -942,7 +952,9 @@ class SlotImage:
 
     def to_bc(self, fmt, srgb=False):
         """-> uint8 (ceil(h/4), ceil(w/4), block bytes): the image's BC1, BC3, BC4, BC5 or BC7 (fmt = BC7) blocks (kc_image_to_bc),
-        encoded on the device from the RGBA8 bytes to_u8(srgb) writes; srgb is for BC1, BC3 and BC7 only."""
+        encoded on the device from the RGBA8 bytes to_u8(srgb) writes; srgb is for BC1, BC3 and BC7 only.  fmt = BC6H: mode-11
+        blocks of the planes' own values, unclamped above 1: R, G, B (Gray: (v, v, v)) as half floats, f16(min(max(v, 0), 65504))
+        rounded to nearest even, NaN as 0; alpha is not read."""
         f = _bc_format(fmt)
         s = self.size()
         out = np.empty(((s.height + 3) // 4, (s.width + 3) // 4, BC_BLOCK_BYTES[f]), np.uint8)
@@ -989,7 +1001,7 @@ class SlotImage:
 
     def bc_error(self, fmt, srgb=False, blocks=None):
         """-> BcError: how far the image's BC encoding is from the image, measured on the device (kc_image_bc_error): the bytes
-        the blocks decode to against the bytes to_u8(srgb) writes, over the image's pixels.  blocks: a uint8 (ceil(h/4), ceil(w/4),
+        the blocks decode to against the bytes to_u8(srgb) writes, over the image's pixels (BC6H: half bit patterns).  blocks: a uint8 (ceil(h/4), ceil(w/4),
         block bytes) tensor in device memory to compare instead of the library's own encoding (kc_image_bc_compare), e.g.
         another encoder's.  Blocks until the values are there."""
         f = _bc_format(fmt)

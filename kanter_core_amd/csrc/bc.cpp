@@ -1,6 +1,6 @@
 // Block compression: kc_bc_image_validate, kc_image_to_bc, kc_image_to_bc_device (include/kanter_core_amd.h).  The host side
 // checks the arguments and the caller's descriptor -- arithmetic first, then that its bytes lie in one allocation of the
-// library's device -- and launches bc.hip's encoder (KC_BC7: bc7.hip's) once per call: on the library's stream, ordered
+// library's device -- and launches bc.hip's encoder (KC_BC7: bc7.hip's, KC_BC6H: bc6h.hip's) once per call: on the library's stream, ordered
 // against the caller's stream by the two event edges of kc_image_to_device, or into pool staging that is copied to the
 // caller's host memory.
 #include "kc_runtime.hpp"
@@ -9,7 +9,7 @@ namespace kc {
 
 size_t bc_block_bytes(int format)
 {
-    return format == KC_BC1 || format == KC_BC4 ? 8 : format == KC_BC3 || format == KC_BC5 || format == KC_BC7 ? 16 : 0;
+    return format == KC_BC1 || format == KC_BC4 ? 8 : format == KC_BC3 || format == KC_BC5 || format == KC_BC7 || format == KC_BC6H ? 16 : 0;
 }
 
 static int bc_refuse(const char *what)
@@ -25,7 +25,7 @@ int bc_check_flags(int format, uint32_t flags, const char *who)
         set_error(std::string(who) + ": flags other than KC_BC_SRGB");
         return KC_ERR_UNSUPPORTED;
     }
-    if ((flags & KC_BC_SRGB) && (format == KC_BC4 || format == KC_BC5)) {
+    if ((flags & KC_BC_SRGB) && (format == KC_BC4 || format == KC_BC5 || format == KC_BC6H)) {
         set_error(std::string(who) + ": KC_BC_SRGB is for BC1, BC3 and BC7 only");
         return KC_ERR_UNSUPPORTED;
     }
@@ -62,14 +62,14 @@ int bc_image_validate(const kc_bc_image *d, size_t *extent_bytes)
 }
 
 // One launch of the encoder for `img` (forced already) into `dst`, block rows `row_pitch` bytes apart.  The channels the format
-// reads come from the image as to_u8 sees it (Gray: (v, v, v, 1)); constants cost no loads.
+// reads come from the image as to_u8 sees it (Gray: (v, v, v, 1)); constants cost no loads.  KC_BC6H reads R, G and B.
 int bc_encode(kc_image *img, int format, bool srgb, char *dst, size_t row_pitch, hipStream_t s)
 {
     Context &c = ctx();
     const bool rgba = img->is_rgba();
     Operand o[4];
     for (int i = 0; i < 4; ++i) o[i] = rgba ? plane_operand(img->planes[i]) : i < 3 ? plane_operand(img->planes[0]) : Operand{ nullptr, 0, 1.0f };
-    const int n_ch = format == KC_BC1 ? 3 : format == KC_BC3 || format == KC_BC7 ? 4 : format == KC_BC4 ? 1 : 2;
+    const int n_ch = format == KC_BC1 || format == KC_BC6H ? 3 : format == KC_BC3 || format == KC_BC7 ? 4 : format == KC_BC4 ? 1 : 2;
     const float *seen[4] = { nullptr, nullptr, nullptr, nullptr };
     uint32_t n_res = 0;  // distinct resident planes the launch reads
     for (int i = 0; i < n_ch; ++i) {
@@ -82,8 +82,9 @@ int bc_encode(kc_image *img, int format, bool srgb, char *dst, size_t row_pitch,
     const uint64_t in_bytes = (uint64_t)w * h * 4 * n_res;
     const uint64_t out_bytes = (uint64_t)((w + 3) / 4) * ((h + 3) / 4) * bc_block_bytes(format);
     const uint32_t nt_mask = cache_policy_mask(in_bytes, out_bytes, n_res ? n_res : 1);
-    hipError_t e = format == KC_BC7 ? launch_bc7_encode(srgb ? 1 : 0, o, rgba ? 0 : 1, dst, row_pitch, w, h, nt_mask, s)
-                                    : launch_bc_encode(format, srgb ? 1 : 0, o, rgba ? 0 : 1, dst, row_pitch, w, h, nt_mask, s);
+    hipError_t e = format == KC_BC6H  ? launch_bc6h_encode(o, rgba ? 0 : 1, dst, row_pitch, w, h, nt_mask, s)
+                   : format == KC_BC7 ? launch_bc7_encode(srgb ? 1 : 0, o, rgba ? 0 : 1, dst, row_pitch, w, h, nt_mask, s)
+                                      : launch_bc_encode(format, srgb ? 1 : 0, o, rgba ? 0 : 1, dst, row_pitch, w, h, nt_mask, s);
     if (e != hipSuccess) return hip_fail(e, "launch_bc_encode");
     c.launches++;
     c.alg_bytes += in_bytes + out_bytes;

@@ -47,7 +47,7 @@ static int bc_decode(const char *src, size_t row_pitch, uint32_t w, uint32_t h, 
                      bool *counted)
 {
     Context &c = ctx();
-    const int n_res = format == KC_BC4 ? 1 : format == KC_BC5 ? 2 : 4;
+    const int n_res = format == KC_BC4 ? 1 : format == KC_BC5 ? 2 : format == KC_BC6H ? 3 : 4;  // BC6H: alpha is the constant 1
     const int n = gray ? 1 : 4;
     kc_plane *p[4] = { nullptr, nullptr, nullptr, nullptr };
     int s = KC_OK;
@@ -55,7 +55,7 @@ static int bc_decode(const char *src, size_t row_pitch, uint32_t w, uint32_t h, 
         if (i < n_res) s = plane_new_mem(w, h, &p[i]);
         else p[i] = plane_new_const(w, h, i == 3 ? 1.0f : 0.0f);  // the sampling convention: missing G, B = 0, A = 1
     }
-    const bool count = want_count && format == KC_BC7;
+    const bool count = want_count && (format == KC_BC7 || format == KC_BC6H);
     BcDecodeArgs a{};
     uint32_t groups = 0;
     if (s == KC_OK) {
@@ -76,7 +76,9 @@ static int bc_decode(const char *src, size_t row_pitch, uint32_t w, uint32_t h, 
     }
     if (s == KC_OK) {
         const uint64_t in_bytes = (uint64_t)a.bx * a.by * bc_block_bytes(format), out_bytes = (uint64_t)w * h * 4 * n_res;
-        hipError_t e = launch_bc_decode(format, a, count, cache_policy_mask(in_bytes, out_bytes, 1), groups, c.stream);
+        const uint32_t nt_mask = cache_policy_mask(in_bytes, out_bytes, 1);
+        hipError_t e = format == KC_BC6H ? launch_bc6h_decode(a, count, nt_mask, groups, c.stream)
+                                         : launch_bc_decode(format, a, count, nt_mask, groups, c.stream);
         if (e != hipSuccess) s = hip_fail(e, "launch_bc_decode");
         else {
             c.launches += count ? 2 : 1;
@@ -160,7 +162,7 @@ static int bc_compare(kc_image *img, int format, uint32_t flags, const char *blo
     const bool rgba = img->is_rgba();
     Operand o[4];
     for (int i = 0; i < 4; ++i) o[i] = rgba ? plane_operand(img->planes[i]) : i < 3 ? plane_operand(img->planes[0]) : Operand{ nullptr, 0, 1.0f };
-    const uint32_t mask = format == KC_BC1 ? 0x7u : format == KC_BC4 ? 0x1u : format == KC_BC5 ? 0x3u : 0xfu;
+    const uint32_t mask = format == KC_BC1 || format == KC_BC6H ? 0x7u : format == KC_BC4 ? 0x1u : format == KC_BC5 ? 0x3u : 0xfu;
     const float *seen[4] = { nullptr, nullptr, nullptr, nullptr };
     uint32_t n_res = 0;  // distinct resident planes the launch reads
     for (int i = 0; i < 4; ++i) {
@@ -175,8 +177,10 @@ static int bc_compare(kc_image *img, int format, uint32_t flags, const char *blo
     const uint64_t in_bytes = (uint64_t)w * h * 4 * n_res;
     const uint64_t blk_bytes = (uint64_t)((w + 3) / 4) * ((h + 3) / 4) * bc_block_bytes(format);
     const uint32_t nt_mask = cache_policy_mask(in_bytes + blk_bytes, 0, n_res ? n_res : 1);
-    hipError_t e = launch_bc_compare(format, (flags & KC_BC_SRGB) ? 1 : 0, o, rgba ? 0 : 1, blocks, row_pitch, w, h, nt_mask, groups,
-                                     (unsigned long long *)c.stats.partials, c.stats.result, c.stream);
+    unsigned long long *partials = (unsigned long long *)c.stats.partials;
+    hipError_t e = format == KC_BC6H ? launch_bc6h_compare(o, rgba ? 0 : 1, blocks, row_pitch, w, h, nt_mask, groups, partials, c.stats.result, c.stream)
+                                     : launch_bc_compare(format, (flags & KC_BC_SRGB) ? 1 : 0, o, rgba ? 0 : 1, blocks, row_pitch, w, h, nt_mask,
+                                                         groups, partials, c.stats.result, c.stream);
     if (e != hipSuccess) return hip_fail(e, "launch_bc_compare");
     c.launches += 2;
     c.alg_bytes += in_bytes + blk_bytes;

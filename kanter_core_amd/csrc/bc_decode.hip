@@ -368,6 +368,13 @@ __global__ __launch_bounds__(256) void bc_combine_kernel(const unsigned long lon
     if (threadIdx.x == 0) result[col] = red[0];
 }
 
+hipError_t launch_bc_combine(const unsigned long long *partials, uint32_t groups, uint32_t rec_words, uint32_t max_cols,
+                             unsigned long long *result, hipStream_t s)
+{
+    bc_combine_kernel<<<dim3(rec_words), 256, 0, s>>>(partials, groups, rec_words, max_cols, result);
+    return hipGetLastError();
+}
+
 uint32_t bc_decode_groups(uint32_t w, uint32_t h, bool count)
 {
     const uint64_t total = (uint64_t)((w + 3) / 4) * ((h + 3) / 4);
@@ -410,8 +417,7 @@ hipError_t launch_bc_decode(int fmt, const BcDecodeArgs &a, bool count, uint32_t
 #undef KC_BCD
     hipError_t e = hipGetLastError();
     if (e != hipSuccess || !count) return e;
-    bc_combine_kernel<<<dim3(1), 256, 0, s>>>(a.partials, groups, 1u, 0u, a.result);
-    return hipGetLastError();
+    return launch_bc_combine(a.partials, groups, 1u, 0u, a.result, s);
 }
 
 hipError_t launch_bc_compare(int fmt, int srgb, const Operand op[4], int gray, const char *blocks, uint64_t row_pitch, uint32_t w, uint32_t h,
@@ -454,8 +460,7 @@ hipError_t launch_bc_compare(int fmt, int srgb, const Operand op[4], int gray, c
 #undef KC_BCC
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
-    bc_combine_kernel<<<dim3(KC_BC_REC_WORDS), 256, 0, s>>>(partials, groups, KC_BC_REC_WORDS, 0xf0u, result);
-    return hipGetLastError();
+    return launch_bc_combine(partials, groups, KC_BC_REC_WORDS, 0xf0u, result, s);
 }
 
 }  // namespace kc

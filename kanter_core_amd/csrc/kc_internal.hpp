@@ -331,6 +331,20 @@ constexpr uint32_t KC_BC_REC_WORDS = 17;
 hipError_t launch_bc_compare(int fmt, int srgb, const Operand op[4], int gray, const char *blocks, uint64_t row_pitch, uint32_t w, uint32_t h,
                              uint32_t nt_mask, uint32_t groups, unsigned long long *partials, unsigned long long *result, hipStream_t s);
 uint32_t bc_compare_groups(uint32_t w, uint32_t h);
+// bc_combine_kernel alone, for the records of another unit's kernels: result[col] = the sum (max_cols bit col set: the maximum)
+// of word col of the `groups` records of rec_words words
+hipError_t launch_bc_combine(const unsigned long long *partials, uint32_t groups, uint32_t rec_words, uint32_t max_cols,
+                             unsigned long long *result, hipStream_t s);
+// -- bc6h.hip --
+// KC_BC6H (16-byte blocks; R, G, B as half bit patterns, alpha never read).  bc6h_encode_kernel<nt>: launch_bc7_encode's stream
+// without the sRGB form.  bc6h_decode_kernel<nt, count>: launch_bc_decode's arguments, dst[0..2] written; count: result[0] = the
+// blocks of the two-subset modes, which are not decoded (a second launch).  bc6h_compare_kernel<nt>, then bc_combine_kernel:
+// launch_bc_compare's arguments and record, the differences taken over the half bit patterns.
+hipError_t launch_bc6h_encode(const Operand op[4], int gray, char *dst, uint64_t row_pitch, uint32_t w, uint32_t h, uint32_t nt_mask,
+                              hipStream_t s);
+hipError_t launch_bc6h_decode(const BcDecodeArgs &a, bool count, uint32_t nt_mask, uint32_t groups, hipStream_t s);
+hipError_t launch_bc6h_compare(const Operand op[4], int gray, const char *blocks, uint64_t row_pitch, uint32_t w, uint32_t h, uint32_t nt_mask,
+                               uint32_t groups, unsigned long long *partials, unsigned long long *result, hipStream_t s);
 // -- mip.hip --
 // Mip chains (mip.hip / mip.cpp): the 2 x 2 box of the header on the n_planes distinct resident planes of one image.
 // mip_pyramid_kernel<nt>: levels 1..n (1 <= n <= 6, both of w >> n and h >> n still >= 1) of the w x h source planes, one

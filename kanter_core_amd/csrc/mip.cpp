@@ -169,7 +169,7 @@ static int bc_mips_check_flags(int format, uint32_t flags, uint32_t allowed, con
         set_error(std::string(who) + ": unknown flag bits");
         return KC_ERR_UNSUPPORTED;
     }
-    if ((flags & KC_BC_SRGB) && (format == KC_BC4 || format == KC_BC5)) {
+    if ((flags & KC_BC_SRGB) && (format == KC_BC4 || format == KC_BC5 || format == KC_BC6H)) {
         set_error(std::string(who) + ": KC_BC_SRGB is for BC1, BC3 and BC7 only");
         return KC_ERR_UNSUPPORTED;
     }
@@ -272,6 +272,7 @@ static uint32_t dxgi_format(int format, bool srgb)
     case KC_BC3: return srgb ? 78u : 77u;
     case KC_BC4: return 80u;
     case KC_BC7: return srgb ? 99u : 98u;
+    case KC_BC6H: return 95u;
     default: return 83u;  // KC_BC5
     }
 }

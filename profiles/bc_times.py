@@ -1,6 +1,7 @@
-"""Block compression at 4096^2 (csrc/bc.hip, csrc/bc7.hip): kernel time, algorithmic bytes and the fraction of 8 TB/s per case --
-Gray BC4; RGBA BC1, BC1 sRGB, BC3, BC3 sRGB, BC4, BC5, BC7 and BC7 sRGB; random data and a uniform image (every block takes the
-d == 0 / c0 == c1 path; BC7 searches its palettes all the same)
+"""Block compression at 4096^2 (csrc/bc.hip, csrc/bc7.hip, csrc/bc6h.hip): kernel time, algorithmic bytes and the fraction of 8 TB/s
+per case -- Gray BC4; RGBA BC1, BC1 sRGB, BC3, BC3 sRGB, BC4, BC5, BC7 and BC7 sRGB; BC6H encode, decode and compare (of its own
+blocks) on planes over [0, 8); random data and a uniform image (every block takes the
+d == 0 / c0 == c1 path; BC7 and BC6H search their palettes all the same)
 -- with kc_image_to_device U8 of the same images beside them as the yardstick, and the wall-clock of kc_image_to_bc against
 kc_image_to_u8 plus the numpy reference encoder (tests/bc_ref.py) for the same blocks.
 
@@ -24,29 +25,36 @@ N = 4096
 PEAK_TBS = 8.0
 PX = N * N
 BC7 = 98  # KC_BC7
-BLOCK_BYTES = {1: 8, 3: 16, 4: 8, 5: 16, BC7: 16}
-PLANES = {1: 3, 3: 4, 4: 1, 5: 2, BC7: 4}  # RGBA planes each format reads
-# (name, channels, data, kind, fmt, srgb); kind "bc" or "u8" (kc_image_to_device U8, the yardstick)
+BC6H = 95  # KC_BC6H
+BLOCK_BYTES = {1: 8, 3: 16, 4: 8, 5: 16, BC6H: 16, BC7: 16}
+PLANES = {1: 3, 3: 4, 4: 1, 5: 2, BC6H: 3, BC7: 4}  # RGBA planes each format reads
+# (name, channels, data, kind, fmt, srgb); kind "bc", "u8" (kc_image_to_device U8, the yardstick), or BC6H's "decode" (the
+# image's own blocks back to three planes) and "compare" (the image against its own blocks: two launches, the first is timed)
 CASES = []
 for _data in ("random", "uniform"):
     CASES.append(("Gray BC4 %s" % _data, 1, _data, "bc", 4, False))
     for _fmt, _srgb in ((1, False), (1, True), (3, False), (3, True), (4, False), (5, False), (BC7, False), (BC7, True)):
         CASES.append(("RGBA BC%d%s %s" % (7 if _fmt == BC7 else _fmt, " sRGB" if _srgb else "", _data), 4, _data, "bc", _fmt, _srgb))
     CASES.append(("RGBA to_device U8 %s" % _data, 4, _data, "u8", 0, False))
+    for _kind in ("bc", "decode", "compare"):
+        CASES.append(("HDR BC6H %s %s" % ("encode" if _kind == "bc" else _kind, _data), 4, "hdr " + _data, _kind, BC6H, False))
+OWN = ("hdr random", "hdr uniform")  # the images whose own BC6H blocks decode and compare read: encoded once, before the cases
+KERNEL = {"u8": "image_export_kernel", "decode": "bc6h_decode_kernel", "compare": "bc6h_compare_kernel"}
 
 
 def planes_for(ch, data):
     import numpy as np
     rng = np.random.default_rng(ch)
-    if data == "random":
-        return [rng.random((N, N), dtype=np.float32) for _ in range(ch)]
-    return [np.full((N, N), 0.4 + 0.1 * c, np.float32) for c in range(ch)]  # resident planes of one value each
+    scale = np.float32(8.0 if data.startswith("hdr ") else 1.0)  # BC6H's planes go above 1
+    if data.endswith("random"):
+        return [rng.random((N, N), dtype=np.float32) * scale for _ in range(ch)]
+    return [np.full((N, N), (0.4 + 0.1 * c) * scale, np.float32) for c in range(ch)]  # resident planes of one value each
 
 
 def case_bytes(ch, kind, fmt):
     if kind == "u8":
         return 4 * ch * PX + 4 * PX
-    return 4 * (1 if ch == 1 else PLANES[fmt]) * PX + (N // 4) * (N // 4) * BLOCK_BYTES[fmt]
+    return 4 * (1 if ch == 1 else PLANES[fmt]) * PX + (N // 4) * (N // 4) * BLOCK_BYTES[fmt]  # decode writes what encode reads
 
 
 def run(reps):
@@ -59,15 +67,23 @@ def run(reps):
     kc.init(0)
     imgs = {}
     for ch in (1, 4):
-        for data in ("random", "uniform"):
+        for data in ("random", "uniform") + (OWN if ch == 4 else ()):
             imgs[ch, data] = kc.SlotImage.from_planes(planes_for(ch, data)).materialize()
+    own = {data: imgs[4, data].to_bc_torch(BC6H) for data in OWN}
     outs = {f: torch.empty((N // 4, N // 4, BLOCK_BYTES[f]), dtype=torch.uint8, device="cuda") for f in BLOCK_BYTES}
     u8 = torch.empty((N, N, 4), dtype=torch.uint8, device="cuda")
     kc.sync()
     torch.cuda.synchronize()
     for name, ch, data, kind, fmt, srgb in CASES:
         img = imgs[ch, data]
-        call = (lambda: img.to_torch(out=u8)) if kind == "u8" else (lambda: img.to_bc_torch(fmt, srgb, out=outs[fmt]))
+        if kind == "u8":
+            call = lambda: img.to_torch(out=u8)  # noqa: E731
+        elif kind == "decode":
+            call = lambda: kc.SlotImage.from_bc_torch(own[data], N, N, fmt)  # noqa: E731
+        elif kind == "compare":
+            call = lambda: img.bc_error(fmt, blocks=own[data])  # noqa: E731
+        else:
+            call = lambda: img.to_bc_torch(fmt, srgb, out=outs[fmt])  # noqa: E731
         call()  # warm-up
         torch.cuda.synchronize()
         b0 = kc.stats()["algorithmic_bytes"]
@@ -99,7 +115,9 @@ def report(trace_csv, log):
     col = lambda key: next(k for k in rows[0] if key in k)  # noqa: E731
     kn, ks, ke = col("Kernel_Name"), col("Start_Timestamp"), col("End_Timestamp")
     rows.sort(key=lambda r: int(r[ks]))
-    ours = [r for r in rows if "bc_encode_kernel" in r[kn] or "bc7_encode_kernel" in r[kn] or "image_export_kernel" in r[kn]]
+    names = ("bc_encode_kernel", "bc7_encode_kernel", "bc6h_encode_kernel", "bc6h_decode_kernel", "bc6h_compare_kernel", "image_export_kernel")
+    ours = [r for r in rows if any(n in r[kn] for n in names)]
+    ours = ours[len(OWN):]
     per = reps + 1
     # the cases' dispatches come first; the wall-clock comparison's calls follow them
     assert len(ours) >= len(CASES) * per, (len(ours), len(CASES) * per)
@@ -109,7 +127,7 @@ def report(trace_csv, log):
     out.append("%-30s %10s %10s %9s" % ("case", "median us", "alg MB", "of 8TB/s"))
     for i, (name, ch, _, kind, fmt, _) in enumerate(CASES):
         seg = ours[i * per:(i + 1) * per]
-        want = "image_export_kernel" if kind == "u8" else "bc7_encode_kernel" if fmt == BC7 else "bc_encode_kernel"
+        want = KERNEL.get(kind) or ("bc7_encode_kernel" if fmt == BC7 else "bc6h_encode_kernel" if fmt == BC6H else "bc_encode_kernel")
         assert all(want in r[kn] for r in seg), name
         ns = statistics.median([int(r[ke]) - int(r[ks]) for r in seg[1:]])
         b = case_bytes(ch, kind, fmt)
