@@ -665,17 +665,10 @@ def _bc_export(call, size, fmt, srgb, out):
     """Allocates (or takes) a uint8 (by, bx, block bytes) tensor and runs `call(desc, flags, stream)` into it.  `out` may be any
     view whose last two dimensions are contiguous (rows of blocks anywhere, e.g. a slice of a larger tensor)."""
     import torch
-    f = _bc_format(fmt)
-    bb = BC_BLOCK_BYTES[f]
-    bx, by = (size.width + 3) // 4, (size.height + 3) // 4
     if out is None:
-        out = torch.empty((by, bx, bb), dtype=torch.uint8, device=torch.device("cuda", torch.cuda.current_device()))
-    if out.dtype != torch.uint8 or tuple(out.shape) != (by, bx, bb):
-        raise ValueError("out must be uint8 of shape %s, got %s %s" % ((by, bx, bb), out.dtype, tuple(out.shape)))
-    if (bx > 1 and out.stride(1) != bb) or out.stride(2) != 1:
-        raise ValueError("out needs each block row packed: strides (..., %d, 1), got %s" % (bb, out.stride()))
-    pitch = out.stride(0) if by > 1 else bx * bb
-    d = _lib.kc_bc_image(out.data_ptr(), size.width, size.height, f, pitch)
+        shape = ((size.height + 3) // 4, (size.width + 3) // 4, BC_BLOCK_BYTES[_bc_format(fmt)])
+        out = torch.empty(shape, dtype=torch.uint8, device=torch.device("cuda", torch.cuda.current_device()))
+    d = _bc_desc(out, size.width, size.height, fmt, what="out", need="needs")
     _check(_on_torch_stream(out, lambda stream: call(C.byref(d), BC_SRGB if srgb else 0, stream)))
     return out
 
@@ -787,16 +780,17 @@ def _bc_error(call, srgb):
                    int(r.undecoded_blocks), np.array(r.bc7_mode_blocks[:], np.uint64))
 
 
-def _bc_desc(t, width, height, fmt):
-    """kc_bc_image of a uint8 (by, bx, block bytes) tensor whose last two dimensions are contiguous"""
+def _bc_desc(t, width, height, fmt, what="blocks", need="need"):
+    """kc_bc_image of a uint8 (by, bx, block bytes) tensor whose last two dimensions are contiguous; `what` (and its verb) name the
+    tensor in the errors"""
     import torch
     f = _bc_format(fmt)
     bb = BC_BLOCK_BYTES[f]
     bx, by = (width + 3) // 4, (height + 3) // 4
     if t.dtype != torch.uint8 or tuple(t.shape) != (by, bx, bb):
-        raise ValueError("blocks must be uint8 of shape %s, got %s %s" % ((by, bx, bb), t.dtype, tuple(t.shape)))
+        raise ValueError("%s must be uint8 of shape %s, got %s %s" % (what, (by, bx, bb), t.dtype, tuple(t.shape)))
     if (bx > 1 and t.stride(1) != bb) or t.stride(2) != 1:
-        raise ValueError("blocks need each block row packed: strides (..., %d, 1), got %s" % (bb, t.stride()))
+        raise ValueError("%s %s each block row packed: strides (..., %d, 1), got %s" % (what, need, bb, t.stride()))
     return _lib.kc_bc_image(t.data_ptr(), width, height, f, t.stride(0) if by > 1 else bx * bb)
 
 

@@ -2,14 +2,61 @@
 // checks the arguments and the caller's descriptor -- arithmetic first, then that its bytes lie in one allocation of the
 // library's device -- and launches bc.hip's encoder (KC_BC7: bc7.hip's, KC_BC6H: bc6h.hip's) once per call: on the library's stream, ordered
 // against the caller's stream by the two event edges of kc_image_to_device, or into pool staging that is copied to the
-// caller's host memory.
+// caller's host memory.  The file also holds what the whole BC family's host side shares (bc_decode.cpp, the BC half of mip.cpp):
+// the format table, the block count and level bytes, the flag rule, the source operands of an image and the choice of a format's device unit.
 #include "kc_runtime.hpp"
 
 namespace kc {
 
+// What a format is, for the whole host side (kc_runtime.hpp has the fields).  BC6H's blocks are written to .dds and not read back.
+static const BcFormat kBcFormats[] = {
+    // format  bytes  channels  planes  srgb   counts  dxgi  dxgi_srgb  dds_read  fourcc
+    { KC_BC1,  8,     0x7u,     4,      true,  false,  71,   72,        true,     { fourcc('D', 'X', 'T', '1'), 0 } },
+    { KC_BC3,  16,    0xfu,     4,      true,  false,  77,   78,        true,     { fourcc('D', 'X', 'T', '5'), 0 } },
+    { KC_BC4,  8,     0x1u,     1,      false, false,  80,   0,         true,     { fourcc('A', 'T', 'I', '1'), fourcc('B', 'C', '4', 'U') } },
+    { KC_BC5,  16,    0x3u,     2,      false, false,  83,   0,         true,     { fourcc('A', 'T', 'I', '2'), fourcc('B', 'C', '5', 'U') } },
+    { KC_BC6H, 16,    0x7u,     3,      false, true,   95,   0,         false,    { 0, 0 } },
+    { KC_BC7,  16,    0xfu,     4,      true,  true,   98,   99,        true,     { 0, 0 } },
+};
+
+const BcFormat *bc_format(int format)
+{
+    for (const BcFormat &f : kBcFormats)
+        if (f.format == format) return &f;
+    return nullptr;
+}
+
+const BcFormat *bc_format_of_dds(uint32_t dxgi, uint32_t cc, uint32_t *flags)
+{
+    for (const BcFormat &f : kBcFormats) {
+        if (!f.dds_read) continue;
+        const bool srgb = dxgi != 0 && dxgi == f.dxgi_srgb;
+        if (srgb || (dxgi != 0 && dxgi == f.dxgi) || (cc != 0 && (cc == f.fourcc[0] || cc == f.fourcc[1]))) {
+            *flags = srgb ? KC_BC_SRGB : 0u;
+            return &f;
+        }
+    }
+    return nullptr;
+}
+
 size_t bc_block_bytes(int format)
 {
-    return format == KC_BC1 || format == KC_BC4 ? 8 : format == KC_BC3 || format == KC_BC5 || format == KC_BC7 || format == KC_BC6H ? 16 : 0;
+    const BcFormat *f = bc_format(format);
+    return f ? f->block_bytes : 0;
+}
+
+size_t bc_level_bytes(uint32_t w, uint32_t h, const BcFormat &f) { return (((size_t)w + 3) / 4) * (((size_t)h + 3) / 4) * f.block_bytes; }
+
+int bc_block_count(uint32_t w, uint32_t h, const char *who, uint64_t *bx, uint64_t *by)
+{
+    *bx = ((uint64_t)w + 3) / 4;
+    *by = ((uint64_t)h + 3) / 4;
+    // the kernels' block index is 32-bit, with room for the grid-stride step
+    if (*bx * *by > (1ull << 31)) {
+        set_error(std::string(who) + ": image too large: more than 2^31 blocks");
+        return KC_ERR_INVALID_ARG;
+    }
+    return KC_OK;
 }
 
 static int bc_refuse(const char *what)
@@ -18,14 +65,14 @@ static int bc_refuse(const char *what)
     return KC_ERR_INVALID_ARG;
 }
 
-// Flag bits other than KC_BC_SRGB, or KC_BC_SRGB with a format without colour, are KC_ERR_UNSUPPORTED
-int bc_check_flags(int format, uint32_t flags, const char *who)
+int bc_check_flags(int format, uint32_t flags, uint32_t allowed, const char *who)
 {
-    if (flags & ~(uint32_t)KC_BC_SRGB) {
-        set_error(std::string(who) + ": flags other than KC_BC_SRGB");
+    if (flags & ~allowed) {
+        set_error(std::string(who) + ": unknown flag bits");
         return KC_ERR_UNSUPPORTED;
     }
-    if ((flags & KC_BC_SRGB) && (format == KC_BC4 || format == KC_BC5 || format == KC_BC6H)) {
+    const BcFormat *f = bc_format(format);
+    if ((flags & KC_BC_SRGB) && f && !f->srgb) {
         set_error(std::string(who) + ": KC_BC_SRGB is for BC1, BC3 and BC7 only");
         return KC_ERR_UNSUPPORTED;
     }
@@ -39,9 +86,8 @@ static int bc_check_arith(const kc_bc_image *d, size_t *extent)
     const size_t bb = bc_block_bytes(d->format);
     if (bb == 0) return bc_refuse("unknown format");
     if (!d->ptr || d->width == 0 || d->height == 0) return bc_refuse("NULL pointer or zero extent");
-    const uint64_t bx = ((uint64_t)d->width + 3) / 4, by = ((uint64_t)d->height + 3) / 4;
-    // the kernel's block index is 32-bit, with room for the grid-stride step
-    if (bx * by > (1ull << 31)) return bc_refuse("image too large: more than 2^31 blocks");
+    uint64_t bx = 0, by = 0;
+    KC_TRY(bc_block_count(d->width, d->height, "kc_bc_image", &bx, &by));
     if ((uintptr_t)d->ptr % bb || d->row_pitch_bytes % bb) return bc_refuse("pointer and row pitch must be multiples of the block bytes");
     size_t row_bytes = 0, last = 0, ext = 0;
     if (__builtin_mul_overflow((size_t)bx, bb, &row_bytes)) return bc_refuse("extent overflows");
@@ -61,30 +107,56 @@ int bc_image_validate(const kc_bc_image *d, size_t *extent_bytes)
     return device_extent_check(d->ptr, ext, "kc_bc_image");
 }
 
+uint32_t bc_source_operands(const kc_image *img, uint32_t mask, Operand (&o)[4])
+{
+    const bool rgba = img->is_rgba();
+    for (int i = 0; i < 4; ++i) o[i] = rgba ? plane_operand(img->planes[i]) : i < 3 ? plane_operand(img->planes[0]) : Operand{ nullptr, 0, 1.0f };
+    const float *seen[4] = { nullptr, nullptr, nullptr, nullptr };
+    uint32_t n_res = 0;
+    for (int i = 0; i < 4; ++i) {
+        if (!((mask >> i) & 1u) || !o[i].ptr) continue;
+        bool dup = false;
+        for (uint32_t k = 0; k < n_res; ++k) dup |= seen[k] == o[i].ptr;
+        if (!dup) seen[n_res++] = o[i].ptr;
+    }
+    return n_res;
+}
+
+// ---------------------------------------------------------------- the device unit of a format
+// BC6H's three kernels are bc6h.hip's, BC7's encoder bc7.hip's; everything else is bc.hip's and bc_decode.hip's
+hipError_t bc_launch_encode(int format, bool srgb, const Operand op[4], int gray, char *dst, uint64_t row_pitch, uint32_t w, uint32_t h,
+                            uint32_t nt_mask, hipStream_t s)
+{
+    if (format == KC_BC6H) return launch_bc6h_encode(op, gray, dst, row_pitch, w, h, nt_mask, s);
+    if (format == KC_BC7) return launch_bc7_encode(srgb ? 1 : 0, op, gray, dst, row_pitch, w, h, nt_mask, s);
+    return launch_bc_encode(format, srgb ? 1 : 0, op, gray, dst, row_pitch, w, h, nt_mask, s);
+}
+
+hipError_t bc_launch_decode(int format, const BcDecodeArgs &a, bool count, uint32_t nt_mask, uint32_t groups, hipStream_t s)
+{
+    if (format == KC_BC6H) return launch_bc6h_decode(a, count, nt_mask, groups, s);
+    return launch_bc_decode(format, a, count, nt_mask, groups, s);
+}
+
+hipError_t bc_launch_compare(int format, bool srgb, const Operand op[4], int gray, const char *blocks, uint64_t row_pitch, uint32_t w, uint32_t h,
+                             uint32_t nt_mask, uint32_t groups, unsigned long long *partials, unsigned long long *result, hipStream_t s)
+{
+    if (format == KC_BC6H) return launch_bc6h_compare(op, gray, blocks, row_pitch, w, h, nt_mask, groups, partials, result, s);
+    return launch_bc_compare(format, srgb ? 1 : 0, op, gray, blocks, row_pitch, w, h, nt_mask, groups, partials, result, s);
+}
+
 // One launch of the encoder for `img` (forced already) into `dst`, block rows `row_pitch` bytes apart.  The channels the format
 // reads come from the image as to_u8 sees it (Gray: (v, v, v, 1)); constants cost no loads.  KC_BC6H reads R, G and B.
 int bc_encode(kc_image *img, int format, bool srgb, char *dst, size_t row_pitch, hipStream_t s)
 {
     Context &c = ctx();
-    const bool rgba = img->is_rgba();
+    const BcFormat &f = *bc_format(format);  // the entry points have refused an unknown format
     Operand o[4];
-    for (int i = 0; i < 4; ++i) o[i] = rgba ? plane_operand(img->planes[i]) : i < 3 ? plane_operand(img->planes[0]) : Operand{ nullptr, 0, 1.0f };
-    const int n_ch = format == KC_BC1 || format == KC_BC6H ? 3 : format == KC_BC3 || format == KC_BC7 ? 4 : format == KC_BC4 ? 1 : 2;
-    const float *seen[4] = { nullptr, nullptr, nullptr, nullptr };
-    uint32_t n_res = 0;  // distinct resident planes the launch reads
-    for (int i = 0; i < n_ch; ++i) {
-        if (!o[i].ptr) continue;
-        bool dup = false;
-        for (uint32_t k = 0; k < n_res; ++k) dup |= seen[k] == o[i].ptr;
-        if (!dup) seen[n_res++] = o[i].ptr;
-    }
+    const uint32_t n_res = bc_source_operands(img, f.channels, o);
     const uint32_t w = img->w(), h = img->h();
-    const uint64_t in_bytes = (uint64_t)w * h * 4 * n_res;
-    const uint64_t out_bytes = (uint64_t)((w + 3) / 4) * ((h + 3) / 4) * bc_block_bytes(format);
+    const uint64_t in_bytes = (uint64_t)w * h * 4 * n_res, out_bytes = bc_level_bytes(w, h, f);
     const uint32_t nt_mask = cache_policy_mask(in_bytes, out_bytes, n_res ? n_res : 1);
-    hipError_t e = format == KC_BC6H  ? launch_bc6h_encode(o, rgba ? 0 : 1, dst, row_pitch, w, h, nt_mask, s)
-                   : format == KC_BC7 ? launch_bc7_encode(srgb ? 1 : 0, o, rgba ? 0 : 1, dst, row_pitch, w, h, nt_mask, s)
-                                      : launch_bc_encode(format, srgb ? 1 : 0, o, rgba ? 0 : 1, dst, row_pitch, w, h, nt_mask, s);
+    hipError_t e = bc_launch_encode(format, srgb, o, img->is_rgba() ? 0 : 1, dst, row_pitch, w, h, nt_mask, s);
     if (e != hipSuccess) return hip_fail(e, "launch_bc_encode");
     c.launches++;
     c.alg_bytes += in_bytes + out_bytes;
@@ -93,47 +165,39 @@ int bc_encode(kc_image *img, int format, bool srgb, char *dst, size_t row_pitch,
 
 int image_to_bc(kc_image *img, int format, uint32_t flags, uint8_t *host, size_t host_bytes)
 {
-    KC_TRY(bc_check_flags(format, flags, "kc_image_to_bc"));
-    const size_t bb = bc_block_bytes(format);
-    if (bb == 0) return bc_refuse("unknown format");
+    KC_TRY(bc_check_flags(format, flags, KC_BC_SRGB, "kc_image_to_bc"));
+    const BcFormat *f = bc_format(format);
+    if (!f) return bc_refuse("unknown format");
     if (!img || !host) return bc_refuse("NULL image or host buffer");
     KC_TRY(need_init());
     Context &c = ctx();
     std::lock_guard<std::recursive_mutex> lk(c.mu);
-    const uint32_t w = img->w(), h = img->h();
-    const uint64_t bx = ((uint64_t)w + 3) / 4, by = ((uint64_t)h + 3) / 4;
-    if (bx * by > (1ull << 31)) return bc_refuse("image too large: more than 2^31 blocks");
-    const size_t nbytes = (size_t)(bx * by) * bb;
+    uint64_t bx = 0, by = 0;
+    KC_TRY(bc_block_count(img->w(), img->h(), "kc_bc_image", &bx, &by));
+    const size_t nbytes = bc_level_bytes(img->w(), img->h(), *f);
     if (host_bytes < nbytes) return bc_refuse("host_bytes < blocks * block bytes");
     KC_TRY(image_force(img));  // a pending fused chain runs first
-    const size_t block = (nbytes + 255) / 256 * 256;
-    void *staging = nullptr;
-    KC_TRY(pool_alloc(block, &staging));
-    int s = bc_encode(img, format, (flags & KC_BC_SRGB) != 0, (char *)staging, (size_t)bx * bb, c.stream);
-    hipError_t e = hipSuccess;
-    if (s == KC_OK) e = hipMemcpyAsync(host, staging, nbytes, hipMemcpyDeviceToHost, c.stream);
-    if (s == KC_OK && e == hipSuccess) e = hipStreamSynchronize(c.stream);
-    pool_free(staging, block);
-    if (s != KC_OK) return s;
+    PoolStaging staging;
+    KC_TRY(staging.alloc(nbytes));
+    KC_TRY(bc_encode(img, format, (flags & KC_BC_SRGB) != 0, (char *)staging.ptr, (size_t)bx * f->block_bytes, c.stream));
+    hipError_t e = hipMemcpyAsync(host, staging.ptr, nbytes, hipMemcpyDeviceToHost, c.stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(c.stream);
     if (e != hipSuccess) return hip_fail(e, "image_to_bc");
     return KC_OK;
 }
 
 int image_to_bc_device(kc_image *img, const kc_bc_image *dst, uint32_t flags, void *hip_stream)
 {
-    KC_TRY(bc_check_flags(dst ? dst->format : 0, flags, "kc_image_to_bc_device"));
+    KC_TRY(bc_check_flags(dst ? dst->format : 0, flags, KC_BC_SRGB, "kc_image_to_bc_device"));
     KC_TRY(bc_image_validate(dst, nullptr));
     if (!img) return bc_refuse("image is NULL");
     if (img->w() != dst->width || img->h() != dst->height) return bc_refuse("descriptor size differs from the image's");
     Context &c = ctx();
     std::lock_guard<std::recursive_mutex> lk(c.mu);
     KC_TRY(image_force(img));  // a pending fused chain runs first
-    hipStream_t hs = (hipStream_t)hip_stream;
-    const bool edges = hs && hs != c.stream;
-    if (edges) KC_TRY(stream_edge(hs, c.stream));
-    KC_TRY(bc_encode(img, dst->format, (flags & KC_BC_SRGB) != 0, (char *)dst->ptr, dst->row_pitch_bytes, c.stream));
-    if (edges) KC_TRY(stream_edge(c.stream, hs));
-    return KC_OK;
+    return with_stream_edges(hip_stream, [&] {
+        return bc_encode(img, dst->format, (flags & KC_BC_SRGB) != 0, (char *)dst->ptr, dst->row_pitch_bytes, c.stream);
+    });
 }
 
 }  // namespace kc

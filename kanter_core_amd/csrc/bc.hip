@@ -4,13 +4,14 @@
 // a wave take consecutive blocks of a block row and each of the block's four pixel rows is one 16-byte load per plane and lane,
 // contiguous across the wave (the library's planes, kc_plane_wrap's included, are readable in whole float4 quads).  The texels
 // are quantised as they arrive and kept as RGBA8 words; the encoder is integer arithmetic on them; a block leaves in one 8- or
-// 16-byte store.  bc7.hip is the same stream with the BC7 encoder.
+// 16-byte store.  The steps of the stream -- the walk over the blocks and its edge rule, the row loads, the quantiser, the staging of
+// the sRGB table -- are bc_blocks.h's; bc7.hip and bc6h.hip run the same loop around their own encoders.
 #include "kc_internal.hpp"
 
 namespace kc {
 
 #include "streaming.h"  // grid_cap, ld_policy, quant_u8 / quant_u8_srgb: shared with u8.hip
-#include "bc_blocks.h"  // the row loaders, the quantiser, the column clamp and BcBlockArgs: shared with bc7.hip
+#include "bc_blocks.h"  // BcBlockArgs, the grid, the block walk, the row loaders and the quantiser: shared by the block-compression units
 
 // The channels a format reads: bit c = channel c (R, G, B, A)
 static constexpr uint32_t bc_channels(int fmt) { return fmt == 1 ? 0x7u : fmt == 3 ? 0xfu : fmt == 4 ? 0x1u : 0x3u; }
@@ -146,51 +147,40 @@ template <int FMT, bool SRGB, bool NT>  // NT: the planes are read once and do n
 __global__ __launch_bounds__(256) void bc_encode_kernel(Operand r, Operand g, Operand b, Operand al, int gray, const BcBlockArgs a)
 {
     __shared__ uint32_t srgb_t[SRGB ? 257 : 1];
+    constexpr uint32_t CH = bc_channels(FMT);
     const Operand op[4] = { r, g, b, al };
-    const uint32_t total = a.bx * a.by;
-    // edge blocks: the last block column when the width is not a multiple of 4, the last block row likewise
-    const uint32_t edge_i = (a.w & 3u) ? a.bx - 1 : 0xffffffffu, edge_j = (a.h & 3u) ? a.by - 1 : 0xffffffffu;
+    const BcWalk k = bc_walk(a.w, a.h, a.bx, a.by);
     uint32_t idx = blockIdx.x * 256u + threadIdx.x;
-    auto block_of = [&](uint32_t n, uint32_t &i, uint32_t &j, bool &wave_edge) {
-        j = n / a.bx;
-        i = n - j * a.bx;
-        // wave-uniform: a wave that holds no edge block skips the clamps
-        wave_edge = __any(n < total && (i == edge_i || j == edge_j)) != 0;
-    };
     if constexpr (SRGB) {
         // The first block's first row of loads goes out BEFORE the threshold table is staged (a global read and a barrier that
         // every thread of the workgroup takes, in range or not), as in to_u8_kernel: the table arrives while they are in flight.
-        const bool in_range = idx < total;
-        uint32_t i = 0u, j = 0u;
-        bool we = false;
-        block_of(in_range ? idx : 0u, i, j, we);
+        const bool in_range = idx < k.total;
+        uint32_t i, j;
+        const bool we = bc_block_of(k, idx, i, j);
         bc_f4 v[4];
-        if (in_range) bc_load_row<bc_channels(FMT), NT>(op, gray, a, i, j, 0, we, v);
-        srgb_t[threadIdx.x] = kSrgbThresholdBits[threadIdx.x];  // 256 threads
-        if (threadIdx.x == 0) srgb_t[256] = 0xffffffffu;         // sentinel: nothing is >= it
-        __syncthreads();
+        if (in_range) bc_load_row<CH, NT>(op, gray, a, i, j, 0, we, v);
+        bc_stage_srgb(srgb_t);
         if (!in_range) return;
         uint32_t rb[16], ga[16];
-        bc_quantise_row<bc_channels(FMT), SRGB>(v, gray, 0, srgb_t, rb, ga);
+        bc_quantise_row<CH, SRGB>(v, gray, 0, srgb_t, rb, ga);
 #pragma unroll
         for (int y = 1; y < 4; ++y) {
-            bc_load_row<bc_channels(FMT), NT>(op, gray, a, i, j, y, we, v);
-            bc_quantise_row<bc_channels(FMT), SRGB>(v, gray, y, srgb_t, rb, ga);
+            bc_load_row<CH, NT>(op, gray, a, i, j, y, we, v);
+            bc_quantise_row<CH, SRGB>(v, gray, y, srgb_t, rb, ga);
         }
         if (we) bc_clamp_columns(a, i, rb, ga);
         bc_encode_store<FMT>(rb, ga, a, i, j);
         idx += gridDim.x * 256u;
     }
-    for (; idx < total; idx += gridDim.x * 256u) {
+    for (; idx < k.total; idx += gridDim.x * 256u) {
         uint32_t i, j;
-        bool we;
-        block_of(idx, i, j, we);
+        const bool we = bc_block_of(k, idx, i, j);
         uint32_t rb[16], ga[16];
 #pragma unroll
         for (int y = 0; y < 4; ++y) {
             bc_f4 v[4];
-            bc_load_row<bc_channels(FMT), NT>(op, gray, a, i, j, y, we, v);
-            bc_quantise_row<bc_channels(FMT), SRGB>(v, gray, y, srgb_t, rb, ga);
+            bc_load_row<CH, NT>(op, gray, a, i, j, y, we, v);
+            bc_quantise_row<CH, SRGB>(v, gray, y, srgb_t, rb, ga);
         }
         if (we) bc_clamp_columns(a, i, rb, ga);
         bc_encode_store<FMT>(rb, ga, a, i, j);
@@ -200,20 +190,13 @@ __global__ __launch_bounds__(256) void bc_encode_kernel(Operand r, Operand g, Op
 hipError_t launch_bc_encode(int fmt, int srgb, const Operand op[4], int gray, char *dst, uint64_t row_pitch, uint32_t w, uint32_t h,
                             uint32_t nt_mask, hipStream_t s)
 {
-    BcBlockArgs a;
-    a.dst = dst;
-    a.row_pitch = row_pitch;
-    a.w = w;
-    a.h = h;
-    a.bx = (w + 3) / 4;
-    a.by = (h + 3) / 4;
+    const BcBlockArgs a = bc_block_args(dst, row_pitch, w, h);
     const uint64_t total = (uint64_t)a.bx * a.by;
     if (total == 0) return hipSuccess;
-    uint64_t blocks = (total + 255) / 256;
-    if (blocks > grid_cap(1u << 30)) blocks = grid_cap(1u << 30);
+    const uint32_t blocks = bc_grid(total, 1u << 30);
     const bool nt = (nt_mask & 0xffu) != 0;
-    if (srgb && fmt != 1 && fmt != 3) return hipErrorInvalidValue;
-#define KC_BC(F, SR, NTL) bc_encode_kernel<F, SR, NTL><<<dim3((unsigned)blocks), 256, 0, s>>>(op[0], op[1], op[2], op[3], gray, a)
+    if (srgb && fmt != KC_BC1 && fmt != KC_BC3) return hipErrorInvalidValue;  // no such instantiation (BC7: bc7.hip)
+#define KC_BC(F, SR, NTL) bc_encode_kernel<F, SR, NTL><<<dim3(blocks), 256, 0, s>>>(op[0], op[1], op[2], op[3], gray, a)
 #define KC_BC_NT(F, SR)                                                                                                               \
     do {                                                                                                                             \
         if (nt) KC_BC(F, SR, true);                                                                                                  \

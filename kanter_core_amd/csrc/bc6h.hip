@@ -1,22 +1,22 @@
 // BC6H, unsigned (KC_BC6H = DXGI_FORMAT_BC6H_UF16; bc.cpp, bc_decode.cpp): the HDR block format, by the integer rules of
 // include/kanter_core_amd.h (tests/bc6h_ref.py is the same rules in numpy).  A plane value is quantised to the bit pattern of a
 // half float, h(v) = f16_rne(min(max(v, 0), 65504)), an integer in 0..31743; everything after that is integer arithmetic on
-// the pattern, so the blocks, the decoded planes and the error record are exact.  The streams are bc7.hip's and bc_decode.hip's:
-// one thread per 4x4 block, a grid-stride loop over the blocks in row order, a 16-byte load per plane, row and lane through
-// bc_blocks.h's loaders, one 16-byte store (decode: one float4 store per plane row), nontemporal instantiations, and the
-// wave-uniform edge-block test.  A thread holds its texels as rg = R | G << 16 and bl = B: 15-bit values, so a packed 16-bit
+// the pattern, so the blocks, the decoded planes and the error record are exact.  The streams are built from bc_blocks.h's steps,
+// as bc7.hip's and bc_decode.hip's: one thread per 4x4 block, a grid-stride loop over the blocks in row order, a 16-byte load per
+// plane, row and lane through its loaders, one 16-byte store (decode: its plane-row store), nontemporal instantiations, and
+// the wave-uniform edge-block test.  A thread holds its texels as rg = R | G << 16 and bl = B: 15-bit values, so a packed 16-bit
 // subtract cannot borrow across the lanes and a difference fits a signed 16-bit lane.
 //   bc6h_encode_kernel   mode 11 only (one subset, two 10-bit endpoints per channel, sixteen palette entries)
 //   bc6h_decode_kernel   the four single-subset modes 11-14; the two-subset modes 1-10 give (0, 0, 0) and are counted
 //   bc6h_compare_kernel  the squared differences of the half bit patterns, decoded against h(source)
-// The counts and sums leave each workgroup as one record of KC_BC_REC_WORDS u64 words, as bc_decode.hip's, and its
-// bc_combine_kernel folds them (launch_bc_combine).
+// The counts and sums leave each workgroup as one record of KC_BC_REC_WORDS u64 words (bc_blocks.h's bc_fold_record), and
+// bc_decode.hip's bc_combine_kernel folds the records (launch_bc_combine).
 #include "kc_internal.hpp"
 
 namespace kc {
 
 #include "streaming.h"  // grid_cap, ld_policy / st_policy
-#include "bc_blocks.h"  // the packed types, the row loader, the column clamp and BcBlockArgs
+#include "bc_blocks.h"  // the packed types and lanes, the block walk, the row loaders, the plane-row store and the record fold
 
 // h(v): NaN, the negatives, -0 and -inf fail the comparison and give 0; +inf and everything >= 65504 give 0x7BFF.  The
 // conversion rounds to nearest even and keeps denormal halves, as devimage.hip's F16 export does.  The compiler makes one
@@ -40,17 +40,6 @@ static __device__ __forceinline__ void bc6h_quantise_row(const bc_f4 (&v)[4], in
         bl[4 * y + x] = b & 0x7fffu;
     }
 }
-
-static __device__ __forceinline__ uint32_t pk_sub(uint32_t a, uint32_t b) { return __builtin_bit_cast(uint32_t, as_s2(a) - as_s2(b)); }
-static __device__ __forceinline__ uint32_t pk_min(uint32_t a, uint32_t b)
-{
-    return __builtin_bit_cast(uint32_t, __builtin_elementwise_min(as_h2(a), as_h2(b)));
-}
-static __device__ __forceinline__ uint32_t pk_max(uint32_t a, uint32_t b)
-{
-    return __builtin_bit_cast(uint32_t, __builtin_elementwise_max(as_h2(a), as_h2(b)));
-}
-static __device__ __forceinline__ int32_t dot2(uint32_t a, uint32_t b, int32_t c) { return __builtin_amdgcn_sdot2(as_s2(a), as_s2(b), c, false); }
 
 static __device__ __forceinline__ uint32_t bc6h_w4(uint32_t i) { return (64u * i + 7u) / 15u; }  // 0, 4, 9, 13, ..., 60, 64
 
@@ -177,13 +166,10 @@ __global__ __launch_bounds__(256) void bc6h_encode_kernel(Operand r, Operand g, 
 {
     constexpr uint32_t CH = 0x7u;  // R, G, B
     const Operand op[4] = { r, g, b, Operand{ nullptr, 0, 1.0f } };
-    const uint32_t total = a.bx * a.by;
-    // edge blocks: the last block column when the width is not a multiple of 4, the last block row likewise
-    const uint32_t edge_i = (a.w & 3u) ? a.bx - 1 : 0xffffffffu, edge_j = (a.h & 3u) ? a.by - 1 : 0xffffffffu;
-    for (uint32_t idx = blockIdx.x * 256u + threadIdx.x; idx < total; idx += gridDim.x * 256u) {
-        const uint32_t j = idx / a.bx, i = idx - j * a.bx;
-        // wave-uniform: a wave that holds no edge block skips the clamps
-        const bool wave_edge = __any(i == edge_i || j == edge_j) != 0;
+    const BcWalk k = bc_walk(a.w, a.h, a.bx, a.by);
+    for (uint32_t idx = blockIdx.x * 256u + threadIdx.x; idx < k.total; idx += gridDim.x * 256u) {
+        uint32_t i, j;
+        const bool wave_edge = bc_block_of(k, idx, i, j);
         uint32_t rg[16], bl[16];
 #pragma unroll
         for (int y = 0; y < 4; ++y) {
@@ -197,15 +183,6 @@ __global__ __launch_bounds__(256) void bc6h_encode_kernel(Operand r, Operand g, 
 }
 
 // ---------------------------------------------------------------- decode
-// n bits of the 128-bit block from bit `at`, LSB first; `at` and n are constants after unrolling
-static __device__ __forceinline__ uint32_t bc6h_bits(const uint32_t (&b)[4], int at, int n)
-{
-    const int w = at >> 5, s = at & 31;
-    uint32_t v = b[w] >> s;
-    if (s + n > 32) v |= b[w + 1] << (32 - s);
-    return v & ((1u << n) - 1u);
-}
-
 // One block into half bit patterns.  The mode field: bit 1 clear, a 2-bit field, modes 1 and 2; otherwise 5 bits, of which
 // 3, 7, 11 and 15 are the single-subset modes 11-14 (m = field >> 2), 19, 23, 27 and 31 are reserved and the rest are modes
 // 3-10.  Mode 11 stores both endpoints in 10 bits; modes 12-14 store endpoint 0 in n = 11, 12, 16 bits -- its low ten in the
@@ -222,7 +199,7 @@ static __device__ __forceinline__ bool decode_bc6h(const uint32_t (&b)[4], uint3
     uint32_t u0[3], u1[3];
 #pragma unroll
     for (int c = 0; c < 3; ++c) {
-        const uint32_t low = bc6h_bits(b, 5 + 10 * c, 10), grp = bc6h_bits(b, 35 + 10 * c, 10);
+        const uint32_t low = bc_bits(b, 5 + 10 * c, 10), grp = bc_bits(b, 35 + 10 * c, 10);
         const uint32_t rev = __brev(grp) >> 22;  // bit j = the group's bit 9 - j = endpoint 0's bit 10 + j
         const uint32_t e0 = low | (rev & ((1u << (n - 10u)) - 1u)) << 10;
         const int32_t delta = (int32_t)(grp << (32u - db)) >> (32u - db);
@@ -232,7 +209,7 @@ static __device__ __forceinline__ bool decode_bc6h(const uint32_t (&b)[4], uint3
     }
 #pragma unroll
     for (int t = 0; t < 16; ++t) {
-        const uint32_t w = bc6h_w4(t == 0 ? bc6h_bits(b, 65, 3) : bc6h_bits(b, 68 + 4 * (t - 1), 4));
+        const uint32_t w = bc6h_w4(t == 0 ? bc_bits(b, 65, 3) : bc_bits(b, 68 + 4 * (t - 1), 4));
         rg[t] = bc6h_entry(u0[0], u1[0], w) | bc6h_entry(u0[1], u1[1], w) << 16;
         bl[t] = bc6h_entry(u0[2], u1[2], w);
     }
@@ -250,67 +227,22 @@ static __device__ __forceinline__ bool bc6h_decode_block(const char *p, uint32_t
 // the exact f32 value of a half bit pattern
 static __device__ __forceinline__ float half_value(uint32_t bits) { return (float)__builtin_bit_cast(_Float16, (uint16_t)bits); }
 
-// Sum / maximum over the wave's 64 lanes, in every lane
-static __device__ __forceinline__ unsigned long long wave_sum(unsigned long long v)
-{
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-        const uint32_t lo = (uint32_t)__shfl_xor((int)(uint32_t)v, off), hi = (uint32_t)__shfl_xor((int)(uint32_t)(v >> 32), off);
-        v += (unsigned long long)hi << 32 | lo;
-    }
-    return v;
-}
-static __device__ __forceinline__ uint32_t wave_max(uint32_t v)
-{
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v = max(v, (uint32_t)__shfl_xor((int)v, off));
-    return v;
-}
-
 // Writes dst[0..2] = R, G, B.  COUNT: the workgroup's undecoded blocks go to a.partials[blockIdx.x]
 template <bool NT, bool COUNT>
 __global__ __launch_bounds__(256) void bc6h_decode_kernel(const BcDecodeArgs a)
 {
-    [[maybe_unused]] __shared__ unsigned long long red[4];  // per wave
-    const uint32_t total = a.bx * a.by;
-    const uint32_t edge_i = (a.w & 3u) ? a.bx - 1 : 0xffffffffu, edge_j = (a.h & 3u) ? a.by - 1 : 0xffffffffu;
-    uint32_t undecoded = 0u;
-    for (uint32_t idx = blockIdx.x * 256u + threadIdx.x; idx < total; idx += gridDim.x * 256u) {
-        const uint32_t j = idx / a.bx, i = idx - j * a.bx;
-        // wave-uniform: a wave that holds no edge block stores whole quads and all four rows
-        const bool wave_edge = __any(i == edge_i || j == edge_j) != 0;
+    [[maybe_unused]] __shared__ unsigned long long red[4][1];  // per wave
+    const BcWalk k = bc_walk(a.w, a.h, a.bx, a.by);
+    unsigned long long undecoded[1] = { 0ull };
+    for (uint32_t idx = blockIdx.x * 256u + threadIdx.x; idx < k.total; idx += gridDim.x * 256u) {
+        uint32_t i, j;
+        const bool wave_edge = bc_block_of(k, idx, i, j);
         uint32_t rg[16], bl[16];
         const bool skipped = bc6h_decode_block<NT>(a.src + (size_t)j * a.row_pitch + (size_t)i * 16, rg, bl);
-        if constexpr (COUNT) undecoded += skipped ? 1u : 0u;
-        const uint32_t cols = wave_edge ? min(a.w - 4u * i, 4u) : 4u, rows = wave_edge ? min(a.h - 4u * j, 4u) : 4u;
-#pragma unroll
-        for (int y = 0; y < 4; ++y) {
-            if (wave_edge && (uint32_t)y >= rows) break;
-#pragma unroll
-            for (int c = 0; c < 3; ++c) {
-                float *row = a.dst[c] + (size_t)(4u * j + y) * a.dst_pitch + 4u * i;
-                bc_f4 v;
-#pragma unroll
-                for (int x = 0; x < 4; ++x) {
-                    const int t = 4 * y + x;
-                    v[x] = half_value(c == 0 ? rg[t] & 0xffffu : c == 1 ? rg[t] >> 16 : bl[t]);
-                }
-                if (!wave_edge || cols == 4u) {
-                    st_policy<NT>(reinterpret_cast<bc_f4 *>(row), v);
-                } else {
-#pragma unroll
-                    for (int x = 0; x < 3; ++x)
-                        if ((uint32_t)x < cols) st_policy<NT>(row + x, v[x]);
-                }
-            }
-        }
+        if constexpr (COUNT) undecoded[0] += skipped ? 1u : 0u;
+        bc_store_planes<3, NT>(a, i, j, wave_edge, [&](int c, int t) { return half_value(c == 0 ? rg[t] & 0xffffu : c == 1 ? rg[t] >> 16 : bl[t]); });
     }
-    if constexpr (COUNT) {
-        const unsigned long long n = wave_sum(undecoded);
-        if ((threadIdx.x & 63u) == 0u) red[threadIdx.x >> 6] = n;
-        __syncthreads();
-        if (threadIdx.x == 0) a.partials[blockIdx.x] = red[0] + red[1] + red[2] + red[3];
-    }
+    if constexpr (COUNT) bc_fold_record<1, 0x1u>(undecoded, red, a.partials + blockIdx.x);
 }
 
 // ---------------------------------------------------------------- the error of an encoding
@@ -323,13 +255,12 @@ __global__ __launch_bounds__(256) void bc6h_compare_kernel(Operand r, Operand g,
     __shared__ unsigned long long red[4][KC_BC_REC_WORDS];  // per wave
     constexpr uint32_t CH = 0x7u;
     const Operand op[4] = { r, g, b, Operand{ nullptr, 0, 1.0f } };
-    const uint32_t total = a.bx * a.by;
-    const uint32_t edge_i = (a.w & 3u) ? a.bx - 1 : 0xffffffffu, edge_j = (a.h & 3u) ? a.by - 1 : 0xffffffffu;
+    const BcWalk k = bc_walk(a.w, a.h, a.bx, a.by);
     unsigned long long sse[3] = { 0ull, 0ull, 0ull };
     uint32_t mx[3] = { 0u, 0u, 0u }, undecoded = 0u;
-    for (uint32_t idx = blockIdx.x * 256u + threadIdx.x; idx < total; idx += gridDim.x * 256u) {
-        const uint32_t j = idx / a.bx, i = idx - j * a.bx;
-        const bool wave_edge = __any(i == edge_i || j == edge_j) != 0;
+    for (uint32_t idx = blockIdx.x * 256u + threadIdx.x; idx < k.total; idx += gridDim.x * 256u) {
+        uint32_t i, j;
+        const bool wave_edge = bc_block_of(k, idx, i, j);
         uint32_t rg[16], bl[16];
 #pragma unroll
         for (int y = 0; y < 4; ++y) {
@@ -352,51 +283,25 @@ __global__ __launch_bounds__(256) void bc6h_compare_kernel(Operand r, Operand g,
             }
         }
     }
-    // the wave, then the workgroup's four waves through LDS: one record per workgroup
     unsigned long long val[KC_BC_REC_WORDS];
 #pragma unroll
-    for (uint32_t k = 0; k < KC_BC_REC_WORDS; ++k) val[k] = 0ull;
+    for (uint32_t w = 0; w < KC_BC_REC_WORDS; ++w) val[w] = 0ull;
 #pragma unroll
-    for (int c = 0; c < 3; ++c) {
-        val[c] = wave_sum(sse[c]);
-        val[4 + c] = wave_max(mx[c]);
-    }
-    val[8] = wave_sum(undecoded);
-    if ((threadIdx.x & 63u) == 0u) {
-#pragma unroll
-        for (uint32_t k = 0; k < KC_BC_REC_WORDS; ++k) red[threadIdx.x >> 6][k] = val[k];
-    }
-    __syncthreads();
-    if (threadIdx.x < KC_BC_REC_WORDS) {
-        const uint32_t k = threadIdx.x;
-        const unsigned long long r0 = red[0][k], r1 = red[1][k], r2 = red[2][k], r3 = red[3][k];
-        partials[(size_t)blockIdx.x * KC_BC_REC_WORDS + k] = k >= 4 && k < 8 ? max(max(r0, r1), max(r2, r3)) : r0 + r1 + r2 + r3;
-    }
+    for (int c = 0; c < 3; ++c) val[c] = sse[c], val[4 + c] = mx[c];
+    val[8] = undecoded;
+    bc_fold_record<KC_BC_REC_WORDS, 0x177u>(val, red, partials + (size_t)blockIdx.x * KC_BC_REC_WORDS);  // words 0-2, 4-6 and 8
 }
 
 // ---------------------------------------------------------------- launchers
-static BcBlockArgs block_args(char *blocks, uint64_t row_pitch, uint32_t w, uint32_t h)
-{
-    BcBlockArgs a;
-    a.dst = blocks;
-    a.row_pitch = row_pitch;
-    a.w = w;
-    a.h = h;
-    a.bx = (w + 3) / 4;
-    a.by = (h + 3) / 4;
-    return a;
-}
-
 hipError_t launch_bc6h_encode(const Operand op[4], int gray, char *dst, uint64_t row_pitch, uint32_t w, uint32_t h, uint32_t nt_mask,
                               hipStream_t s)
 {
-    const BcBlockArgs a = block_args(dst, row_pitch, w, h);
+    const BcBlockArgs a = bc_block_args(dst, row_pitch, w, h);
     const uint64_t total = (uint64_t)a.bx * a.by;
     if (total == 0) return hipSuccess;
-    uint64_t blocks = (total + 255) / 256;
-    if (blocks > grid_cap(1u << 30)) blocks = grid_cap(1u << 30);
-    if ((nt_mask & 0xffu) != 0) bc6h_encode_kernel<true><<<dim3((unsigned)blocks), 256, 0, s>>>(op[0], op[1], op[2], gray, a);
-    else bc6h_encode_kernel<false><<<dim3((unsigned)blocks), 256, 0, s>>>(op[0], op[1], op[2], gray, a);
+    const uint32_t blocks = bc_grid(total, 1u << 30);
+    if ((nt_mask & 0xffu) != 0) bc6h_encode_kernel<true><<<dim3(blocks), 256, 0, s>>>(op[0], op[1], op[2], gray, a);
+    else bc6h_encode_kernel<false><<<dim3(blocks), 256, 0, s>>>(op[0], op[1], op[2], gray, a);
     return hipGetLastError();
 }
 
@@ -420,7 +325,7 @@ hipError_t launch_bc6h_decode(const BcDecodeArgs &a, bool count, uint32_t nt_mas
 hipError_t launch_bc6h_compare(const Operand op[4], int gray, const char *blocks, uint64_t row_pitch, uint32_t w, uint32_t h, uint32_t nt_mask,
                                uint32_t groups, unsigned long long *partials, unsigned long long *result, hipStream_t s)
 {
-    const BcBlockArgs a = block_args(const_cast<char *>(blocks), row_pitch, w, h);  // read only here
+    const BcBlockArgs a = bc_block_args(const_cast<char *>(blocks), row_pitch, w, h);  // read only here
     if (groups == 0 || a.bx == 0 || a.by == 0 || !partials || !result) return hipErrorInvalidValue;
     if ((nt_mask & 0xffu) != 0) bc6h_compare_kernel<true><<<dim3(groups), 256, 0, s>>>(op[0], op[1], op[2], gray, a, partials);
     else bc6h_compare_kernel<false><<<dim3(groups), 256, 0, s>>>(op[0], op[1], op[2], gray, a, partials);

@@ -1,6 +1,6 @@
 // BC7 (kc_image_to_bc with KC_BC7, bc.cpp): the image as kc_image_to_u8 writes it -> 16-byte BC7 blocks of the single-subset
 // modes 6 and 5, by the integer rules of include/kanter_core_amd.h (tests/bc7_ref.py is the same rules in numpy).  The stream is
-// bc_encode_kernel's (bc.hip; the loaders and the quantiser are bc_blocks.h's): one thread per 4x4 block, a 16-byte load per
+// bc_encode_kernel's (bc.hip), built from the same steps of bc_blocks.h: one thread per 4x4 block, a 16-byte load per
 // plane, row and lane, texels kept as rb = R | B << 16 and ga = G | A << 16, one 16-byte store.  Both modes are evaluated in the
 // thread, on the packed lanes: a packed 16-bit subtract and a 16-bit dot product give the squared distance of two channels at
 // once, and the palette entries are made in the outer loop of the exhaustive search, never held.
@@ -9,18 +9,7 @@
 namespace kc {
 
 #include "streaming.h"  // grid_cap, ld_policy, quant_u8 / quant_u8_srgb
-#include "bc_blocks.h"  // the row loaders, the quantiser, the column clamp and BcBlockArgs: shared with bc.hip
-
-static __device__ __forceinline__ uint32_t pk_sub(uint32_t a, uint32_t b) { return __builtin_bit_cast(uint32_t, as_s2(a) - as_s2(b)); }
-static __device__ __forceinline__ uint32_t pk_min(uint32_t a, uint32_t b)
-{
-    return __builtin_bit_cast(uint32_t, __builtin_elementwise_min(as_h2(a), as_h2(b)));
-}
-static __device__ __forceinline__ uint32_t pk_max(uint32_t a, uint32_t b)
-{
-    return __builtin_bit_cast(uint32_t, __builtin_elementwise_max(as_h2(a), as_h2(b)));
-}
-static __device__ __forceinline__ int32_t dot2(uint32_t a, uint32_t b, int32_t c) { return __builtin_amdgcn_sdot2(as_s2(a), as_s2(b), c, false); }
+#include "bc_blocks.h"  // BcBlockArgs, the grid, the block walk, the row loaders and the quantiser: shared by the block-compression units
 
 // interp of both 16-bit lanes: ((64 - w) e0 + w e1 + 32) >> 6; a lane's sum stays below 2^14, so nothing crosses into the other
 static __device__ __forceinline__ uint32_t pk_interp(uint32_t e0, uint32_t e1, uint32_t w)
@@ -219,32 +208,17 @@ __global__ __launch_bounds__(256) void bc7_encode_kernel(Operand r, Operand g, O
     __shared__ uint32_t srgb_t[SRGB ? 257 : 1];
     constexpr uint32_t CH = 0xfu;  // all four channels
     const Operand op[4] = { r, g, b, al };
-    const uint32_t total = a.bx * a.by;
-    // edge blocks: the last block column when the width is not a multiple of 4, the last block row likewise
-    const uint32_t edge_i = (a.w & 3u) ? a.bx - 1 : 0xffffffffu, edge_j = (a.h & 3u) ? a.by - 1 : 0xffffffffu;
+    const BcWalk k = bc_walk(a.w, a.h, a.bx, a.by);
     uint32_t idx = blockIdx.x * 256u + threadIdx.x;
-    auto block_of = [&](uint32_t n, uint32_t &i, uint32_t &j, bool &wave_edge) {
-        j = n / a.bx;
-        i = n - j * a.bx;
-        // wave-uniform: a wave that holds no edge block skips the clamps
-        wave_edge = __any(n < total && (i == edge_i || j == edge_j)) != 0;
-    };
-    auto store = [&](const uint32_t (&rb)[16], const uint32_t (&ga)[16], uint32_t i, uint32_t j) {
-        *reinterpret_cast<bc_u4 *>(a.dst + (size_t)j * a.row_pitch + (size_t)i * 16) = encode_bc7(rb, ga);
-    };
     if constexpr (SRGB) {
-        // As in bc_encode_kernel: the first block's first row of loads goes out BEFORE the threshold table is staged (a global
-        // read and a barrier that every thread of the workgroup takes, in range or not); the table arrives while they are in
-        // flight.
-        const bool in_range = idx < total;
-        uint32_t i = 0u, j = 0u;
-        bool we = false;
-        block_of(in_range ? idx : 0u, i, j, we);
+        // The first block's first row of loads goes out BEFORE the threshold table is staged (a global read and a barrier that
+        // every thread of the workgroup takes, in range or not), as in to_u8_kernel: the table arrives while they are in flight.
+        const bool in_range = idx < k.total;
+        uint32_t i, j;
+        const bool we = bc_block_of(k, idx, i, j);
         bc_f4 v[4];
         if (in_range) bc_load_row<CH, NT>(op, gray, a, i, j, 0, we, v);
-        srgb_t[threadIdx.x] = kSrgbThresholdBits[threadIdx.x];  // 256 threads
-        if (threadIdx.x == 0) srgb_t[256] = 0xffffffffu;         // sentinel: nothing is >= it
-        __syncthreads();
+        bc_stage_srgb(srgb_t);
         if (!in_range) return;
         uint32_t rb[16], ga[16];
         bc_quantise_row<CH, SRGB>(v, gray, 0, srgb_t, rb, ga);
@@ -254,13 +228,12 @@ __global__ __launch_bounds__(256) void bc7_encode_kernel(Operand r, Operand g, O
             bc_quantise_row<CH, SRGB>(v, gray, y, srgb_t, rb, ga);
         }
         if (we) bc_clamp_columns(a, i, rb, ga);
-        store(rb, ga, i, j);
+        *reinterpret_cast<bc_u4 *>(a.dst + (size_t)j * a.row_pitch + (size_t)i * 16) = encode_bc7(rb, ga);
         idx += gridDim.x * 256u;
     }
-    for (; idx < total; idx += gridDim.x * 256u) {
+    for (; idx < k.total; idx += gridDim.x * 256u) {
         uint32_t i, j;
-        bool we;
-        block_of(idx, i, j, we);
+        const bool we = bc_block_of(k, idx, i, j);
         uint32_t rb[16], ga[16];
 #pragma unroll
         for (int y = 0; y < 4; ++y) {
@@ -269,26 +242,19 @@ __global__ __launch_bounds__(256) void bc7_encode_kernel(Operand r, Operand g, O
             bc_quantise_row<CH, SRGB>(v, gray, y, srgb_t, rb, ga);
         }
         if (we) bc_clamp_columns(a, i, rb, ga);
-        store(rb, ga, i, j);
+        *reinterpret_cast<bc_u4 *>(a.dst + (size_t)j * a.row_pitch + (size_t)i * 16) = encode_bc7(rb, ga);
     }
 }
 
 hipError_t launch_bc7_encode(int srgb, const Operand op[4], int gray, char *dst, uint64_t row_pitch, uint32_t w, uint32_t h, uint32_t nt_mask,
                              hipStream_t s)
 {
-    BcBlockArgs a;
-    a.dst = dst;
-    a.row_pitch = row_pitch;
-    a.w = w;
-    a.h = h;
-    a.bx = (w + 3) / 4;
-    a.by = (h + 3) / 4;
+    const BcBlockArgs a = bc_block_args(dst, row_pitch, w, h);
     const uint64_t total = (uint64_t)a.bx * a.by;
     if (total == 0) return hipSuccess;
-    uint64_t blocks = (total + 255) / 256;
-    if (blocks > grid_cap(1u << 30)) blocks = grid_cap(1u << 30);
+    const uint32_t blocks = bc_grid(total, 1u << 30);
     const bool nt = (nt_mask & 0xffu) != 0;
-#define KC_BC7(SR, NTL) bc7_encode_kernel<SR, NTL><<<dim3((unsigned)blocks), 256, 0, s>>>(op[0], op[1], op[2], op[3], gray, a)
+#define KC_BC7(SR, NTL) bc7_encode_kernel<SR, NTL><<<dim3(blocks), 256, 0, s>>>(op[0], op[1], op[2], op[3], gray, a)
     if (srgb) {
         if (nt) KC_BC7(true, true);
         else KC_BC7(true, false);

@@ -1,6 +1,9 @@
-// What the block encoder kernels share -- bc.hip (BC1, BC3, BC4, BC5) and bc7.hip: the packed types, the row loaders, the
-// quantiser, the column clamp and the kernels' arguments.  A thread holds its block's texels as packed 16-bit lanes,
-// rb = R | B << 16 and ga = G | A << 16.
+// What the block-compression units share -- bc.hip (BC1, BC3, BC4, BC5), bc7.hip, bc6h.hip and bc_decode.hip: the packed types,
+// the kernels' arguments and grid, the walk over the blocks with its edge rule, the row loaders, the 8-bit quantiser, the column
+// clamp, the staging of the sRGB table, the decoders' plane-row store, and the fold of a workgroup's counts and sums into one
+// record.  The encoder and comparison kernels write their grid-stride loops out over these steps: the loop as one shared
+// function compiled the sRGB forms to slower code (see DESIGN, "Where the family's code lies").  A thread holds its block's texels as packed 16-bit
+// lanes, rb = R | B << 16 and ga = G | A << 16 (BC6H: rg = R | G << 16 and bl = B, in the same two arrays).
 // Included inside namespace kc after streaming.h; every definition is static, each unit keeps its own copy.
 #pragma once
 
@@ -13,6 +16,74 @@ typedef uint16_t bc_h2 __attribute__((ext_vector_type(2)));
 static __device__ __forceinline__ bc_s2 as_s2(uint32_t x) { return __builtin_bit_cast(bc_s2, x); }
 static __device__ __forceinline__ bc_h2 as_h2(uint32_t x) { return __builtin_bit_cast(bc_h2, x); }
 
+// Both 16-bit lanes of a word at once: difference, unsigned minimum and maximum, and the signed dot product a.b + c
+static __device__ __forceinline__ uint32_t pk_sub(uint32_t a, uint32_t b) { return __builtin_bit_cast(uint32_t, as_s2(a) - as_s2(b)); }
+static __device__ __forceinline__ uint32_t pk_min(uint32_t a, uint32_t b)
+{
+    return __builtin_bit_cast(uint32_t, __builtin_elementwise_min(as_h2(a), as_h2(b)));
+}
+static __device__ __forceinline__ uint32_t pk_max(uint32_t a, uint32_t b)
+{
+    return __builtin_bit_cast(uint32_t, __builtin_elementwise_max(as_h2(a), as_h2(b)));
+}
+static __device__ __forceinline__ int32_t dot2(uint32_t a, uint32_t b, int32_t c) { return __builtin_amdgcn_sdot2(as_s2(a), as_s2(b), c, false); }
+
+// n bits of the 128-bit block from bit `at`, LSB first; `at` and n are constants after unrolling
+static __device__ __forceinline__ uint32_t bc_bits(const uint32_t (&b)[4], int at, int n)
+{
+    const int w = at >> 5, s = at & 31;
+    uint32_t v = b[w] >> s;
+    if (s + n > 32) v |= b[w + 1] << (32 - s);
+    return v & ((1u << n) - 1u);
+}
+
+// ---------------------------------------------------------------- arguments and grid (host)
+struct BcBlockArgs {
+    char *dst;           // the blocks: written by the encoders, read by the comparisons
+    uint64_t row_pitch;  // bytes between block rows
+    uint32_t w, h, bx, by;
+};
+
+static inline BcBlockArgs bc_block_args(char *blocks, uint64_t row_pitch, uint32_t w, uint32_t h)
+{
+    BcBlockArgs a;
+    a.dst = blocks;
+    a.row_pitch = row_pitch;
+    a.w = w;
+    a.h = h;
+    a.bx = (w + 3) / 4;
+    a.by = (h + 3) / 4;
+    return a;
+}
+
+// Workgroups of 256 threads for `total` blocks: one block a thread up to `cap` workgroups (the tune_cap option overrides it), the
+// grid-stride loop takes the rest; at least one
+static inline uint32_t bc_grid(uint64_t total, uint32_t cap)
+{
+    return (uint32_t)std::max<uint64_t>(std::min<uint64_t>((total + 255) / 256, grid_cap(cap)), 1);
+}
+
+// ---------------------------------------------------------------- the walk over the blocks
+// Edge blocks: the last block column when the width is not a multiple of 4, the last block row likewise
+struct BcWalk {
+    uint32_t total, bx, edge_i, edge_j;
+};
+
+static __device__ __forceinline__ BcWalk bc_walk(uint32_t w, uint32_t h, uint32_t bx, uint32_t by)
+{
+    return BcWalk{ bx * by, bx, (w & 3u) ? bx - 1 : 0xffffffffu, (h & 3u) ? by - 1 : 0xffffffffu };
+}
+
+// Block n in row order: its column i and row j.  Returns whether the wave holds an edge block (n >= total: no block, as the
+// lanes that only accompany their workgroup to a barrier): wave-uniform, so a wave without one skips the clamps and the clipping.
+static __device__ __forceinline__ bool bc_block_of(const BcWalk &k, uint32_t n, uint32_t &i, uint32_t &j)
+{
+    j = n / k.bx;
+    i = n - j * k.bx;
+    return __any(n < k.total && (i == k.edge_i || j == k.edge_j)) != 0;
+}
+
+// ---------------------------------------------------------------- rows of the source image
 template <bool NT>
 static __device__ __forceinline__ bc_f4 bc_load(const Operand &o, uint32_t row, uint32_t q)
 {
@@ -26,12 +97,6 @@ static __device__ __forceinline__ uint32_t bc_quant(float v, int c, const uint32
     return (SRGB && c < 3) ? quant_u8_srgb(v, srgb_tab) : quant_u8(v);  // alpha stays linear
 }
 
-struct BcBlockArgs {
-    char *dst;
-    uint64_t row_pitch;  // bytes between block rows
-    uint32_t w, h, bx, by;
-};
-
 // Row y of a block's texels, raw: a 16-byte load per channel the format reads (CH: bit c = channel c; Gray: the plane once, for
 // R; a constant: none)
 template <uint32_t CH, bool NT>
@@ -39,7 +104,7 @@ static __device__ __forceinline__ void bc_load_row(const Operand (&op)[4], int g
                                                    bool wave_edge, bc_f4 (&v)[4])
 {
     uint32_t row = 4 * j + y;
-    if (wave_edge) row = min(row, a.h - 1);  // bottom edge blocks repeat the last row
+    if (wave_edge) row = min(row, a.h - 1);  // bottom edge blocks repeat the last row: in bounds
 #pragma unroll
     for (int c = 0; c < 4; ++c) {
         if (!((CH >> c) & 1u)) continue;
@@ -65,6 +130,7 @@ static __device__ __forceinline__ void bc_quantise_row(const bc_f4 (&v)[4], int 
     }
 }
 
+
 // Right edge blocks: the columns past the width repeat the last one
 static __device__ __forceinline__ void bc_clamp_columns(const BcBlockArgs &a, uint32_t i, uint32_t (&rb)[16], uint32_t (&ga)[16])
 {
@@ -77,4 +143,84 @@ static __device__ __forceinline__ void bc_clamp_columns(const BcBlockArgs &a, ui
                 rb[4 * y + x] = rb[4 * y + x - 1];
                 ga[4 * y + x] = ga[4 * y + x - 1];
             }
+}
+
+// The sRGB threshold table into LDS (257 words), by the workgroup's 256 threads: a global read and a barrier that every thread
+// takes
+static __device__ __forceinline__ void bc_stage_srgb(uint32_t *srgb_t)
+{
+    srgb_t[threadIdx.x] = kSrgbThresholdBits[threadIdx.x];
+    if (threadIdx.x == 0) srgb_t[256] = 0xffffffffu;  // sentinel: nothing is >= it
+    __syncthreads();
+}
+
+// ---------------------------------------------------------------- the decoders' store
+// The four pixel rows of block (i, j) into the first NP planes of a.dst, texel(c, t) the f32 value of channel c at texel t: a
+// float4 per plane row in a wave without an edge block (a wave writes 1 KiB of contiguous bytes per plane row), columns and
+// rows clipped to the image otherwise
+template <int NP, bool NT, class Texel>
+static __device__ __forceinline__ void bc_store_planes(const BcDecodeArgs &a, uint32_t i, uint32_t j, bool wave_edge, Texel texel)
+{
+    const uint32_t cols = wave_edge ? min(a.w - 4u * i, 4u) : 4u, rows = wave_edge ? min(a.h - 4u * j, 4u) : 4u;
+#pragma unroll
+    for (int y = 0; y < 4; ++y) {
+        if (wave_edge && (uint32_t)y >= rows) break;
+#pragma unroll
+        for (int c = 0; c < NP; ++c) {
+            float *row = a.dst[c] + (size_t)(4u * j + y) * a.dst_pitch + 4u * i;
+            bc_f4 v;
+#pragma unroll
+            for (int x = 0; x < 4; ++x) v[x] = texel(c, 4 * y + x);
+            if (!wave_edge || cols == 4u) {
+                st_policy<NT>(reinterpret_cast<bc_f4 *>(row), v);
+            } else {
+#pragma unroll
+                for (int x = 0; x < 3; ++x)
+                    if ((uint32_t)x < cols) st_policy<NT>(row + x, v[x]);
+            }
+        }
+    }
+}
+
+// ---------------------------------------------------------------- counts and sums of a workgroup
+// Sum / maximum over the wave's 64 lanes, in every lane
+static __device__ __forceinline__ unsigned long long wave_sum(unsigned long long v)
+{
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+        const uint32_t lo = (uint32_t)__shfl_xor((int)(uint32_t)v, off), hi = (uint32_t)__shfl_xor((int)(uint32_t)(v >> 32), off);
+        v += (unsigned long long)hi << 32 | lo;
+    }
+    return v;
+}
+static __device__ __forceinline__ uint32_t wave_max(uint32_t v)
+{
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) v = max(v, (uint32_t)__shfl_xor((int)v, off));
+    return v;
+}
+
+// The threads' val[0..WORDS) to one record of the workgroup at out[0..WORDS): the wave (shuffles), then the workgroup's four
+// waves through LDS (red).  Words 4..7 are maxima of 32-bit values, the others sums; USED: bit k clear = word k is 0 in every
+// thread and skips the wave's fold.  The error records have KC_BC_REC_WORDS words, a decoder's count one.
+template <uint32_t WORDS, uint32_t USED>
+static __device__ __forceinline__ void bc_fold_record(unsigned long long (&val)[WORDS], unsigned long long (&red)[4][WORDS],
+                                                      unsigned long long *out)
+{
+#pragma unroll
+    for (uint32_t k = 0; k < WORDS; ++k) {
+        if (!((USED >> k) & 1u)) continue;
+        if (k >= 4 && k < 8) val[k] = wave_max((uint32_t)val[k]);
+        else val[k] = wave_sum(val[k]);
+    }
+    if ((threadIdx.x & 63u) == 0u) {
+#pragma unroll
+        for (uint32_t k = 0; k < WORDS; ++k) red[threadIdx.x >> 6][k] = val[k];
+    }
+    __syncthreads();
+    if (threadIdx.x < WORDS) {
+        const uint32_t k = threadIdx.x;
+        const unsigned long long r0 = red[0][k], r1 = red[1][k], r2 = red[2][k], r3 = red[3][k];
+        out[k] = k >= 4 && k < 8 ? max(max(r0, r1), max(r2, r3)) : r0 + r1 + r2 + r3;
+    }
 }

@@ -24,7 +24,8 @@ static int bcd_check_flags(int format, uint32_t flags, const char *who)
         set_error(std::string(who) + ": flags other than KC_BC_GRAY (no transfer function is applied on decode)");
         return KC_ERR_UNSUPPORTED;
     }
-    if ((flags & KC_BC_GRAY) && format != KC_BC4) {
+    const BcFormat *f = bc_format(format);
+    if ((flags & KC_BC_GRAY) && !(f && f->planes == 1)) {  // a Gray image is one plane: BC4
         set_error(std::string(who) + ": KC_BC_GRAY is for BC4 only");
         return KC_ERR_UNSUPPORTED;
     }
@@ -47,15 +48,15 @@ static int bc_decode(const char *src, size_t row_pitch, uint32_t w, uint32_t h, 
                      bool *counted)
 {
     Context &c = ctx();
-    const int n_res = format == KC_BC4 ? 1 : format == KC_BC5 ? 2 : format == KC_BC6H ? 3 : 4;  // BC6H: alpha is the constant 1
-    const int n = gray ? 1 : 4;
+    const BcFormat &f = *bc_format(format);  // the entry points have refused an unknown format
+    const int n_res = f.planes, n = gray ? 1 : 4;
     kc_plane *p[4] = { nullptr, nullptr, nullptr, nullptr };
     int s = KC_OK;
     for (int i = 0; i < n && s == KC_OK; ++i) {
         if (i < n_res) s = plane_new_mem(w, h, &p[i]);
         else p[i] = plane_new_const(w, h, i == 3 ? 1.0f : 0.0f);  // the sampling convention: missing G, B = 0, A = 1
     }
-    const bool count = want_count && (format == KC_BC7 || format == KC_BC6H);
+    const bool count = want_count && f.counts_undecoded;
     BcDecodeArgs a{};
     uint32_t groups = 0;
     if (s == KC_OK) {
@@ -75,10 +76,8 @@ static int bc_decode(const char *src, size_t row_pitch, uint32_t w, uint32_t h, 
         }
     }
     if (s == KC_OK) {
-        const uint64_t in_bytes = (uint64_t)a.bx * a.by * bc_block_bytes(format), out_bytes = (uint64_t)w * h * 4 * n_res;
-        const uint32_t nt_mask = cache_policy_mask(in_bytes, out_bytes, 1);
-        hipError_t e = format == KC_BC6H ? launch_bc6h_decode(a, count, nt_mask, groups, c.stream)
-                                         : launch_bc_decode(format, a, count, nt_mask, groups, c.stream);
+        const uint64_t in_bytes = bc_level_bytes(w, h, f), out_bytes = (uint64_t)w * h * 4 * n_res;
+        hipError_t e = bc_launch_decode(format, a, count, cache_policy_mask(in_bytes, out_bytes, 1), groups, c.stream);
         if (e != hipSuccess) s = hip_fail(e, "launch_bc_decode");
         else {
             c.launches += count ? 2 : 1;
@@ -95,29 +94,27 @@ int image_from_bc(const uint8_t *host, size_t host_bytes, uint32_t w, uint32_t h
                   uint64_t *undecoded_blocks)
 {
     KC_TRY(bcd_check_flags(format, flags, "kc_image_from_bc"));
-    const size_t bb = bc_block_bytes(format);
-    if (bb == 0) return bcd_refuse("kc_image_from_bc", "unknown format");
+    const BcFormat *f = bc_format(format);
+    if (!f) return bcd_refuse("kc_image_from_bc", "unknown format");
     if (!host || !out) return bcd_refuse("kc_image_from_bc", "NULL host buffer or output");
     if (w == 0 || h == 0) return bcd_refuse("kc_image_from_bc", "zero extent");
-    const uint64_t bx = ((uint64_t)w + 3) / 4, by = ((uint64_t)h + 3) / 4;
-    if (bx * by > (1ull << 31)) return bcd_refuse("kc_image_from_bc", "image too large: more than 2^31 blocks");
-    const size_t nbytes = (size_t)(bx * by) * bb;
+    uint64_t bx = 0, by = 0;
+    KC_TRY(bc_block_count(w, h, "kc_image_from_bc", &bx, &by));
+    const size_t nbytes = bc_level_bytes(w, h, *f);
     if (host_bytes < nbytes) return bcd_refuse("kc_image_from_bc", "host_bytes < blocks * block bytes");
     KC_TRY(need_init());
     Context &c = ctx();
     std::lock_guard<std::recursive_mutex> lk(c.mu);
-    const size_t block = (nbytes + 255) / 256 * 256;
-    void *staging = nullptr;
-    KC_TRY(pool_alloc(block, &staging));
+    PoolStaging staging;
+    KC_TRY(staging.alloc(nbytes));
     kc_image *img = nullptr;
     bool counted = false;
-    hipError_t e = hipMemcpyAsync(staging, host, nbytes, hipMemcpyHostToDevice, c.stream);
-    int s = e == hipSuccess ? bc_decode((const char *)staging, (size_t)bx * bb, w, h, format, (flags & KC_BC_GRAY) != 0, undecoded_blocks != nullptr,
-                                        &img, &counted)
+    hipError_t e = hipMemcpyAsync(staging.ptr, host, nbytes, hipMemcpyHostToDevice, c.stream);
+    int s = e == hipSuccess ? bc_decode((const char *)staging.ptr, (size_t)bx * f->block_bytes, w, h, format, (flags & KC_BC_GRAY) != 0,
+                                        undecoded_blocks != nullptr, &img, &counted)
                             : KC_OK;
     if (s == KC_OK && e == hipSuccess && counted) s = bcd_fetch(1);
     if (e == hipSuccess) e = hipStreamSynchronize(c.stream);  // the caller's bytes have been read
-    pool_free(staging, block);
     if (s == KC_OK && e != hipSuccess) s = hip_fail(e, "image_from_bc");
     if (s != KC_OK) {
         image_release(img);
@@ -135,14 +132,12 @@ int image_from_bc_device(const kc_bc_image *src, uint32_t flags, void *hip_strea
     KC_TRY(bc_image_validate(src, nullptr));
     Context &c = ctx();
     std::lock_guard<std::recursive_mutex> lk(c.mu);
-    hipStream_t hs = (hipStream_t)hip_stream;
-    const bool edges = hs && hs != c.stream;
-    if (edges) KC_TRY(stream_edge(hs, c.stream));
     kc_image *img = nullptr;
     bool counted = false;
-    int s = bc_decode((const char *)src->ptr, src->row_pitch_bytes, src->width, src->height, src->format, (flags & KC_BC_GRAY) != 0,
-                      undecoded_blocks != nullptr, &img, &counted);
-    if (s == KC_OK && edges) s = stream_edge(c.stream, hs);
+    int s = with_stream_edges(hip_stream, [&] {
+        return bc_decode((const char *)src->ptr, src->row_pitch_bytes, src->width, src->height, src->format, (flags & KC_BC_GRAY) != 0,
+                         undecoded_blocks != nullptr, &img, &counted);
+    });
     if (s == KC_OK && counted) s = bcd_fetch(1);
     if (s != KC_OK) {
         image_release(img);
@@ -159,28 +154,18 @@ int image_from_bc_device(const kc_bc_image *src, uint32_t flags, void *hip_strea
 static int bc_compare(kc_image *img, int format, uint32_t flags, const char *blocks, size_t row_pitch, kc_bc_error *out)
 {
     Context &c = ctx();
-    const bool rgba = img->is_rgba();
+    const BcFormat &f = *bc_format(format);  // the entry points have refused an unknown format
     Operand o[4];
-    for (int i = 0; i < 4; ++i) o[i] = rgba ? plane_operand(img->planes[i]) : i < 3 ? plane_operand(img->planes[0]) : Operand{ nullptr, 0, 1.0f };
-    const uint32_t mask = format == KC_BC1 || format == KC_BC6H ? 0x7u : format == KC_BC4 ? 0x1u : format == KC_BC5 ? 0x3u : 0xfu;
-    const float *seen[4] = { nullptr, nullptr, nullptr, nullptr };
-    uint32_t n_res = 0;  // distinct resident planes the launch reads
-    for (int i = 0; i < 4; ++i) {
-        if (!((mask >> i) & 1u) || !o[i].ptr) continue;
-        bool dup = false;
-        for (uint32_t k = 0; k < n_res; ++k) dup |= seen[k] == o[i].ptr;
-        if (!dup) seen[n_res++] = o[i].ptr;
-    }
+    const uint32_t n_res = bc_source_operands(img, f.channels, o);
     const uint32_t w = img->w(), h = img->h();
     const uint32_t groups = bc_compare_groups(w, h);
     KC_TRY(stats_buffers((size_t)groups * KC_BC_REC_WORDS * sizeof(unsigned long long)));
     const uint64_t in_bytes = (uint64_t)w * h * 4 * n_res;
-    const uint64_t blk_bytes = (uint64_t)((w + 3) / 4) * ((h + 3) / 4) * bc_block_bytes(format);
+    const uint64_t blk_bytes = bc_level_bytes(w, h, f);
     const uint32_t nt_mask = cache_policy_mask(in_bytes + blk_bytes, 0, n_res ? n_res : 1);
     unsigned long long *partials = (unsigned long long *)c.stats.partials;
-    hipError_t e = format == KC_BC6H ? launch_bc6h_compare(o, rgba ? 0 : 1, blocks, row_pitch, w, h, nt_mask, groups, partials, c.stats.result, c.stream)
-                                     : launch_bc_compare(format, (flags & KC_BC_SRGB) ? 1 : 0, o, rgba ? 0 : 1, blocks, row_pitch, w, h, nt_mask,
-                                                         groups, partials, c.stats.result, c.stream);
+    hipError_t e = bc_launch_compare(format, (flags & KC_BC_SRGB) != 0, o, img->is_rgba() ? 0 : 1, blocks, row_pitch, w, h, nt_mask, groups, partials,
+                                     c.stats.result, c.stream);
     if (e != hipSuccess) return hip_fail(e, "launch_bc_compare");
     c.launches += 2;
     c.alg_bytes += in_bytes + blk_bytes;
@@ -190,7 +175,7 @@ static int bc_compare(kc_image *img, int format, uint32_t flags, const char *blo
     std::memset(&r, 0, sizeof r);
     r.format = format;
     r.flags = flags;
-    r.channel_mask = mask;
+    r.channel_mask = f.channels;
     r.pixels = (uint64_t)w * h;
     for (int ch = 0; ch < 4; ++ch) {
         r.sse[ch] = res[ch];
@@ -204,7 +189,7 @@ static int bc_compare(kc_image *img, int format, uint32_t flags, const char *blo
 
 int image_bc_compare(kc_image *img, const kc_bc_image *blocks, uint32_t flags, kc_bc_error *out)
 {
-    KC_TRY(bc_check_flags(blocks ? blocks->format : 0, flags, "kc_image_bc_compare"));
+    KC_TRY(bc_check_flags(blocks ? blocks->format : 0, flags, KC_BC_SRGB, "kc_image_bc_compare"));
     if (!img || !out) return bcd_refuse("kc_image_bc_compare", "NULL image or output");
     KC_TRY(bc_image_validate(blocks, nullptr));
     if (img->w() != blocks->width || img->h() != blocks->height) return bcd_refuse("kc_image_bc_compare", "descriptor size differs from the image's");
@@ -216,32 +201,25 @@ int image_bc_compare(kc_image *img, const kc_bc_image *blocks, uint32_t flags, k
 
 int image_bc_error(kc_image *img, int format, uint32_t flags, kc_bc_error *out)
 {
-    KC_TRY(bc_check_flags(format, flags, "kc_image_bc_error"));
-    const size_t bb = bc_block_bytes(format);
-    if (bb == 0) return bcd_refuse("kc_image_bc_error", "unknown format");
+    KC_TRY(bc_check_flags(format, flags, KC_BC_SRGB, "kc_image_bc_error"));
+    const BcFormat *f = bc_format(format);
+    if (!f) return bcd_refuse("kc_image_bc_error", "unknown format");
     if (!img || !out) return bcd_refuse("kc_image_bc_error", "NULL image or output");
     KC_TRY(need_init());
     Context &c = ctx();
     std::lock_guard<std::recursive_mutex> lk(c.mu);
-    const uint64_t bx = ((uint64_t)img->w() + 3) / 4, by = ((uint64_t)img->h() + 3) / 4;
-    if (bx * by > (1ull << 31)) return bcd_refuse("kc_image_bc_error", "image too large: more than 2^31 blocks");
+    uint64_t bx = 0, by = 0;
+    KC_TRY(bc_block_count(img->w(), img->h(), "kc_image_bc_error", &bx, &by));
     KC_TRY(image_force(img));  // a pending fused chain runs first
-    const size_t nbytes = (size_t)(bx * by) * bb, block = (nbytes + 255) / 256 * 256;
-    void *staging = nullptr;
-    KC_TRY(pool_alloc(block, &staging));
-    int s = bc_encode(img, format, (flags & KC_BC_SRGB) != 0, (char *)staging, (size_t)bx * bb, c.stream);
-    if (s == KC_OK) s = bc_compare(img, format, flags, (const char *)staging, (size_t)bx * bb, out);  // waits: the staging is free after it
-    pool_free(staging, block);
-    return s;
+    PoolStaging staging;
+    KC_TRY(staging.alloc(bc_level_bytes(img->w(), img->h(), *f)));
+    const size_t row_pitch = (size_t)bx * f->block_bytes;
+    KC_TRY(bc_encode(img, format, (flags & KC_BC_SRGB) != 0, (char *)staging.ptr, row_pitch, c.stream));
+    return bc_compare(img, format, flags, (const char *)staging.ptr, row_pitch, out);  // waits: the staging is free after it
 }
 
 // ---------------------------------------------------------------- DDS input
 static uint32_t le32(const uint8_t *p) { return (uint32_t)p[0] | (uint32_t)p[1] << 8 | (uint32_t)p[2] << 16 | (uint32_t)p[3] << 24; }
-
-static constexpr uint32_t fourcc(char a, char b, char c, char d)
-{
-    return (uint32_t)(uint8_t)a | (uint32_t)(uint8_t)b << 8 | (uint32_t)(uint8_t)c << 16 | (uint32_t)(uint8_t)d << 24;
-}
 
 int dds_parse(const uint8_t *data, size_t bytes, kc_dds_info *info)
 {
@@ -263,31 +241,17 @@ int dds_parse(const uint8_t *data, size_t bytes, kc_dds_info *info)
     // well-formed from here on: what is not a BC texture this library decodes is unsupported
     if (!(d[20] & 0x4u)) return unsupported("not a FourCC format (uncompressed)");
     if ((d[28] & 0x200u) || (d[28] & 0x200000u) || ((d[2] & 0x800000u) && d[6] > 1)) return unsupported("cube maps and volumes");
-    int format = 0;
     uint32_t flags = 0;
+    const BcFormat *f = dx10 ? bc_format_of_dds(d[32], 0, &flags) : bc_format_of_dds(0, d[21], &flags);  // what kc_dds_header writes, and the legacy files
     if (dx10) {
-        switch (d[32]) {
-        case 71: format = KC_BC1; break;
-        case 72: format = KC_BC1, flags = KC_BC_SRGB; break;
-        case 77: format = KC_BC3; break;
-        case 78: format = KC_BC3, flags = KC_BC_SRGB; break;
-        case 80: format = KC_BC4; break;
-        case 83: format = KC_BC5; break;
-        case 98: format = KC_BC7; break;
-        case 99: format = KC_BC7, flags = KC_BC_SRGB; break;
-        default: return unsupported("a dxgiFormat other than BC1, BC3, BC4, BC5 and BC7 UNORM");
-        }
+        if (!f) return unsupported("a dxgiFormat other than BC1, BC3, BC4, BC5 and BC7 UNORM");
         if (d[33] != 3) return unsupported("a resource dimension other than TEXTURE2D");
         if (d[34] & 0x4u) return unsupported("cube maps");
         if (d[35] != 1) return unsupported("texture arrays");
-    } else {
-        const uint32_t cc = d[21];
-        if (cc == fourcc('D', 'X', 'T', '1')) format = KC_BC1;
-        else if (cc == fourcc('D', 'X', 'T', '5')) format = KC_BC3;
-        else if (cc == fourcc('A', 'T', 'I', '1') || cc == fourcc('B', 'C', '4', 'U')) format = KC_BC4;
-        else if (cc == fourcc('A', 'T', 'I', '2') || cc == fourcc('B', 'C', '5', 'U')) format = KC_BC5;
-        else return unsupported("a FourCC other than DXT1, DXT5, ATI1 / BC4U, ATI2 / BC5U and DX10");
+    } else if (!f) {
+        return unsupported("a FourCC other than DXT1, DXT5, ATI1 / BC4U, ATI2 / BC5U and DX10");
     }
+    const int format = f->format;
     const uint32_t levels = ((d[2] & 0x20000u) && d[7]) ? d[7] : 1u;
     uint32_t L = 0;
     KC_TRY(mip_level_count(w, h, &L));

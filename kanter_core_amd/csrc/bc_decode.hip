@@ -3,19 +3,19 @@
 // is the same rules in numpy).  Both kernels are bc.hip's stream turned round: one thread per 4x4 block, a grid-stride loop over
 // the blocks in row order, so the lanes of a wave hold consecutive blocks of a block row.  A block arrives in one 8- or 16-byte
 // load and is expanded in registers to 16 RGBA8 words.
-//   bc_decode_kernel   stores the four pixel rows of every resident plane as float4 (b / 255.f, from_u8's IEEE division): a
-//                      wave writes 1 KiB of contiguous bytes per plane row.  Waves without an edge block skip the clipping.
+//   bc_decode_kernel   stores the four pixel rows of every resident plane as float4 (b / 255.f, from_u8's IEEE division)
+//                      through bc_blocks.h's bc_store_planes, which bc6h.hip's decoder shares.
 //   bc_compare_kernel  reads the image's planes as the encoder does (bc_blocks.h), quantises them with the encoder's functions
 //                      and sums the squared byte differences over the pixels inside the image.
-// Counts and sums are reduced per wave (shuffles), then per workgroup through LDS, to one record of u64 words per workgroup;
-// bc_combine_kernel folds the records into the result, one workgroup per word, without atomics.  Everything is an integer,
+// The walk over the blocks and its edge rule are bc_blocks.h's.  Counts and sums are reduced per wave (shuffles), then per
+// workgroup through LDS, to one record of u64 words per workgroup (bc_fold_record, there too); bc_combine_kernel folds the records into the result, one workgroup per word, without atomics.  Everything is an integer,
 // so the result does not depend on the order.
 #include "kc_internal.hpp"
 
 namespace kc {
 
 #include "streaming.h"  // grid_cap, ld_policy / st_policy, quant_u8 / quant_u8_srgb
-#include "bc_blocks.h"  // the packed types, the row loaders and the quantiser of the encoders
+#include "bc_blocks.h"  // the block walk, the encoders' row loaders and quantiser, the plane-row store and the record fold
 
 // BC1 into px (R | G << 8 | B << 16 | A << 24).  `four`: BC3's colour block, always in four-colour mode
 static __device__ __forceinline__ void decode_bc1(uint32_t w0, uint32_t idx, bool four, uint32_t (&px)[16])
@@ -71,15 +71,6 @@ static __device__ __forceinline__ void decode_bc4(uint32_t lo, uint32_t hi, uint
     }
 }
 
-// n bits of the 128-bit block from bit `at`, LSB first; `at` and n are constants after unrolling
-static __device__ __forceinline__ uint32_t bc7_bits(const uint32_t (&b)[4], int at, int n)
-{
-    const int w = at >> 5, s = at & 31;
-    uint32_t v = b[w] >> s;
-    if (s + n > 32) v |= b[w + 1] << (32 - s);
-    return v & ((1u << n) - 1u);
-}
-
 // The interpolation weights as expressions: W2[i] = (64 i + 1) div 3, W3[i] = (64 i + 3) div 7, W4[i] = (64 i + 7) div 15
 static __device__ __forceinline__ uint32_t bc7_w2(uint32_t i) { return (64u * i + 1u) / 3u; }
 static __device__ __forceinline__ uint32_t bc7_w3(uint32_t i) { return (64u * i + 3u) / 7u; }
@@ -95,49 +86,49 @@ static __device__ __forceinline__ bool decode_bc7(const uint32_t (&b)[4], uint32
     uint32_t e0[4] = { 0u, 0u, 0u, 0u }, e1[4] = { 0u, 0u, 0u, 0u }, rot = 0u;
     // px holds the weights first: colour | alpha << 8
     if (m == 6u) {
-        const uint32_t p0 = bc7_bits(b, 63, 1), p1 = bc7_bits(b, 64, 1);
+        const uint32_t p0 = bc_bits(b, 63, 1), p1 = bc_bits(b, 64, 1);
 #pragma unroll
         for (int c = 0; c < 4; ++c) {
-            e0[c] = 2u * bc7_bits(b, 7 + 14 * c, 7) + p0;
-            e1[c] = 2u * bc7_bits(b, 14 + 14 * c, 7) + p1;
+            e0[c] = 2u * bc_bits(b, 7 + 14 * c, 7) + p0;
+            e1[c] = 2u * bc_bits(b, 14 + 14 * c, 7) + p1;
         }
 #pragma unroll
         for (int t = 0; t < 16; ++t) {
-            const uint32_t w = bc7_w4(t == 0 ? bc7_bits(b, 65, 3) : bc7_bits(b, 68 + 4 * (t - 1), 4));
+            const uint32_t w = bc7_w4(t == 0 ? bc_bits(b, 65, 3) : bc_bits(b, 68 + 4 * (t - 1), 4));
             px[t] = w | (w << 8);
         }
     } else if (m == 5u) {
-        rot = bc7_bits(b, 6, 2);
+        rot = bc_bits(b, 6, 2);
 #pragma unroll
         for (int c = 0; c < 3; ++c) {
-            const uint32_t q0 = bc7_bits(b, 8 + 14 * c, 7), q1 = bc7_bits(b, 15 + 14 * c, 7);
+            const uint32_t q0 = bc_bits(b, 8 + 14 * c, 7), q1 = bc_bits(b, 15 + 14 * c, 7);
             e0[c] = (q0 << 1) | (q0 >> 6);
             e1[c] = (q1 << 1) | (q1 >> 6);
         }
-        e0[3] = bc7_bits(b, 50, 8);
-        e1[3] = bc7_bits(b, 58, 8);
+        e0[3] = bc_bits(b, 50, 8);
+        e1[3] = bc_bits(b, 58, 8);
 #pragma unroll
         for (int t = 0; t < 16; ++t) {
-            const uint32_t ic = t == 0 ? bc7_bits(b, 66, 1) : bc7_bits(b, 67 + 2 * (t - 1), 2);
-            const uint32_t ia = t == 0 ? bc7_bits(b, 97, 1) : bc7_bits(b, 98 + 2 * (t - 1), 2);
+            const uint32_t ic = t == 0 ? bc_bits(b, 66, 1) : bc_bits(b, 67 + 2 * (t - 1), 2);
+            const uint32_t ia = t == 0 ? bc_bits(b, 97, 1) : bc_bits(b, 98 + 2 * (t - 1), 2);
             px[t] = bc7_w2(ic) | (bc7_w2(ia) << 8);
         }
     } else if (m == 4u) {
-        rot = bc7_bits(b, 5, 2);
-        const bool sel = bc7_bits(b, 7, 1) != 0u;
+        rot = bc_bits(b, 5, 2);
+        const bool sel = bc_bits(b, 7, 1) != 0u;
 #pragma unroll
         for (int c = 0; c < 3; ++c) {
-            const uint32_t q0 = bc7_bits(b, 8 + 10 * c, 5), q1 = bc7_bits(b, 13 + 10 * c, 5);
+            const uint32_t q0 = bc_bits(b, 8 + 10 * c, 5), q1 = bc_bits(b, 13 + 10 * c, 5);
             e0[c] = (q0 << 3) | (q0 >> 2);
             e1[c] = (q1 << 3) | (q1 >> 2);
         }
-        const uint32_t a0 = bc7_bits(b, 38, 6), a1 = bc7_bits(b, 44, 6);
+        const uint32_t a0 = bc_bits(b, 38, 6), a1 = bc_bits(b, 44, 6);
         e0[3] = (a0 << 2) | (a0 >> 4);
         e1[3] = (a1 << 2) | (a1 >> 4);
 #pragma unroll
         for (int t = 0; t < 16; ++t) {
-            const uint32_t w2 = bc7_w2(t == 0 ? bc7_bits(b, 50, 1) : bc7_bits(b, 51 + 2 * (t - 1), 2));
-            const uint32_t w3 = bc7_w3(t == 0 ? bc7_bits(b, 81, 2) : bc7_bits(b, 83 + 3 * (t - 1), 3));
+            const uint32_t w2 = bc7_w2(t == 0 ? bc_bits(b, 50, 1) : bc_bits(b, 51 + 2 * (t - 1), 2));
+            const uint32_t w3 = bc7_w3(t == 0 ? bc_bits(b, 81, 2) : bc_bits(b, 83 + 3 * (t - 1), 3));
             px[t] = sel ? (w3 | (w2 << 8)) : (w2 | (w3 << 8));
         }
     } else {
@@ -197,69 +188,31 @@ static __device__ __forceinline__ bool bc_decode_block(const char *p, uint32_t (
     }
 }
 
-// The planes a format's decode writes: BC4 R; BC5 R, G; the others all four
+// What the kernels know of a format at compile time (the host's table is bc.cpp's bc_format): the block bytes, the channels the
+// comparison reads (bit c = channel c) and the planes a decode writes
+static constexpr size_t bc_bytes(int fmt) { return fmt == KC_BC1 || fmt == KC_BC4 ? 8 : 16; }
+static constexpr uint32_t bc_channels(int fmt) { return fmt == KC_BC1 ? 0x7u : fmt == KC_BC4 ? 0x1u : fmt == KC_BC5 ? 0x3u : 0xfu; }
 static constexpr int bc_decode_planes(int fmt) { return fmt == KC_BC4 ? 1 : fmt == KC_BC5 ? 2 : 4; }
 
-// Sum / maximum over the wave's 64 lanes, in every lane
-static __device__ __forceinline__ unsigned long long wave_sum(unsigned long long v)
-{
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-        const uint32_t lo = (uint32_t)__shfl_xor((int)(uint32_t)v, off), hi = (uint32_t)__shfl_xor((int)(uint32_t)(v >> 32), off);
-        v += (unsigned long long)hi << 32 | lo;
-    }
-    return v;
-}
-static __device__ __forceinline__ uint32_t wave_max(uint32_t v)
-{
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v = max(v, (uint32_t)__shfl_xor((int)v, off));
-    return v;
-}
-
-// COUNT (BC7): the workgroup's undecoded blocks go to a.partials[blockIdx.x]
+// COUNT (instantiated for BC7, the one format of this unit with modes that are not decoded; BC6H's decoder, which counts too, is
+// bc6h.hip's): the workgroup's undecoded blocks go to a.partials[blockIdx.x]
 template <int FMT, bool NT, bool COUNT>
 __global__ __launch_bounds__(256) void bc_decode_kernel(const BcDecodeArgs a)
 {
-    [[maybe_unused]] __shared__ unsigned long long red[4];  // per wave
-    constexpr int NP = bc_decode_planes(FMT);
-    constexpr size_t BB = FMT == KC_BC1 || FMT == KC_BC4 ? 8 : 16;
-    const uint32_t total = a.bx * a.by;
-    const uint32_t edge_i = (a.w & 3u) ? a.bx - 1 : 0xffffffffu, edge_j = (a.h & 3u) ? a.by - 1 : 0xffffffffu;
-    uint32_t undecoded = 0u;
-    for (uint32_t idx = blockIdx.x * 256u + threadIdx.x; idx < total; idx += gridDim.x * 256u) {
-        const uint32_t j = idx / a.bx, i = idx - j * a.bx;
-        // wave-uniform: a wave that holds no edge block stores whole quads and all four rows
-        const bool wave_edge = __any(i == edge_i || j == edge_j) != 0;
+    [[maybe_unused]] __shared__ unsigned long long red[4][1];  // per wave
+    const BcWalk k = bc_walk(a.w, a.h, a.bx, a.by);
+    unsigned long long undecoded[1] = { 0ull };
+    for (uint32_t idx = blockIdx.x * 256u + threadIdx.x; idx < k.total; idx += gridDim.x * 256u) {
+        uint32_t i, j;
+        const bool wave_edge = bc_block_of(k, idx, i, j);
         uint32_t px[16], mode;
-        const bool skipped = bc_decode_block<FMT, NT>(a.src + (size_t)j * a.row_pitch + (size_t)i * BB, px, &mode);
-        if constexpr (COUNT) undecoded += skipped ? 1u : 0u;
-        const uint32_t cols = wave_edge ? min(a.w - 4u * i, 4u) : 4u, rows = wave_edge ? min(a.h - 4u * j, 4u) : 4u;
-#pragma unroll
-        for (int y = 0; y < 4; ++y) {
-            if (wave_edge && (uint32_t)y >= rows) break;
-#pragma unroll
-            for (int c = 0; c < NP; ++c) {
-                float *row = a.dst[c] + (size_t)(4u * j + y) * a.dst_pitch + 4u * i;
-                bc_f4 v;
-#pragma unroll
-                for (int x = 0; x < 4; ++x) v[x] = (float)((px[4 * y + x] >> (8 * c)) & 0xffu) / 255.0f;  // from_u8's IEEE division
-                if (!wave_edge || cols == 4u) {
-                    st_policy<NT>(reinterpret_cast<bc_f4 *>(row), v);
-                } else {
-#pragma unroll
-                    for (int x = 0; x < 3; ++x)
-                        if ((uint32_t)x < cols) st_policy<NT>(row + x, v[x]);
-                }
-            }
-        }
+        const bool skipped = bc_decode_block<FMT, NT>(a.src + (size_t)j * a.row_pitch + (size_t)i * bc_bytes(FMT), px, &mode);
+        if constexpr (COUNT) undecoded[0] += skipped ? 1u : 0u;
+        bc_store_planes<bc_decode_planes(FMT), NT>(a, i, j, wave_edge, [&](int c, int t) {
+            return (float)((px[t] >> (8 * c)) & 0xffu) / 255.0f;  // from_u8's IEEE division
+        });
     }
-    if constexpr (COUNT) {
-        const unsigned long long n = wave_sum(undecoded);
-        if ((threadIdx.x & 63u) == 0u) red[threadIdx.x >> 6] = n;
-        __syncthreads();
-        if (threadIdx.x == 0) a.partials[blockIdx.x] = red[0] + red[1] + red[2] + red[3];
-    }
+    if constexpr (COUNT) bc_fold_record<1, 0x1u>(undecoded, red, a.partials + blockIdx.x);
 }
 
 // Record of a workgroup, KC_BC_REC_WORDS u64: [0..3] the squared error per channel, [4..7] the largest absolute difference,
@@ -270,21 +223,15 @@ __global__ __launch_bounds__(256) void bc_compare_kernel(Operand r, Operand g, O
 {
     __shared__ uint32_t srgb_t[SRGB ? 257 : 1];
     __shared__ unsigned long long red[4][KC_BC_REC_WORDS];  // per wave
-    constexpr uint32_t CH = FMT == KC_BC1 ? 0x7u : FMT == KC_BC4 ? 0x1u : FMT == KC_BC5 ? 0x3u : 0xfu;
-    constexpr size_t BB = FMT == KC_BC1 || FMT == KC_BC4 ? 8 : 16;
+    constexpr uint32_t CH = bc_channels(FMT);
     const Operand op[4] = { r, g, b, al };
-    if constexpr (SRGB) {
-        srgb_t[threadIdx.x] = kSrgbThresholdBits[threadIdx.x];  // 256 threads, as bc_encode_kernel stages it
-        if (threadIdx.x == 0) srgb_t[256] = 0xffffffffu;         // sentinel: nothing is >= it
-        __syncthreads();
-    }
-    const uint32_t total = a.bx * a.by;
-    const uint32_t edge_i = (a.w & 3u) ? a.bx - 1 : 0xffffffffu, edge_j = (a.h & 3u) ? a.by - 1 : 0xffffffffu;
+    if constexpr (SRGB) bc_stage_srgb(srgb_t);
+    const BcWalk k = bc_walk(a.w, a.h, a.bx, a.by);
     unsigned long long sse[4] = { 0ull, 0ull, 0ull, 0ull };
     uint32_t mx[4] = { 0u, 0u, 0u, 0u }, undecoded = 0u, modes[8] = { 0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u };
-    for (uint32_t idx = blockIdx.x * 256u + threadIdx.x; idx < total; idx += gridDim.x * 256u) {
-        const uint32_t j = idx / a.bx, i = idx - j * a.bx;
-        const bool wave_edge = __any(i == edge_i || j == edge_j) != 0;
+    for (uint32_t idx = blockIdx.x * 256u + threadIdx.x; idx < k.total; idx += gridDim.x * 256u) {
+        uint32_t i, j;
+        const bool wave_edge = bc_block_of(k, idx, i, j);
         uint32_t rb[16], ga[16];
 #pragma unroll
         for (int y = 0; y < 4; ++y) {
@@ -293,11 +240,11 @@ __global__ __launch_bounds__(256) void bc_compare_kernel(Operand r, Operand g, O
             bc_quantise_row<CH, SRGB>(v, gray, y, srgb_t, rb, ga);
         }
         uint32_t px[16], mode;
-        const bool skipped = bc_decode_block<FMT, NT>(a.dst + (size_t)j * a.row_pitch + (size_t)i * BB, px, &mode);
+        const bool skipped = bc_decode_block<FMT, NT>(a.dst + (size_t)j * a.row_pitch + (size_t)i * bc_bytes(FMT), px, &mode);
         if constexpr (FMT == KC_BC7) {
             undecoded += skipped ? 1u : 0u;
 #pragma unroll
-            for (uint32_t k = 0; k < 8; ++k) modes[k] += mode == k ? 1u : 0u;
+            for (uint32_t m = 0; m < 8; ++m) modes[m] += mode == m ? 1u : 0u;
         }
         const uint32_t cols = wave_edge ? min(a.w - 4u * i, 4u) : 4u, rows = wave_edge ? min(a.h - 4u * j, 4u) : 4u;
         uint32_t s[4] = { 0u, 0u, 0u, 0u };  // of this block: 16 * 255^2 fits
@@ -317,30 +264,14 @@ __global__ __launch_bounds__(256) void bc_compare_kernel(Operand r, Operand g, O
 #pragma unroll
         for (int c = 0; c < 4; ++c) sse[c] += s[c];
     }
-    // the wave, then the workgroup's four waves through LDS: one record per workgroup
     unsigned long long val[KC_BC_REC_WORDS];
 #pragma unroll
     for (int c = 0; c < 4; ++c) val[c] = sse[c], val[4 + c] = mx[c];
     val[8] = undecoded;
 #pragma unroll
-    for (int k = 0; k < 8; ++k) val[9 + k] = modes[k];
-#pragma unroll
-    for (uint32_t k = 0; k < KC_BC_REC_WORDS; ++k) {
-        const bool used = k < 8 ? ((CH >> (k & 3u)) & 1u) != 0 : FMT == KC_BC7;  // the other words are 0 in every thread
-        if (!used) continue;
-        if (k >= 4 && k < 8) val[k] = wave_max((uint32_t)val[k]);
-        else val[k] = wave_sum(val[k]);
-    }
-    if ((threadIdx.x & 63u) == 0u) {
-#pragma unroll
-        for (uint32_t k = 0; k < KC_BC_REC_WORDS; ++k) red[threadIdx.x >> 6][k] = val[k];
-    }
-    __syncthreads();
-    if (threadIdx.x < KC_BC_REC_WORDS) {
-        const uint32_t k = threadIdx.x;
-        const unsigned long long r0 = red[0][k], r1 = red[1][k], r2 = red[2][k], r3 = red[3][k];
-        partials[(size_t)blockIdx.x * KC_BC_REC_WORDS + k] = k >= 4 && k < 8 ? max(max(r0, r1), max(r2, r3)) : r0 + r1 + r2 + r3;
-    }
+    for (int m = 0; m < 8; ++m) val[9 + m] = modes[m];
+    // the channels the format holds, and BC7's counts: the other words are 0 in every thread
+    bc_fold_record<KC_BC_REC_WORDS, CH | CH << 4 | (FMT == KC_BC7 ? 0x1ff00u : 0u)>(val, red, partials + (size_t)blockIdx.x * KC_BC_REC_WORDS);
 }
 
 // result[col] = the sum (max_cols bit col set: the maximum) of word col of the `groups` records of rec_words words: one
@@ -377,22 +308,20 @@ hipError_t launch_bc_combine(const unsigned long long *partials, uint32_t groups
 
 uint32_t bc_decode_groups(uint32_t w, uint32_t h, bool count)
 {
-    const uint64_t total = (uint64_t)((w + 3) / 4) * ((h + 3) / 4);
     // one record per workgroup when counting: the grid-stride loop takes the rest
-    const uint64_t cap = grid_cap(count ? 1u << 16 : 1u << 30);
-    return (uint32_t)std::max<uint64_t>(std::min<uint64_t>((total + 255) / 256, cap), 1);
+    return bc_grid((uint64_t)((w + 3) / 4) * ((h + 3) / 4), count ? 1u << 16 : 1u << 30);
 }
 
 uint32_t bc_compare_groups(uint32_t w, uint32_t h)
 {
-    const uint64_t total = (uint64_t)((w + 3) / 4) * ((h + 3) / 4);
     // one block a thread, as the encoder, while the records stay few (2^16 of them are 8.5 MiB); the loop takes the rest
-    return (uint32_t)std::max<uint64_t>(std::min<uint64_t>((total + 255) / 256, grid_cap(1u << 16)), 1);
+    return bc_grid((uint64_t)((w + 3) / 4) * ((h + 3) / 4), 1u << 16);
 }
 
 hipError_t launch_bc_decode(int fmt, const BcDecodeArgs &a, bool count, uint32_t nt_mask, uint32_t groups, hipStream_t s)
 {
     if (groups == 0 || a.bx == 0 || a.by == 0) return hipErrorInvalidValue;
+    // of this unit's formats only BC7 has modes that are not decoded (BC6H counts too, in its own unit: launch_bc6h_decode)
     if (count && (fmt != KC_BC7 || !a.partials || !a.result)) return hipErrorInvalidValue;
     const bool nt = (nt_mask & 0x100u) != 0;  // the planes written are the launch's stream
 #define KC_BCD(F, NTL, CNT) bc_decode_kernel<F, NTL, CNT><<<dim3(groups), 256, 0, s>>>(a)
@@ -423,15 +352,9 @@ hipError_t launch_bc_decode(int fmt, const BcDecodeArgs &a, bool count, uint32_t
 hipError_t launch_bc_compare(int fmt, int srgb, const Operand op[4], int gray, const char *blocks, uint64_t row_pitch, uint32_t w, uint32_t h,
                              uint32_t nt_mask, uint32_t groups, unsigned long long *partials, unsigned long long *result, hipStream_t s)
 {
-    BcBlockArgs a;
-    a.dst = const_cast<char *>(blocks);  // read only here
-    a.row_pitch = row_pitch;
-    a.w = w;
-    a.h = h;
-    a.bx = (w + 3) / 4;
-    a.by = (h + 3) / 4;
+    const BcBlockArgs a = bc_block_args(const_cast<char *>(blocks), row_pitch, w, h);  // read only here
     if (groups == 0 || a.bx == 0 || a.by == 0 || !partials || !result) return hipErrorInvalidValue;
-    if (srgb && fmt != KC_BC1 && fmt != KC_BC3 && fmt != KC_BC7) return hipErrorInvalidValue;
+    if (srgb && fmt != KC_BC1 && fmt != KC_BC3 && fmt != KC_BC7) return hipErrorInvalidValue;  // no such instantiation
     const bool nt = (nt_mask & 0xffu) != 0;
 #define KC_BCC(F, SR, NTL) bc_compare_kernel<F, SR, NTL><<<dim3(groups), 256, 0, s>>>(op[0], op[1], op[2], op[3], gray, a, partials)
 #define KC_BCC_NT(F, SR)                                                                                                              \

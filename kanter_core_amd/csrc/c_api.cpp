@@ -1560,7 +1560,7 @@ KC_CATCH
 
 int kc_live_graph_buffer_bc_error(kc_live_graph *lg, uint32_t node, uint32_t slot, int format, uint32_t flags, kc_bc_error *out)
 try {
-    KC_TRY(bc_check_flags(format, flags, "kc_live_graph_buffer_bc_error"));
+    KC_TRY(bc_check_flags(format, flags, KC_BC_SRGB, "kc_live_graph_buffer_bc_error"));
     LG_LOCK(lg);
     KC_ARG(out && bc_block_bytes(format) != 0);
     KC_TRY(need_init());

@@ -146,20 +146,16 @@ int image_from_device(const kc_device_image *src, uint32_t flags, void *hip_stre
             p[i] = plane_new_const(w, h, i == 3 ? 1.0f : 0.0f);  // deconstruct_image: missing R, G, B = 0, A = 1
         }
     }
-    hipStream_t hs = (hipStream_t)hip_stream;
-    const bool edges = hs && hs != c.stream;
-    if (s == KC_OK && edges) s = stream_edge(hs, c.stream);
-    if (s == KC_OK) {
-        const DevImageArgs a = devimage_args(src);
-        const uint64_t in_bytes = (uint64_t)w * h * n * elem_bytes(src->dtype), out_bytes = (uint64_t)w * h * 4 * n;
-        hipError_t e = launch_image_import(src->dtype, a, dp, (uint32_t)(p[0]->pitch / 4), cache_policy_mask(in_bytes, out_bytes, 1), c.stream);
-        if (e != hipSuccess) s = hip_fail(e, "launch_image_import");
-        else {
+    if (s == KC_OK)
+        s = with_stream_edges(hip_stream, [&] {
+            const DevImageArgs a = devimage_args(src);
+            const uint64_t in_bytes = (uint64_t)w * h * n * elem_bytes(src->dtype), out_bytes = (uint64_t)w * h * 4 * n;
+            hipError_t e = launch_image_import(src->dtype, a, dp, (uint32_t)(p[0]->pitch / 4), cache_policy_mask(in_bytes, out_bytes, 1), c.stream);
+            if (e != hipSuccess) return hip_fail(e, "launch_image_import");
             c.launches++;
             c.alg_bytes += in_bytes + out_bytes;
-        }
-    }
-    if (s == KC_OK && edges) s = stream_edge(c.stream, hs);
+            return (int)KC_OK;
+        });
     if (s == KC_OK) *out = image_new(gray ? 1 : 4, p);
     for (int i = 0; i < 4; ++i) plane_release(p[i]);
     return s;
@@ -189,18 +185,16 @@ int image_to_device(kc_image *img, const kc_device_image *dst, uint32_t flags, v
     uint32_t n_res = 0;  // distinct resident planes the launch reads
     for (int i = 0; i < n; ++i) n_res += o[i].ptr != nullptr && (rgba || i == 0);
     const uint32_t w = img->w(), h = img->h();
-    hipStream_t hs = (hipStream_t)hip_stream;
-    const bool edges = hs && hs != c.stream;
-    if (edges) KC_TRY(stream_edge(hs, c.stream));
-    const uint64_t in_bytes = (uint64_t)w * h * 4 * n_res, out_bytes = (uint64_t)w * h * n * elem_bytes(dst->dtype);
-    const DevImageArgs a = devimage_args(dst);
-    hipError_t e = launch_image_export(dst->dtype, srgb ? 1 : 0, o, rgba ? 0 : 1, a, cache_policy_mask(in_bytes, out_bytes, n_res ? n_res : 1),
-                                       c.stream);
-    if (e != hipSuccess) return hip_fail(e, "launch_image_export");
-    c.launches++;
-    c.alg_bytes += in_bytes + out_bytes;
-    if (edges) KC_TRY(stream_edge(c.stream, hs));
-    return KC_OK;
+    return with_stream_edges(hip_stream, [&] {
+        const uint64_t in_bytes = (uint64_t)w * h * 4 * n_res, out_bytes = (uint64_t)w * h * n * elem_bytes(dst->dtype);
+        const DevImageArgs a = devimage_args(dst);
+        hipError_t e = launch_image_export(dst->dtype, srgb ? 1 : 0, o, rgba ? 0 : 1, a, cache_policy_mask(in_bytes, out_bytes, n_res ? n_res : 1),
+                                           c.stream);
+        if (e != hipSuccess) return hip_fail(e, "launch_image_export");
+        c.launches++;
+        c.alg_bytes += in_bytes + out_bytes;
+        return (int)KC_OK;
+    });
 }
 
 }  // namespace kc

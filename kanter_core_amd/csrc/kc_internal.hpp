@@ -300,6 +300,8 @@ hipError_t launch_channel_stats(const StatsArgs &a, bool hist, bool srgb, bool n
 // workgroups of that launch for a w x h image on a device of `cus` CUs (>= 1)
 uint32_t channel_stats_groups(uint32_t w, uint32_t h, bool hist, bool srgb, uint32_t cus);
 // -- bc.hip --
+// The launchers of the block-compression units.  The host calls them through bc.cpp's bc_launch_encode / _decode / _compare, which
+// pick the unit of a format; the units share their loops through bc_blocks.h.
 // Block compression (bc.hip / bc.cpp): bc_encode_kernel<fmt, srgb, nt> writes the ceil(w/4) x ceil(h/4) blocks of format `fmt`
 // (kc_bc_format) at dst, block rows row_pitch bytes apart; channel c is op[c]; gray != 0: op[0] stands for R, G and B (read
 // once); nt_mask bits 0-7: nontemporal plane loads; srgb: BC1 and BC3 only
@@ -321,7 +323,9 @@ struct BcDecodeArgs {
     uint32_t w, h, bx, by;
     unsigned long long *partials, *result;  // count: one word per workgroup, and the sum (bc_combine_kernel: a second launch)
 };
-// count (KC_BC7 only): result[0] = the blocks of the partitioned modes, which are not decoded
+// count: result[0] = the blocks of the modes that are not decoded, by a second launch (bc_combine_kernel).  Of this unit's formats
+// only KC_BC7 has such modes (the partitioned ones) and takes count; the host asks for a count where its format table says the
+// format counts, that is for KC_BC7 here and for KC_BC6H through launch_bc6h_decode
 hipError_t launch_bc_decode(int fmt, const BcDecodeArgs &a, bool count, uint32_t nt_mask, uint32_t groups, hipStream_t s);
 uint32_t bc_decode_groups(uint32_t w, uint32_t h, bool count);
 // bc_compare_kernel<fmt, srgb, nt> on `groups` workgroups, then bc_combine_kernel: two launches.  The image's channels as
@@ -336,7 +340,7 @@ uint32_t bc_compare_groups(uint32_t w, uint32_t h);
 hipError_t launch_bc_combine(const unsigned long long *partials, uint32_t groups, uint32_t rec_words, uint32_t max_cols,
                              unsigned long long *result, hipStream_t s);
 // -- bc6h.hip --
-// KC_BC6H (16-byte blocks; R, G, B as half bit patterns, alpha never read).  bc6h_encode_kernel<nt>: launch_bc7_encode's stream
+// KC_BC6H (16-byte blocks; R, G, B as half bit patterns, alpha never read).  bc6h_encode_kernel<nt>: launch_bc7_encode's arguments
 // without the sRGB form.  bc6h_decode_kernel<nt, count>: launch_bc_decode's arguments, dst[0..2] written; count: result[0] = the
 // blocks of the two-subset modes, which are not decoded (a second launch).  bc6h_compare_kernel<nt>, then bc_combine_kernel:
 // launch_bc_compare's arguments and record, the differences taken over the half bit patterns.

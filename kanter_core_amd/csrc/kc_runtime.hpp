@@ -305,6 +305,24 @@ void sampler_report();
 int pool_alloc(size_t bytes, void **out);
 void pool_free(void *p, size_t bytes);
 int pool_trim();
+// A pool block of `bytes` rounded up to 256 for the scope's staging, back to the pool when the scope ends: after the work that
+// uses it has been enqueued on, or waited for on, the library's stream (the pool hands a block out again only to that stream)
+struct PoolStaging {
+    void *ptr = nullptr;
+    size_t block = 0;
+    PoolStaging() = default;
+    PoolStaging(const PoolStaging &) = delete;
+    PoolStaging &operator=(const PoolStaging &) = delete;
+    int alloc(size_t bytes)
+    {
+        block = (bytes + 255) / 256 * 256;
+        return pool_alloc(block, &ptr);
+    }
+    ~PoolStaging()
+    {
+        if (ptr) pool_free(ptr, block);
+    }
+};
 
 int plane_new_mem(uint32_t w, uint32_t h, kc_plane **out);
 kc_plane *plane_new_const(uint32_t w, uint32_t h, float v);
@@ -343,15 +361,58 @@ int image_to_device(kc_image *img, const kc_device_image *dst, uint32_t flags, v
 // otherwise, with `who` in the error text); stream_edge: `to` waits for the work already enqueued on `from`
 int device_extent_check(const void *ptr, size_t ext, const char *who);
 int stream_edge(hipStream_t from, hipStream_t to);
+// work() -- which enqueues on the library's stream and returns a status -- between the two edges that order it against the
+// caller's `hip_stream`: the library's stream waits for what that stream holds now, and that stream waits for the work.  No edges
+// for NULL or the library's own stream; a failure ends the sequence where it happens.
+template <class Work> int with_stream_edges(void *hip_stream, Work work)
+{
+    hipStream_t hs = (hipStream_t)hip_stream, own = ctx().stream;
+    const bool edges = hs && hs != own;
+    if (edges) KC_TRY(stream_edge(hs, own));
+    KC_TRY(work());
+    if (edges) KC_TRY(stream_edge(own, hs));
+    return KC_OK;
+}
 // block compression (bc.cpp): the bodies of kc_bc_image_validate / kc_image_to_bc / kc_image_to_bc_device
 int bc_image_validate(const kc_bc_image *d, size_t *extent_bytes);
 int image_to_bc(kc_image *img, int format, uint32_t flags, uint8_t *host, size_t host_bytes);
 int image_to_bc_device(kc_image *img, const kc_bc_image *dst, uint32_t flags, void *hip_stream);
+// What a block format is, for the whole host side: one row per kc_bc_format in bc.cpp's table
+struct BcFormat {
+    int format;             // kc_bc_format
+    uint32_t block_bytes;   // 8 or 16
+    uint32_t channels;      // the source channels an encoder and a comparison read: bit c = channel c, contiguous low bits
+    int planes;             // the planes a decode writes (the others are the constants 0, 0, 1)
+    bool srgb;              // KC_BC_SRGB is allowed
+    bool counts_undecoded;  // has modes the decoder does not decode, which it counts
+    uint32_t dxgi, dxgi_srgb;  // the DXGI_FORMAT number kc_dds_header writes; with KC_BC_SRGB (0: none)
+    bool dds_read;          // kc_dds_parse accepts it
+    uint32_t fourcc[2];     // the legacy FourCCs kc_dds_parse accepts besides a DX10 header (0: none)
+};
+constexpr uint32_t fourcc(char a, char b, char c, char d)  // a .dds FourCC as the little-endian word of the file
+{
+    return (uint32_t)(uint8_t)a | (uint32_t)(uint8_t)b << 8 | (uint32_t)(uint8_t)c << 16 | (uint32_t)(uint8_t)d << 24;
+}
+const BcFormat *bc_format(int format);  // nullptr for an unknown format
+// the format kc_dds_parse reads for a DX10 header's dxgiFormat (cc = 0) or a legacy FourCC (dxgi = 0), with its flags; or nullptr
+const BcFormat *bc_format_of_dds(uint32_t dxgi, uint32_t cc, uint32_t *flags);
 size_t bc_block_bytes(int format);  // 8, 16, or 0 for an unknown format
+size_t bc_level_bytes(uint32_t w, uint32_t h, const BcFormat &f);  // the bytes of the blocks of a w x h level
+// *bx, *by = the blocks per row and the block rows of a w x h image; more than 2^31 blocks are KC_ERR_INVALID_ARG under `who`
+int bc_block_count(uint32_t w, uint32_t h, const char *who, uint64_t *bx, uint64_t *by);
+// the encoders' flag rule: bits outside `allowed`, or KC_BC_SRGB with a format without colour, are KC_ERR_UNSUPPORTED
+int bc_check_flags(int format, uint32_t flags, uint32_t allowed, const char *who);
+// o = the channels of `img` (forced) as to_u8 sees them (Gray: (v, v, v, 1)); returns the distinct resident planes among the
+// channels of `mask`, which is what a launch under that mask loads
+uint32_t bc_source_operands(const kc_image *img, uint32_t mask, Operand (&o)[4]);
 // one launch of the encoder for `img` (forced already) into `dst`, block rows `row_pitch` bytes apart, on `s`
 int bc_encode(kc_image *img, int format, bool srgb, char *dst, size_t row_pitch, hipStream_t s);
-// kc_image_to_bc's flag rule: bits other than KC_BC_SRGB, or KC_BC_SRGB with BC4 / BC5, are KC_ERR_UNSUPPORTED
-int bc_check_flags(int format, uint32_t flags, const char *who);
+// the launchers of kc_internal.hpp by format: the one place that knows which device unit holds a format's kernels
+hipError_t bc_launch_encode(int format, bool srgb, const Operand op[4], int gray, char *dst, uint64_t row_pitch, uint32_t w, uint32_t h,
+                            uint32_t nt_mask, hipStream_t s);
+hipError_t bc_launch_decode(int format, const BcDecodeArgs &a, bool count, uint32_t nt_mask, uint32_t groups, hipStream_t s);
+hipError_t bc_launch_compare(int format, bool srgb, const Operand op[4], int gray, const char *blocks, uint64_t row_pitch, uint32_t w, uint32_t h,
+                             uint32_t nt_mask, uint32_t groups, unsigned long long *partials, unsigned long long *result, hipStream_t s);
 // block decode, the error of an encoding and .dds input (bc_decode.cpp): the bodies of kc_image_from_bc, kc_image_from_bc_device,
 // kc_image_bc_compare, kc_image_bc_error, kc_dds_parse and kc_image_read_dds
 int image_from_bc(const uint8_t *host, size_t host_bytes, uint32_t w, uint32_t h, int format, uint32_t flags, kc_image **out,

@@ -162,35 +162,21 @@ int image_build_mips(kc_image *img, uint32_t flags, kc_image **levels, uint32_t 
 }
 
 // ---------------------------------------------------------------- the BC chain
-// flags of the chain exporters: KC_BC_SRGB under kc_image_to_bc's rule, plus KC_MIP_PER_LEVEL
-static int bc_mips_check_flags(int format, uint32_t flags, uint32_t allowed, const char *who)
-{
-    if (flags & ~allowed) {
-        set_error(std::string(who) + ": unknown flag bits");
-        return KC_ERR_UNSUPPORTED;
-    }
-    if ((flags & KC_BC_SRGB) && (format == KC_BC4 || format == KC_BC5 || format == KC_BC6H)) {
-        set_error(std::string(who) + ": KC_BC_SRGB is for BC1, BC3 and BC7 only");
-        return KC_ERR_UNSUPPORTED;
-    }
-    return KC_OK;
-}
-
-static size_t bc_level_bytes(uint32_t W, uint32_t H, size_t bb) { return (((size_t)W + 3) / 4) * (((size_t)H + 3) / 4) * bb; }
-
+// flags of the chain exporters: KC_BC_SRGB under kc_image_to_bc's rule (bc_check_flags), plus KC_MIP_PER_LEVEL
 int bc_mip_layout(uint32_t w, uint32_t h, int format, uint32_t *levels, size_t *offsets, uint32_t cap, size_t *total_bytes)
 {
-    const size_t bb = bc_block_bytes(format);
-    if (bb == 0) return mip_refuse("kc_bc_mip_layout", "unknown format");
+    const BcFormat *f = bc_format(format);
+    if (!f) return mip_refuse("kc_bc_mip_layout", "unknown format");
     if (w == 0 || h == 0) return mip_refuse("kc_bc_mip_layout", "zero extent");
     const uint32_t L = 1u + floor_log2(w > h ? w : h);
     if (levels) *levels = L;
     if (offsets && cap < L) return mip_refuse("kc_bc_mip_layout", "cap is below the level count");
-    if ((((uint64_t)w + 3) / 4) * (((uint64_t)h + 3) / 4) > (1ull << 31)) return mip_refuse("kc_bc_mip_layout", "image too large: more than 2^31 blocks");
+    uint64_t bx = 0, by = 0;
+    KC_TRY(bc_block_count(w, h, "kc_bc_mip_layout", &bx, &by));
     size_t at = 0;
     for (uint32_t k = 0; k < L; ++k) {
         if (offsets) offsets[k] = at;
-        at += bc_level_bytes(level_extent(w, k), level_extent(h, k), bb);
+        at += bc_level_bytes(level_extent(w, k), level_extent(h, k), *f);
     }
     if (total_bytes) *total_bytes = at;
     return KC_OK;
@@ -205,13 +191,13 @@ static int bc_mips_encode(kc_image *img, int format, uint32_t flags, char *dst)
     std::vector<kc_image *> lv(L, nullptr);
     uint32_t count = 0;
     KC_TRY(image_build_mips(img, flags & KC_MIP_PER_LEVEL, lv.data(), L, &count));
-    const size_t bb = bc_block_bytes(format);
+    const BcFormat &f = *bc_format(format);  // the entry points have refused an unknown format
     size_t at = 0;
     int s = KC_OK;
     for (uint32_t k = 0; k < L && s == KC_OK; ++k) {
         const uint32_t W = lv[k]->w(), H = lv[k]->h();
-        s = bc_encode(lv[k], format, (flags & KC_BC_SRGB) != 0, dst + at, (((size_t)W + 3) / 4) * bb, c.stream);
-        at += bc_level_bytes(W, H, bb);
+        s = bc_encode(lv[k], format, (flags & KC_BC_SRGB) != 0, dst + at, (((size_t)W + 3) / 4) * f.block_bytes, c.stream);
+        at += bc_level_bytes(W, H, f);
     }
     // the level planes go back to the pool here; the pool hands a block out again only to work enqueued on the same stream
     for (kc_image *i : lv) image_release(i);
@@ -220,8 +206,8 @@ static int bc_mips_encode(kc_image *img, int format, uint32_t flags, char *dst)
 
 int image_to_bc_mips(kc_image *img, int format, uint32_t flags, uint8_t *host, size_t host_bytes)
 {
-    KC_TRY(bc_mips_check_flags(format, flags, KC_BC_SRGB | KC_MIP_PER_LEVEL, "kc_image_to_bc_mips"));
-    if (bc_block_bytes(format) == 0) return mip_refuse("kc_image_to_bc_mips", "unknown format");
+    KC_TRY(bc_check_flags(format, flags, KC_BC_SRGB | KC_MIP_PER_LEVEL, "kc_image_to_bc_mips"));
+    if (!bc_format(format)) return mip_refuse("kc_image_to_bc_mips", "unknown format");
     if (!img || !host) return mip_refuse("kc_image_to_bc_mips", "NULL image or host buffer");
     KC_TRY(need_init());
     Context &c = ctx();
@@ -229,22 +215,18 @@ int image_to_bc_mips(kc_image *img, int format, uint32_t flags, uint8_t *host, s
     size_t total = 0;
     KC_TRY(bc_mip_layout(img->w(), img->h(), format, nullptr, nullptr, 0, &total));
     if (host_bytes < total) return mip_refuse("kc_image_to_bc_mips", "host_bytes is below the chain's bytes");
-    const size_t block = (total + 255) / 256 * 256;
-    void *staging = nullptr;
-    KC_TRY(pool_alloc(block, &staging));
-    int s = bc_mips_encode(img, format, flags, (char *)staging);
-    hipError_t e = hipSuccess;
-    if (s == KC_OK) e = hipMemcpyAsync(host, staging, total, hipMemcpyDeviceToHost, c.stream);
-    if (s == KC_OK && e == hipSuccess) e = hipStreamSynchronize(c.stream);
-    pool_free(staging, block);
-    if (s != KC_OK) return s;
+    PoolStaging staging;
+    KC_TRY(staging.alloc(total));
+    KC_TRY(bc_mips_encode(img, format, flags, (char *)staging.ptr));
+    hipError_t e = hipMemcpyAsync(host, staging.ptr, total, hipMemcpyDeviceToHost, c.stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(c.stream);
     if (e != hipSuccess) return hip_fail(e, "image_to_bc_mips");
     return KC_OK;
 }
 
 int image_to_bc_mips_device(kc_image *img, int format, uint32_t flags, void *device_ptr, size_t bytes, void *hip_stream)
 {
-    KC_TRY(bc_mips_check_flags(format, flags, KC_BC_SRGB | KC_MIP_PER_LEVEL, "kc_image_to_bc_mips_device"));
+    KC_TRY(bc_check_flags(format, flags, KC_BC_SRGB | KC_MIP_PER_LEVEL, "kc_image_to_bc_mips_device"));
     const size_t bb = bc_block_bytes(format);
     if (bb == 0) return mip_refuse("kc_image_to_bc_mips_device", "unknown format");
     if (!img || !device_ptr) return mip_refuse("kc_image_to_bc_mips_device", "NULL image or device pointer");
@@ -256,39 +238,22 @@ int image_to_bc_mips_device(kc_image *img, int format, uint32_t flags, void *dev
     KC_TRY(bc_mip_layout(img->w(), img->h(), format, nullptr, nullptr, 0, &total));
     if (bytes < total) return mip_refuse("kc_image_to_bc_mips_device", "bytes is below the chain's bytes");
     KC_TRY(device_extent_check(device_ptr, total, "kc_image_to_bc_mips_device"));
-    hipStream_t hs = (hipStream_t)hip_stream;
-    const bool edges = hs && hs != c.stream;
-    if (edges) KC_TRY(stream_edge(hs, c.stream));
-    KC_TRY(bc_mips_encode(img, format, flags, (char *)device_ptr));
-    if (edges) KC_TRY(stream_edge(c.stream, hs));
-    return KC_OK;
+    return with_stream_edges(hip_stream, [&] { return bc_mips_encode(img, format, flags, (char *)device_ptr); });
 }
 
 // ---------------------------------------------------------------- DDS
-static uint32_t dxgi_format(int format, bool srgb)
-{
-    switch (format) {
-    case KC_BC1: return srgb ? 72u : 71u;
-    case KC_BC3: return srgb ? 78u : 77u;
-    case KC_BC4: return 80u;
-    case KC_BC7: return srgb ? 99u : 98u;
-    case KC_BC6H: return 95u;
-    default: return 83u;  // KC_BC5
-    }
-}
-
 int dds_header(uint32_t w, uint32_t h, int format, uint32_t flags, uint32_t levels, uint8_t *out, size_t *bytes)
 {
-    KC_TRY(bc_mips_check_flags(format, flags, KC_BC_SRGB, "kc_dds_header"));
-    const size_t bb = bc_block_bytes(format);
-    if (bb == 0) return mip_refuse("kc_dds_header", "unknown format");
+    KC_TRY(bc_check_flags(format, flags, KC_BC_SRGB, "kc_dds_header"));
+    const BcFormat *f = bc_format(format);
+    if (!f) return mip_refuse("kc_dds_header", "unknown format");
     if (!out || w == 0 || h == 0) return mip_refuse("kc_dds_header", "NULL output or zero extent");
     if (levels == 0 || levels > 1u + floor_log2(w > h ? w : h)) return mip_refuse("kc_dds_header", "levels is 0 or above the chain's level count");
-    const uint64_t linear = (((uint64_t)w + 3) / 4) * (((uint64_t)h + 3) / 4) * bb;
+    const uint64_t linear = (((uint64_t)w + 3) / 4) * (((uint64_t)h + 3) / 4) * f->block_bytes;
     if (linear > 0xffffffffull) return mip_refuse("kc_dds_header", "level 0 is larger than the header can say");
     const bool mips = levels > 1;
     uint32_t d[37] = { 0 };
-    d[0] = 0x20534444u;  // "DDS "
+    d[0] = fourcc('D', 'D', 'S', ' ');
     d[1] = 124;          // DDS_HEADER: dwSize
     d[2] = 0x1u | 0x2u | 0x4u | 0x1000u | 0x80000u | (mips ? 0x20000u : 0u);  // CAPS, HEIGHT, WIDTH, PIXELFORMAT, LINEARSIZE, MIPMAPCOUNT
     d[3] = h;
@@ -298,9 +263,9 @@ int dds_header(uint32_t w, uint32_t h, int format, uint32_t flags, uint32_t leve
     d[7] = levels;            // dwMipMapCount; d[8..18]: reserved
     d[19] = 32;               // DDS_PIXELFORMAT: dwSize
     d[20] = 0x4;              // DDPF_FOURCC
-    d[21] = 0x30315844u;      // "DX10"; d[22..26]: bit count and masks, 0
+    d[21] = fourcc('D', 'X', '1', '0');  // d[22..26]: bit count and masks, 0
     d[27] = 0x1000u | (mips ? 0x8u | 0x400000u : 0u);  // dwCaps: TEXTURE (, COMPLEX, MIPMAP); d[28..31]: 0
-    d[32] = dxgi_format(format, (flags & KC_BC_SRGB) != 0);  // DDS_HEADER_DXT10
+    d[32] = (flags & KC_BC_SRGB) ? f->dxgi_srgb : f->dxgi;  // DDS_HEADER_DXT10: the number kc_dds_parse looks up in the same table
     d[33] = 3;                // D3D10_RESOURCE_DIMENSION_TEXTURE2D
     d[34] = 0;                // miscFlag
     d[35] = 1;                // arraySize
@@ -313,8 +278,8 @@ int dds_header(uint32_t w, uint32_t h, int format, uint32_t flags, uint32_t leve
 
 int image_write_dds(kc_image *img, const char *path, int format, uint32_t flags, int with_mips)
 {
-    KC_TRY(bc_mips_check_flags(format, flags, KC_BC_SRGB | KC_MIP_PER_LEVEL, "kc_image_write_dds"));
-    if (bc_block_bytes(format) == 0) return mip_refuse("kc_image_write_dds", "unknown format");
+    KC_TRY(bc_check_flags(format, flags, KC_BC_SRGB | KC_MIP_PER_LEVEL, "kc_image_write_dds"));
+    if (!bc_format(format)) return mip_refuse("kc_image_write_dds", "unknown format");
     if (!img || !path) return mip_refuse("kc_image_write_dds", "NULL image or path");
     KC_TRY(need_init());
     const uint32_t w = img->w(), h = img->h();
@@ -323,7 +288,7 @@ int image_write_dds(kc_image *img, const char *path, int format, uint32_t flags,
     KC_TRY(bc_mip_layout(w, h, format, &L, nullptr, 0, &total));
     if (!with_mips) {
         L = 1;
-        total = bc_level_bytes(w, h, bc_block_bytes(format));
+        total = bc_level_bytes(w, h, *bc_format(format));
     }
     std::vector<uint8_t> file(148 + total);
     KC_TRY(dds_header(w, h, format, flags & KC_BC_SRGB, L, file.data(), nullptr));

@@ -17,6 +17,7 @@ from pngio import read_png
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 INPUTS = os.path.join(ROOT, "tests", "golden", "inputs")
 BC7 = R.BC7
+BC6H = 95  # KC_BC6H
 KC_OK, KC_ERR_NO_DEVICE, KC_ERR_INVALID_ARG, KC_ERR_UNSUPPORTED = R.KC_OK, R.KC_ERR_NO_DEVICE, R.KC_ERR_INVALID_ARG, R.KC_ERR_UNSUPPORTED
 N_RANDOM = 96  # BC7: four rounds of the 24-block cycle of random_blocks
 
@@ -185,11 +186,13 @@ def both(L, data):
     return status, got
 
 
-@pytest.mark.parametrize("w,h", [(1, 1), (5, 3), (64, 16)])
+@pytest.mark.parametrize("w,h", [(1, 1), (5, 3), (64, 16), (64, 64), (130, 70)])
 @pytest.mark.parametrize("fmt,srgb", sorted(R.DXGI))
 @pytest.mark.parametrize("mips", [False, True])
 def test_dds_header_parses_back(L, w, h, fmt, srgb, mips):
+    """What kc_dds_header writes, kc_dds_parse reads back: every format it reads, with every sRGB flag the format allows."""
     from kanter_core_amd import api
+    assert sorted(R.DXGI) == [(1, 0), (1, 1), (3, 0), (3, 1), (4, 0), (5, 0), (BC7, 0), (BC7, 1)]
     levels = api.mip_level_count(w, h) if mips else 1
     data = api.dds_header(w, h, fmt, bool(srgb), levels) + bytes(R.chain_bytes(w, h, fmt, levels))
     status, info = both(L, data)
@@ -198,6 +201,18 @@ def test_dds_header_parses_back(L, w, h, fmt, srgb, mips):
     assert api.dds_parse(data) == api.DdsInfo(w, h, fmt, bool(srgb), levels, 148, len(data) - 148)
     assert both(L, data[:-1])[0] == KC_ERR_INVALID_ARG  # a short payload
     assert both(L, data + b"xyz")[0] == KC_OK            # bytes after the chain are not the parser's business
+
+
+@pytest.mark.parametrize("w,h", [(64, 64), (130, 70)])
+def test_a_bc6h_header_is_written_and_not_read_back(L, w, h):
+    from kanter_core_amd import api
+    for levels in (1, api.mip_level_count(w, h)):
+        data = api.dds_header(w, h, BC6H, False, levels) + bytes(api.bc_mip_layout(w, h, BC6H)[1])
+        assert struct.unpack("<I", data[128:132])[0] == 95
+        assert parse(L, data)[0] == KC_ERR_UNSUPPORTED
+    with pytest.raises(api.TexProError) as e:
+        api.dds_header(w, h, BC6H, True, 1)  # no sRGB flag to go round with
+    assert e.value.code == KC_ERR_UNSUPPORTED
 
 
 @pytest.mark.parametrize("cc,fmt", [(b"DXT1", 1), (b"DXT5", 3), (b"ATI1", 4), (b"BC4U", 4), (b"ATI2", 5), (b"BC5U", 5)])

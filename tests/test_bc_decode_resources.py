@@ -4,21 +4,19 @@ compiler reports (gfx950: 512 VGPRs a SIMD in steps of 8, so 128 is four waves, 
 
     kernel                               reported     budget
     bc_decode_kernel  BC1 BC3 BC4 BC5    34 39 36 39  64   (eight waves)
-    bc_decode_kernel  BC7                111 / 114    128  (four waves; 114 with the count)
+    bc_decode_kernel  BC7                111 / 115    128  (four waves; 115 with the count)
     bc_compare_kernel BC4 / BC5          53 / 69      64 / 72  (eight and seven waves)
     bc_compare_kernel BC1                89 / 90      96   (five waves; 90 with sRGB)
     bc_compare_kernel BC3                115 / 116    128  (four waves; 116 with sRGB)
     bc_compare_kernel BC7                198 / 199    256  (two waves: the 32 source words, the 16 decoded words and the
                                                             three modes' fields together; see DESIGN)
 """
-import os
 import re
-import shutil
-import subprocess
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from util import kernel_resource_usage
+
 BC7 = 98
 DECODE_BUDGET = {1: 64, 3: 64, 4: 64, 5: 64, BC7: 128}
 COMPARE_BUDGET = {1: 96, 3: 128, 4: 64, 5: 72, BC7: 256}
@@ -27,27 +25,8 @@ COMPARE_BUDGET = {1: 96, 3: 128, 4: 64, 5: 72, BC7: 256}
 @pytest.fixture(scope="module")
 def usage(tmp_path_factory):
     from kanter_core_amd import build as kbuild
-    hipcc = kbuild._hipcc()
-    if shutil.which(hipcc) is None and not os.path.exists(hipcc):
-        pytest.skip("hipcc not available")
-    assert "bc_decode.hip" in kbuild.SOURCES and "bc_decode.cpp" in kbuild.SOURCES and "bc_blocks.h" in kbuild.HEADERS
-    tmp = tmp_path_factory.mktemp("bc_decode_res")
-    src = os.path.join(ROOT, "kanter_core_amd", "csrc", "bc_decode.hip")
-    cmd = [hipcc] + kbuild.FLAGS + kbuild.DEVICE_FLAGS + ["-x", "hip", "-Rpass-analysis=kernel-resource-usage", "-c", src,
-                                                          "-o", str(tmp / "bc_decode.o")]
-    r = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
-    assert r.returncode == 0, r.stdout[-2000:]
-    table, name = {}, None
-    for line in r.stdout.splitlines():
-        m = re.search(r"Function Name: (\S+)", line)
-        if m:
-            name = m.group(1)
-            table[name] = {}
-            continue
-        m = re.search(r"remark:\s+(VGPRs|ScratchSize \[bytes/lane\]): (\d+)", line)
-        if m and name:
-            table[name][m.group(1).split()[0]] = int(m.group(2))
-    return table
+    assert "bc_decode.cpp" in kbuild.SOURCES
+    return kernel_resource_usage("bc_decode.hip", tmp_path_factory.mktemp("bc_decode_res"))
 
 
 def instances(usage, kernel):

@@ -2,39 +2,16 @@
 and sRGB, BC4 and BC5, each in both cache policies -- keeps zero scratch.  BC4 and BC5 stay within 64 VGPRs like the other
 streaming exporters; BC1 and BC3 hold 32 packed texel words through the encoder and are pinned at their spill-free counts (capped
 at 64 they spill to scratch, see DESIGN)."""
-import os
 import re
-import shutil
-import subprocess
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from util import kernel_resource_usage
 
 
 @pytest.fixture(scope="module")
 def usage(tmp_path_factory):
-    from kanter_core_amd import build as kbuild
-    hipcc = kbuild._hipcc()
-    if shutil.which(hipcc) is None and not os.path.exists(hipcc):
-        pytest.skip("hipcc not available")
-    tmp = tmp_path_factory.mktemp("bc_res")
-    src = os.path.join(ROOT, "kanter_core_amd", "csrc", "bc.hip")
-    cmd = [hipcc] + kbuild.FLAGS + kbuild.DEVICE_FLAGS + ["-x", "hip", "-Rpass-analysis=kernel-resource-usage", "-c", src,
-                                                          "-o", str(tmp / "bc.o")]
-    r = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
-    assert r.returncode == 0, r.stdout[-2000:]
-    table, name = {}, None
-    for line in r.stdout.splitlines():
-        m = re.search(r"Function Name: (\S+)", line)
-        if m:
-            name = m.group(1)
-            table[name] = {}
-            continue
-        m = re.search(r"remark:\s+(VGPRs|ScratchSize \[bytes/lane\]): (\d+)", line)
-        if m and name:
-            table[name][m.group(1).split()[0]] = int(m.group(2))
-    return table
+    return kernel_resource_usage("bc.hip", tmp_path_factory.mktemp("bc_res"))
 
 
 def test_every_instantiation_is_there(usage):
@@ -42,8 +19,7 @@ def test_every_instantiation_is_there(usage):
 
 
 def fmt_of(name):
-    import re as _re
-    return int(_re.search(r"bc_encode_kernelILi(\d)E", name).group(1))
+    return int(re.search(r"bc_encode_kernelILi(\d)E", name).group(1))
 
 
 def test_no_scratch_and_register_budget(usage):

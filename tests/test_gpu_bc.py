@@ -41,8 +41,9 @@ def edge_rgba(h, w, seed=SEED_A):
     return [with_edge_cases(p * 1.2 - 0.1, shift=c) for c, p in enumerate(synthetic_rgba(seed, h, w))]
 
 
-def check(img, fmt, srgb):
-    got = img.to_bc(fmt, srgb)
+def check(img, fmt, srgb, got=None):
+    if got is None:
+        got = img.to_bc(fmt, srgb)
     want = bc_ref.encode(img.to_u8(srgb), fmt)
     assert got.shape == want.shape, (got.shape, want.shape)
     bad = np.argwhere((got != want).any(-1))
@@ -83,6 +84,26 @@ def test_large(kc, size):
     img = kc.SlotImage.from_planes(edge_rgba(size, size))
     for fmt, srgb in FORMS if size == 1024 else [(1, False), (3, True), (5, False)]:
         check(img, fmt, srgb)
+
+
+@pytest.mark.parametrize("option,value", [("tune_cap", 2), ("cache_budget_mb", 0)])
+def test_grid_stride_loop(kc, option, value):
+    """Capped at two workgroups, 512 threads, the 33 x 24 = 792 blocks of 131 x 93 take two rounds, the second partly out of
+    range, with edge blocks in both (the sRGB forms: a thread's first block before the loop, its second in it).  5 x 3 is two
+    blocks: nearly every thread of an sRGB form leaves after the barrier of the threshold table.  cache_budget_mb = 0: the
+    same under the cap, in the nontemporal instantiations."""
+    imgs = [kc.SlotImage.from_planes(edge_rgba(93, 131)).materialize(), kc.SlotImage.from_planes(edge_rgba(3, 5, SEED_B)).materialize()]
+    saved = {o: kc.get_option(o) for o in ("tune_cap", option)}
+    try:
+        kc.set_option("tune_cap", 2)
+        kc.set_option(option, value)
+        got = [[img.to_bc(fmt, srgb) for fmt, srgb in FORMS] for img in imgs]
+    finally:
+        for o, v in saved.items():
+            kc.set_option(o, v)
+    for img, blocks in zip(imgs, got):
+        for (fmt, srgb), g in zip(FORMS, blocks):
+            check(img, fmt, srgb, g)
 
 
 @pytest.mark.parametrize("w", [9, 10, 11, 12])

@@ -1,5 +1,10 @@
 """Shared helpers for the parity tests: synthetic planes, ulp distance,
-bitwise comparison that treats NaN == NaN."""
+bitwise comparison that treats NaN == NaN; and the compiler's resource remarks of a device unit for the build-time guards."""
+import os
+import re
+import shutil
+import subprocess
+
 import numpy as np
 
 SEED_A, SEED_B = 0x5EED0001, 0x5EED0002
@@ -147,3 +152,31 @@ def edge_lines(n, periods, count=3):
             for m in (k * p, n - (n % p or p) - (k - 1) * p):
                 out.update(x for x in (m - 1, m) if 0 <= x < n)
     return sorted(out)
+
+
+def kernel_resource_usage(unit, tmp):
+    """{mangled kernel name: {"VGPRs": n, "ScratchSize": bytes per lane}} of every kernel of csrc/<unit> (a member of the
+    build's SOURCES that includes bc_blocks.h), from a cross-compile with the build's own flags and
+    -Rpass-analysis=kernel-resource-usage; the object goes to the directory `tmp`.  Skips the test without hipcc."""
+    import pytest
+    from kanter_core_amd import build as kbuild
+    hipcc = kbuild._hipcc()
+    if shutil.which(hipcc) is None and not os.path.exists(hipcc):
+        pytest.skip("hipcc not available")
+    assert unit in kbuild.SOURCES and "bc_blocks.h" in kbuild.HEADERS
+    src = os.path.join(os.path.dirname(os.path.abspath(kbuild.__file__)), "csrc", unit)
+    cmd = [hipcc] + kbuild.FLAGS + kbuild.DEVICE_FLAGS + ["-x", "hip", "-Rpass-analysis=kernel-resource-usage", "-c", src,
+                                                          "-o", os.path.join(str(tmp), os.path.splitext(unit)[0] + ".o")]
+    r = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
+    assert r.returncode == 0, r.stdout[-2000:]
+    table, name = {}, None
+    for line in r.stdout.splitlines():
+        m = re.search(r"Function Name: (\S+)", line)
+        if m:
+            name = m.group(1)
+            table[name] = {}
+            continue
+        m = re.search(r"remark:\s+(VGPRs|ScratchSize \[bytes/lane\]): (\d+)", line)
+        if m and name:
+            table[name][m.group(1).split()[0]] = int(m.group(2))
+    return table
