@@ -564,6 +564,66 @@ KC_API int kc_image_write_dds(kc_image *img, const char *path, int format, uint3
  *           is RGBA: R, G and B resident planes that hold the halves' exact f32 values (not bytes / 255: up to 65504), A a
  *           constant plane of 1.  A block with a reserved mode field gives (0, 0, 0), as the format defines, and is not counted.
  *           Blocks of the two-subset modes 1-10 are NOT decoded: they give (0, 0, 0) and are counted in `*undecoded_blocks`.
+ *   KC_BC_ALL_MODES  (a decode-side flag) every mode the two formats define: BC7 modes 0-7 and BC6H modes 1-14, so that another
+ *           encoder's blocks decode in full (tests/bc_modes_ref.py is the same rules in numpy).  Nothing is undecoded:
+ *           `*undecoded_blocks` and kc_bc_error.undecoded_blocks are 0, and the count is written without a wait.
+ *           BC7.  A mode's fields follow one another from bit mode + 1: the partition index (4 bits in mode 0, 6 in modes 1, 2, 3,
+ *           7), the rotation and the index selection (modes 4, 5), every R, every G, every B, then every A, the p-bits, the
+ *           index sets.  Endpoint 2 s + k is endpoint k of subset s.  Per mode: subsets, endpoint bits, p-bits, index bits --
+ *           0: 3, RGB 4, one p-bit per endpoint, 3;  1: 2, RGB 6, one p-bit per subset (shared by its two endpoints), 3;
+ *           2: 3, RGB 5, none, 2;  3: 2, RGB 7, per endpoint, 2;  7: 2, RGBA 5, per endpoint, 2 (alpha takes the colour's index);
+ *           modes 4, 5, 6 as above.  An endpoint channel of n stored bits q and p-bit p is x = 2 q + p in n + 1 bits (x = q
+ *           without p-bits), expanded (x << (8 - bits)) | (x >> (2 bits - 8)); alpha is 255 in modes 0-3.  2-, 3- and 4-bit
+ *           indices weigh by W2, W3 and W4; interp, the rotation and the reserved block (byte 0 == 0) as above.
+ *           The subset of texel t is bit t of the two-subset table's entry, or bits 2t..2t+1 of the three-subset table's:
+ *           two subsets, entries 0-63 (16 bits each):
+ *             CCCC 8888 EEEE ECC8 C880 FEEC FEC8 EC80 C800 FFEC FE80 E800 FFE8 FF00 FFF0 F000
+ *             F710 008E 7100 08CE 008C 7310 3100 8CCE 088C 3110 6666 366C 17E8 0FF0 718E 399C
+ *             AAAA F0F0 5A5A 33CC 3C3C 55AA 9696 A55A 73CE 13C8 324C 3BDC 6996 C33C 9966 0660
+ *             0272 04E4 4E40 2720 C936 936C 39C6 639C 9336 9CC6 817E E718 CCF0 0FCC 7744 EE22
+ *           three subsets, entries 0-63 (32 bits each; mode 0 uses the first 16):
+ *             AA685050 6A5A5040 5A5A4200 5450A0A8 A5A50000 A0A05050 5555A0A0 5A5A5050
+ *             AA550000 AA555500 AAAA5500 90909090 94949494 A4A4A4A4 A9A59450 2A0A4250
+ *             A5945040 0A425054 A5A5A500 55A0A0A0 A8A85454 6A6A4040 A4A45000 1A1A0500
+ *             0050A4A4 AAA59090 14696914 69691400 A08585A0 AA821414 50A4A450 6A5A0200
+ *             A9A58000 5090A0A8 A8A09050 24242424 00AA5500 24924924 24499224 50A50A50
+ *             500AA550 AAAA4444 66660000 A5A0A5A0 50A050A0 69286928 44AAAA44 66666600
+ *             AA444444 54A854A8 95809580 96969600 A85454A8 80959580 AA141414 96960000
+ *             AAAA1414 A05050A0 A0A5A5A0 96000000 40804080 A9A8A9A8 AAAAAA44 2A4A5254
+ *           Anchors.  Texel 0 is the anchor of subset 0; the anchors of the other subsets, per entry:
+ *             two subsets, subset 1:    15 15 15 15 15 15 15 15 15 15 15 15 15 15 15 15 15  2  8  2  2  8  8 15  2  8  2  2  8  8  2  2
+ *                                       15 15  6  8  2  8 15 15  2  8  2  2  2 15 15  6  6  2  6  8 15 15  2  2 15 15 15 15 15  2  2 15
+ *             three subsets, subset 1:   3  3 15 15  8  3 15 15  8  8  6  6  6  5  3  3  3  3  8 15  3  3  6 10  5  8  8  6  8  5 15 15
+ *                                        8 15  3  5  6 10  8 15 15  3 15  5 15 15 15 15  3 15  5  5  5  8  5 10  5 10  8 13 15 12  3  3
+ *             three subsets, subset 2:  15  8  8  3 15 15  3  8 15 15 15 15 15 15 15  8 15  8 15  3 15  8 15  8  3 15  6 10 15 15 10  8
+ *                                       15  3 15 10 10  8  9 10  6 15  8 15  3  6  6  8 15  3 15 15 15 15 15 15 15 15 15 15  3 15 15  8
+ *           An anchor's index has one bit less than the others (its top bit is 0), so in a set of n-bit indices that starts at bit
+ *           `base`, texel t's index lies at base + n t - (the anchors below t) and has n - 1 bits if t is an anchor.
+ *           BC6H.  Modes 1-10 have two subsets: the first 32 entries of the two-subset table and of its anchors, 3-bit indices
+ *           from bit 82 weighed by W3, and per channel four endpoints e0..e3 (subset s: e_2s, e_2s+1).  e0 has n bits; in modes
+ *           1-9 e1, e2, e3 are signed deltas of (dR, dG, dB) bits, e_k = (e0 + sign_extend(delta)) mod 2^n; mode 10 stores four
+ *           plain 6-bit endpoints.  n (dR dG dB) for modes 1-10: 10 (5 5 5), 7 (6 6 6), 11 (5 4 4), 11 (4 5 4), 11 (4 4 5),
+ *           9 (5 5 5), 8 (6 5 5), 8 (5 6 5), 8 (5 5 6), 6 (plain).  The header, in every mode: the low min(n, 10) bits of R0, G0,
+ *           B0 from bits 5, 15, 25; R1, R2, R3 from bits 35, 65, 71 (dR bits each); G1 from bit 45 (dG bits); G2[3:0] and G3[3:0]
+ *           at 41-44 and 51-54; B1 from bit 55 (dB bits); B2[3:0] at 61-64; the partition at 77-81.  The remaining bits, as
+ *           `block bit: value bit`, per mode --
+ *             1:  2:G2[4] 3:B2[4] 4:B3[4] 40:G3[4] 50:B3[0] 60:B3[1] 70:B3[2] 76:B3[3]
+ *             2:  2:G2[5] 3:G3[4] 4:G3[5] 12:B3[0] 13:B3[1] 14:B2[4] 22:B2[5] 23:B3[2] 24:G2[4] 32:B3[3] 33:B3[5] 34:B3[4]
+ *             3:  40:R0[10] 49:G0[10] 50:B3[0] 59:B0[10] 60:B3[1] 70:B3[2] 76:B3[3]
+ *             4:  39:R0[10] 40:G3[4] 50:G0[10] 59:B0[10] 60:B3[1] 69:B3[0] 70:B3[2] 75:G2[4] 76:B3[3]
+ *             5:  39:R0[10] 40:B2[4] 49:G0[10] 50:B3[0] 60:B0[10] 69:B3[1] 70:B3[2] 75:B3[4] 76:B3[3]
+ *             6:  14:B2[4] 24:G2[4] 34:B3[4] 40:G3[4] 50:B3[0] 60:B3[1] 70:B3[2] 76:B3[3]
+ *             7:  13:G3[4] 14:B2[4] 23:B3[2] 24:G2[4] 33:B3[3] 34:B3[4] 50:B3[0] 60:B3[1]
+ *             8:  13:B3[0] 14:B2[4] 23:G2[5] 24:G2[4] 33:G3[5] 34:B3[4] 40:G3[4] 60:B3[1] 70:B3[2] 76:B3[3]
+ *             9:  13:B3[1] 14:B2[4] 23:B2[5] 24:G2[4] 33:B3[5] 34:B3[4] 40:G3[4] 50:B3[0] 70:B3[2] 76:B3[3]
+ *             10: 11:G3[4] 12:B3[0] 13:B3[1] 14:B2[4] 21:G2[5] 22:B2[5] 23:B3[2] 24:G2[4] 31:G3[5] 32:B3[3] 33:B3[5] 34:B3[4]
+ *           unq_n, interp (with its + 32) and fin as above; a reserved mode field gives (0, 0, 0).
+ *           The flag is accepted by kc_image_from_bc, kc_image_from_bc_device, kc_image_read_dds and kc_image_bc_compare, with
+ *           every format: with BC1, BC3, BC4 and BC5 it changes nothing (it combines with KC_BC_GRAY for BC4), so a caller who
+ *           reads arbitrary files can always pass it.  Without it nothing changes.  kc_image_bc_error,
+ *           kc_live_graph_buffer_bc_error, the encoders and the mip exporters refuse it as an unknown bit.  kc_stats: a BC7 or
+ *           BC6H decode under the flag is one launch, with or without `undecoded_blocks`; the comparison stays two.
+ *           kc_bc_error.flags echoes the flag and bc7_mode_blocks is filled as without it.
  *   kc_image_from_bc         `host`: tightly packed block rows, exactly what kc_image_to_bc writes (`host_bytes` at least
  *                            bx * by * block bytes).  `*out` (+1 reference) owns new planes; a decoded byte b is the f32
  *                            b / 255.f with the IEEE divide, as kc_image_from_u8 makes it, so kc_image_to_u8(*out, 0) returns
@@ -575,7 +635,7 @@ KC_API int kc_image_write_dds(kc_image *img, const char *path, int format, uint3
  *                            event edges of kc_image_to_bc_device; nothing aliases the caller's blocks.  With a non-NULL
  *                            `undecoded_blocks` and KC_BC7 or KC_BC6H the call blocks until the count is on the host, as
  *                            kc_image_channel_stats does; with NULL, or another format (count 0), it does not wait.
- *                            Errors, in this order: flag bits other than KC_BC_GRAY (KC_BC_SRGB included), or KC_BC_GRAY with a
+ *                            Errors, in this order: flag bits other than KC_BC_GRAY and KC_BC_ALL_MODES (KC_BC_SRGB included), or KC_BC_GRAY with a
  *                            format other than KC_BC4, KC_ERR_UNSUPPORTED; a NULL argument (`undecoded_blocks` may be NULL), an
  *                            unknown format, a zero size, more than 2^31 blocks, `host_bytes` below the blocks' bytes or a
  *                            descriptor kc_bc_image_validate refuses KC_ERR_INVALID_ARG; KC_ERR_NO_DEVICE before kc_init.
@@ -593,7 +653,7 @@ KC_API int kc_image_write_dds(kc_image *img, const char *path, int format, uint3
  *   kc_image_bc_error        encodes into pool staging with kc_image_to_bc's encoder, then compares.
  *                            kc_live_graph_buffer_bc_error: the same for a slot's image.
  *                            Both block until the host values are there (kc_image_channel_stats' event).  Flags: kc_image_to_bc's
- *                            rule.  Errors, in this order: that rule's KC_ERR_UNSUPPORTED; a NULL argument, an unknown format, a
+ *                            rule; kc_image_bc_compare also takes KC_BC_ALL_MODES.  Errors, in this order: that rule's KC_ERR_UNSUPPORTED; a NULL argument, an unknown format, a
  *                            descriptor kc_bc_image_validate refuses KC_ERR_INVALID_ARG; KC_ERR_NO_DEVICE before kc_init; a
  *                            descriptor size that differs from the image's KC_ERR_INVALID_ARG; KC_ERR_NO_SLOT_DATA where
  *                            kc_live_graph_buffer_bc returns it.  `*out` is written on KC_OK only.  A pending chain or resample
@@ -613,12 +673,13 @@ KC_API int kc_image_write_dds(kc_image *img, const char *path, int format, uint3
  *                            dxgiFormat 95 file kc_image_write_dds writes for KC_BC6H is not read back: pass its blocks, from
  *                            byte 148 on, to kc_image_from_bc); `levels`
  *                            above the level count, or a buffer shorter than data_offset + data_bytes, KC_ERR_INVALID_ARG.
- *   kc_image_read_dds        kc_image_from_bc of level `level` of the file (kc_bc_mip_layout's offsets).  flags: KC_BC_GRAY only.
+ *   kc_image_read_dds        kc_image_from_bc of level `level` of the file (kc_bc_mip_layout's offsets).  flags: KC_BC_GRAY | KC_BC_ALL_MODES.
  *                            `info` (optional) is written once the header has parsed.  Errors, in this order: flag bits other
- *                            than KC_BC_GRAY KC_ERR_UNSUPPORTED; a NULL path or `out` KC_ERR_INVALID_ARG; a file that cannot be
+ *                            than these two KC_ERR_UNSUPPORTED; a NULL path or `out` KC_ERR_INVALID_ARG; a file that cannot be
  *                            opened or read KC_ERR_IO; kc_dds_parse's errors (a file shorter than its header says is
  *                            KC_ERR_INVALID_ARG); level >= levels KC_ERR_INVALID_ARG; then kc_image_from_bc's. */
 #define KC_BC_GRAY 4u  /* decode, BC4 only: a Gray image of the channel instead of the RGBA rule */
+#define KC_BC_ALL_MODES 16u  /* decode and kc_image_bc_compare: every BC7 and BC6H mode, partitioned ones included; 8 stays refused */
 typedef struct kc_bc_error {
     int32_t format;              /* kc_bc_format of the blocks */
     uint32_t flags;              /* the flags the call was given */

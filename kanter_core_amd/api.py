@@ -750,6 +750,11 @@ def _channel_stats(call, histogram, srgb):
 
 
 BC_GRAY = 4  # kc_image_from_bc, BC4 only: a Gray image of the channel instead of the RGBA rule
+BC_ALL_MODES = 16  # the decode side (from_bc, from_bc_torch, read_dds, bc_error with blocks): every BC7 and BC6H mode, partitioned ones included
+
+
+def _decode_flags(gray, all_modes):
+    return (BC_GRAY if gray else 0) | (BC_ALL_MODES if all_modes else 0)
 
 
 class BcError(collections.namedtuple("BcError", "format flags channel_mask pixels sse max_abs undecoded_blocks bc7_mode_blocks")):
@@ -773,9 +778,9 @@ class BcError(collections.namedtuple("BcError", "format flags channel_mask pixel
         return float("inf") if sse == 0 else float(10 * np.log10(peak ** 2 * self.pixels * len(chans) / sse))
 
 
-def _bc_error(call, srgb):
+def _bc_error(call, srgb, all_modes=False):
     r = _lib.kc_bc_error()
-    _check(call(BC_SRGB if srgb else 0, C.byref(r)))
+    _check(call((BC_SRGB if srgb else 0) | (BC_ALL_MODES if all_modes else 0), C.byref(r)))
     return BcError(int(r.format), int(r.flags), int(r.channel_mask), int(r.pixels), np.array(r.sse[:], np.uint64), np.array(r.max_abs[:], np.uint32),
                    int(r.undecoded_blocks), np.array(r.bc7_mode_blocks[:], np.uint64))
 
@@ -868,40 +873,43 @@ class SlotImage:
         return SlotImage(out.value)
 
     @staticmethod
-    def from_bc(blocks, width, height, fmt, gray=False, return_undecoded=False):
+    def from_bc(blocks, width, height, fmt, gray=False, return_undecoded=False, all_modes=False):
         """The image BC blocks decode to (kc_image_from_bc): uint8 (ceil(h/4), ceil(w/4), block bytes) as to_bc returns them,
         decoded on the device by the header's integer rules; to_u8() of the result is exactly the decoded bytes.  RGBA (BC4:
         (r, 0, 0, 1), BC5: (r, g, 0, 1), the missing channels constant planes); gray=True, BC4 only: a Gray image.  BC7: modes
         4, 5 and 6; blocks of the partitioned modes give (0, 0, 0, 0) and return_undecoded=True returns (image, their count).
         BC6H: the single-subset modes 11-14; R, G and B hold the decoded halves' exact values (up to 65504, not bytes / 255), A
-        is a constant 1; blocks of the two-subset modes 1-10 give (0, 0, 0) and are counted likewise."""
+        is a constant 1; blocks of the two-subset modes 1-10 give (0, 0, 0) and are counted likewise.  all_modes=True
+        (KC_BC_ALL_MODES): every BC7 mode 0-7 and BC6H mode 1-14 is decoded, as another encoder's blocks need it, and the count
+        is 0; with the other formats it changes nothing."""
         f = _bc_format(fmt)
         blocks = np.ascontiguousarray(blocks, np.uint8)
         out, n = C.c_void_p(), C.c_uint64()
-        _check(_lib.load().kc_image_from_bc(blocks.ctypes.data, blocks.nbytes, width, height, f, BC_GRAY if gray else 0, C.byref(out),
+        _check(_lib.load().kc_image_from_bc(blocks.ctypes.data, blocks.nbytes, width, height, f, _decode_flags(gray, all_modes), C.byref(out),
                                             C.byref(n) if return_undecoded else None))
         img = SlotImage(out.value)
         return (img, n.value) if return_undecoded else img
 
     @staticmethod
-    def from_bc_torch(t, width, height, fmt, gray=False, return_undecoded=False):
+    def from_bc_torch(t, width, height, fmt, gray=False, return_undecoded=False, all_modes=False):
         """from_bc of a uint8 (ceil(h/4), ceil(w/4), block bytes) tensor in device memory (kc_image_from_bc_device); any view
         whose last two dimensions are contiguous.  Ordered on torch's current stream: the image owns its pixels, the tensor may be
-        freed or overwritten by torch as soon as this returns.  return_undecoded=True waits for the count (BC7, BC6H)."""
+        freed or overwritten by torch as soon as this returns.  return_undecoded=True waits for the count (BC7, BC6H; not with
+        all_modes=True, whose count is 0)."""
         d = _bc_desc(t, width, height, fmt)
         out, n = C.c_void_p(), C.c_uint64()
-        _check(_on_torch_stream(t, lambda stream: _lib.load().kc_image_from_bc_device(C.byref(d), BC_GRAY if gray else 0, stream, C.byref(out),
+        _check(_on_torch_stream(t, lambda stream: _lib.load().kc_image_from_bc_device(C.byref(d), _decode_flags(gray, all_modes), stream, C.byref(out),
                                                                                        C.byref(n) if return_undecoded else None)))
         img = SlotImage(out.value)
         return (img, n.value) if return_undecoded else img
 
     @staticmethod
-    def read_dds(path, level=0, gray=False, return_info=False):
+    def read_dds(path, level=0, gray=False, return_info=False, all_modes=False):
         """Level `level` of a .dds file of BC1, BC3, BC4, BC5 or BC7 blocks, decoded as from_bc (kc_image_read_dds);
         return_info=True returns (image, DdsInfo).  A BC6H file (dxgiFormat 95), which write_dds can write, is refused as
-        Unsupported here: pass its blocks to from_bc."""
+        Unsupported here: pass its blocks to from_bc.  all_modes=True: as from_bc's, for files of other encoders."""
         out, d = C.c_void_p(), _lib.kc_dds_info()
-        _check(_lib.load().kc_image_read_dds(os.fspath(path).encode(), level, BC_GRAY if gray else 0, C.byref(out), C.byref(d)))
+        _check(_lib.load().kc_image_read_dds(os.fspath(path).encode(), level, _decode_flags(gray, all_modes), C.byref(out), C.byref(d)))
         img = SlotImage(out.value)
         return (img, _dds_info(d)) if return_info else img
 
@@ -993,19 +1001,23 @@ class SlotImage:
         """Writes a .dds file (DX10 header) with the image's BC blocks: the whole mip chain, or level 0 alone (kc_image_write_dds)."""
         _check(_lib.load().kc_image_write_dds(self._h, os.fspath(path).encode(), _bc_format(fmt), BC_SRGB if srgb else 0, int(mips)))
 
-    def bc_error(self, fmt, srgb=False, blocks=None):
+    def bc_error(self, fmt, srgb=False, blocks=None, all_modes=False):
         """-> BcError: how far the image's BC encoding is from the image, measured on the device (kc_image_bc_error): the bytes
         the blocks decode to against the bytes to_u8(srgb) writes, over the image's pixels (BC6H: half bit patterns).  blocks: a uint8 (ceil(h/4), ceil(w/4),
         block bytes) tensor in device memory to compare instead of the library's own encoding (kc_image_bc_compare), e.g.
-        another encoder's.  Blocks until the values are there."""
+        another encoder's; all_modes=True decodes every BC7 and BC6H mode of such blocks (from_bc's), so that undecoded_blocks
+        is 0.  The library's own encoding needs no such flag: all_modes=True without blocks is a ValueError.  Blocks until the
+        values are there."""
         f = _bc_format(fmt)
+        if blocks is None and all_modes:
+            raise ValueError("all_modes is for blocks=...: the library's own blocks are single-subset modes")
         if blocks is None:
             return _bc_error(lambda fl, out: _lib.load().kc_image_bc_error(self._h, f, fl, out), srgb)
         s = self.size()
         d = _bc_desc(blocks, s.width, s.height, f)
         import torch
         torch.cuda.current_stream(blocks.device).synchronize()  # the call runs on the library's stream: the blocks must be there
-        return _bc_error(lambda fl, out: _lib.load().kc_image_bc_compare(self._h, C.byref(d), fl, out), srgb)
+        return _bc_error(lambda fl, out: _lib.load().kc_image_bc_compare(self._h, C.byref(d), fl, out), srgb, all_modes)
 
     def channel_stats(self, histogram=False, srgb=False):
         """-> ChannelStats of the image, computed on the device (kc_image_channel_stats): the range and NaN count of every

@@ -72,6 +72,7 @@ int bc_check_flags(int format, uint32_t flags, uint32_t allowed, const char *who
         return KC_ERR_UNSUPPORTED;
     }
     const BcFormat *f = bc_format(format);
+    // KC_BC_ALL_MODES, where an entry point allows it, goes with every format: a caller who reads arbitrary files can always pass it
     if ((flags & KC_BC_SRGB) && f && !f->srgb) {
         set_error(std::string(who) + ": KC_BC_SRGB is for BC1, BC3 and BC7 only");
         return KC_ERR_UNSUPPORTED;
@@ -123,7 +124,9 @@ uint32_t bc_source_operands(const kc_image *img, uint32_t mask, Operand (&o)[4])
 }
 
 // ---------------------------------------------------------------- the device unit of a format
-// BC6H's three kernels are bc6h.hip's, BC7's encoder bc7.hip's; everything else is bc.hip's and bc_decode.hip's
+// BC6H's three kernels are bc6h.hip's, BC7's encoder bc7.hip's; everything else is bc.hip's and bc_decode.hip's.  all_modes
+// (KC_BC_ALL_MODES): the formats with modes that the default decoders leave out -- the table's counts_undecoded, BC7 and BC6H --
+// go to bc_modes.hip, which leaves none out and therefore takes no count; for the other formats the flag changes nothing
 hipError_t bc_launch_encode(int format, bool srgb, const Operand op[4], int gray, char *dst, uint64_t row_pitch, uint32_t w, uint32_t h,
                             uint32_t nt_mask, hipStream_t s)
 {
@@ -132,15 +135,20 @@ hipError_t bc_launch_encode(int format, bool srgb, const Operand op[4], int gray
     return launch_bc_encode(format, srgb ? 1 : 0, op, gray, dst, row_pitch, w, h, nt_mask, s);
 }
 
-hipError_t bc_launch_decode(int format, const BcDecodeArgs &a, bool count, uint32_t nt_mask, uint32_t groups, hipStream_t s)
+hipError_t bc_launch_decode(int format, bool all_modes, const BcDecodeArgs &a, bool count, uint32_t nt_mask, uint32_t groups, hipStream_t s)
 {
+    const BcFormat *f = bc_format(format);
+    if (all_modes && f && f->counts_undecoded) return count ? hipErrorInvalidValue : launch_bc_modes_decode(format, a, nt_mask, groups, s);
     if (format == KC_BC6H) return launch_bc6h_decode(a, count, nt_mask, groups, s);
     return launch_bc_decode(format, a, count, nt_mask, groups, s);
 }
 
-hipError_t bc_launch_compare(int format, bool srgb, const Operand op[4], int gray, const char *blocks, uint64_t row_pitch, uint32_t w, uint32_t h,
-                             uint32_t nt_mask, uint32_t groups, unsigned long long *partials, unsigned long long *result, hipStream_t s)
+hipError_t bc_launch_compare(int format, bool srgb, bool all_modes, const Operand op[4], int gray, const char *blocks, uint64_t row_pitch, uint32_t w,
+                             uint32_t h, uint32_t nt_mask, uint32_t groups, unsigned long long *partials, unsigned long long *result, hipStream_t s)
 {
+    const BcFormat *f = bc_format(format);
+    if (all_modes && f && f->counts_undecoded)
+        return launch_bc_modes_compare(format, srgb ? 1 : 0, op, gray, blocks, row_pitch, w, h, nt_mask, groups, partials, result, s);
     if (format == KC_BC6H) return launch_bc6h_compare(op, gray, blocks, row_pitch, w, h, nt_mask, groups, partials, result, s);
     return launch_bc_compare(format, srgb ? 1 : 0, op, gray, blocks, row_pitch, w, h, nt_mask, groups, partials, result, s);
 }

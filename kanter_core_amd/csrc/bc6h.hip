@@ -16,46 +16,9 @@
 namespace kc {
 
 #include "streaming.h"  // grid_cap, ld_policy / st_policy
-#include "bc_blocks.h"  // the packed types and lanes, the block walk, the row loaders, the plane-row store and the record fold
-
-// h(v): NaN, the negatives, -0 and -inf fail the comparison and give 0; +inf and everything >= 65504 give 0x7BFF.  The
-// conversion rounds to nearest even and keeps denormal halves, as devimage.hip's F16 export does.  The compiler makes one
-// median of the two clamps, which may hand -0 through: the callers clear the sign bit, and no other result has it set.
-static __device__ __forceinline__ uint32_t quant_half(float v)
-{
-    float x = v > 0.0f ? v : 0.0f;
-    x = x < 65504.0f ? x : 65504.0f;
-    return (uint32_t)__builtin_bit_cast(uint16_t, (_Float16)x);
-}
-
-// Row y of a block's texels as half bit patterns, rg = R | G << 16 and bl = B (Gray: (v, v, v)); alpha is never read
-static __device__ __forceinline__ void bc6h_quantise_row(const bc_f4 (&v)[4], int gray, int y, uint32_t (&rg)[16], uint32_t (&bl)[16])
-{
-#pragma unroll
-    for (int x = 0; x < 4; ++x) {
-        const uint32_t r = quant_half(v[0][x]);
-        const uint32_t g = gray ? r : quant_half(v[1][x]);
-        const uint32_t b = gray ? r : quant_half(v[2][x]);
-        rg[4 * y + x] = (r | (g << 16)) & 0x7fff7fffu;
-        bl[4 * y + x] = b & 0x7fffu;
-    }
-}
+#include "bc_blocks.h"  // the packed types and lanes, the block walk, the row loaders, the plane-row store, the record fold and BC6H's rules
 
 static __device__ __forceinline__ uint32_t bc6h_w4(uint32_t i) { return (64u * i + 7u) / 15u; }  // 0, 4, 9, 13, ..., 60, 64
-
-// fin(interp(u0, u1, w)): the half bit pattern of a palette entry from two 16-bit endpoints; 31 * 65535 fits with room
-static __device__ __forceinline__ uint32_t bc6h_entry(uint32_t u0, uint32_t u1, uint32_t w)
-{
-    return (31u * (((64u - w) * u0 + w * u1 + 32u) >> 6)) >> 6;
-}
-
-// unq_n(x): an n-bit endpoint as 16 bits
-static __device__ __forceinline__ uint32_t bc6h_unq(uint32_t x, uint32_t n)
-{
-    const uint32_t top = (1u << n) - 1u;
-    const uint32_t mid = ((x << 16) + 0x8000u) >> n;  // n <= 12 here: x << 16 stays below 2^28
-    return n == 16u ? x : x == 0u ? 0u : x == top ? 0xffffu : mid;
-}
 
 // E(q) = fin(unq_10(q)): what a 10-bit endpoint decodes to at weight 0: 0, 46, 77, ..., 31 q + 15, ..., 31697, 31743
 // (as arithmetic on the two comparisons: a chain of selects on q becomes a switch, and the switch divergent branches)
@@ -223,9 +186,6 @@ static __device__ __forceinline__ bool bc6h_decode_block(const char *p, uint32_t
     const uint32_t b[4] = { v.x, v.y, v.z, v.w };
     return decode_bc6h(b, rg, bl);
 }
-
-// the exact f32 value of a half bit pattern
-static __device__ __forceinline__ float half_value(uint32_t bits) { return (float)__builtin_bit_cast(_Float16, (uint16_t)bits); }
 
 // Writes dst[0..2] = R, G, B.  COUNT: the workgroup's undecoded blocks go to a.partials[blockIdx.x]
 template <bool NT, bool COUNT>

@@ -1,7 +1,7 @@
-// What the block-compression units share -- bc.hip (BC1, BC3, BC4, BC5), bc7.hip, bc6h.hip and bc_decode.hip: the packed types,
+// What the block-compression units share -- bc.hip (BC1, BC3, BC4, BC5), bc7.hip, bc6h.hip, bc_decode.hip and bc_modes.hip: the packed types,
 // the kernels' arguments and grid, the walk over the blocks with its edge rule, the row loaders, the 8-bit quantiser, the column
-// clamp, the staging of the sRGB table, the decoders' plane-row store, and the fold of a workgroup's counts and sums into one
-// record.  The encoder and comparison kernels write their grid-stride loops out over these steps: the loop as one shared
+// clamp, the staging of the sRGB table, the decoders' plane-row store, the fold of a workgroup's counts and sums into one
+// record, and BC6H's quantiser and endpoint rules.  The encoder and comparison kernels write their grid-stride loops out over these steps: the loop as one shared
 // function compiled the sRGB forms to slower code (see DESIGN, "Where the family's code lies").  A thread holds its block's texels as packed 16-bit
 // lanes, rb = R | B << 16 and ga = G | A << 16 (BC6H: rg = R | G << 16 and bl = B, in the same two arrays).
 // Included inside namespace kc after streaming.h; every definition is static, each unit keeps its own copy.
@@ -224,3 +224,44 @@ static __device__ __forceinline__ void bc_fold_record(unsigned long long (&val)[
         out[k] = k >= 4 && k < 8 ? max(max(r0, r1), max(r2, r3)) : r0 + r1 + r2 + r3;
     }
 }
+
+// ---------------------------------------------------------------- BC6H's rules, for bc6h.hip and bc_modes.hip
+// h(v): NaN, the negatives, -0 and -inf fail the comparison and give 0; +inf and everything >= 65504 give 0x7BFF.  The
+// conversion rounds to nearest even and keeps denormal halves, as devimage.hip's F16 export does.  The compiler makes one
+// median of the two clamps, which may hand -0 through: the callers clear the sign bit, and no other result has it set.
+static __device__ __forceinline__ uint32_t quant_half(float v)
+{
+    float x = v > 0.0f ? v : 0.0f;
+    x = x < 65504.0f ? x : 65504.0f;
+    return (uint32_t)__builtin_bit_cast(uint16_t, (_Float16)x);
+}
+
+// Row y of a block's texels as half bit patterns, rg = R | G << 16 and bl = B (Gray: (v, v, v)); alpha is never read
+static __device__ __forceinline__ void bc6h_quantise_row(const bc_f4 (&v)[4], int gray, int y, uint32_t (&rg)[16], uint32_t (&bl)[16])
+{
+#pragma unroll
+    for (int x = 0; x < 4; ++x) {
+        const uint32_t r = quant_half(v[0][x]);
+        const uint32_t g = gray ? r : quant_half(v[1][x]);
+        const uint32_t b = gray ? r : quant_half(v[2][x]);
+        rg[4 * y + x] = (r | (g << 16)) & 0x7fff7fffu;
+        bl[4 * y + x] = b & 0x7fffu;
+    }
+}
+
+// fin(interp(u0, u1, w)): the half bit pattern of a palette entry from two 16-bit endpoints; 31 * 65535 fits with room
+static __device__ __forceinline__ uint32_t bc6h_entry(uint32_t u0, uint32_t u1, uint32_t w)
+{
+    return (31u * (((64u - w) * u0 + w * u1 + 32u) >> 6)) >> 6;
+}
+
+// unq_n(x): an n-bit endpoint as 16 bits
+static __device__ __forceinline__ uint32_t bc6h_unq(uint32_t x, uint32_t n)
+{
+    const uint32_t top = (1u << n) - 1u;
+    const uint32_t mid = ((x << 16) + 0x8000u) >> n;  // n <= 12 here: x << 16 stays below 2^28
+    return n == 16u ? x : x == 0u ? 0u : x == top ? 0xffffu : mid;
+}
+
+// the exact f32 value of a half bit pattern
+static __device__ __forceinline__ float half_value(uint32_t bits) { return (float)__builtin_bit_cast(_Float16, (uint16_t)bits); }

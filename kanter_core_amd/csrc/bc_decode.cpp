@@ -17,11 +17,11 @@ static int bcd_refuse(const char *who, const char *what)
     return KC_ERR_INVALID_ARG;
 }
 
-// Flag bits other than KC_BC_GRAY, or KC_BC_GRAY with a format other than BC4, are KC_ERR_UNSUPPORTED
+// Flag bits other than KC_BC_GRAY and KC_BC_ALL_MODES, or KC_BC_GRAY with a format other than BC4, are KC_ERR_UNSUPPORTED
 static int bcd_check_flags(int format, uint32_t flags, const char *who)
 {
-    if (flags & ~(uint32_t)KC_BC_GRAY) {
-        set_error(std::string(who) + ": flags other than KC_BC_GRAY (no transfer function is applied on decode)");
+    if (flags & ~(uint32_t)(KC_BC_GRAY | KC_BC_ALL_MODES)) {
+        set_error(std::string(who) + ": flags other than KC_BC_GRAY and KC_BC_ALL_MODES (no transfer function is applied on decode)");
         return KC_ERR_UNSUPPORTED;
     }
     const BcFormat *f = bc_format(format);
@@ -43,10 +43,12 @@ static int bcd_fetch(uint32_t words)
 }
 
 // One launch of the decoder (two with a count) on the library's stream: the blocks at `src`, block rows `row_pitch` bytes apart,
-// into a new image.  *counted: the count is in flight and bcd_fetch brings it.
-static int bc_decode(const char *src, size_t row_pitch, uint32_t w, uint32_t h, int format, bool gray, bool want_count, kc_image **out,
+// into a new image.  *counted: the count is in flight and bcd_fetch brings it.  KC_BC_ALL_MODES in `flags`: every block is
+// decoded, so nothing is counted and the caller's count is 0 without a wait.
+static int bc_decode(const char *src, size_t row_pitch, uint32_t w, uint32_t h, int format, uint32_t flags, bool want_count, kc_image **out,
                      bool *counted)
 {
+    const bool gray = (flags & KC_BC_GRAY) != 0, all_modes = (flags & KC_BC_ALL_MODES) != 0;
     Context &c = ctx();
     const BcFormat &f = *bc_format(format);  // the entry points have refused an unknown format
     const int n_res = f.planes, n = gray ? 1 : 4;
@@ -56,7 +58,7 @@ static int bc_decode(const char *src, size_t row_pitch, uint32_t w, uint32_t h, 
         if (i < n_res) s = plane_new_mem(w, h, &p[i]);
         else p[i] = plane_new_const(w, h, i == 3 ? 1.0f : 0.0f);  // the sampling convention: missing G, B = 0, A = 1
     }
-    const bool count = want_count && f.counts_undecoded;
+    const bool count = want_count && f.counts_undecoded && !all_modes;
     BcDecodeArgs a{};
     uint32_t groups = 0;
     if (s == KC_OK) {
@@ -77,7 +79,7 @@ static int bc_decode(const char *src, size_t row_pitch, uint32_t w, uint32_t h, 
     }
     if (s == KC_OK) {
         const uint64_t in_bytes = bc_level_bytes(w, h, f), out_bytes = (uint64_t)w * h * 4 * n_res;
-        hipError_t e = bc_launch_decode(format, a, count, cache_policy_mask(in_bytes, out_bytes, 1), groups, c.stream);
+        hipError_t e = bc_launch_decode(format, all_modes, a, count, cache_policy_mask(in_bytes, out_bytes, 1), groups, c.stream);
         if (e != hipSuccess) s = hip_fail(e, "launch_bc_decode");
         else {
             c.launches += count ? 2 : 1;
@@ -110,7 +112,7 @@ int image_from_bc(const uint8_t *host, size_t host_bytes, uint32_t w, uint32_t h
     kc_image *img = nullptr;
     bool counted = false;
     hipError_t e = hipMemcpyAsync(staging.ptr, host, nbytes, hipMemcpyHostToDevice, c.stream);
-    int s = e == hipSuccess ? bc_decode((const char *)staging.ptr, (size_t)bx * f->block_bytes, w, h, format, (flags & KC_BC_GRAY) != 0,
+    int s = e == hipSuccess ? bc_decode((const char *)staging.ptr, (size_t)bx * f->block_bytes, w, h, format, flags,
                                         undecoded_blocks != nullptr, &img, &counted)
                             : KC_OK;
     if (s == KC_OK && e == hipSuccess && counted) s = bcd_fetch(1);
@@ -135,7 +137,7 @@ int image_from_bc_device(const kc_bc_image *src, uint32_t flags, void *hip_strea
     kc_image *img = nullptr;
     bool counted = false;
     int s = with_stream_edges(hip_stream, [&] {
-        return bc_decode((const char *)src->ptr, src->row_pitch_bytes, src->width, src->height, src->format, (flags & KC_BC_GRAY) != 0,
+        return bc_decode((const char *)src->ptr, src->row_pitch_bytes, src->width, src->height, src->format, flags,
                          undecoded_blocks != nullptr, &img, &counted);
     });
     if (s == KC_OK && counted) s = bcd_fetch(1);
@@ -164,7 +166,7 @@ static int bc_compare(kc_image *img, int format, uint32_t flags, const char *blo
     const uint64_t blk_bytes = bc_level_bytes(w, h, f);
     const uint32_t nt_mask = cache_policy_mask(in_bytes + blk_bytes, 0, n_res ? n_res : 1);
     unsigned long long *partials = (unsigned long long *)c.stats.partials;
-    hipError_t e = bc_launch_compare(format, (flags & KC_BC_SRGB) != 0, o, img->is_rgba() ? 0 : 1, blocks, row_pitch, w, h, nt_mask, groups, partials,
+    hipError_t e = bc_launch_compare(format, (flags & KC_BC_SRGB) != 0, (flags & KC_BC_ALL_MODES) != 0, o, img->is_rgba() ? 0 : 1, blocks, row_pitch, w, h, nt_mask, groups, partials,
                                      c.stats.result, c.stream);
     if (e != hipSuccess) return hip_fail(e, "launch_bc_compare");
     c.launches += 2;
@@ -189,7 +191,7 @@ static int bc_compare(kc_image *img, int format, uint32_t flags, const char *blo
 
 int image_bc_compare(kc_image *img, const kc_bc_image *blocks, uint32_t flags, kc_bc_error *out)
 {
-    KC_TRY(bc_check_flags(blocks ? blocks->format : 0, flags, KC_BC_SRGB, "kc_image_bc_compare"));
+    KC_TRY(bc_check_flags(blocks ? blocks->format : 0, flags, KC_BC_SRGB | KC_BC_ALL_MODES, "kc_image_bc_compare"));
     if (!img || !out) return bcd_refuse("kc_image_bc_compare", "NULL image or output");
     KC_TRY(bc_image_validate(blocks, nullptr));
     if (img->w() != blocks->width || img->h() != blocks->height) return bcd_refuse("kc_image_bc_compare", "descriptor size differs from the image's");
@@ -273,8 +275,8 @@ int dds_parse(const uint8_t *data, size_t bytes, kc_dds_info *info)
 
 int image_read_dds(const char *path, uint32_t level, uint32_t flags, kc_image **out, kc_dds_info *info)
 {
-    if (flags & ~(uint32_t)KC_BC_GRAY) {
-        set_error("kc_image_read_dds: flags other than KC_BC_GRAY");
+    if (flags & ~(uint32_t)(KC_BC_GRAY | KC_BC_ALL_MODES)) {
+        set_error("kc_image_read_dds: flags other than KC_BC_GRAY and KC_BC_ALL_MODES");
         return KC_ERR_UNSUPPORTED;
     }
     if (!path || !out) return bcd_refuse("kc_image_read_dds", "NULL path or output");

@@ -349,6 +349,15 @@ hipError_t launch_bc6h_encode(const Operand op[4], int gray, char *dst, uint64_t
 hipError_t launch_bc6h_decode(const BcDecodeArgs &a, bool count, uint32_t nt_mask, uint32_t groups, hipStream_t s);
 hipError_t launch_bc6h_compare(const Operand op[4], int gray, const char *blocks, uint64_t row_pitch, uint32_t w, uint32_t h, uint32_t nt_mask,
                                uint32_t groups, unsigned long long *partials, unsigned long long *result, hipStream_t s);
+// -- bc_modes.hip --
+// KC_BC_ALL_MODES for KC_BC7 and KC_BC6H: every mode of the two formats, partition tables included (bc_modes.h has the decoders).
+// bc7_modes_decode_kernel<nt> / bc6h_modes_decode_kernel<nt>: launch_bc_decode's arguments; nothing is undecoded, so there is no
+// count and no second launch (a.partials and a.result are not used).  bc7_modes_compare_kernel<srgb, nt> /
+// bc6h_modes_compare_kernel<nt>, then bc_combine_kernel: launch_bc_compare's arguments and record, word 8 always 0.
+hipError_t launch_bc_modes_decode(int fmt, const BcDecodeArgs &a, uint32_t nt_mask, uint32_t groups, hipStream_t s);
+hipError_t launch_bc_modes_compare(int fmt, int srgb, const Operand op[4], int gray, const char *blocks, uint64_t row_pitch, uint32_t w,
+                                   uint32_t h, uint32_t nt_mask, uint32_t groups, unsigned long long *partials, unsigned long long *result,
+                                   hipStream_t s);
 // -- mip.hip --
 // Mip chains (mip.hip / mip.cpp): the 2 x 2 box of the header on the n_planes distinct resident planes of one image.
 // mip_pyramid_kernel<nt>: levels 1..n (1 <= n <= 6, both of w >> n and h >> n still >= 1) of the w x h source planes, one

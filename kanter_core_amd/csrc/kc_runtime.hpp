@@ -410,8 +410,8 @@ int bc_encode(kc_image *img, int format, bool srgb, char *dst, size_t row_pitch,
 // the launchers of kc_internal.hpp by format: the one place that knows which device unit holds a format's kernels
 hipError_t bc_launch_encode(int format, bool srgb, const Operand op[4], int gray, char *dst, uint64_t row_pitch, uint32_t w, uint32_t h,
                             uint32_t nt_mask, hipStream_t s);
-hipError_t bc_launch_decode(int format, const BcDecodeArgs &a, bool count, uint32_t nt_mask, uint32_t groups, hipStream_t s);
-hipError_t bc_launch_compare(int format, bool srgb, const Operand op[4], int gray, const char *blocks, uint64_t row_pitch, uint32_t w, uint32_t h,
+hipError_t bc_launch_decode(int format, bool all_modes, const BcDecodeArgs &a, bool count, uint32_t nt_mask, uint32_t groups, hipStream_t s);
+hipError_t bc_launch_compare(int format, bool srgb, bool all_modes, const Operand op[4], int gray, const char *blocks, uint64_t row_pitch, uint32_t w, uint32_t h,
                              uint32_t nt_mask, uint32_t groups, unsigned long long *partials, unsigned long long *result, hipStream_t s);
 // block decode, the error of an encoding and .dds input (bc_decode.cpp): the bodies of kc_image_from_bc, kc_image_from_bc_device,
 // kc_image_bc_compare, kc_image_bc_error, kc_dds_parse and kc_image_read_dds

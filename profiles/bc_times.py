@@ -11,6 +11,13 @@ kc_image_to_u8 plus the numpy reference encoder (tests/bc_ref.py) for the same b
 
 The cases run in a fixed order, each as one warm-up call and `reps` timed calls, so the report assigns the trace's dispatches to
 the cases by their order.
+
+The all-modes decoders (KC_BC_ALL_MODES, csrc/bc_modes.hip) against the single-subset ones, in the same way and in one session,
+the two forms alternating: decode and compare of BC7 and BC6H, on the library's own blocks (both forms give the same image) and
+on tests/bc_modes_ref.py's random blocks of every (mode, partition) pair (the default form leaves the partitioned ones black).
+
+    rocprofv3 --kernel-trace --output-format csv -d DIR -- python profiles/bc_times.py modes-run [reps]
+    python profiles/bc_times.py modes-report DIR/.../*_kernel_trace.csv run.log    -> the table at the end of bc_decode_times.txt
 """
 import csv
 import os
@@ -138,8 +145,82 @@ def report(trace_csv, log):
     print("\n".join(out))
 
 
+# ------------------------------------------------------------------ every mode against the single-subset decoders
+# (name, fmt, kind, blocks "own" | "every mode", all_modes): the two forms of a case follow one another
+MODE_CASES = [("%s %s, %s blocks, %s" % (_kind, "BC7" if _fmt == BC7 else "BC6H", _blocks, "all modes" if _all else "default"), _fmt, _kind, _blocks, _all)
+              for _fmt in (BC7, BC6H) for _kind in ("decode", "compare") for _blocks in ("own", "every mode") for _all in (False, True)]
+MODE_KERNELS = ("bc_decode_kernel", "bc6h_decode_kernel", "bc7_modes_decode_kernel", "bc6h_modes_decode_kernel", "bc_compare_kernel",
+                "bc6h_compare_kernel", "bc7_modes_compare_kernel", "bc6h_modes_compare_kernel")
+
+
+def modes_kernel(fmt, kind, all_modes):
+    if all_modes:
+        return "%s_modes_%s_kernel" % ("bc7" if fmt == BC7 else "bc6h", kind)
+    return "%s_%s_kernel" % ("bc" if fmt == BC7 else "bc6h", kind)
+
+
+def modes_run(reps):
+    import torch
+
+    import kanter_core_amd as kc
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import bc_modes_ref
+    kc.init(0)
+    imgs = {BC7: kc.SlotImage.from_planes(planes_for(4, "random")).materialize(), BC6H: kc.SlotImage.from_planes(planes_for(4, "hdr random")).materialize()}
+    blocks = {}
+    for fmt in (BC7, BC6H):
+        blocks[fmt, "own"] = imgs[fmt].to_bc_torch(fmt)
+        blocks[fmt, "every mode"] = torch.from_numpy(bc_modes_ref.random_image_blocks(fmt, N, N)).cuda()
+    kc.sync()
+    torch.cuda.synchronize()
+    for name, fmt, kind, which, all_modes in MODE_CASES:
+        blk = blocks[fmt, which]
+        if kind == "decode":
+            call = lambda: kc.SlotImage.from_bc_torch(blk, N, N, fmt, all_modes=all_modes)  # noqa: E731
+        else:
+            call = lambda: imgs[fmt].bc_error(fmt, blocks=blk, all_modes=all_modes)  # noqa: E731
+        call()  # warm-up
+        torch.cuda.synchronize()
+        b0 = kc.stats()["algorithmic_bytes"]
+        for _ in range(reps):
+            call()
+        torch.cuda.synchronize()
+        kc.sync()
+        print("bytes %-50s %d per call" % (name, (kc.stats()["algorithmic_bytes"] - b0) // reps))
+    print("reps %d" % reps)
+
+
+def modes_report(trace_csv, log):
+    lines = open(log).read().splitlines()
+    reps = int(next(x.split()[1] for x in lines if x.startswith("reps ")))
+    rows = list(csv.DictReader(open(trace_csv)))
+    col = lambda key: next(k for k in rows[0] if key in k)  # noqa: E731
+    kn, ks, ke = col("Kernel_Name"), col("Start_Timestamp"), col("End_Timestamp")
+    rows.sort(key=lambda r: int(r[ks]))
+    ours = [r for r in rows if any(n + "<" in r[kn] or n + "I" in r[kn] for n in MODE_KERNELS)]
+    per = reps + 1
+    assert len(ours) == len(MODE_CASES) * per, (len(ours), len(MODE_CASES) * per)
+    out = ["Every mode against the single-subset decoders (KC_BC_ALL_MODES), %d x %d, MI355X, one session, the forms alternating; kernel times "
+           "from rocprofv3 --kernel-trace (median of %d calls after a warm-up), fraction of %.0f TB/s as above; the compare rows are the "
+           "comparison kernel alone" % (N, N, reps, PEAK_TBS), ""]
+    out.append("%-52s %10s %10s %9s" % ("case", "median us", "alg MB", "of 8TB/s"))
+    for i, (name, fmt, kind, _, all_modes) in enumerate(MODE_CASES):
+        seg = ours[i * per:(i + 1) * per]
+        assert all(modes_kernel(fmt, kind, all_modes) in r[kn] for r in seg), (name, [r[kn][:40] for r in seg])
+        ns = statistics.median([int(r[ke]) - int(r[ks]) for r in seg[1:]])
+        b = case_bytes(4, kind, fmt)
+        out.append("%-52s %10.1f %10.1f %9.3f" % (name, ns / 1e3, b / 1e6, b / ns / 1e3 / PEAK_TBS))
+    out.append("")
+    out += ["  " + x.rstrip() for x in lines if x.startswith("bytes ")]
+    print("\n".join(out))
+
+
 if __name__ == "__main__":
-    if sys.argv[1] == "run":
+    if sys.argv[1] == "modes-run":
+        modes_run(int(sys.argv[2]) if len(sys.argv) > 2 else 20)
+    elif sys.argv[1] == "modes-report":
+        modes_report(sys.argv[2], sys.argv[3])
+    elif sys.argv[1] == "run":
         run(int(sys.argv[2]) if len(sys.argv) > 2 else 20)
     else:
         report(sys.argv[2], sys.argv[3])
