@@ -8,7 +8,7 @@ import json
 import numpy as np
 import pytest
 
-from util import SEED_A, SEED_B, splitmix_plane, synthetic_rgba, with_edge_cases
+from util import SEED_A, SEED_B, key_range, splitmix_plane, synthetic_rgba, with_edge_cases
 
 pytestmark = pytest.mark.gpu
 
@@ -37,20 +37,6 @@ def counted(kc, img, **kw):
     l0, b0 = launches(kc), kc.stats()["algorithmic_bytes"]
     img.channel_stats(**kw)
     return launches(kc) - l0, kc.stats()["algorithmic_bytes"] - b0
-
-
-def key_range(plane):
-    """(min bits, max bits, NaN count) of a plane through the order key; None bits when it holds no non-NaN value."""
-    a = np.ascontiguousarray(plane, np.float32).reshape(-1).view(np.uint32)
-    nan = (a & 0x7fffffff) > 0x7f800000
-    k = np.where(a >> 31 == 1, ~a, a | np.uint32(0x80000000))[~nan]
-    if k.size == 0:
-        return None, None, int(nan.sum())
-
-    def back(key):
-        key = np.uint32(key)
-        return int(key & np.uint32(0x7fffffff)) if key >> np.uint32(31) else int(~key)
-    return back(k.min()), back(k.max()), int(nan.sum())
 
 
 def bits(x):

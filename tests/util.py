@@ -89,6 +89,20 @@ def assert_planes(got, want, ulp=0, what=""):
             assert max_ulp(g, w) <= ulp, "%s plane %d: max ulp %s > %d" % (what, c, max_ulp(g, w), ulp)
 
 
+def key_range(plane):
+    """(min bits, max bits, NaN count) of a plane through the order key; None bits when it holds no non-NaN value."""
+    a = np.ascontiguousarray(plane, np.float32).reshape(-1).view(np.uint32)
+    nan = (a & 0x7fffffff) > 0x7f800000
+    k = np.where(a >> 31 == 1, ~a, a | np.uint32(0x80000000))[~nan]
+    if k.size == 0:
+        return None, None, int(nan.sum())
+
+    def back(key):
+        key = np.uint32(key)
+        return int(key & np.uint32(0x7fffffff)) if key >> np.uint32(31) else int(~key)
+    return back(k.min()), back(k.max()), int(nan.sum())
+
+
 def pow_mismatch(got, want):
     """Where `got` breaks the Pow contract against `want` (both f32): a match is bit-equal (any NaN matches any NaN) or, for
     two finite nonzero values of the same sign, one ulp apart.  So a zero's sign, inf against FLT_MAX and a flushed
