@@ -207,7 +207,13 @@ KC_API int kc_stats_algorithmic_bytes(uint64_t *bytes);
  * "chain1_nt<0-7>" (a one-step kernel with its nontemporal bits: 1 the start plane, 2 the operand, 4 the result),
  * "specialized_nt_<3 hex digits>" (a kernel compiled at run time and its cache-policy bits: 0x001 << k input plane k < 8,
  * 0x100 the result), "specialized_nt_<3 hex digits>_q2" / "_q4" when that kernel handles 2 / 4 float4 per lane instead of one
- * (kc_set_chain_quads).  The mip kernels (one per launch): "mip_pyramid", "mip_level". */
+ * (kc_set_chain_quads).  The mip kernels (one per launch): "mip_pyramid", "mip_level", and "mip_nt" for each of those launches
+ * that reads its source nontemporally.  The streaming kernels, by the form each launch took: HeightToNormal "h2n_launches", one
+ * of "h2n_plain", "h2n_tiled_q5", "h2n_tiled_q6", "h2n_tiled_q7" (a row per 256 threads, or tiles of 32, 64, 128 column
+ * quads), "h2n_band" (a row band with its halo row), "h2n_nt" (nontemporal stores); the u8 boundary "to_u8_nt", "from_u8_nt"
+ * (kc_image_to_u8 / _from_u8 and the u8 pipe); device images "image_import_vec" or "image_import_scalar" and
+ * "image_export_vec" or "image_export_scalar" (whether the descriptor's alignment allows whole-quad accesses),
+ * "image_import_nt", "image_export_nt"; "stats_nt" (kc_image_channel_stats). */
 KC_API int kc_stats_counter(const char *name, uint64_t *value);
 KC_API int kc_pool_trim(void);
 /* Run-time specialisation of the fused Mix-chain kernel.  A chain of N Mix nodes (src/node/mix.rs:136-192

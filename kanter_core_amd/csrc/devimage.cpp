@@ -150,9 +150,12 @@ int image_from_device(const kc_device_image *src, uint32_t flags, void *hip_stre
         s = with_stream_edges(hip_stream, [&] {
             const DevImageArgs a = devimage_args(src);
             const uint64_t in_bytes = (uint64_t)w * h * n * elem_bytes(src->dtype), out_bytes = (uint64_t)w * h * 4 * n;
-            hipError_t e = launch_image_import(src->dtype, a, dp, (uint32_t)(p[0]->pitch / 4), cache_policy_mask(in_bytes, out_bytes, 1), c.stream);
+            bool nt = false;
+            hipError_t e = launch_image_import(src->dtype, a, dp, (uint32_t)(p[0]->pitch / 4), cache_policy_mask(in_bytes, out_bytes, 1), c.stream, &nt);
             if (e != hipSuccess) return hip_fail(e, "launch_image_import");
             c.launches++;
+            c.counters[a.vec ? "image_import_vec" : "image_import_scalar"]++;
+            if (nt) c.counters["image_import_nt"]++;
             c.alg_bytes += in_bytes + out_bytes;
             return (int)KC_OK;
         });
@@ -188,10 +191,13 @@ int image_to_device(kc_image *img, const kc_device_image *dst, uint32_t flags, v
     return with_stream_edges(hip_stream, [&] {
         const uint64_t in_bytes = (uint64_t)w * h * 4 * n_res, out_bytes = (uint64_t)w * h * n * elem_bytes(dst->dtype);
         const DevImageArgs a = devimage_args(dst);
+        bool nt = false;
         hipError_t e = launch_image_export(dst->dtype, srgb ? 1 : 0, o, rgba ? 0 : 1, a, cache_policy_mask(in_bytes, out_bytes, n_res ? n_res : 1),
-                                           c.stream);
+                                           c.stream, &nt);
         if (e != hipSuccess) return hip_fail(e, "launch_image_export");
         c.launches++;
+        c.counters[a.vec ? "image_export_vec" : "image_export_scalar"]++;
+        if (nt) c.counters["image_export_nt"]++;
         c.alg_bytes += in_bytes + out_bytes;
         return (int)KC_OK;
     });

@@ -263,7 +263,8 @@ static uint64_t devimage_blocks(const DevImageArgs &a)
     return blocks;
 }
 
-hipError_t launch_image_import(int dtype, const DevImageArgs &a, float *const planes[4], uint32_t ppitch, uint32_t nt_mask, hipStream_t s)
+hipError_t launch_image_import(int dtype, const DevImageArgs &a, float *const planes[4], uint32_t ppitch, uint32_t nt_mask, hipStream_t s,
+                               bool *launched_nt)
 {
     const uint64_t blocks = devimage_blocks(a);
     if (blocks == 0) return hipSuccess;
@@ -287,10 +288,12 @@ hipError_t launch_image_import(int dtype, const DevImageArgs &a, float *const pl
     }
 #undef KC_IMPORT_L
 #undef KC_IMPORT
+    if (launched_nt) *launched_nt = nt;
     return hipGetLastError();
 }
 
-hipError_t launch_image_export(int dtype, int srgb, const Operand op[4], int gray, const DevImageArgs &a, uint32_t nt_mask, hipStream_t s)
+hipError_t launch_image_export(int dtype, int srgb, const Operand op[4], int gray, const DevImageArgs &a, uint32_t nt_mask, hipStream_t s,
+                               bool *launched_nt)
 {
     const uint64_t blocks = devimage_blocks(a);
     if (blocks == 0) return hipSuccess;
@@ -318,6 +321,7 @@ hipError_t launch_image_export(int dtype, int srgb, const Operand op[4], int gra
     }
 #undef KC_EXPORT_L
 #undef KC_EXPORT
+    if (launched_nt) *launched_nt = nt;
     return hipGetLastError();
 }
 

@@ -265,7 +265,7 @@ __global__ __launch_bounds__(256) void height_to_normal_kernel(const float *__re
 
 // h = rows to produce; band != 0: `hgt` has h + 1 rows (halo row first) and full_h is the whole image's height.
 hipError_t launch_height_to_normal(const float *hgt, uint32_t hpitch, uint32_t w, uint32_t h, uint32_t full_h, int band,
-                                   float *nx, float *ny, float *nz, uint32_t opitch, uint32_t nt_mask, hipStream_t s)
+                                   float *nx, float *ny, float *nz, uint32_t opitch, uint32_t nt_mask, hipStream_t s, H2nVariant *var)
 {
     const bool nts = (nt_mask & 0x100u) != 0;  // the height plane is re-read by neighbouring rows: never marked
     const uint64_t total = (uint64_t)((w + 3) / 4) * h;
@@ -296,6 +296,7 @@ hipError_t launch_height_to_normal(const float *hgt, uint32_t hpitch, uint32_t w
     else if (nts) KC_H2N(false, true);
     else KC_H2N(false, false);
 #undef KC_H2N
+    if (var) *var = H2nVariant{ true, band != 0, nts, tiled ? tq : 0u };
     return hipGetLastError();
 }
 

@@ -260,14 +260,22 @@ struct UpsamplePlanes {
 hipError_t launch_upsample_chain(const ChainProgram &p, int batch, const UpsampleArgs &u, hipStream_t s);
 hipError_t launch_upsample(const UpsamplePlanes &p, int batch, const UpsampleArgs &u, hipStream_t s);
 // -- h2n.hip --
+// What launch_height_to_normal launched (ops.cpp counts it: kc_stats_counter): height_to_normal_kernel<band, nt, tq != 0>
+// with tiles of 2^tq quads (tq = 0: the plain mapping); launched = false: nothing (an empty plane)
+struct H2nVariant {
+    bool launched = false, band = false, nt = false;
+    uint32_t tq = 0;
+};
 // nt_mask: the launch's cache policy as cache_policy_mask() returns it (bits 0-7: inputs, bit 8: results)
 hipError_t launch_height_to_normal(const float *hgt, uint32_t hpitch, uint32_t w, uint32_t h, uint32_t full_h, int band,
-                                   float *nx, float *ny, float *nz, uint32_t opitch, uint32_t nt_mask, hipStream_t s);
+                                   float *nx, float *ny, float *nz, uint32_t opitch, uint32_t nt_mask, hipStream_t s, H2nVariant *var);
 // -- u8.hip --
+// *launched_nt (here and in devimage.hip's launchers): whether the instantiation launched is the nontemporal one (left alone
+// when nothing is launched: an empty image)
 hipError_t launch_to_u8(Operand r, Operand g, Operand b, Operand a, int gray, int srgb, uint32_t w, uint32_t h,
-                        uint8_t *dst, uint32_t nt_mask, hipStream_t s);
+                        uint8_t *dst, uint32_t nt_mask, hipStream_t s, bool *launched_nt);
 hipError_t launch_from_u8(const uint8_t *src, int channels, uint32_t w, uint32_t h, float *const planes[4],
-                          uint32_t pitch, uint32_t nt_mask, hipStream_t s);
+                          uint32_t pitch, uint32_t nt_mask, hipStream_t s, bool *launched_nt);
 // -- devimage.hip --
 // Device-memory images (devimage.hip / devimage.cpp): a validated kc_device_image as the kernels take it.  vec != 0: the pointer
 // and the pitches are aligned for the widest access of a whole pixel quad (devimage.cpp, devimage_vec).
@@ -279,10 +287,12 @@ struct DevImageArgs {
     int vec;
 };
 // image_import_kernel: the first `channels` planes of `planes` are written (pitch in floats); nt_mask bit 8: nontemporal stores
-hipError_t launch_image_import(int dtype, const DevImageArgs &a, float *const planes[4], uint32_t ppitch, uint32_t nt_mask, hipStream_t s);
+hipError_t launch_image_import(int dtype, const DevImageArgs &a, float *const planes[4], uint32_t ppitch, uint32_t nt_mask, hipStream_t s,
+                               bool *launched_nt);
 // image_export_kernel: channel c of the output is op[c]; gray != 0: op[0] stands for R, G and B (read once); nt_mask bits 0-7:
 // nontemporal plane loads; srgb: U8 only
-hipError_t launch_image_export(int dtype, int srgb, const Operand op[4], int gray, const DevImageArgs &a, uint32_t nt_mask, hipStream_t s);
+hipError_t launch_image_export(int dtype, int srgb, const Operand op[4], int gray, const DevImageArgs &a, uint32_t nt_mask, hipStream_t s,
+                               bool *launched_nt);
 // -- stats.hip --
 // Per-channel statistics (stats.hip / stats.cpp): the n distinct resident planes ("slots") of one image.  Bit s of srgb: slot
 // s bins with the sRGB quantiser.  partials: one record of rec_words u32 per workgroup (stats.hip has the layout); result:

@@ -149,6 +149,7 @@ int image_build_mips(kc_image *img, uint32_t flags, kc_image **levels, uint32_t 
                 c.counters["mip_level"]++;
                 k += 1;
             }
+            if (nt) c.counters["mip_nt"]++;
             c.launches++;
         }
         uint64_t texels = (uint64_t)w * h;  // level 0 read once, every further level written once

@@ -111,9 +111,11 @@ int image_from_u8(const uint8_t *host, uint32_t w, uint32_t h, int channels, kc_
         } else {
             e = hipMemcpyAsync(staging, host, nbytes, hipMemcpyHostToDevice, c.stream);
         }
+        bool nt = false;
         if (e == hipSuccess)
             e = launch_from_u8((const uint8_t *)staging, channels, w, h, dp, (uint32_t)(p[0]->pitch / 4),
-                               cache_policy_mask((uint64_t)w * h * channels, (uint64_t)w * h * 4 * channels, 1), c.stream);
+                               cache_policy_mask((uint64_t)w * h * channels, (uint64_t)w * h * 4 * channels, 1), c.stream, &nt);
+        if (e == hipSuccess && nt) c.counters["from_u8_nt"]++;
         if (e == hipSuccess && !slot) e = hipStreamSynchronize(c.stream);
         if (e != hipSuccess) s = hip_fail(e, "image_from_u8");
         else {
@@ -143,10 +145,12 @@ int image_to_u8(kc_image *img, bool srgb, uint8_t *host)
     for (int i = 0; i < 4; ++i) o[i] = plane_operand(img->planes[img->is_rgba() ? i : 0]);
     uint32_t n_res = 0;
     for (int i = 0; i < (img->is_rgba() ? 4 : 1); ++i) n_res += o[i].ptr != nullptr;
+    bool nt = false;
     hipError_t e = launch_to_u8(o[0], o[1], o[2], o[3], img->is_rgba() ? 0 : 1, srgb ? 1 : 0, w, h, (uint8_t *)staging,
-                                cache_policy_mask((uint64_t)w * h * 4 * n_res, nbytes, n_res ? n_res : 1), c.stream);
+                                cache_policy_mask((uint64_t)w * h * 4 * n_res, nbytes, n_res ? n_res : 1), c.stream, &nt);
     if (e == hipSuccess) {
         c.launches++;
+        if (nt) c.counters["to_u8_nt"]++;
         int resident = 0;
         for (int i = 0; i < (img->is_rgba() ? 4 : 1); ++i) resident += o[i].ptr != nullptr;
         c.alg_bytes += (uint64_t)w * h * 4 * (resident + 1);
@@ -355,14 +359,21 @@ static int height_to_normal_impl(kc_image *in, uint32_t full_h, kc_image **out)
     int s = KC_OK;
     for (int i = 0; i < 3 && s == KC_OK; ++i) s = plane_new_mem(w, h, &p[i]);
     if (s == KC_OK) {
+        H2nVariant v;
         hipError_t e = launch_height_to_normal(src->dptr, (uint32_t)(src->pitch / 4), w, h, band ? full_h : h, band ? 1 : 0,
                                                p[0]->dptr, p[1]->dptr, p[2]->dptr, (uint32_t)(p[0]->pitch / 4),
                                                // three result planes against one input: once they do not all fit the
                                                // Infinity Cache the results are streamed (49.6 against 51.6 us at 4096^2)
-                                               cache_policy_mask((uint64_t)w * h * 4, (uint64_t)w * h * 12, 1) ? 0x100u : 0u, c.stream);
+                                               cache_policy_mask((uint64_t)w * h * 4, (uint64_t)w * h * 12, 1) ? 0x100u : 0u, c.stream, &v);
         if (e != hipSuccess) s = hip_fail(e, "launch_height_to_normal");
         else {
             c.launches++;
+            if (v.launched) {
+                c.counters["h2n_launches"]++;
+                c.counters[v.tq == 0 ? "h2n_plain" : v.tq == 5 ? "h2n_tiled_q5" : v.tq == 6 ? "h2n_tiled_q6" : "h2n_tiled_q7"]++;
+                if (v.band) c.counters["h2n_band"]++;
+                if (v.nt) c.counters["h2n_nt"]++;
+            }
             c.alg_bytes += (uint64_t)w * h * 16;  // 4 B read + 12 B written per pixel
         }
     }

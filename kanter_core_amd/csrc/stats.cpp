@@ -154,6 +154,7 @@ int image_channel_stats(kc_image *img, uint32_t flags, kc_channel_stats *out)
         hipError_t e = launch_channel_stats(a, hist, srgb && a.srgb != 0, nt, groups, c.stream);
         if (e != hipSuccess) return hip_fail(e, "launch_channel_stats");
         c.launches += 2;
+        if (nt) c.counters["stats_nt"]++;
         c.alg_bytes += in_bytes;
         KC_HIP(hipMemcpyAsync(c.stats.host, c.stats.result, a.rec_words * sizeof(unsigned long long), hipMemcpyDeviceToHost, c.stream));
         KC_HIP(hipEventRecord(c.stats.done, c.stream));

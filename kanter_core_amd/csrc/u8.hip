@@ -87,7 +87,7 @@ __global__ __launch_bounds__(256) void to_u8_kernel(Operand r, Operand g, Operan
 }
 
 hipError_t launch_to_u8(Operand r, Operand g, Operand b, Operand a, int gray, int srgb, uint32_t w, uint32_t h,
-                        uint8_t *dst, uint32_t nt_mask, hipStream_t s)
+                        uint8_t *dst, uint32_t nt_mask, hipStream_t s, bool *launched_nt)
 {
     const bool ntl = (nt_mask & 0xffu) != 0;
     const uint64_t total = (uint64_t)((w + 3) / 4) * h;
@@ -102,6 +102,7 @@ hipError_t launch_to_u8(Operand r, Operand g, Operand b, Operand a, int gray, in
         to_u8_kernel<false, true><<<dim3((unsigned)blocks), 256, 0, s>>>(r, g, b, a, gray, w, h, dst);
     else
         to_u8_kernel<false, false><<<dim3((unsigned)blocks), 256, 0, s>>>(r, g, b, a, gray, w, h, dst);
+    if (launched_nt) *launched_nt = ntl;
     return hipGetLastError();
 }
 
@@ -131,16 +132,18 @@ __global__ __launch_bounds__(256) void from_u8_kernel(const uint8_t *__restrict_
 }
 
 hipError_t launch_from_u8(const uint8_t *src, int channels, uint32_t w, uint32_t h, float *const planes[4],
-                          uint32_t pitch, uint32_t nt_mask, hipStream_t s)
+                          uint32_t pitch, uint32_t nt_mask, hipStream_t s, bool *launched_nt)
 {
     const uint64_t total = (uint64_t)w * h;
     if (total == 0) return hipSuccess;
     uint64_t blocks = (total + 255) / 256;
     if (blocks > grid_cap(1u << 30)) blocks = grid_cap(1u << 30);
-    if (nt_mask & 0x100u)
+    const bool nts = (nt_mask & 0x100u) != 0;
+    if (nts)
         from_u8_kernel<true><<<dim3((unsigned)blocks), 256, 0, s>>>(src, channels, w, h, planes[0], planes[1], planes[2], planes[3], pitch);
     else
         from_u8_kernel<false><<<dim3((unsigned)blocks), 256, 0, s>>>(src, channels, w, h, planes[0], planes[1], planes[2], planes[3], pitch);
+    if (launched_nt) *launched_nt = nts;
     return hipGetLastError();
 }
 

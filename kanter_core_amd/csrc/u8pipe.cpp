@@ -138,9 +138,11 @@ int u8_pipe_upload(kc_u8_pipe *p, int slot, kc_image **out)
         if (e == hipSuccess) e = hipMemcpyAsync(s->dev_in, s->host_in, p->in_bytes, hipMemcpyHostToDevice, p->up);
         if (e == hipSuccess) e = hipEventRecord(s->copied_in, p->up);
         if (e == hipSuccess) e = hipStreamWaitEvent(c.stream, s->copied_in, 0);
+        bool nt = false;
         if (e == hipSuccess)
             e = launch_from_u8(s->dev_in, p->channels, p->w, p->h, dp, (uint32_t)(pl[0]->pitch / 4),
-                               cache_policy_mask(p->in_bytes, (uint64_t)p->w * p->h * 4 * p->channels, 1), c.stream);
+                               cache_policy_mask(p->in_bytes, (uint64_t)p->w * p->h * 4 * p->channels, 1), c.stream, &nt);
+        if (e == hipSuccess && nt) c.counters["from_u8_nt"]++;
         if (e == hipSuccess) e = hipEventRecord(s->converted, c.stream);
         if (e != hipSuccess) st = hip_fail(e, "kc_u8_pipe_upload");
         else {
@@ -171,9 +173,11 @@ int u8_pipe_download(kc_u8_pipe *p, int slot, kc_image *img, bool srgb)
     for (int i = 0; i < (img->is_rgba() ? 4 : 1); ++i) n_res += o[i].ptr != nullptr;
     hipError_t e = hipSuccess;
     if (s->out_used) e = hipStreamWaitEvent(c.stream, s->copied_out, 0);  // the slot's previous image has left dev_out
+    bool nt = false;
     if (e == hipSuccess)
         e = launch_to_u8(o[0], o[1], o[2], o[3], img->is_rgba() ? 0 : 1, srgb ? 1 : 0, p->w, p->h, s->dev_out,
-                         cache_policy_mask((uint64_t)p->w * p->h * 4 * n_res, p->out_bytes, n_res ? n_res : 1), c.stream);
+                         cache_policy_mask((uint64_t)p->w * p->h * 4 * n_res, p->out_bytes, n_res ? n_res : 1), c.stream, &nt);
+    if (e == hipSuccess && nt) c.counters["to_u8_nt"]++;
     if (e == hipSuccess) e = hipEventRecord(s->packed, c.stream);
     if (e == hipSuccess) e = hipStreamWaitEvent(p->down, s->packed, 0);
     if (e == hipSuccess) e = hipMemcpyAsync(s->host_out, s->dev_out, p->out_bytes, hipMemcpyDeviceToHost, p->down);
