@@ -139,6 +139,12 @@ impl SlotImage {
         check(unsafe { kc_image_to_bc_mips(self.raw(), format, flags, out.as_mut_ptr(), out.len()) })?;
         Ok((out, offsets))
     }
+    /// The mip level a preview of at most `max_extent` texels a side is cut from (kc_preview_level): (level, its size).  No device.
+    pub fn preview_level(size: Size, max_extent: u32) -> Result<(u32, Size)> {
+        let (mut level, mut w, mut h) = (0u32, 0u32, 0u32);
+        check(unsafe { kc_preview_level(size.width, size.height, max_extent, &mut level, &mut w, &mut h) })?;
+        Ok((level, Size::new(w, h)))
+    }
     /// The image that tightly packed BC blocks decode to (kc_image_from_bc), decoded on the device: to_u8 of the result is exactly
     /// the decoded bytes.  `gray` (BC4 only): a Gray image of the channel.  Also returns the BC7 blocks of partitioned modes,
     /// which are not decoded and give (0, 0, 0, 0).

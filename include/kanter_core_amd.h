@@ -498,6 +498,9 @@ KC_API int kc_image_to_bc_device(kc_image *img, const kc_bc_image *dst, uint32_t
  *             deferred resizes run first.  Planes are linear f32 and sRGB is applied at export (KC_BC_SRGB, kc_image_to_u8 with
  *             srgb), so the average is taken in linear light.
  *   kc_mip_level_count   L for a size; arithmetic, no kc_init needed.
+ *   kc_preview_level     the level a thumbnail or a viewport of at most max_extent texels a side is cut from: the smallest k with
+ *                        max(W_k, H_k) <= max_extent, and that level's size (k < L always: the last level is 1 x 1).  Arithmetic, no
+ *                        kc_init needed.  max_extent == 0, a zero size or a NULL output is KC_ERR_INVALID_ARG and writes nothing.
  *   kc_image_build_mips  levels[0] = img itself (+1 reference), levels[k] a new image of the same kind (+1 reference each);
  *                        `*count` = L whenever the image is known; cap < L is KC_ERR_INVALID_ARG with nothing launched and nothing
  *                        allocated.  Enqueued on the library's stream; the call does not wait.  A failure part-way releases what
@@ -529,6 +532,8 @@ KC_API int kc_image_to_bc_device(kc_image *img, const kc_bc_image *dst, uint32_t
 #define KC_MIP_PER_LEVEL 2u  /* one launch of the one-level kernel per level instead of the fused pyramid kernel; a bit of its
                                 own beside KC_BC_SRGB, since the chain exporters take both in one flags word */
 KC_API int kc_mip_level_count(uint32_t width, uint32_t height, uint32_t *levels);
+KC_API int kc_preview_level(uint32_t width, uint32_t height, uint32_t max_extent, uint32_t *level, uint32_t *level_width,
+                            uint32_t *level_height);
 KC_API int kc_image_build_mips(kc_image *img, uint32_t flags, kc_image **levels, uint32_t cap, uint32_t *count);
 KC_API int kc_bc_mip_layout(uint32_t width, uint32_t height, int format, uint32_t *levels, size_t *offsets, uint32_t cap,
                             size_t *total_bytes);

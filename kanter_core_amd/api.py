@@ -683,6 +683,14 @@ def mip_level_count(width, height):
     return n.value
 
 
+def preview_level(width, height, max_extent):
+    """-> (level, level width, level height): the first mip level of a width x height image whose larger extent is at most
+    max_extent -- the level a thumbnail of that size is cut from (kc_preview_level; no device)."""
+    k, w, h = C.c_uint32(), C.c_uint32(), C.c_uint32()
+    _check(_lib.load().kc_preview_level(width, height, max_extent, C.byref(k), C.byref(w), C.byref(h)))
+    return k.value, w.value, h.value
+
+
 def bc_mip_layout(width, height, fmt):
     """-> (offsets, total_bytes) of the BC mip chain of a width x height image (kc_bc_mip_layout; no device): level k's tightly
     packed blocks start at offsets[k], the chain is total_bytes long."""

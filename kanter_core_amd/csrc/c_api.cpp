@@ -814,6 +814,12 @@ try {
 }
 KC_CATCH
 
+int kc_preview_level(uint32_t width, uint32_t height, uint32_t max_extent, uint32_t *level, uint32_t *level_width, uint32_t *level_height)
+try {
+    return preview_level(width, height, max_extent, level, level_width, level_height);
+}
+KC_CATCH
+
 int kc_image_build_mips(kc_image *img, uint32_t flags, kc_image **levels, uint32_t cap, uint32_t *count)
 try {
     Lock api_lock(ctx().mu);  // reference counts are plain integers, see kc_plane::refs

@@ -1,4 +1,4 @@
-// Mip chains and their export (include/kanter_core_amd.h): kc_mip_level_count, kc_image_build_mips, kc_bc_mip_layout,
+// Mip chains and their export (include/kanter_core_amd.h): kc_mip_level_count, kc_preview_level, kc_image_build_mips, kc_bc_mip_layout,
 // kc_image_to_bc_mips, kc_image_to_bc_mips_device, kc_dds_header, kc_image_write_dds.  The host side does the level arithmetic,
 // folds constant planes with the device's expression, allocates the level planes and enqueues mip.hip's kernels on the library's
 // stream: the pyramid kernel while both extents still halve (up to six levels per launch), the one-level kernel for the rest and
@@ -25,6 +25,18 @@ int mip_level_count(uint32_t w, uint32_t h, uint32_t *levels)
 }
 
 static uint32_t level_extent(uint32_t v, uint32_t k) { return k < 32 && (v >> k) ? v >> k : 1u; }
+
+int preview_level(uint32_t w, uint32_t h, uint32_t max_extent, uint32_t *level, uint32_t *pw, uint32_t *ph)
+{
+    if (!level || !pw || !ph || w == 0 || h == 0 || max_extent == 0)
+        return mip_refuse("kc_preview_level", "NULL output, zero size or zero extent");
+    uint32_t k = 0;
+    while ((w > h ? w : h) >> k > max_extent) ++k;  // max_extent >= 1: ends at the 1 x 1 level at the latest
+    *level = k;
+    *pw = level_extent(w, k);
+    *ph = level_extent(h, k);
+    return KC_OK;
+}
 
 // The contract's expression on a constant plane, once per level: ((c + c) + (c + c)) * 0.25f in f32.  It is not c for very
 // large c (c + c overflows) or denormal c (the product rounds), so nothing is shortcut; the volatile temporaries keep the
