@@ -274,7 +274,16 @@ KC_API int kc_plane_alloc(uint32_t width, uint32_t height, kc_plane **out);
 /* Broadcast constant: what `vec![v; n]` (src/slot_image.rs:28-64) and the 1x1 Value plane
  * (src/node/mod.rs:240-244) hold, kept as a scalar until somebody needs the bytes. */
 KC_API int kc_plane_const(uint32_t width, uint32_t height, float value, kc_plane **out);
-/* Wrap caller-owned device memory (e.g. a torch tensor); not freed by the library. */
+/* Wrap caller-owned device memory (e.g. a torch tensor, a view into a larger one, another library's surface); not freed by
+ * the library.  device_ptr must be 16-byte aligned and pitch_bytes a multiple of 16, at least 16 * ceil(width / 4); nothing
+ * more is assumed of either (no 32-, 64- or 256-byte row starts, no pitch equal to the pool's), else KC_ERR_INVALID_ARG.
+ * What the library may READ through the plane: for each row y in [0, height) the 16 * ceil(width / 4) bytes from
+ * device_ptr + y * pitch_bytes -- the row's pixels and the tail of its last quad of four floats -- and nothing else: not
+ * the rest of the padding between rows, not the bytes before the first row or after the last.  The up to three floats of a
+ * last quad's tail may be loaded but never reach a pixel, whatever they hold (NaN, infinities).  The library never WRITES
+ * there: every operation on a wrapped plane puts its result into planes of its own.  The memory must stay valid and
+ * unchanged until the work that reads it is done (kc_sync) and the plane is released.  tests/test_gpu_wrapped_planes.py runs
+ * every plane-reading kernel on such planes inside guard-filled tensors. */
 KC_API int kc_plane_wrap(void *device_ptr, uint32_t width, uint32_t height, size_t pitch_bytes, kc_plane **out);
 KC_API int kc_plane_retain(kc_plane *p);
 KC_API int kc_plane_release(kc_plane *p);

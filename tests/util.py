@@ -168,6 +168,81 @@ def edge_lines(n, periods, count=3):
     return sorted(out)
 
 
+GUARD_ROWS = 8  # rows of guard above and below a wrapped view inside its parent tensor
+
+
+def wrap_layout(name, w):
+    """(pitch, column offset) in floats of a named layout of a caller-owned plane `w` wide (q = 4 * ceil(w / 4)): "tight" rows
+    q apart, "pad48" q + 12 (48 bytes of padding), "offset" q + 68 with the view 4 floats in: every row starts 16 bytes off a
+    32-byte boundary and the pitch is no multiple of 64 bytes."""
+    q = (w + 3) // 4 * 4
+    return {"tight": (q, 0), "pad48": (q + 12, 0), "offset": (q + 68, 4)}[name]
+
+
+MIXED = ["tight", "pad48", "offset", "pool"]  # the layouts of R, G, B, A of a "mixed" RGBA image
+
+
+class WrappedImage:
+    """What wrapped_image returns: .image (the SlotImage), .planes (the pixels, numpy) and the parent tensors it keeps alive."""
+
+    def __init__(self, kc, torch, image, planes, parents):
+        self.kc, self.torch, self.image, self.planes, self.parents = kc, torch, image, planes, parents
+
+    def assert_untouched(self):
+        """Every parent tensor still holds the bits of its host copy: the library only reads a wrapped plane."""
+        self.kc.sync()
+        self.torch.cuda.synchronize()
+        for k, (t, host) in enumerate(self.parents):
+            now = t.cpu().numpy().view(np.uint32)
+            assert np.array_equal(now, host.view(np.uint32)), "parent tensor %d: %d words written" % (k, int((now != host.view(np.uint32)).sum()))
+
+
+def wrapped_image(kc, torch, planes, layouts, guard):
+    """A SlotImage (Gray for one plane, RGBA for four) whose planes are kc_plane_wrap views into parent tensors filled with
+    `guard`.  layouts: one entry per plane (or one for all) -- a name of wrap_layout, a (pitch_floats, col_offset_floats) pair,
+    "pool" (a plane of the library's pool with the same pixels) or ("const", v) (a constant plane).  The parent of a view is
+    (GUARD_ROWS + h + GUARD_ROWS, pitch) float32; the view starts at row GUARD_ROWS, column col_offset, so everything a kernel
+    could read beside the pixels -- the tail of the last quad, the padding, the rows before and after -- is guard and lies
+    inside memory the test owns."""
+    import ctypes as C
+    from kanter_core_amd import _lib
+    L = _lib.load()
+    planes = [np.ascontiguousarray(p, np.float32) for p in planes]
+    assert len(planes) in (1, 4)
+    h, w = planes[0].shape
+    if isinstance(layouts, (str, tuple)):
+        layouts = [layouts] * len(planes)
+    assert len(layouts) == len(planes)
+    handles, parents = [], []
+    for p, lay in zip(planes, layouts):
+        hnd = C.c_void_p()
+        if lay == "pool":
+            assert L.kc_plane_alloc(w, h, C.byref(hnd)) == 0
+            assert L.kc_plane_upload_f32(hnd, p.ctypes.data, w * 4) == 0
+        elif isinstance(lay, tuple) and lay[0] == "const":
+            assert L.kc_plane_const(w, h, float(lay[1]), C.byref(hnd)) == 0
+        else:
+            pitch, off = wrap_layout(lay, w) if isinstance(lay, str) else lay
+            assert pitch % 4 == 0 and off % 4 == 0 and off + (w + 3) // 4 * 4 <= pitch, (lay, w)
+            host = np.full((GUARD_ROWS + h + GUARD_ROWS, pitch), guard, np.float32)
+            host[GUARD_ROWS:GUARD_ROWS + h, off:off + w] = p
+            t = torch.from_numpy(host).cuda()
+            ptr = t.data_ptr() + (GUARD_ROWS * pitch + off) * 4
+            assert L.kc_plane_wrap(ptr, w, h, pitch * 4, C.byref(hnd)) == 0, (lay, w, h)
+            parents.append((t, host))
+        handles.append(hnd)
+    torch.cuda.synchronize()
+    kc.sync()
+    img = C.c_void_p()
+    if len(planes) == 4:
+        assert L.kc_image_rgba((C.c_void_p * 4)(*handles), C.byref(img)) == 0
+    else:
+        assert L.kc_image_gray(handles[0], C.byref(img)) == 0
+    for hnd in handles:
+        L.kc_plane_release(hnd)
+    return WrappedImage(kc, torch, kc.SlotImage(img.value), planes, parents)
+
+
 def kernel_resource_usage(unit, tmp):
     """{mangled kernel name: {"VGPRs": n, "ScratchSize": bytes per lane}} of every kernel of csrc/<unit> (a member of the
     build's SOURCES that includes bc_blocks.h), from a cross-compile with the build's own flags and
