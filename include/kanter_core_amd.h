@@ -265,6 +265,27 @@ KC_API int kc_kernel_cache_stats(uint64_t *files_accepted, uint64_t *files_refus
 KC_API int kc_kernel_cache_precompile(const uint32_t *words, uint32_t n_ops, uint32_t n_in, int start_src, int flat, uint32_t nt_mask,
                                       uint32_t up_taps, int up_wide, const char *dir);
 KC_API int kc_specialize_reset(void);
+/* The same with packed inputs: in_tiers holds two bits per input plane k (bits 2k, 2k + 1): 0 = f32, 1 = FIX24, 2 = U8
+ * (kc_set_pack_sources).  Flat plain chain programs only; in_tiers = 0 is kc_kernel_cache_precompile with up_taps = 0. */
+KC_API int kc_kernel_cache_precompile_packed(const uint32_t *words, uint32_t n_ops, uint32_t n_in, int start_src, int flat,
+                                             uint32_t nt_mask, uint32_t in_tiers, const char *dir);
+/* Lossless packed copies of long-lived chain inputs.  A source embedded in a graph is read again, as f32, by every
+ * evaluation, although its values are usually quantised: k * 2^-24 (every uniform-float generator; tier FIX24, 3 bytes per
+ * sample) or k / 255.0f (an 8-bit file; tier U8, 1 byte).  The library keeps such a copy beside the f32 plane -- made once, and
+ * only if every sample decodes back to its own bit pattern -- and the compiled flat {+, -, *} chain kernels of up to 16
+ * records read it instead.  Results are bit-identical; this is a throughput knob only.
+ *   kc_set_pack_sources  0: off.  1 (default): a plane is packed at its second sighting as input of a chain launch that does
+ *                        not fit the cache budget ("cache_budget_mb") while somebody besides the chain holds it; planes of
+ *                        smaller launches never are.  2: every eligible input at its first sighting whatever the size (tests).
+ *                        Eligible: planes the library owns, dense, width a multiple of 4; never a wrapped plane, a row-band
+ *                        view, or a plane whose pointer kc_plane_device_ptr has handed out.
+ *   kc_set_pack_budget_mb  what the packed copies may hold in all (default 4096 MiB); past it nothing more is packed.
+ * Counters (kc_stats_counter): "packed_planes", "pack_rejected" (planes that fit no tier), "packed_bytes" (held now),
+ * "packed_launches", and "_pk" behind the "specialized_nt_..." name of a launch that read packed inputs. */
+KC_API int kc_set_pack_sources(int mode);
+KC_API int kc_get_pack_sources(void);
+KC_API int kc_set_pack_budget_mb(int mb);
+KC_API int kc_get_pack_budget_mb(void);
 
 /* ========================================================================================== *
  * Planes -- replaces Buffer / TransientBufferContainer (src/slot_image.rs:12,

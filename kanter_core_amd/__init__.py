@@ -10,7 +10,7 @@ from .api import (Edge, EmbeddedSlotDataId, LiveGraph, MixType, Node, NodeGraph,
                   init, is_initialized, mix_process, resize_image, separate_rgba_process, set_fusion, set_stream,
                   shutdown, stats, sync, value_process, set_specialize, get_specialize, specialize_wait,
                   specialize_stats, specialize_compile_check, Partition, PartitionPolicy, NodeKind, set_resize_mode,
-                  get_resize_mode, resize_upsample_plan, resize_down2_plan, stats_counter, specialize_compile_check_upsample, specialize_compile_check_mask, set_chain_quads, get_chain_quads, set_cache_policy, get_cache_policy, set_option, get_option, comm_unique_id, comm_init,
+                  get_resize_mode, resize_upsample_plan, resize_down2_plan, stats_counter, specialize_compile_check_upsample, specialize_compile_check_mask, set_chain_quads, get_chain_quads, set_pack_sources, get_pack_sources, set_pack_budget_mb, get_pack_budget_mb, set_cache_policy, get_cache_policy, set_option, get_option, comm_unique_id, comm_init,
                   comm_destroy, comm_info, comm_stats, comm_transport, comm_gather_bands, PlanKind, pool_trim, kernel_cache_set_dir, kernel_cache_stats,
                   kernel_cache_precompile, specialize_reset, U8Pipe, device_image_desc, DEVICE_SRGB, DEVICE_GRAY,
                   ChannelStats, STATS_HISTOGRAM, STATS_SRGB, BC_SRGB, BC6H, BC7, BC_BLOCK_BYTES,

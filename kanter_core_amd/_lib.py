@@ -121,6 +121,11 @@ SIGNATURES = {
     "kc_specialize_compile_check": (C.c_int, [c_u32p, C.c_uint32, C.c_uint32, C.c_int, C.c_int, C.c_char_p, C.c_size_t]),
     "kc_specialize_compile_check_mask": (C.c_int, [c_u32p, C.c_uint32, C.c_uint32, C.c_int, C.c_int, C.c_uint32, C.c_char_p, C.c_size_t]),
     "kc_set_chain_quads": (C.c_int, [C.c_int]),
+    "kc_set_pack_sources": (C.c_int, [C.c_int]),
+    "kc_get_pack_sources": (C.c_int, []),
+    "kc_set_pack_budget_mb": (C.c_int, [C.c_int]),
+    "kc_get_pack_budget_mb": (C.c_int, []),
+    "kc_kernel_cache_precompile_packed": (C.c_int, [C.POINTER(C.c_uint32), C.c_uint32, C.c_uint32, C.c_int, C.c_int, C.c_uint32, C.c_uint32, C.c_char_p]),
     "kc_get_chain_quads": (C.c_int, []),
     "kc_specialize_compile_check_upsample": (C.c_int, [c_u32p, C.c_uint32, C.c_uint32, C.c_int, C.c_uint32, C.c_int, C.c_char_p,
                                                        C.c_size_t]),

@@ -256,6 +256,24 @@ def get_chain_quads():
     return _lib.load().kc_get_chain_quads()
 
 
+def set_pack_sources(mode):
+    """Packed copies of long-lived chain inputs (kc_set_pack_sources): 0 off, 1 the default rule, 2 every eligible input at once."""
+    _check(_lib.load().kc_set_pack_sources(int(mode)))
+
+
+def get_pack_sources():
+    return _lib.load().kc_get_pack_sources()
+
+
+def set_pack_budget_mb(mb):
+    """What the packed copies may hold in all, in MiB (kc_set_pack_budget_mb)."""
+    _check(_lib.load().kc_set_pack_budget_mb(int(mb)))
+
+
+def get_pack_budget_mb():
+    return _lib.load().kc_get_pack_budget_mb()
+
+
 def specialize_compile_check_upsample(words, n_in, start_src=0, taps=3, wide=True):
     """The same for a program that runs inside the integer-ratio up-sampling kernel (input n_in - 1 = the resampled
     operand).  Returns the generated source."""
@@ -285,9 +303,16 @@ def kernel_cache_stats():
     return dict(zip(("files_accepted", "files_refused", "files_written", "kernels_loaded"), (x.value for x in v)))
 
 
-def kernel_cache_precompile(words, n_in, start_src, flat, nt_mask, directory, up_taps=0, up_wide=False):
-    """Compiles the program given by its step words with hiprtc (no device needed) and writes its code object into `directory`."""
+def kernel_cache_precompile(words, n_in, start_src, flat, nt_mask, directory, up_taps=0, up_wide=False, in_tiers=0):
+    """Compiles the program given by its step words with hiprtc (no device needed) and writes its code object into `directory`.
+    in_tiers: two bits per input plane (0 f32, 1 FIX24, 2 U8), the kernel that reads those inputs from their packed copies."""
     arr = (C.c_uint32 * len(words))(*words)
+    if in_tiers:
+        if up_taps:
+            raise ValueError("packed inputs: plain chain programs only")
+        _check(_lib.load().kc_kernel_cache_precompile_packed(arr, len(words), int(n_in), int(start_src), int(bool(flat)), int(nt_mask),
+                                                             int(in_tiers), str(directory).encode()))
+        return
     _check(_lib.load().kc_kernel_cache_precompile(arr, len(words), int(n_in), int(start_src), int(bool(flat)), int(nt_mask),
                                                   int(up_taps), int(bool(up_wide)), str(directory).encode()))
 

@@ -444,11 +444,62 @@ int kc_kernel_cache_precompile(const uint32_t *words, uint32_t n_ops, uint32_t n
 try {
     KC_ARG(words && dir);
     std::string log;
-    const int s = kernel_cache_precompile(words, n_ops, n_in, start_src, flat != 0, nt_mask, up_taps, up_wide != 0, dir, &log);
+    const int s = kernel_cache_precompile(words, n_ops, n_in, start_src, flat != 0, nt_mask, 0, up_taps, up_wide != 0, dir, &log);
     if (s != KC_OK) set_error("kernel cache: " + log);
     return s;
 }
 KC_CATCH
+
+int kc_kernel_cache_precompile_packed(const uint32_t *words, uint32_t n_ops, uint32_t n_in, int start_src, int flat, uint32_t nt_mask,
+                                      uint32_t in_tiers, const char *dir)
+try {
+    KC_ARG(words && dir);
+    std::string log = "in_tiers: two bits per input plane, 0 to 2, flat programs only";
+    const int s = kernel_cache_precompile(words, n_ops, n_in, start_src, flat != 0, nt_mask, in_tiers, 0, false, dir, &log);
+    if (s != KC_OK) set_error("kernel cache: " + log);
+    return s;
+}
+KC_CATCH
+
+int kc_set_pack_sources(int mode)
+try {
+    Lock lk(ctx().mu);
+    if (mode < 0 || mode > 2) {
+        set_error("kc_set_pack_sources accepts 0, 1 or 2");
+        return KC_ERR_INVALID_ARG;
+    }
+    ctx().pack_sources = mode;
+    return KC_OK;
+}
+KC_CATCH
+
+int kc_get_pack_sources(void)
+try {
+    return ctx().pack_sources;
+}
+catch (...) {
+    return 0;
+}
+
+int kc_set_pack_budget_mb(int mb)
+try {
+    Lock lk(ctx().mu);
+    if (mb < 0) {
+        set_error("kc_set_pack_budget_mb accepts 0 and up");
+        return KC_ERR_INVALID_ARG;
+    }
+    ctx().pack_budget_mb = mb;
+    return KC_OK;
+}
+KC_CATCH
+
+int kc_get_pack_budget_mb(void)
+try {
+    return ctx().pack_budget_mb;
+}
+catch (...) {
+    return 0;
+}
 
 // Forgets every kernel this process has compiled or loaded (the files stay): the next sighting of a program is a first one.
 int kc_specialize_reset(void)
@@ -619,6 +670,10 @@ int kc_plane_device_ptr(kc_plane *p, void **dptr, size_t *pitch)
 try {
     KC_ARG(p);
     KC_TRY(plane_materialize(p));
+    {
+        Lock lk(ctx().mu);
+        plane_shadow_drop(p, true);  // the caller may write through the pointer from now on: no packed copy, ever
+    }
     if (dptr) *dptr = p->dptr;
     if (pitch) *pitch = p->pitch;
     return KC_OK;
@@ -631,6 +686,7 @@ try {
     KC_ARG(p && host && p->kind == kc_plane::MEM);
     if (host_pitch == 0) host_pitch = (size_t)p->w * 4;
     Lock lk(ctx().mu);
+    plane_shadow_drop(p, false);  // an in-place write: the packed copy is stale
     KC_HIP(hipMemcpy2DAsync(p->dptr, p->pitch, host, host_pitch, (size_t)p->w * 4, p->h, hipMemcpyHostToDevice, ctx().stream));
     KC_HIP(hipStreamSynchronize(ctx().stream));
     return KC_OK;

@@ -12,6 +12,10 @@ enum { KC_CHAIN_MAX_OPS = 80, KC_CHAIN_MAX_IN = 16, KC_CHAIN_INTERP_IN = 4, KC_C
 // (sizes: the argument block -- 16 x 4 pointers and pitches, 41 x 4 record pairs -- is 3.6 KB of the 4 KB a launch may pass)
 // Cache-policy bit of input plane k in ChainProgram::nt_mask: bits 0-7, then 16-23 (bit 8 is the result's).
 #define KC_CHAIN_NT_BIT(k) ((k) < 8 ? 1u << (k) : 1u << ((k) + 8))
+// Tier of input plane k in ChainProgram::in_tiers, two bits each: 0 = f32, else the lossless packed copy of the plane that
+// in[b][k] then points at (chain_pack.h).  Only the kernels compiled at run time read anything but f32.
+enum { KC_PACK_NONE = 0, KC_PACK_FIX24 = 1, KC_PACK_U8 = 2 };
+#define KC_CHAIN_TIER(tiers, k) (((tiers) >> (2 * (k))) & 3u)
 
 // Step codes: which side the running value sits on matters for -, / and pow.
 enum ChainCode : unsigned char {
@@ -62,6 +66,7 @@ struct ChainProgram {
     // the nontemporal hint (streamed once, not worth a place in the 256 MB Infinity Cache), bit 8 = the result is stored
     // with it.  Honoured by the kernels compiled at run time and by the up-sampling kernels; a hint, never semantics.
     unsigned int nt_mask;
+    unsigned int in_tiers;  // KC_CHAIN_TIER(in_tiers, k): what in[.][k] points at, the same for every channel
     const float *in[KC_CHAIN_MAX_BATCH][KC_CHAIN_MAX_IN];
     unsigned int in_pitch[KC_CHAIN_MAX_BATCH][KC_CHAIN_MAX_IN];  // in vector units
     float *out[KC_CHAIN_MAX_BATCH];

@@ -276,6 +276,10 @@ hipError_t launch_to_u8(Operand r, Operand g, Operand b, Operand a, int gray, in
                         uint8_t *dst, uint32_t nt_mask, hipStream_t s, bool *launched_nt);
 hipError_t launch_from_u8(const uint8_t *src, int channels, uint32_t w, uint32_t h, float *const planes[4],
                           uint32_t pitch, uint32_t nt_mask, hipStream_t s, bool *launched_nt);
+// -- chain_pack.hip --
+// The pack pass of one tier (chain_pack.h): `quads` float4 of the dense plane `src` into `dst`, pack_bytes_per_quad(tier) each;
+// *flag (device memory, cleared by the caller) is set to 1 if any sample does not decode back to its own bit pattern.
+hipError_t launch_pack_plane(uint32_t tier, const float *src, void *dst, uint64_t quads, uint32_t *flag, hipStream_t s);
 // -- devimage.hip --
 // Device-memory images (devimage.hip / devimage.cpp): a validated kc_device_image as the kernels take it.  vec != 0: the pointer
 // and the pitches are aligned for the widest access of a whole pixel quad (devimage.cpp, devimage_vec).

@@ -107,6 +107,13 @@ struct kc_plane : kc::Pooled<kc_plane> {
     kc_plane *view_of = nullptr;  // MEM, not owned: rows of this (retained) plane, see bands.cpp
     kc_plane *rz_src = nullptr;  // retained; MEM
     int rz_filter = 0;
+    // The lossless packed copy a chain kernel reads instead of the plane (chain_pack.cpp): MEM, owned, dense planes only.
+    // `shadow` is a pool block of shadow_bytes, released with the plane; pack_tier its KC_PACK_* code.  Whoever writes into the
+    // plane in place or hands its pointer out calls plane_shadow_drop first.
+    enum PackState : uint8_t { PACK_UNTRIED = 0, PACKED = 1, PACK_NEVER = 2 };  // PACK_NEVER: fits no tier, or is not to be tried again
+    void *shadow = nullptr;
+    size_t shadow_bytes = 0;
+    uint8_t pack_tier = 0, pack_state = PACK_UNTRIED, pack_seen = 0;  // pack_seen: sightings by HBM-bound chain launches so far
 };
 
 // SlotImage, src/slot_image.rs:15-19
@@ -204,6 +211,9 @@ struct ReplayLaunch {
     uint32_t in_refs[KC_CHAIN_MAX_IN] = {};
     uint32_t w = 0, h = 0;
     kc_plane *planes[KC_CHAIN_MAX_BATCH] = { nullptr, nullptr, nullptr, nullptr };  // the lazy planes the launch made resident
+    // the planes behind the inputs, by object: a recording made before a source was packed launches its packed form afterwards.
+    // Only those of inputs with in_from < 0 are used in a replay: the recording's images keep exactly those alive.
+    kc_plane *in_plane[KC_CHAIN_MAX_BATCH][KC_CHAIN_MAX_IN] = {};
     // filled when the recording is closed: input (b, k) is output channel in_ch of recorded launch in_from (-1: a plane that
     // existed before the evaluation and is held by the recording)
     int in_from[KC_CHAIN_MAX_BATCH][KC_CHAIN_MAX_IN];
@@ -227,6 +237,10 @@ struct Context {
     std::multimap<size_t, void *> free_blocks;
     uint64_t bytes_in_use = 0, bytes_cached = 0, launches = 0;
     std::map<std::string, uint64_t> counters;  // named event counts (kc_stats_counter): which kernel family ran, transfers ...
+    // packed copies of chain inputs (chain_pack.cpp): pack_sources 0 = off, 1 = sources that HBM-bound launches keep reading, 2 = every
+    // eligible input at once (tests); shadow_bytes = what the shadows hold now, never more than pack_budget_mb
+    int pack_sources = 1, pack_budget_mb = 4096;
+    uint64_t shadow_bytes = 0;
     uint64_t alg_bytes = 0;  // algorithmic HBM bytes of every kernel launched so far (DESIGN.md section 3's per-kernel figures)
     std::map<std::tuple<uint32_t, uint32_t, int>, TapsEntry> taps;
     std::map<std::tuple<uint32_t, uint32_t, int, int32_t, int32_t, int32_t>, TapsEntry> band_taps;  // row-band vertical tables
@@ -464,7 +478,16 @@ hipError_t launch_chain_specialized(const ChainProgram &P, int batch, hipStream_
 // full-size input planes / writes, summed over its channels, under the options o.  Returns the ChainProgram::nt_mask bits.
 uint32_t cache_policy_mask(uint64_t in_bytes, uint64_t out_bytes, uint32_t n_resident, const Options &o = options());
 uint32_t chain_cache_policy(const uint32_t *refs, uint32_t n, uint64_t stream_bytes, uint64_t out_bytes);
-hipError_t chain_dispatch(ChainProgram &P, int batch, int mode, uint32_t w, uint32_t h, size_t out_pitch_bytes);
+// src (optional): the planes behind the inputs, [channel][input], nullptr where a plane must stay f32; refs as for
+// chain_cache_policy.  *packed_saved (optional): the bytes the launch did not read because inputs were packed.
+hipError_t chain_dispatch(ChainProgram &P, int batch, int mode, uint32_t w, uint32_t h, size_t out_pitch_bytes,
+                          kc_plane *const (*src)[KC_CHAIN_MAX_IN] = nullptr, const uint32_t *refs = nullptr, uint64_t *packed_saved = nullptr);
+// ---- packed copies of chain inputs (chain_pack.cpp) ----
+// The tiers of P's inputs for this launch (ChainProgram::in_tiers), packing planes whose turn has come; 0 when nothing is packed.
+uint32_t pack_chain_inputs(const ChainProgram &P, int batch, kc_plane *const (*src)[KC_CHAIN_MAX_IN], const uint32_t *refs, uint32_t w, uint32_t h);
+void plane_shadow_drop(kc_plane *p, bool never_again);  // before an in-place write (never_again: the pointer leaves the library)
+uint32_t pack_bytes_per_quad(uint32_t tier);            // 16 for KC_PACK_NONE
+bool chain_pack_program_ok(const ChainProgram &P);      // specialize.cpp: a flat {+, -, *} program whose kernel may read packed inputs
 hipError_t launch_upsample_chain_specialized(const ChainProgram &P, int batch, const UpsampleArgs &U, hipStream_t s, bool *launched);
 int specialize_set_mode(int mode, int after);  // 0 off, 1 background compile after `after` sightings, 2 compile at once
 int specialize_get_mode();
@@ -480,7 +503,7 @@ int specialize_compile_only(const ChainProgram &P, std::string *log, const Upsam
 int kernel_cache_set_dir(const char *dir);
 void kernel_cache_stats(uint64_t *hits, uint64_t *rejected, uint64_t *written, uint64_t *kernels_loaded);
 bool kernel_cache_populated();
-int kernel_cache_precompile(const uint32_t *words, uint32_t n_ops, uint32_t n_in, int32_t start_src, bool flat, uint32_t nt_mask,
+int kernel_cache_precompile(const uint32_t *words, uint32_t n_ops, uint32_t n_in, int32_t start_src, bool flat, uint32_t nt_mask, uint32_t in_tiers,
                             uint32_t up_taps, bool up_wide, const char *dir, std::string *log);
 
 // ---- the u8 boundary as a pipeline (u8pipe.cpp) ----

@@ -135,6 +135,7 @@ int replay_try(kc_live_graph &lg, uint32_t id, bool *hit)
     for (size_t li = 0; li < e->launches.size(); ++li) {
         const ReplayLaunch &L = e->launches[li];
         ChainProgram P = L.prog;
+        kc_plane *src[KC_CHAIN_MAX_BATCH][KC_CHAIN_MAX_IN] = {};  // the planes the recording holds, for their packed copies
         for (int b = 0; b < L.batch; ++b) {
             kc_plane *&o = outs[li * KC_CHAIN_MAX_BATCH + b];
             int s = plane_new_mem(L.w, L.h, &o);
@@ -146,14 +147,17 @@ int replay_try(kc_live_graph &lg, uint32_t id, bool *hit)
             P.out_pitch[b] = (uint32_t)(o->pitch / 16);
             for (uint32_t k = 0; k < P.n_in; ++k)
                 if (L.in_from[b][k] >= 0) {  // a result of an earlier launch of this replay
-                    const kc_plane *src = outs[(size_t)L.in_from[b][k] * KC_CHAIN_MAX_BATCH + L.in_ch[b][k]];
-                    P.in[b][k] = src->dptr;
-                    P.in_pitch[b][k] = (uint32_t)(src->pitch / 16);
+                    const kc_plane *res = outs[(size_t)L.in_from[b][k] * KC_CHAIN_MAX_BATCH + L.in_ch[b][k]];
+                    P.in[b][k] = res->dptr;
+                    P.in_pitch[b][k] = (uint32_t)(res->pitch / 16);
+                } else {
+                    src[b][k] = L.in_plane[b][k];
                 }
         }
         const uint64_t px4 = 4ull * L.w * L.h;
         P.nt_mask = chain_cache_policy(L.in_refs, P.n_in, px4 * L.batch, px4 * L.batch);
-        hipError_t he = chain_dispatch(P, L.batch, L.mode, L.w, L.h, outs[li * KC_CHAIN_MAX_BATCH]->pitch);
+        uint64_t packed_saved = 0;
+        hipError_t he = chain_dispatch(P, L.batch, L.mode, L.w, L.h, outs[li * KC_CHAIN_MAX_BATCH]->pitch, src, L.in_refs, &packed_saved);
         if (he == hipErrorNotReady) {  // a program that joins two chains, and its kernel is not to be had (kc_set_specialize(0)): walk
             drop_outs();
             return KC_OK;
@@ -163,7 +167,7 @@ int replay_try(kc_live_graph &lg, uint32_t id, bool *hit)
             return hip_fail(he, "launch_chain (replay)");
         }
         c.launches++;
-        c.alg_bytes += (uint64_t)L.batch * px4 * (P.n_in + 1);
+        c.alg_bytes += (uint64_t)L.batch * px4 * (P.n_in + 1) - packed_saved;
     }
     c.counters["replayed_evaluations"]++;
 
@@ -202,12 +206,16 @@ struct ReplayRecorder {
     // results can be embedded) reads the operands of ITS chain, which only its links hold: forced from outside between two
     // evaluations they go back to the pool and a replay would launch on recycled addresses.
     std::set<const void *> resident0;
+    std::set<const kc_plane *> resident_planes;  // the same planes by object: what a replay may ask for a packed copy (chain_pack.cpp)
 };
 
-static void note_resident(std::set<const void *> &set, const kc_image *img)
+static void note_resident(ReplayRecorder &r, const kc_image *img)
 {
     for (int p = 0; p < img->n; ++p)
-        if (img->planes[p]->kind == kc_plane::MEM) set.insert(img->planes[p]->dptr);
+        if (img->planes[p]->kind == kc_plane::MEM) {
+            r.resident0.insert(img->planes[p]->dptr);
+            r.resident_planes.insert(img->planes[p]);
+        }
 }
 
 ReplayRecorder *replay_begin(kc_live_graph &lg, uint32_t id)
@@ -226,7 +234,7 @@ ReplayRecorder *replay_begin(kc_live_graph &lg, uint32_t id)
             if (sd.node_id == id) continue;  // the requested node's previous result: replaced, never read
             image_retain(sd.image);
             e->pre_slots.push_back({ sd.node_id, sd.slot_id, sd.image });
-            note_resident(r->resident0, sd.image);
+            note_resident(*r, sd.image);
         }
     for (auto &em : lg.embedded) {
         if (em.full_h != 0) {  // row-band sources: another evaluation path
@@ -236,7 +244,7 @@ ReplayRecorder *replay_begin(kc_live_graph &lg, uint32_t id)
         }
         image_retain(em.image);
         e->embedded.push_back(em);
-        note_resident(r->resident0, em.image);
+        note_resident(*r, em.image);
     }
     r->launches0 = c.launches;
     r->changed0 = lg.changed;
@@ -340,6 +348,7 @@ void replay_end(kc_live_graph &lg, uint32_t id, ReplayRecorder *r, int s)
                         }
                 // anything else must be a plane the entry itself keeps alive (see ReplayRecorder::resident0)
                 if (L.in_from[b][k] < 0 && !r->resident0.count(L.prog.in[b][k])) return;
+                if (L.in_from[b][k] >= 0 || !r->resident_planes.count(L.in_plane[b][k])) L.in_plane[b][k] = nullptr;  // not the entry's to keep
             }
     }
     for (uint32_t ch : lg.changed)

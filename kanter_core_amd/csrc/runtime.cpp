@@ -253,6 +253,7 @@ void plane_release(kc_plane *p)
         if (p->link) delete p->link;
         if (p->rz_src) plane_release(p->rz_src);
         if (p->view_of) plane_release(p->view_of);
+        if (p->shadow) plane_shadow_drop(p, false);
         if (p->owned && p->dptr) pool_free(p->dptr, p->bytes);
         delete p;
     }
@@ -425,6 +426,7 @@ Operand plane_operand(const kc_plane *p)
 struct BuiltChain {
     ChainProgram prog;
     uint32_t in_refs[KC_CHAIN_MAX_IN] = {};  // reference counts of channel 0's resident inputs when the program was built
+    kc_plane *in_plane[KC_CHAIN_MAX_BATCH][KC_CHAIN_MAX_IN] = {};  // the resident inputs by object (chain_pack.cpp); the chains hold them
     int mode = 0;  // 0 = {+,-,*}, 1 = + divide, 2 = + pow
     kc_plane *sampled[KC_CHAIN_MAX_BATCH] = { nullptr, nullptr, nullptr, nullptr };  // RESIZE operand per channel
     bool joins = false;  // the program holds CH_SAVE_LOAD: only its own compiled kernel can run it
@@ -527,6 +529,7 @@ static bool chain_fill(BuiltChain &bc, int b, const kc_plane *p)
         P.in_pitch[b][k] = (uint32_t)(ins[k]->pitch / 16);
         if (b == 0) bc.in_refs[k] = (uint32_t)ins[k]->refs;
     }
+    for (int k = 0; k < KC_CHAIN_MAX_IN; ++k) bc.in_plane[b][k] = k < km ? const_cast<kc_plane *>(ins[k]) : nullptr;
     if (samp) {
         P.samp_src[b] = samp->rz_src->dptr;
         P.samp_pitch[b] = (uint32_t)(samp->rz_src->pitch / 4);
@@ -605,13 +608,15 @@ uint32_t cache_policy_mask(uint64_t in_bytes, uint64_t out_bytes, uint32_t n_res
 // chain_interp_k<K>_u<U>_m<MODE>[_nt]: chain_kernel<K, U, MODE, NT>; chain_k0_m<MODE>: chain_kernel_k0<MODE>;
 // chain1_nt<bits>: chain1_kernel's nontemporal bits (1 start, 2 operand, 4 result); specialized_nt_<hex>: the cache-policy
 // bits a compiled kernel carries (bits 0-7 inputs 0-7, 0x100 the result; the bits of inputs 8-15 are not part of the name),
-// with "_q2" / "_q4" behind it when the kernel handles that many float4 per lane (specialize.cpp, chain_quads_for).
+// with "_q2" / "_q4" behind it when the kernel handles that many float4 per lane (specialize.cpp, chain_quads_for), and "_pk"
+// last when the launch read packed copies of inputs (chain_pack.cpp; "packed_launches" counts those of every form).
 namespace {
 struct ChainCounterNames {
     std::string interp[5][9][3][2];  // [K][U][MODE][NT]; U in {1, 2, 4, 6, 8}
     std::string k0[3];
     std::string chain1[8];
     std::string spec[0x200], spec_q2[0x200], spec_q4[0x200];
+    std::string spec_pk[0x200], spec_q2_pk[0x200], spec_q4_pk[0x200];  // "_pk" behind the name: the launch read packed inputs
     ChainCounterNames()
     {
         char buf[64];
@@ -629,6 +634,9 @@ struct ChainCounterNames {
             spec[b] = buf;
             spec_q2[b] = spec[b] + "_q2";
             spec_q4[b] = spec[b] + "_q4";
+            spec_pk[b] = spec[b] + "_pk";
+            spec_q2_pk[b] = spec_q2[b] + "_pk";
+            spec_q4_pk[b] = spec_q4[b] + "_pk";
         }
     }
 };
@@ -642,8 +650,10 @@ const ChainCounterNames &chain_counter_names()
 // Launches a (non-resampling) chain program whose inputs and outputs are set: the ahead-of-time kernel of a one-step
 // program, else the kernel compiled for the program at run time if there is one, else the interpreter.  Shared by
 // chain_launch and by the replay of a recorded evaluation (replay.cpp); counts the form it launched (kc_stats_counter).
-hipError_t chain_dispatch(ChainProgram &P, int batch, int mode, uint32_t w, uint32_t h, size_t out_pitch_bytes)
+hipError_t chain_dispatch(ChainProgram &P, int batch, int mode, uint32_t w, uint32_t h, size_t out_pitch_bytes,
+                          kc_plane *const (*src)[KC_CHAIN_MAX_IN], const uint32_t *refs, uint64_t *packed_saved)
 {
+    if (packed_saved) *packed_saved = 0;
     Context &c = ctx();
     const uint32_t row_units = (w + 3) / 4;
     bool launched = false;
@@ -691,10 +701,34 @@ hipError_t chain_dispatch(ChainProgram &P, int batch, int mode, uint32_t w, uint
     if (!launched) {
         // a program-specialised straight-line kernel if one has been compiled (specialize.cpp) ...
         uint32_t spec_nt = 0, spec_quads = 1;
-        hipError_t e = launch_chain_specialized(P, batch, c.stream, &launched, &spec_nt, &spec_quads);
-        if (e == hipSuccess && launched) {
-            const ChainCounterNames &names = chain_counter_names();
-            c.counters[(spec_quads == 2 ? names.spec_q2 : spec_quads == 4 ? names.spec_q4 : names.spec)[spec_nt & 0x1ffu]]++;
+        hipError_t e = hipSuccess;
+        // ... reading the packed copies of its long-lived inputs where there are some (chain_pack.cpp) and the kernel of that
+        // form is ready; P itself keeps the f32 pointers (a recording stores it, the forms below read nothing else)
+        const uint32_t tiers = src && c.pack_sources && chain_pack_program_ok(P) ? pack_chain_inputs(P, batch, src, refs, w, h) : 0u;
+        if (tiers) {
+            ChainProgram Q = P;
+            Q.in_tiers = tiers;
+            uint64_t saved = 0;
+            for (uint32_t k = 0; k < P.n_in; ++k)
+                if (const uint32_t t = KC_CHAIN_TIER(tiers, k))
+                    for (int b = 0; b < batch; ++b) {
+                        Q.in[b][k] = (const float *)src[b][k]->shadow;
+                        saved += (uint64_t)w * h / 4 * (16 - pack_bytes_per_quad(t));
+                    }
+            e = launch_chain_specialized(Q, batch, c.stream, &launched, &spec_nt, &spec_quads);
+            if (e == hipSuccess && launched) {
+                const ChainCounterNames &names = chain_counter_names();
+                c.counters[(spec_quads == 2 ? names.spec_q2_pk : spec_quads == 4 ? names.spec_q4_pk : names.spec_pk)[spec_nt & 0x1ffu]]++;
+                c.counters["packed_launches"]++;
+                if (packed_saved) *packed_saved = saved;
+            }
+        }
+        if (e == hipSuccess && !launched) {
+            e = launch_chain_specialized(P, batch, c.stream, &launched, &spec_nt, &spec_quads);
+            if (e == hipSuccess && launched) {
+                const ChainCounterNames &names = chain_counter_names();
+                c.counters[(spec_quads == 2 ? names.spec_q2 : spec_quads == 4 ? names.spec_q4 : names.spec)[spec_nt & 0x1ffu]]++;
+            }
         }
         // ... otherwise the interpreter -- which does not know the codes of a program that joins two chains (chain_launch
         // never sends it one; a replay of such a launch after kc_set_specialize(0) can)
@@ -738,6 +772,7 @@ static int chain_launch(BuiltChain &bc, kc_plane *const *planes, int batch)
         P.nt_mask = chain_cache_policy(bc.in_refs, resident, px4 * batch, px4 * batch);
     }
     bool launched = false;
+    uint64_t packed_saved = 0;
     if (bc.sampled[0]) {
         int s = chain_resize_launch(P, batch, bc.mode, bc.sampled, &launched);
         if (s != KC_OK || !launched) {
@@ -749,7 +784,7 @@ static int chain_launch(BuiltChain &bc, kc_plane *const *planes, int batch)
         }
     }
     if (!launched) {
-        hipError_t e = chain_dispatch(P, batch, bc.mode, p0->w, p0->h, outs[0]->pitch);
+        hipError_t e = chain_dispatch(P, batch, bc.mode, p0->w, p0->h, outs[0]->pitch, bc.in_plane, bc.in_refs, &packed_saved);
         if (e == hipErrorNotReady && (bc.joins || P.n_in > (uint32_t)KC_CHAIN_INTERP_IN)) {
             // The program joins chains or reads more planes than the interpreter handles, and its own kernel has not been
             // compiled (yet): the joined chains run on their own and the chain is cut to the interpreter's input count, as
@@ -787,7 +822,7 @@ static int chain_launch(BuiltChain &bc, kc_plane *const *planes, int batch)
             bytes += 4 * px * (resident + 1);
             if (bc.sampled[b]) bytes += 4 * (uint64_t)bc.sampled[b]->rz_src->w * bc.sampled[b]->rz_src->h;
         }
-        c.alg_bytes += bytes;
+        c.alg_bytes += bytes - packed_saved;  // a packed input costs 3 or 1 bytes per sample
     }
     if (c.capture) {  // an evaluation is being recorded for replay (replay.cpp)
         ReplayCapture &cap = *c.capture;
@@ -802,6 +837,7 @@ static int chain_launch(BuiltChain &bc, kc_plane *const *planes, int batch)
             L.w = p0->w;
             L.h = p0->h;
             for (int b = 0; b < batch; ++b) L.planes[b] = planes[b];
+            std::memcpy(L.in_plane, bc.in_plane, sizeof L.in_plane);
         }
     }
     for (int b = 0; b < batch; ++b) {
