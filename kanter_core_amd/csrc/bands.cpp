@@ -471,7 +471,10 @@ int evaluate_node(Walk &W, const Node &n)
 //   * an edge leaving the Graph node's slot o leaves the copy of the child's Output node o instead.
 // Nested Graph nodes come to the surface with their parent and are expanded in a later round.  The result holds no Graph
 // node among the root's ancestors; rows, halos and arithmetic are then what the walk below does for any other graph.
-int expand_graph_nodes(kc_live_graph &lg, uint32_t *root, uint32_t *slot, std::unique_ptr<kc_live_graph> &flat)
+// `siblings` receives the copies of the Output nodes of every expanded child graph: graph::process evaluates ALL of them, and a
+// Graph node whose graph fails on any of them fails as a whole, whichever output the band was asked of (check_siblings).
+int expand_graph_nodes(kc_live_graph &lg, uint32_t *root, uint32_t *slot, std::unique_ptr<kc_live_graph> &flat,
+                       std::vector<uint32_t> &siblings)
 {
     auto has_graph_ancestor = [](const NodeGraph &g, uint32_t r, uint32_t *which) {
         std::vector<uint32_t> topo;
@@ -499,7 +502,14 @@ int expand_graph_nodes(kc_live_graph &lg, uint32_t *root, uint32_t *slot, std::u
         image_retain(i.image);
         F.input_slot_datas.push_back(i);
     }
-    for (int round = 0; has_graph_ancestor(F.g, *root, &gid); ++round) {
+    // (a Graph node above a sibling Output only is expanded as well: the sibling's branch has to be looked at)
+    auto next_graph_node = [&](uint32_t *which) {
+        if (has_graph_ancestor(F.g, *root, which)) return true;
+        for (uint32_t s : siblings)
+            if (has_graph_ancestor(F.g, s, which)) return true;
+        return false;
+    };
+    for (int round = 0; next_graph_node(&gid); ++round) {
         if (round > 64) {
             set_error("Graph nodes nested too deeply");
             return KC_ERR_NODE_PROCESSING;
@@ -521,6 +531,14 @@ int expand_graph_nodes(kc_live_graph &lg, uint32_t *root, uint32_t *slot, std::u
             if (!lowest || e.input_slot < lowest->input_slot) lowest = &e;
         // copies of the child's nodes
         const NodeGraph &cg = *gn.graph;
+        // graph::process asks the child for its Output nodes only: an Input node none of them descends from is never
+        // processed, and one without data fails the Graph node only if it is
+        std::set<uint32_t> live;
+        for (uint32_t o : cg.output_ids()) {
+            std::vector<uint32_t> above;
+            KC_TRY(ancestors_topological(cg, o, above));
+            live.insert(above.begin(), above.end());
+        }
         std::map<uint32_t, uint32_t> idmap;
         std::vector<kc_edge> new_edges;
         for (auto &cn : cg.nodes) {
@@ -533,9 +551,13 @@ int expand_graph_nodes(kc_live_graph &lg, uint32_t *root, uint32_t *slot, std::u
                 else
                     for (auto &e : in_edges)
                         if (e.input_slot == cn.node_id) feed = &e;
-                if (!feed) {
+                if (!feed && live.count(cn.node_id)) {
                     set_error("row band: an Input node of a Graph node's graph has nothing connected to it");
                     return KC_ERR_NO_SLOT_DATA;
+                }
+                if (!feed) {  // idle: the copy stays an Input node without data, which nothing below the Outputs reads
+                    F.g.nodes.push_back(c);
+                    continue;
                 }
                 c.type = cn.type == KC_NODE_INPUT_RGBA ? KC_NODE_OUTPUT_RGBA : KC_NODE_OUTPUT_GRAY;
                 c.policy = KC_POLICY_SPECIFIC_SIZE;
@@ -571,6 +593,7 @@ int expand_graph_nodes(kc_live_graph &lg, uint32_t *root, uint32_t *slot, std::u
                 break;
             }
         F.g.touch();
+        for (uint32_t o : cg.output_ids()) siblings.push_back(idmap[o]);
         if (*root == gid) {
             auto it = idmap.find(*slot);
             if (it == idmap.end()) {
@@ -585,16 +608,58 @@ int expand_graph_nodes(kc_live_graph &lg, uint32_t *root, uint32_t *slot, std::u
     return KC_OK;
 }
 
+// What makes an operator fail on the TYPES of its inputs (csrc/ops.cpp): HeightToNormal without a gray image on slot 0
+// produces nothing (InvalidBufferCount), CombineRgba refuses an RGBA image on any slot.  Everything else that fails a node --
+// a source without data, a HeightToNormal without input -- infer_sizes has reported.
+int check_types(Walk &W)
+{
+    const NodeGraph &g = W.lg.g;
+    for (uint32_t id : W.topo) {
+        const Node &n = *g.find(id);
+        if (n.type != KC_NODE_HEIGHT_TO_NORMAL && n.type != KC_NODE_COMBINE_RGBA) continue;
+        bool slot0 = false;
+        for (auto &e : g.edges_into(id)) {
+            const bool rgba = W.rgba[e.output_id];
+            if (n.type == KC_NODE_COMBINE_RGBA && rgba) {
+                set_error("It shouldn't be possible to connect an RGBA image into this slot");
+                return KC_ERR_NODE_PROCESSING;
+            }
+            if (n.type == KC_NODE_HEIGHT_TO_NORMAL && e.input_slot == 0 && !rgba) slot0 = true;
+        }
+        if (n.type == KC_NODE_HEIGHT_TO_NORMAL && !slot0) {
+            set_error("HeightToNormal without a gray image on its input produces no data");
+            return KC_ERR_NO_SLOT_DATA;
+        }
+    }
+    return KC_OK;
+}
+
+// The other Output nodes of the child graphs the band goes through: the band reads nothing of them, but the reference fails
+// the Graph node if any of them fails.  Host work only: their ancestors' sizes and types.
+int check_siblings(kc_live_graph &flat, const std::vector<uint32_t> &siblings)
+{
+    for (uint32_t s : siblings) {
+        if (!flat.g.find(s)) continue;
+        Walk V(flat);
+        KC_TRY(ancestors_topological(flat.g, s, V.topo));
+        KC_TRY(infer_sizes(V));
+        KC_TRY(check_types(V));
+    }
+    return KC_OK;
+}
+
 // Opens the walk every entry point starts with: the Graph nodes above `root` expanded (root and slot then name the node that
 // took the root's place), the ancestors in order and their sizes.
 int open_walk(kc_live_graph &lg0, uint32_t *root, uint32_t *slot, std::unique_ptr<Walk> &W)
 {
     if (!lg0.g.find(*root)) return KC_ERR_INVALID_NODE_ID;
     std::unique_ptr<kc_live_graph> flat;
-    KC_TRY(expand_graph_nodes(lg0, root, slot, flat));
+    std::vector<uint32_t> siblings;
+    KC_TRY(expand_graph_nodes(lg0, root, slot, flat, siblings));
     W.reset(new Walk(lg0, std::move(flat)));
     KC_TRY(ancestors_topological(W->lg.g, *root, W->topo));
-    return infer_sizes(*W);
+    KC_TRY(infer_sizes(*W));
+    return siblings.empty() ? KC_OK : check_siblings(W->lg, siblings);
 }
 
 }  // namespace

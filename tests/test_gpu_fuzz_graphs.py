@@ -35,8 +35,8 @@ def orc():
     return orc
 
 
-def _source(rng, rgba):
-    w, h = SIZES[rng.integers(len(SIZES))]
+def _source(rng, rgba, sizes=SIZES):
+    w, h = sizes[rng.integers(len(sizes))]
     planes = []
     for _ in range(4 if rgba else 1):
         p = (rng.random((h, w), dtype=np.float32) * np.float32(1.6) - np.float32(0.3)).astype(np.float32)
@@ -47,20 +47,21 @@ def _source(rng, rgba):
     return planes
 
 
-def _policy(kc, rng, n_inputs):
+def _policy(kc, rng, n_inputs, sizes=SIZES):
     k = rng.integers(6)
     P = kc.ResizePolicy
     if k == 4:
         return P.SpecificSlot(kc.SlotId(int(rng.integers(max(n_inputs, 1)))))
     if k == 5:
-        w, h = SIZES[rng.integers(len(SIZES))]
+        w, h = sizes[rng.integers(len(sizes))]
         return P.SpecificSize(kc.Size(w + int(rng.integers(3)), h))
     return [P.MostPixels, P.LeastPixels, P.LargestAxes, P.SmallestAxes][k]
 
 
-def _build(kc, orc, seed, info=None):
+def _build(kc, orc, seed, info=None, sizes=SIZES):
     """-> (live graph, RefGraph, node ids to request); `info` (optional dict) receives what the mutation
-    fuzzer needs: embedded images, every output slot with its creator's position, every node with its slots."""
+    fuzzer needs: embedded images, every output slot with its creator's position, every node with its slots.
+    `sizes`: the (w, h) list sources and SpecificSize policies draw from (tests/band_fuzz.py passes one without tiny images)."""
     rng = np.random.default_rng(seed)
     tp = kc.TextureProcessor.new()
     lg = tp.new_live_graph()
@@ -72,7 +73,7 @@ def _build(kc, orc, seed, info=None):
     outs = []
     for eid in range(int(rng.integers(2, 5))):
         rgba = bool(rng.random() < 0.6)
-        planes = _source(rng, rgba)
+        planes = _source(rng, rgba, sizes)
         lg.embed_slot_data_with_id(kc.SlotData(0, 0, kc.SlotImage.from_planes(planes)), eid)
         embedded[eid] = orc.Image([p.copy() for p in planes])
         n = lg.add_node(kc.Node.new(kc.NodeType.Embed(eid)))
@@ -110,7 +111,7 @@ def _build(kc, orc, seed, info=None):
             ins = [(one, 0, "G"), pick("X")]
             produces = [(0, "X")]
         n_in = sum(i is not None for i in ins)
-        node = node.with_resize_policy(_policy(kc, rng, n_in)).with_resize_filter(
+        node = node.with_resize_policy(_policy(kc, rng, n_in, sizes)).with_resize_filter(
             kc.ResizeFilter.parse(FILTERS[rng.integers(len(FILTERS))]))
         n = lg.add_node(node)
         order = list(range(len(ins)))
