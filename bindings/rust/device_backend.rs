@@ -145,6 +145,24 @@ impl SlotImage {
         check(unsafe { kc_preview_level(size.width, size.height, max_extent, &mut level, &mut w, &mut h) })?;
         Ok((level, Size::new(w, h)))
     }
+    /// RGBA8 rects of mip levels of many images in one call (kc_image_previews), without building a chain: each request is
+    /// (image, level, rect (x, y, width, height) in texels of that level, None = the whole level).  Returns one tightly packed
+    /// width * height * 4 byte vector per request: to_u8 (`srgb`: to_u8_srgb) of that level of the chain, cut to the rect.
+    pub fn previews(requests: &[(&SlotImage, u32, Option<(u32, u32, u32, u32)>)], srgb: bool) -> Result<Vec<Vec<u8>>> {
+        let mut reqs = Vec::with_capacity(requests.len());
+        let mut total = 0usize;
+        for (img, level, rect) in requests {
+            let s = img.size()?;
+            let (x, y, w, h) = rect.unwrap_or((0, 0, s.width.checked_shr(*level).unwrap_or(0).max(1), s.height.checked_shr(*level).unwrap_or(0).max(1)));
+            reqs.push(KcPreviewRequest { image: img.raw(), level: *level, x, y, width: w, height: h, offset_bytes: total,
+                                         row_pitch_bytes: w as usize * 4 });
+            total += w as usize * h as usize * 4;
+        }
+        let mut out = vec![0u8; total.max(4)];
+        let flags = if srgb { KC_PREVIEW_SRGB } else { 0 };
+        check(unsafe { kc_image_previews(reqs.as_ptr(), reqs.len() as u32, flags, out.as_mut_ptr(), out.len()) })?;
+        Ok(reqs.iter().map(|q| out[q.offset_bytes..q.offset_bytes + q.width as usize * q.height as usize * 4].to_vec()).collect())
+    }
     /// The image that tightly packed BC blocks decode to (kc_image_from_bc), decoded on the device: to_u8 of the result is exactly
     /// the decoded bytes.  `gray` (BC4 only): a Gray image of the channel.  Also returns the BC7 blocks of partitioned modes,
     /// which are not decoded and give (0, 0, 0, 0).

@@ -564,6 +564,65 @@ KC_API int kc_image_to_bc_device(kc_image *img, const kc_bc_image *dst, uint32_t
 KC_API int kc_mip_level_count(uint32_t width, uint32_t height, uint32_t *levels);
 KC_API int kc_preview_level(uint32_t width, uint32_t height, uint32_t max_extent, uint32_t *level, uint32_t *level_width,
                             uint32_t *level_height);
+/* Previews: rects of mip levels of many images as RGBA8, without building a chain -- the thumbnails of an editor's nodes and
+ * the viewport of the selected one, in one call.  The bytes of one request are exactly kc_image_to_u8(levels[level], srgb) of
+ * kc_image_build_mips(image), cut to the rect: the 2 x 2 box above with every level rounded to f32, kc_image_to_u8's quantisers
+ * (Gray is (v, v, v, 255), alpha stays linear under KC_PREVIEW_SRGB, NaN exports as 255), constant planes folded on the host once
+ * per level.  Row j of the rect starts at byte offset_bytes + j * row_pitch_bytes of the output; bytes between the rows of a rect
+ * and bytes outside every rect are never written.  Requests whose byte ranges overlap are the caller's error: the library does
+ * not detect it and what such bytes hold afterwards is undefined.
+ *   Passes.   With H = min(floor(log2 w), floor(log2 h)) -- how often both extents halve -- a request with level <= H is fused:
+ *             one workgroup per 64 x 64 source tile that touches the rect's footprint reduces it min(level, 6) levels in
+ *             registers and stores only the last, straight to RGBA8 when level <= 6.  A deeper level first writes the level-6
+ *             values of the footprint (the rect scaled by 2^(level - 6)) to an f32 scratch, which the next pass reads as an image
+ *             of its own, and so on: ceil(level / 6) passes, no level in between ever stored.  Level 0 is read directly, four
+ *             texels per thread.  A request with level > H (one extent has reached 1, the box clamps) takes the fallback:
+ *             kc_image_build_mips, then the rect of levels[level] (counter "preview_fallback").  An image of constant planes
+ *             reads nothing and is filled by the same launch.
+ *   Launches. All requests of a call share each pass: a batch without fallbacks is max(1, ceil(max level / 6)) launches whatever
+ *             `count` is (kc_stats; counter "preview_launches"), the jobs of a pass one table uploaded with one copy.  Planes that
+ *             alias (kc_image_as_type's [p, p, p, ones]) are read once.  kc_stats_algorithmic_bytes: 4 bytes per source texel
+ *             read -- the tiles that touch the footprint, clipped to the image; the rect itself at level 0 -- per distinct
+ *             resident plane, plus the bytes written (4 per texel of the rect, 4 per plane and scratch texel).
+ *   kc_image_previews         into host memory; blocks until the bytes are there.
+ *   kc_image_previews_device  into device memory (a multiple of 4; `bytes` at least the last byte of any request, that extent in
+ *                             one allocation of the library's device, as kc_image_to_bc_mips_device validates it), ordered
+ *                             against `hip_stream` by the two event edges of kc_image_to_device.
+ *   kc_live_graph_buffer_previews  request i reads the image of slot slot_ids[i] of node node_ids[i]; r[i].image is ignored.
+ *   kc_preview_plan           what one request of a w x h image takes: arithmetic, no kc_init needed -- the same host function the
+ *                             entry points plan with.  An all-constant image is not planned: it always runs as one level-0 pass.
+ * Pending chains and deferred resizes of every named image run first.  count == 0 is KC_OK and launches nothing; count > 4096 is
+ * KC_ERR_INVALID_ARG.  Errors, in this order: flag bits other than KC_PREVIEW_SRGB KC_ERR_UNSUPPORTED; a NULL argument (also with
+ * count == 0), a NULL image, an empty rect, an offset or a pitch that is not a multiple of 4, a pitch below 4 * width, a request
+ * whose last byte lies past the buffer KC_ERR_INVALID_ARG; KC_ERR_NO_DEVICE before kc_init; KC_ERR_NO_SLOT_DATA where
+ * kc_live_graph_buffer_device returns it; a level at or above L or a rect that reaches outside the level KC_ERR_INVALID_ARG.  A
+ * failed call writes nothing. */
+typedef struct kc_preview_request {
+    kc_image *image;              /* ignored by the live-graph form */
+    uint32_t level;               /* 0 .. L-1 */
+    uint32_t x, y, width, height; /* rect in texels of that level: non-empty, inside the level */
+    size_t offset_bytes;          /* first byte of the rect's RGBA8 rows in the output; multiple of 4 */
+    size_t row_pitch_bytes;       /* multiple of 4, >= 4 * width */
+} kc_preview_request;
+#define KC_PREVIEW_SRGB 1u        /* R, G, B (Gray: the value) as kc_image_to_u8 with srgb = 1 writes them; alpha linear */
+#define KC_PREVIEW_MAX_PASSES 6
+typedef struct kc_preview_plan_info {
+    uint32_t passes;              /* launches the request takes part in (the fallback: 1, after the chain's own) */
+    uint32_t fallback;            /* 1: level > H, kc_image_build_mips runs first */
+    uint32_t level_width, level_height;                   /* the extent of the requested level */
+    uint32_t levels[KC_PREVIEW_MAX_PASSES];               /* per pass: the levels it reduces, 0 .. 6 */
+    uint32_t workgroups[KC_PREVIEW_MAX_PASSES];           /* per pass: its workgroups of 256 threads */
+    uint32_t scratch_width[KC_PREVIEW_MAX_PASSES];        /* per pass: the extent it writes to the f32 scratch of the next */
+    uint32_t scratch_height[KC_PREVIEW_MAX_PASSES];       /*   pass; 0 x 0 for the last pass */
+    uint64_t scratch_bytes[KC_PREVIEW_MAX_PASSES];        /* per pass: that scratch's bytes per distinct resident plane */
+} kc_preview_plan_info;
+KC_API int kc_image_previews(const kc_preview_request *r, uint32_t count, uint32_t flags, uint8_t *host, size_t host_bytes);
+KC_API int kc_image_previews_device(const kc_preview_request *r, uint32_t count, uint32_t flags, void *device_ptr, size_t bytes,
+                                    void *hip_stream);
+KC_API int kc_live_graph_buffer_previews(kc_live_graph *lg, const uint32_t *node_ids, const uint32_t *slot_ids,
+                                         const kc_preview_request *r, uint32_t count, uint32_t flags, uint8_t *host, size_t host_bytes);
+KC_API int kc_preview_plan(uint32_t width, uint32_t height, uint32_t level, uint32_t x, uint32_t y, uint32_t rect_w, uint32_t rect_h,
+                           kc_preview_plan_info *out);
 KC_API int kc_image_build_mips(kc_image *img, uint32_t flags, kc_image **levels, uint32_t cap, uint32_t *count);
 KC_API int kc_bc_mip_layout(uint32_t width, uint32_t height, int format, uint32_t *levels, size_t *offsets, uint32_t cap,
                             size_t *total_bytes);

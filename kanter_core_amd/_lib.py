@@ -71,6 +71,21 @@ class kc_dds_info(C.Structure):
                 ("data_offset", C.c_size_t), ("data_bytes", C.c_size_t)]
 
 
+class kc_preview_request(C.Structure):
+    _fields_ = [("image", c_vp), ("level", C.c_uint32), ("x", C.c_uint32), ("y", C.c_uint32), ("width", C.c_uint32), ("height", C.c_uint32),
+                ("offset_bytes", C.c_size_t), ("row_pitch_bytes", C.c_size_t)]
+
+
+PREVIEW_MAX_PASSES = 6
+
+
+class kc_preview_plan_info(C.Structure):
+    _fields_ = [("passes", C.c_uint32), ("fallback", C.c_uint32), ("level_width", C.c_uint32), ("level_height", C.c_uint32),
+                ("levels", C.c_uint32 * PREVIEW_MAX_PASSES), ("workgroups", C.c_uint32 * PREVIEW_MAX_PASSES),
+                ("scratch_width", C.c_uint32 * PREVIEW_MAX_PASSES), ("scratch_height", C.c_uint32 * PREVIEW_MAX_PASSES),
+                ("scratch_bytes", C.c_uint64 * PREVIEW_MAX_PASSES)]
+
+
 # name -> (restype, argtypes); every symbol include/kanter_core_amd.h declares.
 SIGNATURES = {
     "kc_init": (C.c_int, [C.c_int]),
@@ -178,6 +193,10 @@ SIGNATURES = {
     "kc_image_build_mips": (C.c_int, [c_vp, C.c_uint32, C.POINTER(c_vp), C.c_uint32, C.POINTER(C.c_uint32)]),
     "kc_bc_mip_layout": (C.c_int, [C.c_uint32, C.c_uint32, C.c_int, C.POINTER(C.c_uint32), C.POINTER(C.c_size_t), C.c_uint32,
                                    C.POINTER(C.c_size_t)]),
+    "kc_image_previews": (C.c_int, [C.POINTER(kc_preview_request), C.c_uint32, C.c_uint32, c_vp, C.c_size_t]),
+    "kc_image_previews_device": (C.c_int, [C.POINTER(kc_preview_request), C.c_uint32, C.c_uint32, c_vp, C.c_size_t, c_vp]),
+    "kc_live_graph_buffer_previews": (C.c_int, [c_vp, c_u32p, c_u32p, C.POINTER(kc_preview_request), C.c_uint32, C.c_uint32, c_vp, C.c_size_t]),
+    "kc_preview_plan": (C.c_int, [C.c_uint32] * 7 + [C.POINTER(kc_preview_plan_info)]),
     "kc_image_to_bc_mips": (C.c_int, [c_vp, C.c_int, C.c_uint32, c_vp, C.c_size_t]),
     "kc_image_to_bc_mips_device": (C.c_int, [c_vp, C.c_int, C.c_uint32, c_vp, C.c_size_t, c_vp]),
     "kc_dds_header": (C.c_int, [C.c_uint32, C.c_uint32, C.c_int, C.c_uint32, C.c_uint32, c_vp, C.POINTER(C.c_size_t)]),

@@ -716,6 +716,69 @@ def preview_level(width, height, max_extent):
     return k.value, w.value, h.value
 
 
+PREVIEW_SRGB = 1  # kc_image_previews: R, G, B (Gray: the value) as to_u8_srgb writes them, alpha linear
+
+PreviewPlan = collections.namedtuple("PreviewPlan", "passes fallback level_size levels workgroups scratch_sizes scratch_bytes")
+PreviewPlan.__doc__ = """What one preview request takes (kc_preview_plan): passes = the launches it takes part in, fallback = the
+chain is built first (level past the last one at which both extents halve), level_size = (width, height) of the level, and per
+pass the levels it reduces (0 .. 6), its workgroups, the (width, height) it writes to the f32 scratch of the next pass ((0, 0)
+for the last) and that scratch's bytes per distinct resident plane."""
+
+
+def preview_plan(width, height, level, rect=None):
+    """-> PreviewPlan of texels rect = (x, y, w, h) (None: the whole level) of mip level `level` of a width x height image
+    (kc_preview_plan; no device)."""
+    x, y, rw, rh = (0, 0, max(1, width >> level), max(1, height >> level)) if rect is None else rect
+    info = _lib.kc_preview_plan_info()
+    _check(_lib.load().kc_preview_plan(width, height, level, x, y, rw, rh, C.byref(info)))
+    n = info.passes
+    return PreviewPlan(n, bool(info.fallback), (info.level_width, info.level_height), list(info.levels[:n]), list(info.workgroups[:n]),
+                       [(info.scratch_width[p], info.scratch_height[p]) for p in range(n)], list(info.scratch_bytes[:n]))
+
+
+def _preview_requests(items):
+    """items: (image handle or None, Size, level, rect or None) -> (kc_preview_request array, offsets, (h, w) shapes, total bytes):
+    the rects tightly packed one after the other."""
+    reqs = (_lib.kc_preview_request * max(1, len(items)))()
+    offsets, shapes, total = [], [], 0
+    for i, (handle, size, level, rect) in enumerate(items):
+        x, y, w, h = (0, 0, max(1, size.width >> level), max(1, size.height >> level)) if rect is None else rect
+        reqs[i] = _lib.kc_preview_request(handle, level, x, y, w, h, total, 4 * w)
+        offsets.append(total)
+        shapes.append((h, w))
+        total += 4 * w * h
+    return reqs, offsets, shapes, total
+
+
+def _preview_views(buf, offsets, shapes):
+    return [buf[o:o + 4 * w * h].reshape(h, w, 4) for o, (h, w) in zip(offsets, shapes)]
+
+
+def previews(requests, srgb=False):
+    """RGBA8 rects of mip levels of many images in one call (kc_image_previews): requests = [(image, level, rect or None)], rect =
+    (x, y, w, h) in texels of that level, None = the whole level.  -> one (h, w, 4) uint8 array per request, views of one buffer:
+    exactly to_u8 of that level of build_mips(image), cut to the rect, without building a chain."""
+    reqs, offsets, shapes, total = _preview_requests([(img._h, img.size(), level, rect) for img, level, rect in requests])
+    buf = np.empty((max(total, 4),), dtype=np.uint8)
+    _check(_lib.load().kc_image_previews(reqs, len(requests), PREVIEW_SRGB if srgb else 0, buf.ctypes.data, buf.nbytes))
+    return _preview_views(buf, offsets, shapes)
+
+
+def previews_torch(requests, srgb=False, out=None):
+    """previews into device memory (kc_image_previews_device) -> (flat uint8 tensor, offsets): request i's tightly packed (h, w, 4)
+    rows start at offsets[i].  `out` (contiguous, 1-D, at least the total) is written instead of a new tensor, bytes outside the
+    rects are not touched.  Ready on torch's current stream."""
+    import torch
+    reqs, offsets, shapes, total = _preview_requests([(img._h, img.size(), level, rect) for img, level, rect in requests])
+    if out is None:
+        out = torch.empty((max(total, 4),), dtype=torch.uint8, device=torch.device("cuda", torch.cuda.current_device()))
+    if out.dtype != torch.uint8 or out.dim() != 1 or not out.is_contiguous() or out.numel() < total:
+        raise ValueError("out must be a contiguous 1-D uint8 tensor of at least %d bytes" % total)
+    _check(_on_torch_stream(out, lambda stream: _lib.load().kc_image_previews_device(reqs, len(requests), PREVIEW_SRGB if srgb else 0,
+                                                                                     C.c_void_p(out.data_ptr()), out.numel(), stream)))
+    return out, offsets
+
+
 def bc_mip_layout(width, height, fmt):
     """-> (offsets, total_bytes) of the BC mip chain of a width x height image (kc_bc_mip_layout; no device): level k's tightly
     packed blocks start at offsets[k], the chain is total_bytes long."""
@@ -1029,6 +1092,12 @@ class SlotImage:
         Ready on torch's current stream."""
         return _bc_mips_export(lambda f, fl, p, n, st: _lib.load().kc_image_to_bc_mips_device(self._h, f, fl, p, n, st), self.size(), fmt,
                                srgb, per_level, out)
+
+    def preview(self, max_extent, srgb=False):
+        """-> (h, w, 4) uint8: the whole mip level a preview of at most max_extent texels a side is cut from (preview_level), read
+        without building the chain (kc_image_previews)."""
+        s = self.size()
+        return previews([(self, preview_level(s.width, s.height, max_extent)[0], None)], srgb)[0]
 
     def write_dds(self, path, fmt, srgb=False, mips=True):
         """Writes a .dds file (DX10 header) with the image's BC blocks: the whole mip chain, or level 0 alone (kc_image_write_dds)."""
@@ -1412,6 +1481,17 @@ class LiveGraph:
         """SlotImage.to_bc_mips_torch of a slot's image (kc_live_graph_buffer_bc_mips)."""
         return _bc_mips_export(lambda f, fl, p, n, st: _lib.load().kc_live_graph_buffer_bc_mips(self._h, node_id, slot_id, f, fl, p, n, st),
                                self.slot_data_size(node_id, slot_id), fmt, srgb, per_level, out)
+
+    def buffer_previews(self, items, srgb=False):
+        """previews of slots' images (kc_live_graph_buffer_previews): items = [(node_id, slot_id, level, rect or None)] -> one
+        (h, w, 4) uint8 array per item."""
+        reqs, offsets, shapes, total = _preview_requests([(None, self.slot_data_size(n, sl), level, rect) for n, sl, level, rect in items])
+        nodes = (C.c_uint32 * max(1, len(items)))(*[it[0] for it in items])
+        slots = (C.c_uint32 * max(1, len(items)))(*[it[1] for it in items])
+        buf = np.empty((max(total, 4),), dtype=np.uint8)
+        _check(_lib.load().kc_live_graph_buffer_previews(self._h, nodes, slots, reqs, len(items), PREVIEW_SRGB if srgb else 0, buf.ctypes.data,
+                                                         buf.nbytes))
+        return _preview_views(buf, offsets, shapes)
 
     def buffer_bc_error(self, node_id, slot_id, fmt, srgb=False):
         """SlotImage.bc_error of a slot's image (kc_live_graph_buffer_bc_error)."""

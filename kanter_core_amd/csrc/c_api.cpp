@@ -174,6 +174,7 @@ try {
     }
     c.upload_next = 0;
     channel_stats_release();
+    preview_release();
     for (auto &kv : c.taps) (void)hipFree(kv.second.dev_block);
     c.taps.clear();
     for (auto &kv : c.band_taps) (void)hipFree(kv.second.dev_block);
@@ -873,6 +874,27 @@ KC_CATCH
 int kc_preview_level(uint32_t width, uint32_t height, uint32_t max_extent, uint32_t *level, uint32_t *level_width, uint32_t *level_height)
 try {
     return preview_level(width, height, max_extent, level, level_width, level_height);
+}
+KC_CATCH
+
+int kc_preview_plan(uint32_t width, uint32_t height, uint32_t level, uint32_t x, uint32_t y, uint32_t rect_w, uint32_t rect_h,
+                    kc_preview_plan_info *out)
+try {
+    return preview_plan(width, height, level, x, y, rect_w, rect_h, out);
+}
+KC_CATCH
+
+int kc_image_previews(const kc_preview_request *r, uint32_t count, uint32_t flags, uint8_t *host, size_t host_bytes)
+try {
+    Lock api_lock(ctx().mu);  // reference counts are plain integers, see kc_plane::refs
+    return image_previews(r, nullptr, count, flags, host, host_bytes, "kc_image_previews");  // the flags, the arguments, then need_init()
+}
+KC_CATCH
+
+int kc_image_previews_device(const kc_preview_request *r, uint32_t count, uint32_t flags, void *device_ptr, size_t bytes, void *hip_stream)
+try {
+    Lock api_lock(ctx().mu);  // reference counts are plain integers, see kc_plane::refs
+    return image_previews_device(r, count, flags, device_ptr, bytes, hip_stream);
 }
 KC_CATCH
 
@@ -1617,6 +1639,26 @@ try {
     const SlotData *sd = lg->find_slot(node, slot);
     if (!sd) return KC_ERR_NO_SLOT_DATA;
     return image_to_bc_mips_device(sd->image, format, flags, device_ptr, bytes, hip_stream);
+}
+KC_CATCH
+
+int kc_live_graph_buffer_previews(kc_live_graph *lg, const uint32_t *node_ids, const uint32_t *slot_ids, const kc_preview_request *r,
+                                  uint32_t count, uint32_t flags, uint8_t *host, size_t host_bytes)
+try {
+    const char *who = "kc_live_graph_buffer_previews";
+    // the flags and the arithmetic of the requests first (no image is looked at), then need_init(), then the slots
+    KC_TRY(preview_check(r, count, flags, host, host_bytes, false, who));
+    LG_LOCK(lg);
+    KC_ARG(node_ids && slot_ids);
+    if (count == 0) return KC_OK;
+    std::vector<kc_image *> imgs(count, nullptr);
+    KC_TRY(need_init());
+    for (uint32_t i = 0; i < count; ++i) {
+        const SlotData *sd = lg->find_slot(node_ids[i], slot_ids[i]);
+        if (!sd) return KC_ERR_NO_SLOT_DATA;
+        imgs[i] = sd->image;
+    }
+    return image_previews(r, imgs.data(), count, flags, host, host_bytes, who);
 }
 KC_CATCH
 

@@ -22,6 +22,7 @@
 #include <vector>
 
 #include "../../include/kanter_core_amd.h"
+#include "preview_walk.h"  // PreviewJob and the index arithmetic of preview.hip / preview.cpp (namespace kc; compiles without HIP too)
 
 namespace kc {
 
@@ -394,5 +395,10 @@ struct MipLevelArgs {
     uint32_t w, h;
 };
 hipError_t launch_mip_level(const MipLevelArgs &a, uint32_t n_planes, bool nt, hipStream_t s);
+// -- preview.hip --
+// Previews (preview.hip / preview.cpp): preview_kernel<srgb, nt> on `workgroups` workgroups, one pass of a batch.  jobs: `count`
+// PreviewJob (preview_walk.h) in device memory; prefix: count + 1 words, prefix[j] = the first workgroup of job j, prefix[count] =
+// workgroups.  srgb: R, G, B (Gray: the value) of the jobs that store RGBA8 go through quant_u8_srgb.
+hipError_t launch_preview(const PreviewJob *jobs, const uint32_t *prefix, uint32_t count, uint32_t workgroups, bool srgb, bool nt, hipStream_t s);
 
 }  // namespace kc

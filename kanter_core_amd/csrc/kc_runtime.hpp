@@ -270,6 +270,14 @@ struct Context {
         uint32_t cus = 0;
     };
     StatsBuffers stats;
+    // kc_image_previews (preview.cpp): the pinned host copy of a batch's job tables and the event behind its upload -- allocated
+    // on first use, grown when needed, freed at kc_shutdown
+    struct PreviewBuffers {
+        void *host = nullptr;
+        size_t bytes = 0;
+        hipEvent_t copied = nullptr;
+    };
+    PreviewBuffers preview;
 };
 
 // RAII scope for the resize memo (nested Graph nodes share the outermost scope).
@@ -447,6 +455,14 @@ int image_to_bc_mips(kc_image *img, int format, uint32_t flags, uint8_t *host, s
 int image_to_bc_mips_device(kc_image *img, int format, uint32_t flags, void *device_ptr, size_t bytes, void *hip_stream);
 int dds_header(uint32_t w, uint32_t h, int format, uint32_t flags, uint32_t levels, uint8_t *out, size_t *bytes);
 int image_write_dds(kc_image *img, const char *path, int format, uint32_t flags, int with_mips);
+// previews (preview.cpp): the bodies of kc_preview_plan, kc_image_previews, kc_image_previews_device and (given the slots' images)
+// kc_live_graph_buffer_previews; `imgs` (optional): the image of request i instead of r[i].image.  The context's buffers.
+int preview_plan(uint32_t w, uint32_t h, uint32_t level, uint32_t x, uint32_t y, uint32_t rect_w, uint32_t rect_h, kc_preview_plan_info *out);
+// the checks that look at no image: the flags, the arguments, every request's rect, offset, pitch and last byte (images_named: and its image)
+int preview_check(const kc_preview_request *r, uint32_t count, uint32_t flags, const void *out, size_t out_bytes, bool images_named, const char *who);
+int image_previews(const kc_preview_request *r, kc_image *const *imgs, uint32_t count, uint32_t flags, uint8_t *host, size_t host_bytes, const char *who);
+int image_previews_device(const kc_preview_request *r, uint32_t count, uint32_t flags, void *device_ptr, size_t bytes, void *hip_stream);
+void preview_release();
 // per-channel statistics (stats.cpp): the body of kc_image_channel_stats; the context's buffers, released at kc_shutdown
 int image_channel_stats(kc_image *img, uint32_t flags, kc_channel_stats *out);
 int stats_buffers(size_t partials_bytes);  // the context's StatsBuffers, with room for that many bytes of partial records
