@@ -129,13 +129,20 @@ impl SlotImage {
     /// the level above it in f32, built on the device; the levels follow one another, tightly packed, down to 1 x 1.  Returns the
     /// bytes and the offset of every level (kc_bc_mip_layout).
     pub fn to_bc_mips(&self, format: i32, srgb: bool) -> Result<(Vec<u8>, Vec<usize>)> {
+        self.bc_mips_with(format, if srgb { KC_BC_SRGB } else { 0 })
+    }
+    /// to_bc_mips of a normal map (KC_MIP_NORMALS; KC_BC5 is the usual format): R, G, B are a vector stored as n * 0.5 + 0.5 and
+    /// every level is renormalised on the device before the next is made, so the coarser levels do not flatten.
+    pub fn to_normal_bc_mips(&self, format: i32) -> Result<(Vec<u8>, Vec<usize>)> {
+        self.bc_mips_with(format, KC_MIP_NORMALS)
+    }
+    fn bc_mips_with(&self, format: i32, flags: u32) -> Result<(Vec<u8>, Vec<usize>)> {
         let s = self.size()?;
         let (mut levels, mut total) = (0u32, 0usize);
         check(unsafe { kc_bc_mip_layout(s.width, s.height, format, &mut levels, ptr::null_mut(), 0, &mut total) })?;
         let mut offsets = vec![0usize; levels as usize];
         check(unsafe { kc_bc_mip_layout(s.width, s.height, format, &mut levels, offsets.as_mut_ptr(), levels, &mut total) })?;
         let mut out = vec![0u8; total];
-        let flags = if srgb { KC_BC_SRGB } else { 0 };
         check(unsafe { kc_image_to_bc_mips(self.raw(), format, flags, out.as_mut_ptr(), out.len()) })?;
         Ok((out, offsets))
     }

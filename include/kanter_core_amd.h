@@ -207,8 +207,8 @@ KC_API int kc_stats_algorithmic_bytes(uint64_t *bytes);
  * "chain1_nt<0-7>" (a one-step kernel with its nontemporal bits: 1 the start plane, 2 the operand, 4 the result),
  * "specialized_nt_<3 hex digits>" (a kernel compiled at run time and its cache-policy bits: 0x001 << k input plane k < 8,
  * 0x100 the result), "specialized_nt_<3 hex digits>_q2" / "_q4" when that kernel handles 2 / 4 float4 per lane instead of one
- * (kc_set_chain_quads).  The mip kernels (one per launch): "mip_pyramid", "mip_level", and "mip_nt" for each of those launches
- * that reads its source nontemporally.  The streaming kernels, by the form each launch took: HeightToNormal "h2n_launches", one
+ * (kc_set_chain_quads).  The mip kernels (one per launch): "mip_pyramid", "mip_level", under KC_MIP_NORMALS "mip_normals_pyramid",
+ * "mip_normals_level" for R, G, B, and "mip_nt" for each of those launches that reads its source nontemporally.  The streaming kernels, by the form each launch took: HeightToNormal "h2n_launches", one
  * of "h2n_plain", "h2n_tiled_q5", "h2n_tiled_q6", "h2n_tiled_q7" (a row per 256 threads, or tiles of 32, 64, 128 column
  * quads), "h2n_band" (a row band with its halo row), "h2n_nt" (nontemporal stores); the u8 boundary "to_u8_nt", "from_u8_nt"
  * (kc_image_to_u8 / _from_u8 and the u8 pipe); device images "image_import_vec" or "image_import_scalar" and
@@ -527,14 +527,43 @@ KC_API int kc_image_to_bc_device(kc_image *img, const kc_bc_image *dst, uint32_t
  *             (kc_image_as_type's [p, p, p, ones]) are reduced once and the level images alias the same way.  Pending chains and
  *             deferred resizes run first.  Planes are linear f32 and sRGB is applied at export (KC_BC_SRGB, kc_image_to_u8 with
  *             srgb), so the average is taken in linear light.
- *   kc_mip_level_count   L for a size; arithmetic, no kc_init needed.
+ *   Normal maps (KC_MIP_NORMALS).  The box of four unit vectors is shorter than 1, and a renderer that rebuilds Z from a BC5
+ *             texel as sqrt(1 - x^2 - y^2) reads the shortened XY pair as a flatter surface at every coarser level.  With the
+ *             flag, an RGBA image is a normal map: X, Y, Z are R, G, B stored as n * 0.5 + 0.5 (what kc_height_to_normal_process
+ *             writes), and every level is renormalised on the device before the next is made (tests/mip_normals_ref.py is the
+ *             same rule in numpy).  Level 0 is the image itself, untouched.  Level k >= 1 is made from level k - 1 as stored;
+ *             per texel, with b_c the plain rule's box of channel c (the same expression, order and clamps), c over R, G, B:
+ *                 v_c = b_c * 2.0f - 1.0f                      one multiplication, one subtraction, nothing fused
+ *                 q = (v_x * v_x + v_y * v_y) + v_z * v_z,  l = sqrtf(q)    correctly rounded
+ *                 u_c = v_c / l (IEEE divide) if l > 0 && l < +inf, else u = (0, 0, 1)
+ *                 d_c = u_c * 0.5f + 0.5f
+ *             The comparison is false for NaN: a zero vector, an underflowed or overflowed q and a NaN or infinity in any of
+ *             the three channels all store exactly (0.5, 0.5, 1.0), so R, G, B of levels >= 1 never hold a NaN (NaN payloads
+ *             do not enter the contract).  Denormals are kept.  Alpha follows the plain rule unchanged, constant or resident.
+ *             Each level is normalised and rounded to f32 before the next is made, so the fused form and KC_MIP_PER_LEVEL give
+ *             the same bits.  Planes: if R, G and B are all constant, levels >= 1 are constant planes, folded on the host with
+ *             the same expression (kc_mip_normal_texel of the three folded boxes) and nothing is launched for them; if at least
+ *             one is resident, every level >= 1 has three new resident planes for R, G, B -- a constant channel enters the first
+ *             level as its value (its box is ((c + c) + (c + c)) * 0.25f), aliased channels are read once and written three
+ *             times.  kc_stats: the same launches as the plain chain of the three planes (counters "mip_normals_pyramid",
+ *             "mip_normals_level"; a resident alpha is reduced by launches of its own under "mip_pyramid" / "mip_level"), so a
+ *             kc_height_to_normal_process result takes as many launches as its plain chain; 4 w h algorithmic bytes per
+ *             distinct resident plane among R, G, B read plus 12 sum_{k >= 1} W_k H_k written, plus alpha's by the plain rule.
+ *             Accepted by kc_image_build_mips, kc_image_to_bc_mips, kc_image_to_bc_mips_device, kc_live_graph_buffer_bc_mips
+ *             and kc_image_write_dds (without mips it has no effect); any BC format (BC5 is the point; BC4 reads R alone).
+ *             With KC_BC_SRGB it is KC_ERR_UNSUPPORTED (a vector is not a colour), refused with the other flag errors; a Gray
+ *             image is KC_ERR_INVALID_ARG, after KC_ERR_NO_DEVICE, with nothing launched or allocated (`*count` is written).
+ *             kc_dds_header refuses the flag: the header does not depend on it.  Previews stay defined by the plain rule.
+ *   kc_mip_normal_texel  the rule above from the three boxes to the stored texel, out = d(box): the function the constant fold
+ *                        calls.  Arithmetic, no kc_init needed.  A NULL argument is KC_ERR_INVALID_ARG.
+ *   kc_mip_level_count  L for a size; arithmetic, no kc_init needed.
  *   kc_preview_level     the level a thumbnail or a viewport of at most max_extent texels a side is cut from: the smallest k with
  *                        max(W_k, H_k) <= max_extent, and that level's size (k < L always: the last level is 1 x 1).  Arithmetic, no
  *                        kc_init needed.  max_extent == 0, a zero size or a NULL output is KC_ERR_INVALID_ARG and writes nothing.
  *   kc_image_build_mips  levels[0] = img itself (+1 reference), levels[k] a new image of the same kind (+1 reference each);
  *                        `*count` = L whenever the image is known; cap < L is KC_ERR_INVALID_ARG with nothing launched and nothing
  *                        allocated.  Enqueued on the library's stream; the call does not wait.  A failure part-way releases what
- *                        it made.  KC_MIP_PER_LEVEL: one launch per level (A/B runs and tests; the same bits).
+ *                        it made.  KC_MIP_PER_LEVEL: one launch per level (A/B runs and tests; the same bits).  KC_MIP_NORMALS: above.
  *                        kc_stats: one launch per up to six levels while both extents still halve, one per level after that
  *                        (4096 x 4096: two; counters "mip_pyramid", "mip_level"); 4 w h algorithmic bytes per distinct resident
  *                        plane read plus 4 sum_{k >= 1} W_k H_k per plane written; constant planes launch nothing.
@@ -543,7 +572,8 @@ KC_API int kc_image_to_bc_device(kc_image *img, const kc_bc_image *dst, uint32_t
  *                        levels 0 .. L - 1 follow one another.  `*levels` = L, offsets[k] = level k's first byte (`offsets` may be
  *                        NULL; otherwise cap < L is KC_ERR_INVALID_ARG), `*total_bytes` = the chain's bytes.  Arithmetic, no kc_init.
  *   kc_image_to_bc_mips  kc_image_build_mips, then the encoder of kc_image_to_bc once per level, into host memory (`host_bytes`
- *                        at least the total); blocks until the bytes are there.  flags: KC_BC_SRGB (BC1 / BC3 / BC7) | KC_MIP_PER_LEVEL.
+ *                        at least the total); blocks until the bytes are there.  flags: KC_BC_SRGB (BC1 / BC3 / BC7) | KC_MIP_PER_LEVEL |
+ *                        KC_MIP_NORMALS.
  *                        KC_BC6H quantises every level's own f32 values, so the chain keeps the range of the planes.
  *   kc_image_to_bc_mips_device  the same into device memory (a multiple of the block bytes; `bytes` at least the total, the
  *                        total's extent in one allocation of the library's device), ordered against `hip_stream` by the two event
@@ -556,11 +586,13 @@ KC_API int kc_image_to_bc_device(kc_image *img, const kc_bc_image *dst, uint32_t
  *                        BC5 83, BC6H 95, BC7 98, with KC_BC_SRGB BC1 72, BC3 78, BC7 99.  1 <= levels <= L.  `*bytes` (optional) = 148.
  *                        No kc_init.
  *   kc_image_write_dds   the header, then the chain (with_mips != 0) or level 0 alone.
- * Errors, in this order: unknown flag bits, or KC_BC_SRGB with BC4 / BC5 / BC6H, KC_ERR_UNSUPPORTED; a NULL argument, a zero size, an
+ * Errors, in this order: unknown flag bits, KC_BC_SRGB with BC4 / BC5 / BC6H, or KC_MIP_NORMALS with KC_BC_SRGB, KC_ERR_UNSUPPORTED; a NULL argument, a zero size, an
  * unknown format, a size below the total KC_ERR_INVALID_ARG; KC_ERR_NO_DEVICE before kc_init; KC_ERR_NO_SLOT_DATA where
  * kc_live_graph_buffer_bc returns it; KC_ERR_IO for a file that cannot be written. */
 #define KC_MIP_PER_LEVEL 2u  /* one launch of the one-level kernel per level instead of the fused pyramid kernel; a bit of its
                                 own beside KC_BC_SRGB, since the chain exporters take both in one flags word */
+#define KC_MIP_NORMALS 32u   /* R, G, B are a normal map: every level is renormalised before the next is made (above); 4 and 8
+                                stay refused by the chain entry points, 16 is KC_BC_ALL_MODES */
 KC_API int kc_mip_level_count(uint32_t width, uint32_t height, uint32_t *levels);
 KC_API int kc_preview_level(uint32_t width, uint32_t height, uint32_t max_extent, uint32_t *level, uint32_t *level_width,
                             uint32_t *level_height);
@@ -623,6 +655,7 @@ KC_API int kc_live_graph_buffer_previews(kc_live_graph *lg, const uint32_t *node
                                          const kc_preview_request *r, uint32_t count, uint32_t flags, uint8_t *host, size_t host_bytes);
 KC_API int kc_preview_plan(uint32_t width, uint32_t height, uint32_t level, uint32_t x, uint32_t y, uint32_t rect_w, uint32_t rect_h,
                            kc_preview_plan_info *out);
+KC_API int kc_mip_normal_texel(const float box[3], float out[3]);
 KC_API int kc_image_build_mips(kc_image *img, uint32_t flags, kc_image **levels, uint32_t cap, uint32_t *count);
 KC_API int kc_bc_mip_layout(uint32_t width, uint32_t height, int format, uint32_t *levels, size_t *offsets, uint32_t cap,
                             size_t *total_bytes);

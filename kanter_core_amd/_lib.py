@@ -190,6 +190,7 @@ SIGNATURES = {
     "kc_image_to_bc_device": (C.c_int, [c_vp, C.POINTER(kc_bc_image), C.c_uint32, c_vp]),
     "kc_mip_level_count": (C.c_int, [C.c_uint32, C.c_uint32, C.POINTER(C.c_uint32)]),
     "kc_preview_level": (C.c_int, [C.c_uint32, C.c_uint32, C.c_uint32, c_u32p, c_u32p, c_u32p]),
+    "kc_mip_normal_texel": (C.c_int, [c_vp, c_vp]),
     "kc_image_build_mips": (C.c_int, [c_vp, C.c_uint32, C.POINTER(c_vp), C.c_uint32, C.POINTER(C.c_uint32)]),
     "kc_bc_mip_layout": (C.c_int, [C.c_uint32, C.c_uint32, C.c_int, C.POINTER(C.c_uint32), C.POINTER(C.c_size_t), C.c_uint32,
                                    C.POINTER(C.c_size_t)]),

@@ -699,6 +699,22 @@ def _bc_export(call, size, fmt, srgb, out):
 
 
 MIP_PER_LEVEL = 2  # kc_image_build_mips and the chain exporters: one launch of the one-level kernel per level
+MIP_NORMALS = 32   # ... R, G, B are a normal map (n * 0.5 + 0.5): every level is renormalised before the next is made
+
+
+def _mip_flags(srgb, per_level, normals):
+    return (BC_SRGB if srgb else 0) | (MIP_PER_LEVEL if per_level else 0) | (MIP_NORMALS if normals else 0)
+
+
+def mip_normal_texel(box):
+    """-> (3,) float32: what a texel of a normal-map chain (normals=True) stores for the 2 x 2 boxes `box` of R, G, B -- decoded,
+    normalised (a vector without a direction becomes (0, 0, 1)) and encoded again in f32 (kc_mip_normal_texel; no device)."""
+    b = np.ascontiguousarray(box, np.float32)
+    if b.shape != (3,):
+        raise ValueError("box must hold three values")
+    out = np.empty(3, np.float32)
+    _check(_lib.load().kc_mip_normal_texel(b.ctypes.data, out.ctypes.data))
+    return out
 
 
 def mip_level_count(width, height):
@@ -811,7 +827,7 @@ def _bc_mip_views(buf, size, fmt):
     return views
 
 
-def _bc_mips_export(call, size, fmt, srgb, per_level, out):
+def _bc_mips_export(call, size, fmt, srgb, per_level, out, normals=False):
     """Allocates (or takes) a flat uint8 tensor of at least the chain's bytes and runs `call(fmt, flags, ptr, bytes, stream)`."""
     import torch
     f = _bc_format(fmt)
@@ -820,7 +836,7 @@ def _bc_mips_export(call, size, fmt, srgb, per_level, out):
         out = torch.empty((total,), dtype=torch.uint8, device=torch.device("cuda", torch.cuda.current_device()))
     if out.dtype != torch.uint8 or out.dim() != 1 or not out.is_contiguous() or out.numel() < total:
         raise ValueError("out must be a contiguous 1-D uint8 tensor of at least %d bytes" % total)
-    flags = (BC_SRGB if srgb else 0) | (MIP_PER_LEVEL if per_level else 0)
+    flags = _mip_flags(srgb, per_level, normals)
     _check(_on_torch_stream(out, lambda stream: call(f, flags, C.c_void_p(out.data_ptr()), out.numel(), stream)))
     return out, offs
 
@@ -1064,34 +1080,36 @@ class SlotImage:
         whose last two dimensions are contiguous) is written instead of a new tensor.  Ready on torch's current stream."""
         return _bc_export(lambda d, f, st: _lib.load().kc_image_to_bc_device(self._h, d, f, st), self.size(), fmt, srgb, out)
 
-    def mips(self, per_level=False):
+    def mips(self, per_level=False, normals=False):
         """-> the mip chain as a list of SlotImage (kc_image_build_mips): entry 0 is this image, entry k is max(1, w >> k) by
         max(1, h >> k), the 2 x 2 box of the level above it in f32, down to 1 x 1.  per_level=True runs one launch per level
-        instead of the fused kernel (the same bits)."""
+        instead of the fused kernel (the same bits).  normals=True (RGBA only): R, G, B are a normal map stored as n * 0.5 + 0.5 and
+        every level is renormalised on the device before the next is made (KC_MIP_NORMALS); alpha follows the plain rule."""
         s = self.size()
         n = mip_level_count(s.width, s.height)
         arr = (C.c_void_p * n)()
         count = C.c_uint32()
-        _check(_lib.load().kc_image_build_mips(self._h, MIP_PER_LEVEL if per_level else 0, arr, n, C.byref(count)))
+        _check(_lib.load().kc_image_build_mips(self._h, _mip_flags(False, per_level, normals), arr, n, C.byref(count)))
         return [SlotImage(arr[k]) for k in range(count.value)]
 
-    def to_bc_mips(self, fmt, srgb=False, per_level=False):
+    def to_bc_mips(self, fmt, srgb=False, per_level=False, normals=False):
         """-> one uint8 (ceil(H_k/4), ceil(W_k/4), block bytes) array per level, shaped like to_bc's and views of one buffer
-        that holds the chain as a texture file stores it (kc_image_to_bc_mips)."""
+        that holds the chain as a texture file stores it (kc_image_to_bc_mips).  normals=True: the chain of a normal map, as mips
+        builds it (BC5 is the usual format; not with srgb)."""
         f = _bc_format(fmt)
         s = self.size()
         offs, total = bc_mip_layout(s.width, s.height, f)
         buf = np.empty((total,), np.uint8)
-        flags = (BC_SRGB if srgb else 0) | (MIP_PER_LEVEL if per_level else 0)
+        flags = _mip_flags(srgb, per_level, normals)
         _check(_lib.load().kc_image_to_bc_mips(self._h, f, flags, buf.ctypes.data, buf.nbytes))
         return _bc_mip_views(buf, s, f)
 
-    def to_bc_mips_torch(self, fmt, srgb=False, out=None, per_level=False):
+    def to_bc_mips_torch(self, fmt, srgb=False, out=None, per_level=False, normals=False):
         """-> (flat uint8 tensor in device memory holding the chain, offsets of the levels) (kc_image_to_bc_mips_device); `out`
         (contiguous, 1-D, at least the chain's bytes) is written instead of a new tensor, bytes past the chain are not touched.
         Ready on torch's current stream."""
         return _bc_mips_export(lambda f, fl, p, n, st: _lib.load().kc_image_to_bc_mips_device(self._h, f, fl, p, n, st), self.size(), fmt,
-                               srgb, per_level, out)
+                               srgb, per_level, out, normals)
 
     def preview(self, max_extent, srgb=False):
         """-> (h, w, 4) uint8: the whole mip level a preview of at most max_extent texels a side is cut from (preview_level), read
@@ -1099,9 +1117,10 @@ class SlotImage:
         s = self.size()
         return previews([(self, preview_level(s.width, s.height, max_extent)[0], None)], srgb)[0]
 
-    def write_dds(self, path, fmt, srgb=False, mips=True):
-        """Writes a .dds file (DX10 header) with the image's BC blocks: the whole mip chain, or level 0 alone (kc_image_write_dds)."""
-        _check(_lib.load().kc_image_write_dds(self._h, os.fspath(path).encode(), _bc_format(fmt), BC_SRGB if srgb else 0, int(mips)))
+    def write_dds(self, path, fmt, srgb=False, mips=True, normals=False):
+        """Writes a .dds file (DX10 header) with the image's BC blocks: the whole mip chain, or level 0 alone (kc_image_write_dds).
+        normals=True: the chain of a normal map, as to_bc_mips(normals=True) (no effect with mips=False)."""
+        _check(_lib.load().kc_image_write_dds(self._h, os.fspath(path).encode(), _bc_format(fmt), _mip_flags(srgb, False, normals), int(mips)))
 
     def bc_error(self, fmt, srgb=False, blocks=None, all_modes=False):
         """-> BcError: how far the image's BC encoding is from the image, measured on the device (kc_image_bc_error): the bytes
@@ -1477,10 +1496,10 @@ class LiveGraph:
         return _bc_export(lambda d, f, st: _lib.load().kc_live_graph_buffer_bc(self._h, node_id, slot_id, d, f, st),
                           self.slot_data_size(node_id, slot_id), fmt, srgb, out)
 
-    def buffer_bc_mips_torch(self, node_id, slot_id, fmt, srgb=False, out=None, per_level=False):
+    def buffer_bc_mips_torch(self, node_id, slot_id, fmt, srgb=False, out=None, per_level=False, normals=False):
         """SlotImage.to_bc_mips_torch of a slot's image (kc_live_graph_buffer_bc_mips)."""
         return _bc_mips_export(lambda f, fl, p, n, st: _lib.load().kc_live_graph_buffer_bc_mips(self._h, node_id, slot_id, f, fl, p, n, st),
-                               self.slot_data_size(node_id, slot_id), fmt, srgb, per_level, out)
+                               self.slot_data_size(node_id, slot_id), fmt, srgb, per_level, out, normals)
 
     def buffer_previews(self, items, srgb=False):
         """previews of slots' images (kc_live_graph_buffer_previews): items = [(node_id, slot_id, level, rect or None)] -> one

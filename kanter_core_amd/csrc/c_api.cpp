@@ -898,6 +898,14 @@ try {
 }
 KC_CATCH
 
+int kc_mip_normal_texel(const float box[3], float out[3])
+try {
+    KC_ARG(box && out);
+    mip_normal_texel(box, out);
+    return KC_OK;
+}
+KC_CATCH
+
 int kc_image_build_mips(kc_image *img, uint32_t flags, kc_image **levels, uint32_t cap, uint32_t *count)
 try {
     Lock api_lock(ctx().mu);  // reference counts are plain integers, see kc_plane::refs
@@ -1629,8 +1637,12 @@ KC_CATCH
 int kc_live_graph_buffer_bc_mips(kc_live_graph *lg, uint32_t node, uint32_t slot, int format, uint32_t flags, void *device_ptr,
                                  size_t bytes, void *hip_stream)
 try {
-    if (flags & ~(uint32_t)(KC_BC_SRGB | KC_MIP_PER_LEVEL)) {
+    if (flags & ~(uint32_t)(KC_BC_SRGB | KC_MIP_PER_LEVEL | KC_MIP_NORMALS)) {
         set_error("kc_live_graph_buffer_bc_mips: unknown flag bits");
+        return KC_ERR_UNSUPPORTED;
+    }
+    if ((flags & KC_MIP_NORMALS) && (flags & KC_BC_SRGB)) {
+        set_error("kc_live_graph_buffer_bc_mips: KC_MIP_NORMALS with KC_BC_SRGB");
         return KC_ERR_UNSUPPORTED;
     }
     LG_LOCK(lg);

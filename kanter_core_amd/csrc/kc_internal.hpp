@@ -395,6 +395,33 @@ struct MipLevelArgs {
     uint32_t w, h;
 };
 hipError_t launch_mip_level(const MipLevelArgs &a, uint32_t n_planes, bool nt, hipStream_t s);
+// -- mip_normals.hip --
+// Normal-map chains (KC_MIP_NORMALS): the same two walks with R, G, B coupled in one thread -- the box of each channel, then the
+// header's renormalisation of the three, at every level.  Channel c is a resident plane (src[c], src_pitch[c]), the constant
+// cval[c] (bit c of const_mask; src[c] is not looked at) or the loads of an earlier channel that aliases it (bits 2c, 2c + 1 of
+// `from` = that channel, c itself otherwise).  Every level has three resident planes of its own: dst[c][k - 1] is level k of
+// channel c in normal_pyramid_kernel<nt> (n, the tiles and the pitches as in MipPyramidArgs), dst[c] the one level of
+// normal_level_kernel<nt> (as MipLevelArgs).
+struct NormalPyramidArgs {
+    const float *src[3];
+    uint32_t src_pitch[3];  // floats
+    float cval[3];
+    uint32_t const_mask, from;
+    float *dst[3][6];
+    uint32_t dst_pitch[6];  // floats
+    uint32_t w, h, n;
+};
+hipError_t launch_normal_pyramid(const NormalPyramidArgs &a, bool nt, hipStream_t s);
+struct NormalLevelArgs {
+    const float *src[3];
+    uint32_t src_pitch[3];  // floats
+    float cval[3];
+    uint32_t const_mask, from;
+    float *dst[3];
+    uint32_t dst_pitch;  // floats
+    uint32_t w, h;
+};
+hipError_t launch_normal_level(const NormalLevelArgs &a, bool nt, hipStream_t s);
 // -- preview.hip --
 // Previews (preview.hip / preview.cpp): preview_kernel<srgb, nt> on `workgroups` workgroups, one pass of a batch.  jobs: `count`
 // PreviewJob (preview_walk.h) in device memory; prefix: count + 1 words, prefix[j] = the first workgroup of job j, prefix[count] =

@@ -445,10 +445,11 @@ int image_bc_error(kc_image *img, int format, uint32_t flags, kc_bc_error *out);
 int dds_parse(const uint8_t *data, size_t bytes, kc_dds_info *info);
 int image_read_dds(const char *path, uint32_t level, uint32_t flags, kc_image **out, kc_dds_info *info);
 // mip chains and their export (mip.cpp): the bodies of kc_mip_level_count, kc_preview_level, kc_image_build_mips, kc_bc_mip_layout,
-// kc_image_to_bc_mips, kc_image_to_bc_mips_device, kc_dds_header, kc_image_write_dds
+// kc_image_to_bc_mips, kc_image_to_bc_mips_device, kc_dds_header, kc_image_write_dds, kc_mip_normal_texel
 int mip_level_count(uint32_t w, uint32_t h, uint32_t *levels);
 int preview_level(uint32_t w, uint32_t h, uint32_t max_extent, uint32_t *level, uint32_t *pw, uint32_t *ph);
 float mip_const_fold(float c);  // ((c + c) + (c + c)) * 0.25f, as the device computes it
+void mip_normal_texel(const float box[3], float out[3]);  // KC_MIP_NORMALS: the boxes of R, G, B -> the stored texel, as the device computes it
 int image_build_mips(kc_image *img, uint32_t flags, kc_image **levels, uint32_t cap, uint32_t *count);
 int bc_mip_layout(uint32_t w, uint32_t h, int format, uint32_t *levels, size_t *offsets, uint32_t cap, size_t *total_bytes);
 int image_to_bc_mips(kc_image *img, int format, uint32_t flags, uint8_t *host, size_t host_bytes);

@@ -2,8 +2,11 @@
 // kc_image_to_bc_mips, kc_image_to_bc_mips_device, kc_dds_header, kc_image_write_dds.  The host side does the level arithmetic,
 // folds constant planes with the device's expression, allocates the level planes and enqueues mip.hip's kernels on the library's
 // stream: the pyramid kernel while both extents still halve (up to six levels per launch), the one-level kernel for the rest and
-// for every level under KC_MIP_PER_LEVEL.  The BC chain is bc.cpp's encoder launch once per level; the DDS writer is host code.
+// for every level under KC_MIP_PER_LEVEL; under KC_MIP_NORMALS mip_normals.hip's two kernels take R, G, B together and
+// renormalise every level.  The BC chain is bc.cpp's encoder launch once per level; the DDS writer is host code.
+#include <cmath>
 #include <cstdio>
+#include <limits>
 
 #include "kc_runtime.hpp"
 
@@ -51,12 +54,43 @@ float mip_const_fold(float c)
     return r;
 }
 
+// KC_MIP_NORMALS on one texel, from the boxes of R, G, B to the stored values: the device's expression (mip_normals.hip) with
+// the host's correctly rounded sqrtf and /, every operation through a volatile temporary like mip_const_fold.  This is
+// kc_mip_normal_texel and what folds an image whose R, G, B are all constant.
+void mip_normal_texel(const float box[3], float out[3])
+{
+    volatile float v[3], u[3] = { 0.0f, 0.0f, 1.0f };
+    volatile float two = 2.0f, one = 1.0f, half = 0.5f;
+    for (int c = 0; c < 3; ++c) {
+        volatile float m = box[c] * two;
+        v[c] = m - one;
+    }
+    volatile float xx = v[0] * v[0], yy = v[1] * v[1], zz = v[2] * v[2];
+    volatile float xy = xx + yy;
+    volatile float q = xy + zz;
+    volatile float l = std::sqrt((float)q);
+    if (l > 0.0f && l < std::numeric_limits<float>::infinity())  // false for NaN
+        for (int c = 0; c < 3; ++c) u[c] = v[c] / l;
+    for (int c = 0; c < 3; ++c) {
+        volatile float m = u[c] * half;
+        out[c] = m + half;
+    }
+}
+
 namespace {
 // The distinct resident planes of an image: slot s reads src[s]; slot_of[ch] = the slot of channel ch, -1 for a constant
 struct MipSlots {
     const kc_plane *src[4];
     int n = 0;
     int slot_of[4] = { -1, -1, -1, -1 };
+    void add(int ch, const kc_plane *p)
+    {
+        if (p->kind == kc_plane::CONST) return;
+        int s = 0;
+        while (s < n && !(src[s] == p || (src[s]->dptr == p->dptr && src[s]->pitch == p->pitch))) ++s;
+        if (s == n) src[n++] = p;
+        slot_of[ch] = s;
+    }
 };
 
 struct MipChain {
@@ -68,60 +102,11 @@ struct MipChain {
 };
 }  // namespace
 
-int image_build_mips(kc_image *img, uint32_t flags, kc_image **levels, uint32_t cap, uint32_t *count)
+// The plain rule's launches for the resident planes of sl: level k of slot s is slot_planes[(k - 1) * 4 + s]
+static int mip_launch_plain(Context &c, const MipSlots &sl, const std::vector<kc_plane *> &slot_planes, uint32_t w, uint32_t h, uint32_t L,
+                            bool per_level)
 {
-    if (flags & ~(uint32_t)KC_MIP_PER_LEVEL) {
-        set_error("kc_image_build_mips: flags other than KC_MIP_PER_LEVEL");
-        return KC_ERR_UNSUPPORTED;
-    }
-    if (!img || !levels || !count) return mip_refuse("kc_image_build_mips", "NULL image, level array or count");
-    KC_TRY(need_init());
-    Context &c = ctx();
-    std::lock_guard<std::recursive_mutex> lk(c.mu);
-    const uint32_t w = img->w(), h = img->h(), L = 1u + floor_log2(w > h ? w : h);
-    *count = L;
-    if (cap < L) return mip_refuse("kc_image_build_mips", "cap is below the level count");
-    // the kernels' indices are 32-bit and the pyramid's tile rows a grid dimension
-    if (w > (1u << 30) || ((uint64_t)h + 63) / 64 > 65535ull || (((uint64_t)w + 3) / 4) * h > (1ull << 31))
-        return mip_refuse("kc_image_build_mips", "image too large");
-    KC_TRY(image_force(img));  // pending chains and deferred resizes run first
-    const int n = img->n;
-    MipSlots sl;
-    for (int ch = 0; ch < n; ++ch) {
-        const kc_plane *p = img->planes[ch];
-        if (p->kind == kc_plane::CONST) continue;
-        int s = 0;
-        while (s < sl.n && !(sl.src[s] == p || (sl.src[s]->dptr == p->dptr && sl.src[s]->pitch == p->pitch))) ++s;
-        if (s == sl.n) sl.src[sl.n++] = p;
-        sl.slot_of[ch] = s;
-    }
-    // the planes of every level: one new resident plane per slot, shared by the channels that alias it, one constant per
-    // constant channel
-    MipChain mc;
-    mc.planes.reserve((size_t)(L - 1) * n);
-    std::vector<kc_plane *> slot_planes((size_t)(L - 1) * 4, nullptr);  // [level - 1][slot], owned through mc.planes
-    float cv[4] = { 0.0f, 0.0f, 0.0f, 0.0f };
-    for (int ch = 0; ch < n; ++ch) cv[ch] = img->planes[ch]->cval;
-    for (uint32_t k = 1; k < L; ++k) {
-        const uint32_t W = level_extent(w, k), H = level_extent(h, k);
-        for (int ch = 0; ch < n; ++ch) {
-            const int s = sl.slot_of[ch];
-            kc_plane *p = nullptr;
-            if (s < 0) {
-                cv[ch] = mip_const_fold(cv[ch]);
-                p = plane_new_const(W, H, cv[ch]);
-            } else if (slot_planes[(size_t)(k - 1) * 4 + s]) {
-                p = slot_planes[(size_t)(k - 1) * 4 + s];
-                plane_retain(p);
-            } else {
-                KC_TRY(plane_new_mem(W, H, &p));
-                slot_planes[(size_t)(k - 1) * 4 + s] = p;
-            }
-            mc.planes.push_back(p);
-        }
-    }
     if (sl.n > 0 && L > 1) {
-        const bool per_level = (flags & KC_MIP_PER_LEVEL) != 0;
         auto plane_at = [&](uint32_t k, int s) -> const kc_plane * { return k == 0 ? sl.src[s] : slot_planes[(size_t)(k - 1) * 4 + s]; };
         uint32_t k = 0;  // the level the next launch reads
         while (k + 1 < L) {
@@ -168,6 +153,143 @@ int image_build_mips(kc_image *img, uint32_t flags, kc_image **levels, uint32_t 
         for (uint32_t j = 1; j < L; ++j) texels += (uint64_t)level_extent(w, j) * level_extent(h, j);
         c.alg_bytes += 4 * texels * sl.n;
     }
+    return KC_OK;
+}
+
+// KC_MIP_NORMALS: the coupled launches for R, G, B (rgb[c]: the channel's plane at level 0, at least one of them resident; sl:
+// its distinct resident planes); level k of channel c is rgb_planes[(k - 1) * 3 + c], resident at every level
+static int mip_launch_normals(Context &c, const kc_plane *const rgb[3], const MipSlots &sl, const std::vector<kc_plane *> &rgb_planes,
+                              uint32_t w, uint32_t h, uint32_t L, bool per_level)
+{
+    if (L < 2) return KC_OK;
+    // level 0: constants, and channels that read an earlier channel's plane; below it every channel has a plane of its own
+    uint32_t const_mask = 0, from = 0;
+    for (int ch = 0; ch < 3; ++ch) {
+        int f = ch;
+        if (sl.slot_of[ch] < 0) const_mask |= 1u << ch;
+        else
+            for (int e = ch - 1; e >= 0; --e)
+                if (sl.slot_of[e] == sl.slot_of[ch]) f = e;
+        from |= (uint32_t)f << (2 * ch);
+    }
+    auto fill = [&](auto &a, uint32_t k) {  // the source side of a launch that reads level k
+        for (int ch = 0; ch < 3; ++ch) {
+            const kc_plane *p = k == 0 ? rgb[ch] : rgb_planes[(size_t)(k - 1) * 3 + ch];
+            const bool is_const = k == 0 && ((const_mask >> ch) & 1u);
+            a.src[ch] = is_const ? nullptr : p->dptr;
+            a.src_pitch[ch] = is_const ? 0u : (uint32_t)(p->pitch / sizeof(float));
+            a.cval[ch] = is_const ? p->cval : 0.0f;
+        }
+        a.const_mask = k == 0 ? const_mask : 0u;
+        a.from = k == 0 ? from : (0u | 1u << 2 | 2u << 4);
+    };
+    uint32_t k = 0;  // the level the next launch reads
+    while (k + 1 < L) {
+        const uint32_t sw = level_extent(w, k), sh = level_extent(h, k);
+        const uint32_t small = sw < sh ? sw : sh;
+        const uint32_t fused = per_level || small < 2 ? 0u : floor_log2(small) < 6u ? floor_log2(small) : 6u;
+        const uint32_t n_src = k == 0 ? (uint32_t)sl.n : 3u;
+        const uint64_t in_bytes = (uint64_t)sw * sh * 4 * n_src;
+        const uint64_t out_bytes = (uint64_t)level_extent(w, k + 1) * level_extent(h, k + 1) * 4 * 3;
+        const bool nt = (cache_policy_mask(in_bytes, out_bytes, n_src) & 0xffu) != 0;
+        if (fused) {
+            NormalPyramidArgs a{};
+            a.w = sw;
+            a.h = sh;
+            a.n = fused;
+            fill(a, k);
+            for (int ch = 0; ch < 3; ++ch)
+                for (uint32_t j = 0; j < fused; ++j) a.dst[ch][j] = rgb_planes[(size_t)(k + j) * 3 + ch]->dptr;
+            for (uint32_t j = 0; j < fused; ++j) a.dst_pitch[j] = (uint32_t)(rgb_planes[(size_t)(k + j) * 3]->pitch / sizeof(float));
+            hipError_t e = launch_normal_pyramid(a, nt, c.stream);
+            if (e != hipSuccess) return hip_fail(e, "launch_normal_pyramid");
+            c.counters["mip_normals_pyramid"]++;
+            k += fused;
+        } else {
+            NormalLevelArgs a{};
+            a.w = sw;
+            a.h = sh;
+            fill(a, k);
+            for (int ch = 0; ch < 3; ++ch) a.dst[ch] = rgb_planes[(size_t)k * 3 + ch]->dptr;
+            a.dst_pitch = (uint32_t)(rgb_planes[(size_t)k * 3]->pitch / sizeof(float));
+            hipError_t e = launch_normal_level(a, nt, c.stream);
+            if (e != hipSuccess) return hip_fail(e, "launch_normal_level");
+            c.counters["mip_normals_level"]++;
+            k += 1;
+        }
+        if (nt) c.counters["mip_nt"]++;
+        c.launches++;
+    }
+    uint64_t written = 0;  // every distinct resident plane of level 0 read once, three planes of every further level written once
+    for (uint32_t j = 1; j < L; ++j) written += (uint64_t)level_extent(w, j) * level_extent(h, j);
+    c.alg_bytes += 4 * (uint64_t)w * h * sl.n + 12 * written;
+    return KC_OK;
+}
+
+int image_build_mips(kc_image *img, uint32_t flags, kc_image **levels, uint32_t cap, uint32_t *count)
+{
+    if (flags & ~(uint32_t)(KC_MIP_PER_LEVEL | KC_MIP_NORMALS)) {
+        set_error("kc_image_build_mips: flags other than KC_MIP_PER_LEVEL and KC_MIP_NORMALS");
+        return KC_ERR_UNSUPPORTED;
+    }
+    if (!img || !levels || !count) return mip_refuse("kc_image_build_mips", "NULL image, level array or count");
+    KC_TRY(need_init());
+    Context &c = ctx();
+    std::lock_guard<std::recursive_mutex> lk(c.mu);
+    const uint32_t w = img->w(), h = img->h(), L = 1u + floor_log2(w > h ? w : h);
+    *count = L;
+    const bool normals = (flags & KC_MIP_NORMALS) != 0, per_level = (flags & KC_MIP_PER_LEVEL) != 0;
+    if (normals && !img->is_rgba()) return mip_refuse("kc_image_build_mips", "KC_MIP_NORMALS is for RGBA images (X, Y, Z in R, G, B)");
+    if (cap < L) return mip_refuse("kc_image_build_mips", "cap is below the level count");
+    // the kernels' indices are 32-bit and the pyramid's tile rows a grid dimension
+    if (w > (1u << 30) || ((uint64_t)h + 63) / 64 > 65535ull || (((uint64_t)w + 3) / 4) * h > (1ull << 31))
+        return mip_refuse("kc_image_build_mips", "image too large");
+    KC_TRY(image_force(img));  // pending chains and deferred resizes run first
+    const int n = img->n;
+    // sl: the planes the plain rule reduces (under KC_MIP_NORMALS: alpha alone); rgb: R, G, B under KC_MIP_NORMALS
+    MipSlots sl, rgb;
+    for (int ch = normals ? 3 : 0; ch < n; ++ch) sl.add(ch, img->planes[ch]);
+    if (normals)
+        for (int ch = 0; ch < 3; ++ch) rgb.add(ch, img->planes[ch]);
+    // the planes of every level: one new resident plane per slot, shared by the channels that alias it, one constant per
+    // constant channel; under KC_MIP_NORMALS three constants for R, G, B when all three are, three new resident planes otherwise
+    MipChain mc;
+    mc.planes.reserve((size_t)(L - 1) * n);
+    std::vector<kc_plane *> slot_planes((size_t)(L - 1) * 4, nullptr);  // [level - 1][slot], owned through mc.planes
+    std::vector<kc_plane *> rgb_planes(normals && rgb.n > 0 ? (size_t)(L - 1) * 3 : 0, nullptr);  // [level - 1][channel], likewise
+    float cv[4] = { 0.0f, 0.0f, 0.0f, 0.0f };
+    for (int ch = 0; ch < n; ++ch) cv[ch] = img->planes[ch]->cval;
+    for (uint32_t k = 1; k < L; ++k) {
+        const uint32_t W = level_extent(w, k), H = level_extent(h, k);
+        if (normals && rgb.n == 0) {  // the fold: the box of each constant, then the texel's rule
+            const float box[3] = { mip_const_fold(cv[0]), mip_const_fold(cv[1]), mip_const_fold(cv[2]) };
+            mip_normal_texel(box, cv);
+        }
+        for (int ch = 0; ch < n; ++ch) {
+            const int s = sl.slot_of[ch];
+            kc_plane *p = nullptr;
+            if (normals && ch < 3) {
+                if (rgb.n == 0) {
+                    p = plane_new_const(W, H, cv[ch]);
+                } else {
+                    KC_TRY(plane_new_mem(W, H, &p));
+                    rgb_planes[(size_t)(k - 1) * 3 + ch] = p;
+                }
+            } else if (s < 0) {
+                cv[ch] = mip_const_fold(cv[ch]);
+                p = plane_new_const(W, H, cv[ch]);
+            } else if (slot_planes[(size_t)(k - 1) * 4 + s]) {
+                p = slot_planes[(size_t)(k - 1) * 4 + s];
+                plane_retain(p);
+            } else {
+                KC_TRY(plane_new_mem(W, H, &p));
+                slot_planes[(size_t)(k - 1) * 4 + s] = p;
+            }
+            mc.planes.push_back(p);
+        }
+    }
+    if (normals && rgb.n > 0) KC_TRY(mip_launch_normals(c, img->planes, rgb, rgb_planes, w, h, L, per_level));
+    KC_TRY(mip_launch_plain(c, sl, slot_planes, w, h, L, per_level));
     image_retain(img);
     levels[0] = img;
     for (uint32_t k = 1; k < L; ++k) levels[k] = image_new(n, mc.planes.data() + (size_t)(k - 1) * n);  // retains; mc drops its own
@@ -175,7 +297,18 @@ int image_build_mips(kc_image *img, uint32_t flags, kc_image **levels, uint32_t 
 }
 
 // ---------------------------------------------------------------- the BC chain
-// flags of the chain exporters: KC_BC_SRGB under kc_image_to_bc's rule (bc_check_flags), plus KC_MIP_PER_LEVEL
+// flags of the chain exporters: KC_BC_SRGB under kc_image_to_bc's rule (bc_check_flags), plus KC_MIP_PER_LEVEL and KC_MIP_NORMALS,
+// which does not go with KC_BC_SRGB: a vector is not a colour
+static int bc_mips_check_flags(int format, uint32_t flags, const char *who)
+{
+    KC_TRY(bc_check_flags(format, flags, KC_BC_SRGB | KC_MIP_PER_LEVEL | KC_MIP_NORMALS, who));
+    if ((flags & KC_MIP_NORMALS) && (flags & KC_BC_SRGB)) {
+        set_error(std::string(who) + ": KC_MIP_NORMALS with KC_BC_SRGB");
+        return KC_ERR_UNSUPPORTED;
+    }
+    return KC_OK;
+}
+
 int bc_mip_layout(uint32_t w, uint32_t h, int format, uint32_t *levels, size_t *offsets, uint32_t cap, size_t *total_bytes)
 {
     const BcFormat *f = bc_format(format);
@@ -203,7 +336,7 @@ static int bc_mips_encode(kc_image *img, int format, uint32_t flags, char *dst)
     KC_TRY(mip_level_count(img->w(), img->h(), &L));
     std::vector<kc_image *> lv(L, nullptr);
     uint32_t count = 0;
-    KC_TRY(image_build_mips(img, flags & KC_MIP_PER_LEVEL, lv.data(), L, &count));
+    KC_TRY(image_build_mips(img, flags & (KC_MIP_PER_LEVEL | KC_MIP_NORMALS), lv.data(), L, &count));
     const BcFormat &f = *bc_format(format);  // the entry points have refused an unknown format
     size_t at = 0;
     int s = KC_OK;
@@ -219,10 +352,11 @@ static int bc_mips_encode(kc_image *img, int format, uint32_t flags, char *dst)
 
 int image_to_bc_mips(kc_image *img, int format, uint32_t flags, uint8_t *host, size_t host_bytes)
 {
-    KC_TRY(bc_check_flags(format, flags, KC_BC_SRGB | KC_MIP_PER_LEVEL, "kc_image_to_bc_mips"));
+    KC_TRY(bc_mips_check_flags(format, flags, "kc_image_to_bc_mips"));
     if (!bc_format(format)) return mip_refuse("kc_image_to_bc_mips", "unknown format");
     if (!img || !host) return mip_refuse("kc_image_to_bc_mips", "NULL image or host buffer");
     KC_TRY(need_init());
+    if ((flags & KC_MIP_NORMALS) && !img->is_rgba()) return mip_refuse("kc_image_to_bc_mips", "KC_MIP_NORMALS is for RGBA images");
     Context &c = ctx();
     std::lock_guard<std::recursive_mutex> lk(c.mu);
     size_t total = 0;
@@ -239,12 +373,13 @@ int image_to_bc_mips(kc_image *img, int format, uint32_t flags, uint8_t *host, s
 
 int image_to_bc_mips_device(kc_image *img, int format, uint32_t flags, void *device_ptr, size_t bytes, void *hip_stream)
 {
-    KC_TRY(bc_check_flags(format, flags, KC_BC_SRGB | KC_MIP_PER_LEVEL, "kc_image_to_bc_mips_device"));
+    KC_TRY(bc_mips_check_flags(format, flags, "kc_image_to_bc_mips_device"));
     const size_t bb = bc_block_bytes(format);
     if (bb == 0) return mip_refuse("kc_image_to_bc_mips_device", "unknown format");
     if (!img || !device_ptr) return mip_refuse("kc_image_to_bc_mips_device", "NULL image or device pointer");
     if ((uintptr_t)device_ptr % bb) return mip_refuse("kc_image_to_bc_mips_device", "the pointer must be a multiple of the block bytes");
     KC_TRY(need_init());  // an image exists only after kc_init: it is not looked at before
+    if ((flags & KC_MIP_NORMALS) && !img->is_rgba()) return mip_refuse("kc_image_to_bc_mips_device", "KC_MIP_NORMALS is for RGBA images");
     Context &c = ctx();
     std::lock_guard<std::recursive_mutex> lk(c.mu);
     size_t total = 0;
@@ -291,7 +426,7 @@ int dds_header(uint32_t w, uint32_t h, int format, uint32_t flags, uint32_t leve
 
 int image_write_dds(kc_image *img, const char *path, int format, uint32_t flags, int with_mips)
 {
-    KC_TRY(bc_check_flags(format, flags, KC_BC_SRGB | KC_MIP_PER_LEVEL, "kc_image_write_dds"));
+    KC_TRY(bc_mips_check_flags(format, flags, "kc_image_write_dds"));
     if (!bc_format(format)) return mip_refuse("kc_image_write_dds", "unknown format");
     if (!img || !path) return mip_refuse("kc_image_write_dds", "NULL image or path");
     KC_TRY(need_init());
