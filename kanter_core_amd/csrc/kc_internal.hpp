@@ -374,7 +374,9 @@ hipError_t launch_bc_modes_compare(int fmt, int srgb, const Operand op[4], int g
                                    uint32_t h, uint32_t nt_mask, uint32_t groups, unsigned long long *partials, unsigned long long *result,
                                    hipStream_t s);
 // -- mip.hip --
-// Mip chains (mip.hip / mip.cpp): the 2 x 2 box of the header on the n_planes distinct resident planes of one image.
+// Mip chains (mip.hip / mip.cpp): the 2 x 2 box of the header on the n_planes distinct resident planes of one image.  The device
+// steps of this family, of mip_normals.hip and of preview.hip's reduction are one copy, mip_steps.h, with the launch checks of
+// the four launch functions below.
 // mip_pyramid_kernel<nt>: levels 1..n (1 <= n <= 6, both of w >> n and h >> n still >= 1) of the w x h source planes, one
 // workgroup per 64 x 64 tile; dst[p][k - 1] is level k of plane p, dst_pitch[k - 1] floats between its rows.
 struct MipPyramidArgs {
@@ -396,8 +398,8 @@ struct MipLevelArgs {
 };
 hipError_t launch_mip_level(const MipLevelArgs &a, uint32_t n_planes, bool nt, hipStream_t s);
 // -- mip_normals.hip --
-// Normal-map chains (KC_MIP_NORMALS): the same two walks with R, G, B coupled in one thread -- the box of each channel, then the
-// header's renormalisation of the three, at every level.  Channel c is a resident plane (src[c], src_pitch[c]), the constant
+// Normal-map chains (KC_MIP_NORMALS): the same two walks (mip_steps.h) with R, G, B coupled in one thread -- the box of each
+// channel, then the header's renormalisation of the three, at every level.  Channel c is a resident plane (src[c], src_pitch[c]), the constant
 // cval[c] (bit c of const_mask; src[c] is not looked at) or the loads of an earlier channel that aliases it (bits 2c, 2c + 1 of
 // `from` = that channel, c itself otherwise).  Every level has three resident planes of its own: dst[c][k - 1] is level k of
 // channel c in normal_pyramid_kernel<nt> (n, the tiles and the pitches as in MipPyramidArgs), dst[c] the one level of
@@ -423,7 +425,8 @@ struct NormalLevelArgs {
 };
 hipError_t launch_normal_level(const NormalLevelArgs &a, bool nt, hipStream_t s);
 // -- preview.hip --
-// Previews (preview.hip / preview.cpp): preview_kernel<srgb, nt> on `workgroups` workgroups, one pass of a batch.  jobs: `count`
+// Previews (preview.hip / preview.cpp): preview_kernel<srgb, nt> on `workgroups` workgroups, one pass of a batch (the tile
+// reduction is mip_steps.h's).  jobs: `count`
 // PreviewJob (preview_walk.h) in device memory; prefix: count + 1 words, prefix[j] = the first workgroup of job j, prefix[count] =
 // workgroups.  srgb: R, G, B (Gray: the value) of the jobs that store RGBA8 go through quant_u8_srgb.
 hipError_t launch_preview(const PreviewJob *jobs, const uint32_t *prefix, uint32_t count, uint32_t workgroups, bool srgb, bool nt, hipStream_t s);

@@ -102,57 +102,71 @@ struct MipChain {
 };
 }  // namespace
 
+// The level walk of a chain of L levels of a w x h image, for both families: launch(k, sw, sh, fused, nt) enqueues the launch
+// that reads level k (sw x sh) and writes `fused` levels with the pyramid kernel -- as many as both extents still halve, six at
+// the most -- or, with fused == 0, one level with the one-level kernel: after an extent has reached 1, and at every level under
+// KC_MIP_PER_LEVEL.  nt is the cache policy of a launch that reads in_planes(k) planes and writes out_planes per level.
+template <class Planes, class Launch>
+static int mip_walk(Context &c, uint32_t w, uint32_t h, uint32_t L, bool per_level, uint32_t out_planes, Planes in_planes, Launch launch)
+{
+    for (uint32_t k = 0; k + 1 < L;) {  // k: the level the next launch reads
+        const uint32_t sw = level_extent(w, k), sh = level_extent(h, k);
+        const uint32_t small = sw < sh ? sw : sh;
+        const uint32_t fused = per_level || small < 2 ? 0u : floor_log2(small) < 6u ? floor_log2(small) : 6u;
+        const uint32_t n_src = in_planes(k);
+        const uint64_t in_bytes = (uint64_t)sw * sh * 4 * n_src;
+        const uint64_t out_bytes = (uint64_t)level_extent(w, k + 1) * level_extent(h, k + 1) * 4 * out_planes;
+        const bool nt = (cache_policy_mask(in_bytes, out_bytes, n_src) & 0xffu) != 0;
+        KC_TRY(launch(k, sw, sh, fused, nt));
+        if (nt) c.counters["mip_nt"]++;
+        c.launches++;
+        k += fused ? fused : 1u;
+    }
+    return KC_OK;
+}
+
 // The plain rule's launches for the resident planes of sl: level k of slot s is slot_planes[(k - 1) * 4 + s]
 static int mip_launch_plain(Context &c, const MipSlots &sl, const std::vector<kc_plane *> &slot_planes, uint32_t w, uint32_t h, uint32_t L,
                             bool per_level)
 {
-    if (sl.n > 0 && L > 1) {
-        auto plane_at = [&](uint32_t k, int s) -> const kc_plane * { return k == 0 ? sl.src[s] : slot_planes[(size_t)(k - 1) * 4 + s]; };
-        uint32_t k = 0;  // the level the next launch reads
-        while (k + 1 < L) {
-            const uint32_t sw = level_extent(w, k), sh = level_extent(h, k);
-            const uint32_t small = sw < sh ? sw : sh;
-            const uint32_t fused = per_level || small < 2 ? 0u : floor_log2(small) < 6u ? floor_log2(small) : 6u;
-            const uint64_t in_bytes = (uint64_t)sw * sh * 4 * sl.n;
-            const uint64_t out_bytes = (uint64_t)level_extent(w, k + 1) * level_extent(h, k + 1) * 4 * sl.n;
-            const bool nt = (cache_policy_mask(in_bytes, out_bytes, (uint32_t)sl.n) & 0xffu) != 0;
-            if (fused) {
-                MipPyramidArgs a{};
-                a.w = sw;
-                a.h = sh;
-                a.n = fused;
-                for (int s = 0; s < sl.n; ++s) {
-                    a.src[s] = plane_at(k, s)->dptr;
-                    a.src_pitch[s] = (uint32_t)(plane_at(k, s)->pitch / sizeof(float));
-                    for (uint32_t j = 0; j < fused; ++j) a.dst[s][j] = plane_at(k + 1 + j, s)->dptr;
-                }
-                for (uint32_t j = 0; j < fused; ++j) a.dst_pitch[j] = (uint32_t)(plane_at(k + 1 + j, 0)->pitch / sizeof(float));
-                hipError_t e = launch_mip_pyramid(a, (uint32_t)sl.n, nt, c.stream);
-                if (e != hipSuccess) return hip_fail(e, "launch_mip_pyramid");
-                c.counters["mip_pyramid"]++;
-                k += fused;
-            } else {
-                MipLevelArgs a{};
-                a.w = sw;
-                a.h = sh;
-                for (int s = 0; s < sl.n; ++s) {
-                    a.src[s] = plane_at(k, s)->dptr;
-                    a.src_pitch[s] = (uint32_t)(plane_at(k, s)->pitch / sizeof(float));
-                    a.dst[s] = plane_at(k + 1, s)->dptr;
-                }
-                a.dst_pitch = (uint32_t)(plane_at(k + 1, 0)->pitch / sizeof(float));
-                hipError_t e = launch_mip_level(a, (uint32_t)sl.n, nt, c.stream);
-                if (e != hipSuccess) return hip_fail(e, "launch_mip_level");
-                c.counters["mip_level"]++;
-                k += 1;
-            }
-            if (nt) c.counters["mip_nt"]++;
-            c.launches++;
+    if (sl.n == 0 || L < 2) return KC_OK;
+    auto plane_at = [&](uint32_t k, int s) -> const kc_plane * { return k == 0 ? sl.src[s] : slot_planes[(size_t)(k - 1) * 4 + s]; };
+    auto pitch_at = [&](uint32_t k) { return (uint32_t)(plane_at(k, 0)->pitch / sizeof(float)); };
+    auto fill = [&](auto &a, uint32_t k, uint32_t sw, uint32_t sh) {  // the source side of a launch that reads level k
+        a.w = sw;
+        a.h = sh;
+        for (int s = 0; s < sl.n; ++s) {
+            a.src[s] = plane_at(k, s)->dptr;
+            a.src_pitch[s] = (uint32_t)(plane_at(k, s)->pitch / sizeof(float));
         }
-        uint64_t texels = (uint64_t)w * h;  // level 0 read once, every further level written once
-        for (uint32_t j = 1; j < L; ++j) texels += (uint64_t)level_extent(w, j) * level_extent(h, j);
-        c.alg_bytes += 4 * texels * sl.n;
-    }
+    };
+    KC_TRY(mip_walk(c, w, h, L, per_level, (uint32_t)sl.n, [&](uint32_t) { return (uint32_t)sl.n; },
+                    [&](uint32_t k, uint32_t sw, uint32_t sh, uint32_t fused, bool nt) {
+        if (fused) {
+            MipPyramidArgs a{};
+            fill(a, k, sw, sh);
+            a.n = fused;
+            for (uint32_t j = 0; j < fused; ++j) {
+                for (int s = 0; s < sl.n; ++s) a.dst[s][j] = plane_at(k + 1 + j, s)->dptr;
+                a.dst_pitch[j] = pitch_at(k + 1 + j);
+            }
+            hipError_t e = launch_mip_pyramid(a, (uint32_t)sl.n, nt, c.stream);
+            if (e != hipSuccess) return hip_fail(e, "launch_mip_pyramid");
+            c.counters["mip_pyramid"]++;
+        } else {
+            MipLevelArgs a{};
+            fill(a, k, sw, sh);
+            for (int s = 0; s < sl.n; ++s) a.dst[s] = plane_at(k + 1, s)->dptr;
+            a.dst_pitch = pitch_at(k + 1);
+            hipError_t e = launch_mip_level(a, (uint32_t)sl.n, nt, c.stream);
+            if (e != hipSuccess) return hip_fail(e, "launch_mip_level");
+            c.counters["mip_level"]++;
+        }
+        return (int)KC_OK;
+    }));
+    uint64_t texels = (uint64_t)w * h;  // level 0 read once, every further level written once
+    for (uint32_t j = 1; j < L; ++j) texels += (uint64_t)level_extent(w, j) * level_extent(h, j);
+    c.alg_bytes += 4 * texels * sl.n;
     return KC_OK;
 }
 
@@ -172,7 +186,9 @@ static int mip_launch_normals(Context &c, const kc_plane *const rgb[3], const Mi
                 if (sl.slot_of[e] == sl.slot_of[ch]) f = e;
         from |= (uint32_t)f << (2 * ch);
     }
-    auto fill = [&](auto &a, uint32_t k) {  // the source side of a launch that reads level k
+    auto fill = [&](auto &a, uint32_t k, uint32_t sw, uint32_t sh) {  // the source side of a launch that reads level k
+        a.w = sw;
+        a.h = sh;
         for (int ch = 0; ch < 3; ++ch) {
             const kc_plane *p = k == 0 ? rgb[ch] : rgb_planes[(size_t)(k - 1) * 3 + ch];
             const bool is_const = k == 0 && ((const_mask >> ch) & 1u);
@@ -183,43 +199,30 @@ static int mip_launch_normals(Context &c, const kc_plane *const rgb[3], const Mi
         a.const_mask = k == 0 ? const_mask : 0u;
         a.from = k == 0 ? from : (0u | 1u << 2 | 2u << 4);
     };
-    uint32_t k = 0;  // the level the next launch reads
-    while (k + 1 < L) {
-        const uint32_t sw = level_extent(w, k), sh = level_extent(h, k);
-        const uint32_t small = sw < sh ? sw : sh;
-        const uint32_t fused = per_level || small < 2 ? 0u : floor_log2(small) < 6u ? floor_log2(small) : 6u;
-        const uint32_t n_src = k == 0 ? (uint32_t)sl.n : 3u;
-        const uint64_t in_bytes = (uint64_t)sw * sh * 4 * n_src;
-        const uint64_t out_bytes = (uint64_t)level_extent(w, k + 1) * level_extent(h, k + 1) * 4 * 3;
-        const bool nt = (cache_policy_mask(in_bytes, out_bytes, n_src) & 0xffu) != 0;
+    KC_TRY(mip_walk(c, w, h, L, per_level, 3u, [&](uint32_t k) { return k == 0 ? (uint32_t)sl.n : 3u; },
+                    [&](uint32_t k, uint32_t sw, uint32_t sh, uint32_t fused, bool nt) {
         if (fused) {
             NormalPyramidArgs a{};
-            a.w = sw;
-            a.h = sh;
+            fill(a, k, sw, sh);
             a.n = fused;
-            fill(a, k);
-            for (int ch = 0; ch < 3; ++ch)
-                for (uint32_t j = 0; j < fused; ++j) a.dst[ch][j] = rgb_planes[(size_t)(k + j) * 3 + ch]->dptr;
-            for (uint32_t j = 0; j < fused; ++j) a.dst_pitch[j] = (uint32_t)(rgb_planes[(size_t)(k + j) * 3]->pitch / sizeof(float));
+            for (uint32_t j = 0; j < fused; ++j) {
+                for (int ch = 0; ch < 3; ++ch) a.dst[ch][j] = rgb_planes[(size_t)(k + j) * 3 + ch]->dptr;
+                a.dst_pitch[j] = (uint32_t)(rgb_planes[(size_t)(k + j) * 3]->pitch / sizeof(float));
+            }
             hipError_t e = launch_normal_pyramid(a, nt, c.stream);
             if (e != hipSuccess) return hip_fail(e, "launch_normal_pyramid");
             c.counters["mip_normals_pyramid"]++;
-            k += fused;
         } else {
             NormalLevelArgs a{};
-            a.w = sw;
-            a.h = sh;
-            fill(a, k);
+            fill(a, k, sw, sh);
             for (int ch = 0; ch < 3; ++ch) a.dst[ch] = rgb_planes[(size_t)k * 3 + ch]->dptr;
             a.dst_pitch = (uint32_t)(rgb_planes[(size_t)k * 3]->pitch / sizeof(float));
             hipError_t e = launch_normal_level(a, nt, c.stream);
             if (e != hipSuccess) return hip_fail(e, "launch_normal_level");
             c.counters["mip_normals_level"]++;
-            k += 1;
         }
-        if (nt) c.counters["mip_nt"]++;
-        c.launches++;
-    }
+        return (int)KC_OK;
+    }));
     uint64_t written = 0;  // every distinct resident plane of level 0 read once, three planes of every further level written once
     for (uint32_t j = 1; j < L; ++j) written += (uint64_t)level_extent(w, j) * level_extent(h, j);
     c.alg_bytes += 4 * (uint64_t)w * h * sl.n + 12 * written;

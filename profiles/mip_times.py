@@ -12,7 +12,9 @@ printed beside it.  Also: (a) == (b) byte for byte at 4096^2 and 8192 x 2048, an
 
     python profiles/mip_times.py [rounds] [calls]          (on the GPU box)        -> profiles/mip_times.txt
     python profiles/mip_times.py [rounds] [calls] normals  the normal-map case alone
-    KC_LIB_PATH=profiles/ab_libs/mip_lds.so python profiles/mip_times.py ...       (tools/build_variant.sh mip_lds -DKC_MIP_LDS_TILE)
+    KC_LIB_PATH=profiles/ab_libs/NAME.so python profiles/mip_times.py ...       another build of the library, for A/B runs (section 2
+                                                                                 of mip_times.txt: a build variant of mip.hip that is
+                                                                                 no longer kept)
 """
 import os
 import statistics

@@ -137,7 +137,8 @@ static uint32_t as_bits(float f)
     return u;
 }
 
-// preview.hip's reduction by lane (pv_reduce and the steps behind its barrier), all 256 threads of a workgroup in lockstep: raw[t] =
+// preview.hip's reduction by lane (mip_steps.h's mip_tile_reduce and mip_tile_tail, written out here a second time on purpose: the
+// host's oracle does not share the device's header), all 256 threads of a workgroup in lockstep: raw[t] =
 // the 4 x 4 texels thread t loaded; out[t][e] = the level-n values thread t holds afterwards, where pw_out_texel says it holds
 // one.  A wave is 64 consecutive threads; an exchange with mask m reads lane ^ m of the same wave.
 static void lanes_reduce(const float (*raw)[4][4], uint32_t n, float (*out)[4])
