@@ -136,6 +136,11 @@ impl SlotImage {
     pub fn to_normal_bc_mips(&self, format: i32) -> Result<(Vec<u8>, Vec<usize>)> {
         self.bc_mips_with(format, KC_MIP_NORMALS)
     }
+    /// to_bc_mips of an alpha-tested cutout (KC_MIP_COVERAGE_REF; KC_BC3 and KC_BC7 carry alpha): every level's alpha is rescaled
+    /// on the device so that the share of texels a renderer's test against the byte `reference` (1..=255) keeps stays level 0's.
+    pub fn to_cutout_bc_mips(&self, format: i32, srgb: bool, reference: u8) -> Result<(Vec<u8>, Vec<usize>)> {
+        self.bc_mips_with(format, kc_mip_coverage_ref(reference) | if srgb { KC_BC_SRGB } else { 0 })
+    }
     fn bc_mips_with(&self, format: i32, flags: u32) -> Result<(Vec<u8>, Vec<usize>)> {
         let s = self.size()?;
         let (mut levels, mut total) = (0u32, 0usize);

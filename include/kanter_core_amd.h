@@ -208,7 +208,8 @@ KC_API int kc_stats_algorithmic_bytes(uint64_t *bytes);
  * "specialized_nt_<3 hex digits>" (a kernel compiled at run time and its cache-policy bits: 0x001 << k input plane k < 8,
  * 0x100 the result), "specialized_nt_<3 hex digits>_q2" / "_q4" when that kernel handles 2 / 4 float4 per lane instead of one
  * (kc_set_chain_quads).  The mip kernels (one per launch): "mip_pyramid", "mip_level", under KC_MIP_NORMALS "mip_normals_pyramid",
- * "mip_normals_level" for R, G, B, and "mip_nt" for each of those launches that reads its source nontemporally.  The streaming kernels, by the form each launch took: HeightToNormal "h2n_launches", one
+ * "mip_normals_level" for R, G, B, "mip_nt" for each of those launches that reads its source nontemporally, and "mip_coverage" for
+ * the launches KC_MIP_COVERAGE adds.  The streaming kernels, by the form each launch took: HeightToNormal "h2n_launches", one
  * of "h2n_plain", "h2n_tiled_q5", "h2n_tiled_q6", "h2n_tiled_q7" (a row per 256 threads, or tiles of 32, 64, 128 column
  * quads), "h2n_band" (a row band with its halo row), "h2n_nt" (nontemporal stores); the u8 boundary "to_u8_nt", "from_u8_nt"
  * (kc_image_to_u8 / _from_u8 and the u8 pipe); device images "image_import_vec" or "image_import_scalar" and
@@ -554,6 +555,48 @@ KC_API int kc_image_to_bc_device(kc_image *img, const kc_bc_image *dst, uint32_t
  *             With KC_BC_SRGB it is KC_ERR_UNSUPPORTED (a vector is not a colour), refused with the other flag errors; a Gray
  *             image is KC_ERR_INVALID_ARG, after KC_ERR_NO_DEVICE, with nothing launched or allocated (`*count` is written).
  *             kc_dds_header refuses the flag: the header does not depend on it.  Previews stay defined by the plain rule.
+ *   Alpha-tested textures (KC_MIP_COVERAGE).  Foliage, fences and hair cards are cutouts: a renderer discards a texel whose
+ *             alpha byte is below a reference B.  The box pulls alpha towards the middle, so thin features fall under B and the
+ *             object thins out with distance.  With the flag every level's alpha is rescaled so that the share of texels that
+ *             pass the test stays what it was at level 0 (tests/mip_coverage_ref.py is the same rule in numpy).  Everything is
+ *             f32 or integer and bit-exact.  B, 1..255, travels in bits 24-31 of the flags word: KC_MIP_COVERAGE_REF(B).
+ *               Covered.  A texel with alpha a is covered when quant_u8(a) >= B, kc_image_to_u8's linear quantiser (clamp,
+ *                         * 255.0f, truncate, NaN -> 255); equivalently clamp01(a) >= r_B, r_B = (float)B / 255.0f (one IEEE
+ *                         divide; kc_alpha_ref_threshold): the smallest f32 that quantises to at least B.
+ *               Key.      key(a) = a clamped to [0, 1], NaN -> 1.0f, -0.0 and anything not greater than 0 -> +0.0f.
+ *               Level k >= 1.  N_k its texels, p_k the plain rule's alpha (always made from the unscaled p_{k-1}: the scaling never
+ *                         compounds), C_0 the covered texels of level 0, P_k those of p_k;
+ *                         T_k = 0 if C_0 == 0, else min(N_k, max(1, (C_0 * N_k + N_0 / 2) / N_0)) in integers
+ *                         (kc_mip_coverage_target).  If T_k == 0 or P_k == T_k the level keeps the plain alpha bit for bit
+ *                         (s_k = 1.0f): a fully opaque or fully empty texture never changes.  Otherwise v_k = the T_k-th largest
+ *                         key of the level, ve = max(v_k, 0x1p-16f) (alpha below one step of a 16-bit export counts as empty, which
+ *                         keeps s finite), s_k = r_B / ve (IEEE divide), and while quant_u8(ve * s_k) < B, s_k is the next f32
+ *                         above it (kc_mip_coverage_scale; the loop is the definition).  The stored alpha is d = p * s_k: one f32
+ *                         multiplication, nothing clamped; NaN stays NaN, zeros stay zeros, infinities follow IEEE.
+ *                         Whenever s_k != 1 and v_k >= 2^-16 the covered texels C_k of the stored level satisfy
+ *                         T_k <= C_k <= #{key(p_k) >= v_k * (1 - 2^-20)}: ties, plus the texels within a few ulps below v_k.
+ *             Planes: the flag is for RGBA images; a Gray image is KC_ERR_INVALID_ARG exactly where KC_MIP_NORMALS refuses it.  R,
+ *             G, B follow the plain rule, or the normals rule with KC_MIP_NORMALS (the two combine); KC_MIP_PER_LEVEL gives the
+ *             same bits.  A constant alpha is left as the plain rule leaves it and launches nothing.  A resident alpha gets a new
+ *             plane of its own at every level >= 1, also where it aliases R, G or B at level 0: the shared plain plane is never
+ *             scaled.  Level 0 is the image itself.  Images of more than 2^31 texels are KC_ERR_INVALID_ARG ("image too large").
+ *             Bits 24-31 without KC_MIP_COVERAGE, or KC_MIP_COVERAGE with B == 0, are KC_ERR_UNSUPPORTED, refused with the other
+ *             flag errors.  Accepted by the entry points that accept KC_MIP_NORMALS; kc_dds_header refuses it; previews stay
+ *             defined by the plain rule.  On the device the T_k-th largest key is an exact radix select over integer counts (three
+ *             passes of 10 key bits over all levels at once), so no bit depends on the launch shape.  kc_stats: seven launches
+ *             on top of the plain chain's whatever the level count (three counts, three picks, one scale, behind one
+ *             hipMemsetAsync that zeroes the scratch; none for a 1 x 1 image or a constant alpha; counter "mip_coverage" counts
+ *             them), and 4 N_0 + 20 sum_{k >= 1} N_k algorithmic bytes:
+ *             level 0's alpha read once, every further level once per pass and once for the scale, and written once.  The
+ *             scratch comes from the pool and goes back to it; the call still does not wait.
+ *   kc_alpha_ref_threshold, kc_mip_coverage_target, kc_mip_coverage_scale  r_B, T_k (level 0: C_0) and s_k of the rule above:
+ *                        arithmetic, no kc_init needed.  A NULL output, ref_u8 outside 1..255, a zero size, more than 2^31 texels,
+ *                        covered0 > N_0 or level >= L is KC_ERR_INVALID_ARG.
+ *   kc_image_mip_coverage_info  one record per level of what kc_image_build_mips with the same flags does to alpha (flags must
+ *                        hold KC_MIP_COVERAGE_REF(B); RGBA only): texels N_k, target T_k, plain_covered P_k, v = v_k and scale =
+ *                        s_k (v = 0 where nothing was selected; level 0: C_0 in both counts, scale 1).  `*count` = L; cap < L is
+ *                        KC_ERR_INVALID_ARG.  Runs alpha's plain chain and the select (not the scale) and blocks until the records
+ *                        are back; a constant alpha is answered on the host.
  *   kc_mip_normal_texel  the rule above from the three boxes to the stored texel, out = d(box): the function the constant fold
  *                        calls.  Arithmetic, no kc_init needed.  A NULL argument is KC_ERR_INVALID_ARG.
  *   kc_mip_level_count  L for a size; arithmetic, no kc_init needed.
@@ -563,7 +606,8 @@ KC_API int kc_image_to_bc_device(kc_image *img, const kc_bc_image *dst, uint32_t
  *   kc_image_build_mips  levels[0] = img itself (+1 reference), levels[k] a new image of the same kind (+1 reference each);
  *                        `*count` = L whenever the image is known; cap < L is KC_ERR_INVALID_ARG with nothing launched and nothing
  *                        allocated.  Enqueued on the library's stream; the call does not wait.  A failure part-way releases what
- *                        it made.  KC_MIP_PER_LEVEL: one launch per level (A/B runs and tests; the same bits).  KC_MIP_NORMALS: above.
+ *                        it made.  KC_MIP_PER_LEVEL: one launch per level (A/B runs and tests; the same bits).  KC_MIP_NORMALS,
+ *                        KC_MIP_COVERAGE: above.
  *                        kc_stats: one launch per up to six levels while both extents still halve, one per level after that
  *                        (4096 x 4096: two; counters "mip_pyramid", "mip_level"); 4 w h algorithmic bytes per distinct resident
  *                        plane read plus 4 sum_{k >= 1} W_k H_k per plane written; constant planes launch nothing.
@@ -573,7 +617,7 @@ KC_API int kc_image_to_bc_device(kc_image *img, const kc_bc_image *dst, uint32_t
  *                        NULL; otherwise cap < L is KC_ERR_INVALID_ARG), `*total_bytes` = the chain's bytes.  Arithmetic, no kc_init.
  *   kc_image_to_bc_mips  kc_image_build_mips, then the encoder of kc_image_to_bc once per level, into host memory (`host_bytes`
  *                        at least the total); blocks until the bytes are there.  flags: KC_BC_SRGB (BC1 / BC3 / BC7) | KC_MIP_PER_LEVEL |
- *                        KC_MIP_NORMALS.
+ *                        KC_MIP_NORMALS | KC_MIP_COVERAGE_REF(B).
  *                        KC_BC6H quantises every level's own f32 values, so the chain keeps the range of the planes.
  *   kc_image_to_bc_mips_device  the same into device memory (a multiple of the block bytes; `bytes` at least the total, the
  *                        total's extent in one allocation of the library's device), ordered against `hip_stream` by the two event
@@ -586,13 +630,20 @@ KC_API int kc_image_to_bc_device(kc_image *img, const kc_bc_image *dst, uint32_t
  *                        BC5 83, BC6H 95, BC7 98, with KC_BC_SRGB BC1 72, BC3 78, BC7 99.  1 <= levels <= L.  `*bytes` (optional) = 148.
  *                        No kc_init.
  *   kc_image_write_dds   the header, then the chain (with_mips != 0) or level 0 alone.
- * Errors, in this order: unknown flag bits, KC_BC_SRGB with BC4 / BC5 / BC6H, or KC_MIP_NORMALS with KC_BC_SRGB, KC_ERR_UNSUPPORTED; a NULL argument, a zero size, an
+ * Errors, in this order: unknown flag bits, KC_BC_SRGB with BC4 / BC5 / BC6H, KC_MIP_NORMALS with KC_BC_SRGB, or a reference byte
+ * without KC_MIP_COVERAGE or the reverse, KC_ERR_UNSUPPORTED; a NULL argument, a zero size, an
  * unknown format, a size below the total KC_ERR_INVALID_ARG; KC_ERR_NO_DEVICE before kc_init; KC_ERR_NO_SLOT_DATA where
  * kc_live_graph_buffer_bc returns it; KC_ERR_IO for a file that cannot be written. */
 #define KC_MIP_PER_LEVEL 2u  /* one launch of the one-level kernel per level instead of the fused pyramid kernel; a bit of its
                                 own beside KC_BC_SRGB, since the chain exporters take both in one flags word */
 #define KC_MIP_NORMALS 32u   /* R, G, B are a normal map: every level is renormalised before the next is made (above); 4 and 8
                                 stay refused by the chain entry points, 16 is KC_BC_ALL_MODES */
+#define KC_MIP_COVERAGE 64u  /* alpha is tested against the byte in bits 24-31: every level keeps level 0's coverage (above) */
+#define KC_MIP_COVERAGE_REF(b) (64u | ((uint32_t)(b) << 24))  /* KC_MIP_COVERAGE with the reference byte b, 1..255 */
+typedef struct kc_mip_coverage_level {
+    uint64_t texels, target, plain_covered;  /* N_k, T_k, P_k (level 0: C_0 in both counts) */
+    float v, scale;                          /* v_k (0 where nothing was selected) and s_k */
+} kc_mip_coverage_level;
 KC_API int kc_mip_level_count(uint32_t width, uint32_t height, uint32_t *levels);
 KC_API int kc_preview_level(uint32_t width, uint32_t height, uint32_t max_extent, uint32_t *level, uint32_t *level_width,
                             uint32_t *level_height);
@@ -656,6 +707,10 @@ KC_API int kc_live_graph_buffer_previews(kc_live_graph *lg, const uint32_t *node
 KC_API int kc_preview_plan(uint32_t width, uint32_t height, uint32_t level, uint32_t x, uint32_t y, uint32_t rect_w, uint32_t rect_h,
                            kc_preview_plan_info *out);
 KC_API int kc_mip_normal_texel(const float box[3], float out[3]);
+KC_API int kc_alpha_ref_threshold(uint32_t ref_u8, float *r);
+KC_API int kc_mip_coverage_target(uint32_t width, uint32_t height, uint64_t covered0, uint32_t level, uint64_t *target);
+KC_API int kc_mip_coverage_scale(float v, uint32_t ref_u8, float *s);
+KC_API int kc_image_mip_coverage_info(kc_image *img, uint32_t flags, kc_mip_coverage_level *out, uint32_t cap, uint32_t *count);
 KC_API int kc_image_build_mips(kc_image *img, uint32_t flags, kc_image **levels, uint32_t cap, uint32_t *count);
 KC_API int kc_bc_mip_layout(uint32_t width, uint32_t height, int format, uint32_t *levels, size_t *offsets, uint32_t cap,
                             size_t *total_bytes);

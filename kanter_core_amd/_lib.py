@@ -57,6 +57,10 @@ class kc_channel_stats(C.Structure):
                 ("nan_count", C.c_uint64 * 4), ("histogram", (C.c_uint64 * 256) * 4)]
 
 
+class kc_mip_coverage_level(C.Structure):
+    _fields_ = [("texels", C.c_uint64), ("target", C.c_uint64), ("plain_covered", C.c_uint64), ("v", C.c_float), ("scale", C.c_float)]
+
+
 class kc_bc_image(C.Structure):
     _fields_ = [("ptr", c_vp), ("width", C.c_uint32), ("height", C.c_uint32), ("format", C.c_int32), ("row_pitch_bytes", C.c_size_t)]
 
@@ -191,6 +195,10 @@ SIGNATURES = {
     "kc_mip_level_count": (C.c_int, [C.c_uint32, C.c_uint32, C.POINTER(C.c_uint32)]),
     "kc_preview_level": (C.c_int, [C.c_uint32, C.c_uint32, C.c_uint32, c_u32p, c_u32p, c_u32p]),
     "kc_mip_normal_texel": (C.c_int, [c_vp, c_vp]),
+    "kc_alpha_ref_threshold": (C.c_int, [C.c_uint32, C.POINTER(C.c_float)]),
+    "kc_mip_coverage_target": (C.c_int, [C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint32, C.POINTER(C.c_uint64)]),
+    "kc_mip_coverage_scale": (C.c_int, [C.c_float, C.c_uint32, C.POINTER(C.c_float)]),
+    "kc_image_mip_coverage_info": (C.c_int, [c_vp, C.c_uint32, C.POINTER(kc_mip_coverage_level), C.c_uint32, C.POINTER(C.c_uint32)]),
     "kc_image_build_mips": (C.c_int, [c_vp, C.c_uint32, C.POINTER(c_vp), C.c_uint32, C.POINTER(C.c_uint32)]),
     "kc_bc_mip_layout": (C.c_int, [C.c_uint32, C.c_uint32, C.c_int, C.POINTER(C.c_uint32), C.POINTER(C.c_size_t), C.c_uint32,
                                    C.POINTER(C.c_size_t)]),

@@ -702,8 +702,48 @@ MIP_PER_LEVEL = 2  # kc_image_build_mips and the chain exporters: one launch of 
 MIP_NORMALS = 32   # ... R, G, B are a normal map (n * 0.5 + 0.5): every level is renormalised before the next is made
 
 
-def _mip_flags(srgb, per_level, normals):
-    return (BC_SRGB if srgb else 0) | (MIP_PER_LEVEL if per_level else 0) | (MIP_NORMALS if normals else 0)
+MIP_COVERAGE = 64  # ... alpha is tested against the byte in bits 24-31: every level keeps level 0's coverage
+
+
+def mip_coverage_ref(ref):
+    """KC_MIP_COVERAGE_REF(ref): the flag with the reference byte 1..255 a renderer's alpha test compares with."""
+    ref = int(ref)
+    if not 1 <= ref <= 255:
+        raise ValueError("coverage must be a byte 1..255")
+    return MIP_COVERAGE | ref << 24
+
+
+def _mip_flags(srgb, per_level, normals, coverage=None):
+    return ((BC_SRGB if srgb else 0) | (MIP_PER_LEVEL if per_level else 0) | (MIP_NORMALS if normals else 0)
+            | (mip_coverage_ref(coverage) if coverage is not None else 0))
+
+
+MipCoverageLevel = collections.namedtuple("MipCoverageLevel", "texels target plain_covered v scale")
+MipCoverageLevel.__doc__ = """One level of SlotImage.mip_coverage_info (kc_mip_coverage_level): its texels, the covered texels it is
+to keep (level 0: the covered texels of the image), those of the plain chain's alpha, the target-th largest alpha key (np.float32,
+0 where nothing was selected) and the scale of the level's alpha (np.float32, 1 where it keeps the plain alpha)."""
+
+
+def alpha_ref_threshold(ref):
+    """-> np.float32: the smallest alpha that to_u8 writes as at least the byte `ref`, ref / 255 in f32 (kc_alpha_ref_threshold; no device)."""
+    r = C.c_float()
+    _check(_lib.load().kc_alpha_ref_threshold(ref, C.byref(r)))
+    return np.float32(r.value)
+
+
+def mip_coverage_target(width, height, covered0, level):
+    """-> the covered texels level `level` of a width x height chain keeps when `covered0` texels of level 0 are covered
+    (kc_mip_coverage_target; no device)."""
+    t = C.c_uint64()
+    _check(_lib.load().kc_mip_coverage_target(width, height, covered0, level, C.byref(t)))
+    return t.value
+
+
+def mip_coverage_scale(v, ref):
+    """-> np.float32: the scale that takes the alpha `v` to the byte `ref` (kc_mip_coverage_scale; no device)."""
+    s = C.c_float()
+    _check(_lib.load().kc_mip_coverage_scale(C.c_float(float(np.float32(v))), ref, C.byref(s)))
+    return np.float32(s.value)
 
 
 def mip_normal_texel(box):
@@ -827,7 +867,7 @@ def _bc_mip_views(buf, size, fmt):
     return views
 
 
-def _bc_mips_export(call, size, fmt, srgb, per_level, out, normals=False):
+def _bc_mips_export(call, size, fmt, srgb, per_level, out, normals=False, coverage=None):
     """Allocates (or takes) a flat uint8 tensor of at least the chain's bytes and runs `call(fmt, flags, ptr, bytes, stream)`."""
     import torch
     f = _bc_format(fmt)
@@ -836,7 +876,7 @@ def _bc_mips_export(call, size, fmt, srgb, per_level, out, normals=False):
         out = torch.empty((total,), dtype=torch.uint8, device=torch.device("cuda", torch.cuda.current_device()))
     if out.dtype != torch.uint8 or out.dim() != 1 or not out.is_contiguous() or out.numel() < total:
         raise ValueError("out must be a contiguous 1-D uint8 tensor of at least %d bytes" % total)
-    flags = _mip_flags(srgb, per_level, normals)
+    flags = _mip_flags(srgb, per_level, normals, coverage)
     _check(_on_torch_stream(out, lambda stream: call(f, flags, C.c_void_p(out.data_ptr()), out.numel(), stream)))
     return out, offs
 
@@ -1080,36 +1120,56 @@ class SlotImage:
         whose last two dimensions are contiguous) is written instead of a new tensor.  Ready on torch's current stream."""
         return _bc_export(lambda d, f, st: _lib.load().kc_image_to_bc_device(self._h, d, f, st), self.size(), fmt, srgb, out)
 
-    def mips(self, per_level=False, normals=False):
+    def mips(self, per_level=False, normals=False, coverage=None):
         """-> the mip chain as a list of SlotImage (kc_image_build_mips): entry 0 is this image, entry k is max(1, w >> k) by
         max(1, h >> k), the 2 x 2 box of the level above it in f32, down to 1 x 1.  per_level=True runs one launch per level
         instead of the fused kernel (the same bits).  normals=True (RGBA only): R, G, B are a normal map stored as n * 0.5 + 0.5 and
-        every level is renormalised on the device before the next is made (KC_MIP_NORMALS); alpha follows the plain rule."""
+        every level is renormalised on the device before the next is made (KC_MIP_NORMALS); alpha follows the plain rule.
+        coverage=B (RGBA only, a byte 1..255): alpha is a cutout tested against B, and every level's alpha is rescaled so that the
+        share of texels that pass the test stays what it is at level 0 (KC_MIP_COVERAGE)."""
         s = self.size()
         n = mip_level_count(s.width, s.height)
         arr = (C.c_void_p * n)()
         count = C.c_uint32()
-        _check(_lib.load().kc_image_build_mips(self._h, _mip_flags(False, per_level, normals), arr, n, C.byref(count)))
+        _check(_lib.load().kc_image_build_mips(self._h, _mip_flags(False, per_level, normals, coverage), arr, n, C.byref(count)))
         return [SlotImage(arr[k]) for k in range(count.value)]
 
-    def to_bc_mips(self, fmt, srgb=False, per_level=False, normals=False):
+    def mip_coverage_info(self, coverage):
+        """-> one MipCoverageLevel per level: what mips(coverage=coverage) does to alpha (kc_image_mip_coverage_info).  Blocks
+        until the values are there."""
+        s = self.size()
+        n = mip_level_count(s.width, s.height)
+        arr = (_lib.kc_mip_coverage_level * n)()
+        count = C.c_uint32()
+        _check(_lib.load().kc_image_mip_coverage_info(self._h, mip_coverage_ref(coverage), arr, n, C.byref(count)))
+        return [MipCoverageLevel(int(r.texels), int(r.target), int(r.plain_covered), np.float32(r.v), np.float32(r.scale))
+                for r in arr[:count.value]]
+
+    def alpha_coverage(self, ref):
+        """-> the texels whose alpha to_u8 writes as at least the byte `ref`: what a renderer's alpha test keeps (bins >= ref of
+        channel 3 of channel_stats(histogram=True); RGBA only)."""
+        if not self.is_rgba():
+            raise ValueError("alpha_coverage is for RGBA images")
+        return int(self.channel_stats(histogram=True).histogram[3][int(ref):].sum())
+
+    def to_bc_mips(self, fmt, srgb=False, per_level=False, normals=False, coverage=None):
         """-> one uint8 (ceil(H_k/4), ceil(W_k/4), block bytes) array per level, shaped like to_bc's and views of one buffer
         that holds the chain as a texture file stores it (kc_image_to_bc_mips).  normals=True: the chain of a normal map, as mips
-        builds it (BC5 is the usual format; not with srgb)."""
+        builds it (BC5 is the usual format; not with srgb).  coverage=B: the chain mips(coverage=B) builds."""
         f = _bc_format(fmt)
         s = self.size()
         offs, total = bc_mip_layout(s.width, s.height, f)
         buf = np.empty((total,), np.uint8)
-        flags = _mip_flags(srgb, per_level, normals)
+        flags = _mip_flags(srgb, per_level, normals, coverage)
         _check(_lib.load().kc_image_to_bc_mips(self._h, f, flags, buf.ctypes.data, buf.nbytes))
         return _bc_mip_views(buf, s, f)
 
-    def to_bc_mips_torch(self, fmt, srgb=False, out=None, per_level=False, normals=False):
+    def to_bc_mips_torch(self, fmt, srgb=False, out=None, per_level=False, normals=False, coverage=None):
         """-> (flat uint8 tensor in device memory holding the chain, offsets of the levels) (kc_image_to_bc_mips_device); `out`
         (contiguous, 1-D, at least the chain's bytes) is written instead of a new tensor, bytes past the chain are not touched.
         Ready on torch's current stream."""
         return _bc_mips_export(lambda f, fl, p, n, st: _lib.load().kc_image_to_bc_mips_device(self._h, f, fl, p, n, st), self.size(), fmt,
-                               srgb, per_level, out, normals)
+                               srgb, per_level, out, normals, coverage)
 
     def preview(self, max_extent, srgb=False):
         """-> (h, w, 4) uint8: the whole mip level a preview of at most max_extent texels a side is cut from (preview_level), read
@@ -1117,10 +1177,11 @@ class SlotImage:
         s = self.size()
         return previews([(self, preview_level(s.width, s.height, max_extent)[0], None)], srgb)[0]
 
-    def write_dds(self, path, fmt, srgb=False, mips=True, normals=False):
+    def write_dds(self, path, fmt, srgb=False, mips=True, normals=False, coverage=None):
         """Writes a .dds file (DX10 header) with the image's BC blocks: the whole mip chain, or level 0 alone (kc_image_write_dds).
-        normals=True: the chain of a normal map, as to_bc_mips(normals=True) (no effect with mips=False)."""
-        _check(_lib.load().kc_image_write_dds(self._h, os.fspath(path).encode(), _bc_format(fmt), _mip_flags(srgb, False, normals), int(mips)))
+        normals=True: the chain of a normal map, as to_bc_mips(normals=True); coverage=B: the chain of a cutout, as
+        to_bc_mips(coverage=B) (neither has an effect with mips=False)."""
+        _check(_lib.load().kc_image_write_dds(self._h, os.fspath(path).encode(), _bc_format(fmt), _mip_flags(srgb, False, normals, coverage), int(mips)))
 
     def bc_error(self, fmt, srgb=False, blocks=None, all_modes=False):
         """-> BcError: how far the image's BC encoding is from the image, measured on the device (kc_image_bc_error): the bytes
@@ -1496,10 +1557,10 @@ class LiveGraph:
         return _bc_export(lambda d, f, st: _lib.load().kc_live_graph_buffer_bc(self._h, node_id, slot_id, d, f, st),
                           self.slot_data_size(node_id, slot_id), fmt, srgb, out)
 
-    def buffer_bc_mips_torch(self, node_id, slot_id, fmt, srgb=False, out=None, per_level=False, normals=False):
+    def buffer_bc_mips_torch(self, node_id, slot_id, fmt, srgb=False, out=None, per_level=False, normals=False, coverage=None):
         """SlotImage.to_bc_mips_torch of a slot's image (kc_live_graph_buffer_bc_mips)."""
         return _bc_mips_export(lambda f, fl, p, n, st: _lib.load().kc_live_graph_buffer_bc_mips(self._h, node_id, slot_id, f, fl, p, n, st),
-                               self.slot_data_size(node_id, slot_id), fmt, srgb, per_level, out, normals)
+                               self.slot_data_size(node_id, slot_id), fmt, srgb, per_level, out, normals, coverage)
 
     def buffer_previews(self, items, srgb=False):
         """previews of slots' images (kc_live_graph_buffer_previews): items = [(node_id, slot_id, level, rect or None)] -> one

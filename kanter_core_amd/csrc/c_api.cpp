@@ -906,6 +906,35 @@ try {
 }
 KC_CATCH
 
+int kc_alpha_ref_threshold(uint32_t ref_u8, float *r)
+try {
+    KC_ARG(r && ref_u8 >= 1 && ref_u8 <= 255);
+    *r = alpha_ref_threshold(ref_u8);
+    return KC_OK;
+}
+KC_CATCH
+
+int kc_mip_coverage_target(uint32_t width, uint32_t height, uint64_t covered0, uint32_t level, uint64_t *target)
+try {
+    return mip_coverage_target(width, height, covered0, level, target);
+}
+KC_CATCH
+
+int kc_mip_coverage_scale(float v, uint32_t ref_u8, float *s)
+try {
+    KC_ARG(s && ref_u8 >= 1 && ref_u8 <= 255);
+    *s = mip_coverage_scale(v, ref_u8);
+    return KC_OK;
+}
+KC_CATCH
+
+int kc_image_mip_coverage_info(kc_image *img, uint32_t flags, kc_mip_coverage_level *out, uint32_t cap, uint32_t *count)
+try {
+    Lock api_lock(ctx().mu);  // reference counts are plain integers, see kc_plane::refs
+    return image_mip_coverage_info(img, flags, out, cap, count);  // the flags, the arguments, then need_init()
+}
+KC_CATCH
+
 int kc_image_build_mips(kc_image *img, uint32_t flags, kc_image **levels, uint32_t cap, uint32_t *count)
 try {
     Lock api_lock(ctx().mu);  // reference counts are plain integers, see kc_plane::refs
@@ -1637,7 +1666,7 @@ KC_CATCH
 int kc_live_graph_buffer_bc_mips(kc_live_graph *lg, uint32_t node, uint32_t slot, int format, uint32_t flags, void *device_ptr,
                                  size_t bytes, void *hip_stream)
 try {
-    if (flags & ~(uint32_t)(KC_BC_SRGB | KC_MIP_PER_LEVEL | KC_MIP_NORMALS)) {
+    if (flags & ~(uint32_t)(KC_BC_SRGB | KC_MIP_PER_LEVEL | KC_MIP_NORMALS | KC_MIP_COVERAGE | 0xff000000u)) {
         set_error("kc_live_graph_buffer_bc_mips: unknown flag bits");
         return KC_ERR_UNSUPPORTED;
     }
@@ -1645,6 +1674,7 @@ try {
         set_error("kc_live_graph_buffer_bc_mips: KC_MIP_NORMALS with KC_BC_SRGB");
         return KC_ERR_UNSUPPORTED;
     }
+    KC_TRY(mip_check_coverage_flags(flags, "kc_live_graph_buffer_bc_mips"));
     LG_LOCK(lg);
     KC_ARG(device_ptr && bytes > 0);
     KC_TRY(need_init());

@@ -424,6 +424,51 @@ struct NormalLevelArgs {
     uint32_t w, h;
 };
 hipError_t launch_normal_level(const NormalLevelArgs &a, bool nt, hipStream_t s);
+// -- mip_coverage.hip --
+// Alpha-test coverage (KC_MIP_COVERAGE): an exact k-th-largest selection over the alpha plane of every level of a chain -- a
+// radix select on the 30 significant bits of the header's key, 10 bits (KC_COVERAGE_BINS bins) per pass -- and the scale of
+// every level.  Everything the selection computes is an integer count, so no result depends on the launch shape or the order
+// of the atomics.  One table of CoverageJob, one per level; it is small (a chain has at most 32 levels) and travels in the
+// launches' arguments, so that nothing is uploaded and kc_image_build_mips never waits for a staging buffer.  Workgroup first_wg ..
+// first_wg + wgs - 1 of a count or scale launch works on that level (level 0 takes part in the first count launch only).
+constexpr uint32_t KC_COVERAGE_BINS = 1024, KC_COVERAGE_MAX_LEVELS = 32;
+struct CoverageJob {
+    const float *src;  // the plain rule's alpha of the level, p_k
+    float *dst;        // the stored alpha, d_k (levels >= 1 of a chain; nullptr for the query, which does not scale)
+    uint32_t src_pitch, dst_pitch;  // floats
+    uint32_t w, h;
+    uint32_t first_wg, wgs;
+};
+// Per level in device memory, zeroed before the first launch: the public kc_mip_coverage_level, then the state of the select --
+// the key bits found so far, the rank that remains among the texels with that prefix, done != 0 once the scale is known.
+struct CoverageRecord {
+    unsigned long long texels, target, plain_covered;
+    float v, scale;
+    uint32_t prefix, rank, done, unused;
+};
+struct CoverageArgs {
+    CoverageJob jobs[KC_COVERAGE_MAX_LEVELS];
+    CoverageRecord *rec;
+    uint32_t *hist;  // levels x KC_COVERAGE_BINS, zeroed before the first launch; a pick leaves its level's bins zero again
+    uint32_t levels;
+    uint32_t ref;    // B
+    float r_b;       // (float)B / 255.0f
+};
+// workgroups of a level's job: few, every thread of 256 sixteen quads where the level has them and 1024 workgroups at the most --
+// every workgroup of a level ends with atomics on that level's one histogram, and their depth per address is what a count costs
+inline uint32_t coverage_job_wgs(uint32_t w, uint32_t h)
+{
+    const uint64_t quads = (uint64_t)((w + 3) / 4) * h;
+    return (uint32_t)std::min<uint64_t>(std::max<uint64_t>((quads + 4095) / 4096, 1), 1024);
+}
+// coverage_count_kernel, pass 0 .. 2: the histogram of the pass's 10 key bits over the texels whose higher bits equal the
+// level's prefix, for every level >= 1 that is not done; pass 0 also counts the covered texels of every level, level 0
+// included.  coverage_pick_kernel, one workgroup per level, after each count: pass 0 sets the targets and finishes the levels
+// that keep the plain alpha, every pass finds the bin that holds the rank, pass 2 ends with v and the scale.
+// coverage_scale_kernel: d_k = p_k * s_k for every level >= 1, a copy where s_k == 1.
+hipError_t launch_coverage_count(const CoverageArgs &a, uint32_t pass, uint32_t first_wg, uint32_t wgs, hipStream_t s);
+hipError_t launch_coverage_pick(const CoverageArgs &a, uint32_t pass, hipStream_t s);
+hipError_t launch_coverage_scale(const CoverageArgs &a, uint32_t first_wg, uint32_t wgs, hipStream_t s);
 // -- preview.hip --
 // Previews (preview.hip / preview.cpp): preview_kernel<srgb, nt> on `workgroups` workgroups, one pass of a batch (the tile
 // reduction is mip_steps.h's).  jobs: `count`

@@ -451,6 +451,14 @@ int preview_level(uint32_t w, uint32_t h, uint32_t max_extent, uint32_t *level, 
 float mip_const_fold(float c);  // ((c + c) + (c + c)) * 0.25f, as the device computes it
 void mip_normal_texel(const float box[3], float out[3]);  // KC_MIP_NORMALS: the boxes of R, G, B -> the stored texel, as the device computes it
 int image_build_mips(kc_image *img, uint32_t flags, kc_image **levels, uint32_t cap, uint32_t *count);
+// KC_MIP_COVERAGE (mip.cpp): the rule's arithmetic as kc_alpha_ref_threshold, kc_mip_coverage_target and kc_mip_coverage_scale
+// return it, the flag rule of the chain entry points (bit 64 and the reference byte in bits 24-31 go together), and the body of
+// kc_image_mip_coverage_info
+float alpha_ref_threshold(uint32_t ref_u8);
+int mip_coverage_target(uint32_t w, uint32_t h, uint64_t covered0, uint32_t level, uint64_t *target);
+float mip_coverage_scale(float v, uint32_t ref_u8);
+int mip_check_coverage_flags(uint32_t flags, const char *who);
+int image_mip_coverage_info(kc_image *img, uint32_t flags, kc_mip_coverage_level *out, uint32_t cap, uint32_t *count);
 int bc_mip_layout(uint32_t w, uint32_t h, int format, uint32_t *levels, size_t *offsets, uint32_t cap, size_t *total_bytes);
 int image_to_bc_mips(kc_image *img, int format, uint32_t flags, uint8_t *host, size_t host_bytes);
 int image_to_bc_mips_device(kc_image *img, int format, uint32_t flags, void *device_ptr, size_t bytes, void *hip_stream);
@@ -466,6 +474,7 @@ int image_previews_device(const kc_preview_request *r, uint32_t count, uint32_t 
 void preview_release();
 // per-channel statistics (stats.cpp): the body of kc_image_channel_stats; the context's buffers, released at kc_shutdown
 int image_channel_stats(kc_image *img, uint32_t flags, kc_channel_stats *out);
+uint32_t quant_u8_host(float v);  // streaming.h's quant_u8 on the host
 int stats_buffers(size_t partials_bytes);  // the context's StatsBuffers, with room for that many bytes of partial records
 void channel_stats_release();
 int calculate_size(int policy, const kc_size *sizes, int n, int slot_index, kc_size specific, kc_size *out);

@@ -3,7 +3,8 @@
 // folds constant planes with the device's expression, allocates the level planes and enqueues mip.hip's kernels on the library's
 // stream: the pyramid kernel while both extents still halve (up to six levels per launch), the one-level kernel for the rest and
 // for every level under KC_MIP_PER_LEVEL; under KC_MIP_NORMALS mip_normals.hip's two kernels take R, G, B together and
-// renormalise every level.  The BC chain is bc.cpp's encoder launch once per level; the DDS writer is host code.
+// renormalise every level; under KC_MIP_COVERAGE mip_coverage.hip's select and scale give alpha planes of their own.  The BC chain
+// is bc.cpp's encoder launch once per level; the DDS writer is host code.
 #include <cmath>
 #include <cstdio>
 #include <limits>
@@ -77,6 +78,59 @@ void mip_normal_texel(const float box[3], float out[3])
     }
 }
 
+// ---------------------------------------------------------------- KC_MIP_COVERAGE: the rule's arithmetic
+static constexpr uint32_t kCoverageFlagBits = KC_MIP_COVERAGE | 0xff000000u;
+
+int mip_check_coverage_flags(uint32_t flags, const char *who)
+{
+    const uint32_t ref = flags >> 24;
+    if ((flags & KC_MIP_COVERAGE) ? ref == 0 : ref != 0) {
+        set_error(std::string(who) + ": KC_MIP_COVERAGE goes with a reference byte 1..255 in bits 24-31 (KC_MIP_COVERAGE_REF)");
+        return KC_ERR_UNSUPPORTED;
+    }
+    return KC_OK;
+}
+
+// r_B = (float)B / 255.0f, one IEEE divide: the smallest f32 that quant_u8 takes to at least B
+float alpha_ref_threshold(uint32_t ref_u8)
+{
+    volatile float b = (float)ref_u8, d = 255.0f;
+    volatile float r = b / d;
+    return r;
+}
+
+// T_k of n_k texels for c_0 covered of n_0 (n_0 <= 2^31: the product fits 64 bits)
+static uint64_t coverage_target(uint64_t n_0, uint64_t n_k, uint64_t c_0)
+{
+    if (c_0 == 0) return 0;
+    const uint64_t t = (c_0 * n_k + n_0 / 2) / n_0;
+    return std::min(n_k, std::max<uint64_t>(t, 1));
+}
+
+int mip_coverage_target(uint32_t w, uint32_t h, uint64_t covered0, uint32_t level, uint64_t *target)
+{
+    const char *who = "kc_mip_coverage_target";
+    if (!target || w == 0 || h == 0) return mip_refuse(who, "NULL output or zero extent");
+    const uint64_t n_0 = (uint64_t)w * h;
+    if (n_0 > (1ull << 31)) return mip_refuse(who, "image too large");
+    if (covered0 > n_0 || level >= 1u + floor_log2(w > h ? w : h)) return mip_refuse(who, "covered0 above the texels, or level at or above the level count");
+    *target = level == 0 ? covered0 : coverage_target(n_0, (uint64_t)level_extent(w, level) * level_extent(h, level), covered0);
+    return KC_OK;
+}
+
+// s_k from v_k: the device's expression (mip_coverage.hip, coverage_scale), every operation through a volatile temporary like
+// mip_const_fold.  ve >= 2^-16 keeps r_B / ve finite; the loop ends because ve * s grows with s.
+float mip_coverage_scale(float v, uint32_t ref_u8)
+{
+    volatile float ve = v > 0x1p-16f ? v : 0x1p-16f;  // NaN takes the floor too
+    volatile float s = alpha_ref_threshold(ref_u8) / ve;
+    for (;;) {
+        volatile float m = ve * s;
+        if (quant_u8_host(m) >= ref_u8) return s;
+        s = std::nextafter((float)s, std::numeric_limits<float>::infinity());
+    }
+}
+
 namespace {
 // The distinct resident planes of an image: slot s reads src[s]; slot_of[ch] = the slot of channel ch, -1 for a constant
 struct MipSlots {
@@ -95,9 +149,11 @@ struct MipSlots {
 
 struct MipChain {
     std::vector<kc_plane *> planes;  // [level - 1][channel], one reference each held here until the images exist
+    std::vector<kc_plane *> scratch;  // planes no level image keeps (KC_MIP_COVERAGE: a plain alpha nothing else aliases)
     ~MipChain()
     {
         for (kc_plane *p : planes) plane_release(p);
+        for (kc_plane *p : scratch) plane_release(p);
     }
 };
 }  // namespace
@@ -229,12 +285,68 @@ static int mip_launch_normals(Context &c, const kc_plane *const rgb[3], const Mi
     return KC_OK;
 }
 
+// KC_MIP_COVERAGE: the select over alpha's plain chain (plain[k]: p_k, plain[0] the image's alpha; L levels of a w x h image,
+// w h <= 2^31) and, with `scaled` (scaled[k - 1]: d_k), the scale launch.  The records and the histograms live in
+// `scratch`, which the caller gives back to the pool once everything that reads it is enqueued (or waited for); *rec = the L
+// device records.  Launches: a count and a pick per pass, three passes when there is a level >= 1, and the scale.
+static int coverage_enqueue(Context &c, const std::vector<const kc_plane *> &plain, const std::vector<kc_plane *> *scaled, uint32_t w, uint32_t h,
+                            uint32_t L, uint32_t ref, PoolStaging &scratch, CoverageRecord **rec)
+{
+    if (L > KC_COVERAGE_MAX_LEVELS) return mip_refuse("KC_MIP_COVERAGE", "more levels than the job table holds");
+    const size_t rec_bytes = ((size_t)L * sizeof(CoverageRecord) + 255) / 256 * 256, hist_bytes = (size_t)L * KC_COVERAGE_BINS * sizeof(uint32_t);
+    KC_TRY(scratch.alloc(rec_bytes + hist_bytes));
+    CoverageArgs a{};
+    uint32_t wgs = 0;
+    uint64_t below = 0;  // the texels of the levels >= 1
+    for (uint32_t k = 0; k < L; ++k) {
+        CoverageJob &J = a.jobs[k];
+        J.src = plain[k]->dptr;
+        J.src_pitch = (uint32_t)(plain[k]->pitch / sizeof(float));
+        J.dst = scaled && k ? (*scaled)[k - 1]->dptr : nullptr;
+        J.dst_pitch = scaled && k ? (uint32_t)((*scaled)[k - 1]->pitch / sizeof(float)) : 0u;
+        J.w = level_extent(w, k);
+        J.h = level_extent(h, k);
+        J.first_wg = wgs;
+        J.wgs = coverage_job_wgs(J.w, J.h);
+        wgs += J.wgs;
+        if (k) below += (uint64_t)J.w * J.h;
+    }
+    const uint32_t wgs0 = a.jobs[0].wgs;
+    a.rec = (CoverageRecord *)scratch.ptr;
+    a.hist = (uint32_t *)((char *)scratch.ptr + rec_bytes);
+    a.levels = L;
+    a.ref = ref;
+    a.r_b = alpha_ref_threshold(ref);
+    KC_HIP(hipMemsetAsync(scratch.ptr, 0, rec_bytes + hist_bytes, c.stream));
+    uint32_t launches = 0;
+    for (uint32_t pass = 0; pass < (L > 1 ? 3u : 1u); ++pass) {
+        hipError_t e = pass == 0 ? launch_coverage_count(a, 0, 0, wgs, c.stream) : launch_coverage_count(a, pass, wgs0, wgs - wgs0, c.stream);
+        if (e != hipSuccess) return hip_fail(e, "launch_coverage_count");
+        e = launch_coverage_pick(a, pass, c.stream);
+        if (e != hipSuccess) return hip_fail(e, "launch_coverage_pick");
+        launches += 2;
+    }
+    uint64_t texels = (uint64_t)w * h + 3 * below;  // level 0 once, every further level once per pass
+    if (scaled && L > 1) {
+        hipError_t e = launch_coverage_scale(a, wgs0, wgs - wgs0, c.stream);
+        if (e != hipSuccess) return hip_fail(e, "launch_coverage_scale");
+        launches++;
+        texels += 2 * below;  // read once more, written once
+    }
+    c.launches += launches;
+    c.counters["mip_coverage"] += launches;
+    c.alg_bytes += 4 * texels;
+    *rec = a.rec;
+    return KC_OK;
+}
+
 int image_build_mips(kc_image *img, uint32_t flags, kc_image **levels, uint32_t cap, uint32_t *count)
 {
-    if (flags & ~(uint32_t)(KC_MIP_PER_LEVEL | KC_MIP_NORMALS)) {
-        set_error("kc_image_build_mips: flags other than KC_MIP_PER_LEVEL and KC_MIP_NORMALS");
+    if (flags & ~(uint32_t)(KC_MIP_PER_LEVEL | KC_MIP_NORMALS | kCoverageFlagBits)) {
+        set_error("kc_image_build_mips: flags other than KC_MIP_PER_LEVEL, KC_MIP_NORMALS and KC_MIP_COVERAGE_REF");
         return KC_ERR_UNSUPPORTED;
     }
+    KC_TRY(mip_check_coverage_flags(flags, "kc_image_build_mips"));
     if (!img || !levels || !count) return mip_refuse("kc_image_build_mips", "NULL image, level array or count");
     KC_TRY(need_init());
     Context &c = ctx();
@@ -242,11 +354,14 @@ int image_build_mips(kc_image *img, uint32_t flags, kc_image **levels, uint32_t 
     const uint32_t w = img->w(), h = img->h(), L = 1u + floor_log2(w > h ? w : h);
     *count = L;
     const bool normals = (flags & KC_MIP_NORMALS) != 0, per_level = (flags & KC_MIP_PER_LEVEL) != 0;
+    const uint32_t ref = flags >> 24;  // != 0: KC_MIP_COVERAGE
     if (normals && !img->is_rgba()) return mip_refuse("kc_image_build_mips", "KC_MIP_NORMALS is for RGBA images (X, Y, Z in R, G, B)");
+    if (ref && !img->is_rgba()) return mip_refuse("kc_image_build_mips", "KC_MIP_COVERAGE is for RGBA images");
     if (cap < L) return mip_refuse("kc_image_build_mips", "cap is below the level count");
     // the kernels' indices are 32-bit and the pyramid's tile rows a grid dimension
     if (w > (1u << 30) || ((uint64_t)h + 63) / 64 > 65535ull || (((uint64_t)w + 3) / 4) * h > (1ull << 31))
         return mip_refuse("kc_image_build_mips", "image too large");
+    if (ref && (uint64_t)w * h > (1ull << 31)) return mip_refuse("kc_image_build_mips", "image too large");  // the targets' 64-bit products
     KC_TRY(image_force(img));  // pending chains and deferred resizes run first
     const int n = img->n;
     // sl: the planes the plain rule reduces (under KC_MIP_NORMALS: alpha alone); rgb: R, G, B under KC_MIP_NORMALS
@@ -260,6 +375,10 @@ int image_build_mips(kc_image *img, uint32_t flags, kc_image **levels, uint32_t 
     mc.planes.reserve((size_t)(L - 1) * n);
     std::vector<kc_plane *> slot_planes((size_t)(L - 1) * 4, nullptr);  // [level - 1][slot], owned through mc.planes
     std::vector<kc_plane *> rgb_planes(normals && rgb.n > 0 ? (size_t)(L - 1) * 3 : 0, nullptr);  // [level - 1][channel], likewise
+    // KC_MIP_COVERAGE with a resident alpha: the level images get alpha planes of their own (d_k), the slot's planes keep the
+    // plain alpha (p_k) that the next level is made from -- shared with R, G, B where they alias alpha, scratch otherwise
+    const bool coverage = ref != 0 && sl.slot_of[3] >= 0 && L > 1;
+    std::vector<kc_plane *> alpha_planes(coverage ? L - 1 : 0, nullptr);  // [level - 1], owned through mc.planes
     float cv[4] = { 0.0f, 0.0f, 0.0f, 0.0f };
     for (int ch = 0; ch < n; ++ch) cv[ch] = img->planes[ch]->cval;
     for (uint32_t k = 1; k < L; ++k) {
@@ -281,6 +400,14 @@ int image_build_mips(kc_image *img, uint32_t flags, kc_image **levels, uint32_t 
             } else if (s < 0) {
                 cv[ch] = mip_const_fold(cv[ch]);
                 p = plane_new_const(W, H, cv[ch]);
+            } else if (coverage && ch == 3) {
+                kc_plane *&plain = slot_planes[(size_t)(k - 1) * 4 + s];
+                if (!plain) {
+                    KC_TRY(plane_new_mem(W, H, &plain));
+                    mc.scratch.push_back(plain);
+                }
+                KC_TRY(plane_new_mem(W, H, &p));
+                alpha_planes[k - 1] = p;
             } else if (slot_planes[(size_t)(k - 1) * 4 + s]) {
                 p = slot_planes[(size_t)(k - 1) * 4 + s];
                 plane_retain(p);
@@ -293,23 +420,85 @@ int image_build_mips(kc_image *img, uint32_t flags, kc_image **levels, uint32_t 
     }
     if (normals && rgb.n > 0) KC_TRY(mip_launch_normals(c, img->planes, rgb, rgb_planes, w, h, L, per_level));
     KC_TRY(mip_launch_plain(c, sl, slot_planes, w, h, L, per_level));
+    PoolStaging coverage_scratch;  // back to the pool when the call returns: everything that reads it is enqueued by then
+    if (coverage) {
+        std::vector<const kc_plane *> plain(L, img->planes[3]);
+        for (uint32_t k = 1; k < L; ++k) plain[k] = slot_planes[(size_t)(k - 1) * 4 + sl.slot_of[3]];
+        CoverageRecord *rec = nullptr;
+        KC_TRY(coverage_enqueue(c, plain, &alpha_planes, w, h, L, ref, coverage_scratch, &rec));
+    }
     image_retain(img);
     levels[0] = img;
     for (uint32_t k = 1; k < L; ++k) levels[k] = image_new(n, mc.planes.data() + (size_t)(k - 1) * n);  // retains; mc drops its own
     return KC_OK;
 }
 
+// kc_image_mip_coverage_info: alpha's plain chain in scratch planes, the select, the records back
+int image_mip_coverage_info(kc_image *img, uint32_t flags, kc_mip_coverage_level *out, uint32_t cap, uint32_t *count)
+{
+    const char *who = "kc_image_mip_coverage_info";
+    if ((flags & ~(uint32_t)(KC_MIP_PER_LEVEL | KC_MIP_NORMALS | kCoverageFlagBits)) || !(flags & KC_MIP_COVERAGE)) {
+        set_error(std::string(who) + ": flags must hold KC_MIP_COVERAGE_REF, with KC_MIP_PER_LEVEL and KC_MIP_NORMALS at the most");
+        return KC_ERR_UNSUPPORTED;
+    }
+    KC_TRY(mip_check_coverage_flags(flags, who));
+    if (!img || !out || !count) return mip_refuse(who, "NULL image, record array or count");
+    KC_TRY(need_init());
+    Context &c = ctx();
+    std::lock_guard<std::recursive_mutex> lk(c.mu);
+    const uint32_t w = img->w(), h = img->h(), L = 1u + floor_log2(w > h ? w : h), ref = flags >> 24;
+    *count = L;
+    if (!img->is_rgba()) return mip_refuse(who, "KC_MIP_COVERAGE is for RGBA images");
+    if (cap < L) return mip_refuse(who, "cap is below the level count");
+    if (w > (1u << 30) || ((uint64_t)h + 63) / 64 > 65535ull || (uint64_t)w * h > (1ull << 31)) return mip_refuse(who, "image too large");
+    KC_TRY(image_force(img));
+    const uint64_t n_0 = (uint64_t)w * h;
+    const kc_plane *alpha = img->planes[3];
+    if (alpha->kind == kc_plane::CONST) {  // answered here: every texel of a level is covered or none is
+        float cv = alpha->cval;
+        const uint64_t c_0 = quant_u8_host(cv) >= ref ? n_0 : 0;
+        for (uint32_t k = 0; k < L; ++k) {
+            const uint64_t n_k = (uint64_t)level_extent(w, k) * level_extent(h, k);
+            if (k) cv = mip_const_fold(cv);
+            out[k] = kc_mip_coverage_level{ n_k, k ? coverage_target(n_0, n_k, c_0) : c_0, quant_u8_host(cv) >= ref ? n_k : 0, 0.0f, 1.0f };
+        }
+        return KC_OK;
+    }
+    MipSlots sl;
+    sl.add(3, alpha);
+    MipChain mc;
+    std::vector<kc_plane *> slot_planes((size_t)(L - 1) * 4, nullptr);
+    std::vector<const kc_plane *> plain(L, alpha);
+    for (uint32_t k = 1; k < L; ++k) {
+        kc_plane *p = nullptr;
+        KC_TRY(plane_new_mem(level_extent(w, k), level_extent(h, k), &p));
+        mc.scratch.push_back(p);
+        slot_planes[(size_t)(k - 1) * 4] = p;
+        plain[k] = p;
+    }
+    KC_TRY(mip_launch_plain(c, sl, slot_planes, w, h, L, (flags & KC_MIP_PER_LEVEL) != 0));
+    PoolStaging scratch;
+    CoverageRecord *rec = nullptr;
+    KC_TRY(coverage_enqueue(c, plain, nullptr, w, h, L, ref, scratch, &rec));
+    std::vector<CoverageRecord> got(L);
+    hipError_t e = hipMemcpyAsync(got.data(), rec, (size_t)L * sizeof(CoverageRecord), hipMemcpyDeviceToHost, c.stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(c.stream);
+    if (e != hipSuccess) return hip_fail(e, who);
+    for (uint32_t k = 0; k < L; ++k) out[k] = kc_mip_coverage_level{ got[k].texels, got[k].target, got[k].plain_covered, got[k].v, got[k].scale };
+    return KC_OK;
+}
+
 // ---------------------------------------------------------------- the BC chain
-// flags of the chain exporters: KC_BC_SRGB under kc_image_to_bc's rule (bc_check_flags), plus KC_MIP_PER_LEVEL and KC_MIP_NORMALS,
-// which does not go with KC_BC_SRGB: a vector is not a colour
+// flags of the chain exporters: KC_BC_SRGB under kc_image_to_bc's rule (bc_check_flags), plus KC_MIP_PER_LEVEL, KC_MIP_NORMALS,
+// which does not go with KC_BC_SRGB: a vector is not a colour, and KC_MIP_COVERAGE_REF
 static int bc_mips_check_flags(int format, uint32_t flags, const char *who)
 {
-    KC_TRY(bc_check_flags(format, flags, KC_BC_SRGB | KC_MIP_PER_LEVEL | KC_MIP_NORMALS, who));
+    KC_TRY(bc_check_flags(format, flags, KC_BC_SRGB | KC_MIP_PER_LEVEL | KC_MIP_NORMALS | kCoverageFlagBits, who));
     if ((flags & KC_MIP_NORMALS) && (flags & KC_BC_SRGB)) {
         set_error(std::string(who) + ": KC_MIP_NORMALS with KC_BC_SRGB");
         return KC_ERR_UNSUPPORTED;
     }
-    return KC_OK;
+    return mip_check_coverage_flags(flags, who);
 }
 
 int bc_mip_layout(uint32_t w, uint32_t h, int format, uint32_t *levels, size_t *offsets, uint32_t cap, size_t *total_bytes)
@@ -339,7 +528,7 @@ static int bc_mips_encode(kc_image *img, int format, uint32_t flags, char *dst)
     KC_TRY(mip_level_count(img->w(), img->h(), &L));
     std::vector<kc_image *> lv(L, nullptr);
     uint32_t count = 0;
-    KC_TRY(image_build_mips(img, flags & (KC_MIP_PER_LEVEL | KC_MIP_NORMALS), lv.data(), L, &count));
+    KC_TRY(image_build_mips(img, flags & (KC_MIP_PER_LEVEL | KC_MIP_NORMALS | kCoverageFlagBits), lv.data(), L, &count));
     const BcFormat &f = *bc_format(format);  // the entry points have refused an unknown format
     size_t at = 0;
     int s = KC_OK;
@@ -359,7 +548,8 @@ int image_to_bc_mips(kc_image *img, int format, uint32_t flags, uint8_t *host, s
     if (!bc_format(format)) return mip_refuse("kc_image_to_bc_mips", "unknown format");
     if (!img || !host) return mip_refuse("kc_image_to_bc_mips", "NULL image or host buffer");
     KC_TRY(need_init());
-    if ((flags & KC_MIP_NORMALS) && !img->is_rgba()) return mip_refuse("kc_image_to_bc_mips", "KC_MIP_NORMALS is for RGBA images");
+    if ((flags & (KC_MIP_NORMALS | KC_MIP_COVERAGE)) && !img->is_rgba())
+        return mip_refuse("kc_image_to_bc_mips", "KC_MIP_NORMALS and KC_MIP_COVERAGE are for RGBA images");
     Context &c = ctx();
     std::lock_guard<std::recursive_mutex> lk(c.mu);
     size_t total = 0;
@@ -382,7 +572,8 @@ int image_to_bc_mips_device(kc_image *img, int format, uint32_t flags, void *dev
     if (!img || !device_ptr) return mip_refuse("kc_image_to_bc_mips_device", "NULL image or device pointer");
     if ((uintptr_t)device_ptr % bb) return mip_refuse("kc_image_to_bc_mips_device", "the pointer must be a multiple of the block bytes");
     KC_TRY(need_init());  // an image exists only after kc_init: it is not looked at before
-    if ((flags & KC_MIP_NORMALS) && !img->is_rgba()) return mip_refuse("kc_image_to_bc_mips_device", "KC_MIP_NORMALS is for RGBA images");
+    if ((flags & (KC_MIP_NORMALS | KC_MIP_COVERAGE)) && !img->is_rgba())
+        return mip_refuse("kc_image_to_bc_mips_device", "KC_MIP_NORMALS and KC_MIP_COVERAGE are for RGBA images");
     Context &c = ctx();
     std::lock_guard<std::recursive_mutex> lk(c.mu);
     size_t total = 0;

@@ -18,7 +18,7 @@ namespace host_srgb {
 }  // namespace host_srgb
 
 // streaming.h's quant_u8, on the host: ((v.clamp(0,1) * 255.).min(255.)) as u8, NaN -> 255
-static uint32_t quant_u8_host(float v)
+uint32_t quant_u8_host(float v)
 {
     float x = v;
     if (x < 0.0f) x = 0.0f;

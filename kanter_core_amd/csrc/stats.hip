@@ -10,26 +10,13 @@
 
 namespace kc {
 
-#include "streaming.h"  // ld_policy, quant_u8 / quant_u8_srgb: the bins are what the u8 exports write
+#include "streaming.h"  // ld_policy, hist_add, quant_u8 / quant_u8_srgb: the bins are what the u8 exports write
 
 typedef float st_f4 __attribute__((ext_vector_type(4)));
 
 // The total order of the non-NaN floats (-0.0 < +0.0, infinities included) as unsigned integers
 static __device__ __forceinline__ uint32_t order_key(uint32_t b) { return (b >> 31) ? ~b : (b | 0x80000000u); }
 static __device__ __forceinline__ bool nan_bits(uint32_t b) { return (b & 0x7fffffffu) > 0x7f800000u; }
-
-// One pixel of every lane into the wave's histogram.  When every counted pixel of the wave falls in one bin (a mask that is
-// mostly 0, values clamped to 0 or 1), one lane adds the wave's count: 64 lanes on one LDS address would serialise the atomics.
-static __device__ __forceinline__ void hist_add(uint32_t *wh, uint32_t b, bool in)
-{
-    const uint32_t b0 = __builtin_amdgcn_readfirstlane(b);  // may be a pixel past the row's end: it only picks the path
-    if (__ballot(in && b != b0) == 0) {
-        const uint32_t cnt = (uint32_t)__popcll(__ballot(in));
-        if (__lane_id() == __builtin_ctzll(__ballot(1))) atomicAdd(&wh[b0], cnt);
-    } else if (in) {
-        atomicAdd(&wh[b], 1u);
-    }
-}
 
 template <int N, bool NT, bool HIST, bool SRGB>
 static __device__ __forceinline__ void stats_quads(const StatsArgs &a, uint32_t *wh, const uint32_t *T, uint32_t (&kmin)[4],

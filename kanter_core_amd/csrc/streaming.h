@@ -1,6 +1,6 @@
 // What the streaming kernels share -- u8.hip (to_u8, from_u8), h2n.hip (height_to_normal), devimage.hip (device-memory images),
-// stats.hip, bc.hip, and chain.hip for the policy loads / stores: the grid cap of their grid-stride loops, loads / stores with a
-// launch's cache policy and the two 8-bit quantisers.
+// stats.hip, mip_coverage.hip, bc.hip, and chain.hip for the policy loads / stores: the grid cap of their grid-stride loops, loads /
+// stores with a launch's cache policy, the wave histogram step and the two 8-bit quantisers.
 // Included inside namespace kc by each unit; every definition is static, each unit keeps its own copy.
 #pragma once
 
@@ -26,6 +26,19 @@ static __device__ __forceinline__ void st_policy(V *p, V v)
 {
     if constexpr (NT) __builtin_nontemporal_store(v, p);
     else *p = v;
+}
+
+// One pixel of every lane into the wave's LDS histogram `wh` (stats.hip, mip_coverage.hip): bin b, counted where `in`.  When every counted pixel of the wave falls in one bin (a mask that is
+// mostly 0, values clamped to 0 or 1), one lane adds the wave's count: 64 lanes on one LDS address would serialise the atomics.
+static __device__ __forceinline__ void hist_add(uint32_t *wh, uint32_t b, bool in)
+{
+    const uint32_t b0 = __builtin_amdgcn_readfirstlane(b);  // may be a pixel past the row's end: it only picks the path
+    if (__ballot(in && b != b0) == 0) {
+        const uint32_t cnt = (uint32_t)__popcll(__ballot(in));
+        if (__lane_id() == __builtin_ctzll(__ballot(1))) atomicAdd(&wh[b0], cnt);
+    } else if (in) {
+        atomicAdd(&wh[b], 1u);
+    }
 }
 
 // ------------------------------------------------------------------------------------------
