@@ -18,17 +18,14 @@ import os
 
 import numpy as np
 
-from . import _lib
+from . import _abi, _lib
 from ._lib import kc_edge, kc_node_desc, kc_size
 
 # ------------------------------------------------------------------ errors (src/error.rs)
-_ERROR_NAMES = {
-    1: "Generic", 2: "Canceled", 3: "Image", 4: "InvalidBufferCount", 5: "InvalidNodeId", 6: "InvalidNodeType",
-    7: "InvalidSlotId", 8: "InvalidSlotType", 9: "InvalidEdge", 10: "NoSlotData", 11: "SlotOccupied",
-    12: "SlotNotOccupied", 13: "UnableToLock", 14: "NodeProcessing", 15: "PoisonError", 16: "TryLockError",
-    17: "NodeDirty", 18: "Io", 19: "InvalidName", 100: "Hip", 101: "NoDevice", 102: "InvalidArgument",
-    103: "OutOfMemory", 104: "Unsupported",
-}
+# kc_status enumerator -> variant name: KC_ERR_NO_SLOT_DATA is "NoSlotData"; these are the ones the reference spells otherwise
+_VARIANT_NAMES = {"KC_ERR_POISON": "PoisonError", "KC_ERR_TRY_LOCK": "TryLockError", "KC_ERR_INVALID_ARG": "InvalidArgument"}
+_ERROR_NAMES = {v: _VARIANT_NAMES.get(k, k[len("KC_ERR_"):].title().replace("_", ""))
+                for k, v in vars(_abi).items() if k.startswith("KC_ERR_")}
 
 
 class TexProError(Exception):
@@ -47,11 +44,14 @@ class TexProError(Exception):
     __hash__ = Exception.__hash__
 
 
+_DETAILED = (_abi.KC_ERR_GENERIC, _abi.KC_ERR_IMAGE, _abi.KC_ERR_NODE_PROCESSING, _abi.KC_ERR_IO)  # TexProError variants with a payload
+
+
 def _check(status):
-    if status != 0:
+    if status != _abi.KC_OK:
         L = _lib.load()
         detail = L.kc_last_error() or b""
-        raise TexProError(status, detail.decode(errors="replace") if status >= 100 or status in (1, 3, 14, 18) else "")
+        raise TexProError(status, detail.decode(errors="replace") if status >= _abi.KC_ERR_HIP or status in _DETAILED else "")
     return status
 
 
@@ -106,7 +106,7 @@ def get_cache_policy():
     return _lib.load().kc_get_cache_policy()
 
 
-COMM_ID_BYTES = 256
+COMM_ID_BYTES = _abi.KC_COMM_ID_BYTES
 
 
 def comm_unique_id():
@@ -413,11 +413,11 @@ class ResizePolicy:
 
     @staticmethod
     def SpecificSlot(slot_id):
-        return ResizePolicy(4, slot=slot_id)
+        return ResizePolicy(_abi.KC_POLICY_SPECIFIC_SLOT, slot=slot_id)
 
     @staticmethod
     def SpecificSize(size):
-        return ResizePolicy(5, size=size if isinstance(size, Size) else Size(*size))
+        return ResizePolicy(_abi.KC_POLICY_SPECIFIC_SIZE, size=size if isinstance(size, Size) else Size(*size))
 
     @staticmethod
     def default():
@@ -599,10 +599,11 @@ def _edges(fn, handle):
 
 
 # ------------------------------------------------------------------ device-memory images (kc_image_from_device / _to_device)
-DEVICE_SRGB = 1  # export, U8 only: to_u8_srgb on R, G, B
-DEVICE_GRAY = 2  # import, one channel only: a Gray image
-LAYOUT_HWC, LAYOUT_CHW = 0, 1
-_DEVICE_DTYPES = {"uint8": (0, 1), "uint16": (1, 2), "float16": (2, 2), "bfloat16": (3, 2), "float32": (4, 4)}  # code, bytes
+DEVICE_SRGB = _abi.KC_DEVICE_SRGB  # export, U8 only: to_u8_srgb on R, G, B
+DEVICE_GRAY = _abi.KC_DEVICE_GRAY  # import, one channel only: a Gray image
+LAYOUT_HWC, LAYOUT_CHW = _abi.KC_LAYOUT_INTERLEAVED, _abi.KC_LAYOUT_PLANAR
+_DEVICE_DTYPES = {"uint8": (_abi.KC_DTYPE_U8, 1), "uint16": (_abi.KC_DTYPE_U16, 2), "float16": (_abi.KC_DTYPE_F16, 2),
+                  "bfloat16": (_abi.KC_DTYPE_BF16, 2), "float32": (_abi.KC_DTYPE_F32, 4)}  # kc_dtype, bytes
 
 
 def device_image_desc(t, layout="hwc"):
@@ -667,10 +668,10 @@ def _device_export(call, size, dtype, layout, channels, srgb, out):
     return out
 
 
-BC_SRGB = 1  # kc_image_to_bc: BC1 / BC3 / BC7 colour as to_u8_srgb writes it (alpha linear)
-BC7 = 98     # KC_BC7: DXGI_FORMAT_BC7_UNORM's number (7 is not a format and stays refused)
-BC6H = 95    # KC_BC6H: DXGI_FORMAT_BC6H_UF16's number; HDR blocks of the planes' values as half floats, never sRGB
-BC_BLOCK_BYTES = {1: 8, 3: 16, 4: 8, 5: 16, BC6H: 16, BC7: 16}  # kc_bc_format -> bytes per 4 x 4 block
+BC_SRGB = _abi.KC_BC_SRGB  # kc_image_to_bc: BC1 / BC3 / BC7 colour as to_u8_srgb writes it (alpha linear)
+BC7 = _abi.KC_BC7    # KC_BC7: DXGI_FORMAT_BC7_UNORM's number (7 is not a format and stays refused)
+BC6H = _abi.KC_BC6H  # KC_BC6H: DXGI_FORMAT_BC6H_UF16's number; HDR blocks of the planes' values as half floats, never sRGB
+BC_BLOCK_BYTES = {_abi.KC_BC1: 8, _abi.KC_BC3: 16, _abi.KC_BC4: 8, _abi.KC_BC5: 16, BC6H: 16, BC7: 16}  # kc_bc_format -> bytes per 4 x 4 block
 BC6H_PEAK = 31743  # 0x7BFF, the bit pattern of 65504: the largest texel of a BC6H image, as an integer
 
 
@@ -698,11 +699,11 @@ def _bc_export(call, size, fmt, srgb, out):
     return out
 
 
-MIP_PER_LEVEL = 2  # kc_image_build_mips and the chain exporters: one launch of the one-level kernel per level
-MIP_NORMALS = 32   # ... R, G, B are a normal map (n * 0.5 + 0.5): every level is renormalised before the next is made
+MIP_PER_LEVEL = _abi.KC_MIP_PER_LEVEL  # kc_image_build_mips and the chain exporters: one launch of the one-level kernel per level
+MIP_NORMALS = _abi.KC_MIP_NORMALS  # ... R, G, B are a normal map (n * 0.5 + 0.5): every level is renormalised before the next is made
 
 
-MIP_COVERAGE = 64  # ... alpha is tested against the byte in bits 24-31: every level keeps level 0's coverage
+MIP_COVERAGE = _abi.KC_MIP_COVERAGE  # ... alpha is tested against the byte in bits 24-31: every level keeps level 0's coverage
 
 
 def mip_coverage_ref(ref):
@@ -772,7 +773,7 @@ def preview_level(width, height, max_extent):
     return k.value, w.value, h.value
 
 
-PREVIEW_SRGB = 1  # kc_image_previews: R, G, B (Gray: the value) as to_u8_srgb writes them, alpha linear
+PREVIEW_SRGB = _abi.KC_PREVIEW_SRGB  # kc_image_previews: R, G, B (Gray: the value) as to_u8_srgb writes them, alpha linear
 
 PreviewPlan = collections.namedtuple("PreviewPlan", "passes fallback level_size levels workgroups scratch_sizes scratch_bytes")
 PreviewPlan.__doc__ = """What one preview request takes (kc_preview_plan): passes = the launches it takes part in, fallback = the
@@ -881,8 +882,8 @@ def _bc_mips_export(call, size, fmt, srgb, per_level, out, normals=False, covera
     return out, offs
 
 
-STATS_HISTOGRAM = 1  # kc_image_channel_stats: also the u8 histograms
-STATS_SRGB = 2       # ... binned as to_u8_srgb (R, G, B; alpha linear)
+STATS_HISTOGRAM = _abi.KC_STATS_HISTOGRAM  # kc_image_channel_stats: also the u8 histograms
+STATS_SRGB = _abi.KC_STATS_SRGB  # ... binned as to_u8_srgb (R, G, B; alpha linear)
 
 ChannelStats = collections.namedtuple("ChannelStats", "min max nan_count pixels histogram")
 ChannelStats.__doc__ = """Per-channel statistics (kc_image_channel_stats), one entry per channel of the image (1 Gray, 4 RGBA):
@@ -901,8 +902,8 @@ def _channel_stats(call, histogram, srgb):
                         int(r.pixels), hist)
 
 
-BC_GRAY = 4  # kc_image_from_bc, BC4 only: a Gray image of the channel instead of the RGBA rule
-BC_ALL_MODES = 16  # the decode side (from_bc, from_bc_torch, read_dds, bc_error with blocks): every BC7 and BC6H mode, partitioned ones included
+BC_GRAY = _abi.KC_BC_GRAY  # kc_image_from_bc, BC4 only: a Gray image of the channel instead of the RGBA rule
+BC_ALL_MODES = _abi.KC_BC_ALL_MODES  # the decode side (from_bc, from_bc_torch, read_dds, bc_error with blocks): every BC7 and BC6H mode, partitioned ones included
 
 
 def _decode_flags(gray, all_modes):
