@@ -589,6 +589,64 @@ KC_API int kc_image_to_bc_device(kc_image *img, const kc_bc_image *dst, uint32_t
  *             them), and 4 N_0 + 20 sum_{k >= 1} N_k algorithmic bytes:
  *             level 0's alpha read once, every further level once per pass and once for the scale, and written once.  The
  *             scratch comes from the pool and goes back to it; the call still does not wait.
+ *   Roughness chains (kc_image_build_roughness_mips).  Renormalising a coarser level of a normal map throws away the length of
+ *             the averaged vector, the only record of how much the normals varied under the texel: beside a plain-boxed
+ *             roughness chain, bumpy surfaces turn mirror-smooth with distance and sparkle.  This chain raises every level of a
+ *             roughness plane by the variance of the normals under the texel (Toksvig; tests/mip_roughness_ref.py is the same
+ *             rule in numpy).  Inputs: a roughness plane rho, one channel of an image, linear f32; a normal map of the same
+ *             size, an RGBA image with X, Y, Z in R, G, B stored as n * 0.5 + 0.5; `power`, a finite f32, 0 < power <= 65536.
+ *             Everything is f32, nothing is fused, denormals are kept, / and sqrtf are correctly rounded.
+ *               Level 0 of the normals: unit vectors.  Per texel, with e_c the stored channel:
+ *                         v_c = e_c * 2.0f - 1.0f,  q = (v_x * v_x + v_y * v_y) + v_z * v_z,  l0 = sqrtf(q),
+ *                         u_c = v_c / l0 if l0 > 0 && l0 < +inf, else u = (0, 0, 1)      (kc_mip_unit_normal)
+ *                         The comparison is false for NaN: a zero vector, an overflow, a NaN or an infinity in any channel
+ *                         give (0, 0, 1), and u is always finite.  A map that went through 8 bits has lengths of 1 +- 0.004;
+ *                         without this step that quantisation error would read as variance on every smooth surface.
+ *               State.    m_c,k is the plain rule's chain of u_c (the box above, the same order and clamps, every level rounded
+ *                         to f32 before the next is made); m lives in vector space, never re-encoded and never renormalised.
+ *                         r_k is the plain rule's chain of rho, always made from the unadjusted r_{k-1}: the adjustment never
+ *                         compounds, exactly as coverage treats alpha.
+ *               A texel of level k >= 1, d = rough(m, r, power)                          (kc_mip_roughness_texel):
+ *                         if r != r:                 d = r          (NaN stays NaN; payload not in the contract)
+ *                         q = (m_x * m_x + m_y * m_y) + m_z * m_z,  l = sqrtf(q)
+ *                         else if l == 0:            d = 1.0f       (the normals cancel: every direction is present)
+ *                         else t = (1.0f - l) / l
+ *                              if !(t > 0x1p-14f):   d = r          (a flat footprint keeps the plain box bit for bit, unclamped)
+ *                              else te = t - 0x1p-14f
+ *                                   rc = min(max(r, 0.0f), 1.0f),  a = rc * rc,  a2 = a * a
+ *                                   B  = ((2.0f * te) * power) * (a2 - 1.0f)
+ *                                   n  = (B - a2) / (B - 1.0f)
+ *                                   d  = sqrtf(sqrtf(n))
+ *                         B <= 0 and B - 1 <= -1, so n lies in [a2, 1] up to rounding and no NaN or infinity arises for a
+ *                         non-NaN r; d may lie an ulp or two below rc near 1, which is not part of the contract.  The floor
+ *                         2^-14 swallows the rounding of the normalisation (unit vectors and their 8-bit quantisations have
+ *                         t <= 1.8e-7), so a normal map that is flat under a texel leaves the roughness chain equal to the plain
+ *                         chain bit for bit.  Level 0 is the image itself, untouched.  m and r are rounded per level, so the
+ *                         fused form and KC_MIP_PER_LEVEL give the same bits.
+ *             kc_image_build_roughness_mips: `img` is Gray (`channel` must be 0) or RGBA (`channel` 0..3: an ORM texture keeps
+ *             roughness in G, a normal map often in its own alpha, so img == normals is legal).  `levels`, `count` and `cap` as
+ *             kc_image_build_mips: levels[0] is img (+1 reference), the level images are of img's kind.  The named channel
+ *             follows the rule above and gets a new resident plane of its own at every level >= 1, also where it aliases
+ *             another channel at level 0 or is a constant plane; every other channel follows the plain rule (constants folded,
+ *             aliases shared).  If R, G and B of `normals` are all constant planes the rule gives d = r everywhere: the call is
+ *             then the plain chain of img and launches nothing new.  Pending chains and deferred resizes of both images run
+ *             first.  flags: KC_MIP_PER_LEVEL only.  Errors, in this order: other flag bits KC_ERR_UNSUPPORTED; a NULL argument
+ *             or a `power` that is NaN, not finite, <= 0 or > 65536 KC_ERR_INVALID_ARG; KC_ERR_NO_DEVICE; then, with `*count`
+ *             written and nothing launched or allocated, KC_ERR_INVALID_ARG for `normals` not RGBA, sizes that differ (there is
+ *             no implicit resize), `channel` out of range for the kind, cap < L, or the size limits of kc_image_build_mips.  A
+ *             failure part-way releases what it made.  kc_stats: the four channels go down together, so the launches are those
+ *             of the plain chain of one plane (4096 x 4096: two; counters "mip_roughness_pyramid", "mip_roughness_level"), beside
+ *             the plain launches of the other resident channels; 4 w h algorithmic bytes per distinct resident plane read among
+ *             the four, 4 sum_{k >= 1} W_k H_k written, and 32 W_k H_k for every level k whose four boxes are handed to a
+ *             further launch through planes from the pool (written once, read once).
+ *   kc_mip_unit_normal, kc_mip_roughness_texel  u of a stored texel and rough() of the rule above: arithmetic, no kc_init needed.
+ *                        A NULL argument, or a `power` outside (0, 65536], is KC_ERR_INVALID_ARG.
+ *   kc_image_levels_to_bc_mips, kc_image_levels_write_dds  encode a chain the caller holds -- kc_image_build_roughness_mips's
+ *                        result, or any edited chain: 1 <= count <= L of levels[0]'s size, every levels[k] non-NULL, of one
+ *                        kind and max(1, w >> k) by max(1, h >> k); anything else is KC_ERR_INVALID_ARG.  flags: KC_BC_SRGB
+ *                        under kc_image_to_bc's rule for the format.  Level k goes at its kc_bc_mip_layout offset; `host_bytes`
+ *                        is at least the bytes of the first `count` levels.  The DDS form writes kc_dds_header(..., count) in
+ *                        front.  Pending chains of the levels run first; blocks until the bytes are there.
  *   kc_alpha_ref_threshold, kc_mip_coverage_target, kc_mip_coverage_scale  r_B, T_k (level 0: C_0) and s_k of the rule above:
  *                        arithmetic, no kc_init needed.  A NULL output, ref_u8 outside 1..255, a zero size, more than 2^31 texels,
  *                        covered0 > N_0 or level >= L is KC_ERR_INVALID_ARG.
@@ -718,6 +776,13 @@ KC_API int kc_image_to_bc_mips(kc_image *img, int format, uint32_t flags, uint8_
 KC_API int kc_image_to_bc_mips_device(kc_image *img, int format, uint32_t flags, void *device_ptr, size_t bytes, void *hip_stream);
 KC_API int kc_dds_header(uint32_t width, uint32_t height, int format, uint32_t flags, uint32_t levels, uint8_t out[148], size_t *bytes);
 KC_API int kc_image_write_dds(kc_image *img, const char *path, int format, uint32_t flags, int with_mips);
+KC_API int kc_mip_unit_normal(const float rgb[3], float u[3]);
+KC_API int kc_mip_roughness_texel(const float m[3], float r, float power, float *d);
+KC_API int kc_image_build_roughness_mips(kc_image *img, uint32_t channel, kc_image *normals, float power, uint32_t flags,
+                                         kc_image **levels, uint32_t cap, uint32_t *count);
+KC_API int kc_image_levels_to_bc_mips(kc_image *const *levels, uint32_t count, int format, uint32_t flags, uint8_t *host,
+                                      size_t host_bytes);
+KC_API int kc_image_levels_write_dds(kc_image *const *levels, uint32_t count, const char *path, int format, uint32_t flags);
 /* The way back: BC blocks decoded on the device, the error of an encoding measured on the device, and .dds files read.
  * Decoding is integer arithmetic on the block's bytes, so the pixels are exact (tests/bc_decode_ref.py is the same rules in
  * numpy).  Pixel (x, y) is texel 4 (y % 4) + x % 4 of block (x / 4, y / 4); texels of edge blocks outside the image are dropped.

@@ -758,6 +758,56 @@ def mip_normal_texel(box):
     return out
 
 
+def mip_unit_normal(rgb):
+    """-> (3,) float32: the unit vector a roughness chain (SlotImage.roughness_mips) reads from the stored texel `rgb` of a normal
+    map, n * 0.5 + 0.5 -- decoded and normalised in f32; a texel without a direction gives (0, 0, 1) (kc_mip_unit_normal; no device)."""
+    e = np.ascontiguousarray(rgb, np.float32)
+    if e.shape != (3,):
+        raise ValueError("rgb must hold three values")
+    out = np.empty(3, np.float32)
+    _check(_lib.load().kc_mip_unit_normal(e.ctypes.data, out.ctypes.data))
+    return out
+
+
+def mip_roughness_texel(m, r, power=1.0):
+    """-> np.float32: what a texel of a roughness chain stores for the boxes `m` of the normals' vector and `r` of the roughness:
+    r itself where the footprint is flat, 1 where the normals cancel, r raised by the normals' variance in between
+    (kc_mip_roughness_texel; no device)."""
+    v = np.ascontiguousarray(m, np.float32)
+    if v.shape != (3,):
+        raise ValueError("m must hold three values")
+    d = C.c_float()
+    _check(_lib.load().kc_mip_roughness_texel(v.ctypes.data, C.c_float(float(np.float32(r))), C.c_float(float(np.float32(power))), C.byref(d)))
+    return np.float32(d.value)
+
+
+def _level_handles(levels):
+    levels = list(levels)
+    return levels, (C.c_void_p * max(1, len(levels)))(*[l._h.value for l in levels])
+
+
+def levels_to_bc_mips(levels, fmt, srgb=False):
+    """-> one uint8 (ceil(H_k/4), ceil(W_k/4), block bytes) array per level, as SlotImage.to_bc_mips returns them: the BC blocks of
+    a chain the caller holds -- roughness_mips's result, or any edited chain -- or of its first levels
+    (kc_image_levels_to_bc_mips).  levels[k] is max(1, w >> k) by max(1, h >> k) and of levels[0]'s kind."""
+    f = _bc_format(fmt)
+    levels, arr = _level_handles(levels)
+    if not levels:
+        raise ValueError("levels is empty")
+    s = levels[0].size()
+    offs, total = bc_mip_layout(s.width, s.height, f)
+    buf = np.empty((total,), np.uint8)
+    _check(_lib.load().kc_image_levels_to_bc_mips(arr, len(levels), f, BC_SRGB if srgb else 0, buf.ctypes.data, buf.nbytes))
+    return _bc_mip_views(buf, s, f)[:len(levels)]
+
+
+def write_dds_levels(path, levels, fmt, srgb=False):
+    """Writes a .dds file (DX10 header) with the BC blocks of a chain the caller holds, or of its first levels
+    (kc_image_levels_write_dds)."""
+    levels, arr = _level_handles(levels)
+    _check(_lib.load().kc_image_levels_write_dds(arr, len(levels), os.fspath(path).encode(), _bc_format(fmt), BC_SRGB if srgb else 0))
+
+
 def mip_level_count(width, height):
     """Levels of the mip chain of a width x height image: 1 + floor(log2(max(width, height))) (kc_mip_level_count; no device)."""
     n = C.c_uint32()
@@ -1133,6 +1183,20 @@ class SlotImage:
         arr = (C.c_void_p * n)()
         count = C.c_uint32()
         _check(_lib.load().kc_image_build_mips(self._h, _mip_flags(False, per_level, normals, coverage), arr, n, C.byref(count)))
+        return [SlotImage(arr[k]) for k in range(count.value)]
+
+    def roughness_mips(self, normals, channel=0, power=1.0, per_level=False):
+        """-> the mip chain as mips() returns it, with channel `channel` a roughness that absorbs the variance of the normal map
+        `normals` (RGBA of this image's size, n * 0.5 + 0.5; may be this image): every level >= 1 of that channel is the plain
+        box raised by how much the normals under the texel vary -- unchanged where they agree, 1 where they cancel -- so that a
+        surface whose bumps have left the normal chain stays rough instead of turning mirror-smooth; power scales the effect.
+        The other channels follow the plain rule (kc_image_build_roughness_mips)."""
+        s = self.size()
+        n = mip_level_count(s.width, s.height)
+        arr = (C.c_void_p * n)()
+        count = C.c_uint32()
+        _check(_lib.load().kc_image_build_roughness_mips(self._h, channel, normals._h, C.c_float(float(np.float32(power))),
+                                                         MIP_PER_LEVEL if per_level else 0, arr, n, C.byref(count)))
         return [SlotImage(arr[k]) for k in range(count.value)]
 
     def mip_coverage_info(self, coverage):

@@ -906,6 +906,23 @@ try {
 }
 KC_CATCH
 
+int kc_mip_unit_normal(const float rgb[3], float u[3])
+try {
+    KC_ARG(rgb && u);
+    mip_unit_normal(rgb, u);
+    return KC_OK;
+}
+KC_CATCH
+
+int kc_mip_roughness_texel(const float m[3], float r, float power, float *d)
+try {
+    KC_ARG(m && d);
+    KC_ARG(power > 0.0f && power <= 65536.0f);  // false for NaN
+    *d = mip_roughness_texel(m, r, power);
+    return KC_OK;
+}
+KC_CATCH
+
 int kc_alpha_ref_threshold(uint32_t ref_u8, float *r)
 try {
     KC_ARG(r && ref_u8 >= 1 && ref_u8 <= 255);
@@ -939,6 +956,28 @@ int kc_image_build_mips(kc_image *img, uint32_t flags, kc_image **levels, uint32
 try {
     Lock api_lock(ctx().mu);  // reference counts are plain integers, see kc_plane::refs
     return image_build_mips(img, flags, levels, cap, count);  // the flags, the arguments, then need_init()
+}
+KC_CATCH
+
+int kc_image_build_roughness_mips(kc_image *img, uint32_t channel, kc_image *normals, float power, uint32_t flags, kc_image **levels,
+                                  uint32_t cap, uint32_t *count)
+try {
+    Lock api_lock(ctx().mu);  // reference counts are plain integers, see kc_plane::refs
+    return image_build_roughness_mips(img, channel, normals, power, flags, levels, cap, count);  // the flags, the arguments, then need_init()
+}
+KC_CATCH
+
+int kc_image_levels_to_bc_mips(kc_image *const *levels, uint32_t count, int format, uint32_t flags, uint8_t *host, size_t host_bytes)
+try {
+    Lock api_lock(ctx().mu);  // reference counts are plain integers, see kc_plane::refs
+    return image_levels_to_bc_mips(levels, count, format, flags, host, host_bytes, "kc_image_levels_to_bc_mips");
+}
+KC_CATCH
+
+int kc_image_levels_write_dds(kc_image *const *levels, uint32_t count, const char *path, int format, uint32_t flags)
+try {
+    Lock api_lock(ctx().mu);  // reference counts are plain integers, see kc_plane::refs
+    return image_levels_write_dds(levels, count, path, format, flags);
 }
 KC_CATCH
 

@@ -375,8 +375,8 @@ hipError_t launch_bc_modes_compare(int fmt, int srgb, const Operand op[4], int g
                                    hipStream_t s);
 // -- mip.hip --
 // Mip chains (mip.hip / mip.cpp): the 2 x 2 box of the header on the n_planes distinct resident planes of one image.  The device
-// steps of this family, of mip_normals.hip and of preview.hip's reduction are one copy, mip_steps.h, with the launch checks of
-// the four launch functions below.
+// steps of this family, of mip_normals.hip, of mip_roughness.hip and of preview.hip's reduction are one copy, mip_steps.h, with
+// the launch checks of the six launch functions below.
 // mip_pyramid_kernel<nt>: levels 1..n (1 <= n <= 6, both of w >> n and h >> n still >= 1) of the w x h source planes, one
 // workgroup per 64 x 64 tile; dst[p][k - 1] is level k of plane p, dst_pitch[k - 1] floats between its rows.
 struct MipPyramidArgs {
@@ -424,6 +424,40 @@ struct NormalLevelArgs {
     uint32_t w, h;
 };
 hipError_t launch_normal_level(const NormalLevelArgs &a, bool nt, hipStream_t s);
+// -- mip_roughness.hip --
+// Roughness chains (kc_image_build_roughness_mips): the same two walks with four channels coupled in one thread -- the vector of
+// the normals (0..2) and the roughness (3), each down the plain rule -- and the header's rough() of the four boxes as the one
+// plane a level stores.  `first`: the sources are level 0, X, Y, Z of the normal map as stored (decoded to unit vectors texel by
+// texel right after the loads) and the roughness plane; channel c is then a resident plane (src[c], src_pitch[c]; channels that
+// alias carry the same pointer) or the constant cval[c] (bit c of const_mask; src[c] is not looked at).  Otherwise the sources
+// are the four state planes of the level read, m_x, m_y, m_z, r, and const_mask is 0.  dst[k - 1] is the stored plane of level
+// k in roughness_pyramid_kernel<nt, first> (n, the tiles and the pitches as in MipPyramidArgs), dst the one level of
+// roughness_level_kernel<nt, first> (as MipLevelArgs).  state: where more levels follow, the four plain boxes of the last level
+// written (level n; the one level) go to these planes, rows as far apart as that level's dst rows; all NULL when none follows.
+struct RoughnessPyramidArgs {
+    const float *src[4];
+    uint32_t src_pitch[4];  // floats
+    float cval[4];
+    uint32_t const_mask;
+    float power;
+    float *dst[6];
+    uint32_t dst_pitch[6];  // floats
+    float *state[4];
+    uint32_t w, h, n;
+};
+hipError_t launch_roughness_pyramid(const RoughnessPyramidArgs &a, bool first, bool nt, hipStream_t s);
+struct RoughnessLevelArgs {
+    const float *src[4];
+    uint32_t src_pitch[4];  // floats
+    float cval[4];
+    uint32_t const_mask;
+    float power;
+    float *dst;
+    uint32_t dst_pitch;  // floats
+    float *state[4];
+    uint32_t w, h;
+};
+hipError_t launch_roughness_level(const RoughnessLevelArgs &a, bool first, bool nt, hipStream_t s);
 // -- mip_coverage.hip --
 // Alpha-test coverage (KC_MIP_COVERAGE): an exact k-th-largest selection over the alpha plane of every level of a chain -- a
 // radix select on the 30 significant bits of the header's key, 10 bits (KC_COVERAGE_BINS bins) per pass -- and the scale of

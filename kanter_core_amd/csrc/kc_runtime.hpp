@@ -451,6 +451,12 @@ int preview_level(uint32_t w, uint32_t h, uint32_t max_extent, uint32_t *level, 
 float mip_const_fold(float c);  // ((c + c) + (c + c)) * 0.25f, as the device computes it
 void mip_normal_texel(const float box[3], float out[3]);  // KC_MIP_NORMALS: the boxes of R, G, B -> the stored texel, as the device computes it
 int image_build_mips(kc_image *img, uint32_t flags, kc_image **levels, uint32_t cap, uint32_t *count);
+// roughness chains (mip.cpp): the rule's arithmetic as kc_mip_unit_normal and kc_mip_roughness_texel return it, as the device
+// computes it, and the body of kc_image_build_roughness_mips
+void mip_unit_normal(const float rgb[3], float u[3]);
+float mip_roughness_texel(const float m[3], float r, float power);
+int image_build_roughness_mips(kc_image *img, uint32_t channel, kc_image *normals, float power, uint32_t flags, kc_image **levels, uint32_t cap,
+                               uint32_t *count);
 // KC_MIP_COVERAGE (mip.cpp): the rule's arithmetic as kc_alpha_ref_threshold, kc_mip_coverage_target and kc_mip_coverage_scale
 // return it, the flag rule of the chain entry points (bit 64 and the reference byte in bits 24-31 go together), and the body of
 // kc_image_mip_coverage_info
@@ -464,6 +470,9 @@ int image_to_bc_mips(kc_image *img, int format, uint32_t flags, uint8_t *host, s
 int image_to_bc_mips_device(kc_image *img, int format, uint32_t flags, void *device_ptr, size_t bytes, void *hip_stream);
 int dds_header(uint32_t w, uint32_t h, int format, uint32_t flags, uint32_t levels, uint8_t *out, size_t *bytes);
 int image_write_dds(kc_image *img, const char *path, int format, uint32_t flags, int with_mips);
+// a chain the caller holds (mip.cpp): the bodies of kc_image_levels_to_bc_mips (who: the entry point's name) and kc_image_levels_write_dds
+int image_levels_to_bc_mips(kc_image *const *levels, uint32_t count, int format, uint32_t flags, uint8_t *host, size_t host_bytes, const char *who);
+int image_levels_write_dds(kc_image *const *levels, uint32_t count, const char *path, int format, uint32_t flags);
 // previews (preview.cpp): the bodies of kc_preview_plan, kc_image_previews, kc_image_previews_device and (given the slots' images)
 // kc_live_graph_buffer_previews; `imgs` (optional): the image of request i instead of r[i].image.  The context's buffers.
 int preview_plan(uint32_t w, uint32_t h, uint32_t level, uint32_t x, uint32_t y, uint32_t rect_w, uint32_t rect_h, kc_preview_plan_info *out);

@@ -1,9 +1,11 @@
-// Mip chains and their export (include/kanter_core_amd.h): kc_mip_level_count, kc_preview_level, kc_image_build_mips, kc_bc_mip_layout,
-// kc_image_to_bc_mips, kc_image_to_bc_mips_device, kc_dds_header, kc_image_write_dds.  The host side does the level arithmetic,
+// Mip chains and their export (include/kanter_core_amd.h): kc_mip_level_count, kc_preview_level, kc_image_build_mips,
+// kc_image_build_roughness_mips, kc_bc_mip_layout, kc_image_to_bc_mips, kc_image_to_bc_mips_device, kc_image_levels_to_bc_mips,
+// kc_dds_header, kc_image_write_dds, kc_image_levels_write_dds.  The host side does the level arithmetic,
 // folds constant planes with the device's expression, allocates the level planes and enqueues mip.hip's kernels on the library's
 // stream: the pyramid kernel while both extents still halve (up to six levels per launch), the one-level kernel for the rest and
 // for every level under KC_MIP_PER_LEVEL; under KC_MIP_NORMALS mip_normals.hip's two kernels take R, G, B together and
-// renormalise every level; under KC_MIP_COVERAGE mip_coverage.hip's select and scale give alpha planes of their own.  The BC chain
+// renormalise every level; under KC_MIP_COVERAGE mip_coverage.hip's select and scale give alpha planes of their own; a roughness
+// chain is mip_roughness.hip's two kernels on the vector of a normal map and the roughness plane together.  The BC chain
 // is bc.cpp's encoder launch once per level; the DDS writer is host code.
 #include <cmath>
 #include <cstdio>
@@ -76,6 +78,57 @@ void mip_normal_texel(const float box[3], float out[3])
         volatile float m = u[c] * half;
         out[c] = m + half;
     }
+}
+
+// ---------------------------------------------------------------- roughness chains: the rule's arithmetic
+// Level 0 of the normals on one texel, from the stored R, G, B to the unit vector: the device's expression (mip_roughness.hip,
+// unit_normal), every operation through a volatile temporary like mip_const_fold.  This is kc_mip_unit_normal.
+void mip_unit_normal(const float rgb[3], float u[3])
+{
+    volatile float v[3];
+    volatile float two = 2.0f, one = 1.0f;
+    for (int c = 0; c < 3; ++c) {
+        volatile float m = rgb[c] * two;
+        v[c] = m - one;
+    }
+    volatile float xx = v[0] * v[0], yy = v[1] * v[1], zz = v[2] * v[2];
+    volatile float xy = xx + yy;
+    volatile float q = xy + zz;
+    volatile float l = std::sqrt((float)q);
+    const bool ok = l > 0.0f && l < std::numeric_limits<float>::infinity();  // false for NaN
+    for (int c = 0; c < 3; ++c) {
+        volatile float d = ok ? v[c] / l : (c == 2 ? 1.0f : 0.0f);
+        u[c] = d;
+    }
+}
+
+// rough(m, r, power) of the header, the stored texel of a level >= 1: the device's expression (mip_roughness.hip, rough_texel)
+// likewise.  This is kc_mip_roughness_texel.
+float mip_roughness_texel(const float m[3], float r, float power)
+{
+    if (r != r) return r;
+    volatile float xx = m[0] * m[0], yy = m[1] * m[1], zz = m[2] * m[2];
+    volatile float xy = xx + yy;
+    volatile float q = xy + zz;
+    volatile float l = std::sqrt((float)q);
+    if (l == 0.0f) return 1.0f;
+    volatile float one = 1.0f, floor = 0x1p-14f, two = 2.0f;
+    volatile float s = one - l;
+    volatile float t = s / l;
+    if (!(t > floor)) return r;
+    volatile float te = t - floor;
+    volatile float rc = std::fmin(std::fmax(r, 0.0f), 1.0f);
+    volatile float a = rc * rc;
+    volatile float a2 = a * a;
+    volatile float te2 = two * te;
+    volatile float tp = te2 * power;
+    volatile float am = a2 - one;
+    volatile float B = tp * am;
+    volatile float num = B - a2, den = B - one;
+    volatile float n = num / den;
+    volatile float h = std::sqrt((float)n);
+    volatile float d = std::sqrt((float)h);
+    return d;
 }
 
 // ---------------------------------------------------------------- KC_MIP_COVERAGE: the rule's arithmetic
@@ -285,6 +338,84 @@ static int mip_launch_normals(Context &c, const kc_plane *const rgb[3], const Mi
     return KC_OK;
 }
 
+// kc_image_build_roughness_mips: the coupled launches for the vector of the normals and the roughness (src0: X, Y, Z of the
+// normal map and the roughness plane at level 0, constant or resident, at least one of the first three resident); level k's
+// stored plane is dst_planes[k - 1].  The four plain boxes of the last level a launch writes are the next launch's sources:
+// state planes from the pool, held in mc.scratch until the call returns (everything that reads them is enqueued by then).
+static int mip_launch_roughness(Context &c, const kc_plane *const src0[4], const std::vector<kc_plane *> &dst_planes, MipChain &mc, float power,
+                                uint32_t w, uint32_t h, uint32_t L, bool per_level)
+{
+    if (L < 2) return KC_OK;
+    MipSlots sl;  // the distinct resident planes of level 0
+    uint32_t const_mask = 0;
+    for (int ch = 0; ch < 4; ++ch) {
+        sl.add(ch, src0[ch]);
+        if (sl.slot_of[ch] < 0) const_mask |= 1u << ch;
+    }
+    const kc_plane *state[4] = { nullptr, nullptr, nullptr, nullptr };  // of the level the next launch reads
+    uint64_t state_texels = 0;
+    auto fill = [&](auto &a, uint32_t k, uint32_t sw, uint32_t sh, uint32_t last) -> int {  // a launch that reads level k and ends at `last`
+        a.w = sw;
+        a.h = sh;
+        a.power = power;
+        for (int ch = 0; ch < 4; ++ch) {
+            const kc_plane *p = k == 0 ? src0[ch] : state[ch];
+            const bool is_const = k == 0 && ((const_mask >> ch) & 1u);
+            a.src[ch] = is_const ? nullptr : p->dptr;
+            a.src_pitch[ch] = is_const ? 0u : (uint32_t)(p->pitch / sizeof(float));
+            a.cval[ch] = is_const ? p->cval : 0.0f;
+        }
+        a.const_mask = k == 0 ? const_mask : 0u;
+        for (int ch = 0; ch < 4; ++ch) {
+            state[ch] = nullptr;
+            a.state[ch] = nullptr;
+        }
+        if (last + 1 < L) {  // more levels follow
+            const uint32_t W = level_extent(w, last), H = level_extent(h, last);
+            for (int ch = 0; ch < 4; ++ch) {
+                kc_plane *p = nullptr;
+                KC_TRY(plane_new_mem(W, H, &p));
+                mc.scratch.push_back(p);
+                if (p->pitch != dst_planes[last - 1]->pitch) return mip_refuse("kc_image_build_roughness_mips", "planes of one size differ in pitch");
+                state[ch] = p;
+                a.state[ch] = p->dptr;
+            }
+            state_texels += (uint64_t)W * H;
+        }
+        return KC_OK;
+    };
+    KC_TRY(mip_walk(c, w, h, L, per_level, 1u, [&](uint32_t k) { return k == 0 ? (uint32_t)sl.n : 4u; },
+                    [&](uint32_t k, uint32_t sw, uint32_t sh, uint32_t fused, bool nt) {
+        if (fused) {
+            RoughnessPyramidArgs a{};
+            KC_TRY(fill(a, k, sw, sh, k + fused));
+            a.n = fused;
+            for (uint32_t j = 0; j < fused; ++j) {
+                a.dst[j] = dst_planes[k + j]->dptr;
+                a.dst_pitch[j] = (uint32_t)(dst_planes[k + j]->pitch / sizeof(float));
+            }
+            hipError_t e = launch_roughness_pyramid(a, k == 0, nt, c.stream);
+            if (e != hipSuccess) return hip_fail(e, "launch_roughness_pyramid");
+            c.counters["mip_roughness_pyramid"]++;
+        } else {
+            RoughnessLevelArgs a{};
+            KC_TRY(fill(a, k, sw, sh, k + 1));
+            a.dst = dst_planes[k]->dptr;
+            a.dst_pitch = (uint32_t)(dst_planes[k]->pitch / sizeof(float));
+            hipError_t e = launch_roughness_level(a, k == 0, nt, c.stream);
+            if (e != hipSuccess) return hip_fail(e, "launch_roughness_level");
+            c.counters["mip_roughness_level"]++;
+        }
+        return (int)KC_OK;
+    }));
+    // every distinct resident plane of level 0 read once, one plane of every further level written once, the four state planes
+    // of a level written once and read once
+    uint64_t written = 0;
+    for (uint32_t j = 1; j < L; ++j) written += (uint64_t)level_extent(w, j) * level_extent(h, j);
+    c.alg_bytes += 4 * (uint64_t)w * h * sl.n + 4 * written + 32 * state_texels;
+    return KC_OK;
+}
+
 // KC_MIP_COVERAGE: the select over alpha's plain chain (plain[k]: p_k, plain[0] the image's alpha; L levels of a w x h image,
 // w h <= 2^31) and, with `scaled` (scaled[k - 1]: d_k), the scale launch.  The records and the histograms live in
 // `scratch`, which the caller gives back to the pool once everything that reads it is enqueued (or waited for); *rec = the L
@@ -340,6 +471,12 @@ static int coverage_enqueue(Context &c, const std::vector<const kc_plane *> &pla
     return KC_OK;
 }
 
+// the kernels' indices are 32-bit and the pyramid's tile rows a grid dimension
+static bool mip_size_ok(uint32_t w, uint32_t h)
+{
+    return !(w > (1u << 30) || ((uint64_t)h + 63) / 64 > 65535ull || (((uint64_t)w + 3) / 4) * h > (1ull << 31));
+}
+
 int image_build_mips(kc_image *img, uint32_t flags, kc_image **levels, uint32_t cap, uint32_t *count)
 {
     if (flags & ~(uint32_t)(KC_MIP_PER_LEVEL | KC_MIP_NORMALS | kCoverageFlagBits)) {
@@ -358,9 +495,7 @@ int image_build_mips(kc_image *img, uint32_t flags, kc_image **levels, uint32_t 
     if (normals && !img->is_rgba()) return mip_refuse("kc_image_build_mips", "KC_MIP_NORMALS is for RGBA images (X, Y, Z in R, G, B)");
     if (ref && !img->is_rgba()) return mip_refuse("kc_image_build_mips", "KC_MIP_COVERAGE is for RGBA images");
     if (cap < L) return mip_refuse("kc_image_build_mips", "cap is below the level count");
-    // the kernels' indices are 32-bit and the pyramid's tile rows a grid dimension
-    if (w > (1u << 30) || ((uint64_t)h + 63) / 64 > 65535ull || (((uint64_t)w + 3) / 4) * h > (1ull << 31))
-        return mip_refuse("kc_image_build_mips", "image too large");
+    if (!mip_size_ok(w, h)) return mip_refuse("kc_image_build_mips", "image too large");
     if (ref && (uint64_t)w * h > (1ull << 31)) return mip_refuse("kc_image_build_mips", "image too large");  // the targets' 64-bit products
     KC_TRY(image_force(img));  // pending chains and deferred resizes run first
     const int n = img->n;
@@ -427,6 +562,74 @@ int image_build_mips(kc_image *img, uint32_t flags, kc_image **levels, uint32_t 
         CoverageRecord *rec = nullptr;
         KC_TRY(coverage_enqueue(c, plain, &alpha_planes, w, h, L, ref, coverage_scratch, &rec));
     }
+    image_retain(img);
+    levels[0] = img;
+    for (uint32_t k = 1; k < L; ++k) levels[k] = image_new(n, mc.planes.data() + (size_t)(k - 1) * n);  // retains; mc drops its own
+    return KC_OK;
+}
+
+// kc_image_build_roughness_mips: the named channel by the roughness rule (mip_launch_roughness), every other channel by the
+// plain one, exactly as image_build_mips places them
+int image_build_roughness_mips(kc_image *img, uint32_t channel, kc_image *normals, float power, uint32_t flags, kc_image **levels, uint32_t cap,
+                               uint32_t *count)
+{
+    const char *who = "kc_image_build_roughness_mips";
+    if (flags & ~(uint32_t)KC_MIP_PER_LEVEL) {
+        set_error(std::string(who) + ": flags other than KC_MIP_PER_LEVEL");
+        return KC_ERR_UNSUPPORTED;
+    }
+    if (!img || !normals || !levels || !count) return mip_refuse(who, "NULL image, normal map, level array or count");
+    if (!(power > 0.0f && power <= 65536.0f)) return mip_refuse(who, "power must be a finite number above 0 and at most 65536");  // false for NaN
+    KC_TRY(need_init());
+    Context &c = ctx();
+    std::lock_guard<std::recursive_mutex> lk(c.mu);
+    const uint32_t w = img->w(), h = img->h(), L = 1u + floor_log2(w > h ? w : h);
+    *count = L;
+    if (!normals->is_rgba()) return mip_refuse(who, "the normal map must be an RGBA image (X, Y, Z in R, G, B)");
+    if (normals->w() != w || normals->h() != h) return mip_refuse(who, "the normal map and the image differ in size");
+    if (channel >= (uint32_t)img->n) return mip_refuse(who, "channel out of range for the image's kind");
+    if (cap < L) return mip_refuse(who, "cap is below the level count");
+    if (!mip_size_ok(w, h)) return mip_refuse(who, "image too large");
+    KC_TRY(image_force(img));  // pending chains and deferred resizes of both run first
+    KC_TRY(image_force(normals));
+    const bool per_level = (flags & KC_MIP_PER_LEVEL) != 0;
+    const kc_plane *src0[4] = { normals->planes[0], normals->planes[1], normals->planes[2], img->planes[channel] };
+    // flat normals leave d = r everywhere: the plain chain of img, nothing new launched
+    if (src0[0]->kind == kc_plane::CONST && src0[1]->kind == kc_plane::CONST && src0[2]->kind == kc_plane::CONST)
+        return image_build_mips(img, flags, levels, cap, count);
+    const int n = img->n;
+    MipSlots sl;  // the planes the plain rule reduces: every channel but the named one
+    for (int ch = 0; ch < n; ++ch)
+        if ((uint32_t)ch != channel) sl.add(ch, img->planes[ch]);
+    MipChain mc;
+    mc.planes.reserve((size_t)(L - 1) * n);
+    std::vector<kc_plane *> slot_planes((size_t)(L - 1) * 4, nullptr);  // [level - 1][slot], owned through mc.planes
+    std::vector<kc_plane *> rough_planes(L - 1, nullptr);                // [level - 1], likewise: the named channel's own planes
+    float cv[4] = { 0.0f, 0.0f, 0.0f, 0.0f };
+    for (int ch = 0; ch < n; ++ch) cv[ch] = img->planes[ch]->cval;
+    for (uint32_t k = 1; k < L; ++k) {
+        const uint32_t W = level_extent(w, k), H = level_extent(h, k);
+        for (int ch = 0; ch < n; ++ch) {
+            const int s = sl.slot_of[ch];
+            kc_plane *p = nullptr;
+            if ((uint32_t)ch == channel) {
+                KC_TRY(plane_new_mem(W, H, &p));
+                rough_planes[k - 1] = p;
+            } else if (s < 0) {
+                cv[ch] = mip_const_fold(cv[ch]);
+                p = plane_new_const(W, H, cv[ch]);
+            } else if (slot_planes[(size_t)(k - 1) * 4 + s]) {
+                p = slot_planes[(size_t)(k - 1) * 4 + s];
+                plane_retain(p);
+            } else {
+                KC_TRY(plane_new_mem(W, H, &p));
+                slot_planes[(size_t)(k - 1) * 4 + s] = p;
+            }
+            mc.planes.push_back(p);
+        }
+    }
+    KC_TRY(mip_launch_roughness(c, src0, rough_planes, mc, power, w, h, L, per_level));
+    KC_TRY(mip_launch_plain(c, sl, slot_planes, w, h, L, per_level));
     image_retain(img);
     levels[0] = img;
     for (uint32_t k = 1; k < L; ++k) levels[k] = image_new(n, mc.planes.data() + (size_t)(k - 1) * n);  // retains; mc drops its own
@@ -520,26 +723,73 @@ int bc_mip_layout(uint32_t w, uint32_t h, int format, uint32_t *levels, size_t *
     return KC_OK;
 }
 
-// The chain of `img` (forced by image_build_mips) as blocks at dst, level k at its kc_bc_mip_layout offset; on the library's stream
-static int bc_mips_encode(kc_image *img, int format, uint32_t flags, char *dst)
+// The first `count` levels of a chain (forced) as blocks at dst, level k at its kc_bc_mip_layout offset; on the library's stream
+static int bc_levels_encode(kc_image *const *lv, uint32_t count, int format, uint32_t flags, char *dst)
 {
     Context &c = ctx();
+    const BcFormat &f = *bc_format(format);  // the entry points have refused an unknown format
+    size_t at = 0;
+    int s = KC_OK;
+    for (uint32_t k = 0; k < count && s == KC_OK; ++k) {
+        const uint32_t W = lv[k]->w(), H = lv[k]->h();
+        s = bc_encode(lv[k], format, (flags & KC_BC_SRGB) != 0, dst + at, (((size_t)W + 3) / 4) * f.block_bytes, c.stream);
+        at += bc_level_bytes(W, H, f);
+    }
+    return s;
+}
+
+// The chain of `img` (forced by image_build_mips) as blocks at dst
+static int bc_mips_encode(kc_image *img, int format, uint32_t flags, char *dst)
+{
     uint32_t L = 0;
     KC_TRY(mip_level_count(img->w(), img->h(), &L));
     std::vector<kc_image *> lv(L, nullptr);
     uint32_t count = 0;
     KC_TRY(image_build_mips(img, flags & (KC_MIP_PER_LEVEL | KC_MIP_NORMALS | kCoverageFlagBits), lv.data(), L, &count));
-    const BcFormat &f = *bc_format(format);  // the entry points have refused an unknown format
-    size_t at = 0;
-    int s = KC_OK;
-    for (uint32_t k = 0; k < L && s == KC_OK; ++k) {
-        const uint32_t W = lv[k]->w(), H = lv[k]->h();
-        s = bc_encode(lv[k], format, (flags & KC_BC_SRGB) != 0, dst + at, (((size_t)W + 3) / 4) * f.block_bytes, c.stream);
-        at += bc_level_bytes(W, H, f);
-    }
+    const int s = bc_levels_encode(lv.data(), L, format, flags, dst);
     // the level planes go back to the pool here; the pool hands a block out again only to work enqueued on the same stream
     for (kc_image *i : lv) image_release(i);
     return s;
+}
+
+// kc_image_levels_to_bc_mips / kc_image_levels_write_dds: the checks of a chain the caller holds; *total = the bytes of its
+// `count` levels.  The flags, the arguments, need_init(), then the levels themselves, which are forced.
+static int bc_levels_check(kc_image *const *levels, uint32_t count, int format, uint32_t flags, const void *out, const char *who, size_t *total)
+{
+    KC_TRY(bc_check_flags(format, flags, KC_BC_SRGB, who));
+    const BcFormat *f = bc_format(format);
+    if (!f) return mip_refuse(who, "unknown format");
+    if (!levels || !out || count == 0) return mip_refuse(who, "NULL level array or output, or no level");
+    KC_TRY(need_init());
+    if (!levels[0]) return mip_refuse(who, "a NULL level");
+    const uint32_t w = levels[0]->w(), h = levels[0]->h();
+    if (count > 1u + floor_log2(w > h ? w : h)) return mip_refuse(who, "more levels than the chain of level 0's size has");
+    uint64_t bx = 0, by = 0;
+    KC_TRY(bc_block_count(w, h, who, &bx, &by));
+    *total = 0;
+    for (uint32_t k = 0; k < count; ++k) {
+        if (!levels[k] || levels[k]->n != levels[0]->n || levels[k]->w() != level_extent(w, k) || levels[k]->h() != level_extent(h, k))
+            return mip_refuse(who, "every level must be an image of level 0's kind, max(1, w >> k) by max(1, h >> k)");
+        *total += bc_level_bytes(level_extent(w, k), level_extent(h, k), *f);
+    }
+    for (uint32_t k = 0; k < count; ++k) KC_TRY(image_force(levels[k]));
+    return KC_OK;
+}
+
+int image_levels_to_bc_mips(kc_image *const *levels, uint32_t count, int format, uint32_t flags, uint8_t *host, size_t host_bytes, const char *who)
+{
+    Context &c = ctx();
+    std::lock_guard<std::recursive_mutex> lk(c.mu);
+    size_t total = 0;
+    KC_TRY(bc_levels_check(levels, count, format, flags, host, who, &total));
+    if (host_bytes < total) return mip_refuse(who, "host_bytes is below the levels' bytes");
+    PoolStaging staging;
+    KC_TRY(staging.alloc(total));
+    KC_TRY(bc_levels_encode(levels, count, format, flags, (char *)staging.ptr));
+    hipError_t e = hipMemcpyAsync(host, staging.ptr, total, hipMemcpyDeviceToHost, c.stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(c.stream);
+    if (e != hipSuccess) return hip_fail(e, who);
+    return KC_OK;
 }
 
 int image_to_bc_mips(kc_image *img, int format, uint32_t flags, uint8_t *host, size_t host_bytes)
@@ -618,6 +868,21 @@ int dds_header(uint32_t w, uint32_t h, int format, uint32_t flags, uint32_t leve
     return KC_OK;
 }
 
+static int dds_write_file(const char *path, const std::vector<uint8_t> &file, const char *who)
+{
+    FILE *f = std::fopen(path, "wb");
+    if (!f) {
+        set_error(std::string(who) + ": cannot open " + path);
+        return KC_ERR_IO;
+    }
+    const bool ok = std::fwrite(file.data(), 1, file.size(), f) == file.size();
+    if (std::fclose(f) != 0 || !ok) {
+        set_error(std::string(who) + ": cannot write " + path);
+        return KC_ERR_IO;
+    }
+    return KC_OK;
+}
+
 int image_write_dds(kc_image *img, const char *path, int format, uint32_t flags, int with_mips)
 {
     KC_TRY(bc_mips_check_flags(format, flags, "kc_image_write_dds"));
@@ -636,17 +901,20 @@ int image_write_dds(kc_image *img, const char *path, int format, uint32_t flags,
     KC_TRY(dds_header(w, h, format, flags & KC_BC_SRGB, L, file.data(), nullptr));
     if (with_mips) KC_TRY(image_to_bc_mips(img, format, flags, file.data() + 148, total));
     else KC_TRY(image_to_bc(img, format, flags & KC_BC_SRGB, file.data() + 148, total));
-    FILE *f = std::fopen(path, "wb");
-    if (!f) {
-        set_error(std::string("kc_image_write_dds: cannot open ") + path);
-        return KC_ERR_IO;
-    }
-    const bool ok = std::fwrite(file.data(), 1, file.size(), f) == file.size();
-    if (std::fclose(f) != 0 || !ok) {
-        set_error(std::string("kc_image_write_dds: cannot write ") + path);
-        return KC_ERR_IO;
-    }
-    return KC_OK;
+    return dds_write_file(path, file, "kc_image_write_dds");
+}
+
+int image_levels_write_dds(kc_image *const *levels, uint32_t count, const char *path, int format, uint32_t flags)
+{
+    const char *who = "kc_image_levels_write_dds";
+    Context &c = ctx();
+    std::lock_guard<std::recursive_mutex> lk(c.mu);
+    size_t total = 0;
+    KC_TRY(bc_levels_check(levels, count, format, flags, path, who, &total));
+    std::vector<uint8_t> file(148 + total);
+    KC_TRY(dds_header(levels[0]->w(), levels[0]->h(), format, flags, count, file.data(), nullptr));
+    KC_TRY(image_levels_to_bc_mips(levels, count, format, flags, file.data() + 148, total, who));
+    return dds_write_file(path, file, who);
 }
 
 }  // namespace kc

@@ -1,8 +1,10 @@
-// The one copy of the mip steps that mip.hip, mip_normals.hip and preview.hip share: the box, the reduction of a 64 x 64 tile by
-// a 16 x 16 workgroup, the tile's loads and stores, the one-level step, where a channel of a normal map comes from, and the two
-// launch checks.  C channels (1 or 3) go down together; a unit supplies its rule, rule(float (&b)[C]), called with the C boxes of
-// one texel before they are stored or passed on (nothing for the plain chain and the previews, normal_texel for normal maps), and
-// says what happens to a finished level.  The fused form equals the level-by-level one, a preview equals to_u8 of the chain and a
+// The one copy of the mip steps that mip.hip, mip_normals.hip, mip_roughness.hip and preview.hip share: the box, the reduction of
+// a 64 x 64 tile by a 16 x 16 workgroup, the tile's loads and stores, the one-level step, where a channel of a normal map comes
+// from, and the two launch checks.  C channels (1, 3, or the 4 of a roughness chain: the normals' vector and the roughness) go
+// down together; a unit supplies its rule, rule(float (&b)[C]), called with the C boxes of one texel before they are stored or
+// passed on (nothing for the plain chain, the previews and the roughness chain's state, normal_texel for normal maps), and says
+// what happens to a finished level: the tile walk's `done`, the one-level walk's `sink` -- a roughness chain stores one plane
+// that is none of the four it passes on.  The fused form equals the level-by-level one, a preview equals to_u8 of the chain and a
 // normal map's alpha equals the plain rule because all of them run these additions in this order;
 // tests/host/preview_walk_check.cpp keeps a copy of its own (lanes_reduce): the host's check stays independent of this header.
 // Included inside namespace kc after streaming.h; every definition is static, each unit keeps its own copy.
@@ -17,6 +19,12 @@ struct MipRows {  // a thread's 4 x 4 texels of one channel of the tile
 static __device__ __forceinline__ float mip_box(float a, float b, float c, float d) { return ((a + b) + (c + d)) * 0.25f; }
 
 static __device__ __forceinline__ mip_f4 mip_splat(float v) { return mip_f4{ v, v, v, v }; }
+
+// What the one-level walk stores: a whole quad under the launch's cache policy, a texel of a row's tail plainly.
+template <bool NT>
+static __device__ __forceinline__ void mip_level_store(float *p, mip_f4 v) { st_policy<NT>(reinterpret_cast<mip_f4 *>(p), v); }
+template <bool NT>
+static __device__ __forceinline__ void mip_level_store(float *p, float v) { *p = v; }
 
 // The plain rule: the boxes are the texel.
 struct MipPlainRule {
@@ -184,12 +192,59 @@ static __device__ __forceinline__ void mip_tile_store(uint32_t k, const float (&
 }
 
 // ---------------------------------------------------------------- one level of any size, with the clamps
+// The four source texels under one output texel (T = float: the scalar tail) or the 2 x 8 under a quad of them (T = mip_f4: t0,
+// t1 the upper row's columns 0 .. 3 and 4 .. 7, b0, b1 the lower row's), of one channel, as loaded.
+template <class T>
+struct MipSrc {
+    T t0, t1, b0, b1;
+};
+static __device__ __forceinline__ MipSrc<float> mip_src_const(float cv, const float &) { return MipSrc<float>{ cv, cv, cv, cv }; }
+static __device__ __forceinline__ MipSrc<mip_f4> mip_src_const(float cv, const mip_f4 &)
+{
+    return MipSrc<mip_f4>{ mip_splat(cv), mip_splat(cv), mip_splat(cv), mip_splat(cv) };
+}
+static __device__ __forceinline__ float mip_src_box(const MipSrc<float> &s) { return mip_box(s.t0, s.t1, s.b0, s.b1); }
+static __device__ __forceinline__ mip_f4 mip_src_box(const MipSrc<mip_f4> &s)
+{
+    return mip_f4{ mip_box(s.t0[0], s.t0[1], s.b0[0], s.b0[1]), mip_box(s.t0[2], s.t0[3], s.b0[2], s.b0[3]),
+                   mip_box(s.t1[0], s.t1[1], s.b1[0], s.b1[1]), mip_box(s.t1[2], s.t1[3], s.b1[2], s.b1[3]) };
+}
+// Nothing happens to the source texels before the box (every unit but mip_roughness.hip's first launch).
+struct MipNoDecode {
+    static constexpr bool kNone = true;
+};
+
+// The C boxes of one output position (T = mip_f4: a quad of texels; float: one): fetch(c, s) loads the source texels of channel
+// c, channels(v, of_const, load) says where the channels come from (MipOwnPlanes, normal_channels).  Without a decode every
+// channel is boxed as it arrives.  A decode (kNone == false; decode(s) on MipSrc<T> (&s)[C]) couples the channels before the
+// box, so the source texels of all C are held first.
+template <int C, class T, class Channels, class Decode, class Fetch>
+static __device__ __forceinline__ void mip_level_boxes(T (&b)[C], Channels channels, Decode decode, Fetch fetch)
+{
+    if constexpr (Decode::kNone) {
+        channels(
+            b, [](float cv, T &o) __attribute__((always_inline)) { o = mip_src_box(mip_src_const(cv, o)); },
+            [&](int c, T &o) __attribute__((always_inline)) {
+                MipSrc<T> s;
+                fetch(c, s);
+                o = mip_src_box(s);
+            });
+    } else {
+        MipSrc<T> s[C];
+        channels(s, [](float cv, MipSrc<T> &o) __attribute__((always_inline)) { o = mip_src_const(cv, o.t0); }, fetch);
+        decode(s);
+#pragma unroll
+        for (int c = 0; c < C; ++c) b[c] = mip_src_box(s[c]);
+    }
+}
+
 // One thread per quad of output texels, rows in order.  A whole quad (4 q + 3 < W, hence source columns up to 8 q + 7 <= w - 1)
-// is two 16-byte loads per source row and channel and one 16-byte store per channel; the tail of a row is scalar, with the
-// column clamp.  channels(v, of_const, load) says where the channels come from (MipOwnPlanes, normal_channels).
-template <bool NT, int C, class Rule, class Channels>
-static __device__ __forceinline__ void mip_level_step(const float *const *src, const uint32_t *src_pitch, uint32_t w, uint32_t h, float *const *dst,
-                                                      uint32_t dst_pitch, Rule rule, Channels channels)
+// is two 16-byte loads per source row and channel and one 16-byte value per channel; the tail of a row is scalar, with the
+// column clamp.  channels and decode: mip_level_boxes; rule(v) is applied to the C boxes of every texel, and sink(o, v) takes
+// them: a quad (v: mip_f4[C]) or one texel (v: float[C]) that starts o floats into a plane whose rows are dst_pitch floats apart.
+template <bool NT, int C, class Channels, class Decode, class Rule, class Sink>
+static __device__ __forceinline__ void mip_level_walk(const float *const *src, const uint32_t *src_pitch, uint32_t w, uint32_t h, uint32_t dst_pitch,
+                                                      Channels channels, Decode decode, Rule rule, Sink sink)
 {
     const uint32_t W = max(w >> 1, 1u), H = max(h >> 1, 1u), quads = (W + 3u) / 4u;
     const uint32_t idx = blockIdx.x * 256u + threadIdx.x;
@@ -199,17 +254,13 @@ static __device__ __forceinline__ void mip_level_step(const float *const *src, c
     const size_t o = (size_t)y * dst_pitch + 4u * q;
     if (4u * q + 3u < W) {
         mip_f4 b[C];
-        channels(
-            b, [](float cv, mip_f4 &o) __attribute__((always_inline)) { o = mip_splat(mip_box(cv, cv, cv, cv)); },
-            [&](int c, mip_f4 &o) __attribute__((always_inline)) {
-                const float *r0 = src[c] + (size_t)y0 * src_pitch[c], *r1 = src[c] + (size_t)y1 * src_pitch[c];
-                const mip_f4 t0 = ld_policy<NT>(reinterpret_cast<const mip_f4 *>(r0 + 8u * q));
-                const mip_f4 t1 = ld_policy<NT>(reinterpret_cast<const mip_f4 *>(r0 + 8u * q + 4u));
-                const mip_f4 b0 = ld_policy<NT>(reinterpret_cast<const mip_f4 *>(r1 + 8u * q));
-                const mip_f4 b1 = ld_policy<NT>(reinterpret_cast<const mip_f4 *>(r1 + 8u * q + 4u));
-                o = mip_f4{ mip_box(t0[0], t0[1], b0[0], b0[1]), mip_box(t0[2], t0[3], b0[2], b0[3]),
-                               mip_box(t1[0], t1[1], b1[0], b1[1]), mip_box(t1[2], t1[3], b1[2], b1[3]) };
-            });
+        mip_level_boxes(b, channels, decode, [&](int c, MipSrc<mip_f4> &s) __attribute__((always_inline)) {
+            const float *r0 = src[c] + (size_t)y0 * src_pitch[c], *r1 = src[c] + (size_t)y1 * src_pitch[c];
+            s.t0 = ld_policy<NT>(reinterpret_cast<const mip_f4 *>(r0 + 8u * q));
+            s.t1 = ld_policy<NT>(reinterpret_cast<const mip_f4 *>(r0 + 8u * q + 4u));
+            s.b0 = ld_policy<NT>(reinterpret_cast<const mip_f4 *>(r1 + 8u * q));
+            s.b1 = ld_policy<NT>(reinterpret_cast<const mip_f4 *>(r1 + 8u * q + 4u));
+        });
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
             float v[C];
@@ -219,23 +270,30 @@ static __device__ __forceinline__ void mip_level_step(const float *const *src, c
 #pragma unroll
             for (int c = 0; c < C; ++c) b[c][j] = v[c];
         }
-#pragma unroll
-        for (int c = 0; c < C; ++c) st_policy<NT>(reinterpret_cast<mip_f4 *>(dst[c] + o), b[c]);
+        sink(o, b);
         return;
     }
     for (uint32_t x = 4u * q; x < W; ++x) {
         const uint32_t x0 = 2u * x, x1 = min(2u * x + 1u, w - 1u);
         float v[C];
-        channels(
-            v, [](float cv, float &o) __attribute__((always_inline)) { o = mip_box(cv, cv, cv, cv); },
-            [&](int c, float &o) __attribute__((always_inline)) {
-                const float *r0 = src[c] + (size_t)y0 * src_pitch[c], *r1 = src[c] + (size_t)y1 * src_pitch[c];
-                o = mip_box(r0[x0], r0[x1], r1[x0], r1[x1]);
-            });
+        mip_level_boxes(v, channels, decode, [&](int c, MipSrc<float> &s) __attribute__((always_inline)) {
+            const float *r0 = src[c] + (size_t)y0 * src_pitch[c], *r1 = src[c] + (size_t)y1 * src_pitch[c];
+            s = MipSrc<float>{ r0[x0], r0[x1], r1[x0], r1[x1] };
+        });
         rule(v);
-#pragma unroll
-        for (int c = 0; c < C; ++c) dst[c][o + (x - 4u * q)] = v[c];
+        sink(o + (x - 4u * q), v);
     }
+}
+
+// The walk for the units that store what the rule leaves: channel c of the level goes to dst[c].
+template <bool NT, int C, class Rule, class Channels>
+static __device__ __forceinline__ void mip_level_step(const float *const *src, const uint32_t *src_pitch, uint32_t w, uint32_t h, float *const *dst,
+                                                      uint32_t dst_pitch, Rule rule, Channels channels)
+{
+    mip_level_walk<NT, C>(src, src_pitch, w, h, dst_pitch, channels, MipNoDecode(), rule, [&](size_t o, const auto (&v)[C]) __attribute__((always_inline)) {
+#pragma unroll
+        for (int c = 0; c < C; ++c) mip_level_store<NT>(dst[c] + o, v[c]);
+    });
 }
 
 // ---------------------------------------------------------------- the launch checks (host)
