@@ -208,8 +208,9 @@ KC_API int kc_stats_algorithmic_bytes(uint64_t *bytes);
  * "specialized_nt_<3 hex digits>" (a kernel compiled at run time and its cache-policy bits: 0x001 << k input plane k < 8,
  * 0x100 the result), "specialized_nt_<3 hex digits>_q2" / "_q4" when that kernel handles 2 / 4 float4 per lane instead of one
  * (kc_set_chain_quads).  The mip kernels (one per launch): "mip_pyramid", "mip_level", under KC_MIP_NORMALS "mip_normals_pyramid",
- * "mip_normals_level" for R, G, B, "mip_nt" for each of those launches that reads its source nontemporally, and "mip_coverage" for
- * the launches KC_MIP_COVERAGE adds.  The streaming kernels, by the form each launch took: HeightToNormal "h2n_launches", one
+ * "mip_normals_level" for R, G, B, "mip_nt" for each of those launches that reads its source nontemporally, "mip_coverage" for
+ * the launches KC_MIP_COVERAGE adds, and under KC_MIP_ALPHA_WEIGHT "mip_alpha_pull_pyramid", "mip_alpha_pull_level" and
+ * "mip_alpha_push".  The streaming kernels, by the form each launch took: HeightToNormal "h2n_launches", one
  * of "h2n_plain", "h2n_tiled_q5", "h2n_tiled_q6", "h2n_tiled_q7" (a row per 256 threads, or tiles of 32, 64, 128 column
  * quads), "h2n_band" (a row band with its halo row), "h2n_nt" (nontemporal stores); the u8 boundary "to_u8_nt", "from_u8_nt"
  * (kc_image_to_u8 / _from_u8 and the u8 pipe); device images "image_import_vec" or "image_import_scalar" and
@@ -589,6 +590,60 @@ KC_API int kc_image_to_bc_device(kc_image *img, const kc_bc_image *dst, uint32_t
  *             them), and 4 N_0 + 20 sum_{k >= 1} N_k algorithmic bytes:
  *             level 0's alpha read once, every further level once per pass and once for the scale, and written once.  The
  *             scratch comes from the pool and goes back to it; the call still does not wait.
+ *   Alpha-weighted colour (KC_MIP_ALPHA_WEIGHT).  The plain rule boxes R, G, B without regard to alpha, so whatever colour lies
+ *             under the transparent texels of a cutout (black, magenta, what the graph left there) is averaged into the edge
+ *             texels of every coarser level: a halo that grows with distance, and at level 0 block endpoints and bilinear taps
+ *             spent on a colour nobody should see.  With the flag the colour of every level is the alpha-weighted average of
+ *             the texels under it, and the texels that have none are filled from the coarser levels (pull-push;
+ *             tests/mip_alpha_ref.py is the same rule in numpy).  Everything is f32, nothing is fused, denormals are kept, / is
+ *             the correctly rounded divide.  Inputs: an RGBA image, colour c = (R, G, B), alpha a.
+ *               Weight.   w0 = a > 0 ? min(a, 1.0f) : 0.0f                                  (kc_mip_alpha_weight)
+ *                         The comparison is false for NaN: NaN, -0.0 and negatives give +0.0.
+ *               Premultiplied level 0.  p_c = w0 > 0 ? c * w0 : 0.0f: a select, not a product, so a NaN or an infinity under a
+ *                         transparent texel never enters.
+ *               Pull.     P_c,k and W_k are the plain rule's chains of p_c and w0 (the box above, the same order and clamps, every
+ *                         level rounded to f32 before the next is made, so the fused form and KC_MIP_PER_LEVEL give the same
+ *                         bits).  A texel of level k >= 1 is known when W_k > 0, and its colour is then q_c = P_c,k / W_k
+ *                         (kc_mip_alpha_texel, which also reports known or unknown; unknown: q = 0).  A texel of level 0 is known
+ *                         when w0 > 0, and its colour is c itself, bit for bit.  A known texel with a NaN or infinite colour
+ *                         follows IEEE; NaN payloads are not in the contract.
+ *               Push.     F_k(x, y), the stored colour: q where the texel is known; otherwise
+ *                         F_{k+1}(min(x >> 1, W - 1), min(y >> 1, H - 1)) with W x H the size of level k + 1; an unknown texel of
+ *                         the last level stores +0.0 in all three channels.  Equivalently a texel takes the q of its nearest known
+ *                         ancestor (min(x >> (j - k), W_j - 1), min(y >> (j - k), H_j - 1)), j > k, or 0.0 if it has none; the
+ *                         per-texel form has no ordering between levels, and it is what the device runs.
+ *               Alpha     is not touched: the plain rule, or coverage's with KC_MIP_COVERAGE (the two combine: coverage rewrites
+ *                         alpha and never looks at colour, this rule rewrites colour and reads only level 0's alpha).
+ *             Consequences: a constant alpha of 1 gives the plain chain bit for bit (c * 1 = c, box(1) = 1, P / 1 = P); an image
+ *             without a positive alpha gets zero colour everywhere; a known texel's colour lies in the hull of the known
+ *             level-0 colours under it, up to rounding; on odd extents the box drops the last column or row, so an opaque texel
+ *             there has no known ancestor above it.
+ *             Levels: under the flag levels[0] is an image of its own (+1 reference as before): its R, G, B are new planes --
+ *             the known texels copied, the unknown ones filled -- and its alpha is img's plane, shared; every level >= 1 gets
+ *             new colour planes.  Constants: a constant alpha >= 1 makes the call the plain chain of the image (levels[0] is
+ *             img itself, nothing new is launched); a constant alpha of weight 0 gives constant-zero colour planes at every
+ *             level and launches nothing new; constant or aliased colour planes beside a resident alpha, and a constant alpha
+ *             strictly between 0 and 1, go through the kernels (a constant channel is a value in the launch's arguments, aliased
+ *             ones are loaded once each from memory); four constant planes are folded on the host through kc_mip_alpha_texel.
+ *             The flag is for RGBA images: a Gray image is KC_ERR_INVALID_ARG exactly where KC_MIP_COVERAGE refuses it.  With
+ *             KC_MIP_NORMALS it is KC_ERR_UNSUPPORTED (a vector is not a colour), refused with the other flag errors.  It
+ *             combines with KC_MIP_COVERAGE_REF(B), KC_MIP_PER_LEVEL and KC_BC_SRGB.  Accepted by the entry points that accept
+ *             KC_MIP_COVERAGE (kc_image_write_dds without mips: no effect); kc_dds_header, kc_image_build_roughness_mips and
+ *             kc_image_mip_coverage_info refuse it, and previews stay defined by the plain rule.
+ *             kc_stats: the four channels p_r, p_g, p_b, w go down together in one thread, so the pull takes the launches of
+ *             the plain chain of one plane (4096 x 4096: two; counters "mip_alpha_pull_pyramid", "mip_alpha_pull_level"; the
+ *             first launch also stores level 0's colour); the push is one launch over all levels ("mip_alpha_push") and runs
+ *             whenever the pull does; a 1 x 1 image takes one "mip_alpha_pull_level" launch that only writes level 0, and the
+ *             push.  A resident alpha keeps its plain launches.  Algorithmic bytes, with N_k = W_k H_k: 4 N_0 per distinct
+ *             resident plane read by the pull, 12 N_0 for level 0's colour, 16 N_k for the three colours and the weight of every
+ *             level k >= 1 (the weights live in scratch planes from the pool, returned when the call returns), 28 N_k for every
+ *             level whose P and W are handed to a further launch (three state planes written and read, the weight read), and
+ *             for the push 4 N_0 where alpha is resident plus 4 N_k for every k >= 1 -- 38.7 bytes per level-0 texel of an
+ *             image of four resident planes, 44.0 with alpha's plain chain; the unknown texels the push writes (12 bytes each,
+ *             with the ancestors' colours they read) depend on the data and are not counted.
+ *   kc_mip_alpha_weight, kc_mip_alpha_texel  w0 of an alpha, and q = P / W with known = 1 where W > 0, q = 0 with known = 0
+ *                        elsewhere: arithmetic, no kc_init needed; the constant fold calls them.  A NULL argument is
+ *                        KC_ERR_INVALID_ARG.
  *   Roughness chains (kc_image_build_roughness_mips).  Renormalising a coarser level of a normal map throws away the length of
  *             the averaged vector, the only record of how much the normals varied under the texel: beside a plain-boxed
  *             roughness chain, bumpy surfaces turn mirror-smooth with distance and sparkle.  This chain raises every level of a
@@ -665,7 +720,7 @@ KC_API int kc_image_to_bc_device(kc_image *img, const kc_bc_image *dst, uint32_t
  *                        `*count` = L whenever the image is known; cap < L is KC_ERR_INVALID_ARG with nothing launched and nothing
  *                        allocated.  Enqueued on the library's stream; the call does not wait.  A failure part-way releases what
  *                        it made.  KC_MIP_PER_LEVEL: one launch per level (A/B runs and tests; the same bits).  KC_MIP_NORMALS,
- *                        KC_MIP_COVERAGE: above.
+ *                        KC_MIP_COVERAGE, KC_MIP_ALPHA_WEIGHT: above.
  *                        kc_stats: one launch per up to six levels while both extents still halve, one per level after that
  *                        (4096 x 4096: two; counters "mip_pyramid", "mip_level"); 4 w h algorithmic bytes per distinct resident
  *                        plane read plus 4 sum_{k >= 1} W_k H_k per plane written; constant planes launch nothing.
@@ -675,7 +730,7 @@ KC_API int kc_image_to_bc_device(kc_image *img, const kc_bc_image *dst, uint32_t
  *                        NULL; otherwise cap < L is KC_ERR_INVALID_ARG), `*total_bytes` = the chain's bytes.  Arithmetic, no kc_init.
  *   kc_image_to_bc_mips  kc_image_build_mips, then the encoder of kc_image_to_bc once per level, into host memory (`host_bytes`
  *                        at least the total); blocks until the bytes are there.  flags: KC_BC_SRGB (BC1 / BC3 / BC7) | KC_MIP_PER_LEVEL |
- *                        KC_MIP_NORMALS | KC_MIP_COVERAGE_REF(B).
+ *                        KC_MIP_NORMALS | KC_MIP_COVERAGE_REF(B) | KC_MIP_ALPHA_WEIGHT.
  *                        KC_BC6H quantises every level's own f32 values, so the chain keeps the range of the planes.
  *   kc_image_to_bc_mips_device  the same into device memory (a multiple of the block bytes; `bytes` at least the total, the
  *                        total's extent in one allocation of the library's device), ordered against `hip_stream` by the two event
@@ -688,8 +743,8 @@ KC_API int kc_image_to_bc_device(kc_image *img, const kc_bc_image *dst, uint32_t
  *                        BC5 83, BC6H 95, BC7 98, with KC_BC_SRGB BC1 72, BC3 78, BC7 99.  1 <= levels <= L.  `*bytes` (optional) = 148.
  *                        No kc_init.
  *   kc_image_write_dds   the header, then the chain (with_mips != 0) or level 0 alone.
- * Errors, in this order: unknown flag bits, KC_BC_SRGB with BC4 / BC5 / BC6H, KC_MIP_NORMALS with KC_BC_SRGB, or a reference byte
- * without KC_MIP_COVERAGE or the reverse, KC_ERR_UNSUPPORTED; a NULL argument, a zero size, an
+ * Errors, in this order: unknown flag bits, KC_BC_SRGB with BC4 / BC5 / BC6H, KC_MIP_NORMALS with KC_BC_SRGB or with
+ * KC_MIP_ALPHA_WEIGHT, or a reference byte without KC_MIP_COVERAGE or the reverse, KC_ERR_UNSUPPORTED; a NULL argument, a zero size, an
  * unknown format, a size below the total KC_ERR_INVALID_ARG; KC_ERR_NO_DEVICE before kc_init; KC_ERR_NO_SLOT_DATA where
  * kc_live_graph_buffer_bc returns it; KC_ERR_IO for a file that cannot be written. */
 #define KC_MIP_PER_LEVEL 2u  /* one launch of the one-level kernel per level instead of the fused pyramid kernel; a bit of its
@@ -698,6 +753,7 @@ KC_API int kc_image_to_bc_device(kc_image *img, const kc_bc_image *dst, uint32_t
                                 stay refused by the chain entry points, 16 is KC_BC_ALL_MODES */
 #define KC_MIP_COVERAGE 64u  /* alpha is tested against the byte in bits 24-31: every level keeps level 0's coverage (above) */
 #define KC_MIP_COVERAGE_REF(b) (64u | ((uint32_t)(b) << 24))  /* KC_MIP_COVERAGE with the reference byte b, 1..255 */
+#define KC_MIP_ALPHA_WEIGHT 128u  /* R, G, B of every level are alpha-weighted and the empty texels filled from the coarser levels (above) */
 typedef struct kc_mip_coverage_level {
     uint64_t texels, target, plain_covered;  /* N_k, T_k, P_k (level 0: C_0 in both counts) */
     float v, scale;                          /* v_k (0 where nothing was selected) and s_k */
@@ -769,6 +825,8 @@ KC_API int kc_alpha_ref_threshold(uint32_t ref_u8, float *r);
 KC_API int kc_mip_coverage_target(uint32_t width, uint32_t height, uint64_t covered0, uint32_t level, uint64_t *target);
 KC_API int kc_mip_coverage_scale(float v, uint32_t ref_u8, float *s);
 KC_API int kc_image_mip_coverage_info(kc_image *img, uint32_t flags, kc_mip_coverage_level *out, uint32_t cap, uint32_t *count);
+KC_API int kc_mip_alpha_weight(float a, float *w);
+KC_API int kc_mip_alpha_texel(const float p[3], float w, float q[3], int *known);
 KC_API int kc_image_build_mips(kc_image *img, uint32_t flags, kc_image **levels, uint32_t cap, uint32_t *count);
 KC_API int kc_bc_mip_layout(uint32_t width, uint32_t height, int format, uint32_t *levels, size_t *offsets, uint32_t cap,
                             size_t *total_bytes);

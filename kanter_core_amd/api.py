@@ -714,9 +714,32 @@ def mip_coverage_ref(ref):
     return MIP_COVERAGE | ref << 24
 
 
-def _mip_flags(srgb, per_level, normals, coverage=None):
+MIP_ALPHA_WEIGHT = _abi.KC_MIP_ALPHA_WEIGHT  # ... R, G, B of every level are alpha-weighted, the empty texels filled from the coarser levels
+
+
+def _mip_flags(srgb, per_level, normals, coverage=None, alpha_weighted=False):
     return ((BC_SRGB if srgb else 0) | (MIP_PER_LEVEL if per_level else 0) | (MIP_NORMALS if normals else 0)
-            | (mip_coverage_ref(coverage) if coverage is not None else 0))
+            | (mip_coverage_ref(coverage) if coverage is not None else 0) | (MIP_ALPHA_WEIGHT if alpha_weighted else 0))
+
+
+def mip_alpha_weight(a):
+    """-> np.float32: the weight an alpha-weighted chain (mips(alpha_weighted=True)) gives a level-0 texel of alpha `a`: a clamped
+    to [0, 1], 0 for NaN (kc_mip_alpha_weight; no device)."""
+    w = C.c_float()
+    _check(_lib.load().kc_mip_alpha_weight(C.c_float(float(np.float32(a))), C.byref(w)))
+    return np.float32(w.value)
+
+
+def mip_alpha_texel(p, w):
+    """-> ((3,) float32, bool): the colour a texel of an alpha-weighted chain stores for the boxes `p` of the premultiplied colour
+    and `w` of the weight, p / w, and whether the texel is known (w > 0; an unknown texel gives zeros and is filled from the
+    coarser levels) (kc_mip_alpha_texel; no device)."""
+    v = np.ascontiguousarray(p, np.float32)
+    if v.shape != (3,):
+        raise ValueError("p must hold three values")
+    q, known = np.empty(3, np.float32), C.c_int()
+    _check(_lib.load().kc_mip_alpha_texel(v.ctypes.data, C.c_float(float(np.float32(w))), q.ctypes.data, C.byref(known)))
+    return q, bool(known.value)
 
 
 MipCoverageLevel = collections.namedtuple("MipCoverageLevel", "texels target plain_covered v scale")
@@ -918,7 +941,7 @@ def _bc_mip_views(buf, size, fmt):
     return views
 
 
-def _bc_mips_export(call, size, fmt, srgb, per_level, out, normals=False, coverage=None):
+def _bc_mips_export(call, size, fmt, srgb, per_level, out, normals=False, coverage=None, alpha_weighted=False):
     """Allocates (or takes) a flat uint8 tensor of at least the chain's bytes and runs `call(fmt, flags, ptr, bytes, stream)`."""
     import torch
     f = _bc_format(fmt)
@@ -927,7 +950,7 @@ def _bc_mips_export(call, size, fmt, srgb, per_level, out, normals=False, covera
         out = torch.empty((total,), dtype=torch.uint8, device=torch.device("cuda", torch.cuda.current_device()))
     if out.dtype != torch.uint8 or out.dim() != 1 or not out.is_contiguous() or out.numel() < total:
         raise ValueError("out must be a contiguous 1-D uint8 tensor of at least %d bytes" % total)
-    flags = _mip_flags(srgb, per_level, normals, coverage)
+    flags = _mip_flags(srgb, per_level, normals, coverage, alpha_weighted)
     _check(_on_torch_stream(out, lambda stream: call(f, flags, C.c_void_p(out.data_ptr()), out.numel(), stream)))
     return out, offs
 
@@ -1171,18 +1194,21 @@ class SlotImage:
         whose last two dimensions are contiguous) is written instead of a new tensor.  Ready on torch's current stream."""
         return _bc_export(lambda d, f, st: _lib.load().kc_image_to_bc_device(self._h, d, f, st), self.size(), fmt, srgb, out)
 
-    def mips(self, per_level=False, normals=False, coverage=None):
+    def mips(self, per_level=False, normals=False, coverage=None, alpha_weighted=False):
         """-> the mip chain as a list of SlotImage (kc_image_build_mips): entry 0 is this image, entry k is max(1, w >> k) by
         max(1, h >> k), the 2 x 2 box of the level above it in f32, down to 1 x 1.  per_level=True runs one launch per level
         instead of the fused kernel (the same bits).  normals=True (RGBA only): R, G, B are a normal map stored as n * 0.5 + 0.5 and
         every level is renormalised on the device before the next is made (KC_MIP_NORMALS); alpha follows the plain rule.
         coverage=B (RGBA only, a byte 1..255): alpha is a cutout tested against B, and every level's alpha is rescaled so that the
-        share of texels that pass the test stays what it is at level 0 (KC_MIP_COVERAGE)."""
+        share of texels that pass the test stays what it is at level 0 (KC_MIP_COVERAGE).
+        alpha_weighted=True (RGBA only, not with normals): R, G, B of every level are the alpha-weighted average of the texels
+        under them and the texels without weight are filled from the coarser levels, so the colour under transparent texels
+        never bleeds into a cutout's edge; entry 0 is then an image of its own, with this image's alpha (KC_MIP_ALPHA_WEIGHT)."""
         s = self.size()
         n = mip_level_count(s.width, s.height)
         arr = (C.c_void_p * n)()
         count = C.c_uint32()
-        _check(_lib.load().kc_image_build_mips(self._h, _mip_flags(False, per_level, normals, coverage), arr, n, C.byref(count)))
+        _check(_lib.load().kc_image_build_mips(self._h, _mip_flags(False, per_level, normals, coverage, alpha_weighted), arr, n, C.byref(count)))
         return [SlotImage(arr[k]) for k in range(count.value)]
 
     def roughness_mips(self, normals, channel=0, power=1.0, per_level=False):
@@ -1217,24 +1243,25 @@ class SlotImage:
             raise ValueError("alpha_coverage is for RGBA images")
         return int(self.channel_stats(histogram=True).histogram[3][int(ref):].sum())
 
-    def to_bc_mips(self, fmt, srgb=False, per_level=False, normals=False, coverage=None):
+    def to_bc_mips(self, fmt, srgb=False, per_level=False, normals=False, coverage=None, alpha_weighted=False):
         """-> one uint8 (ceil(H_k/4), ceil(W_k/4), block bytes) array per level, shaped like to_bc's and views of one buffer
         that holds the chain as a texture file stores it (kc_image_to_bc_mips).  normals=True: the chain of a normal map, as mips
-        builds it (BC5 is the usual format; not with srgb).  coverage=B: the chain mips(coverage=B) builds."""
+        builds it (BC5 is the usual format; not with srgb).  coverage=B: the chain mips(coverage=B) builds; alpha_weighted=True: the
+        chain mips(alpha_weighted=True) builds."""
         f = _bc_format(fmt)
         s = self.size()
         offs, total = bc_mip_layout(s.width, s.height, f)
         buf = np.empty((total,), np.uint8)
-        flags = _mip_flags(srgb, per_level, normals, coverage)
+        flags = _mip_flags(srgb, per_level, normals, coverage, alpha_weighted)
         _check(_lib.load().kc_image_to_bc_mips(self._h, f, flags, buf.ctypes.data, buf.nbytes))
         return _bc_mip_views(buf, s, f)
 
-    def to_bc_mips_torch(self, fmt, srgb=False, out=None, per_level=False, normals=False, coverage=None):
+    def to_bc_mips_torch(self, fmt, srgb=False, out=None, per_level=False, normals=False, coverage=None, alpha_weighted=False):
         """-> (flat uint8 tensor in device memory holding the chain, offsets of the levels) (kc_image_to_bc_mips_device); `out`
         (contiguous, 1-D, at least the chain's bytes) is written instead of a new tensor, bytes past the chain are not touched.
         Ready on torch's current stream."""
         return _bc_mips_export(lambda f, fl, p, n, st: _lib.load().kc_image_to_bc_mips_device(self._h, f, fl, p, n, st), self.size(), fmt,
-                               srgb, per_level, out, normals, coverage)
+                               srgb, per_level, out, normals, coverage, alpha_weighted)
 
     def preview(self, max_extent, srgb=False):
         """-> (h, w, 4) uint8: the whole mip level a preview of at most max_extent texels a side is cut from (preview_level), read
@@ -1242,11 +1269,12 @@ class SlotImage:
         s = self.size()
         return previews([(self, preview_level(s.width, s.height, max_extent)[0], None)], srgb)[0]
 
-    def write_dds(self, path, fmt, srgb=False, mips=True, normals=False, coverage=None):
+    def write_dds(self, path, fmt, srgb=False, mips=True, normals=False, coverage=None, alpha_weighted=False):
         """Writes a .dds file (DX10 header) with the image's BC blocks: the whole mip chain, or level 0 alone (kc_image_write_dds).
         normals=True: the chain of a normal map, as to_bc_mips(normals=True); coverage=B: the chain of a cutout, as
-        to_bc_mips(coverage=B) (neither has an effect with mips=False)."""
-        _check(_lib.load().kc_image_write_dds(self._h, os.fspath(path).encode(), _bc_format(fmt), _mip_flags(srgb, False, normals, coverage), int(mips)))
+        to_bc_mips(coverage=B); alpha_weighted=True: the chain of to_bc_mips(alpha_weighted=True) (none has an effect with
+        mips=False)."""
+        _check(_lib.load().kc_image_write_dds(self._h, os.fspath(path).encode(), _bc_format(fmt), _mip_flags(srgb, False, normals, coverage, alpha_weighted), int(mips)))
 
     def bc_error(self, fmt, srgb=False, blocks=None, all_modes=False):
         """-> BcError: how far the image's BC encoding is from the image, measured on the device (kc_image_bc_error): the bytes
@@ -1622,10 +1650,11 @@ class LiveGraph:
         return _bc_export(lambda d, f, st: _lib.load().kc_live_graph_buffer_bc(self._h, node_id, slot_id, d, f, st),
                           self.slot_data_size(node_id, slot_id), fmt, srgb, out)
 
-    def buffer_bc_mips_torch(self, node_id, slot_id, fmt, srgb=False, out=None, per_level=False, normals=False, coverage=None):
+    def buffer_bc_mips_torch(self, node_id, slot_id, fmt, srgb=False, out=None, per_level=False, normals=False, coverage=None,
+                             alpha_weighted=False):
         """SlotImage.to_bc_mips_torch of a slot's image (kc_live_graph_buffer_bc_mips)."""
         return _bc_mips_export(lambda f, fl, p, n, st: _lib.load().kc_live_graph_buffer_bc_mips(self._h, node_id, slot_id, f, fl, p, n, st),
-                               self.slot_data_size(node_id, slot_id), fmt, srgb, per_level, out, normals, coverage)
+                               self.slot_data_size(node_id, slot_id), fmt, srgb, per_level, out, normals, coverage, alpha_weighted)
 
     def buffer_previews(self, items, srgb=False):
         """previews of slots' images (kc_live_graph_buffer_previews): items = [(node_id, slot_id, level, rect or None)] -> one

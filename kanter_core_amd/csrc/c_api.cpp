@@ -923,6 +923,22 @@ try {
 }
 KC_CATCH
 
+int kc_mip_alpha_weight(float a, float *w)
+try {
+    KC_ARG(w);
+    *w = mip_alpha_weight(a);
+    return KC_OK;
+}
+KC_CATCH
+
+int kc_mip_alpha_texel(const float p[3], float w, float q[3], int *known)
+try {
+    KC_ARG(p && q && known);
+    *known = mip_alpha_texel(p, w, q) ? 1 : 0;
+    return KC_OK;
+}
+KC_CATCH
+
 int kc_alpha_ref_threshold(uint32_t ref_u8, float *r)
 try {
     KC_ARG(r && ref_u8 >= 1 && ref_u8 <= 255);
@@ -1705,8 +1721,12 @@ KC_CATCH
 int kc_live_graph_buffer_bc_mips(kc_live_graph *lg, uint32_t node, uint32_t slot, int format, uint32_t flags, void *device_ptr,
                                  size_t bytes, void *hip_stream)
 try {
-    if (flags & ~(uint32_t)(KC_BC_SRGB | KC_MIP_PER_LEVEL | KC_MIP_NORMALS | KC_MIP_COVERAGE | 0xff000000u)) {
+    if (flags & ~(uint32_t)(KC_BC_SRGB | KC_MIP_PER_LEVEL | KC_MIP_NORMALS | KC_MIP_COVERAGE | KC_MIP_ALPHA_WEIGHT | 0xff000000u)) {
         set_error("kc_live_graph_buffer_bc_mips: unknown flag bits");
+        return KC_ERR_UNSUPPORTED;
+    }
+    if ((flags & KC_MIP_NORMALS) && (flags & KC_MIP_ALPHA_WEIGHT)) {
+        set_error("kc_live_graph_buffer_bc_mips: KC_MIP_NORMALS with KC_MIP_ALPHA_WEIGHT");
         return KC_ERR_UNSUPPORTED;
     }
     if ((flags & KC_MIP_NORMALS) && (flags & KC_BC_SRGB)) {

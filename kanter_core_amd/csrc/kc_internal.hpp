@@ -375,8 +375,8 @@ hipError_t launch_bc_modes_compare(int fmt, int srgb, const Operand op[4], int g
                                    hipStream_t s);
 // -- mip.hip --
 // Mip chains (mip.hip / mip.cpp): the 2 x 2 box of the header on the n_planes distinct resident planes of one image.  The device
-// steps of this family, of mip_normals.hip, of mip_roughness.hip and of preview.hip's reduction are one copy, mip_steps.h, with
-// the launch checks of the six launch functions below.
+// steps of this family, of mip_normals.hip, of mip_roughness.hip, of mip_alpha.hip and of preview.hip's reduction are one copy, mip_steps.h, with
+// the launch checks of the eight launch functions below.
 // mip_pyramid_kernel<nt>: levels 1..n (1 <= n <= 6, both of w >> n and h >> n still >= 1) of the w x h source planes, one
 // workgroup per 64 x 64 tile; dst[p][k - 1] is level k of plane p, dst_pitch[k - 1] floats between its rows.
 struct MipPyramidArgs {
@@ -458,6 +458,65 @@ struct RoughnessLevelArgs {
     uint32_t w, h;
 };
 hipError_t launch_roughness_level(const RoughnessLevelArgs &a, bool first, bool nt, hipStream_t s);
+// -- mip_alpha.hip --
+// Alpha-weighted chains (KC_MIP_ALPHA_WEIGHT): the same two walks with four channels coupled in one thread -- the premultiplied
+// colour p_r, p_g, p_b (0..2) and the weight w (3), each down the plain rule -- then one push launch over all levels.  `first`:
+// the sources are level 0, R, G, B and alpha as stored, each a resident plane (src[c], src_pitch[c]; channels that alias carry
+// the same pointer) or the constant cval[c] (bit c of const_mask; src[c] is not looked at); the weight and the premultiplication
+// are applied right after the loads, and the thread stores its level-0 colour texels (c where w0 > 0, else 0) to dst0[c], rows
+// dst0_pitch floats apart.  Otherwise the sources are the three state planes P_r, P_g, P_b and the weight plane of the level
+// read, and const_mask is 0.  Every level k the launch finishes stores W > 0 ? P_c / W : 0 to dst[c][k - 1] and W to
+// wdst[k - 1] (alpha_pull_pyramid_kernel<nt, first>: n, the tiles and the pitches as in MipPyramidArgs; alpha_pull_level_kernel
+// <nt, first>: the one level, as MipLevelArgs).  state: where more levels follow, P_c of the last level written go to these three
+// planes, rows as far apart as that level's dst rows (its W is wdst's plane); all NULL when none follows.  A first one-level
+// launch on a 1 x 1 image has no level to write (dst, wdst NULL): it stores level 0's colour alone.
+struct AlphaPullPyramidArgs {
+    const float *src[4];
+    uint32_t src_pitch[4];  // floats
+    float cval[4];
+    uint32_t const_mask;
+    float *dst0[3];
+    uint32_t dst0_pitch;  // floats
+    float *dst[3][6];
+    float *wdst[6];
+    uint32_t dst_pitch[6];  // floats
+    float *state[3];
+    uint32_t w, h, n;
+};
+hipError_t launch_alpha_pull_pyramid(const AlphaPullPyramidArgs &a, bool first, bool nt, hipStream_t s);
+struct AlphaPullLevelArgs {
+    const float *src[4];
+    uint32_t src_pitch[4];  // floats
+    float cval[4];
+    uint32_t const_mask;
+    float *dst0[3];
+    uint32_t dst0_pitch;  // floats
+    float *dst[3];
+    float *wdst;
+    uint32_t dst_pitch;  // floats
+    float *state[3];
+    uint32_t w, h;
+};
+hipError_t launch_alpha_pull_level(const AlphaPullLevelArgs &a, bool first, bool nt, hipStream_t s);
+// alpha_push_kernel: one thread per quad of every level, level 0 included, through a job table in the launch's arguments (one
+// AlphaPushJob per level, as CoverageJob: nothing is uploaded).  known: level 0's alpha (a > 0), or W_k (> 0) of a level below
+// it; wsrc NULL: every texel of the level is known (a constant alpha of positive weight).  A thread stores, for each unknown
+// texel of its quad, the three colours of the nearest ancestor whose weight is positive; known texels and the weights are
+// never written, so the launch has no race.  Workgroups first_wg .. first_wg + wgs - 1 work on the level.
+constexpr uint32_t KC_ALPHA_MAX_LEVELS = 32;  // a chain has at most 32 levels
+struct AlphaPushJob {
+    float *dst[3];      // the level's colour planes
+    const float *wsrc;  // level 0: the image's alpha; below: the level's weight plane
+    uint32_t dst_pitch, w_pitch;  // floats
+    uint32_t w, h;
+    uint32_t first_wg, wgs;
+};
+struct AlphaPushArgs {
+    AlphaPushJob jobs[KC_ALPHA_MAX_LEVELS + 3];  // three spare entries: level j's kernel code names entries j + 1 .. j + 3
+    uint32_t levels;
+};
+inline uint32_t alpha_push_job_wgs(uint32_t w, uint32_t h) { return (uint32_t)(((uint64_t)((w + 3) / 4) * h + 255) / 256); }
+hipError_t launch_alpha_push(const AlphaPushArgs &a, uint32_t wgs, hipStream_t s);
 // -- mip_coverage.hip --
 // Alpha-test coverage (KC_MIP_COVERAGE): an exact k-th-largest selection over the alpha plane of every level of a chain -- a
 // radix select on the 30 significant bits of the header's key, 10 bits (KC_COVERAGE_BINS bins) per pass -- and the scale of

@@ -457,6 +457,10 @@ void mip_unit_normal(const float rgb[3], float u[3]);
 float mip_roughness_texel(const float m[3], float r, float power);
 int image_build_roughness_mips(kc_image *img, uint32_t channel, kc_image *normals, float power, uint32_t flags, kc_image **levels, uint32_t cap,
                                uint32_t *count);
+// KC_MIP_ALPHA_WEIGHT (mip.cpp): the rule's arithmetic as kc_mip_alpha_weight and kc_mip_alpha_texel return it, as the device
+// computes it (mip_alpha_texel returns known)
+float mip_alpha_weight(float a);
+bool mip_alpha_texel(const float p[3], float w, float q[3]);
 // KC_MIP_COVERAGE (mip.cpp): the rule's arithmetic as kc_alpha_ref_threshold, kc_mip_coverage_target and kc_mip_coverage_scale
 // return it, the flag rule of the chain entry points (bit 64 and the reference byte in bits 24-31 go together), and the body of
 // kc_image_mip_coverage_info

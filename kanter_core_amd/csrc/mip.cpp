@@ -4,7 +4,8 @@
 // folds constant planes with the device's expression, allocates the level planes and enqueues mip.hip's kernels on the library's
 // stream: the pyramid kernel while both extents still halve (up to six levels per launch), the one-level kernel for the rest and
 // for every level under KC_MIP_PER_LEVEL; under KC_MIP_NORMALS mip_normals.hip's two kernels take R, G, B together and
-// renormalise every level; under KC_MIP_COVERAGE mip_coverage.hip's select and scale give alpha planes of their own; a roughness
+// renormalise every level; under KC_MIP_COVERAGE mip_coverage.hip's select and scale give alpha planes of their own; under
+// KC_MIP_ALPHA_WEIGHT mip_alpha.hip's pull and push give colour planes of their own, level 0 included; a roughness
 // chain is mip_roughness.hip's two kernels on the vector of a normal map and the roughness plane together.  The BC chain
 // is bc.cpp's encoder launch once per level; the DDS writer is host code.
 #include <cmath>
@@ -129,6 +130,38 @@ float mip_roughness_texel(const float m[3], float r, float power)
     volatile float h = std::sqrt((float)n);
     volatile float d = std::sqrt((float)h);
     return d;
+}
+
+// ---------------------------------------------------------------- KC_MIP_ALPHA_WEIGHT: the rule's arithmetic
+// w0 of an alpha: the device's expression (mip_alpha.hip, alpha_weight).  This is kc_mip_alpha_weight.
+float mip_alpha_weight(float a)
+{
+    if (!(a > 0.0f)) return 0.0f;  // NaN, -0.0 and negatives
+    return a < 1.0f ? a : 1.0f;
+}
+
+// q = P / W of a texel of a level >= 1, known where W > 0 (false for NaN), q = 0 elsewhere: the device's expression
+// (mip_alpha.hip, alpha_texel), the host's correctly rounded divide through a volatile temporary like mip_const_fold.  This is
+// kc_mip_alpha_texel and what folds an image of four constant planes.
+bool mip_alpha_texel(const float p[3], float w, float q[3])
+{
+    const bool known = w > 0.0f;
+    for (int c = 0; c < 3; ++c) {
+        volatile float n = p[c], d = w;
+        volatile float r = known ? n / d : 0.0f;
+        q[c] = r;
+    }
+    return known;
+}
+
+// the flag's own refusal: a vector is not a colour
+static int mip_check_alpha_flags(uint32_t flags, const char *who)
+{
+    if ((flags & KC_MIP_ALPHA_WEIGHT) && (flags & KC_MIP_NORMALS)) {
+        set_error(std::string(who) + ": KC_MIP_NORMALS with KC_MIP_ALPHA_WEIGHT");
+        return KC_ERR_UNSUPPORTED;
+    }
+    return KC_OK;
 }
 
 // ---------------------------------------------------------------- KC_MIP_COVERAGE: the rule's arithmetic
@@ -416,6 +449,129 @@ static int mip_launch_roughness(Context &c, const kc_plane *const src0[4], const
     return KC_OK;
 }
 
+// KC_MIP_ALPHA_WEIGHT: the pull launches for the premultiplied colour and the weight (src0: R, G, B, alpha at level 0, constant
+// or resident, the colours or alpha resident) and the push launch over all levels; level k's colour planes are col[3 k + c],
+// level 0 included.  The weight of every level >= 1 lives in a scratch plane, and P_c of the last level a launch writes in
+// three state planes that the next launch reads: all from the pool, held in mc.scratch until the call returns (everything
+// that reads them is enqueued by then).
+static int mip_launch_alpha(Context &c, const kc_plane *const src0[4], const std::vector<kc_plane *> &col, MipChain &mc, uint32_t w, uint32_t h,
+                            uint32_t L, bool per_level)
+{
+    const char *who = "kc_image_build_mips";
+    if (L > KC_ALPHA_MAX_LEVELS) return mip_refuse("KC_MIP_ALPHA_WEIGHT", "more levels than the job table holds");
+    MipSlots sl;  // the distinct resident planes of level 0
+    uint32_t const_mask = 0;
+    for (int ch = 0; ch < 4; ++ch) {
+        sl.add(ch, src0[ch]);
+        if (sl.slot_of[ch] < 0) const_mask |= 1u << ch;
+    }
+    auto pitch_of = [](const kc_plane *p) { return (uint32_t)(p->pitch / sizeof(float)); };
+    std::vector<kc_plane *> weight(L, nullptr);  // [level], levels >= 1
+    for (uint32_t k = 0; k < L; ++k) {
+        if (k) {
+            KC_TRY(plane_new_mem(level_extent(w, k), level_extent(h, k), &weight[k]));
+            mc.scratch.push_back(weight[k]);
+        }
+        for (int ch = 0; ch < 3; ++ch)
+            if (col[3 * k + ch]->pitch != (k ? weight[k] : col[0])->pitch) return mip_refuse(who, "planes of one size differ in pitch");
+    }
+    const kc_plane *state[3] = { nullptr, nullptr, nullptr };  // of the level the next launch reads
+    uint64_t state_texels = 0;
+    auto fill = [&](auto &a, uint32_t k, uint32_t sw, uint32_t sh, uint32_t last) -> int {  // a launch that reads level k and ends at `last`
+        a.w = sw;
+        a.h = sh;
+        for (int ch = 0; ch < 4; ++ch) {
+            const kc_plane *p = k == 0 ? src0[ch] : ch < 3 ? state[ch] : weight[k];
+            const bool is_const = k == 0 && ((const_mask >> ch) & 1u);
+            a.src[ch] = is_const ? nullptr : p->dptr;
+            a.src_pitch[ch] = is_const ? 0u : pitch_of(p);
+            a.cval[ch] = is_const ? p->cval : 0.0f;
+        }
+        a.const_mask = k == 0 ? const_mask : 0u;
+        for (int ch = 0; ch < 3; ++ch) {
+            a.dst0[ch] = k == 0 ? col[ch]->dptr : nullptr;
+            state[ch] = nullptr;
+            a.state[ch] = nullptr;
+        }
+        a.dst0_pitch = k == 0 ? pitch_of(col[0]) : 0u;
+        if (last + 1 < L && last > k) {  // more levels follow
+            const uint32_t W = level_extent(w, last), H = level_extent(h, last);
+            for (int ch = 0; ch < 3; ++ch) {
+                kc_plane *p = nullptr;
+                KC_TRY(plane_new_mem(W, H, &p));
+                mc.scratch.push_back(p);
+                if (p->pitch != weight[last]->pitch) return mip_refuse(who, "planes of one size differ in pitch");
+                state[ch] = p;
+                a.state[ch] = p->dptr;
+            }
+            state_texels += (uint64_t)W * H;
+        }
+        return KC_OK;
+    };
+    if (L == 1) {  // a 1 x 1 image: no level to pull, level 0's colour alone
+        AlphaPullLevelArgs a{};
+        KC_TRY(fill(a, 0, w, h, 0));
+        hipError_t e = launch_alpha_pull_level(a, true, false, c.stream);
+        if (e != hipSuccess) return hip_fail(e, "launch_alpha_pull_level");
+        c.counters["mip_alpha_pull_level"]++;
+        c.launches++;
+    }
+    KC_TRY(mip_walk(c, w, h, L, per_level, 4u, [&](uint32_t k) { return k == 0 ? (uint32_t)sl.n : 4u; },
+                    [&](uint32_t k, uint32_t sw, uint32_t sh, uint32_t fused, bool nt) {
+        if (fused) {
+            AlphaPullPyramidArgs a{};
+            KC_TRY(fill(a, k, sw, sh, k + fused));
+            a.n = fused;
+            for (uint32_t j = 0; j < fused; ++j) {
+                for (int ch = 0; ch < 3; ++ch) a.dst[ch][j] = col[3 * (k + 1 + j) + ch]->dptr;
+                a.wdst[j] = weight[k + 1 + j]->dptr;
+                a.dst_pitch[j] = pitch_of(weight[k + 1 + j]);
+            }
+            hipError_t e = launch_alpha_pull_pyramid(a, k == 0, nt, c.stream);
+            if (e != hipSuccess) return hip_fail(e, "launch_alpha_pull_pyramid");
+            c.counters["mip_alpha_pull_pyramid"]++;
+        } else {
+            AlphaPullLevelArgs a{};
+            KC_TRY(fill(a, k, sw, sh, k + 1));
+            for (int ch = 0; ch < 3; ++ch) a.dst[ch] = col[3 * (k + 1) + ch]->dptr;
+            a.wdst = weight[k + 1]->dptr;
+            a.dst_pitch = pitch_of(weight[k + 1]);
+            hipError_t e = launch_alpha_pull_level(a, k == 0, nt, c.stream);
+            if (e != hipSuccess) return hip_fail(e, "launch_alpha_pull_level");
+            c.counters["mip_alpha_pull_level"]++;
+        }
+        return (int)KC_OK;
+    }));
+    AlphaPushArgs pa{};
+    uint32_t wgs = 0;
+    uint64_t below = 0;  // the texels of the levels >= 1
+    for (uint32_t k = 0; k < L; ++k) {
+        AlphaPushJob &J = pa.jobs[k];
+        for (int ch = 0; ch < 3; ++ch) J.dst[ch] = col[3 * k + ch]->dptr;
+        J.dst_pitch = pitch_of(col[3 * k]);
+        const kc_plane *ws = k ? weight[k] : (const_mask & 8u) ? nullptr : src0[3];
+        J.wsrc = ws ? ws->dptr : nullptr;
+        J.w_pitch = ws ? pitch_of(ws) : 0u;
+        J.w = level_extent(w, k);
+        J.h = level_extent(h, k);
+        J.first_wg = wgs;
+        J.wgs = alpha_push_job_wgs(J.w, J.h);
+        wgs += J.wgs;
+        if (k) below += (uint64_t)J.w * J.h;
+    }
+    pa.levels = L;
+    hipError_t e = launch_alpha_push(pa, wgs, c.stream);
+    if (e != hipSuccess) return hip_fail(e, "launch_alpha_push");
+    c.counters["mip_alpha_push"]++;
+    c.launches++;
+    // the pull: every distinct resident plane of level 0 read once, level 0's three colour planes written, three colours and the
+    // weight of every further level written, the three state planes of a level written and read and its weight read; the push:
+    // level 0's alpha where it is resident and every weight read (what it writes depends on the data and is not counted)
+    const uint64_t n0 = (uint64_t)w * h;
+    c.alg_bytes += 4 * n0 * sl.n + 12 * n0 + 16 * below + 28 * state_texels + ((const_mask & 8u) ? 0 : 4 * n0) + 4 * below;
+    return KC_OK;
+}
+
 // KC_MIP_COVERAGE: the select over alpha's plain chain (plain[k]: p_k, plain[0] the image's alpha; L levels of a w x h image,
 // w h <= 2^31) and, with `scaled` (scaled[k - 1]: d_k), the scale launch.  The records and the histograms live in
 // `scratch`, which the caller gives back to the pool once everything that reads it is enqueued (or waited for); *rec = the L
@@ -477,12 +633,100 @@ static bool mip_size_ok(uint32_t w, uint32_t h)
     return !(w > (1u << 30) || ((uint64_t)h + 63) / 64 > 65535ull || (((uint64_t)w + 3) / 4) * h > (1ull << 31));
 }
 
+// KC_MIP_ALPHA_WEIGHT on a forced RGBA image whose alpha is not a constant >= 1: levels[0] is an image of its own -- new colour
+// planes beside img's alpha -- and every further level has new colour planes.  A constant alpha of weight 0 gives constant-zero
+// colour, four constants are folded here through mip_alpha_texel (pull, then push from the last level up; every texel of a
+// level is the same), everything else goes through mip_launch_alpha.  Alpha itself is placed exactly as image_build_mips
+// places it: folded, or the plain launches and KC_MIP_COVERAGE's planes.
+static int image_build_alpha_mips(Context &c, kc_image *img, uint32_t ref, bool per_level, kc_image **levels, uint32_t w, uint32_t h, uint32_t L)
+{
+    const kc_plane *A = img->planes[3];
+    const bool a_const = A->kind == kc_plane::CONST;
+    const float w0 = a_const ? mip_alpha_weight(A->cval) : 0.0f;
+    const bool zero = a_const && !(w0 > 0.0f);
+    const bool fold = !zero && a_const && img->planes[0]->kind == kc_plane::CONST && img->planes[1]->kind == kc_plane::CONST &&
+                      img->planes[2]->kind == kc_plane::CONST;
+    MipChain mc;  // planes: one reference per plane of the level images, in no particular order
+    mc.planes.reserve((size_t)L * 4);
+    // alpha: alpha_out[k] is the plane of level k's image
+    MipSlots sl;
+    sl.add(3, A);
+    std::vector<kc_plane *> slot_planes(L > 1 ? (size_t)(L - 1) * 4 : 0, nullptr), alpha_out(L, img->planes[3]);
+    const bool coverage = ref != 0 && !a_const && L > 1;
+    std::vector<kc_plane *> scaled(coverage ? L - 1 : 0, nullptr);
+    float av = A->cval;
+    for (uint32_t k = 1; k < L; ++k) {
+        const uint32_t W = level_extent(w, k), H = level_extent(h, k);
+        kc_plane *p = nullptr;
+        if (a_const) {
+            av = mip_const_fold(av);
+            p = plane_new_const(W, H, av);
+        } else {
+            KC_TRY(plane_new_mem(W, H, &p));
+            slot_planes[(size_t)(k - 1) * 4] = p;
+            if (coverage) {
+                mc.scratch.push_back(p);
+                p = nullptr;
+                KC_TRY(plane_new_mem(W, H, &p));
+                scaled[k - 1] = p;
+            }
+        }
+        mc.planes.push_back(p);
+        alpha_out[k] = p;
+    }
+    // colour: col[3 k + ch], level 0 included
+    std::vector<kc_plane *> col((size_t)L * 3, nullptr);
+    std::vector<float> folded((size_t)L * 3, 0.0f);
+    if (fold) {
+        float P[3], W = w0;
+        std::vector<char> known(L, 1);
+        for (int ch = 0; ch < 3; ++ch) {
+            volatile float v = img->planes[ch]->cval, m = v * W;  // w0 > 0: the product
+            P[ch] = m;
+            folded[ch] = img->planes[ch]->cval;  // level 0 is known: c itself
+        }
+        for (uint32_t k = 1; k < L; ++k) {
+            for (int ch = 0; ch < 3; ++ch) P[ch] = mip_const_fold(P[ch]);
+            W = mip_const_fold(W);
+            known[k] = mip_alpha_texel(P, W, &folded[3 * k]);
+        }
+        for (uint32_t k = L - 1; k >= 1; --k)  // the push; an unknown last level keeps its 0
+            if (!known[k] && k + 1 < L)
+                for (int ch = 0; ch < 3; ++ch) folded[3 * k + ch] = folded[3 * (k + 1) + ch];
+    }
+    for (uint32_t k = 0; k < L; ++k) {
+        const uint32_t W = level_extent(w, k), H = level_extent(h, k);
+        for (int ch = 0; ch < 3; ++ch) {
+            kc_plane *p = nullptr;
+            if (zero || fold) p = plane_new_const(W, H, folded[3 * k + ch]);
+            else KC_TRY(plane_new_mem(W, H, &p));
+            mc.planes.push_back(p);
+            col[3 * k + ch] = p;
+        }
+    }
+    if (!zero && !fold) KC_TRY(mip_launch_alpha(c, img->planes, col, mc, w, h, L, per_level));
+    KC_TRY(mip_launch_plain(c, sl, slot_planes, w, h, L, per_level));
+    PoolStaging coverage_scratch;  // back to the pool when the call returns: everything that reads it is enqueued by then
+    if (coverage) {
+        std::vector<const kc_plane *> plain(L, img->planes[3]);
+        for (uint32_t k = 1; k < L; ++k) plain[k] = slot_planes[(size_t)(k - 1) * 4];
+        CoverageRecord *rec = nullptr;
+        KC_TRY(coverage_enqueue(c, plain, &scaled, w, h, L, ref, coverage_scratch, &rec));
+    }
+    for (uint32_t k = 0; k < L; ++k) {
+        kc_plane *const planes[4] = { col[3 * k], col[3 * k + 1], col[3 * k + 2], alpha_out[k] };
+        levels[k] = image_new(4, planes);  // retains; mc drops its own
+    }
+    return KC_OK;
+}
+
 int image_build_mips(kc_image *img, uint32_t flags, kc_image **levels, uint32_t cap, uint32_t *count)
 {
-    if (flags & ~(uint32_t)(KC_MIP_PER_LEVEL | KC_MIP_NORMALS | kCoverageFlagBits)) {
-        set_error("kc_image_build_mips: flags other than KC_MIP_PER_LEVEL, KC_MIP_NORMALS and KC_MIP_COVERAGE_REF");
+    if (flags & ~(uint32_t)(KC_MIP_PER_LEVEL | KC_MIP_NORMALS | KC_MIP_ALPHA_WEIGHT | kCoverageFlagBits)) {
+        set_error("kc_image_build_mips: flags other than KC_MIP_PER_LEVEL, KC_MIP_NORMALS, KC_MIP_ALPHA_WEIGHT and KC_MIP_COVERAGE_REF");
         return KC_ERR_UNSUPPORTED;
     }
+    KC_TRY(mip_check_alpha_flags(flags, "kc_image_build_mips"));
     KC_TRY(mip_check_coverage_flags(flags, "kc_image_build_mips"));
     if (!img || !levels || !count) return mip_refuse("kc_image_build_mips", "NULL image, level array or count");
     KC_TRY(need_init());
@@ -494,10 +738,14 @@ int image_build_mips(kc_image *img, uint32_t flags, kc_image **levels, uint32_t 
     const uint32_t ref = flags >> 24;  // != 0: KC_MIP_COVERAGE
     if (normals && !img->is_rgba()) return mip_refuse("kc_image_build_mips", "KC_MIP_NORMALS is for RGBA images (X, Y, Z in R, G, B)");
     if (ref && !img->is_rgba()) return mip_refuse("kc_image_build_mips", "KC_MIP_COVERAGE is for RGBA images");
+    if ((flags & KC_MIP_ALPHA_WEIGHT) && !img->is_rgba()) return mip_refuse("kc_image_build_mips", "KC_MIP_ALPHA_WEIGHT is for RGBA images");
     if (cap < L) return mip_refuse("kc_image_build_mips", "cap is below the level count");
     if (!mip_size_ok(w, h)) return mip_refuse("kc_image_build_mips", "image too large");
     if (ref && (uint64_t)w * h > (1ull << 31)) return mip_refuse("kc_image_build_mips", "image too large");  // the targets' 64-bit products
     KC_TRY(image_force(img));  // pending chains and deferred resizes run first
+    // KC_MIP_ALPHA_WEIGHT: a constant alpha >= 1 weighs every texel 1, which is the plain chain of the image bit for bit
+    if ((flags & KC_MIP_ALPHA_WEIGHT) && !(img->planes[3]->kind == kc_plane::CONST && mip_alpha_weight(img->planes[3]->cval) == 1.0f))
+        return image_build_alpha_mips(c, img, ref, per_level, levels, w, h, L);
     const int n = img->n;
     // sl: the planes the plain rule reduces (under KC_MIP_NORMALS: alpha alone); rgb: R, G, B under KC_MIP_NORMALS
     MipSlots sl, rgb;
@@ -696,11 +944,12 @@ int image_mip_coverage_info(kc_image *img, uint32_t flags, kc_mip_coverage_level
 // which does not go with KC_BC_SRGB: a vector is not a colour, and KC_MIP_COVERAGE_REF
 static int bc_mips_check_flags(int format, uint32_t flags, const char *who)
 {
-    KC_TRY(bc_check_flags(format, flags, KC_BC_SRGB | KC_MIP_PER_LEVEL | KC_MIP_NORMALS | kCoverageFlagBits, who));
+    KC_TRY(bc_check_flags(format, flags, KC_BC_SRGB | KC_MIP_PER_LEVEL | KC_MIP_NORMALS | KC_MIP_ALPHA_WEIGHT | kCoverageFlagBits, who));
     if ((flags & KC_MIP_NORMALS) && (flags & KC_BC_SRGB)) {
         set_error(std::string(who) + ": KC_MIP_NORMALS with KC_BC_SRGB");
         return KC_ERR_UNSUPPORTED;
     }
+    KC_TRY(mip_check_alpha_flags(flags, who));
     return mip_check_coverage_flags(flags, who);
 }
 
@@ -745,7 +994,7 @@ static int bc_mips_encode(kc_image *img, int format, uint32_t flags, char *dst)
     KC_TRY(mip_level_count(img->w(), img->h(), &L));
     std::vector<kc_image *> lv(L, nullptr);
     uint32_t count = 0;
-    KC_TRY(image_build_mips(img, flags & (KC_MIP_PER_LEVEL | KC_MIP_NORMALS | kCoverageFlagBits), lv.data(), L, &count));
+    KC_TRY(image_build_mips(img, flags & (KC_MIP_PER_LEVEL | KC_MIP_NORMALS | KC_MIP_ALPHA_WEIGHT | kCoverageFlagBits), lv.data(), L, &count));
     const int s = bc_levels_encode(lv.data(), L, format, flags, dst);
     // the level planes go back to the pool here; the pool hands a block out again only to work enqueued on the same stream
     for (kc_image *i : lv) image_release(i);
@@ -798,8 +1047,8 @@ int image_to_bc_mips(kc_image *img, int format, uint32_t flags, uint8_t *host, s
     if (!bc_format(format)) return mip_refuse("kc_image_to_bc_mips", "unknown format");
     if (!img || !host) return mip_refuse("kc_image_to_bc_mips", "NULL image or host buffer");
     KC_TRY(need_init());
-    if ((flags & (KC_MIP_NORMALS | KC_MIP_COVERAGE)) && !img->is_rgba())
-        return mip_refuse("kc_image_to_bc_mips", "KC_MIP_NORMALS and KC_MIP_COVERAGE are for RGBA images");
+    if ((flags & (KC_MIP_NORMALS | KC_MIP_COVERAGE | KC_MIP_ALPHA_WEIGHT)) && !img->is_rgba())
+        return mip_refuse("kc_image_to_bc_mips", "KC_MIP_NORMALS, KC_MIP_COVERAGE and KC_MIP_ALPHA_WEIGHT are for RGBA images");
     Context &c = ctx();
     std::lock_guard<std::recursive_mutex> lk(c.mu);
     size_t total = 0;
@@ -822,8 +1071,8 @@ int image_to_bc_mips_device(kc_image *img, int format, uint32_t flags, void *dev
     if (!img || !device_ptr) return mip_refuse("kc_image_to_bc_mips_device", "NULL image or device pointer");
     if ((uintptr_t)device_ptr % bb) return mip_refuse("kc_image_to_bc_mips_device", "the pointer must be a multiple of the block bytes");
     KC_TRY(need_init());  // an image exists only after kc_init: it is not looked at before
-    if ((flags & (KC_MIP_NORMALS | KC_MIP_COVERAGE)) && !img->is_rgba())
-        return mip_refuse("kc_image_to_bc_mips_device", "KC_MIP_NORMALS and KC_MIP_COVERAGE are for RGBA images");
+    if ((flags & (KC_MIP_NORMALS | KC_MIP_COVERAGE | KC_MIP_ALPHA_WEIGHT)) && !img->is_rgba())
+        return mip_refuse("kc_image_to_bc_mips_device", "KC_MIP_NORMALS, KC_MIP_COVERAGE and KC_MIP_ALPHA_WEIGHT are for RGBA images");
     Context &c = ctx();
     std::lock_guard<std::recursive_mutex> lk(c.mu);
     size_t total = 0;

@@ -1,6 +1,7 @@
-// The one copy of the mip steps that mip.hip, mip_normals.hip, mip_roughness.hip and preview.hip share: the box, the reduction of
+// The one copy of the mip steps that mip.hip, mip_normals.hip, mip_roughness.hip, mip_alpha.hip and preview.hip share: the box, the reduction of
 // a 64 x 64 tile by a 16 x 16 workgroup, the tile's loads and stores, the one-level step, where a channel of a normal map comes
-// from, and the two launch checks.  C channels (1, 3, or the 4 of a roughness chain: the normals' vector and the roughness) go
+// from, and the two launch checks.  C channels (1, 3, or the 4 of a roughness chain -- the normals' vector and the roughness -- and of
+// an alpha-weighted one -- the premultiplied colour and the weight) go
 // down together; a unit supplies its rule, rule(float (&b)[C]), called with the C boxes of one texel before they are stored or
 // passed on (nothing for the plain chain, the previews and the roughness chain's state, normal_texel for normal maps), and says
 // what happens to a finished level: the tile walk's `done`, the one-level walk's `sink` -- a roughness chain stores one plane
@@ -209,7 +210,7 @@ static __device__ __forceinline__ mip_f4 mip_src_box(const MipSrc<mip_f4> &s)
     return mip_f4{ mip_box(s.t0[0], s.t0[1], s.b0[0], s.b0[1]), mip_box(s.t0[2], s.t0[3], s.b0[2], s.b0[3]),
                    mip_box(s.t1[0], s.t1[1], s.b1[0], s.b1[1]), mip_box(s.t1[2], s.t1[3], s.b1[2], s.b1[3]) };
 }
-// Nothing happens to the source texels before the box (every unit but mip_roughness.hip's first launch).
+// Nothing happens to the source texels before the box (every unit but the first launches of mip_roughness.hip and mip_alpha.hip).
 struct MipNoDecode {
     static constexpr bool kNone = true;
 };
