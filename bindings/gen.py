@@ -20,10 +20,14 @@ OUTPUTS = {"_abi.py": os.path.join(ROOT, "kanter_core_amd"), "kanter_core_amd_sy
 SCALARS = {"int": ("c_int", "i32"), "int32_t": ("c_int32", "i32"), "uint32_t": ("c_uint32", "u32"), "uint64_t": ("c_uint64", "u64"),
            "uint8_t": ("c_uint8", "u8"), "size_t": ("c_size_t", "usize"), "float": ("c_float", "f32"), "double": ("c_double", "f64"),
            "char": ("c_char", "c_char"), "void": (None, "c_void")}
-# The one function-like macro of the header stays hand-written wherever it is used (api.mip_coverage_ref, this one-liner).
-MACRO = "KC_MIP_COVERAGE_REF"
-MACRO_RUST = """/// KC_MIP_COVERAGE with the reference byte b, 1..255 (KC_MIP_COVERAGE_REF)
-pub const fn kc_mip_coverage_ref(b: u8) -> u32 { KC_MIP_COVERAGE | (b as u32) << 24 }"""
+# The two function-like macros of the header stay hand-written wherever they are used (api.mip_coverage_ref and
+# api.bc_punch_through_ref, these one-liners); every other one is refused.
+MACROS = {
+    "KC_MIP_COVERAGE_REF": """/// KC_MIP_COVERAGE with the reference byte b, 1..255 (KC_MIP_COVERAGE_REF)
+pub const fn kc_mip_coverage_ref(b: u8) -> u32 { KC_MIP_COVERAGE | (b as u32) << 24 }""",
+    "KC_BC_PUNCH_THROUGH_REF": """/// KC_BC_PUNCH_THROUGH with the reference byte b, 1..255 (KC_BC_PUNCH_THROUGH_REF)
+pub const fn kc_bc_punch_through_ref(b: u8) -> u32 { KC_BC_PUNCH_THROUGH | (b as u32) << 24 }""",
+}
 
 
 class HeaderError(ValueError):
@@ -37,7 +41,7 @@ class HeaderError(ValueError):
 Type = collections.namedtuple("Type", "base const stars ptr_const dims")
 Define = collections.namedtuple("Define", "name value unsigned")
 Enum = collections.namedtuple("Enum", "name members")          # members: [(name, value)]
-Macro = collections.namedtuple("Macro", "name")                # the function-like one
+Macro = collections.namedtuple("Macro", "name")                # one of the function-like ones
 Opaque = collections.namedtuple("Opaque", "name")
 Struct = collections.namedtuple("Struct", "name fields")       # fields: [(name, Type)]
 Func = collections.namedtuple("Func", "name ret params")       # params: [(name, Type)]
@@ -87,12 +91,12 @@ class Header:
                     skipping = True
                 elif s.startswith("#endif"):
                     skipping = False
-                elif d and d.group(1) == MACRO and d.group(2):
-                    self.found.append((n, Macro(MACRO)))
+                elif d and d.group(1) in MACROS and d.group(2):
+                    self.found.append((n, Macro(d.group(1))))
                 elif d and d.group(1) != "KC_API" and (d.group(2) or d.group(3)):  # KC_API: the export attribute; no body: the guard
                     v = re.fullmatch(r"(\d+|0[xX][0-9a-fA-F]+)([uU]?)", d.group(3))
                     if d.group(2) or not v:
-                        raise HeaderError(n, "#define %s is neither an integer literal nor %s" % (d.group(1), MACRO))
+                        raise HeaderError(n, "#define %s is neither an integer literal nor %s" % (d.group(1), " or ".join(MACROS)))
                     self.found.append((n, Define(d.group(1), int(v.group(1), 0), bool(v.group(2)))))
                     self.values[d.group(1)] = int(v.group(1), 0)
             if skipping or s.lstrip().startswith("#"):  # `extern "C" {` and its brace are C++ only
@@ -227,7 +231,7 @@ def render_rust(h):
         if isinstance(i, Define):
             blocks.append("pub const %s: %s = %d;" % (i.name, "u32" if i.unsigned else "usize", i.value))
         elif isinstance(i, Macro):
-            blocks.append(MACRO_RUST)
+            blocks.append(MACROS[i.name])
         elif isinstance(i, Enum):
             blocks.append("\n".join(["// %s" % i.name] + ["pub const %s: i32 = %d;" % m for m in i.members]))
         elif isinstance(i, Opaque):

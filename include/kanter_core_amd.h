@@ -446,8 +446,43 @@ KC_API int kc_image_channel_stats(kc_image *img, uint32_t flags, kc_channel_stat
  *           P3 = E(c0) + 2E(c1).  c0 == c1: every index 0; otherwise texel t's index is the j minimising
  *           sum_c (3 p_t,c - P_j,c)^2, the lowest j on a tie.  Bytes: c0 and c1 as u16 LE, then a u32 LE with texel t's index at
  *           bits 2t..2t+1.  A block with a non-zero index has c0 > c1: it decodes in four-colour mode, never transparent.
+ *   BC1 with punch-through alpha (KC_BC_PUNCH_THROUGH, BC1 only): the format of alpha-TESTED cutouts at 8 bytes a block, its
+ *           1-bit alpha exactly the bit the test keeps.  The reference byte B, 1..255, travels in bits 24-31 of the flags word,
+ *           KC_BC_PUNCH_THROUGH_REF(B): the field of KC_MIP_COVERAGE_REF, which the two flags share in one word --
+ *           KC_BC_PUNCH_THROUGH | KC_MIP_COVERAGE_REF(B) builds the chain that keeps coverage at B and cuts every level at B.
+ *           The texels are kc_image_to_u8's bytes with alpha (always linear; edge blocks repeat the last column and row, alpha
+ *           included).  Texel t is opaque when its alpha byte is >= B: KC_MIP_COVERAGE's "covered" exactly (NaN alpha
+ *           quantises to 255 and is opaque).  n = the opaque texels of the block.  All integer arithmetic, so bit-exact
+ *           (tests/bc1a_ref.py is the same rule in numpy; kc_bc1_punch_through_block is the rule on one block, no device).
+ *             n == 16:     the plain BC1 block above, bit for bit.
+ *             n == 0:      the bytes 00 00 00 00 FF FF FF FF: c0 = c1 = 0, every index 3.
+ *             0 < n < 16:  lo, hi, k and s_c as for BC1 -- the same formulas and tie order -- with every min, max and sum over the
+ *                          opaque texels only.  m_c = (hi_c - lo_c) >> 3: twice the four-colour inset, because a three-colour
+ *                          palette has one interior point and its ends sit further in (a fixed part of the rule).  a_c = hi_c -
+ *                          m_c, b_c = lo_c + m_c, swapped where s_c < 0; c0 = pack(a), c1 = pack(b), swapped when c0 > c1: the
+ *                          block has c0 <= c1 and decodes in three-colour mode (c0 == c1 is legal).  The palette is the
+ *                          decoder's: Q0 = E(c0), Q1 = E(c1), Q2 = (E(c0) + E(c1)) div 2 per channel.  An opaque texel takes the
+ *                          j in 0..2 minimising sum_c (p_c - Q_j,c)^2, the lowest j on a tie; a texel that is not opaque takes
+ *                          index 3.  The byte layout is BC1's.
+ *           So a decoded texel has alpha 0 exactly where the source texel is not opaque; the colour under such texels never
+ *           influences a block; and an image whose alpha is everywhere >= B gives plain BC1, bit for bit.  The file is an
+ *           ordinary BC1 file (dxgiFormat 71 / 72): kc_dds_header, like kc_image_build_mips, kc_image_build_roughness_mips, the
+ *           previews and the decode entry points, refuses the flag as an unknown bit, and kc_image_from_bc / kc_image_read_dds
+ *           return such blocks with alpha 0 or 1 as they always have.  Accepted by kc_image_to_bc, kc_image_to_bc_device,
+ *           kc_live_graph_buffer_bc; kc_image_bc_error, kc_live_graph_buffer_bc_error, kc_image_bc_compare;
+ *           kc_image_to_bc_mips, kc_image_to_bc_mips_device, kc_live_graph_buffer_bc_mips; kc_image_levels_to_bc_mips,
+ *           kc_image_write_dds, kc_image_levels_write_dds.  It combines with KC_BC_SRGB, KC_MIP_PER_LEVEL, KC_MIP_COVERAGE and
+ *           KC_MIP_ALPHA_WEIGHT.  KC_ERR_UNSUPPORTED, refused with the other flag errors (before NULL arguments and kc_init):
+ *           the flag with a format other than KC_BC1, with a zero byte or with KC_MIP_NORMALS; a byte with neither this flag nor
+ *           KC_MIP_COVERAGE (as ever).  A Gray image is KC_ERR_INVALID_ARG exactly where KC_MIP_COVERAGE refuses it.
+ *           The error measure under the flag (kc_bc_error keeps its layout): channel_mask is 0xF; the source alpha is 255 where
+ *           the source texel is opaque and 0 otherwise, and sse[3] / max_abs[3] compare the decoded alpha against that; a pixel
+ *           whose source texel is not opaque contributes 0 to R, G and B (the renderer discards it, and its decoded colour is
+ *           the format's black); `pixels` stays width * height.  kc_stats: the encode is one launch, with 4 w h algorithmic
+ *           bytes per distinct resident plane of R, G, B and A plus the blocks' bytes (a constant alpha costs no loads); the
+ *           comparison stays two launches.
  *   BC3     the BC4 block of alpha, then the BC1 block (16 bytes).  BC5: the BC4 block of R, then that of G (16 bytes).  BC1
- *           ignores alpha; BC4 reads R only, BC5 R and G.
+ *           ignores alpha (without KC_BC_PUNCH_THROUGH); BC4 reads R only, BC5 R and G.
  *   BC7 of texels p_t = (r, g, b, a), 16 bytes: the two single-subset modes 6 and 5 (rotation 0) only.
  *           interp(e0, e1, w) = ((64 - w) e0 + w e1 + 32) >> 6; W4 = 0, 4, 9, 13, 17, 21, 26, 30, 34, 38, 43, 47, 51, 55, 60, 64;
  *           W2 = 0, 21, 43, 64.  axis(p over channels C): per channel lo = min, hi = max; k the first channel (order R, G, B, A)
@@ -491,7 +526,8 @@ KC_API int kc_image_channel_stats(kc_image *img, uint32_t flags, kc_channel_stat
  *                         Blocks until they are there, as kc_image_to_u8.
  *   kc_image_to_bc_device blocks into `dst`, ordered against `hip_stream` by the two event edges of kc_image_to_device (the
  *                         host does not wait).  kc_live_graph_buffer_bc: the same for a slot's image.
- * Errors: flag bits other than KC_BC_SRGB, or KC_BC_SRGB with BC4 / BC5 / BC6H, KC_ERR_UNSUPPORTED; a NULL argument, an unknown
+ * Errors: flag bits other than KC_BC_SRGB and KC_BC_PUNCH_THROUGH_REF, KC_BC_SRGB with BC4 / BC5 / BC6H, or
+ * KC_BC_PUNCH_THROUGH against its rule above, KC_ERR_UNSUPPORTED; a NULL argument, an unknown
  * format, a descriptor size that differs from the image's or `host_bytes` below the blocks' bytes KC_ERR_INVALID_ARG; then
  * KC_ERR_NO_DEVICE before kc_init; kc_live_graph_buffer_bc returns KC_ERR_NO_SLOT_DATA where kc_live_graph_buffer_device does.
  * A refused call launches nothing.  A pending chain or resample runs first; then one launch (kc_stats), constant channels
@@ -507,7 +543,12 @@ typedef struct kc_bc_image {
     size_t row_pitch_bytes;  /* distance between block rows */
 } kc_bc_image;
 #define KC_BC_SRGB 1u        /* BC1 / BC3 / BC7: R, G, B as kc_image_to_u8 with srgb = 1 writes them; alpha linear */
+#define KC_BC_PUNCH_THROUGH 256u  /* BC1 only: texels whose alpha byte is below the byte in bits 24-31 decode transparent (above) */
+#define KC_BC_PUNCH_THROUGH_REF(b) (256u | ((uint32_t)(b) << 24))  /* KC_BC_PUNCH_THROUGH with the reference byte b, 1..255 */
 KC_API int kc_bc_image_validate(const kc_bc_image *d, size_t *extent_bytes);
+/* The punch-through rule on one block, without a device: texel t is rgba + 4 t, ref_u8 the reference byte B.  A NULL pointer or
+ * a byte outside 1..255 is KC_ERR_INVALID_ARG and nothing is written. */
+KC_API int kc_bc1_punch_through_block(const uint8_t rgba[64], uint32_t ref_u8, uint8_t block[8]);
 KC_API int kc_image_to_bc(kc_image *img, int format, uint32_t flags, uint8_t *host, size_t host_bytes);
 KC_API int kc_image_to_bc_device(kc_image *img, const kc_bc_image *dst, uint32_t flags, void *hip_stream);
 /* Mip chains, built on the device, and their export as BC textures and DDS files: what a renderer samples is a chain, not one
@@ -994,7 +1035,7 @@ KC_API int kc_image_levels_write_dds(kc_image *const *levels, uint32_t count, co
 typedef struct kc_bc_error {
     int32_t format;              /* kc_bc_format of the blocks */
     uint32_t flags;              /* the flags the call was given */
-    uint32_t channel_mask;       /* bit c: channel c is compared: BC1 / BC6H 0x7, BC3 / BC7 0xF, BC4 0x1, BC5 0x3 */
+    uint32_t channel_mask;       /* bit c: channel c is compared: BC1 / BC6H 0x7, BC3 / BC7 / KC_BC_PUNCH_THROUGH 0xF, BC4 0x1, BC5 0x3 */
     uint64_t pixels;             /* width * height: the image's pixels, not the blocks' texels */
     uint64_t sse[4];             /* sum over the pixels of (decoded byte - source byte)^2; 0 outside the mask; BC6H: half bit patterns */
     uint32_t max_abs[4];         /* largest |decoded byte - source byte|; 0 outside the mask; BC6H: of half bit patterns, <= 31743 */

@@ -687,15 +687,53 @@ def _bc_format(fmt):
     return f
 
 
-def _bc_export(call, size, fmt, srgb, out):
+BC_PUNCH_THROUGH = _abi.KC_BC_PUNCH_THROUGH  # BC1 only: texels whose alpha byte is below the byte in bits 24-31 decode transparent
+
+
+def bc_punch_through_ref(ref):
+    """KC_BC_PUNCH_THROUGH_REF(ref): the flag with the reference byte 1..255 a renderer's alpha test compares with."""
+    ref = int(ref)
+    if not 1 <= ref <= 255:
+        raise ValueError("punch_through must be a byte 1..255")
+    return BC_PUNCH_THROUGH | ref << 24
+
+
+def _punch_flags(punch_through, coverage=None):
+    """The flag bits of a punch_through= keyword: None -> 0; the byte B -> KC_BC_PUNCH_THROUGH_REF(B), which beside coverage=
+    must be coverage's byte (the two share the field); True -> the flag alone, the byte being coverage's."""
+    if punch_through is None or punch_through is False:
+        return 0
+    if punch_through is True:
+        if coverage is None:
+            raise ValueError("punch_through=True reuses coverage=B; without coverage give the byte: punch_through=B")
+        return BC_PUNCH_THROUGH
+    word = bc_punch_through_ref(punch_through)
+    if coverage is not None and int(coverage) != int(punch_through):
+        raise ValueError("punch_through and coverage share one reference byte: %d is not %d" % (int(punch_through), int(coverage)))
+    return word
+
+
+def bc1_punch_through_block(rgba, ref):
+    """-> (8,) uint8: the BC1 block of the 16 RGBA8 texels `rgba` ((16, 4) or (4, 4, 4) uint8, texel t = 4 y + x) under the
+    reference byte `ref`: texels whose alpha is below it decode transparent (kc_bc1_punch_through_block; no device)."""
+    t = np.ascontiguousarray(rgba, np.uint8)
+    if t.size != 64 or t.shape[-1] != 4:
+        raise ValueError("rgba must hold 16 texels of 4 bytes")
+    out = np.empty(8, np.uint8)
+    _check(_lib.load().kc_bc1_punch_through_block(t.ctypes.data, int(ref), out.ctypes.data))
+    return out
+
+
+def _bc_export(call, size, fmt, srgb, out, punch_through=None):
     """Allocates (or takes) a uint8 (by, bx, block bytes) tensor and runs `call(desc, flags, stream)` into it.  `out` may be any
     view whose last two dimensions are contiguous (rows of blocks anywhere, e.g. a slice of a larger tensor)."""
     import torch
+    flags = (BC_SRGB if srgb else 0) | _punch_flags(punch_through)
     if out is None:
         shape = ((size.height + 3) // 4, (size.width + 3) // 4, BC_BLOCK_BYTES[_bc_format(fmt)])
         out = torch.empty(shape, dtype=torch.uint8, device=torch.device("cuda", torch.cuda.current_device()))
     d = _bc_desc(out, size.width, size.height, fmt, what="out", need="needs")
-    _check(_on_torch_stream(out, lambda stream: call(C.byref(d), BC_SRGB if srgb else 0, stream)))
+    _check(_on_torch_stream(out, lambda stream: call(C.byref(d), flags, stream)))
     return out
 
 
@@ -717,9 +755,10 @@ def mip_coverage_ref(ref):
 MIP_ALPHA_WEIGHT = _abi.KC_MIP_ALPHA_WEIGHT  # ... R, G, B of every level are alpha-weighted, the empty texels filled from the coarser levels
 
 
-def _mip_flags(srgb, per_level, normals, coverage=None, alpha_weighted=False):
+def _mip_flags(srgb, per_level, normals, coverage=None, alpha_weighted=False, punch_through=None):
     return ((BC_SRGB if srgb else 0) | (MIP_PER_LEVEL if per_level else 0) | (MIP_NORMALS if normals else 0)
-            | (mip_coverage_ref(coverage) if coverage is not None else 0) | (MIP_ALPHA_WEIGHT if alpha_weighted else 0))
+            | (mip_coverage_ref(coverage) if coverage is not None else 0) | (MIP_ALPHA_WEIGHT if alpha_weighted else 0)
+            | _punch_flags(punch_through, coverage))
 
 
 def mip_alpha_weight(a):
@@ -809,10 +848,11 @@ def _level_handles(levels):
     return levels, (C.c_void_p * max(1, len(levels)))(*[l._h.value for l in levels])
 
 
-def levels_to_bc_mips(levels, fmt, srgb=False):
+def levels_to_bc_mips(levels, fmt, srgb=False, punch_through=None):
     """-> one uint8 (ceil(H_k/4), ceil(W_k/4), block bytes) array per level, as SlotImage.to_bc_mips returns them: the BC blocks of
     a chain the caller holds -- roughness_mips's result, or any edited chain -- or of its first levels
-    (kc_image_levels_to_bc_mips).  levels[k] is max(1, w >> k) by max(1, h >> k) and of levels[0]'s kind."""
+    (kc_image_levels_to_bc_mips).  levels[k] is max(1, w >> k) by max(1, h >> k) and of levels[0]'s kind.  punch_through=B: as
+    SlotImage.to_bc."""
     f = _bc_format(fmt)
     levels, arr = _level_handles(levels)
     if not levels:
@@ -820,15 +860,17 @@ def levels_to_bc_mips(levels, fmt, srgb=False):
     s = levels[0].size()
     offs, total = bc_mip_layout(s.width, s.height, f)
     buf = np.empty((total,), np.uint8)
-    _check(_lib.load().kc_image_levels_to_bc_mips(arr, len(levels), f, BC_SRGB if srgb else 0, buf.ctypes.data, buf.nbytes))
+    flags = (BC_SRGB if srgb else 0) | _punch_flags(punch_through)
+    _check(_lib.load().kc_image_levels_to_bc_mips(arr, len(levels), f, flags, buf.ctypes.data, buf.nbytes))
     return _bc_mip_views(buf, s, f)[:len(levels)]
 
 
-def write_dds_levels(path, levels, fmt, srgb=False):
+def write_dds_levels(path, levels, fmt, srgb=False, punch_through=None):
     """Writes a .dds file (DX10 header) with the BC blocks of a chain the caller holds, or of its first levels
-    (kc_image_levels_write_dds)."""
+    (kc_image_levels_write_dds).  punch_through=B: as SlotImage.to_bc."""
     levels, arr = _level_handles(levels)
-    _check(_lib.load().kc_image_levels_write_dds(arr, len(levels), os.fspath(path).encode(), _bc_format(fmt), BC_SRGB if srgb else 0))
+    flags = (BC_SRGB if srgb else 0) | _punch_flags(punch_through)
+    _check(_lib.load().kc_image_levels_write_dds(arr, len(levels), os.fspath(path).encode(), _bc_format(fmt), flags))
 
 
 def mip_level_count(width, height):
@@ -941,7 +983,7 @@ def _bc_mip_views(buf, size, fmt):
     return views
 
 
-def _bc_mips_export(call, size, fmt, srgb, per_level, out, normals=False, coverage=None, alpha_weighted=False):
+def _bc_mips_export(call, size, fmt, srgb, per_level, out, normals=False, coverage=None, alpha_weighted=False, punch_through=None):
     """Allocates (or takes) a flat uint8 tensor of at least the chain's bytes and runs `call(fmt, flags, ptr, bytes, stream)`."""
     import torch
     f = _bc_format(fmt)
@@ -950,7 +992,7 @@ def _bc_mips_export(call, size, fmt, srgb, per_level, out, normals=False, covera
         out = torch.empty((total,), dtype=torch.uint8, device=torch.device("cuda", torch.cuda.current_device()))
     if out.dtype != torch.uint8 or out.dim() != 1 or not out.is_contiguous() or out.numel() < total:
         raise ValueError("out must be a contiguous 1-D uint8 tensor of at least %d bytes" % total)
-    flags = _mip_flags(srgb, per_level, normals, coverage, alpha_weighted)
+    flags = _mip_flags(srgb, per_level, normals, coverage, alpha_weighted, punch_through)
     _check(_on_torch_stream(out, lambda stream: call(f, flags, C.c_void_p(out.data_ptr()), out.numel(), stream)))
     return out, offs
 
@@ -1004,9 +1046,9 @@ class BcError(collections.namedtuple("BcError", "format flags channel_mask pixel
         return float("inf") if sse == 0 else float(10 * np.log10(peak ** 2 * self.pixels * len(chans) / sse))
 
 
-def _bc_error(call, srgb, all_modes=False):
+def _bc_error(call, srgb, all_modes=False, punch_through=None):
     r = _lib.kc_bc_error()
-    _check(call((BC_SRGB if srgb else 0) | (BC_ALL_MODES if all_modes else 0), C.byref(r)))
+    _check(call((BC_SRGB if srgb else 0) | (BC_ALL_MODES if all_modes else 0) | _punch_flags(punch_through), C.byref(r)))
     return BcError(int(r.format), int(r.flags), int(r.channel_mask), int(r.pixels), np.array(r.sse[:], np.uint64), np.array(r.max_abs[:], np.uint32),
                    int(r.undecoded_blocks), np.array(r.bc7_mode_blocks[:], np.uint64))
 
@@ -1178,21 +1220,24 @@ class SlotImage:
         return _device_export(lambda d, f, s: _lib.load().kc_image_to_device(self._h, d, f, s), self.size(), dtype, layout, channels,
                               srgb, out)
 
-    def to_bc(self, fmt, srgb=False):
+    def to_bc(self, fmt, srgb=False, punch_through=None):
         """-> uint8 (ceil(h/4), ceil(w/4), block bytes): the image's BC1, BC3, BC4, BC5 or BC7 (fmt = BC7) blocks (kc_image_to_bc),
         encoded on the device from the RGBA8 bytes to_u8(srgb) writes; srgb is for BC1, BC3 and BC7 only.  fmt = BC6H: mode-11
         blocks of the planes' own values, unclamped above 1: R, G, B (Gray: (v, v, v)) as half floats, f16(min(max(v, 0), 65504))
-        rounded to nearest even, NaN as 0; alpha is not read."""
+        rounded to nearest even, NaN as 0; alpha is not read.  punch_through=B (BC1 of an RGBA image, a byte 1..255): BC1 with
+        1-bit alpha for cutouts -- texels whose alpha byte is below B decode transparent and their colour never enters a block
+        (KC_BC_PUNCH_THROUGH)."""
         f = _bc_format(fmt)
         s = self.size()
         out = np.empty(((s.height + 3) // 4, (s.width + 3) // 4, BC_BLOCK_BYTES[f]), np.uint8)
-        _check(_lib.load().kc_image_to_bc(self._h, f, BC_SRGB if srgb else 0, out.ctypes.data, out.nbytes))
+        _check(_lib.load().kc_image_to_bc(self._h, f, (BC_SRGB if srgb else 0) | _punch_flags(punch_through), out.ctypes.data, out.nbytes))
         return out
 
-    def to_bc_torch(self, fmt, srgb=False, out=None):
+    def to_bc_torch(self, fmt, srgb=False, out=None, punch_through=None):
         """to_bc into a uint8 tensor (ceil(h/4), ceil(w/4), block bytes) in device memory (kc_image_to_bc_device); `out` (any view
         whose last two dimensions are contiguous) is written instead of a new tensor.  Ready on torch's current stream."""
-        return _bc_export(lambda d, f, st: _lib.load().kc_image_to_bc_device(self._h, d, f, st), self.size(), fmt, srgb, out)
+        return _bc_export(lambda d, f, st: _lib.load().kc_image_to_bc_device(self._h, d, f, st), self.size(), fmt, srgb, out,
+                          punch_through)
 
     def mips(self, per_level=False, normals=False, coverage=None, alpha_weighted=False):
         """-> the mip chain as a list of SlotImage (kc_image_build_mips): entry 0 is this image, entry k is max(1, w >> k) by
@@ -1243,25 +1288,27 @@ class SlotImage:
             raise ValueError("alpha_coverage is for RGBA images")
         return int(self.channel_stats(histogram=True).histogram[3][int(ref):].sum())
 
-    def to_bc_mips(self, fmt, srgb=False, per_level=False, normals=False, coverage=None, alpha_weighted=False):
+    def to_bc_mips(self, fmt, srgb=False, per_level=False, normals=False, coverage=None, alpha_weighted=False, punch_through=None):
         """-> one uint8 (ceil(H_k/4), ceil(W_k/4), block bytes) array per level, shaped like to_bc's and views of one buffer
         that holds the chain as a texture file stores it (kc_image_to_bc_mips).  normals=True: the chain of a normal map, as mips
         builds it (BC5 is the usual format; not with srgb).  coverage=B: the chain mips(coverage=B) builds; alpha_weighted=True: the
-        chain mips(alpha_weighted=True) builds."""
+        chain mips(alpha_weighted=True) builds.  punch_through=B: every level is cut at B as to_bc(punch_through=B) cuts it; beside
+        coverage=B it may be True and reuses that byte (another byte is a ValueError: the two share one field)."""
         f = _bc_format(fmt)
         s = self.size()
         offs, total = bc_mip_layout(s.width, s.height, f)
         buf = np.empty((total,), np.uint8)
-        flags = _mip_flags(srgb, per_level, normals, coverage, alpha_weighted)
+        flags = _mip_flags(srgb, per_level, normals, coverage, alpha_weighted, punch_through)
         _check(_lib.load().kc_image_to_bc_mips(self._h, f, flags, buf.ctypes.data, buf.nbytes))
         return _bc_mip_views(buf, s, f)
 
-    def to_bc_mips_torch(self, fmt, srgb=False, out=None, per_level=False, normals=False, coverage=None, alpha_weighted=False):
+    def to_bc_mips_torch(self, fmt, srgb=False, out=None, per_level=False, normals=False, coverage=None, alpha_weighted=False,
+                         punch_through=None):
         """-> (flat uint8 tensor in device memory holding the chain, offsets of the levels) (kc_image_to_bc_mips_device); `out`
         (contiguous, 1-D, at least the chain's bytes) is written instead of a new tensor, bytes past the chain are not touched.
         Ready on torch's current stream."""
         return _bc_mips_export(lambda f, fl, p, n, st: _lib.load().kc_image_to_bc_mips_device(self._h, f, fl, p, n, st), self.size(), fmt,
-                               srgb, per_level, out, normals, coverage, alpha_weighted)
+                               srgb, per_level, out, normals, coverage, alpha_weighted, punch_through)
 
     def preview(self, max_extent, srgb=False):
         """-> (h, w, 4) uint8: the whole mip level a preview of at most max_extent texels a side is cut from (preview_level), read
@@ -1269,30 +1316,33 @@ class SlotImage:
         s = self.size()
         return previews([(self, preview_level(s.width, s.height, max_extent)[0], None)], srgb)[0]
 
-    def write_dds(self, path, fmt, srgb=False, mips=True, normals=False, coverage=None, alpha_weighted=False):
+    def write_dds(self, path, fmt, srgb=False, mips=True, normals=False, coverage=None, alpha_weighted=False, punch_through=None):
         """Writes a .dds file (DX10 header) with the image's BC blocks: the whole mip chain, or level 0 alone (kc_image_write_dds).
         normals=True: the chain of a normal map, as to_bc_mips(normals=True); coverage=B: the chain of a cutout, as
         to_bc_mips(coverage=B); alpha_weighted=True: the chain of to_bc_mips(alpha_weighted=True) (none has an effect with
-        mips=False)."""
-        _check(_lib.load().kc_image_write_dds(self._h, os.fspath(path).encode(), _bc_format(fmt), _mip_flags(srgb, False, normals, coverage, alpha_weighted), int(mips)))
+        mips=False).  punch_through=B (or True beside coverage=B): BC1 with 1-bit alpha, as to_bc_mips; it cuts level 0 with
+        mips=False too.  The file is an ordinary BC1 file."""
+        flags = _mip_flags(srgb, False, normals, coverage, alpha_weighted, punch_through)
+        _check(_lib.load().kc_image_write_dds(self._h, os.fspath(path).encode(), _bc_format(fmt), flags, int(mips)))
 
-    def bc_error(self, fmt, srgb=False, blocks=None, all_modes=False):
+    def bc_error(self, fmt, srgb=False, blocks=None, all_modes=False, punch_through=None):
         """-> BcError: how far the image's BC encoding is from the image, measured on the device (kc_image_bc_error): the bytes
         the blocks decode to against the bytes to_u8(srgb) writes, over the image's pixels (BC6H: half bit patterns).  blocks: a uint8 (ceil(h/4), ceil(w/4),
         block bytes) tensor in device memory to compare instead of the library's own encoding (kc_image_bc_compare), e.g.
         another encoder's; all_modes=True decodes every BC7 and BC6H mode of such blocks (from_bc's), so that undecoded_blocks
-        is 0.  The library's own encoding needs no such flag: all_modes=True without blocks is a ValueError.  Blocks until the
-        values are there."""
+        is 0.  The library's own encoding needs no such flag: all_modes=True without blocks is a ValueError.  punch_through=B: the
+        error of to_bc(1, punch_through=B) as a renderer that tests alpha against B sees it -- the 1-bit alpha is compared too
+        (channel_mask 0xF), and a pixel the test discards does not count in R, G, B.  Blocks until the values are there."""
         f = _bc_format(fmt)
         if blocks is None and all_modes:
             raise ValueError("all_modes is for blocks=...: the library's own blocks are single-subset modes")
         if blocks is None:
-            return _bc_error(lambda fl, out: _lib.load().kc_image_bc_error(self._h, f, fl, out), srgb)
+            return _bc_error(lambda fl, out: _lib.load().kc_image_bc_error(self._h, f, fl, out), srgb, False, punch_through)
         s = self.size()
         d = _bc_desc(blocks, s.width, s.height, f)
         import torch
         torch.cuda.current_stream(blocks.device).synchronize()  # the call runs on the library's stream: the blocks must be there
-        return _bc_error(lambda fl, out: _lib.load().kc_image_bc_compare(self._h, C.byref(d), fl, out), srgb, all_modes)
+        return _bc_error(lambda fl, out: _lib.load().kc_image_bc_compare(self._h, C.byref(d), fl, out), srgb, all_modes, punch_through)
 
     def channel_stats(self, histogram=False, srgb=False):
         """-> ChannelStats of the image, computed on the device (kc_image_channel_stats): the range and NaN count of every
@@ -1645,16 +1695,17 @@ class LiveGraph:
         return _device_export(lambda d, f, s: _lib.load().kc_live_graph_buffer_device(self._h, node_id, slot_id, d, f, s),
                               self.slot_data_size(node_id, slot_id), dtype, layout, channels, srgb, out)
 
-    def buffer_bc_torch(self, node_id, slot_id, fmt, srgb=False, out=None):
+    def buffer_bc_torch(self, node_id, slot_id, fmt, srgb=False, out=None, punch_through=None):
         """SlotImage.to_bc_torch of a slot's image (kc_live_graph_buffer_bc)."""
         return _bc_export(lambda d, f, st: _lib.load().kc_live_graph_buffer_bc(self._h, node_id, slot_id, d, f, st),
-                          self.slot_data_size(node_id, slot_id), fmt, srgb, out)
+                          self.slot_data_size(node_id, slot_id), fmt, srgb, out, punch_through)
 
     def buffer_bc_mips_torch(self, node_id, slot_id, fmt, srgb=False, out=None, per_level=False, normals=False, coverage=None,
-                             alpha_weighted=False):
+                             alpha_weighted=False, punch_through=None):
         """SlotImage.to_bc_mips_torch of a slot's image (kc_live_graph_buffer_bc_mips)."""
         return _bc_mips_export(lambda f, fl, p, n, st: _lib.load().kc_live_graph_buffer_bc_mips(self._h, node_id, slot_id, f, fl, p, n, st),
-                               self.slot_data_size(node_id, slot_id), fmt, srgb, per_level, out, normals, coverage, alpha_weighted)
+                               self.slot_data_size(node_id, slot_id), fmt, srgb, per_level, out, normals, coverage, alpha_weighted,
+                               punch_through)
 
     def buffer_previews(self, items, srgb=False):
         """previews of slots' images (kc_live_graph_buffer_previews): items = [(node_id, slot_id, level, rect or None)] -> one
@@ -1667,10 +1718,11 @@ class LiveGraph:
                                                          buf.nbytes))
         return _preview_views(buf, offsets, shapes)
 
-    def buffer_bc_error(self, node_id, slot_id, fmt, srgb=False):
+    def buffer_bc_error(self, node_id, slot_id, fmt, srgb=False, punch_through=None):
         """SlotImage.bc_error of a slot's image (kc_live_graph_buffer_bc_error)."""
         f = _bc_format(fmt)
-        return _bc_error(lambda fl, out: _lib.load().kc_live_graph_buffer_bc_error(self._h, node_id, slot_id, f, fl, out), srgb)
+        return _bc_error(lambda fl, out: _lib.load().kc_live_graph_buffer_bc_error(self._h, node_id, slot_id, f, fl, out), srgb,
+                         False, punch_through)
 
     def buffer_channel_stats(self, node_id, slot_id, histogram=False, srgb=False):
         """SlotImage.channel_stats of a slot's image (kc_live_graph_buffer_channel_stats)."""

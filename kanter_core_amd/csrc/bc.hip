@@ -52,81 +52,7 @@ static __device__ __forceinline__ bc_u2 encode_bc4(const uint32_t (&wd)[16], uin
     return bc_u2{ lo, hi };
 }
 
-static __device__ __forceinline__ uint32_t pack565(uint32_t r, uint32_t g, uint32_t b)
-{
-    return ((31u * r + 127u) / 255u) << 11 | ((63u * g + 127u) / 255u) << 5 | ((31u * b + 127u) / 255u);
-}
-
-// BC1 of texels held as rb = R | B << 16 and ga = G | A << 16 (alpha ignored), so that the channel ranges are packed 16-bit
-// min / max and the sums over channels 16-bit dot products.  Endpoints: the colour box inset by 1/16 of each range, on the
-// diagonal the covariance signs against the channel of the largest range choose (s_c = 2 sum a p_c - S_c sum a with
-// a = 2 p_k - S_k, S = lo + hi).  Indices: the palette P_j = 3 E0 + k_j D (D = E1 - E0, k = 0, 3, 1, 2 for j = 0..3) lies on
-// one line, so |3p - P_j|^2 = |3p - 3E0|^2 - 6 k v + k^2 L with v = (p - E0).D and L = |D|^2, and the nearest k is the number of
-// thresholds 6v > L, 6v > 3L, 6v >= 5L that v passes (the last one >= : the tie of k = 2 and 3 goes to j = 1, the lower index)
-// -- the contract's arg-min, without computing the four distances.
-static __device__ __forceinline__ bc_u2 encode_bc1(const uint32_t (&rb)[16], const uint32_t (&ga)[16])
-{
-    bc_h2 lrb = as_h2(rb[0]), hrb = lrb, lga = as_h2(ga[0]), hga = lga;
-#pragma unroll
-    for (int t = 1; t < 16; ++t) {
-        lrb = __builtin_elementwise_min(lrb, as_h2(rb[t]));
-        hrb = __builtin_elementwise_max(hrb, as_h2(rb[t]));
-        lga = __builtin_elementwise_min(lga, as_h2(ga[t]));
-        hga = __builtin_elementwise_max(hga, as_h2(ga[t]));
-    }
-    const uint32_t lo[3] = { lrb.x, lga.x, lrb.y }, hi[3] = { hrb.x, hga.x, hrb.y };
-    const uint32_t rr = hi[0] - lo[0], rg = hi[1] - lo[1], rb_ = hi[2] - lo[2];
-    const uint32_t k = (rr >= rg && rr >= rb_) ? 0u : (rg >= rb_ ? 1u : 2u);
-    const int32_t sk = (int32_t)(k == 0u ? lo[0] + hi[0] : k == 1u ? lo[1] + hi[1] : lo[2] + hi[2]);
-    const uint32_t ksh = k == 2u ? 16u : 0u;
-    int32_t sa = 0, sr = 0, sg = 0, sb = 0;
-#pragma unroll
-    for (int t = 0; t < 16; ++t) {
-        const int32_t a = 2 * (int32_t)__builtin_amdgcn_ubfe(k == 1u ? ga[t] : rb[t], ksh, 16u) - sk;  // -510..510
-        sa += a;
-        const uint32_t alo = (uint32_t)a & 0xffffu, ahi = (uint32_t)a << 16;
-        sr = __builtin_amdgcn_sdot2(as_s2(rb[t]), as_s2(alo), sr, false);
-        sb = __builtin_amdgcn_sdot2(as_s2(rb[t]), as_s2(ahi), sb, false);
-        sg = __builtin_amdgcn_sdot2(as_s2(ga[t]), as_s2(alo), sg, false);
-    }
-    const int32_t s[3] = { 2 * sr - (int32_t)(lo[0] + hi[0]) * sa, 2 * sg - (int32_t)(lo[1] + hi[1]) * sa,
-                           2 * sb - (int32_t)(lo[2] + hi[2]) * sa };
-    uint32_t ea[3], eb[3];
-#pragma unroll
-    for (int c = 0; c < 3; ++c) {
-        const uint32_t m = (hi[c] - lo[c]) >> 4;
-        const uint32_t a = hi[c] - m, b = lo[c] + m;
-        ea[c] = s[c] < 0 ? b : a;  // s_k >= 0: the reference channel keeps its direction
-        eb[c] = s[c] < 0 ? a : b;
-    }
-    uint32_t c0 = pack565(ea[0], ea[1], ea[2]), c1 = pack565(eb[0], eb[1], eb[2]);
-    if (c0 < c1) {
-        const uint32_t tmp = c0;
-        c0 = c1;
-        c1 = tmp;
-    }
-    uint32_t word = 0u;
-    if (c0 != c1) {
-        const int32_t r5 = (int32_t)(c0 >> 11), g6 = (int32_t)((c0 >> 5) & 63u), b5 = (int32_t)(c0 & 31u);
-        const int32_t s5 = (int32_t)(c1 >> 11), h6 = (int32_t)((c1 >> 5) & 63u), c5 = (int32_t)(c1 & 31u);
-        const int32_t E0[3] = { (r5 << 3) | (r5 >> 2), (g6 << 2) | (g6 >> 4), (b5 << 3) | (b5 >> 2) };
-        const int32_t E1[3] = { (s5 << 3) | (s5 >> 2), (h6 << 2) | (h6 >> 4), (c5 << 3) | (c5 >> 2) };
-        const int32_t D[3] = { E1[0] - E0[0], E1[1] - E0[1], E1[2] - E0[2] };
-        const int32_t L = D[0] * D[0] + D[1] * D[1] + D[2] * D[2];
-        const int32_t L3 = 3 * L, L5 = 5 * L;
-        const int32_t e0d = -(E0[0] * D[0] + E0[1] * D[1] + E0[2] * D[2]);
-        const bc_s2 drb = as_s2(((uint32_t)D[0] & 0xffffu) | ((uint32_t)D[2] << 16)), dg = as_s2((uint32_t)D[1] & 0xffffu);
-#pragma unroll
-        for (int t = 0; t < 16; ++t) {
-            const int32_t v = __builtin_amdgcn_sdot2(as_s2(ga[t]), dg, __builtin_amdgcn_sdot2(as_s2(rb[t]), drb, e0d, false), false);
-            const int32_t v6 = 6 * v;
-            const uint32_t kk = (uint32_t)(v6 > L) + (uint32_t)(v6 > L3) + (uint32_t)(v6 >= L5);
-            word |= __builtin_amdgcn_ubfe(0x78u, 2u * kk, 2u) << (2 * t);  // k = 0, 1, 2, 3 -> j = 0, 2, 3, 1
-        }
-    }
-    return bc_u2{ c0 | (c1 << 16), word };
-}
-
+// encode_bc1: bc_blocks.h's, which bc1a.hip shares
 template <int FMT>
 static __device__ __forceinline__ void bc_encode_store(const uint32_t (&rb)[16], const uint32_t (&ga)[16], const BcBlockArgs &a, uint32_t i,
                                                        uint32_t j)

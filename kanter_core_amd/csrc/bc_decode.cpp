@@ -157,8 +157,10 @@ static int bc_compare(kc_image *img, int format, uint32_t flags, const char *blo
 {
     Context &c = ctx();
     const BcFormat &f = *bc_format(format);  // the entry points have refused an unknown format
+    const uint32_t pt_ref = bc_punch_through_ref(flags);  // KC_BC_PUNCH_THROUGH: alpha is read and compared too
+    const uint32_t channels = pt_ref ? 0xfu : f.channels;
     Operand o[4];
-    const uint32_t n_res = bc_source_operands(img, f.channels, o);
+    const uint32_t n_res = bc_source_operands(img, channels, o);
     const uint32_t w = img->w(), h = img->h();
     const uint32_t groups = bc_compare_groups(w, h);
     KC_TRY(stats_buffers((size_t)groups * KC_BC_REC_WORDS * sizeof(unsigned long long)));
@@ -167,7 +169,7 @@ static int bc_compare(kc_image *img, int format, uint32_t flags, const char *blo
     const uint32_t nt_mask = cache_policy_mask(in_bytes + blk_bytes, 0, n_res ? n_res : 1);
     unsigned long long *partials = (unsigned long long *)c.stats.partials;
     hipError_t e = bc_launch_compare(format, (flags & KC_BC_SRGB) != 0, (flags & KC_BC_ALL_MODES) != 0, o, img->is_rgba() ? 0 : 1, blocks, row_pitch, w, h, nt_mask, groups, partials,
-                                     c.stats.result, c.stream);
+                                     c.stats.result, c.stream, pt_ref);
     if (e != hipSuccess) return hip_fail(e, "launch_bc_compare");
     c.launches += 2;
     c.alg_bytes += in_bytes + blk_bytes;
@@ -177,7 +179,7 @@ static int bc_compare(kc_image *img, int format, uint32_t flags, const char *blo
     std::memset(&r, 0, sizeof r);
     r.format = format;
     r.flags = flags;
-    r.channel_mask = f.channels;
+    r.channel_mask = channels;
     r.pixels = (uint64_t)w * h;
     for (int ch = 0; ch < 4; ++ch) {
         r.sse[ch] = res[ch];
@@ -191,9 +193,10 @@ static int bc_compare(kc_image *img, int format, uint32_t flags, const char *blo
 
 int image_bc_compare(kc_image *img, const kc_bc_image *blocks, uint32_t flags, kc_bc_error *out)
 {
-    KC_TRY(bc_check_flags(blocks ? blocks->format : 0, flags, KC_BC_SRGB | KC_BC_ALL_MODES, "kc_image_bc_compare"));
+    KC_TRY(bc_check_flags(blocks ? blocks->format : 0, flags, KC_BC_SRGB | KC_BC_ALL_MODES | kBcPunchThroughBits, "kc_image_bc_compare"));
     if (!img || !out) return bcd_refuse("kc_image_bc_compare", "NULL image or output");
     KC_TRY(bc_image_validate(blocks, nullptr));
+    if ((flags & KC_BC_PUNCH_THROUGH) && !img->is_rgba()) return bcd_refuse("kc_image_bc_compare", "KC_BC_PUNCH_THROUGH is for RGBA images");
     if (img->w() != blocks->width || img->h() != blocks->height) return bcd_refuse("kc_image_bc_compare", "descriptor size differs from the image's");
     Context &c = ctx();
     std::lock_guard<std::recursive_mutex> lk(c.mu);
@@ -203,11 +206,12 @@ int image_bc_compare(kc_image *img, const kc_bc_image *blocks, uint32_t flags, k
 
 int image_bc_error(kc_image *img, int format, uint32_t flags, kc_bc_error *out)
 {
-    KC_TRY(bc_check_flags(format, flags, KC_BC_SRGB, "kc_image_bc_error"));
+    KC_TRY(bc_check_flags(format, flags, KC_BC_SRGB | kBcPunchThroughBits, "kc_image_bc_error"));
     const BcFormat *f = bc_format(format);
     if (!f) return bcd_refuse("kc_image_bc_error", "unknown format");
     if (!img || !out) return bcd_refuse("kc_image_bc_error", "NULL image or output");
     KC_TRY(need_init());
+    if ((flags & KC_BC_PUNCH_THROUGH) && !img->is_rgba()) return bcd_refuse("kc_image_bc_error", "KC_BC_PUNCH_THROUGH is for RGBA images");
     Context &c = ctx();
     std::lock_guard<std::recursive_mutex> lk(c.mu);
     uint64_t bx = 0, by = 0;
@@ -216,7 +220,7 @@ int image_bc_error(kc_image *img, int format, uint32_t flags, kc_bc_error *out)
     PoolStaging staging;
     KC_TRY(staging.alloc(bc_level_bytes(img->w(), img->h(), *f)));
     const size_t row_pitch = (size_t)bx * f->block_bytes;
-    KC_TRY(bc_encode(img, format, (flags & KC_BC_SRGB) != 0, (char *)staging.ptr, row_pitch, c.stream));
+    KC_TRY(bc_encode(img, format, (flags & KC_BC_SRGB) != 0, (char *)staging.ptr, row_pitch, c.stream, bc_punch_through_ref(flags)));
     return bc_compare(img, format, flags, (const char *)staging.ptr, row_pitch, out);  // waits: the staging is free after it
 }
 

@@ -17,36 +17,7 @@ namespace kc {
 #include "streaming.h"  // grid_cap, ld_policy / st_policy, quant_u8 / quant_u8_srgb
 #include "bc_blocks.h"  // the block walk, the encoders' row loaders and quantiser, the plane-row store and the record fold
 
-// BC1 into px (R | G << 8 | B << 16 | A << 24).  `four`: BC3's colour block, always in four-colour mode
-static __device__ __forceinline__ void decode_bc1(uint32_t w0, uint32_t idx, bool four, uint32_t (&px)[16])
-{
-    const uint32_t c0 = w0 & 0xffffu, c1 = w0 >> 16;
-    four = four || c0 > c1;
-    uint32_t pal[4] = { 0u, 0u, 0u, 0u };
-#pragma unroll
-    for (int c = 0; c < 3; ++c) {
-        const uint32_t sh = c == 0 ? 11u : c == 1 ? 5u : 0u, n = c == 1 ? 6u : 5u;
-        const uint32_t q0 = (c0 >> sh) & ((1u << n) - 1u), q1 = (c1 >> sh) & ((1u << n) - 1u);
-        const uint32_t e0 = (q0 << (8u - n)) | (q0 >> (2u * n - 8u)), e1 = (q1 << (8u - n)) | (q1 >> (2u * n - 8u));
-        const uint32_t p2 = four ? (2u * e0 + e1 + 1u) / 3u : (e0 + e1) >> 1;
-        const uint32_t p3 = four ? (e0 + 2u * e1 + 1u) / 3u : 0u;
-        pal[0] |= e0 << (8 * c);
-        pal[1] |= e1 << (8 * c);
-        pal[2] |= p2 << (8 * c);
-        pal[3] |= p3 << (8 * c);
-    }
-    pal[0] |= 0xff000000u;
-    pal[1] |= 0xff000000u;
-    pal[2] |= 0xff000000u;
-    if (four) pal[3] |= 0xff000000u;  // otherwise index 3 is transparent black
-#pragma unroll
-    for (int t = 0; t < 16; ++t) {
-        const uint32_t i = idx >> (2 * t);
-        const uint32_t lo = (i & 1u) ? pal[1] : pal[0], hi = (i & 1u) ? pal[3] : pal[2];
-        px[t] = (i & 2u) ? hi : lo;
-    }
-}
-
+// decode_bc1: bc_blocks.h's
 // BC4 of the 8 bytes (lo, hi) into bits sh..sh+7 of px
 static __device__ __forceinline__ void decode_bc4(uint32_t lo, uint32_t hi, uint32_t sh, uint32_t (&px)[16])
 {

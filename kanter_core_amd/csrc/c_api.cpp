@@ -939,6 +939,14 @@ try {
 }
 KC_CATCH
 
+int kc_bc1_punch_through_block(const uint8_t rgba[64], uint32_t ref, uint8_t block[8])
+try {
+    KC_ARG(rgba && block && ref >= 1 && ref <= 255);
+    bc1_punch_through_block(rgba, ref, block);
+    return KC_OK;
+}
+KC_CATCH
+
 int kc_alpha_ref_threshold(uint32_t ref_u8, float *r)
 try {
     KC_ARG(r && ref_u8 >= 1 && ref_u8 <= 255);
@@ -1710,6 +1718,7 @@ KC_CATCH
 
 int kc_live_graph_buffer_bc(kc_live_graph *lg, uint32_t node, uint32_t slot, const kc_bc_image *dst, uint32_t flags, void *hip_stream)
 try {
+    KC_TRY(bc_check_flags(dst ? dst->format : 0, flags, KC_BC_SRGB | kBcPunchThroughBits, "kc_live_graph_buffer_bc"));
     LG_LOCK(lg);
     KC_ARG(dst);
     const SlotData *sd = lg->find_slot(node, slot);
@@ -1721,10 +1730,10 @@ KC_CATCH
 int kc_live_graph_buffer_bc_mips(kc_live_graph *lg, uint32_t node, uint32_t slot, int format, uint32_t flags, void *device_ptr,
                                  size_t bytes, void *hip_stream)
 try {
-    if (flags & ~(uint32_t)(KC_BC_SRGB | KC_MIP_PER_LEVEL | KC_MIP_NORMALS | KC_MIP_COVERAGE | KC_MIP_ALPHA_WEIGHT | 0xff000000u)) {
-        set_error("kc_live_graph_buffer_bc_mips: unknown flag bits");
-        return KC_ERR_UNSUPPORTED;
-    }
+    // the unknown bits, KC_BC_SRGB's and KC_BC_PUNCH_THROUGH's rules; the chain flags' own follow
+    KC_TRY(bc_check_flags(format, flags,
+                          KC_BC_SRGB | KC_MIP_PER_LEVEL | KC_MIP_NORMALS | KC_MIP_COVERAGE | KC_MIP_ALPHA_WEIGHT | kBcPunchThroughBits,
+                          "kc_live_graph_buffer_bc_mips"));
     if ((flags & KC_MIP_NORMALS) && (flags & KC_MIP_ALPHA_WEIGHT)) {
         set_error("kc_live_graph_buffer_bc_mips: KC_MIP_NORMALS with KC_MIP_ALPHA_WEIGHT");
         return KC_ERR_UNSUPPORTED;
@@ -1765,7 +1774,7 @@ KC_CATCH
 
 int kc_live_graph_buffer_bc_error(kc_live_graph *lg, uint32_t node, uint32_t slot, int format, uint32_t flags, kc_bc_error *out)
 try {
-    KC_TRY(bc_check_flags(format, flags, KC_BC_SRGB, "kc_live_graph_buffer_bc_error"));
+    KC_TRY(bc_check_flags(format, flags, KC_BC_SRGB | kBcPunchThroughBits, "kc_live_graph_buffer_bc_error"));
     LG_LOCK(lg);
     KC_ARG(out && bc_block_bytes(format) != 0);
     KC_TRY(need_init());

@@ -322,6 +322,13 @@ uint32_t channel_stats_groups(uint32_t w, uint32_t h, bool hist, bool srgb, uint
 // once); nt_mask bits 0-7: nontemporal plane loads; srgb: BC1 and BC3 only
 hipError_t launch_bc_encode(int fmt, int srgb, const Operand op[4], int gray, char *dst, uint64_t row_pitch, uint32_t w, uint32_t h,
                             uint32_t nt_mask, hipStream_t s);
+// -- bc1a.hip --
+// KC_BC_PUNCH_THROUGH: bc1a_encode_kernel<srgb, nt>, BC1 blocks of an RGBA image whose texels with an alpha byte below `ref`
+// (1..255) decode transparent; bc1a_compare_kernel<srgb, nt> then bc_combine_kernel, launch_bc_compare's record under the flag
+hipError_t launch_bc1a_encode(int srgb, const Operand op[4], uint32_t ref, char *dst, uint64_t row_pitch, uint32_t w, uint32_t h, uint32_t nt_mask,
+                              hipStream_t s);
+hipError_t launch_bc1a_compare(int srgb, const Operand op[4], uint32_t ref, const char *blocks, uint64_t row_pitch, uint32_t w, uint32_t h,
+                               uint32_t nt_mask, uint32_t groups, unsigned long long *partials, unsigned long long *result, hipStream_t s);
 // -- bc7.hip --
 // bc7_encode_kernel<srgb, nt>: the same for KC_BC7 (16-byte blocks, all four channels)
 hipError_t launch_bc7_encode(int srgb, const Operand op[4], int gray, char *dst, uint64_t row_pitch, uint32_t w, uint32_t h, uint32_t nt_mask,

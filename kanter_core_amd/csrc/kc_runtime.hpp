@@ -423,18 +423,27 @@ size_t bc_level_bytes(uint32_t w, uint32_t h, const BcFormat &f);  // the bytes 
 // *bx, *by = the blocks per row and the block rows of a w x h image; more than 2^31 blocks are KC_ERR_INVALID_ARG under `who`
 int bc_block_count(uint32_t w, uint32_t h, const char *who, uint64_t *bx, uint64_t *by);
 // the encoders' flag rule: bits outside `allowed`, or KC_BC_SRGB with a format without colour, are KC_ERR_UNSUPPORTED
+// KC_BC_PUNCH_THROUGH in `allowed` brings its rule: BC1 only, a reference byte 1..255 in bits 24-31 (which it shares with
+// KC_MIP_COVERAGE; a byte with neither flag is refused), not with KC_MIP_NORMALS
 int bc_check_flags(int format, uint32_t flags, uint32_t allowed, const char *who);
+// the bits an entry point that takes KC_BC_PUNCH_THROUGH allows for it, and the reference byte of a checked flags word (0: no flag)
+constexpr uint32_t kBcPunchThroughBits = KC_BC_PUNCH_THROUGH | 0xff000000u;
+inline uint32_t bc_punch_through_ref(uint32_t flags) { return (flags & KC_BC_PUNCH_THROUGH) ? flags >> 24 : 0u; }
+// kc_bc1_punch_through_block's rule on the host: 16 RGBA8 texels -> the 8 bytes of the block (ref 1..255)
+void bc1_punch_through_block(const uint8_t rgba[64], uint32_t ref, uint8_t block[8]);
 // o = the channels of `img` (forced) as to_u8 sees them (Gray: (v, v, v, 1)); returns the distinct resident planes among the
 // channels of `mask`, which is what a launch under that mask loads
 uint32_t bc_source_operands(const kc_image *img, uint32_t mask, Operand (&o)[4]);
 // one launch of the encoder for `img` (forced already) into `dst`, block rows `row_pitch` bytes apart, on `s`
-int bc_encode(kc_image *img, int format, bool srgb, char *dst, size_t row_pitch, hipStream_t s);
+// (pt_ref != 0: KC_BC_PUNCH_THROUGH with that reference byte)
+int bc_encode(kc_image *img, int format, bool srgb, char *dst, size_t row_pitch, hipStream_t s, uint32_t pt_ref = 0);
 // the launchers of kc_internal.hpp by format: the one place that knows which device unit holds a format's kernels
 hipError_t bc_launch_encode(int format, bool srgb, const Operand op[4], int gray, char *dst, uint64_t row_pitch, uint32_t w, uint32_t h,
-                            uint32_t nt_mask, hipStream_t s);
+                            uint32_t nt_mask, hipStream_t s, uint32_t pt_ref = 0);
 hipError_t bc_launch_decode(int format, bool all_modes, const BcDecodeArgs &a, bool count, uint32_t nt_mask, uint32_t groups, hipStream_t s);
 hipError_t bc_launch_compare(int format, bool srgb, bool all_modes, const Operand op[4], int gray, const char *blocks, uint64_t row_pitch, uint32_t w, uint32_t h,
-                             uint32_t nt_mask, uint32_t groups, unsigned long long *partials, unsigned long long *result, hipStream_t s);
+                             uint32_t nt_mask, uint32_t groups, unsigned long long *partials, unsigned long long *result, hipStream_t s,
+                             uint32_t pt_ref = 0);
 // block decode, the error of an encoding and .dds input (bc_decode.cpp): the bodies of kc_image_from_bc, kc_image_from_bc_device,
 // kc_image_bc_compare, kc_image_bc_error, kc_dds_parse and kc_image_read_dds
 int image_from_bc(const uint8_t *host, size_t host_bytes, uint32_t w, uint32_t h, int format, uint32_t flags, kc_image **out,

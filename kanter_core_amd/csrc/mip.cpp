@@ -170,7 +170,8 @@ static constexpr uint32_t kCoverageFlagBits = KC_MIP_COVERAGE | 0xff000000u;
 int mip_check_coverage_flags(uint32_t flags, const char *who)
 {
     const uint32_t ref = flags >> 24;
-    if ((flags & KC_MIP_COVERAGE) ? ref == 0 : ref != 0) {
+    // a byte if and only if coverage or punch-through: where KC_BC_PUNCH_THROUGH is not accepted it has been refused as an unknown bit
+    if ((flags & KC_MIP_COVERAGE) ? ref == 0 : (ref != 0 && !(flags & KC_BC_PUNCH_THROUGH))) {
         set_error(std::string(who) + ": KC_MIP_COVERAGE goes with a reference byte 1..255 in bits 24-31 (KC_MIP_COVERAGE_REF)");
         return KC_ERR_UNSUPPORTED;
     }
@@ -941,10 +942,11 @@ int image_mip_coverage_info(kc_image *img, uint32_t flags, kc_mip_coverage_level
 
 // ---------------------------------------------------------------- the BC chain
 // flags of the chain exporters: KC_BC_SRGB under kc_image_to_bc's rule (bc_check_flags), plus KC_MIP_PER_LEVEL, KC_MIP_NORMALS,
-// which does not go with KC_BC_SRGB: a vector is not a colour, and KC_MIP_COVERAGE_REF
+// which does not go with KC_BC_SRGB: a vector is not a colour, KC_MIP_COVERAGE_REF, and KC_BC_PUNCH_THROUGH, which shares its byte
 static int bc_mips_check_flags(int format, uint32_t flags, const char *who)
 {
-    KC_TRY(bc_check_flags(format, flags, KC_BC_SRGB | KC_MIP_PER_LEVEL | KC_MIP_NORMALS | KC_MIP_ALPHA_WEIGHT | kCoverageFlagBits, who));
+    KC_TRY(bc_check_flags(format, flags,
+                          KC_BC_SRGB | KC_MIP_PER_LEVEL | KC_MIP_NORMALS | KC_MIP_ALPHA_WEIGHT | kCoverageFlagBits | kBcPunchThroughBits, who));
     if ((flags & KC_MIP_NORMALS) && (flags & KC_BC_SRGB)) {
         set_error(std::string(who) + ": KC_MIP_NORMALS with KC_BC_SRGB");
         return KC_ERR_UNSUPPORTED;
@@ -981,7 +983,8 @@ static int bc_levels_encode(kc_image *const *lv, uint32_t count, int format, uin
     int s = KC_OK;
     for (uint32_t k = 0; k < count && s == KC_OK; ++k) {
         const uint32_t W = lv[k]->w(), H = lv[k]->h();
-        s = bc_encode(lv[k], format, (flags & KC_BC_SRGB) != 0, dst + at, (((size_t)W + 3) / 4) * f.block_bytes, c.stream);
+        s = bc_encode(lv[k], format, (flags & KC_BC_SRGB) != 0, dst + at, (((size_t)W + 3) / 4) * f.block_bytes, c.stream,
+                      bc_punch_through_ref(flags));
         at += bc_level_bytes(W, H, f);
     }
     return s;
@@ -994,7 +997,9 @@ static int bc_mips_encode(kc_image *img, int format, uint32_t flags, char *dst)
     KC_TRY(mip_level_count(img->w(), img->h(), &L));
     std::vector<kc_image *> lv(L, nullptr);
     uint32_t count = 0;
-    KC_TRY(image_build_mips(img, flags & (KC_MIP_PER_LEVEL | KC_MIP_NORMALS | KC_MIP_ALPHA_WEIGHT | kCoverageFlagBits), lv.data(), L, &count));
+    // the byte goes to the chain only with KC_MIP_COVERAGE: under KC_BC_PUNCH_THROUGH alone it is the encoder's
+    const uint32_t chain_bits = KC_MIP_PER_LEVEL | KC_MIP_NORMALS | KC_MIP_ALPHA_WEIGHT | ((flags & KC_MIP_COVERAGE) ? kCoverageFlagBits : 0u);
+    KC_TRY(image_build_mips(img, flags & chain_bits, lv.data(), L, &count));
     const int s = bc_levels_encode(lv.data(), L, format, flags, dst);
     // the level planes go back to the pool here; the pool hands a block out again only to work enqueued on the same stream
     for (kc_image *i : lv) image_release(i);
@@ -1005,12 +1010,13 @@ static int bc_mips_encode(kc_image *img, int format, uint32_t flags, char *dst)
 // `count` levels.  The flags, the arguments, need_init(), then the levels themselves, which are forced.
 static int bc_levels_check(kc_image *const *levels, uint32_t count, int format, uint32_t flags, const void *out, const char *who, size_t *total)
 {
-    KC_TRY(bc_check_flags(format, flags, KC_BC_SRGB, who));
+    KC_TRY(bc_check_flags(format, flags, KC_BC_SRGB | kBcPunchThroughBits, who));
     const BcFormat *f = bc_format(format);
     if (!f) return mip_refuse(who, "unknown format");
     if (!levels || !out || count == 0) return mip_refuse(who, "NULL level array or output, or no level");
     KC_TRY(need_init());
     if (!levels[0]) return mip_refuse(who, "a NULL level");
+    if ((flags & KC_BC_PUNCH_THROUGH) && !levels[0]->is_rgba()) return mip_refuse(who, "KC_BC_PUNCH_THROUGH is for RGBA images");
     const uint32_t w = levels[0]->w(), h = levels[0]->h();
     if (count > 1u + floor_log2(w > h ? w : h)) return mip_refuse(who, "more levels than the chain of level 0's size has");
     uint64_t bx = 0, by = 0;
@@ -1047,8 +1053,8 @@ int image_to_bc_mips(kc_image *img, int format, uint32_t flags, uint8_t *host, s
     if (!bc_format(format)) return mip_refuse("kc_image_to_bc_mips", "unknown format");
     if (!img || !host) return mip_refuse("kc_image_to_bc_mips", "NULL image or host buffer");
     KC_TRY(need_init());
-    if ((flags & (KC_MIP_NORMALS | KC_MIP_COVERAGE | KC_MIP_ALPHA_WEIGHT)) && !img->is_rgba())
-        return mip_refuse("kc_image_to_bc_mips", "KC_MIP_NORMALS, KC_MIP_COVERAGE and KC_MIP_ALPHA_WEIGHT are for RGBA images");
+    if ((flags & (KC_MIP_NORMALS | KC_MIP_COVERAGE | KC_MIP_ALPHA_WEIGHT | KC_BC_PUNCH_THROUGH)) && !img->is_rgba())
+        return mip_refuse("kc_image_to_bc_mips", "KC_MIP_NORMALS, KC_MIP_COVERAGE, KC_MIP_ALPHA_WEIGHT and KC_BC_PUNCH_THROUGH are for RGBA images");
     Context &c = ctx();
     std::lock_guard<std::recursive_mutex> lk(c.mu);
     size_t total = 0;
@@ -1071,8 +1077,8 @@ int image_to_bc_mips_device(kc_image *img, int format, uint32_t flags, void *dev
     if (!img || !device_ptr) return mip_refuse("kc_image_to_bc_mips_device", "NULL image or device pointer");
     if ((uintptr_t)device_ptr % bb) return mip_refuse("kc_image_to_bc_mips_device", "the pointer must be a multiple of the block bytes");
     KC_TRY(need_init());  // an image exists only after kc_init: it is not looked at before
-    if ((flags & (KC_MIP_NORMALS | KC_MIP_COVERAGE | KC_MIP_ALPHA_WEIGHT)) && !img->is_rgba())
-        return mip_refuse("kc_image_to_bc_mips_device", "KC_MIP_NORMALS, KC_MIP_COVERAGE and KC_MIP_ALPHA_WEIGHT are for RGBA images");
+    if ((flags & (KC_MIP_NORMALS | KC_MIP_COVERAGE | KC_MIP_ALPHA_WEIGHT | KC_BC_PUNCH_THROUGH)) && !img->is_rgba())
+        return mip_refuse("kc_image_to_bc_mips_device", "KC_MIP_NORMALS, KC_MIP_COVERAGE, KC_MIP_ALPHA_WEIGHT and KC_BC_PUNCH_THROUGH are for RGBA images");
     Context &c = ctx();
     std::lock_guard<std::recursive_mutex> lk(c.mu);
     size_t total = 0;
@@ -1149,7 +1155,7 @@ int image_write_dds(kc_image *img, const char *path, int format, uint32_t flags,
     std::vector<uint8_t> file(148 + total);
     KC_TRY(dds_header(w, h, format, flags & KC_BC_SRGB, L, file.data(), nullptr));
     if (with_mips) KC_TRY(image_to_bc_mips(img, format, flags, file.data() + 148, total));
-    else KC_TRY(image_to_bc(img, format, flags & KC_BC_SRGB, file.data() + 148, total));
+    else KC_TRY(image_to_bc(img, format, flags & (KC_BC_SRGB | ((flags & KC_BC_PUNCH_THROUGH) ? kBcPunchThroughBits : 0u)), file.data() + 148, total));
     return dds_write_file(path, file, "kc_image_write_dds");
 }
 
@@ -1161,7 +1167,7 @@ int image_levels_write_dds(kc_image *const *levels, uint32_t count, const char *
     size_t total = 0;
     KC_TRY(bc_levels_check(levels, count, format, flags, path, who, &total));
     std::vector<uint8_t> file(148 + total);
-    KC_TRY(dds_header(levels[0]->w(), levels[0]->h(), format, flags, count, file.data(), nullptr));
+    KC_TRY(dds_header(levels[0]->w(), levels[0]->h(), format, flags & KC_BC_SRGB, count, file.data(), nullptr));
     KC_TRY(image_levels_to_bc_mips(levels, count, format, flags, file.data() + 148, total, who));
     return dds_write_file(path, file, who);
 }

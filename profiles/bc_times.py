@@ -2,6 +2,8 @@
 per case -- Gray BC4; RGBA BC1, BC1 sRGB, BC3, BC3 sRGB, BC4, BC5, BC7 and BC7 sRGB; BC6H encode, decode and compare (of its own
 blocks) on planes over [0, 8); random data and a uniform image (every block takes the
 d == 0 / c0 == c1 path; BC7 and BC6H search their palettes all the same)
+-- and BC1 with punch-through alpha (csrc/bc1a.hip, KC_BC_PUNCH_THROUGH at byte 128), linear and sRGB, on random alpha (nearly
+every block mixed: the worst case) and on a cutout of a few large disks (mostly full and empty blocks: the shipping case)
 -- with kc_image_to_device U8 of the same images beside them as the yardstick, and the wall-clock of kc_image_to_bc against
 kc_image_to_u8 plus the numpy reference encoder (tests/bc_ref.py) for the same blocks.
 
@@ -45,13 +47,24 @@ for _data in ("random", "uniform"):
     CASES.append(("RGBA to_device U8 %s" % _data, 4, _data, "u8", 0, False))
     for _kind in ("bc", "decode", "compare"):
         CASES.append(("HDR BC6H %s %s" % ("encode" if _kind == "bc" else _kind, _data), 4, "hdr " + _data, _kind, BC6H, False))
+PT_REF = 128  # the reference byte of the punch-through cases
+for _data in ("cutout random", "cutout disks"):  # kind "pt": BC1 under KC_BC_PUNCH_THROUGH_REF(PT_REF), which reads alpha too
+    for _srgb in (False, True):
+        CASES.append(("RGBA BC1a%s %s" % (" sRGB" if _srgb else "", _data.split()[1]), 4, _data, "pt", 1, _srgb))
+CUTOUTS = ("cutout random", "cutout disks")
 OWN = ("hdr random", "hdr uniform")  # the images whose own BC6H blocks decode and compare read: encoded once, before the cases
-KERNEL = {"u8": "image_export_kernel", "decode": "bc6h_decode_kernel", "compare": "bc6h_compare_kernel"}
+KERNEL = {"u8": "image_export_kernel", "decode": "bc6h_decode_kernel", "compare": "bc6h_compare_kernel", "pt": "bc1a_encode_kernel"}
 
 
 def planes_for(ch, data):
     import numpy as np
     rng = np.random.default_rng(ch)
+    if data == "cutout disks":  # random colour under five large soft-edged disks of alpha: most blocks lie wholly inside or outside
+        y, x = np.mgrid[0:N, 0:N].astype(np.float32)
+        alpha = np.zeros((N, N), np.float32)
+        for cx, cy, r in ((0.25, 0.3, 0.2), (0.7, 0.25, 0.18), (0.5, 0.6, 0.22), (0.2, 0.8, 0.15), (0.8, 0.8, 0.17)):
+            alpha = np.maximum(alpha, np.clip((r * N - np.hypot(x - cx * N, y - cy * N)) / 8.0 + 0.5, 0.0, 1.0))
+        return [rng.random((N, N), dtype=np.float32) for _ in range(3)] + [alpha.astype(np.float32)]
     scale = np.float32(8.0 if data.startswith("hdr ") else 1.0)  # BC6H's planes go above 1
     if data.endswith("random"):
         return [rng.random((N, N), dtype=np.float32) * scale for _ in range(ch)]
@@ -61,6 +74,8 @@ def planes_for(ch, data):
 def case_bytes(ch, kind, fmt):
     if kind == "u8":
         return 4 * ch * PX + 4 * PX
+    if kind == "pt":
+        return 4 * 4 * PX + (N // 4) * (N // 4) * 8  # alpha is read too
     return 4 * (1 if ch == 1 else PLANES[fmt]) * PX + (N // 4) * (N // 4) * BLOCK_BYTES[fmt]  # decode writes what encode reads
 
 
@@ -74,7 +89,7 @@ def run(reps):
     kc.init(0)
     imgs = {}
     for ch in (1, 4):
-        for data in ("random", "uniform") + (OWN if ch == 4 else ()):
+        for data in ("random", "uniform") + (OWN + CUTOUTS if ch == 4 else ()):
             imgs[ch, data] = kc.SlotImage.from_planes(planes_for(ch, data)).materialize()
     own = {data: imgs[4, data].to_bc_torch(BC6H) for data in OWN}
     outs = {f: torch.empty((N // 4, N // 4, BLOCK_BYTES[f]), dtype=torch.uint8, device="cuda") for f in BLOCK_BYTES}
@@ -89,6 +104,8 @@ def run(reps):
             call = lambda: kc.SlotImage.from_bc_torch(own[data], N, N, fmt)  # noqa: E731
         elif kind == "compare":
             call = lambda: img.bc_error(fmt, blocks=own[data])  # noqa: E731
+        elif kind == "pt":
+            call = lambda: img.to_bc_torch(fmt, srgb, out=outs[fmt], punch_through=PT_REF)  # noqa: E731
         else:
             call = lambda: img.to_bc_torch(fmt, srgb, out=outs[fmt])  # noqa: E731
         call()  # warm-up
@@ -122,7 +139,7 @@ def report(trace_csv, log):
     col = lambda key: next(k for k in rows[0] if key in k)  # noqa: E731
     kn, ks, ke = col("Kernel_Name"), col("Start_Timestamp"), col("End_Timestamp")
     rows.sort(key=lambda r: int(r[ks]))
-    names = ("bc_encode_kernel", "bc7_encode_kernel", "bc6h_encode_kernel", "bc6h_decode_kernel", "bc6h_compare_kernel", "image_export_kernel")
+    names = ("bc_encode_kernel", "bc1a_encode_kernel", "bc7_encode_kernel", "bc6h_encode_kernel", "bc6h_decode_kernel", "bc6h_compare_kernel", "image_export_kernel")
     ours = [r for r in rows if any(n in r[kn] for n in names)]
     ours = ours[len(OWN):]
     per = reps + 1
