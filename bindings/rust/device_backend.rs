@@ -114,6 +114,16 @@ impl SlotImage {
         check(unsafe { kc_image_channel_stats(self.raw(), flags, &mut *out) })?;
         Ok(out)
     }
+    /// The signed distance field of a cutout, for alpha-tested magnification (kc_image_distance_field): a new Gray image in which
+    /// every texel holds 0.5 + sd / (2 spread), sd its exact distance in texels to the boundary of the mask "to_u8 writes
+    /// `channel` (None: alpha of an RGBA image, the value of a Gray one) as at least `ref_u8`", positive inside, saturating at 0
+    /// and 1 beyond `spread` (1..KC_SDF_MAX_SPREAD) texels.  `tiles`: the image tiles on both axes (KC_SDF_WRAP).
+    pub fn distance_field(&self, ref_u8: u8, spread: u32, channel: Option<u32>, tiles: bool) -> Result<Self> {
+        let ch = channel.unwrap_or(if self.is_rgba() { 3 } else { 0 });
+        let mut out = ptr::null_mut();
+        check(unsafe { kc_image_distance_field(self.raw(), ch, ref_u8 as u32, spread, if tiles { KC_SDF_WRAP } else { 0 }, &mut out) })?;
+        Ok(wrap(out))
+    }
     /// The image's BC1, BC3, BC4, BC5 or BC7 blocks (kc_image_to_bc), encoded on the device from the bytes to_u8 (`srgb`:
     /// to_u8_srgb, BC1, BC3 and BC7 only) writes: ceil(h/4) rows of ceil(w/4) blocks of 8 (BC1, BC4) or 16 (BC3, BC5, BC7) bytes,
     /// tightly packed.

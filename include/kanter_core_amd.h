@@ -882,6 +882,41 @@ KC_API int kc_image_build_roughness_mips(kc_image *img, uint32_t channel, kc_ima
 KC_API int kc_image_levels_to_bc_mips(kc_image *const *levels, uint32_t count, int format, uint32_t flags, uint8_t *host,
                                       size_t host_bytes);
 KC_API int kc_image_levels_write_dds(kc_image *const *levels, uint32_t count, const char *path, int format, uint32_t flags);
+/* Signed distance fields: the cutout seen from close up.  The chains above keep a cutout right under minification; under
+ * magnification a bilinear tap of a 1-bit or steep alpha gives staircase edges, and the standard answer (alpha-tested
+ * magnification) is to ship the signed distance field of the mask instead: built at the authoring resolution, resized down
+ * hard, stored in one BC4 channel, and tested against 0.5.  kc_image_distance_field builds the field on the device; the rule
+ * is integer arithmetic up to one f64 expression, so the f32 words are exact (tests/sdf_ref.py is the same rule in numpy).
+ *   Inside.   With B = ref_u8 (1..255) a texel of the channel is inside when quant_u8(a) >= B: the "covered" test of
+ *             KC_MIP_COVERAGE and kc_alpha_ref_threshold; NaN counts as inside.  Every other texel is outside.
+ *   D2.       For the texel at integer coordinates (x, y), the smallest dx^2 + dy^2 over all texels of the other class: a plain
+ *             integer.  Texels beyond the image do not exist; with KC_SDF_WRAP the image tiles on both axes and dx, dy are
+ *             torus distances, min(|d|, n - |d|).  If the other class is empty, D2 is "none".
+ *   Cap.      With S = spread (1..KC_SDF_MAX_SPREAD), cap = S S + S + 1 and D2c = min(D2, cap), "none" giving cap.  The largest
+ *             integer D2 with sqrt(D2) < S + 0.5 is S S + S, and a texel at that distance has |dx| <= S and |dy| <= S: a search
+ *             window of radius S on each axis is exact for everything below the cap, and everything else saturates.
+ *   Value.    D2c == cap: v = 1.0f inside, 0.0f outside.  Otherwise, in f64: d = sqrt((double)D2c), sd = inside ? d - 0.5 :
+ *             0.5 - d, v = (float)(0.5 + sd / (2.0 * S)) -- IEEE sqrt, divide and add, one rounding to f32 at the end.  The
+ *             boundary sits midway between texel centres: an inside texel next to an outside one gets 0.5 + 0.25 / S, so
+ *             v >= 0.5 holds exactly for the inside texels of the source.
+ *   kc_image_distance_field  `*out` (+1 reference) = a new Gray image of the source's size; the source is untouched.  channel:
+ *             0 for Gray, 0..3 for RGBA.  A pending chain of the image runs first.  A constant plane launches nothing and gives
+ *             the constant image 1.0 (inside) or 0.0 (outside).  Otherwise two launches whatever the size (kc_stats; counters
+ *             "sdf_columns", "sdf_rows"): per column the distance to the nearest texel of the other class within S rows, then
+ *             per row the minimum over the columns within S; 12 algorithmic bytes per texel (4 read, a 16-bit intermediate
+ *             written and read back, 4 written).  Enqueued on the library's stream; the call does not wait.
+ *             Errors, in this order: KC_ERR_NO_DEVICE before kc_init; flag bits other than KC_SDF_WRAP KC_ERR_UNSUPPORTED; a NULL
+ *             argument, ref_u8 outside 1..255, spread outside 1..KC_SDF_MAX_SPREAD, a channel the image does not have, more
+ *             than 2^31 texels KC_ERR_INVALID_ARG.  Nothing is launched or allocated on a refusal.
+ *   kc_sdf_texel  the value rule on one texel: d2 is taken after capping (d2 >= cap saturates), inside != 0 is the class.
+ *   kc_sdf_cap    cap for a spread.  Both are arithmetic, no kc_init needed; a NULL output or a spread outside
+ *             1..KC_SDF_MAX_SPREAD is KC_ERR_INVALID_ARG.
+ * Not here: anti-aliased (sub-texel) edge estimates from fractional alpha, per-axis wrap, a graph node type, multi-channel fields. */
+#define KC_SDF_WRAP 1u         /* the image tiles on both axes: torus distances */
+#define KC_SDF_MAX_SPREAD 254  /* a capped axis distance, S + 1, fits one byte */
+KC_API int kc_image_distance_field(kc_image *img, uint32_t channel, uint32_t ref_u8, uint32_t spread, uint32_t flags, kc_image **out);
+KC_API int kc_sdf_texel(uint32_t d2, int inside, uint32_t spread, float *v);
+KC_API int kc_sdf_cap(uint32_t spread, uint32_t *cap);
 /* The way back: BC blocks decoded on the device, the error of an encoding measured on the device, and .dds files read.
  * Decoding is integer arithmetic on the block's bytes, so the pixels are exact (tests/bc_decode_ref.py is the same rules in
  * numpy).  Pixel (x, y) is texel 4 (y % 4) + x % 4 of block (x / 4, y / 4); texels of edge blocks outside the image are dropped.

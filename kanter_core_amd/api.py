@@ -809,6 +809,25 @@ def mip_coverage_scale(v, ref):
     return np.float32(s.value)
 
 
+SDF_WRAP = _abi.KC_SDF_WRAP  # SlotImage.distance_field: the image tiles on both axes
+SDF_MAX_SPREAD = _abi.KC_SDF_MAX_SPREAD
+
+
+def sdf_cap(spread):
+    """-> the squared distance at which a distance field of that spread saturates, spread^2 + spread + 1 (kc_sdf_cap; no device)."""
+    cap = C.c_uint32()
+    _check(_lib.load().kc_sdf_cap(spread, C.byref(cap)))
+    return cap.value
+
+
+def sdf_texel(d2, inside, spread):
+    """-> np.float32: what a texel of SlotImage.distance_field(spread=spread) stores for the squared distance `d2` to the nearest
+    texel of the other class (d2 >= sdf_cap(spread): saturated) and its class (kc_sdf_texel; no device)."""
+    v = C.c_float()
+    _check(_lib.load().kc_sdf_texel(d2, int(bool(inside)), spread, C.byref(v)))
+    return np.float32(v.value)
+
+
 def mip_normal_texel(box):
     """-> (3,) float32: what a texel of a normal-map chain (normals=True) stores for the 2 x 2 boxes `box` of R, G, B -- decoded,
     normalised (a vector without a direction becomes (0, 0, 1)) and encoded again in f32 (kc_mip_normal_texel; no device)."""
@@ -1287,6 +1306,18 @@ class SlotImage:
         if not self.is_rgba():
             raise ValueError("alpha_coverage is for RGBA images")
         return int(self.channel_stats(histogram=True).histogram[3][int(ref):].sum())
+
+    def distance_field(self, ref=128, spread=8, channel=None, wrap=False):
+        """-> a Gray SlotImage: the signed distance field of a cutout, for alpha-tested magnification (kc_image_distance_field).
+        A texel of `channel` (None: alpha of an RGBA image, the value of a Gray one) is inside when to_u8 writes it as at least
+        the byte `ref`.  Every texel stores 0.5 + sd / (2 spread), sd its exact Euclidean distance in texels to the boundary
+        between the classes (midway between texel centres), positive inside, saturating at 0 and 1 beyond `spread` texels
+        (1..SDF_MAX_SPREAD); the alpha test at 0.5 gives back the mask.  wrap=True: the image tiles on both axes.  The usual
+        recipe: distance_field(spread=64) at the authoring size, resize_image down, write_dds(..., "bc4")."""
+        ch = (3 if self.is_rgba() else 0) if channel is None else int(channel)
+        out = C.c_void_p()
+        _check(_lib.load().kc_image_distance_field(self._h, ch, ref, spread, SDF_WRAP if wrap else 0, C.byref(out)))
+        return SlotImage(out.value)
 
     def to_bc_mips(self, fmt, srgb=False, per_level=False, normals=False, coverage=None, alpha_weighted=False, punch_through=None):
         """-> one uint8 (ceil(H_k/4), ceil(W_k/4), block bytes) array per level, shaped like to_bc's and views of one buffer

@@ -1088,6 +1088,29 @@ try {
 }
 KC_CATCH
 
+int kc_image_distance_field(kc_image *img, uint32_t channel, uint32_t ref_u8, uint32_t spread, uint32_t flags, kc_image **out)
+try {
+    Lock api_lock(ctx().mu);  // reference counts are plain integers, see kc_plane::refs
+    return image_distance_field(img, channel, ref_u8, spread, flags, out);  // need_init(), the flags, then the arguments
+}
+KC_CATCH
+
+int kc_sdf_texel(uint32_t d2, int inside, uint32_t spread, float *v)
+try {
+    KC_ARG(v && spread >= 1 && spread <= KC_SDF_MAX_SPREAD);
+    *v = sdf_texel(d2, inside != 0, spread);
+    return KC_OK;
+}
+KC_CATCH
+
+int kc_sdf_cap(uint32_t spread, uint32_t *cap)
+try {
+    KC_ARG(cap && spread >= 1 && spread <= KC_SDF_MAX_SPREAD);
+    *cap = sdf_cap(spread);
+    return KC_OK;
+}
+KC_CATCH
+
 int kc_image_from_f32(const float *const host_planes[], int n, uint32_t w, uint32_t h, kc_image **out)
 try {
     Lock api_lock(ctx().mu);  // reference counts are plain integers, see kc_plane::refs

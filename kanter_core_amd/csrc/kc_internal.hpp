@@ -575,5 +575,25 @@ hipError_t launch_coverage_scale(const CoverageArgs &a, uint32_t first_wg, uint3
 // PreviewJob (preview_walk.h) in device memory; prefix: count + 1 words, prefix[j] = the first workgroup of job j, prefix[count] =
 // workgroups.  srgb: R, G, B (Gray: the value) of the jobs that store RGBA8 go through quant_u8_srgb.
 hipError_t launch_preview(const PreviewJob *jobs, const uint32_t *prefix, uint32_t count, uint32_t workgroups, bool srgb, bool nt, hipStream_t s);
+// -- sdf.hip --
+// Signed distance fields (sdf.hip / sdf.cpp): the header's rule as a separable exact transform with windows of radius `spread`.
+// mid: one 16-bit word per texel, rows w words apart -- bits 0-7 the distance along the column to the nearest texel of the
+// other class, capped at spread + 1 (1..255: a texel is its own class), bit 8 the class (1: inside).
+// sdf_columns_kernel<nt, wrap>: src -> mid, one thread per column of a band of KC_SDF_BAND rows, one workgroup per KC_SDF_SEG
+// columns of a band.  sdf_rows_kernel<nt, wrap>: mid -> dst, one workgroup per KC_SDF_SEG columns of KC_SDF_ROWS rows.  Both
+// grids are one-dimensional.  nt: the source loads of the first, the result stores of the second.
+constexpr uint32_t KC_SDF_BAND = 64, KC_SDF_SEG = 256, KC_SDF_ROWS = 4;
+struct SdfArgs {
+    const float *src;
+    uint32_t src_pitch;  // floats
+    uint16_t *mid;
+    float *dst;
+    uint32_t dst_pitch;  // floats
+    uint32_t w, h, ref, spread;  // ref: B, 1..255; spread: S, 1..KC_SDF_MAX_SPREAD
+};
+inline uint64_t sdf_columns_groups(uint32_t w, uint32_t h) { return (uint64_t)((w + KC_SDF_SEG - 1) / KC_SDF_SEG) * ((h + KC_SDF_BAND - 1) / KC_SDF_BAND); }
+inline uint64_t sdf_rows_groups(uint32_t w, uint32_t h) { return (uint64_t)((w + KC_SDF_SEG - 1) / KC_SDF_SEG) * ((h + KC_SDF_ROWS - 1) / KC_SDF_ROWS); }
+hipError_t launch_sdf_columns(const SdfArgs &a, bool wrap, bool nt, hipStream_t s);
+hipError_t launch_sdf_rows(const SdfArgs &a, bool wrap, bool nt, hipStream_t s);
 
 }  // namespace kc

@@ -499,6 +499,11 @@ int image_channel_stats(kc_image *img, uint32_t flags, kc_channel_stats *out);
 uint32_t quant_u8_host(float v);  // streaming.h's quant_u8 on the host
 int stats_buffers(size_t partials_bytes);  // the context's StatsBuffers, with room for that many bytes of partial records
 void channel_stats_release();
+// signed distance fields (sdf.cpp): the rule's arithmetic as kc_sdf_cap and kc_sdf_texel return it, as the device computes it
+// (spread 1..KC_SDF_MAX_SPREAD), and the body of kc_image_distance_field
+uint32_t sdf_cap(uint32_t spread);
+float sdf_texel(uint32_t d2, bool inside, uint32_t spread);
+int image_distance_field(kc_image *img, uint32_t channel, uint32_t ref_u8, uint32_t spread, uint32_t flags, kc_image **out);
 int calculate_size(int policy, const kc_size *sizes, int n, int slot_index, kc_size specific, kc_size *out);
 int mix_process(kc_image *left, kc_image *right, int mix_type, kc_image **out);
 int separate_process(kc_image *in, kc_image *out[4]);
