@@ -2,7 +2,7 @@
 // checks the arguments and the caller's descriptor -- arithmetic first, then that its bytes lie in one allocation of the
 // library's device -- and launches bc.hip's encoder (KC_BC7: bc7.hip's, KC_BC6H: bc6h.hip's) once per call: on the library's stream, ordered
 // against the caller's stream by the two event edges of kc_image_to_device, or into pool staging that is copied to the
-// caller's host memory.  The file also holds what the whole BC family's host side shares (bc_decode.cpp, the BC half of mip.cpp):
+// caller's host memory.  The file also holds what the whole BC family's host side shares (bc_decode.cpp, the BC chain of mip_export.cpp):
 // the format table, the block count and level bytes, the flag rule, the source operands of an image and the choice of a format's device unit.
 #include "kc_runtime.hpp"
 

@@ -453,8 +453,23 @@ int image_bc_compare(kc_image *img, const kc_bc_image *blocks, uint32_t flags, k
 int image_bc_error(kc_image *img, int format, uint32_t flags, kc_bc_error *out);
 int dds_parse(const uint8_t *data, size_t bytes, kc_dds_info *info);
 int image_read_dds(const char *path, uint32_t level, uint32_t flags, kc_image **out, kc_dds_info *info);
-// mip chains and their export (mip.cpp): the bodies of kc_mip_level_count, kc_preview_level, kc_image_build_mips, kc_bc_mip_layout,
-// kc_image_to_bc_mips, kc_image_to_bc_mips_device, kc_dds_header, kc_image_write_dds, kc_mip_normal_texel
+// mip chains (mip.cpp): the bodies of kc_mip_level_count, kc_preview_level, kc_image_build_mips, kc_mip_normal_texel
+inline uint32_t floor_log2(uint32_t v) { return 31u - (uint32_t)__builtin_clz(v); }  // v > 0
+inline uint32_t level_extent(uint32_t v, uint32_t k) { return k < 32 && (v >> k) ? v >> k : 1u; }
+int mip_refuse(const char *who, const char *what);  // records "who: what", returns KC_ERR_INVALID_ARG
+// One launch of a chain's level walk: it reads level k (sw x sh) and writes `fused` levels with the family's pyramid kernel, or,
+// with fused == 0, one level with its one-level kernel; nt: the cache policy of the launch
+struct MipStep {
+    uint32_t k, sw, sh, fused;
+    bool nt;
+    uint32_t last() const { return k + (fused ? fused : 1u); }  // the last level the launch writes; more follow where last() + 1 < L
+};
+// The launches of a chain of L levels of a w x h image, in stream order, for every family; nothing is enqueued.  A launch fuses
+// as many levels as both extents still halve, six at the most; none after an extent has reached 1, and none under `per_level`
+// (KC_MIP_PER_LEVEL).  nt is cache_policy_mask's answer for a launch that reads in0 planes (at level 0; in_below at a level
+// below it) and writes out_planes planes per level.
+std::vector<MipStep> mip_plan(uint32_t w, uint32_t h, uint32_t L, bool per_level, uint32_t in0, uint32_t in_below, uint32_t out_planes,
+                              const Options &o = options());
 int mip_level_count(uint32_t w, uint32_t h, uint32_t *levels);
 int preview_level(uint32_t w, uint32_t h, uint32_t max_extent, uint32_t *level, uint32_t *pw, uint32_t *ph);
 float mip_const_fold(float c);  // ((c + c) + (c + c)) * 0.25f, as the device computes it
@@ -470,20 +485,24 @@ int image_build_roughness_mips(kc_image *img, uint32_t channel, kc_image *normal
 // computes it (mip_alpha_texel returns known)
 float mip_alpha_weight(float a);
 bool mip_alpha_texel(const float p[3], float w, float q[3]);
+int mip_check_alpha_flags(uint32_t flags, const char *who);  // the flag's own refusal: a vector is not a colour
 // KC_MIP_COVERAGE (mip.cpp): the rule's arithmetic as kc_alpha_ref_threshold, kc_mip_coverage_target and kc_mip_coverage_scale
 // return it, the flag rule of the chain entry points (bit 64 and the reference byte in bits 24-31 go together), and the body of
 // kc_image_mip_coverage_info
+constexpr uint32_t kCoverageFlagBits = KC_MIP_COVERAGE | 0xff000000u;
 float alpha_ref_threshold(uint32_t ref_u8);
 int mip_coverage_target(uint32_t w, uint32_t h, uint64_t covered0, uint32_t level, uint64_t *target);
 float mip_coverage_scale(float v, uint32_t ref_u8);
 int mip_check_coverage_flags(uint32_t flags, const char *who);
 int image_mip_coverage_info(kc_image *img, uint32_t flags, kc_mip_coverage_level *out, uint32_t cap, uint32_t *count);
+// the export of mip chains (mip_export.cpp): the bodies of kc_bc_mip_layout, kc_image_to_bc_mips, kc_image_to_bc_mips_device,
+// kc_dds_header, kc_image_write_dds
 int bc_mip_layout(uint32_t w, uint32_t h, int format, uint32_t *levels, size_t *offsets, uint32_t cap, size_t *total_bytes);
 int image_to_bc_mips(kc_image *img, int format, uint32_t flags, uint8_t *host, size_t host_bytes);
 int image_to_bc_mips_device(kc_image *img, int format, uint32_t flags, void *device_ptr, size_t bytes, void *hip_stream);
 int dds_header(uint32_t w, uint32_t h, int format, uint32_t flags, uint32_t levels, uint8_t *out, size_t *bytes);
 int image_write_dds(kc_image *img, const char *path, int format, uint32_t flags, int with_mips);
-// a chain the caller holds (mip.cpp): the bodies of kc_image_levels_to_bc_mips (who: the entry point's name) and kc_image_levels_write_dds
+// a chain the caller holds (mip_export.cpp): the bodies of kc_image_levels_to_bc_mips (who: the entry point's name) and kc_image_levels_write_dds
 int image_levels_to_bc_mips(kc_image *const *levels, uint32_t count, int format, uint32_t flags, uint8_t *host, size_t host_bytes, const char *who);
 int image_levels_write_dds(kc_image *const *levels, uint32_t count, const char *path, int format, uint32_t flags);
 // previews (preview.cpp): the bodies of kc_preview_plan, kc_image_previews, kc_image_previews_device and (given the slots' images)

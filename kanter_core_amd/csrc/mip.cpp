@@ -1,28 +1,26 @@
-// Mip chains and their export (include/kanter_core_amd.h): kc_mip_level_count, kc_preview_level, kc_image_build_mips,
-// kc_image_build_roughness_mips, kc_bc_mip_layout, kc_image_to_bc_mips, kc_image_to_bc_mips_device, kc_image_levels_to_bc_mips,
-// kc_dds_header, kc_image_write_dds, kc_image_levels_write_dds.  The host side does the level arithmetic,
+// Mip chains (include/kanter_core_amd.h): kc_mip_level_count, kc_preview_level, kc_image_build_mips,
+// kc_image_build_roughness_mips, kc_image_mip_coverage_info.  The host side does the level arithmetic,
 // folds constant planes with the device's expression, allocates the level planes and enqueues mip.hip's kernels on the library's
 // stream: the pyramid kernel while both extents still halve (up to six levels per launch), the one-level kernel for the rest and
 // for every level under KC_MIP_PER_LEVEL; under KC_MIP_NORMALS mip_normals.hip's two kernels take R, G, B together and
 // renormalise every level; under KC_MIP_COVERAGE mip_coverage.hip's select and scale give alpha planes of their own; under
 // KC_MIP_ALPHA_WEIGHT mip_alpha.hip's pull and push give colour planes of their own, level 0 included; a roughness
-// chain is mip_roughness.hip's two kernels on the vector of a normal map and the roughness plane together.  The BC chain
-// is bc.cpp's encoder launch once per level; the DDS writer is host code.
+// chain is mip_roughness.hip's two kernels on the vector of a normal map and the roughness plane together.  The file holds the
+// rules' host arithmetic, then the chains: mip_plan decides the launches of a chain, mip_enqueue enqueues them for every
+// family, mip_place places the planes of the levels.  The export of a chain is mip_export.cpp.
+#include <array>
 #include <cmath>
-#include <cstdio>
 #include <limits>
 
 #include "kc_runtime.hpp"
 
 namespace kc {
 
-static int mip_refuse(const char *who, const char *what)
+int mip_refuse(const char *who, const char *what)
 {
     set_error(std::string(who) + ": " + what);
     return KC_ERR_INVALID_ARG;
 }
-
-static uint32_t floor_log2(uint32_t v) { return 31u - (uint32_t)__builtin_clz(v); }  // v > 0
 
 int mip_level_count(uint32_t w, uint32_t h, uint32_t *levels)
 {
@@ -30,8 +28,6 @@ int mip_level_count(uint32_t w, uint32_t h, uint32_t *levels)
     *levels = 1u + floor_log2(w > h ? w : h);
     return KC_OK;
 }
-
-static uint32_t level_extent(uint32_t v, uint32_t k) { return k < 32 && (v >> k) ? v >> k : 1u; }
 
 int preview_level(uint32_t w, uint32_t h, uint32_t max_extent, uint32_t *level, uint32_t *pw, uint32_t *ph)
 {
@@ -155,7 +151,7 @@ bool mip_alpha_texel(const float p[3], float w, float q[3])
 }
 
 // the flag's own refusal: a vector is not a colour
-static int mip_check_alpha_flags(uint32_t flags, const char *who)
+int mip_check_alpha_flags(uint32_t flags, const char *who)
 {
     if ((flags & KC_MIP_ALPHA_WEIGHT) && (flags & KC_MIP_NORMALS)) {
         set_error(std::string(who) + ": KC_MIP_NORMALS with KC_MIP_ALPHA_WEIGHT");
@@ -165,8 +161,6 @@ static int mip_check_alpha_flags(uint32_t flags, const char *who)
 }
 
 // ---------------------------------------------------------------- KC_MIP_COVERAGE: the rule's arithmetic
-static constexpr uint32_t kCoverageFlagBits = KC_MIP_COVERAGE | 0xff000000u;
-
 int mip_check_coverage_flags(uint32_t flags, const char *who)
 {
     const uint32_t ref = flags >> 24;
@@ -218,6 +212,24 @@ float mip_coverage_scale(float v, uint32_t ref_u8)
     }
 }
 
+// ---------------------------------------------------------------- the chains: the plan of the launches
+std::vector<MipStep> mip_plan(uint32_t w, uint32_t h, uint32_t L, bool per_level, uint32_t in0, uint32_t in_below, uint32_t out_planes,
+                              const Options &o)
+{
+    std::vector<MipStep> plan;
+    plan.reserve(L);
+    for (uint32_t k = 0; k + 1 < L; k = plan.back().last()) {  // k: the level the next launch reads
+        const uint32_t sw = level_extent(w, k), sh = level_extent(h, k);
+        const uint32_t small = sw < sh ? sw : sh;
+        const uint32_t fused = per_level || small < 2 ? 0u : floor_log2(small) < 6u ? floor_log2(small) : 6u;
+        const uint32_t n_src = k == 0 ? in0 : in_below;
+        const uint64_t in_bytes = (uint64_t)sw * sh * 4 * n_src;
+        const uint64_t out_bytes = (uint64_t)level_extent(w, k + 1) * level_extent(h, k + 1) * 4 * out_planes;
+        plan.push_back(MipStep{ k, sw, sh, fused, (cache_policy_mask(in_bytes, out_bytes, n_src, o) & 0xffu) != 0 });
+    }
+    return plan;
+}
+
 namespace {
 // The distinct resident planes of an image: slot s reads src[s]; slot_of[ch] = the slot of channel ch, -1 for a constant
 struct MipSlots {
@@ -243,230 +255,268 @@ struct MipChain {
         for (kc_plane *p : scratch) plane_release(p);
     }
 };
-}  // namespace
 
-// The level walk of a chain of L levels of a w x h image, for both families: launch(k, sw, sh, fused, nt) enqueues the launch
-// that reads level k (sw x sh) and writes `fused` levels with the pyramid kernel -- as many as both extents still halve, six at
-// the most -- or, with fused == 0, one level with the one-level kernel: after an extent has reached 1, and at every level under
-// KC_MIP_PER_LEVEL.  nt is the cache policy of a launch that reads in_planes(k) planes and writes out_planes per level.
-template <class Planes, class Launch>
-static int mip_walk(Context &c, uint32_t w, uint32_t h, uint32_t L, bool per_level, uint32_t out_planes, Planes in_planes, Launch launch)
+uint32_t pitch_of(const kc_plane *p) { return (uint32_t)(p->pitch / sizeof(float)); }
+
+// the texels of the levels >= 1
+uint64_t texels_below(uint32_t w, uint32_t h, uint32_t L)
 {
-    for (uint32_t k = 0; k + 1 < L;) {  // k: the level the next launch reads
-        const uint32_t sw = level_extent(w, k), sh = level_extent(h, k);
-        const uint32_t small = sw < sh ? sw : sh;
-        const uint32_t fused = per_level || small < 2 ? 0u : floor_log2(small) < 6u ? floor_log2(small) : 6u;
-        const uint32_t n_src = in_planes(k);
-        const uint64_t in_bytes = (uint64_t)sw * sh * 4 * n_src;
-        const uint64_t out_bytes = (uint64_t)level_extent(w, k + 1) * level_extent(h, k + 1) * 4 * out_planes;
-        const bool nt = (cache_policy_mask(in_bytes, out_bytes, n_src) & 0xffu) != 0;
-        KC_TRY(launch(k, sw, sh, fused, nt));
-        if (nt) c.counters["mip_nt"]++;
-        c.launches++;
-        k += fused ? fused : 1u;
-    }
-    return KC_OK;
+    uint64_t texels = 0;
+    for (uint32_t k = 1; k < L; ++k) texels += (uint64_t)level_extent(w, k) * level_extent(h, k);
+    return texels;
 }
 
-// The plain rule's launches for the resident planes of sl: level k of slot s is slot_planes[(k - 1) * 4 + s]
-static int mip_launch_plain(Context &c, const MipSlots &sl, const std::vector<kc_plane *> &slot_planes, uint32_t w, uint32_t h, uint32_t L,
-                            bool per_level)
-{
-    if (sl.n == 0 || L < 2) return KC_OK;
-    auto plane_at = [&](uint32_t k, int s) -> const kc_plane * { return k == 0 ? sl.src[s] : slot_planes[(size_t)(k - 1) * 4 + s]; };
-    auto pitch_at = [&](uint32_t k) { return (uint32_t)(plane_at(k, 0)->pitch / sizeof(float)); };
-    auto fill = [&](auto &a, uint32_t k, uint32_t sw, uint32_t sh) {  // the source side of a launch that reads level k
-        a.w = sw;
-        a.h = sh;
-        for (int s = 0; s < sl.n; ++s) {
-            a.src[s] = plane_at(k, s)->dptr;
-            a.src_pitch[s] = (uint32_t)(plane_at(k, s)->pitch / sizeof(float));
-        }
-    };
-    KC_TRY(mip_walk(c, w, h, L, per_level, (uint32_t)sl.n, [&](uint32_t) { return (uint32_t)sl.n; },
-                    [&](uint32_t k, uint32_t sw, uint32_t sh, uint32_t fused, bool nt) {
-        if (fused) {
-            MipPyramidArgs a{};
-            fill(a, k, sw, sh);
-            a.n = fused;
-            for (uint32_t j = 0; j < fused; ++j) {
-                for (int s = 0; s < sl.n; ++s) a.dst[s][j] = plane_at(k + 1 + j, s)->dptr;
-                a.dst_pitch[j] = pitch_at(k + 1 + j);
-            }
-            hipError_t e = launch_mip_pyramid(a, (uint32_t)sl.n, nt, c.stream);
-            if (e != hipSuccess) return hip_fail(e, "launch_mip_pyramid");
-            c.counters["mip_pyramid"]++;
-        } else {
-            MipLevelArgs a{};
-            fill(a, k, sw, sh);
-            for (int s = 0; s < sl.n; ++s) a.dst[s] = plane_at(k + 1, s)->dptr;
-            a.dst_pitch = pitch_at(k + 1);
-            hipError_t e = launch_mip_level(a, (uint32_t)sl.n, nt, c.stream);
-            if (e != hipSuccess) return hip_fail(e, "launch_mip_level");
-            c.counters["mip_level"]++;
-        }
-        return (int)KC_OK;
-    }));
-    uint64_t texels = (uint64_t)w * h;  // level 0 read once, every further level written once
-    for (uint32_t j = 1; j < L; ++j) texels += (uint64_t)level_extent(w, j) * level_extent(h, j);
-    c.alg_bytes += 4 * texels * sl.n;
-    return KC_OK;
-}
-
-// KC_MIP_NORMALS: the coupled launches for R, G, B (rgb[c]: the channel's plane at level 0, at least one of them resident; sl:
-// its distinct resident planes); level k of channel c is rgb_planes[(k - 1) * 3 + c], resident at every level
-static int mip_launch_normals(Context &c, const kc_plane *const rgb[3], const MipSlots &sl, const std::vector<kc_plane *> &rgb_planes,
-                              uint32_t w, uint32_t h, uint32_t L, bool per_level)
-{
-    if (L < 2) return KC_OK;
-    // level 0: constants, and channels that read an earlier channel's plane; below it every channel has a plane of its own
+// Level 0 of a family that couples n channels (3 or 4) in one thread: plane[ch], constant or resident; sl: its distinct
+// resident planes; bit ch of const_mask: a constant; bits 2 ch, 2 ch + 1 of `from` (KC_MIP_NORMALS): the earliest channel that
+// reads the same plane, ch itself otherwise.  Below level 0 every channel has a resident plane of its own.
+struct MipSource {
+    const kc_plane *const *plane;
+    int n;
+    MipSlots sl;
     uint32_t const_mask = 0, from = 0;
-    for (int ch = 0; ch < 3; ++ch) {
-        int f = ch;
-        if (sl.slot_of[ch] < 0) const_mask |= 1u << ch;
-        else
-            for (int e = ch - 1; e >= 0; --e)
-                if (sl.slot_of[e] == sl.slot_of[ch]) f = e;
-        from |= (uint32_t)f << (2 * ch);
+    MipSource(const kc_plane *const *planes, int channels) : plane(planes), n(channels)
+    {
+        for (int ch = 0; ch < n; ++ch) {
+            sl.add(ch, plane[ch]);
+            int f = ch;
+            if (sl.slot_of[ch] < 0) const_mask |= 1u << ch;
+            else
+                for (int e = ch - 1; e >= 0; --e)
+                    if (sl.slot_of[e] == sl.slot_of[ch]) f = e;
+            from |= (uint32_t)f << (2 * ch);
+        }
     }
-    auto fill = [&](auto &a, uint32_t k, uint32_t sw, uint32_t sh) {  // the source side of a launch that reads level k
-        a.w = sw;
-        a.h = sh;
-        for (int ch = 0; ch < 3; ++ch) {
-            const kc_plane *p = k == 0 ? rgb[ch] : rgb_planes[(size_t)(k - 1) * 3 + ch];
-            const bool is_const = k == 0 && ((const_mask >> ch) & 1u);
+    // the source side of the launch s in any of the coupled argument blocks: level 0, or the planes `below` of level s.k
+    template <class Args> void fill(Args &a, const MipStep &s, const kc_plane *const *below) const
+    {
+        a.w = s.sw;
+        a.h = s.sh;
+        for (int ch = 0; ch < n; ++ch) {
+            const kc_plane *p = s.k == 0 ? plane[ch] : below[ch];
+            const bool is_const = s.k == 0 && ((const_mask >> ch) & 1u);
             a.src[ch] = is_const ? nullptr : p->dptr;
-            a.src_pitch[ch] = is_const ? 0u : (uint32_t)(p->pitch / sizeof(float));
+            a.src_pitch[ch] = is_const ? 0u : pitch_of(p);
             a.cval[ch] = is_const ? p->cval : 0.0f;
         }
-        a.const_mask = k == 0 ? const_mask : 0u;
-        a.from = k == 0 ? from : (0u | 1u << 2 | 2u << 4);
-    };
-    KC_TRY(mip_walk(c, w, h, L, per_level, 3u, [&](uint32_t k) { return k == 0 ? (uint32_t)sl.n : 3u; },
-                    [&](uint32_t k, uint32_t sw, uint32_t sh, uint32_t fused, bool nt) {
-        if (fused) {
-            NormalPyramidArgs a{};
-            fill(a, k, sw, sh);
-            a.n = fused;
-            for (uint32_t j = 0; j < fused; ++j) {
-                for (int ch = 0; ch < 3; ++ch) a.dst[ch][j] = rgb_planes[(size_t)(k + j) * 3 + ch]->dptr;
-                a.dst_pitch[j] = (uint32_t)(rgb_planes[(size_t)(k + j) * 3]->pitch / sizeof(float));
-            }
-            hipError_t e = launch_normal_pyramid(a, nt, c.stream);
-            if (e != hipSuccess) return hip_fail(e, "launch_normal_pyramid");
-            c.counters["mip_normals_pyramid"]++;
-        } else {
-            NormalLevelArgs a{};
-            fill(a, k, sw, sh);
-            for (int ch = 0; ch < 3; ++ch) a.dst[ch] = rgb_planes[(size_t)k * 3 + ch]->dptr;
-            a.dst_pitch = (uint32_t)(rgb_planes[(size_t)k * 3]->pitch / sizeof(float));
-            hipError_t e = launch_normal_level(a, nt, c.stream);
-            if (e != hipSuccess) return hip_fail(e, "launch_normal_level");
-            c.counters["mip_normals_level"]++;
-        }
-        return (int)KC_OK;
-    }));
-    uint64_t written = 0;  // every distinct resident plane of level 0 read once, three planes of every further level written once
-    for (uint32_t j = 1; j < L; ++j) written += (uint64_t)level_extent(w, j) * level_extent(h, j);
-    c.alg_bytes += 4 * (uint64_t)w * h * sl.n + 12 * written;
+        a.const_mask = s.k == 0 ? const_mask : 0u;
+    }
+};
+
+// ---------------------------------------------------------------- the chains: one enqueue loop, and the families
+// The state planes of a launch: the boxes of the last level it writes, which the next launch reads instead of stored planes
+// (four under the roughness rule, three under KC_MIP_ALPHA_WEIGHT); all NULL where a family has none or no level follows.
+using MipState = std::array<kc_plane *, 4>;
+
+// The n state planes of a W x H level, from the pool, held in mc.scratch until the call returns (everything that reads them is
+// enqueued by then); pitch: of the level's stored planes, which the kernels take for the state planes' too
+int mip_state_planes(MipChain &mc, int n, uint32_t W, uint32_t H, size_t pitch, const char *who, MipState &out)
+{
+    for (int ch = 0; ch < n; ++ch) {
+        KC_TRY(plane_new_mem(W, H, &out[ch]));
+        mc.scratch.push_back(out[ch]);
+        if (out[ch]->pitch != pitch) return mip_refuse(who, "planes of one size differ in pitch");
+    }
     return KC_OK;
 }
 
-// kc_image_build_roughness_mips: the coupled launches for the vector of the normals and the roughness (src0: X, Y, Z of the
-// normal map and the roughness plane at level 0, constant or resident, at least one of the first three resident); level k's
-// stored plane is dst_planes[k - 1].  The four plain boxes of the last level a launch writes are the next launch's sources:
-// state planes from the pool, held in mc.scratch until the call returns (everything that reads them is enqueued by then).
-static int mip_launch_roughness(Context &c, const kc_plane *const src0[4], const std::vector<kc_plane *> &dst_planes, MipChain &mc, float power,
+// a field of an argument block that a pyramid kernel has once per fused level and a one-level kernel once
+template <class T, size_t N> T &at_level(T (&field)[N], uint32_t j) { return field[j]; }
+template <class T> T &at_level(T &field, uint32_t) { return field; }
+
+// Enqueues the launches of `plan` (a chain of L levels of a w x h image) for the family f on the library's stream and counts
+// them.  A family names its two argument blocks, their launchers and counters and the state planes it passes from launch to
+// launch (kState, with level_pitch and kWho for mip_state_planes); its fill(a, s, in, out) writes either block for the step s,
+// where `in` are the state planes of level s.k and `out` those of level s.last().  *state_texels grows by the texels of every
+// level that got state planes.
+template <class Family>
+int mip_enqueue(Context &c, const Family &f, MipChain &mc, const std::vector<MipStep> &plan, uint32_t w, uint32_t h, uint32_t L,
+                uint64_t *state_texels = nullptr)
+{
+    MipState in{}, out{};
+    for (const MipStep &s : plan) {
+        out = MipState{};
+        if constexpr (Family::kState > 0)
+            if (s.last() + 1 < L) {  // more levels follow
+                const uint32_t W = level_extent(w, s.last()), H = level_extent(h, s.last());
+                KC_TRY(mip_state_planes(mc, Family::kState, W, H, f.level_pitch(s.last()), Family::kWho, out));
+                *state_texels += (uint64_t)W * H;
+            }
+        hipError_t e;
+        if (s.fused) {
+            typename Family::Pyramid a{};
+            a.n = s.fused;
+            f.fill(a, s, in, out);
+            e = f.launch(a, s, c.stream);
+        } else {
+            typename Family::Level a{};
+            f.fill(a, s, in, out);
+            e = f.launch(a, s, c.stream);
+        }
+        if (e != hipSuccess) return hip_fail(e, s.fused ? Family::kPyramid : Family::kLevel);
+        c.counters[s.fused ? Family::kPyramidCounter : Family::kLevelCounter]++;
+        if (s.nt) c.counters["mip_nt"]++;
+        c.launches++;
+        in = out;
+    }
+    return KC_OK;
+}
+
+// The plain rule on the resident planes of sl: level k of slot s is slot_planes[(k - 1) * 4 + s]
+struct PlainFamily {
+    using Pyramid = MipPyramidArgs;
+    using Level = MipLevelArgs;
+    static constexpr int kState = 0;
+    static constexpr const char *kPyramid = "launch_mip_pyramid", *kLevel = "launch_mip_level", *kPyramidCounter = "mip_pyramid",
+                                *kLevelCounter = "mip_level";
+    const MipSlots &sl;
+    const std::vector<kc_plane *> &slot_planes;
+    const kc_plane *at(uint32_t k, int s) const { return k == 0 ? sl.src[s] : slot_planes[(size_t)(k - 1) * 4 + s]; }
+    template <class Args> void fill(Args &a, const MipStep &s, const MipState &, const MipState &) const
+    {
+        a.w = s.sw;
+        a.h = s.sh;
+        for (int p = 0; p < sl.n; ++p) {
+            a.src[p] = at(s.k, p)->dptr;
+            a.src_pitch[p] = pitch_of(at(s.k, p));
+        }
+        for (uint32_t j = 0, k = s.k + 1; k <= s.last(); ++j, ++k) {
+            for (int p = 0; p < sl.n; ++p) at_level(a.dst[p], j) = at(k, p)->dptr;
+            at_level(a.dst_pitch, j) = pitch_of(at(k, 0));
+        }
+    }
+    hipError_t launch(const Pyramid &a, const MipStep &s, hipStream_t stream) const { return launch_mip_pyramid(a, (uint32_t)sl.n, s.nt, stream); }
+    hipError_t launch(const Level &a, const MipStep &s, hipStream_t stream) const { return launch_mip_level(a, (uint32_t)sl.n, s.nt, stream); }
+};
+
+// KC_MIP_NORMALS: R, G, B coupled (src: level 0, at least one of the three resident); level k of channel c is
+// own[(k - 1) * 4 + c], resident at every level
+struct NormalFamily {
+    using Pyramid = NormalPyramidArgs;
+    using Level = NormalLevelArgs;
+    static constexpr int kState = 0;
+    static constexpr const char *kPyramid = "launch_normal_pyramid", *kLevel = "launch_normal_level",
+                                *kPyramidCounter = "mip_normals_pyramid", *kLevelCounter = "mip_normals_level";
+    const MipSource &src;
+    const std::vector<kc_plane *> &own;
+    kc_plane *const *at(uint32_t k) const { return &own[(size_t)(k - 1) * 4]; }  // k >= 1
+    template <class Args> void fill(Args &a, const MipStep &s, const MipState &, const MipState &) const
+    {
+        src.fill(a, s, s.k ? at(s.k) : nullptr);
+        a.from = s.k == 0 ? src.from : (0u | 1u << 2 | 2u << 4);
+        for (uint32_t j = 0, k = s.k + 1; k <= s.last(); ++j, ++k) {
+            for (int ch = 0; ch < 3; ++ch) at_level(a.dst[ch], j) = at(k)[ch]->dptr;
+            at_level(a.dst_pitch, j) = pitch_of(at(k)[0]);
+        }
+    }
+    hipError_t launch(const Pyramid &a, const MipStep &s, hipStream_t stream) const { return launch_normal_pyramid(a, s.nt, stream); }
+    hipError_t launch(const Level &a, const MipStep &s, hipStream_t stream) const { return launch_normal_level(a, s.nt, stream); }
+};
+
+// kc_image_build_roughness_mips: the vector of the normals and the roughness coupled (src: X, Y, Z of the normal map and the
+// roughness plane at level 0, at least one of the first three resident); level k's stored plane is own[(k - 1) * 4 + channel].
+// The four plain boxes of the last level a launch writes are the next launch's sources: its state planes.
+struct RoughnessFamily {
+    using Pyramid = RoughnessPyramidArgs;
+    using Level = RoughnessLevelArgs;
+    static constexpr int kState = 4;
+    static constexpr const char *kPyramid = "launch_roughness_pyramid", *kLevel = "launch_roughness_level",
+                                *kPyramidCounter = "mip_roughness_pyramid", *kLevelCounter = "mip_roughness_level",
+                                *kWho = "kc_image_build_roughness_mips";
+    const MipSource &src;
+    const std::vector<kc_plane *> &own;
+    uint32_t channel;
+    float power;
+    const kc_plane *at(uint32_t k) const { return own[(size_t)(k - 1) * 4 + channel]; }  // k >= 1
+    size_t level_pitch(uint32_t k) const { return at(k)->pitch; }
+    template <class Args> void fill(Args &a, const MipStep &s, const MipState &in, const MipState &out) const
+    {
+        src.fill(a, s, in.data());
+        a.power = power;
+        for (int ch = 0; ch < 4; ++ch) a.state[ch] = out[ch] ? out[ch]->dptr : nullptr;
+        for (uint32_t j = 0, k = s.k + 1; k <= s.last(); ++j, ++k) {
+            at_level(a.dst, j) = at(k)->dptr;
+            at_level(a.dst_pitch, j) = pitch_of(at(k));
+        }
+    }
+    hipError_t launch(const Pyramid &a, const MipStep &s, hipStream_t stream) const { return launch_roughness_pyramid(a, s.k == 0, s.nt, stream); }
+    hipError_t launch(const Level &a, const MipStep &s, hipStream_t stream) const { return launch_roughness_level(a, s.k == 0, s.nt, stream); }
+};
+
+// KC_MIP_ALPHA_WEIGHT, the pull: the premultiplied colour and the weight coupled (src: R, G, B, alpha at level 0, the colours
+// or alpha resident); level k's colour planes are col[3 k + c], level 0 included, and weight[k] the weight plane of a level
+// k >= 1.  P_c of the last level a launch writes are the next launch's sources beside that level's weight: its state planes.
+struct AlphaPullFamily {
+    using Pyramid = AlphaPullPyramidArgs;
+    using Level = AlphaPullLevelArgs;
+    static constexpr int kState = 3;
+    static constexpr const char *kPyramid = "launch_alpha_pull_pyramid", *kLevel = "launch_alpha_pull_level",
+                                *kPyramidCounter = "mip_alpha_pull_pyramid", *kLevelCounter = "mip_alpha_pull_level",
+                                *kWho = "kc_image_build_mips";
+    const MipSource &src;
+    const std::vector<kc_plane *> &col, &weight;
+    uint32_t L;
+    size_t level_pitch(uint32_t k) const { return weight[k]->pitch; }
+    template <class Args> void fill(Args &a, const MipStep &s, const MipState &in, const MipState &out) const
+    {
+        const kc_plane *const below[4] = { in[0], in[1], in[2], weight[s.k] };
+        src.fill(a, s, below);
+        for (int ch = 0; ch < 3; ++ch) {
+            a.dst0[ch] = s.k == 0 ? col[ch]->dptr : nullptr;
+            a.state[ch] = out[ch] ? out[ch]->dptr : nullptr;
+        }
+        a.dst0_pitch = s.k == 0 ? pitch_of(col[0]) : 0u;
+        for (uint32_t j = 0, k = s.k + 1; k <= s.last() && k < L; ++j, ++k) {  // k == L on a 1 x 1 image: level 0's colour alone
+            for (int ch = 0; ch < 3; ++ch) at_level(a.dst[ch], j) = col[3 * k + ch]->dptr;
+            at_level(a.wdst, j) = weight[k]->dptr;
+            at_level(a.dst_pitch, j) = pitch_of(weight[k]);
+        }
+    }
+    hipError_t launch(const Pyramid &a, const MipStep &s, hipStream_t stream) const { return launch_alpha_pull_pyramid(a, s.k == 0, s.nt, stream); }
+    hipError_t launch(const Level &a, const MipStep &s, hipStream_t stream) const { return launch_alpha_pull_level(a, s.k == 0, s.nt, stream); }
+};
+}  // namespace
+
+// The plain rule's launches for the resident planes of sl
+static int mip_launch_plain(Context &c, const MipSlots &sl, const std::vector<kc_plane *> &slot_planes, MipChain &mc, uint32_t w, uint32_t h,
+                            uint32_t L, bool per_level)
+{
+    if (sl.n == 0 || L < 2) return KC_OK;
+    KC_TRY(mip_enqueue(c, PlainFamily{ sl, slot_planes }, mc, mip_plan(w, h, L, per_level, (uint32_t)sl.n, (uint32_t)sl.n, (uint32_t)sl.n), w, h, L));
+    c.alg_bytes += 4 * ((uint64_t)w * h + texels_below(w, h, L)) * sl.n;  // level 0 read once, every further level written once
+    return KC_OK;
+}
+
+// KC_MIP_NORMALS: the coupled launches for R, G, B
+static int mip_launch_normals(Context &c, const MipSource &rgb, const std::vector<kc_plane *> &own, MipChain &mc, uint32_t w, uint32_t h, uint32_t L,
+                              bool per_level)
+{
+    if (L < 2) return KC_OK;
+    KC_TRY(mip_enqueue(c, NormalFamily{ rgb, own }, mc, mip_plan(w, h, L, per_level, (uint32_t)rgb.sl.n, 3u, 3u), w, h, L));
+    // every distinct resident plane of level 0 read once, three planes of every further level written once
+    c.alg_bytes += 4 * (uint64_t)w * h * rgb.sl.n + 12 * texels_below(w, h, L);
+    return KC_OK;
+}
+
+// kc_image_build_roughness_mips: the coupled launches for the vector of the normals and the roughness
+static int mip_launch_roughness(Context &c, const MipSource &src, const std::vector<kc_plane *> &own, uint32_t channel, MipChain &mc, float power,
                                 uint32_t w, uint32_t h, uint32_t L, bool per_level)
 {
     if (L < 2) return KC_OK;
-    MipSlots sl;  // the distinct resident planes of level 0
-    uint32_t const_mask = 0;
-    for (int ch = 0; ch < 4; ++ch) {
-        sl.add(ch, src0[ch]);
-        if (sl.slot_of[ch] < 0) const_mask |= 1u << ch;
-    }
-    const kc_plane *state[4] = { nullptr, nullptr, nullptr, nullptr };  // of the level the next launch reads
     uint64_t state_texels = 0;
-    auto fill = [&](auto &a, uint32_t k, uint32_t sw, uint32_t sh, uint32_t last) -> int {  // a launch that reads level k and ends at `last`
-        a.w = sw;
-        a.h = sh;
-        a.power = power;
-        for (int ch = 0; ch < 4; ++ch) {
-            const kc_plane *p = k == 0 ? src0[ch] : state[ch];
-            const bool is_const = k == 0 && ((const_mask >> ch) & 1u);
-            a.src[ch] = is_const ? nullptr : p->dptr;
-            a.src_pitch[ch] = is_const ? 0u : (uint32_t)(p->pitch / sizeof(float));
-            a.cval[ch] = is_const ? p->cval : 0.0f;
-        }
-        a.const_mask = k == 0 ? const_mask : 0u;
-        for (int ch = 0; ch < 4; ++ch) {
-            state[ch] = nullptr;
-            a.state[ch] = nullptr;
-        }
-        if (last + 1 < L) {  // more levels follow
-            const uint32_t W = level_extent(w, last), H = level_extent(h, last);
-            for (int ch = 0; ch < 4; ++ch) {
-                kc_plane *p = nullptr;
-                KC_TRY(plane_new_mem(W, H, &p));
-                mc.scratch.push_back(p);
-                if (p->pitch != dst_planes[last - 1]->pitch) return mip_refuse("kc_image_build_roughness_mips", "planes of one size differ in pitch");
-                state[ch] = p;
-                a.state[ch] = p->dptr;
-            }
-            state_texels += (uint64_t)W * H;
-        }
-        return KC_OK;
-    };
-    KC_TRY(mip_walk(c, w, h, L, per_level, 1u, [&](uint32_t k) { return k == 0 ? (uint32_t)sl.n : 4u; },
-                    [&](uint32_t k, uint32_t sw, uint32_t sh, uint32_t fused, bool nt) {
-        if (fused) {
-            RoughnessPyramidArgs a{};
-            KC_TRY(fill(a, k, sw, sh, k + fused));
-            a.n = fused;
-            for (uint32_t j = 0; j < fused; ++j) {
-                a.dst[j] = dst_planes[k + j]->dptr;
-                a.dst_pitch[j] = (uint32_t)(dst_planes[k + j]->pitch / sizeof(float));
-            }
-            hipError_t e = launch_roughness_pyramid(a, k == 0, nt, c.stream);
-            if (e != hipSuccess) return hip_fail(e, "launch_roughness_pyramid");
-            c.counters["mip_roughness_pyramid"]++;
-        } else {
-            RoughnessLevelArgs a{};
-            KC_TRY(fill(a, k, sw, sh, k + 1));
-            a.dst = dst_planes[k]->dptr;
-            a.dst_pitch = (uint32_t)(dst_planes[k]->pitch / sizeof(float));
-            hipError_t e = launch_roughness_level(a, k == 0, nt, c.stream);
-            if (e != hipSuccess) return hip_fail(e, "launch_roughness_level");
-            c.counters["mip_roughness_level"]++;
-        }
-        return (int)KC_OK;
-    }));
+    KC_TRY(mip_enqueue(c, RoughnessFamily{ src, own, channel, power }, mc, mip_plan(w, h, L, per_level, (uint32_t)src.sl.n, 4u, 1u), w, h, L,
+                       &state_texels));
     // every distinct resident plane of level 0 read once, one plane of every further level written once, the four state planes
     // of a level written once and read once
-    uint64_t written = 0;
-    for (uint32_t j = 1; j < L; ++j) written += (uint64_t)level_extent(w, j) * level_extent(h, j);
-    c.alg_bytes += 4 * (uint64_t)w * h * sl.n + 4 * written + 32 * state_texels;
+    c.alg_bytes += 4 * (uint64_t)w * h * src.sl.n + 4 * texels_below(w, h, L) + 32 * state_texels;
     return KC_OK;
 }
 
-// KC_MIP_ALPHA_WEIGHT: the pull launches for the premultiplied colour and the weight (src0: R, G, B, alpha at level 0, constant
-// or resident, the colours or alpha resident) and the push launch over all levels; level k's colour planes are col[3 k + c],
-// level 0 included.  The weight of every level >= 1 lives in a scratch plane, and P_c of the last level a launch writes in
-// three state planes that the next launch reads: all from the pool, held in mc.scratch until the call returns (everything
-// that reads them is enqueued by then).
-static int mip_launch_alpha(Context &c, const kc_plane *const src0[4], const std::vector<kc_plane *> &col, MipChain &mc, uint32_t w, uint32_t h,
-                            uint32_t L, bool per_level)
+// KC_MIP_ALPHA_WEIGHT: the pull launches and the push launch over all levels.  The weight of every level >= 1 lives in a
+// scratch plane from the pool, held in mc.scratch like the state planes.
+static int mip_launch_alpha(Context &c, const MipSource &src, const std::vector<kc_plane *> &col, MipChain &mc, uint32_t w, uint32_t h, uint32_t L,
+                            bool per_level)
 {
-    const char *who = "kc_image_build_mips";
     if (L > KC_ALPHA_MAX_LEVELS) return mip_refuse("KC_MIP_ALPHA_WEIGHT", "more levels than the job table holds");
-    MipSlots sl;  // the distinct resident planes of level 0
-    uint32_t const_mask = 0;
-    for (int ch = 0; ch < 4; ++ch) {
-        sl.add(ch, src0[ch]);
-        if (sl.slot_of[ch] < 0) const_mask |= 1u << ch;
-    }
-    auto pitch_of = [](const kc_plane *p) { return (uint32_t)(p->pitch / sizeof(float)); };
     std::vector<kc_plane *> weight(L, nullptr);  // [level], levels >= 1
     for (uint32_t k = 0; k < L; ++k) {
         if (k) {
@@ -474,83 +524,21 @@ static int mip_launch_alpha(Context &c, const kc_plane *const src0[4], const std
             mc.scratch.push_back(weight[k]);
         }
         for (int ch = 0; ch < 3; ++ch)
-            if (col[3 * k + ch]->pitch != (k ? weight[k] : col[0])->pitch) return mip_refuse(who, "planes of one size differ in pitch");
+            if (col[3 * k + ch]->pitch != (k ? weight[k] : col[0])->pitch) return mip_refuse(AlphaPullFamily::kWho, "planes of one size differ in pitch");
     }
-    const kc_plane *state[3] = { nullptr, nullptr, nullptr };  // of the level the next launch reads
     uint64_t state_texels = 0;
-    auto fill = [&](auto &a, uint32_t k, uint32_t sw, uint32_t sh, uint32_t last) -> int {  // a launch that reads level k and ends at `last`
-        a.w = sw;
-        a.h = sh;
-        for (int ch = 0; ch < 4; ++ch) {
-            const kc_plane *p = k == 0 ? src0[ch] : ch < 3 ? state[ch] : weight[k];
-            const bool is_const = k == 0 && ((const_mask >> ch) & 1u);
-            a.src[ch] = is_const ? nullptr : p->dptr;
-            a.src_pitch[ch] = is_const ? 0u : pitch_of(p);
-            a.cval[ch] = is_const ? p->cval : 0.0f;
-        }
-        a.const_mask = k == 0 ? const_mask : 0u;
-        for (int ch = 0; ch < 3; ++ch) {
-            a.dst0[ch] = k == 0 ? col[ch]->dptr : nullptr;
-            state[ch] = nullptr;
-            a.state[ch] = nullptr;
-        }
-        a.dst0_pitch = k == 0 ? pitch_of(col[0]) : 0u;
-        if (last + 1 < L && last > k) {  // more levels follow
-            const uint32_t W = level_extent(w, last), H = level_extent(h, last);
-            for (int ch = 0; ch < 3; ++ch) {
-                kc_plane *p = nullptr;
-                KC_TRY(plane_new_mem(W, H, &p));
-                mc.scratch.push_back(p);
-                if (p->pitch != weight[last]->pitch) return mip_refuse(who, "planes of one size differ in pitch");
-                state[ch] = p;
-                a.state[ch] = p->dptr;
-            }
-            state_texels += (uint64_t)W * H;
-        }
-        return KC_OK;
-    };
-    if (L == 1) {  // a 1 x 1 image: no level to pull, level 0's colour alone
-        AlphaPullLevelArgs a{};
-        KC_TRY(fill(a, 0, w, h, 0));
-        hipError_t e = launch_alpha_pull_level(a, true, false, c.stream);
-        if (e != hipSuccess) return hip_fail(e, "launch_alpha_pull_level");
-        c.counters["mip_alpha_pull_level"]++;
-        c.launches++;
-    }
-    KC_TRY(mip_walk(c, w, h, L, per_level, 4u, [&](uint32_t k) { return k == 0 ? (uint32_t)sl.n : 4u; },
-                    [&](uint32_t k, uint32_t sw, uint32_t sh, uint32_t fused, bool nt) {
-        if (fused) {
-            AlphaPullPyramidArgs a{};
-            KC_TRY(fill(a, k, sw, sh, k + fused));
-            a.n = fused;
-            for (uint32_t j = 0; j < fused; ++j) {
-                for (int ch = 0; ch < 3; ++ch) a.dst[ch][j] = col[3 * (k + 1 + j) + ch]->dptr;
-                a.wdst[j] = weight[k + 1 + j]->dptr;
-                a.dst_pitch[j] = pitch_of(weight[k + 1 + j]);
-            }
-            hipError_t e = launch_alpha_pull_pyramid(a, k == 0, nt, c.stream);
-            if (e != hipSuccess) return hip_fail(e, "launch_alpha_pull_pyramid");
-            c.counters["mip_alpha_pull_pyramid"]++;
-        } else {
-            AlphaPullLevelArgs a{};
-            KC_TRY(fill(a, k, sw, sh, k + 1));
-            for (int ch = 0; ch < 3; ++ch) a.dst[ch] = col[3 * (k + 1) + ch]->dptr;
-            a.wdst = weight[k + 1]->dptr;
-            a.dst_pitch = pitch_of(weight[k + 1]);
-            hipError_t e = launch_alpha_pull_level(a, k == 0, nt, c.stream);
-            if (e != hipSuccess) return hip_fail(e, "launch_alpha_pull_level");
-            c.counters["mip_alpha_pull_level"]++;
-        }
-        return (int)KC_OK;
-    }));
+    // a 1 x 1 image has no level to pull: one one-level launch for level 0's colour, which no level follows
+    const std::vector<MipStep> plan = L == 1 ? std::vector<MipStep>{ MipStep{ 0, w, h, 0, false } }
+                                             : mip_plan(w, h, L, per_level, (uint32_t)src.sl.n, 4u, 4u);
+    KC_TRY(mip_enqueue(c, AlphaPullFamily{ src, col, weight, L }, mc, plan, w, h, L, &state_texels));
     AlphaPushArgs pa{};
     uint32_t wgs = 0;
-    uint64_t below = 0;  // the texels of the levels >= 1
+    const bool a_const = (src.const_mask & 8u) != 0;
     for (uint32_t k = 0; k < L; ++k) {
         AlphaPushJob &J = pa.jobs[k];
         for (int ch = 0; ch < 3; ++ch) J.dst[ch] = col[3 * k + ch]->dptr;
         J.dst_pitch = pitch_of(col[3 * k]);
-        const kc_plane *ws = k ? weight[k] : (const_mask & 8u) ? nullptr : src0[3];
+        const kc_plane *ws = k ? weight[k] : a_const ? nullptr : src.plane[3];
         J.wsrc = ws ? ws->dptr : nullptr;
         J.w_pitch = ws ? pitch_of(ws) : 0u;
         J.w = level_extent(w, k);
@@ -558,7 +546,6 @@ static int mip_launch_alpha(Context &c, const kc_plane *const src0[4], const std
         J.first_wg = wgs;
         J.wgs = alpha_push_job_wgs(J.w, J.h);
         wgs += J.wgs;
-        if (k) below += (uint64_t)J.w * J.h;
     }
     pa.levels = L;
     hipError_t e = launch_alpha_push(pa, wgs, c.stream);
@@ -568,36 +555,36 @@ static int mip_launch_alpha(Context &c, const kc_plane *const src0[4], const std
     // the pull: every distinct resident plane of level 0 read once, level 0's three colour planes written, three colours and the
     // weight of every further level written, the three state planes of a level written and read and its weight read; the push:
     // level 0's alpha where it is resident and every weight read (what it writes depends on the data and is not counted)
-    const uint64_t n0 = (uint64_t)w * h;
-    c.alg_bytes += 4 * n0 * sl.n + 12 * n0 + 16 * below + 28 * state_texels + ((const_mask & 8u) ? 0 : 4 * n0) + 4 * below;
+    const uint64_t n0 = (uint64_t)w * h, below = texels_below(w, h, L);
+    c.alg_bytes += 4 * n0 * src.sl.n + 12 * n0 + 16 * below + 28 * state_texels + (a_const ? 0 : 4 * n0) + 4 * below;
     return KC_OK;
 }
 
-// KC_MIP_COVERAGE: the select over alpha's plain chain (plain[k]: p_k, plain[0] the image's alpha; L levels of a w x h image,
-// w h <= 2^31) and, with `scaled` (scaled[k - 1]: d_k), the scale launch.  The records and the histograms live in
-// `scratch`, which the caller gives back to the pool once everything that reads it is enqueued (or waited for); *rec = the L
-// device records.  Launches: a count and a pick per pass, three passes when there is a level >= 1, and the scale.
-static int coverage_enqueue(Context &c, const std::vector<const kc_plane *> &plain, const std::vector<kc_plane *> *scaled, uint32_t w, uint32_t h,
-                            uint32_t L, uint32_t ref, PoolStaging &scratch, CoverageRecord **rec)
+// KC_MIP_COVERAGE: the select over alpha's plain chain (p_0 = alpha0, the image's alpha; p_k = slot_planes[(k - 1) * 4 + slot];
+// L levels of a w x h image, w h <= 2^31) and, with `own` (d_k = (*own)[(k - 1) * 4 + 3]), the scale launch.  The records and
+// the histograms live in `scratch`, which the caller gives back to the pool once everything that reads it is enqueued (or
+// waited for); *rec = the L device records.  Launches: a count and a pick per pass, three passes when there is a level >= 1,
+// and the scale.
+static int coverage_enqueue(Context &c, const kc_plane *alpha0, const std::vector<kc_plane *> &slot_planes, int slot, const std::vector<kc_plane *> *own,
+                            uint32_t w, uint32_t h, uint32_t L, uint32_t ref, PoolStaging &scratch, CoverageRecord **rec)
 {
     if (L > KC_COVERAGE_MAX_LEVELS) return mip_refuse("KC_MIP_COVERAGE", "more levels than the job table holds");
     const size_t rec_bytes = ((size_t)L * sizeof(CoverageRecord) + 255) / 256 * 256, hist_bytes = (size_t)L * KC_COVERAGE_BINS * sizeof(uint32_t);
     KC_TRY(scratch.alloc(rec_bytes + hist_bytes));
     CoverageArgs a{};
     uint32_t wgs = 0;
-    uint64_t below = 0;  // the texels of the levels >= 1
     for (uint32_t k = 0; k < L; ++k) {
         CoverageJob &J = a.jobs[k];
-        J.src = plain[k]->dptr;
-        J.src_pitch = (uint32_t)(plain[k]->pitch / sizeof(float));
-        J.dst = scaled && k ? (*scaled)[k - 1]->dptr : nullptr;
-        J.dst_pitch = scaled && k ? (uint32_t)((*scaled)[k - 1]->pitch / sizeof(float)) : 0u;
+        const kc_plane *plain = k ? slot_planes[(size_t)(k - 1) * 4 + slot] : alpha0, *scaled = own && k ? (*own)[(size_t)(k - 1) * 4 + 3] : nullptr;
+        J.src = plain->dptr;
+        J.src_pitch = pitch_of(plain);
+        J.dst = scaled ? scaled->dptr : nullptr;
+        J.dst_pitch = scaled ? pitch_of(scaled) : 0u;
         J.w = level_extent(w, k);
         J.h = level_extent(h, k);
         J.first_wg = wgs;
         J.wgs = coverage_job_wgs(J.w, J.h);
         wgs += J.wgs;
-        if (k) below += (uint64_t)J.w * J.h;
     }
     const uint32_t wgs0 = a.jobs[0].wgs;
     a.rec = (CoverageRecord *)scratch.ptr;
@@ -614,8 +601,9 @@ static int coverage_enqueue(Context &c, const std::vector<const kc_plane *> &pla
         if (e != hipSuccess) return hip_fail(e, "launch_coverage_pick");
         launches += 2;
     }
+    const uint64_t below = texels_below(w, h, L);
     uint64_t texels = (uint64_t)w * h + 3 * below;  // level 0 once, every further level once per pass
-    if (scaled && L > 1) {
+    if (own && L > 1) {
         hipError_t e = launch_coverage_scale(a, wgs0, wgs - wgs0, c.stream);
         if (e != hipSuccess) return hip_fail(e, "launch_coverage_scale");
         launches++;
@@ -626,6 +614,57 @@ static int coverage_enqueue(Context &c, const std::vector<const kc_plane *> &pla
     c.alg_bytes += 4 * texels;
     *rec = a.rec;
     return KC_OK;
+}
+
+// ---------------------------------------------------------------- the chains: the planes of the levels
+// The planes of levels 1 .. L - 1 of the channels first .. n - 1 of an image (`planes`: level 0), pushed to mc.planes as
+// [level - 1][channel - first].  A channel follows the plain rule: a constant is folded, channels that alias one resident
+// plane (sl: the distinct ones) share one new resident plane per level, slot_planes[(k - 1) * 4 + slot], which
+// mip_launch_plain writes.  A channel in own_mask follows a rule of its own: own(k, ch, W, H, p) gives its plane of level k,
+// recorded as own_planes[(k - 1) * 4 + ch] for the launches of that rule.
+template <class Own>
+static int mip_place(MipChain &mc, const MipSlots &sl, std::vector<kc_plane *> &slot_planes, std::vector<kc_plane *> &own_planes,
+                     kc_plane *const *planes, int first, int n, uint32_t own_mask, uint32_t w, uint32_t h, uint32_t L, Own own)
+{
+    float cv[4] = { 0.0f, 0.0f, 0.0f, 0.0f };
+    for (int ch = first; ch < n; ++ch) cv[ch] = planes[ch]->cval;
+    for (uint32_t k = 1; k < L; ++k) {
+        const uint32_t W = level_extent(w, k), H = level_extent(h, k);
+        for (int ch = first; ch < n; ++ch) {
+            const int s = sl.slot_of[ch];
+            kc_plane *p = nullptr;
+            if ((own_mask >> ch) & 1u) {
+                KC_TRY(own(k, ch, W, H, p));
+                own_planes[(size_t)(k - 1) * 4 + ch] = p;
+            } else if (s < 0) {
+                cv[ch] = mip_const_fold(cv[ch]);
+                p = plane_new_const(W, H, cv[ch]);
+            } else if (kc_plane *&shared = slot_planes[(size_t)(k - 1) * 4 + s]; shared) {
+                p = shared;
+                plane_retain(p);
+            } else {
+                KC_TRY(plane_new_mem(W, H, &p));
+                shared = p;
+            }
+            mc.planes.push_back(p);
+        }
+    }
+    return KC_OK;
+}
+
+// the rule of its own of a channel that gets a new resident plane at every level, whatever it is at level 0
+static int mip_own_plane(uint32_t, int, uint32_t W, uint32_t H, kc_plane *&p) { return plane_new_mem(W, H, &p); }
+
+// KC_MIP_COVERAGE with a resident alpha, one level: the level image gets an alpha plane of its own (d_k, *scaled); the slot's
+// plane keeps the plain alpha (p_k) that the next level is made from -- shared with R, G, B where they alias alpha and have
+// placed it, scratch otherwise
+static int mip_place_coverage(MipChain &mc, kc_plane *&plain, uint32_t W, uint32_t H, kc_plane *&scaled)
+{
+    if (!plain) {
+        KC_TRY(plane_new_mem(W, H, &plain));
+        mc.scratch.push_back(plain);
+    }
+    return plane_new_mem(W, H, &scaled);
 }
 
 // the kernels' indices are 32-bit and the pyramid's tile rows a grid dimension
@@ -647,34 +686,14 @@ static int image_build_alpha_mips(Context &c, kc_image *img, uint32_t ref, bool 
     const bool zero = a_const && !(w0 > 0.0f);
     const bool fold = !zero && a_const && img->planes[0]->kind == kc_plane::CONST && img->planes[1]->kind == kc_plane::CONST &&
                       img->planes[2]->kind == kc_plane::CONST;
-    MipChain mc;  // planes: one reference per plane of the level images, in no particular order
+    MipChain mc;  // planes: one reference per plane of the level images: alpha of the levels >= 1 first, then the colours
     mc.planes.reserve((size_t)L * 4);
-    // alpha: alpha_out[k] is the plane of level k's image
     MipSlots sl;
     sl.add(3, A);
-    std::vector<kc_plane *> slot_planes(L > 1 ? (size_t)(L - 1) * 4 : 0, nullptr), alpha_out(L, img->planes[3]);
     const bool coverage = ref != 0 && !a_const && L > 1;
-    std::vector<kc_plane *> scaled(coverage ? L - 1 : 0, nullptr);
-    float av = A->cval;
-    for (uint32_t k = 1; k < L; ++k) {
-        const uint32_t W = level_extent(w, k), H = level_extent(h, k);
-        kc_plane *p = nullptr;
-        if (a_const) {
-            av = mip_const_fold(av);
-            p = plane_new_const(W, H, av);
-        } else {
-            KC_TRY(plane_new_mem(W, H, &p));
-            slot_planes[(size_t)(k - 1) * 4] = p;
-            if (coverage) {
-                mc.scratch.push_back(p);
-                p = nullptr;
-                KC_TRY(plane_new_mem(W, H, &p));
-                scaled[k - 1] = p;
-            }
-        }
-        mc.planes.push_back(p);
-        alpha_out[k] = p;
-    }
+    std::vector<kc_plane *> slot_planes((size_t)(L - 1) * 4, nullptr), own_planes(coverage ? (size_t)(L - 1) * 4 : 0, nullptr);
+    KC_TRY(mip_place(mc, sl, slot_planes, own_planes, img->planes, 3, 4, coverage ? 8u : 0u, w, h, L,
+                     [&](uint32_t k, int, uint32_t W, uint32_t H, kc_plane *&p) { return mip_place_coverage(mc, slot_planes[(size_t)(k - 1) * 4], W, H, p); }));
     // colour: col[3 k + ch], level 0 included
     std::vector<kc_plane *> col((size_t)L * 3, nullptr);
     std::vector<float> folded((size_t)L * 3, 0.0f);
@@ -705,17 +724,13 @@ static int image_build_alpha_mips(Context &c, kc_image *img, uint32_t ref, bool 
             col[3 * k + ch] = p;
         }
     }
-    if (!zero && !fold) KC_TRY(mip_launch_alpha(c, img->planes, col, mc, w, h, L, per_level));
-    KC_TRY(mip_launch_plain(c, sl, slot_planes, w, h, L, per_level));
+    if (!zero && !fold) KC_TRY(mip_launch_alpha(c, MipSource(img->planes, 4), col, mc, w, h, L, per_level));
+    KC_TRY(mip_launch_plain(c, sl, slot_planes, mc, w, h, L, per_level));
     PoolStaging coverage_scratch;  // back to the pool when the call returns: everything that reads it is enqueued by then
-    if (coverage) {
-        std::vector<const kc_plane *> plain(L, img->planes[3]);
-        for (uint32_t k = 1; k < L; ++k) plain[k] = slot_planes[(size_t)(k - 1) * 4];
-        CoverageRecord *rec = nullptr;
-        KC_TRY(coverage_enqueue(c, plain, &scaled, w, h, L, ref, coverage_scratch, &rec));
-    }
+    CoverageRecord *rec = nullptr;
+    if (coverage) KC_TRY(coverage_enqueue(c, A, slot_planes, 0, &own_planes, w, h, L, ref, coverage_scratch, &rec));
     for (uint32_t k = 0; k < L; ++k) {
-        kc_plane *const planes[4] = { col[3 * k], col[3 * k + 1], col[3 * k + 2], alpha_out[k] };
+        kc_plane *const planes[4] = { col[3 * k], col[3 * k + 1], col[3 * k + 2], k ? mc.planes[k - 1] : img->planes[3] };
         levels[k] = image_new(4, planes);  // retains; mc drops its own
     }
     return KC_OK;
@@ -749,68 +764,39 @@ int image_build_mips(kc_image *img, uint32_t flags, kc_image **levels, uint32_t 
         return image_build_alpha_mips(c, img, ref, per_level, levels, w, h, L);
     const int n = img->n;
     // sl: the planes the plain rule reduces (under KC_MIP_NORMALS: alpha alone); rgb: R, G, B under KC_MIP_NORMALS
-    MipSlots sl, rgb;
+    MipSlots sl;
     for (int ch = normals ? 3 : 0; ch < n; ++ch) sl.add(ch, img->planes[ch]);
-    if (normals)
-        for (int ch = 0; ch < 3; ++ch) rgb.add(ch, img->planes[ch]);
-    // the planes of every level: one new resident plane per slot, shared by the channels that alias it, one constant per
-    // constant channel; under KC_MIP_NORMALS three constants for R, G, B when all three are, three new resident planes otherwise
-    MipChain mc;
-    mc.planes.reserve((size_t)(L - 1) * n);
-    std::vector<kc_plane *> slot_planes((size_t)(L - 1) * 4, nullptr);  // [level - 1][slot], owned through mc.planes
-    std::vector<kc_plane *> rgb_planes(normals && rgb.n > 0 ? (size_t)(L - 1) * 3 : 0, nullptr);  // [level - 1][channel], likewise
-    // KC_MIP_COVERAGE with a resident alpha: the level images get alpha planes of their own (d_k), the slot's planes keep the
-    // plain alpha (p_k) that the next level is made from -- shared with R, G, B where they alias alpha, scratch otherwise
-    const bool coverage = ref != 0 && sl.slot_of[3] >= 0 && L > 1;
-    std::vector<kc_plane *> alpha_planes(coverage ? L - 1 : 0, nullptr);  // [level - 1], owned through mc.planes
-    float cv[4] = { 0.0f, 0.0f, 0.0f, 0.0f };
-    for (int ch = 0; ch < n; ++ch) cv[ch] = img->planes[ch]->cval;
-    for (uint32_t k = 1; k < L; ++k) {
-        const uint32_t W = level_extent(w, k), H = level_extent(h, k);
-        if (normals && rgb.n == 0) {  // the fold: the box of each constant, then the texel's rule
+    const MipSource rgb(img->planes, normals ? 3 : 0);
+    // KC_MIP_NORMALS on constant R, G, B, [level - 1][channel]: the box of each constant, then the texel's rule
+    std::vector<float> flat;
+    if (normals && rgb.sl.n == 0) {
+        float cv[3] = { img->planes[0]->cval, img->planes[1]->cval, img->planes[2]->cval };
+        for (uint32_t k = 1; k < L; ++k) {
             const float box[3] = { mip_const_fold(cv[0]), mip_const_fold(cv[1]), mip_const_fold(cv[2]) };
             mip_normal_texel(box, cv);
-        }
-        for (int ch = 0; ch < n; ++ch) {
-            const int s = sl.slot_of[ch];
-            kc_plane *p = nullptr;
-            if (normals && ch < 3) {
-                if (rgb.n == 0) {
-                    p = plane_new_const(W, H, cv[ch]);
-                } else {
-                    KC_TRY(plane_new_mem(W, H, &p));
-                    rgb_planes[(size_t)(k - 1) * 3 + ch] = p;
-                }
-            } else if (s < 0) {
-                cv[ch] = mip_const_fold(cv[ch]);
-                p = plane_new_const(W, H, cv[ch]);
-            } else if (coverage && ch == 3) {
-                kc_plane *&plain = slot_planes[(size_t)(k - 1) * 4 + s];
-                if (!plain) {
-                    KC_TRY(plane_new_mem(W, H, &plain));
-                    mc.scratch.push_back(plain);
-                }
-                KC_TRY(plane_new_mem(W, H, &p));
-                alpha_planes[k - 1] = p;
-            } else if (slot_planes[(size_t)(k - 1) * 4 + s]) {
-                p = slot_planes[(size_t)(k - 1) * 4 + s];
-                plane_retain(p);
-            } else {
-                KC_TRY(plane_new_mem(W, H, &p));
-                slot_planes[(size_t)(k - 1) * 4 + s] = p;
-            }
-            mc.planes.push_back(p);
+            flat.insert(flat.end(), cv, cv + 3);
         }
     }
-    if (normals && rgb.n > 0) KC_TRY(mip_launch_normals(c, img->planes, rgb, rgb_planes, w, h, L, per_level));
-    KC_TRY(mip_launch_plain(c, sl, slot_planes, w, h, L, per_level));
+    // KC_MIP_COVERAGE with a resident alpha: the level images get alpha planes of their own (mip_place_coverage)
+    const bool coverage = ref != 0 && sl.slot_of[3] >= 0 && L > 1;
+    MipChain mc;
+    mc.planes.reserve((size_t)(L - 1) * n);
+    // rules of their own: alpha under coverage; under KC_MIP_NORMALS R, G, B -- three constants when all three are, three new
+    // resident planes otherwise
+    const uint32_t own_mask = (normals ? 7u : 0u) | (coverage ? 8u : 0u);
+    std::vector<kc_plane *> slot_planes((size_t)(L - 1) * 4, nullptr), own_planes(own_mask ? (size_t)(L - 1) * 4 : 0, nullptr);  // owned through mc
+    KC_TRY(mip_place(mc, sl, slot_planes, own_planes, img->planes, 0, n, own_mask, w, h, L,
+                     [&](uint32_t k, int ch, uint32_t W, uint32_t H, kc_plane *&p) {
+                         if (ch == 3) return mip_place_coverage(mc, slot_planes[(size_t)(k - 1) * 4 + sl.slot_of[3]], W, H, p);
+                         if (rgb.sl.n > 0) return plane_new_mem(W, H, &p);
+                         p = plane_new_const(W, H, flat[(size_t)(k - 1) * 3 + ch]);
+                         return (int)KC_OK;
+                     }));
+    if (normals && rgb.sl.n > 0) KC_TRY(mip_launch_normals(c, rgb, own_planes, mc, w, h, L, per_level));
+    KC_TRY(mip_launch_plain(c, sl, slot_planes, mc, w, h, L, per_level));
     PoolStaging coverage_scratch;  // back to the pool when the call returns: everything that reads it is enqueued by then
-    if (coverage) {
-        std::vector<const kc_plane *> plain(L, img->planes[3]);
-        for (uint32_t k = 1; k < L; ++k) plain[k] = slot_planes[(size_t)(k - 1) * 4 + sl.slot_of[3]];
-        CoverageRecord *rec = nullptr;
-        KC_TRY(coverage_enqueue(c, plain, &alpha_planes, w, h, L, ref, coverage_scratch, &rec));
-    }
+    CoverageRecord *rec = nullptr;
+    if (coverage) KC_TRY(coverage_enqueue(c, img->planes[3], slot_planes, sl.slot_of[3], &own_planes, w, h, L, ref, coverage_scratch, &rec));
     image_retain(img);
     levels[0] = img;
     for (uint32_t k = 1; k < L; ++k) levels[k] = image_new(n, mc.planes.data() + (size_t)(k - 1) * n);  // retains; mc drops its own
@@ -852,40 +838,17 @@ int image_build_roughness_mips(kc_image *img, uint32_t channel, kc_image *normal
         if ((uint32_t)ch != channel) sl.add(ch, img->planes[ch]);
     MipChain mc;
     mc.planes.reserve((size_t)(L - 1) * n);
-    std::vector<kc_plane *> slot_planes((size_t)(L - 1) * 4, nullptr);  // [level - 1][slot], owned through mc.planes
-    std::vector<kc_plane *> rough_planes(L - 1, nullptr);                // [level - 1], likewise: the named channel's own planes
-    float cv[4] = { 0.0f, 0.0f, 0.0f, 0.0f };
-    for (int ch = 0; ch < n; ++ch) cv[ch] = img->planes[ch]->cval;
-    for (uint32_t k = 1; k < L; ++k) {
-        const uint32_t W = level_extent(w, k), H = level_extent(h, k);
-        for (int ch = 0; ch < n; ++ch) {
-            const int s = sl.slot_of[ch];
-            kc_plane *p = nullptr;
-            if ((uint32_t)ch == channel) {
-                KC_TRY(plane_new_mem(W, H, &p));
-                rough_planes[k - 1] = p;
-            } else if (s < 0) {
-                cv[ch] = mip_const_fold(cv[ch]);
-                p = plane_new_const(W, H, cv[ch]);
-            } else if (slot_planes[(size_t)(k - 1) * 4 + s]) {
-                p = slot_planes[(size_t)(k - 1) * 4 + s];
-                plane_retain(p);
-            } else {
-                KC_TRY(plane_new_mem(W, H, &p));
-                slot_planes[(size_t)(k - 1) * 4 + s] = p;
-            }
-            mc.planes.push_back(p);
-        }
-    }
-    KC_TRY(mip_launch_roughness(c, src0, rough_planes, mc, power, w, h, L, per_level));
-    KC_TRY(mip_launch_plain(c, sl, slot_planes, w, h, L, per_level));
+    std::vector<kc_plane *> slot_planes((size_t)(L - 1) * 4, nullptr), own_planes((size_t)(L - 1) * 4, nullptr);  // owned through mc
+    KC_TRY(mip_place(mc, sl, slot_planes, own_planes, img->planes, 0, n, 1u << channel, w, h, L, mip_own_plane));
+    KC_TRY(mip_launch_roughness(c, MipSource(src0, 4), own_planes, channel, mc, power, w, h, L, per_level));
+    KC_TRY(mip_launch_plain(c, sl, slot_planes, mc, w, h, L, per_level));
     image_retain(img);
     levels[0] = img;
     for (uint32_t k = 1; k < L; ++k) levels[k] = image_new(n, mc.planes.data() + (size_t)(k - 1) * n);  // retains; mc drops its own
     return KC_OK;
 }
 
-// kc_image_mip_coverage_info: alpha's plain chain in scratch planes, the select, the records back
+// kc_image_mip_coverage_info: alpha's plain chain in planes that live until the call returns, the select, the records back
 int image_mip_coverage_info(kc_image *img, uint32_t flags, kc_mip_coverage_level *out, uint32_t cap, uint32_t *count)
 {
     const char *who = "kc_image_mip_coverage_info";
@@ -902,7 +865,7 @@ int image_mip_coverage_info(kc_image *img, uint32_t flags, kc_mip_coverage_level
     *count = L;
     if (!img->is_rgba()) return mip_refuse(who, "KC_MIP_COVERAGE is for RGBA images");
     if (cap < L) return mip_refuse(who, "cap is below the level count");
-    if (w > (1u << 30) || ((uint64_t)h + 63) / 64 > 65535ull || (uint64_t)w * h > (1ull << 31)) return mip_refuse(who, "image too large");
+    if (!mip_size_ok(w, h) || (uint64_t)w * h > (1ull << 31)) return mip_refuse(who, "image too large");  // the targets' 64-bit products
     KC_TRY(image_force(img));
     const uint64_t n_0 = (uint64_t)w * h;
     const kc_plane *alpha = img->planes[3];
@@ -918,20 +881,13 @@ int image_mip_coverage_info(kc_image *img, uint32_t flags, kc_mip_coverage_level
     }
     MipSlots sl;
     sl.add(3, alpha);
-    MipChain mc;
-    std::vector<kc_plane *> slot_planes((size_t)(L - 1) * 4, nullptr);
-    std::vector<const kc_plane *> plain(L, alpha);
-    for (uint32_t k = 1; k < L; ++k) {
-        kc_plane *p = nullptr;
-        KC_TRY(plane_new_mem(level_extent(w, k), level_extent(h, k), &p));
-        mc.scratch.push_back(p);
-        slot_planes[(size_t)(k - 1) * 4] = p;
-        plain[k] = p;
-    }
-    KC_TRY(mip_launch_plain(c, sl, slot_planes, w, h, L, (flags & KC_MIP_PER_LEVEL) != 0));
+    MipChain mc;  // alpha alone, by the plain rule: the planes of its levels go back to the pool when the call returns
+    std::vector<kc_plane *> slot_planes((size_t)(L - 1) * 4, nullptr), own_planes;
+    KC_TRY(mip_place(mc, sl, slot_planes, own_planes, img->planes, 3, 4, 0u, w, h, L, mip_own_plane));  // own_mask 0: the hook is not called
+    KC_TRY(mip_launch_plain(c, sl, slot_planes, mc, w, h, L, (flags & KC_MIP_PER_LEVEL) != 0));
     PoolStaging scratch;
     CoverageRecord *rec = nullptr;
-    KC_TRY(coverage_enqueue(c, plain, nullptr, w, h, L, ref, scratch, &rec));
+    KC_TRY(coverage_enqueue(c, alpha, slot_planes, 0, nullptr, w, h, L, ref, scratch, &rec));
     std::vector<CoverageRecord> got(L);
     hipError_t e = hipMemcpyAsync(got.data(), rec, (size_t)L * sizeof(CoverageRecord), hipMemcpyDeviceToHost, c.stream);
     if (e == hipSuccess) e = hipStreamSynchronize(c.stream);
@@ -940,236 +896,5 @@ int image_mip_coverage_info(kc_image *img, uint32_t flags, kc_mip_coverage_level
     return KC_OK;
 }
 
-// ---------------------------------------------------------------- the BC chain
-// flags of the chain exporters: KC_BC_SRGB under kc_image_to_bc's rule (bc_check_flags), plus KC_MIP_PER_LEVEL, KC_MIP_NORMALS,
-// which does not go with KC_BC_SRGB: a vector is not a colour, KC_MIP_COVERAGE_REF, and KC_BC_PUNCH_THROUGH, which shares its byte
-static int bc_mips_check_flags(int format, uint32_t flags, const char *who)
-{
-    KC_TRY(bc_check_flags(format, flags,
-                          KC_BC_SRGB | KC_MIP_PER_LEVEL | KC_MIP_NORMALS | KC_MIP_ALPHA_WEIGHT | kCoverageFlagBits | kBcPunchThroughBits, who));
-    if ((flags & KC_MIP_NORMALS) && (flags & KC_BC_SRGB)) {
-        set_error(std::string(who) + ": KC_MIP_NORMALS with KC_BC_SRGB");
-        return KC_ERR_UNSUPPORTED;
-    }
-    KC_TRY(mip_check_alpha_flags(flags, who));
-    return mip_check_coverage_flags(flags, who);
-}
-
-int bc_mip_layout(uint32_t w, uint32_t h, int format, uint32_t *levels, size_t *offsets, uint32_t cap, size_t *total_bytes)
-{
-    const BcFormat *f = bc_format(format);
-    if (!f) return mip_refuse("kc_bc_mip_layout", "unknown format");
-    if (w == 0 || h == 0) return mip_refuse("kc_bc_mip_layout", "zero extent");
-    const uint32_t L = 1u + floor_log2(w > h ? w : h);
-    if (levels) *levels = L;
-    if (offsets && cap < L) return mip_refuse("kc_bc_mip_layout", "cap is below the level count");
-    uint64_t bx = 0, by = 0;
-    KC_TRY(bc_block_count(w, h, "kc_bc_mip_layout", &bx, &by));
-    size_t at = 0;
-    for (uint32_t k = 0; k < L; ++k) {
-        if (offsets) offsets[k] = at;
-        at += bc_level_bytes(level_extent(w, k), level_extent(h, k), *f);
-    }
-    if (total_bytes) *total_bytes = at;
-    return KC_OK;
-}
-
-// The first `count` levels of a chain (forced) as blocks at dst, level k at its kc_bc_mip_layout offset; on the library's stream
-static int bc_levels_encode(kc_image *const *lv, uint32_t count, int format, uint32_t flags, char *dst)
-{
-    Context &c = ctx();
-    const BcFormat &f = *bc_format(format);  // the entry points have refused an unknown format
-    size_t at = 0;
-    int s = KC_OK;
-    for (uint32_t k = 0; k < count && s == KC_OK; ++k) {
-        const uint32_t W = lv[k]->w(), H = lv[k]->h();
-        s = bc_encode(lv[k], format, (flags & KC_BC_SRGB) != 0, dst + at, (((size_t)W + 3) / 4) * f.block_bytes, c.stream,
-                      bc_punch_through_ref(flags));
-        at += bc_level_bytes(W, H, f);
-    }
-    return s;
-}
-
-// The chain of `img` (forced by image_build_mips) as blocks at dst
-static int bc_mips_encode(kc_image *img, int format, uint32_t flags, char *dst)
-{
-    uint32_t L = 0;
-    KC_TRY(mip_level_count(img->w(), img->h(), &L));
-    std::vector<kc_image *> lv(L, nullptr);
-    uint32_t count = 0;
-    // the byte goes to the chain only with KC_MIP_COVERAGE: under KC_BC_PUNCH_THROUGH alone it is the encoder's
-    const uint32_t chain_bits = KC_MIP_PER_LEVEL | KC_MIP_NORMALS | KC_MIP_ALPHA_WEIGHT | ((flags & KC_MIP_COVERAGE) ? kCoverageFlagBits : 0u);
-    KC_TRY(image_build_mips(img, flags & chain_bits, lv.data(), L, &count));
-    const int s = bc_levels_encode(lv.data(), L, format, flags, dst);
-    // the level planes go back to the pool here; the pool hands a block out again only to work enqueued on the same stream
-    for (kc_image *i : lv) image_release(i);
-    return s;
-}
-
-// kc_image_levels_to_bc_mips / kc_image_levels_write_dds: the checks of a chain the caller holds; *total = the bytes of its
-// `count` levels.  The flags, the arguments, need_init(), then the levels themselves, which are forced.
-static int bc_levels_check(kc_image *const *levels, uint32_t count, int format, uint32_t flags, const void *out, const char *who, size_t *total)
-{
-    KC_TRY(bc_check_flags(format, flags, KC_BC_SRGB | kBcPunchThroughBits, who));
-    const BcFormat *f = bc_format(format);
-    if (!f) return mip_refuse(who, "unknown format");
-    if (!levels || !out || count == 0) return mip_refuse(who, "NULL level array or output, or no level");
-    KC_TRY(need_init());
-    if (!levels[0]) return mip_refuse(who, "a NULL level");
-    if ((flags & KC_BC_PUNCH_THROUGH) && !levels[0]->is_rgba()) return mip_refuse(who, "KC_BC_PUNCH_THROUGH is for RGBA images");
-    const uint32_t w = levels[0]->w(), h = levels[0]->h();
-    if (count > 1u + floor_log2(w > h ? w : h)) return mip_refuse(who, "more levels than the chain of level 0's size has");
-    uint64_t bx = 0, by = 0;
-    KC_TRY(bc_block_count(w, h, who, &bx, &by));
-    *total = 0;
-    for (uint32_t k = 0; k < count; ++k) {
-        if (!levels[k] || levels[k]->n != levels[0]->n || levels[k]->w() != level_extent(w, k) || levels[k]->h() != level_extent(h, k))
-            return mip_refuse(who, "every level must be an image of level 0's kind, max(1, w >> k) by max(1, h >> k)");
-        *total += bc_level_bytes(level_extent(w, k), level_extent(h, k), *f);
-    }
-    for (uint32_t k = 0; k < count; ++k) KC_TRY(image_force(levels[k]));
-    return KC_OK;
-}
-
-int image_levels_to_bc_mips(kc_image *const *levels, uint32_t count, int format, uint32_t flags, uint8_t *host, size_t host_bytes, const char *who)
-{
-    Context &c = ctx();
-    std::lock_guard<std::recursive_mutex> lk(c.mu);
-    size_t total = 0;
-    KC_TRY(bc_levels_check(levels, count, format, flags, host, who, &total));
-    if (host_bytes < total) return mip_refuse(who, "host_bytes is below the levels' bytes");
-    PoolStaging staging;
-    KC_TRY(staging.alloc(total));
-    KC_TRY(bc_levels_encode(levels, count, format, flags, (char *)staging.ptr));
-    hipError_t e = hipMemcpyAsync(host, staging.ptr, total, hipMemcpyDeviceToHost, c.stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(c.stream);
-    if (e != hipSuccess) return hip_fail(e, who);
-    return KC_OK;
-}
-
-int image_to_bc_mips(kc_image *img, int format, uint32_t flags, uint8_t *host, size_t host_bytes)
-{
-    KC_TRY(bc_mips_check_flags(format, flags, "kc_image_to_bc_mips"));
-    if (!bc_format(format)) return mip_refuse("kc_image_to_bc_mips", "unknown format");
-    if (!img || !host) return mip_refuse("kc_image_to_bc_mips", "NULL image or host buffer");
-    KC_TRY(need_init());
-    if ((flags & (KC_MIP_NORMALS | KC_MIP_COVERAGE | KC_MIP_ALPHA_WEIGHT | KC_BC_PUNCH_THROUGH)) && !img->is_rgba())
-        return mip_refuse("kc_image_to_bc_mips", "KC_MIP_NORMALS, KC_MIP_COVERAGE, KC_MIP_ALPHA_WEIGHT and KC_BC_PUNCH_THROUGH are for RGBA images");
-    Context &c = ctx();
-    std::lock_guard<std::recursive_mutex> lk(c.mu);
-    size_t total = 0;
-    KC_TRY(bc_mip_layout(img->w(), img->h(), format, nullptr, nullptr, 0, &total));
-    if (host_bytes < total) return mip_refuse("kc_image_to_bc_mips", "host_bytes is below the chain's bytes");
-    PoolStaging staging;
-    KC_TRY(staging.alloc(total));
-    KC_TRY(bc_mips_encode(img, format, flags, (char *)staging.ptr));
-    hipError_t e = hipMemcpyAsync(host, staging.ptr, total, hipMemcpyDeviceToHost, c.stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(c.stream);
-    if (e != hipSuccess) return hip_fail(e, "image_to_bc_mips");
-    return KC_OK;
-}
-
-int image_to_bc_mips_device(kc_image *img, int format, uint32_t flags, void *device_ptr, size_t bytes, void *hip_stream)
-{
-    KC_TRY(bc_mips_check_flags(format, flags, "kc_image_to_bc_mips_device"));
-    const size_t bb = bc_block_bytes(format);
-    if (bb == 0) return mip_refuse("kc_image_to_bc_mips_device", "unknown format");
-    if (!img || !device_ptr) return mip_refuse("kc_image_to_bc_mips_device", "NULL image or device pointer");
-    if ((uintptr_t)device_ptr % bb) return mip_refuse("kc_image_to_bc_mips_device", "the pointer must be a multiple of the block bytes");
-    KC_TRY(need_init());  // an image exists only after kc_init: it is not looked at before
-    if ((flags & (KC_MIP_NORMALS | KC_MIP_COVERAGE | KC_MIP_ALPHA_WEIGHT | KC_BC_PUNCH_THROUGH)) && !img->is_rgba())
-        return mip_refuse("kc_image_to_bc_mips_device", "KC_MIP_NORMALS, KC_MIP_COVERAGE, KC_MIP_ALPHA_WEIGHT and KC_BC_PUNCH_THROUGH are for RGBA images");
-    Context &c = ctx();
-    std::lock_guard<std::recursive_mutex> lk(c.mu);
-    size_t total = 0;
-    KC_TRY(bc_mip_layout(img->w(), img->h(), format, nullptr, nullptr, 0, &total));
-    if (bytes < total) return mip_refuse("kc_image_to_bc_mips_device", "bytes is below the chain's bytes");
-    KC_TRY(device_extent_check(device_ptr, total, "kc_image_to_bc_mips_device"));
-    return with_stream_edges(hip_stream, [&] { return bc_mips_encode(img, format, flags, (char *)device_ptr); });
-}
-
-// ---------------------------------------------------------------- DDS
-int dds_header(uint32_t w, uint32_t h, int format, uint32_t flags, uint32_t levels, uint8_t *out, size_t *bytes)
-{
-    KC_TRY(bc_check_flags(format, flags, KC_BC_SRGB, "kc_dds_header"));
-    const BcFormat *f = bc_format(format);
-    if (!f) return mip_refuse("kc_dds_header", "unknown format");
-    if (!out || w == 0 || h == 0) return mip_refuse("kc_dds_header", "NULL output or zero extent");
-    if (levels == 0 || levels > 1u + floor_log2(w > h ? w : h)) return mip_refuse("kc_dds_header", "levels is 0 or above the chain's level count");
-    const uint64_t linear = (((uint64_t)w + 3) / 4) * (((uint64_t)h + 3) / 4) * f->block_bytes;
-    if (linear > 0xffffffffull) return mip_refuse("kc_dds_header", "level 0 is larger than the header can say");
-    const bool mips = levels > 1;
-    uint32_t d[37] = { 0 };
-    d[0] = fourcc('D', 'D', 'S', ' ');
-    d[1] = 124;          // DDS_HEADER: dwSize
-    d[2] = 0x1u | 0x2u | 0x4u | 0x1000u | 0x80000u | (mips ? 0x20000u : 0u);  // CAPS, HEIGHT, WIDTH, PIXELFORMAT, LINEARSIZE, MIPMAPCOUNT
-    d[3] = h;
-    d[4] = w;
-    d[5] = (uint32_t)linear;  // dwPitchOrLinearSize
-    d[6] = 0;                 // dwDepth
-    d[7] = levels;            // dwMipMapCount; d[8..18]: reserved
-    d[19] = 32;               // DDS_PIXELFORMAT: dwSize
-    d[20] = 0x4;              // DDPF_FOURCC
-    d[21] = fourcc('D', 'X', '1', '0');  // d[22..26]: bit count and masks, 0
-    d[27] = 0x1000u | (mips ? 0x8u | 0x400000u : 0u);  // dwCaps: TEXTURE (, COMPLEX, MIPMAP); d[28..31]: 0
-    d[32] = (flags & KC_BC_SRGB) ? f->dxgi_srgb : f->dxgi;  // DDS_HEADER_DXT10: the number kc_dds_parse looks up in the same table
-    d[33] = 3;                // D3D10_RESOURCE_DIMENSION_TEXTURE2D
-    d[34] = 0;                // miscFlag
-    d[35] = 1;                // arraySize
-    d[36] = 0;                // miscFlags2
-    for (int i = 0; i < 37; ++i)  // little-endian, whatever the host's order
-        for (int b = 0; b < 4; ++b) out[4 * i + b] = (uint8_t)(d[i] >> (8 * b));
-    if (bytes) *bytes = 148;
-    return KC_OK;
-}
-
-static int dds_write_file(const char *path, const std::vector<uint8_t> &file, const char *who)
-{
-    FILE *f = std::fopen(path, "wb");
-    if (!f) {
-        set_error(std::string(who) + ": cannot open " + path);
-        return KC_ERR_IO;
-    }
-    const bool ok = std::fwrite(file.data(), 1, file.size(), f) == file.size();
-    if (std::fclose(f) != 0 || !ok) {
-        set_error(std::string(who) + ": cannot write " + path);
-        return KC_ERR_IO;
-    }
-    return KC_OK;
-}
-
-int image_write_dds(kc_image *img, const char *path, int format, uint32_t flags, int with_mips)
-{
-    KC_TRY(bc_mips_check_flags(format, flags, "kc_image_write_dds"));
-    if (!bc_format(format)) return mip_refuse("kc_image_write_dds", "unknown format");
-    if (!img || !path) return mip_refuse("kc_image_write_dds", "NULL image or path");
-    KC_TRY(need_init());
-    const uint32_t w = img->w(), h = img->h();
-    uint32_t L = 1;
-    size_t total = 0;
-    KC_TRY(bc_mip_layout(w, h, format, &L, nullptr, 0, &total));
-    if (!with_mips) {
-        L = 1;
-        total = bc_level_bytes(w, h, *bc_format(format));
-    }
-    std::vector<uint8_t> file(148 + total);
-    KC_TRY(dds_header(w, h, format, flags & KC_BC_SRGB, L, file.data(), nullptr));
-    if (with_mips) KC_TRY(image_to_bc_mips(img, format, flags, file.data() + 148, total));
-    else KC_TRY(image_to_bc(img, format, flags & (KC_BC_SRGB | ((flags & KC_BC_PUNCH_THROUGH) ? kBcPunchThroughBits : 0u)), file.data() + 148, total));
-    return dds_write_file(path, file, "kc_image_write_dds");
-}
-
-int image_levels_write_dds(kc_image *const *levels, uint32_t count, const char *path, int format, uint32_t flags)
-{
-    const char *who = "kc_image_levels_write_dds";
-    Context &c = ctx();
-    std::lock_guard<std::recursive_mutex> lk(c.mu);
-    size_t total = 0;
-    KC_TRY(bc_levels_check(levels, count, format, flags, path, who, &total));
-    std::vector<uint8_t> file(148 + total);
-    KC_TRY(dds_header(levels[0]->w(), levels[0]->h(), format, flags & KC_BC_SRGB, count, file.data(), nullptr));
-    KC_TRY(image_levels_to_bc_mips(levels, count, format, flags, file.data() + 148, total, who));
-    return dds_write_file(path, file, who);
-}
-
 }  // namespace kc
+

@@ -15,7 +15,7 @@ def usage(tmp_path_factory):
 
 def test_the_unit_is_part_of_the_build():
     from kanter_core_amd import build as kbuild
-    assert "mip_coverage.hip" in kbuild.SOURCES and "mip.cpp" in kbuild.SOURCES
+    assert "mip_coverage.hip" in kbuild.SOURCES and "mip.cpp" in kbuild.SOURCES and "mip_export.cpp" in kbuild.SOURCES
     assert "streaming.h" in kbuild.HEADERS  # hist_add, which the count pass shares with stats.hip
 
 

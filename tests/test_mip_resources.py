@@ -37,7 +37,7 @@ def usage(tmp_path_factory):
 
 def test_the_unit_is_part_of_the_build():
     from kanter_core_amd import build as kbuild
-    assert "mip.hip" in kbuild.SOURCES and "mip.cpp" in kbuild.SOURCES
+    assert "mip.hip" in kbuild.SOURCES and "mip.cpp" in kbuild.SOURCES and "mip_export.cpp" in kbuild.SOURCES
 
 
 @pytest.mark.parametrize("kernel", ["mip_pyramid_kernel", "mip_level_kernel"])
