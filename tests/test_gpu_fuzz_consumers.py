@@ -14,43 +14,52 @@ Launches only, no bytes, for the states where that derivation would be a guess: 
 resized, and a CombineRgba that takes the same slot twice through a resize (whether the two results are one plane is the
 evaluator's memo's business).  The fused mip kernel's launch count is a table of shapes in test_gpu_mips, not a formula: bytes only.
 
-Each seed runs ROWS_PER_SEED of the eight consumer rows, drawn from the seed (all eight fit the time).  Among the slots of the
+Two rows put the later mip rules behind the same states: "mips_rules" calls mips() under the five flag sets that are not the plain
+rule (normals, coverage, both, alpha_weighted, alpha_weighted with coverage; tests/mip_states.py), fused and per level, in an order
+drawn from the seed, against mip_states.reference of the oracle's planes, launches by test_gpu_mip_states.expected_mips_cost;
+"bc_mips_rules" holds to_bc_mips under each rule to levels_to_bc_mips of the chain mips() builds and to bc_ref / bc1a_ref of the
+reference levels.  The rules are for RGBA images: on a Gray slot both rows assert the documented refusal and that nothing is launched.
+
+Each seed runs ROWS_PER_SEED of the ten consumer rows, drawn from the seed (all ten fit the time).  Among the slots of the
 nodes _build requests, the one taken is larger than 1 x 1 and an aliased CombineRgba if it can be (either alone comes next), then has a
 constant channel, then is Gray: left to chance, two thirds of the seeds would hand over a 1 x 1 image and aliased channels
 would hardly occur.  The last test asserts that every row met every state and that at most a quarter of the seeds had to be
 skipped because the reference refuses their nodes.  No seed has found a defect so far; one that does is pinned in a
 test_seeds_that_found_defects case here, with its cause, as test_gpu_fuzz_graphs does.
 
-Run time on an MI355X: 18 s for the module (153 tests: 120 seeds with eight rows each, 32 hand-made cases, the coverage test), of
-which 11 s are the first test's set-up (library start-up); no seed takes longer than 0.25 s."""
+Run time on an MI355X: 19 s for the module (161 tests: 120 seeds with ten rows each, 40 hand-made cases, the coverage test), of
+which 12 s are the first test's set-up (library start-up); no seed takes longer than 0.3 s."""
 import ctypes as C
 
 import numpy as np
 import pytest
 
+import bc1a_ref
 import bc6h_ref
 import bc7_ref
 import bc_decode_ref
 import bc_modes_ref
 import bc_ref
 import mip_ref
+import mip_states
 from test_gpu_bc_decode import record
 from test_gpu_device_image import u16_formula
 from test_gpu_fuzz_graphs import _build
+from test_gpu_mip_states import EXPORT, expected_mips_cost
 from util import SEED_A, assert_planes, bit_equal, key_range, splitmix_plane
 
 pytestmark = pytest.mark.gpu
 
 BASE = 0xF0270000  # test_gpu_fuzz_graphs uses 0xF0220000 .. 0xF0260000 and the soak 0xF0990000
 SEEDS = 120
-ROWS_PER_SEED = 8
+ROWS_PER_SEED = 10
 BC7, BC6H = 98, 95
 BC_SRGB, BC_ALL_MODES = 1, 16
 BC_FORMS = [(1, False), (1, True), (3, False), (3, True), (4, False), (5, False)]
 ALL_FORMS = BC_FORMS + [(BC7, False), (BC7, True), (BC6H, False)]
 BLOCK_BYTES = {1: 8, 3: 16, 4: 8, 5: 16, BC7: 16, BC6H: 16}
 READ_MASK = {1: 0x7, 3: 0xF, 4: 0x1, 5: 0x3, BC7: 0xF, BC6H: 0x7}  # the channels a format's encoder and comparison read
-ROWS = ["bc", "bc7", "bc6h", "mips", "bc_mips", "bc_error", "stats", "export"]
+ROWS = ["bc", "bc7", "bc6h", "mips", "bc_mips", "bc_error", "stats", "export", "mips_rules", "bc_mips_rules"]
 STATES = ["gray", "aliased", "constant", "mix", "resize", "w%4", "h%4", "1x1"]
 
 _TALLY = set()   # (row, state) pairs that a seed test reached
@@ -447,8 +456,72 @@ def row_export(kc, orc, torch, src, rng):
     return out
 
 
+RULES = mip_states.FLAG_SETS[1:]  # the five flag sets of mips() that are not the plain rule
+
+
+def _refusals(kc, src, calls):
+    """The variant of a rule row on a Gray slot: every call is refused as the header documents, and nothing is launched."""
+    def call():
+        img = src["img"]()
+        n0 = kc.stats()["kernel_launches"]
+        for c in calls:
+            with pytest.raises(kc.TexProError):
+                c(img)
+        assert kc.stats()["kernel_launches"] == n0
+        return [np.array([len(calls)], np.int64)]
+    return [("refused on a Gray image", call, [np.array([len(calls)], np.int64)], (0, 0))]
+
+
+def _rule_cost(src, flags, per_level):
+    """launches of mips(**flags) by test_gpu_mip_states.expected_mips_cost, residency from _provenance; None where ambiguous"""
+    keys, image = src["keys"], src["image"]
+    if keys is None:
+        return None, None
+    info = [(k is None, image.planes[ch].reshape(-1)[0], k) for ch, k in enumerate(keys)]
+    return expected_mips_cost(flags, info, image.size[0], image.size[1], per_level)[1], None
+
+
+def row_mips_rules(kc, orc, torch, src, rng):
+    image = src["image"]
+    if not image.is_rgba:
+        return _refusals(kc, src, [lambda img, f=f, p=p: img.mips(per_level=p, **f) for f in RULES for p in (False, True)])
+    out = []
+    for i in rng.permutation(2 * len(RULES)):
+        flags, per_level = RULES[i // 2], bool(i % 2)
+        chains = mip_states.reference(image.planes, flags)
+        want = [[c[k] for c in chains] for k in range(len(chains[0]))]
+        out.append(("mips %s per_level=%s" % (mip_states.flag_id(flags), per_level),
+                    lambda f=flags, p=per_level: [lv.planes() for lv in src["img"]().mips(per_level=p, **f)], want, _rule_cost(src, flags, per_level)))
+    return out
+
+
+def row_bc_mips_rules(kc, orc, torch, src, rng):
+    """to_bc_mips under a rule encodes the chain mips builds under it; the blocks are the encoders' references of the reference levels"""
+    image = src["image"]
+    forms = [(flags,) + EXPORT[mip_states.flag_id(flags)] for flags in RULES]
+    if not image.is_rgba:
+        return _refusals(kc, src, [lambda img, f=f, fmt=fmt, pt=pt: img.to_bc_mips(fmt, punch_through=pt, **f) for f, fmt, pt in forms])
+    out = []
+    for i in rng.permutation(len(forms)):
+        flags, fmt, punch = forms[i]
+        ref = flags["coverage"] if punch else None
+        chains = mip_states.reference(image.planes, flags)
+        want = []
+        for k in range(len(chains[0])):
+            px = orc.to_u8(orc.Image([c[k] for c in chains]), False)
+            want.append(bc1a_ref.encode(px, ref) if punch else bc_ref.encode(px, fmt))
+
+        def call(flags=flags, fmt=fmt, punch=punch, ref=ref):
+            img = src["img"]()
+            got = img.to_bc_mips(fmt, punch_through=punch, **flags)
+            _same(kc.levels_to_bc_mips(img.mips(**flags), fmt, punch_through=ref), got, "levels_to_bc_mips of mips(%s)" % mip_states.flag_id(flags))
+            return got
+        out.append(("BC%d chain %s" % (fmt, mip_states.flag_id(flags)), call, want, (None, None)))
+    return out
+
+
 ROW_FUNCTIONS = dict(bc=row_bc, bc7=row_bc7, bc6h=row_bc6h, mips=row_mips, bc_mips=row_bc_mips, bc_error=row_bc_error, stats=row_stats,
-                     export=row_export)
+                     export=row_export, mips_rules=row_mips_rules, bc_mips_rules=row_bc_mips_rules)
 
 
 # ------------------------------------------------------------------ the comparison and the driver
