@@ -3,7 +3,7 @@
 // library's device -- and launches bc.hip's encoder (KC_BC7: bc7.hip's, KC_BC6H: bc6h.hip's) once per call: on the library's stream, ordered
 // against the caller's stream by the two event edges of kc_image_to_device, or into pool staging that is copied to the
 // caller's host memory.  The file also holds what the whole BC family's host side shares (bc_decode.cpp, the BC chain of mip_export.cpp):
-// the format table, the block count and level bytes, the flag rule, the source operands of an image and the choice of a format's device unit.
+// the format table, the block count and level bytes, the flag rule and the choice of a format's device unit.
 #include "kc_runtime.hpp"
 
 namespace kc {
@@ -203,21 +203,6 @@ int bc_image_validate(const kc_bc_image *d, size_t *extent_bytes)
     return device_extent_check(d->ptr, ext, "kc_bc_image");
 }
 
-uint32_t bc_source_operands(const kc_image *img, uint32_t mask, Operand (&o)[4])
-{
-    const bool rgba = img->is_rgba();
-    for (int i = 0; i < 4; ++i) o[i] = rgba ? plane_operand(img->planes[i]) : i < 3 ? plane_operand(img->planes[0]) : Operand{ nullptr, 0, 1.0f };
-    const float *seen[4] = { nullptr, nullptr, nullptr, nullptr };
-    uint32_t n_res = 0;
-    for (int i = 0; i < 4; ++i) {
-        if (!((mask >> i) & 1u) || !o[i].ptr) continue;
-        bool dup = false;
-        for (uint32_t k = 0; k < n_res; ++k) dup |= seen[k] == o[i].ptr;
-        if (!dup) seen[n_res++] = o[i].ptr;
-    }
-    return n_res;
-}
-
 // ---------------------------------------------------------------- the device unit of a format
 // BC6H's three kernels are bc6h.hip's, BC7's encoder bc7.hip's; everything else is bc.hip's and bc_decode.hip's.  all_modes
 // (KC_BC_ALL_MODES): the formats with modes that the default decoders leave out -- the table's counts_undecoded, BC7 and BC6H --
@@ -262,7 +247,7 @@ int bc_encode(kc_image *img, int format, bool srgb, char *dst, size_t row_pitch,
     Context &c = ctx();
     const BcFormat &f = *bc_format(format);  // the entry points have refused an unknown format
     Operand o[4];
-    const uint32_t n_res = bc_source_operands(img, pt_ref ? 0xfu : f.channels, o);
+    const uint32_t n_res = image_source_operands(img, pt_ref ? 0xfu : f.channels, o);
     const uint32_t w = img->w(), h = img->h();
     const uint64_t in_bytes = (uint64_t)w * h * 4 * n_res, out_bytes = bc_level_bytes(w, h, f);
     const uint32_t nt_mask = cache_policy_mask(in_bytes, out_bytes, n_res ? n_res : 1);

@@ -32,18 +32,8 @@ static int bcd_check_flags(int format, uint32_t flags, const char *who)
     return KC_OK;
 }
 
-// The result words of a reduction, on the host once the call's event has fired
-static int bcd_fetch(uint32_t words)
-{
-    Context &c = ctx();
-    KC_HIP(hipMemcpyAsync(c.stats.host, c.stats.result, words * sizeof(unsigned long long), hipMemcpyDeviceToHost, c.stream));
-    KC_HIP(hipEventRecord(c.stats.done, c.stream));
-    KC_HIP(hipEventSynchronize(c.stats.done));
-    return KC_OK;
-}
-
 // One launch of the decoder (two with a count) on the library's stream: the blocks at `src`, block rows `row_pitch` bytes apart,
-// into a new image.  *counted: the count is in flight and bcd_fetch brings it.  KC_BC_ALL_MODES in `flags`: every block is
+// into a new image.  *counted: the count is in flight and stats_fetch brings it.  KC_BC_ALL_MODES in `flags`: every block is
 // decoded, so nothing is counted and the caller's count is 0 without a wait.
 static int bc_decode(const char *src, size_t row_pitch, uint32_t w, uint32_t h, int format, uint32_t flags, bool want_count, kc_image **out,
                      bool *counted)
@@ -52,12 +42,9 @@ static int bc_decode(const char *src, size_t row_pitch, uint32_t w, uint32_t h, 
     Context &c = ctx();
     const BcFormat &f = *bc_format(format);  // the entry points have refused an unknown format
     const int n_res = f.planes, n = gray ? 1 : 4;
-    kc_plane *p[4] = { nullptr, nullptr, nullptr, nullptr };
-    int s = KC_OK;
-    for (int i = 0; i < n && s == KC_OK; ++i) {
-        if (i < n_res) s = plane_new_mem(w, h, &p[i]);
-        else p[i] = plane_new_const(w, h, i == 3 ? 1.0f : 0.0f);  // the sampling convention: missing G, B = 0, A = 1
-    }
+    kc_plane *p[4];
+    float *dp[4];
+    int s = image_planes_for_import(w, h, n_res, n, p, dp);  // the sampling convention: missing G, B = 0, A = 1
     const bool count = want_count && f.counts_undecoded && !all_modes;
     BcDecodeArgs a{};
     uint32_t groups = 0;
@@ -69,7 +56,7 @@ static int bc_decode(const char *src, size_t row_pitch, uint32_t w, uint32_t h, 
         a.bx = (w + 3) / 4;
         a.by = (h + 3) / 4;
         a.dst_pitch = (uint32_t)(p[0]->pitch / sizeof(float));
-        for (int i = 0; i < n_res; ++i) a.dst[i] = p[i]->dptr;
+        for (int i = 0; i < n_res; ++i) a.dst[i] = dp[i];
         groups = bc_decode_groups(w, h, count);
         if (count) {
             s = stats_buffers((size_t)groups * sizeof(unsigned long long));
@@ -86,10 +73,8 @@ static int bc_decode(const char *src, size_t row_pitch, uint32_t w, uint32_t h, 
             c.alg_bytes += in_bytes + out_bytes;
         }
     }
-    if (s == KC_OK) *out = image_new(n, p);
-    for (int i = 0; i < 4; ++i) plane_release(p[i]);
     *counted = s == KC_OK && count;
-    return s;
+    return image_of_import_planes(s, n, p, out);
 }
 
 int image_from_bc(const uint8_t *host, size_t host_bytes, uint32_t w, uint32_t h, int format, uint32_t flags, kc_image **out,
@@ -115,7 +100,7 @@ int image_from_bc(const uint8_t *host, size_t host_bytes, uint32_t w, uint32_t h
     int s = e == hipSuccess ? bc_decode((const char *)staging.ptr, (size_t)bx * f->block_bytes, w, h, format, flags,
                                         undecoded_blocks != nullptr, &img, &counted)
                             : KC_OK;
-    if (s == KC_OK && e == hipSuccess && counted) s = bcd_fetch(1);
+    if (s == KC_OK && e == hipSuccess && counted) s = stats_fetch(1);
     if (e == hipSuccess) e = hipStreamSynchronize(c.stream);  // the caller's bytes have been read
     if (s == KC_OK && e != hipSuccess) s = hip_fail(e, "image_from_bc");
     if (s != KC_OK) {
@@ -140,7 +125,7 @@ int image_from_bc_device(const kc_bc_image *src, uint32_t flags, void *hip_strea
         return bc_decode((const char *)src->ptr, src->row_pitch_bytes, src->width, src->height, src->format, flags,
                          undecoded_blocks != nullptr, &img, &counted);
     });
-    if (s == KC_OK && counted) s = bcd_fetch(1);
+    if (s == KC_OK && counted) s = stats_fetch(1);
     if (s != KC_OK) {
         image_release(img);
         return s;
@@ -160,7 +145,7 @@ static int bc_compare(kc_image *img, int format, uint32_t flags, const char *blo
     const uint32_t pt_ref = bc_punch_through_ref(flags);  // KC_BC_PUNCH_THROUGH: alpha is read and compared too
     const uint32_t channels = pt_ref ? 0xfu : f.channels;
     Operand o[4];
-    const uint32_t n_res = bc_source_operands(img, channels, o);
+    const uint32_t n_res = image_source_operands(img, channels, o);
     const uint32_t w = img->w(), h = img->h();
     const uint32_t groups = bc_compare_groups(w, h);
     KC_TRY(stats_buffers((size_t)groups * KC_BC_REC_WORDS * sizeof(unsigned long long)));
@@ -173,7 +158,7 @@ static int bc_compare(kc_image *img, int format, uint32_t flags, const char *blo
     if (e != hipSuccess) return hip_fail(e, "launch_bc_compare");
     c.launches += 2;
     c.alg_bytes += in_bytes + blk_bytes;
-    KC_TRY(bcd_fetch(KC_BC_REC_WORDS));
+    KC_TRY(stats_fetch(KC_BC_REC_WORDS));
     const unsigned long long *res = c.stats.host;
     kc_bc_error r;
     std::memset(&r, 0, sizeof r);

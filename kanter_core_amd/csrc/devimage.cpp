@@ -135,17 +135,9 @@ int image_from_device(const kc_device_image *src, uint32_t flags, void *hip_stre
     std::lock_guard<std::recursive_mutex> lk(c.mu);
     const uint32_t w = src->width, h = src->height;
     const int n = src->channels;
-    kc_plane *p[4] = { nullptr, nullptr, nullptr, nullptr };
-    float *dp[4] = { nullptr, nullptr, nullptr, nullptr };
-    int s = KC_OK;
-    for (int i = 0; i < (gray ? 1 : 4) && s == KC_OK; ++i) {
-        if (i < n) {
-            s = plane_new_mem(w, h, &p[i]);
-            if (s == KC_OK) dp[i] = p[i]->dptr;
-        } else {
-            p[i] = plane_new_const(w, h, i == 3 ? 1.0f : 0.0f);  // deconstruct_image: missing R, G, B = 0, A = 1
-        }
-    }
+    kc_plane *p[4];
+    float *dp[4];
+    int s = image_planes_for_import(w, h, n, gray ? 1 : 4, p, dp);
     if (s == KC_OK)
         s = with_stream_edges(hip_stream, [&] {
             const DevImageArgs a = devimage_args(src);
@@ -159,9 +151,7 @@ int image_from_device(const kc_device_image *src, uint32_t flags, void *hip_stre
             c.alg_bytes += in_bytes + out_bytes;
             return (int)KC_OK;
         });
-    if (s == KC_OK) *out = image_new(gray ? 1 : 4, p);
-    for (int i = 0; i < 4; ++i) plane_release(p[i]);
-    return s;
+    return image_of_import_planes(s, gray ? 1 : 4, p, out);
 }
 
 int image_to_device(kc_image *img, const kc_device_image *dst, uint32_t flags, void *hip_stream)
@@ -184,9 +174,7 @@ int image_to_device(kc_image *img, const kc_device_image *dst, uint32_t flags, v
     const bool rgba = img->is_rgba();
     const int n = dst->channels;
     Operand o[4];
-    for (int i = 0; i < 4; ++i) o[i] = rgba ? plane_operand(img->planes[i]) : i < 3 ? plane_operand(img->planes[0]) : Operand{ nullptr, 0, 1.0f };
-    uint32_t n_res = 0;  // distinct resident planes the launch reads
-    for (int i = 0; i < n; ++i) n_res += o[i].ptr != nullptr && (rgba || i == 0);
+    const uint32_t n_res = image_source_operands(img, (1u << n) - 1, o);  // the distinct resident planes among the channels written
     const uint32_t w = img->w(), h = img->h();
     return with_stream_edges(hip_stream, [&] {
         const uint64_t in_bytes = (uint64_t)w * h * 4 * n_res, out_bytes = (uint64_t)w * h * n * elem_bytes(dst->dtype);

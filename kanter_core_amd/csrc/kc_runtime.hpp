@@ -369,12 +369,26 @@ inline void image_retain(kc_image *img)
 }
 void image_release(kc_image *img);
 int image_force(kc_image *img);
+// What every exporter reads.  o = the channels of `img` (forced) as to_u8 sees them (Gray: (v, v, v, 1)); returns the distinct
+// resident planes among the channels of `mask`, which is what a launch under that mask loads: the one n_resident of
+// cache_policy_mask and of alg_bytes
+uint32_t image_source_operands(const kc_image *img, uint32_t mask, Operand (&o)[4]);
+// What every importer writes.  p = `n_planes` (1: Gray, 4) fresh w x h planes, the first `n_mem` in memory (dp = their device
+// pointers), the others the constants 0, 0, 0, 1 by channel; on failure nothing is left allocated.  image_of_import_planes is
+// the tail of such a call: the image of the planes where `status` is KC_OK, the planes released either way; returns `status`.
+int image_planes_for_import(uint32_t w, uint32_t h, int n_mem, int n_planes, kc_plane *(&p)[4], float *(&dp)[4]);
+int image_of_import_planes(int status, int n_planes, kc_plane *(&p)[4], kc_image **out);
 
 // ---- node operators (ops.cpp) ----
 int image_from_value(kc_size size, float v, bool rgba, kc_image **out);
 int image_as_type(kc_image *img, bool rgba, kc_image **out);
 int image_from_u8(const uint8_t *host, uint32_t w, uint32_t h, int channels, kc_image **out);
 int image_to_u8(kc_image *img, bool srgb, uint8_t *host);
+// The u8 launches on the library's stream, with their cache policy and counters, between whatever copies and events the caller
+// puts around them (u8pipe.cpp): from_u8_kernel of the bytes at `dev_src` into a new RGBA image / to_u8_kernel of `img` (forced)
+// into the w * h * 4 bytes at `dev_dst`
+int enqueue_from_u8(const uint8_t *dev_src, int channels, uint32_t w, uint32_t h, kc_image **out);
+int enqueue_to_u8(kc_image *img, bool srgb, uint8_t *dev_dst);
 // device-memory images (devimage.cpp): the bodies of kc_device_image_validate / kc_image_from_device / kc_image_to_device
 int device_image_validate(const kc_device_image *d, size_t *extent_bytes);
 int image_from_device(const kc_device_image *src, uint32_t flags, void *hip_stream, kc_image **out);
@@ -431,9 +445,6 @@ constexpr uint32_t kBcPunchThroughBits = KC_BC_PUNCH_THROUGH | 0xff000000u;
 inline uint32_t bc_punch_through_ref(uint32_t flags) { return (flags & KC_BC_PUNCH_THROUGH) ? flags >> 24 : 0u; }
 // kc_bc1_punch_through_block's rule on the host: 16 RGBA8 texels -> the 8 bytes of the block (ref 1..255)
 void bc1_punch_through_block(const uint8_t rgba[64], uint32_t ref, uint8_t block[8]);
-// o = the channels of `img` (forced) as to_u8 sees them (Gray: (v, v, v, 1)); returns the distinct resident planes among the
-// channels of `mask`, which is what a launch under that mask loads
-uint32_t bc_source_operands(const kc_image *img, uint32_t mask, Operand (&o)[4]);
 // one launch of the encoder for `img` (forced already) into `dst`, block rows `row_pitch` bytes apart, on `s`
 // (pt_ref != 0: KC_BC_PUNCH_THROUGH with that reference byte)
 int bc_encode(kc_image *img, int format, bool srgb, char *dst, size_t row_pitch, hipStream_t s, uint32_t pt_ref = 0);
@@ -517,6 +528,7 @@ void preview_release();
 int image_channel_stats(kc_image *img, uint32_t flags, kc_channel_stats *out);
 uint32_t quant_u8_host(float v);  // streaming.h's quant_u8 on the host
 int stats_buffers(size_t partials_bytes);  // the context's StatsBuffers, with room for that many bytes of partial records
+int stats_fetch(uint32_t words);  // the first `words` result words of a reduction, in StatsBuffers::host once the call's event has fired
 void channel_stats_release();
 // signed distance fields (sdf.cpp): the rule's arithmetic as kc_sdf_cap and kc_sdf_texel return it, as the device computes it
 // (spread 1..KC_SDF_MAX_SPREAD), and the body of kc_image_distance_field

@@ -56,6 +56,45 @@ int image_as_type(kc_image *img, bool rgba, kc_image **out)
     return KC_OK;
 }
 
+// from_u8_kernel of the w x h x channels bytes at `dev_src` into fresh planes; the missing channels are constants.
+int enqueue_from_u8(const uint8_t *dev_src, int channels, uint32_t w, uint32_t h, kc_image **out)
+{
+    Context &c = ctx();
+    kc_plane *p[4];
+    float *dp[4];
+    int s = image_planes_for_import(w, h, channels, 4, p, dp);
+    if (s == KC_OK) {
+        const uint64_t in_bytes = (uint64_t)w * h * channels;
+        bool nt = false;
+        hipError_t e = launch_from_u8(dev_src, channels, w, h, dp, (uint32_t)(p[0]->pitch / 4), cache_policy_mask(in_bytes, 4 * in_bytes, 1), c.stream, &nt);
+        if (e != hipSuccess) s = hip_fail(e, "launch_from_u8");
+        else {
+            c.launches++;
+            if (nt) c.counters["from_u8_nt"]++;
+            c.alg_bytes += 5 * in_bytes;  // 1 B read + 4 B written per sample
+        }
+    }
+    return image_of_import_planes(s, 4, p, out);
+}
+
+// to_u8_kernel of `img` (forced already) into the w * h * 4 bytes at `dev_dst`; constants cost no loads.
+int enqueue_to_u8(kc_image *img, bool srgb, uint8_t *dev_dst)
+{
+    Context &c = ctx();
+    Operand o[4];
+    const uint32_t n_res = image_source_operands(img, 0xfu, o);
+    const uint32_t w = img->w(), h = img->h();
+    const uint64_t in_bytes = (uint64_t)w * h * 4 * n_res, out_bytes = (uint64_t)w * h * 4;
+    bool nt = false;
+    hipError_t e = launch_to_u8(o[0], o[1], o[2], o[3], img->is_rgba() ? 0 : 1, srgb ? 1 : 0, w, h, dev_dst,
+                                cache_policy_mask(in_bytes, out_bytes, n_res ? n_res : 1), c.stream, &nt);
+    if (e != hipSuccess) return hip_fail(e, "launch_to_u8");
+    c.launches++;
+    if (nt) c.counters["to_u8_nt"]++;
+    c.alg_bytes += in_bytes + out_bytes;
+    return KC_OK;
+}
+
 // deconstruct_image + read_slot_image, src/shared.rs:16-56,218-261.
 int image_from_u8(const uint8_t *host, uint32_t w, uint32_t h, int channels, kc_image **out)
 {
@@ -67,65 +106,44 @@ int image_from_u8(const uint8_t *host, uint32_t w, uint32_t h, int channels, kc_
     Context &c = ctx();
     std::lock_guard<std::recursive_mutex> lk(c.mu);
     const size_t nbytes = (size_t)w * h * channels;
-    const size_t block = (nbytes + 255) / 256 * 256;
-    void *staging = nullptr;
-    KC_TRY(pool_alloc(block, &staging));
-    kc_plane *p[4] = { nullptr, nullptr, nullptr, nullptr };
-    float *dp[4] = { nullptr, nullptr, nullptr, nullptr };
-    int s = KC_OK;
-    for (int i = 0; i < 4 && s == KC_OK; ++i) {
-        if (i < channels) {
-            s = plane_new_mem(w, h, &p[i]);
-            if (s == KC_OK) dp[i] = p[i]->dptr;
-        } else {
-            p[i] = plane_new_const(w, h, i == 3 ? 1.0f : 0.0f);
-        }
-    }
-    if (s == KC_OK) {
-        hipError_t e = hipSuccess;
-        // The caller may free `host` as soon as we return.  Small images (the reference's own sizes) go through a pinned
-        // ring slot and the call does not wait for the stream; larger ones are copied from `host` directly and waited for.
-        Context::UploadSlot *slot = nullptr;
-        if (c.opt.upload_ring && nbytes <= Context::kUploadSlotMax) {
-            slot = &c.upload_ring[c.upload_next];
-            c.upload_next = (c.upload_next + 1) % Context::kUploadSlots;
-            if (slot->bytes < nbytes) {
-                if (slot->host) {
-                    if (slot->copied) (void)hipEventSynchronize(slot->copied);
-                    (void)hipHostFree(slot->host);
-                    slot->host = nullptr;
-                    slot->bytes = 0;
-                }
-                const size_t want = std::max(nbytes, (size_t)256 << 10);
-                e = hipHostMalloc(&slot->host, want, hipHostMallocDefault);
-                if (e == hipSuccess) slot->bytes = want;
-                else slot->host = nullptr;
+    PoolStaging staging;
+    KC_TRY(staging.alloc(nbytes));
+    hipError_t e = hipSuccess;
+    // The caller may free `host` as soon as we return.  Small images (the reference's own sizes) go through a pinned
+    // ring slot and the call does not wait for the stream; larger ones are copied from `host` directly and waited for.
+    Context::UploadSlot *slot = nullptr;
+    if (c.opt.upload_ring && nbytes <= Context::kUploadSlotMax) {
+        slot = &c.upload_ring[c.upload_next];
+        c.upload_next = (c.upload_next + 1) % Context::kUploadSlots;
+        if (slot->bytes < nbytes) {
+            if (slot->host) {
+                if (slot->copied) (void)hipEventSynchronize(slot->copied);
+                (void)hipHostFree(slot->host);
+                slot->host = nullptr;
+                slot->bytes = 0;
             }
-            if (e == hipSuccess && !slot->copied) e = hipEventCreateWithFlags(&slot->copied, hipEventDisableTiming);
-            else if (e == hipSuccess) e = hipEventSynchronize(slot->copied);  // the slot's previous upload
-            if (e == hipSuccess) {
-                std::memcpy(slot->host, host, nbytes);
-                e = hipMemcpyAsync(staging, slot->host, nbytes, hipMemcpyHostToDevice, c.stream);
-                if (e == hipSuccess) e = hipEventRecord(slot->copied, c.stream);
-            }
-        } else {
-            e = hipMemcpyAsync(staging, host, nbytes, hipMemcpyHostToDevice, c.stream);
+            const size_t want = std::max(nbytes, (size_t)256 << 10);
+            e = hipHostMalloc(&slot->host, want, hipHostMallocDefault);
+            if (e == hipSuccess) slot->bytes = want;
+            else slot->host = nullptr;
         }
-        bool nt = false;
-        if (e == hipSuccess)
-            e = launch_from_u8((const uint8_t *)staging, channels, w, h, dp, (uint32_t)(p[0]->pitch / 4),
-                               cache_policy_mask((uint64_t)w * h * channels, (uint64_t)w * h * 4 * channels, 1), c.stream, &nt);
-        if (e == hipSuccess && nt) c.counters["from_u8_nt"]++;
-        if (e == hipSuccess && !slot) e = hipStreamSynchronize(c.stream);
-        if (e != hipSuccess) s = hip_fail(e, "image_from_u8");
-        else {
-            c.launches++;
-            c.alg_bytes += (uint64_t)w * h * channels * 5;  // 1 B read + 4 B written per sample
+        if (e == hipSuccess && !slot->copied) e = hipEventCreateWithFlags(&slot->copied, hipEventDisableTiming);
+        else if (e == hipSuccess) e = hipEventSynchronize(slot->copied);  // the slot's previous upload
+        if (e == hipSuccess) {
+            std::memcpy(slot->host, host, nbytes);
+            e = hipMemcpyAsync(staging.ptr, slot->host, nbytes, hipMemcpyHostToDevice, c.stream);
+            if (e == hipSuccess) e = hipEventRecord(slot->copied, c.stream);
         }
+    } else {
+        e = hipMemcpyAsync(staging.ptr, host, nbytes, hipMemcpyHostToDevice, c.stream);
     }
-    pool_free(staging, block);
-    if (s == KC_OK) *out = image_new(4, p);
-    for (int i = 0; i < 4; ++i) plane_release(p[i]);
+    if (e != hipSuccess) return hip_fail(e, "image_from_u8");
+    kc_image *img = nullptr;
+    int s = enqueue_from_u8((const uint8_t *)staging.ptr, channels, w, h, &img);
+    if (!slot) e = hipStreamSynchronize(c.stream);  // whatever `s` says: the copy reads `host`
+    if (s == KC_OK && e != hipSuccess) s = hip_fail(e, "image_from_u8");
+    if (s == KC_OK) *out = img;
+    else image_release(img);
     return s;
 }
 
@@ -136,28 +154,12 @@ int image_to_u8(kc_image *img, bool srgb, uint8_t *host)
     Context &c = ctx();
     std::lock_guard<std::recursive_mutex> lk(c.mu);
     KC_TRY(image_force(img));
-    const uint32_t w = img->w(), h = img->h();
-    const size_t nbytes = (size_t)w * h * 4;
-    const size_t block = (nbytes + 255) / 256 * 256;
-    void *staging = nullptr;
-    KC_TRY(pool_alloc(block, &staging));
-    Operand o[4];
-    for (int i = 0; i < 4; ++i) o[i] = plane_operand(img->planes[img->is_rgba() ? i : 0]);
-    uint32_t n_res = 0;
-    for (int i = 0; i < (img->is_rgba() ? 4 : 1); ++i) n_res += o[i].ptr != nullptr;
-    bool nt = false;
-    hipError_t e = launch_to_u8(o[0], o[1], o[2], o[3], img->is_rgba() ? 0 : 1, srgb ? 1 : 0, w, h, (uint8_t *)staging,
-                                cache_policy_mask((uint64_t)w * h * 4 * n_res, nbytes, n_res ? n_res : 1), c.stream, &nt);
-    if (e == hipSuccess) {
-        c.launches++;
-        if (nt) c.counters["to_u8_nt"]++;
-        int resident = 0;
-        for (int i = 0; i < (img->is_rgba() ? 4 : 1); ++i) resident += o[i].ptr != nullptr;
-        c.alg_bytes += (uint64_t)w * h * 4 * (resident + 1);
-        e = hipMemcpyAsync(host, staging, nbytes, hipMemcpyDeviceToHost, c.stream);
-    }
+    const size_t nbytes = (size_t)img->w() * img->h() * 4;
+    PoolStaging staging;
+    KC_TRY(staging.alloc(nbytes));
+    KC_TRY(enqueue_to_u8(img, srgb, (uint8_t *)staging.ptr));
+    hipError_t e = hipMemcpyAsync(host, staging.ptr, nbytes, hipMemcpyDeviceToHost, c.stream);
     if (e == hipSuccess) e = hipStreamSynchronize(c.stream);
-    pool_free(staging, block);
     if (e != hipSuccess) return hip_fail(e, "image_to_u8");
     return KC_OK;
 }

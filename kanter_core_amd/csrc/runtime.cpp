@@ -422,6 +422,42 @@ Operand plane_operand(const kc_plane *p)
     return o;
 }
 
+uint32_t image_source_operands(const kc_image *img, uint32_t mask, Operand (&o)[4])
+{
+    const bool rgba = img->is_rgba();
+    for (int i = 0; i < 4; ++i) o[i] = rgba ? plane_operand(img->planes[i]) : i < 3 ? plane_operand(img->planes[0]) : Operand{ nullptr, 0, 1.0f };
+    const float *seen[4] = { nullptr, nullptr, nullptr, nullptr };
+    uint32_t n_res = 0;
+    for (int i = 0; i < 4; ++i) {
+        if (!((mask >> i) & 1u) || !o[i].ptr) continue;
+        bool dup = false;
+        for (uint32_t k = 0; k < n_res; ++k) dup |= seen[k] == o[i].ptr;
+        if (!dup) seen[n_res++] = o[i].ptr;
+    }
+    return n_res;
+}
+
+int image_planes_for_import(uint32_t w, uint32_t h, int n_mem, int n_planes, kc_plane *(&p)[4], float *(&dp)[4])
+{
+    for (int i = 0; i < 4; ++i) p[i] = nullptr, dp[i] = nullptr;
+    int s = KC_OK;
+    for (int i = 0; i < n_planes && s == KC_OK; ++i) {
+        if (i >= n_mem) p[i] = plane_new_const(w, h, i == 3 ? 1.0f : 0.0f);  // deconstruct_image: missing R, G, B = 0, A = 1
+        else if ((s = plane_new_mem(w, h, &p[i])) == KC_OK) dp[i] = p[i]->dptr;
+    }
+    return s == KC_OK ? s : image_of_import_planes(s, n_planes, p, nullptr);  // releases what was made
+}
+
+int image_of_import_planes(int status, int n_planes, kc_plane *(&p)[4], kc_image **out)
+{
+    if (status == KC_OK) *out = image_new(n_planes, p);
+    for (int i = 0; i < 4; ++i) {
+        plane_release(p[i]);
+        p[i] = nullptr;
+    }
+    return status;
+}
+
 // ---- building the kernel program for one lazy plane -------------------------------------
 struct BuiltChain {
     ChainProgram prog;

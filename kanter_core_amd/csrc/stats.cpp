@@ -88,6 +88,15 @@ int stats_buffers(size_t partials_bytes)
     return KC_OK;
 }
 
+int stats_fetch(uint32_t words)
+{
+    Context &c = ctx();
+    KC_HIP(hipMemcpyAsync(c.stats.host, c.stats.result, words * sizeof(unsigned long long), hipMemcpyDeviceToHost, c.stream));
+    KC_HIP(hipEventRecord(c.stats.done, c.stream));
+    KC_HIP(hipEventSynchronize(c.stats.done));
+    return KC_OK;
+}
+
 int image_channel_stats(kc_image *img, uint32_t flags, kc_channel_stats *out)
 {
     if (flags & ~(uint32_t)(KC_STATS_HISTOGRAM | KC_STATS_SRGB)) {
@@ -156,9 +165,7 @@ int image_channel_stats(kc_image *img, uint32_t flags, kc_channel_stats *out)
         c.launches += 2;
         if (nt) c.counters["stats_nt"]++;
         c.alg_bytes += in_bytes;
-        KC_HIP(hipMemcpyAsync(c.stats.host, c.stats.result, a.rec_words * sizeof(unsigned long long), hipMemcpyDeviceToHost, c.stream));
-        KC_HIP(hipEventRecord(c.stats.done, c.stream));
-        KC_HIP(hipEventSynchronize(c.stats.done));
+        KC_TRY(stats_fetch(a.rec_words));
         const unsigned long long *res = c.stats.host;
         for (int ch = 0; ch < n; ++ch) {
             const int s = slot_of[ch];

@@ -121,39 +121,21 @@ int u8_pipe_upload(kc_u8_pipe *p, int slot, kc_image **out)
     kc_u8_pipe::Slot *s = nullptr;
     KC_TRY(slot_of(p, slot, &s));
     Context &c = ctx();
-    kc_plane *pl[4] = { nullptr, nullptr, nullptr, nullptr };
-    float *dp[4] = { nullptr, nullptr, nullptr, nullptr };
-    int st = KC_OK;
-    for (int i = 0; i < 4 && st == KC_OK; ++i) {
-        if (i < p->channels) {
-            st = plane_new_mem(p->w, p->h, &pl[i]);
-            if (st == KC_OK) dp[i] = pl[i]->dptr;
-        } else {
-            pl[i] = plane_new_const(p->w, p->h, i == 3 ? 1.0f : 0.0f);
-        }
+    hipError_t e = hipSuccess;
+    if (s->in_used) e = hipStreamWaitEvent(p->up, s->converted, 0);  // the slot's previous image has been read
+    if (e == hipSuccess) e = hipMemcpyAsync(s->dev_in, s->host_in, p->in_bytes, hipMemcpyHostToDevice, p->up);
+    if (e == hipSuccess) e = hipEventRecord(s->copied_in, p->up);
+    if (e == hipSuccess) e = hipStreamWaitEvent(c.stream, s->copied_in, 0);
+    if (e != hipSuccess) return hip_fail(e, "kc_u8_pipe_upload");
+    kc_image *img = nullptr;
+    KC_TRY(enqueue_from_u8(s->dev_in, p->channels, p->w, p->h, &img));
+    if ((e = hipEventRecord(s->converted, c.stream)) != hipSuccess) {
+        image_release(img);
+        return hip_fail(e, "kc_u8_pipe_upload");
     }
-    if (st == KC_OK) {
-        hipError_t e = hipSuccess;
-        if (s->in_used) e = hipStreamWaitEvent(p->up, s->converted, 0);  // the slot's previous image has been read
-        if (e == hipSuccess) e = hipMemcpyAsync(s->dev_in, s->host_in, p->in_bytes, hipMemcpyHostToDevice, p->up);
-        if (e == hipSuccess) e = hipEventRecord(s->copied_in, p->up);
-        if (e == hipSuccess) e = hipStreamWaitEvent(c.stream, s->copied_in, 0);
-        bool nt = false;
-        if (e == hipSuccess)
-            e = launch_from_u8(s->dev_in, p->channels, p->w, p->h, dp, (uint32_t)(pl[0]->pitch / 4),
-                               cache_policy_mask(p->in_bytes, (uint64_t)p->w * p->h * 4 * p->channels, 1), c.stream, &nt);
-        if (e == hipSuccess && nt) c.counters["from_u8_nt"]++;
-        if (e == hipSuccess) e = hipEventRecord(s->converted, c.stream);
-        if (e != hipSuccess) st = hip_fail(e, "kc_u8_pipe_upload");
-        else {
-            s->in_used = true;
-            c.launches++;
-            c.alg_bytes += (uint64_t)p->w * p->h * p->channels * 5;  // 1 B read + 4 B written per sample
-        }
-    }
-    if (st == KC_OK) *out = image_new(4, pl);
-    for (int i = 0; i < 4; ++i) plane_release(pl[i]);
-    return st;
+    s->in_used = true;
+    *out = img;
+    return KC_OK;
 }
 
 // SlotImage::to_u8 / to_u8_srgb (src/slot_image.rs:141-207) into the slot's output buffer, asynchronously.
@@ -167,25 +149,14 @@ int u8_pipe_download(kc_u8_pipe *p, int slot, kc_image *img, bool srgb)
     }
     Context &c = ctx();
     KC_TRY(image_force(img));
-    Operand o[4];
-    for (int i = 0; i < 4; ++i) o[i] = plane_operand(img->planes[img->is_rgba() ? i : 0]);
-    uint32_t n_res = 0;
-    for (int i = 0; i < (img->is_rgba() ? 4 : 1); ++i) n_res += o[i].ptr != nullptr;
-    hipError_t e = hipSuccess;
-    if (s->out_used) e = hipStreamWaitEvent(c.stream, s->copied_out, 0);  // the slot's previous image has left dev_out
-    bool nt = false;
-    if (e == hipSuccess)
-        e = launch_to_u8(o[0], o[1], o[2], o[3], img->is_rgba() ? 0 : 1, srgb ? 1 : 0, p->w, p->h, s->dev_out,
-                         cache_policy_mask((uint64_t)p->w * p->h * 4 * n_res, p->out_bytes, n_res ? n_res : 1), c.stream, &nt);
-    if (e == hipSuccess && nt) c.counters["to_u8_nt"]++;
-    if (e == hipSuccess) e = hipEventRecord(s->packed, c.stream);
+    if (s->out_used) KC_HIP(hipStreamWaitEvent(c.stream, s->copied_out, 0));  // the slot's previous image has left dev_out
+    KC_TRY(enqueue_to_u8(img, srgb, s->dev_out));
+    hipError_t e = hipEventRecord(s->packed, c.stream);
     if (e == hipSuccess) e = hipStreamWaitEvent(p->down, s->packed, 0);
     if (e == hipSuccess) e = hipMemcpyAsync(s->host_out, s->dev_out, p->out_bytes, hipMemcpyDeviceToHost, p->down);
     if (e == hipSuccess) e = hipEventRecord(s->copied_out, p->down);
     if (e != hipSuccess) return hip_fail(e, "kc_u8_pipe_download");
     s->out_used = true;
-    c.launches++;
-    c.alg_bytes += (uint64_t)p->w * p->h * 4 * (n_res + 1);
     return KC_OK;
 }
 

@@ -27,7 +27,11 @@ would hardly occur.  The last test asserts that every row met every state and th
 skipped because the reference refuses their nodes.  No seed has found a defect so far; one that does is pinned in a
 test_seeds_that_found_defects case here, with its cause, as test_gpu_fuzz_graphs does.
 
-Run time on an MI355X: 19 s for the module (161 tests: 120 seeds with ten rows each, 40 hand-made cases, the coverage test), of
+test_exporters_count_distinct_resident_planes pins the same count of distinct resident planes on the exporters the rows' formulas
+leave out -- to_u8, to_torch to U8 and the u8 pipe's download -- on hand-made aliased, constant and Gray images, next to BC3.
+
+Run time on an MI355X: 19 s for the module (163 tests: 120 seeds with ten rows each, 40 hand-made cases, the two exporter-count
+cases, the coverage test), of
 which 12 s are the first test's set-up (library start-up); no seed takes longer than 0.3 s."""
 import ctypes as C
 
@@ -672,6 +676,51 @@ def test_consumers_behind_hand_made_states(kc, orc, torch, state, row):
     _consume(kc, orc, torch, row, lambda: HAND_STATES[state](kc, orc), np.random.default_rng([len(state), ROWS.index(row)]), state)
     torch.cuda.synchronize()  # the wrapped tensor is freed after the library has read it
     kc.sync()
+
+
+# ------------------------------------------------------------------ one count of resident planes for every exporter
+def _export_states(kc, orc, w, h):
+    """-> [(name, SlotImage, the oracle's image, the distinct resident planes among channels 0-3, among channels 0-1)]"""
+    p = [splitmix_plane(SEED_A, 40 + c, h, w) * np.float32(1.2) - np.float32(0.1) for c in range(4)]
+    p[0][0, :3] = [np.nan, np.inf, -0.0]
+    zero, one = np.zeros((h, w), np.float32), np.ones((h, w), np.float32)
+    g = kc.SlotImage.from_planes([p[0]])
+    return [("four planes", kc.SlotImage.from_planes(p), orc.Image(p), 4, 2),
+            ("one plane in four channels", kc.combine_rgba_process([g, g, g, g]), orc.Image([p[0]] * 4), 1, 1),
+            ("one plane as R and A, G and B constant", kc.combine_rgba_process([g, None, None, g]), orc.Image([p[0], zero, zero, p[0]]), 1, 1),
+            ("R and G constant, one plane as B and A", kc.combine_rgba_process([None, None, g, g]), orc.Image([zero, zero, p[0], p[0]]), 1, 0),
+            ("gray", g, orc.Image([p[0]]), 1, 1),
+            ("constant", kc.SlotImage.from_value((w, h), 0.25, True), orc.Image([one * np.float32(0.25)] * 3 + [one]), 0, 0)]
+
+
+@pytest.mark.parametrize("w,h", [(12, 8), (7, 5)])
+def test_exporters_count_distinct_resident_planes(kc, orc, torch, w, h):
+    """to_u8, to_torch to U8 and the u8 pipe's download read an image as to_bc does: a plane that sits in several channels is
+    loaded and counted once, a constant channel not at all.  On a forced image each call is one launch and
+    4 * w * h * (distinct resident planes among the channels written) + (bytes written) algorithmic bytes -- also where no
+    channel written is resident and the launch reads nothing -- and BC3, which reads all four channels, counts the same planes."""
+    pipe = kc.U8Pipe(w, h, 4, depth=1)
+    try:
+        for name, img, image, d4, d2 in _export_states(kc, orc, w, h):
+            def download(img=img):
+                pipe.download(0, img)
+                return pipe.wait_download(0).copy()
+            px, px_srgb = orc.to_u8(image), orc.to_u8(image, True)
+            calls = [("to_u8", lambda img=img: img.to_u8(), px, d4, 4),
+                     ("to_u8 srgb", lambda img=img: img.to_u8(True), px_srgb, d4, 4),
+                     ("to_torch 4 channels", lambda img=img: img.to_torch(torch.uint8, channels=4).cpu().numpy(), px, d4, 4),
+                     ("to_torch 2 channels", lambda img=img: img.to_torch(torch.uint8, channels=2).cpu().numpy(), np.ascontiguousarray(px[:, :, :2]), d2, 2),
+                     ("pipe download", download, px, d4, 4),
+                     ("to_bc bc3", lambda img=img: img.to_bc("bc3"), _ref_blocks(orc, image, 3, False), d4, None)]
+            for call_name, call, want, distinct, channels in calls:
+                what = "%d x %d, %s, %s" % (w, h, name, call_name)
+                _same(call(), want, what)  # nothing is left to force after it
+                got, launches, nbytes = _counted(kc, call)
+                _same(got, want, what + ", second call")
+                written = ((w + 3) // 4) * ((h + 3) // 4) * BLOCK_BYTES[3] if channels is None else w * h * channels
+                _check_cost(launches, nbytes, (1, 4 * w * h * distinct + written), what)
+    finally:
+        pipe.close()
 
 
 # ------------------------------------------------------------------ the coverage
