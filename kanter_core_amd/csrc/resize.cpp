@@ -957,6 +957,10 @@ int chain_resize_launch(const ChainProgram &P, int batch, int mode, kc_plane *co
     Context &c = ctx();
     *launched = false;
     if (mode != 0 || P.n_ops > 16 || P.n_in < 1 || P.n_in > 4) return KC_OK;
+    // neither fused kernel knows the code of a program that joins chains (runtime.cpp, chain_full_with, builds none with a
+    // resampled operand): never as if it were a plain step
+    for (uint32_t i = 0; i < P.n_ops; ++i)
+        if ((((i & 1u) ? P.step[0][i / 2].b.word : P.step[0][i / 2].a.word) & 0xffu) == CH_SAVE_LOAD) return KC_OK;
     const kc_plane *s0 = sampled[0];
     TapsEntry *tv = nullptr, *th = nullptr;
     KC_TRY(get_taps(s0->rz_src->h, s0->h, s0->rz_filter, &tv));

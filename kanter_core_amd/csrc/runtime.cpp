@@ -1092,6 +1092,9 @@ static bool chain_full_with(const kc_plane *acc, const kc_plane *opnd)
 {
     if (acc->link->length >= (uint32_t)KC_CHAIN_MAX_OPS) return true;
     int limit = chain_in_limit();
+    // the fused resize + chain kernels keep their programs plain (join_ok refuses a chain that holds a resampled operand; the
+    // other order is this one): a chain that holds a join runs first and the resampled operand meets its result
+    if (opnd->kind == kc_plane::RESIZE && acc->link->saved) return true;
     if (opnd->kind == kc_plane::RESIZE) limit = KC_CHAIN_INTERP_IN;  // the fused resize + chain kernels
     for (int i = 0; i < acc->link->n_in && i <= KC_CHAIN_MAX_IN; ++i)
         if (acc->link->ins[i].q == ~(size_t)0) limit = KC_CHAIN_INTERP_IN;
