@@ -293,7 +293,7 @@ def stats():
 
 
 def kernel_cache_set_dir(path):
-    """Where compiled kernels are kept between processes (csrc/specialize.cpp); None: the environment's choice, "off": nowhere."""
+    """Where compiled kernels are kept between processes (csrc/kernel_cache.cpp); None: the environment's choice, "off": nowhere."""
     _check(_lib.load().kc_kernel_cache_set_dir(None if path is None else str(path).encode()))
 
 

@@ -8,7 +8,7 @@
 #include <fstream>
 #include <sstream>
 
-#include "kc_runtime.hpp"
+#include "chain_codegen.h"
 
 namespace kc {
 const std::string &last_error();
@@ -351,64 +351,35 @@ try {
 }
 KC_CATCH
 
-int kc_specialize_compile_check(const uint32_t *words, uint32_t n_ops, uint32_t n_in, int start_src, int flat, char *source,
-                                size_t cap)
-try {
-    KC_ARG(words && n_ops >= 1 && n_ops <= (uint32_t)KC_CHAIN_MAX_OPS && n_in <= (uint32_t)KC_CHAIN_MAX_IN);
-    KC_ARG(start_src >= -1 && start_src < (int)n_in);
-    ChainProgram P;
-    std::memset(&P, 0, sizeof P);
-    P.n_ops = n_ops;
-    P.n_in = n_in;
-    P.start_src = start_src;
-    P.rows = flat ? 1u : 2u;
-    P.row_units = 1;
-    for (uint32_t i = 0; i < n_ops; ++i) {
-        const uint32_t from = (words[i] >> 8) & 0xffu, level = words[i] >> 16;
-        KC_ARG((words[i] & 0xffu) <= CH_SAVE_LOAD && (from <= n_in || (from == (uint32_t)KC_CHAIN_SRC_SAVED && (words[i] & 0xffu) != CH_SAVE_LOAD)));
-        KC_ARG(level < (uint32_t)KC_CHAIN_MAX_SAVED && (level == 0 || from == (uint32_t)KC_CHAIN_SRC_SAVED || (words[i] & 0xffu) == CH_SAVE_LOAD));
-        ((i & 1u) ? P.step[0][i / 2].b : P.step[0][i / 2].a).word = words[i];
-    }
-    if (source && cap) {
-        const std::string src = specialize_source(P);
-        std::snprintf(source, cap, "%s", src.c_str());
-    }
+// The text of a signature's kernel into `source` (optional) and a compile of it for gfx950; `what` names the kernel in the message.
+static int compile_check(const Signature &sig, const char *what, char *source, size_t cap)
+{
+    const std::string src = generate(sig);
+    if (source && cap) std::snprintf(source, cap, "%s", src.c_str());
     std::string log;
-    int s = specialize_compile_only(P, &log);
-    if (s != KC_OK) set_error("specialised chain kernel did not compile: " + log);
+    const int s = specialize_compile_only(src, &log);
+    if (s != KC_OK) set_error(std::string(what) + " did not compile: " + log);
     return s;
 }
-KC_CATCH
 
 int kc_specialize_compile_check_mask(const uint32_t *words, uint32_t n_ops, uint32_t n_in, int start_src, int flat, uint32_t nt_mask,
                                      char *source, size_t cap)
 try {
     KC_ARG(words && n_ops >= 1 && n_ops <= (uint32_t)KC_CHAIN_MAX_OPS && n_in <= (uint32_t)KC_CHAIN_MAX_IN);
     KC_ARG(start_src >= -1 && start_src < (int)n_in);
-    ChainProgram P;
-    std::memset(&P, 0, sizeof P);
-    P.n_ops = n_ops;
-    P.n_in = n_in;
-    P.start_src = start_src;
-    P.rows = flat ? 1u : 2u;
-    P.row_units = 1;
-    P.nt_mask = nt_mask;
     for (uint32_t i = 0; i < n_ops; ++i) {
         const uint32_t from = (words[i] >> 8) & 0xffu, level = words[i] >> 16;
         KC_ARG((words[i] & 0xffu) <= CH_SAVE_LOAD && (from <= n_in || (from == (uint32_t)KC_CHAIN_SRC_SAVED && (words[i] & 0xffu) != CH_SAVE_LOAD)));
         KC_ARG(level < (uint32_t)KC_CHAIN_MAX_SAVED && (level == 0 || from == (uint32_t)KC_CHAIN_SRC_SAVED || (words[i] & 0xffu) == CH_SAVE_LOAD));
-        ((i & 1u) ? P.step[0][i / 2].b : P.step[0][i / 2].a).word = words[i];
     }
-    if (source && cap) {
-        const std::string src = specialize_source(P);
-        std::snprintf(source, cap, "%s", src.c_str());
-    }
-    std::string log;
-    int s = specialize_compile_only(P, &log);
-    if (s != KC_OK) set_error("specialised chain kernel did not compile: " + log);
-    return s;
+    return compile_check(make_signature(words, n_ops, n_in, start_src, flat != 0, nt_mask, 0, 0, false), "specialised chain kernel", source, cap);
 }
 KC_CATCH
+
+int kc_specialize_compile_check(const uint32_t *words, uint32_t n_ops, uint32_t n_in, int start_src, int flat, char *source, size_t cap)
+{
+    return kc_specialize_compile_check_mask(words, n_ops, n_in, start_src, flat, 0, source, cap);
+}
 
 int kc_set_chain_quads(int quads)
 try {
@@ -507,9 +478,7 @@ int kc_specialize_reset(void)
 try {
     Lock lk(ctx().mu);
     if (ctx().stream) (void)hipStreamSynchronize(ctx().stream);
-    const int mode = specialize_get_mode();
     specialize_shutdown();
-    (void)mode;
     return KC_OK;
 }
 KC_CATCH
@@ -519,27 +488,9 @@ int kc_specialize_compile_check_upsample(const uint32_t *words, uint32_t n_ops, 
 try {
     KC_ARG(words && n_ops >= 1 && n_ops <= (uint32_t)KC_CHAIN_MAX_OPS && n_in >= 1 && n_in <= (uint32_t)KC_CHAIN_INTERP_IN);
     KC_ARG(start_src >= -1 && start_src < (int)n_in && (taps == 1 || taps == 3));
-    ChainProgram P;
-    std::memset(&P, 0, sizeof P);
-    P.n_ops = n_ops;
-    P.n_in = n_in;
-    P.start_src = start_src;
-    for (uint32_t i = 0; i < n_ops; ++i) {
-        const uint32_t from = words[i] >> 8, code = words[i] & 0xffu;
-        KC_ARG(code <= CH_MUL_INV && from <= n_in && code != CH_DIV_L && code != CH_DIV_R && code != CH_POW_L && code != CH_POW_R);
-        ((i & 1u) ? P.step[0][i / 2].b : P.step[0][i / 2].a).word = words[i];
-    }
-    UpsampleArgs U{};
-    U.H.taps = U.V.taps = taps;
-    U.tile_w = wide ? 1024u : 256u;
-    if (source && cap) {
-        const std::string src = specialize_source(P, &U);
-        std::snprintf(source, cap, "%s", src.c_str());
-    }
-    std::string log;
-    int s = specialize_compile_only(P, &log, &U);
-    if (s != KC_OK) set_error("specialised up-sampling kernel did not compile: " + log);
-    return s;
+    for (uint32_t i = 0; i < n_ops; ++i) KC_ARG((words[i] & 0xffu) <= CH_MUL_INV && words[i] >> 8 <= n_in);
+    KC_ARG(!has_div_or_pow(words, n_ops));
+    return compile_check(make_signature(words, n_ops, n_in, start_src, false, 0, 0, taps, wide != 0), "specialised up-sampling kernel", source, cap);
 }
 KC_CATCH
 

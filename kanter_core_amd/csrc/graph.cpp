@@ -1122,8 +1122,7 @@ int kc_live_graph::await_clean(uint32_t id)
     // there is no chance of finding a compiled kernel for anything else: a process that evaluates a graph once must not pay for
     // programs whose own kernels it will never see compiled.  From the second evaluation on the chains are built for those
     // kernels (csrc/runtime.cpp chain_in_limit / join_ok); "compile at first sight" (kc_set_specialize(2)) has them from the
-    // start, and so has a process that finds code objects of earlier processes or of the build on disk (specialize.cpp,
-    // kernel cache) -- where a program's kernel is missing all the same, chain_launch cuts the chain as before.
+    // start, and so has a process that finds code objects of earlier processes or of the build on disk (kernel_cache.cpp) -- where a program's kernel is missing all the same, chain_launch cuts the chain as before.
     Context &c = ctx();
     const bool plain_before = c.plain_chains;
     c.plain_chains = plain_before || (walks == 0 && specialize_get_mode() == 1 && !kernel_cache_populated());

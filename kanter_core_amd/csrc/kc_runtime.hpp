@@ -555,7 +555,7 @@ int resize_force_many(kc_plane *const *planes, int n);  // same; equal resamples
 // in registers, tile does not fit LDS, program too long): the caller forces the RESIZE planes.
 int chain_resize_launch(const ChainProgram &P, int batch, int mode, kc_plane *const *sampled, bool *launched);
 
-// ---- run-time specialisation of the chain kernel (specialize.cpp) ----
+// ---- run-time specialisation of the chain kernel (chain_codegen.cpp: signature and text; specialize.cpp: hiprtc, registry, launches) ----
 // *nt_mask, *quads (optional): the cache-policy bits and the float4 per lane of the kernel that was launched
 hipError_t launch_chain_specialized(const ChainProgram &P, int batch, hipStream_t s, bool *launched, uint32_t *nt_mask, uint32_t *quads = nullptr);
 // Which streams of a launch are marked nontemporal: `in_bytes` / `out_bytes` = what the launch reads from its n_resident
@@ -571,7 +571,7 @@ hipError_t chain_dispatch(ChainProgram &P, int batch, int mode, uint32_t w, uint
 uint32_t pack_chain_inputs(const ChainProgram &P, int batch, kc_plane *const (*src)[KC_CHAIN_MAX_IN], const uint32_t *refs, uint32_t w, uint32_t h);
 void plane_shadow_drop(kc_plane *p, bool never_again);  // before an in-place write (never_again: the pointer leaves the library)
 uint32_t pack_bytes_per_quad(uint32_t tier);            // 16 for KC_PACK_NONE
-bool chain_pack_program_ok(const ChainProgram &P);      // specialize.cpp: a flat {+, -, *} program whose kernel may read packed inputs
+bool chain_pack_program_ok(const ChainProgram &P);      // chain_codegen.cpp: a flat {+, -, *} program whose kernel may read packed inputs
 hipError_t launch_upsample_chain_specialized(const ChainProgram &P, int batch, const UpsampleArgs &U, hipStream_t s, bool *launched);
 int specialize_set_mode(int mode, int after);  // 0 off, 1 background compile after `after` sightings, 2 compile at once
 int specialize_get_mode();
@@ -582,8 +582,21 @@ void specialize_stats(uint64_t *compiled, uint64_t *failed, uint64_t *launches, 
 std::string specialize_last_log();
 void specialize_shutdown();
 std::string specialize_source(const ChainProgram &P, const UpsampleArgs *U = nullptr);
-int specialize_compile_only(const ChainProgram &P, std::string *log, const UpsampleArgs *U = nullptr);
-// code objects that outlive the process (specialize.cpp, "code objects that outlive the process")
+int specialize_compile_only(const std::string &src, std::string *log);
+// what a cache file depends on besides the source text; the compile unit (specialize.cpp) hands it to kernel_cache.cpp
+struct CompilerId {
+    const char *const *opts;
+    int n_opts;
+    int version[2];  // of hiprtc
+};
+const CompilerId &compiler_id();
+int rtc_compile(const std::string &src, std::vector<char> &code, std::string *log);
+// code objects that outlive the process (kernel_cache.cpp)
+struct Signature;  // chain_codegen.h
+bool disk_load(const Signature &sig, const std::string &src, const CompilerId &cc, std::vector<char> &code);
+void disk_load_refused();
+void disk_store(const Signature &sig, const std::string &src, const CompilerId &cc, const std::vector<char> &code);
+void disk_counters(uint64_t *hits, uint64_t *rejected, uint64_t *written);
 int kernel_cache_set_dir(const char *dir);
 void kernel_cache_stats(uint64_t *hits, uint64_t *rejected, uint64_t *written, uint64_t *kernels_loaded);
 bool kernel_cache_populated();

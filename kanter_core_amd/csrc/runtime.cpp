@@ -644,7 +644,7 @@ uint32_t cache_policy_mask(uint64_t in_bytes, uint64_t out_bytes, uint32_t n_res
 // chain_interp_k<K>_u<U>_m<MODE>[_nt]: chain_kernel<K, U, MODE, NT>; chain_k0_m<MODE>: chain_kernel_k0<MODE>;
 // chain1_nt<bits>: chain1_kernel's nontemporal bits (1 start, 2 operand, 4 result); specialized_nt_<hex>: the cache-policy
 // bits a compiled kernel carries (bits 0-7 inputs 0-7, 0x100 the result; the bits of inputs 8-15 are not part of the name),
-// with "_q2" / "_q4" behind it when the kernel handles that many float4 per lane (specialize.cpp, chain_quads_for), and "_pk"
+// with "_q2" / "_q4" behind it when the kernel handles that many float4 per lane (chain_codegen.cpp, chain_quads_for), and "_pk"
 // last when the launch read packed copies of inputs (chain_pack.cpp; "packed_launches" counts those of every form).
 namespace {
 struct ChainCounterNames {

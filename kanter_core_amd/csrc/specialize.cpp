@@ -1,42 +1,14 @@
-// Run-time specialisation of the fused chain kernel.
-//
-// chain_kernel<K,U,MODE> (chain.hip) interprets a step table: per step ~13 scalar instructions of decode
-// and a branch, amortised over four float4 per lane.  PMC on the BASELINE graph showed more scalar than
-// vector instructions and 52 % of wave cycles issue-stalled; worse, the interpreter needs U = 4 to amortise
-// the decode, and four float4 per lane is the memory system's slower operating point (profiles/
-// r02_straightline.txt: 105.9 us at U = 4, 102.9 us at U = 1, 100.7 us with 64-thread workgroups, for the
-// same 604 MB).  The step list is known on the host before the launch, so for a program that keeps coming
-// back (an editor re-evaluating a graph, a batch job running one graph over many images) the library emits
-// the SAME per-pixel operations as straight-line HIP -- one line per record, constants still fetched from the
-// argument block so that programs differing only in constants share a kernel -- compiles it with hiprtc
-// (the parity flags of the offline build: -ffp-contract=off, correctly rounded divide / sqrt) on a worker
-// thread, and uses it from the next launch on.  The interpreter stays the immediate path: first sightings,
-// a missing libhiprtc, and a failed compile all run through it, on the GPU, with identical results (the
-// tests run every chain case in both modes and compare bit for bit).
-//
-// This replaces nothing of the reference: it is how the Mix loops of src/node/mix.rs:136-192 reach the HBM
-// roofline when N of them are fused into one launch.
+// Run-time specialisation of the fused chain kernel: hiprtc, the registry of compiled kernels with its worker thread, and
+// the launches.  What a kernel is and what its text says: chain_codegen.cpp; its file on disk: kernel_cache.cpp.
 #include <dlfcn.h>
-#include <sys/stat.h>
-#include <unistd.h>
 
 #include <condition_variable>
-#include <cstdio>
 #include <cstdlib>
-#include <cstring>
 #include <thread>
 
-#include "kc_runtime.hpp"
+#include "chain_codegen.h"
 
 namespace kc {
-
-extern const char kJitChainProgramH[];  // chain_program.h as text (generated by build.py)
-extern const char kJitPowPositiveInc[];  // pow_positive.inc as text
-extern const char kJitUpsampleH[];         // upsample.h as text
-extern const char kJitUpsampleChainInc[];  // upsample_chain.inc as text
-// chain_pack.h as text.  Weak: a program that links this file on its own for the generator's sake (tests/c_host) and never
-// asks for a kernel with packed inputs does without it.
-extern const char kJitChainPackH[] __attribute__((weak));
 
 namespace {
 
@@ -53,7 +25,6 @@ struct Rtc {
     int (*destroy)(hiprtcProgram *) = nullptr;
     int (*version)(int *, int *) = nullptr;
     bool ok = false;
-    bool tried = false;
 };
 
 void specialize_stop_at_exit();
@@ -64,7 +35,6 @@ Rtc &rtc()
     static Rtc r;
     static std::once_flag once;
     std::call_once(once, [] {
-        r.tried = true;
         for (const char *name : { "libhiprtc.so", "libhiprtc.so.7", "/opt/rocm/lib/libhiprtc.so" }) {
             r.lib = dlopen(name, RTLD_NOW | RTLD_LOCAL);
             if (r.lib) break;
@@ -89,657 +59,57 @@ Rtc &rtc()
     return r;
 }
 
-// ---- signature: everything the generated code depends on (constants and pointers do not) ----
-struct Signature {
-    uint32_t n_in = 0, n_ops = 0;
-    int32_t start_src = 0;
-    bool flat = false;
-    // up_taps > 0: the program runs inside the integer-ratio up-sampling kernel (upsample_chain.inc), input slot
-    // n_in - 1 being the resampled operand; up_wide = its 1024-column tile form
-    uint32_t up_taps = 0;
-    bool up_wide = false;
-    uint32_t nt_mask = 0;  // ChainProgram::nt_mask: which loads / stores carry the nontemporal hint (plain chain kernels)
-    uint32_t quads = 1;    // float4 per lane (chain_quads_for); the grid of a launch follows from it
-    uint32_t in_tiers = 0; // ChainProgram::in_tiers: which inputs are read from their packed copies (plain flat chain kernels)
-    uint32_t word[KC_CHAIN_MAX_OPS] = {};
-
-    std::string key() const
-    {
-        std::string k((const char *)&n_in, sizeof n_in);
-        k.append((const char *)&n_ops, sizeof n_ops);
-        k.append((const char *)&start_src, sizeof start_src);
-        k.push_back(flat ? 'f' : 'p');
-        k.push_back((char)('0' + up_taps));
-        k.push_back(up_wide ? 'w' : 'n');
-        k.append((const char *)&nt_mask, sizeof nt_mask);
-        k.append((const char *)word, sizeof(uint32_t) * n_ops);
-        if (quads > 1) {  // (a one-quad kernel keeps the key, and so the name, it always had)
-            k.push_back('q');
-            k.push_back((char)('0' + quads));
-        }
-        if (in_tiers) {  // (likewise: a kernel that reads f32 only keeps its key)
-            k.push_back('t');
-            k.append((const char *)&in_tiers, sizeof in_tiers);
-        }
-        return k;
-    }
-};
-
-// How many float4 a lane of the plain chain kernel of `s` handles.  One, as ever, unless the launch is the warm case of
-// chain_cache_policy -- at least one input left plain (served by the Infinity Cache) beside a nontemporal input or result --
-// of a flat {+, -, *} program: there the wave slots, not the bandwidth, limit the launch, and a slot that holds kQuadsWarm
-// quads has the loads of the later ones outstanding while the body of the first runs (DESIGN.md section 3,
-// profiles/chain_inflight_times.txt).  Programs of up to kQuadsMaxOps records only: the gain is measured at 1 and at 16
-// records, and the two launches of 40 records each of a 160-node graph are 5.6 % SLOWER with two quads per lane (vector
-// issue is then 0.7 of the time the bytes take, and half as many waves of twice the length interleave it worse with the
-// memory traffic).  `forced`: the chain_quads setting, 0 = this rule, 1 / 2 / 4 = that many where eligible.
-constexpr uint32_t kQuadsWarm = 2, kQuadsMaxOps = 16;
-std::atomic<int> g_chain_quads{ 0 };
-
-uint32_t chain_quads_for(const Signature &s, uint64_t total_units)
-{
-    if (s.up_taps || !s.flat || s.n_in < 1 || s.n_ops > kQuadsMaxOps || total_units > 0xF0000000ull) return 1;
-    bool plain = false;
-    for (uint32_t k = 0; k < s.n_in; ++k) plain |= !(s.nt_mask & KC_CHAIN_NT_BIT(k));
-    if (!plain || !s.nt_mask) return 1;
-    for (uint32_t i = 0; i < s.n_ops; ++i) {
-        const uint32_t code = s.word[i] & 0xffu;
-        if (code == CH_DIV_L || code == CH_DIV_R || code == CH_POW_L || code == CH_POW_R) return 1;
-    }
-    const int forced = g_chain_quads.load(std::memory_order_relaxed);
-    return forced ? (uint32_t)forced : kQuadsWarm;
-}
-
-// May the kernel of this program read packed inputs?  {+, -, *} programs of up to kQuadsMaxOps records: there the decode (some
-// 24 vector instructions per quad for two FIX24 inputs) stays under the time the bytes take; divide and Pow programs and longer
-// ones keep f32 (the two 40-record launches of a 160-node graph issue for 0.7 of their byte time already).
-bool pack_program_ok(const ChainProgram &P)
-{
-    if (P.n_ops < 1 || P.n_ops > kQuadsMaxOps || P.n_in < 1 || P.rows != 1) return false;
-    for (uint32_t i = 0; i < P.n_ops; ++i) {
-        const uint32_t code = ((i & 1u) ? P.step[0][i / 2].b.word : P.step[0][i / 2].a.word) & 0xffu;
-        if (code == CH_DIV_L || code == CH_DIV_R || code == CH_POW_L || code == CH_POW_R) return false;
-    }
-    return true;
-}
-
-Signature signature_of(const ChainProgram &P, const UpsampleArgs *U = nullptr)
-{
-    Signature s;
-    s.n_in = P.n_in;
-    s.n_ops = P.n_ops;
-    s.start_src = P.start_src;
-    s.flat = U ? false : P.rows == 1;
-    {
-        uint32_t valid = 0x100u;
-        for (uint32_t k = 0; k < (U ? P.n_in - 1u : P.n_in); ++k) valid |= KC_CHAIN_NT_BIT(k);
-        s.nt_mask = P.nt_mask & valid;
-    }
-    if (U) {
-        s.up_taps = U->H.taps;
-        s.up_wide = U->tile_w == 1024;
-    }
-    for (uint32_t i = 0; i < P.n_ops; ++i) s.word[i] = (i & 1u) ? P.step[0][i / 2].b.word : P.step[0][i / 2].a.word;
-    if (!U && s.flat) s.in_tiers = P.n_in >= 16 ? P.in_tiers : P.in_tiers & ((1u << (2 * P.n_in)) - 1u);
-    s.quads = chain_quads_for(s, (uint64_t)P.rows * P.row_units);
-    return s;
-}
-
-// ---- the generator ----
-// Workgroup size of the generated kernels; one float4 per lane.  On the headline workload 64 / 128 / 256 / 1024
-// measure 102.3-103.2 / 103.9 / 102.4-102.7 / 103.1-103.2 us (profiles/r02_spec_wg_sweep.txt; interpreter 108.5):
-// nothing between them, 256 kept.  KC_SPEC_WG overrides for tuning.
-static int spec_wg()
-{
-    static int wg = [] {
-        int v = 256;
-        if (const char *e = std::getenv("KC_SPEC_WG")) {
-            const int x = std::atoi(e);
-            if (x == 64 || x == 128 || x == 256 || x == 512 || x == 1024) v = x;
-        }
-        return v;
-    }();
-    return wg;
-}
-
-// Kernel name of a signature: kc_chain_<8 hex digits of an FNV-1a hash of its key>, so that profilers list every
-// program separately.
-std::string kernel_name(const Signature &s)
-{
-    uint32_t h = 2166136261u;
-    for (unsigned char c : s.key()) h = (h ^ c) * 16777619u;
-    char buf[32];
-    std::snprintf(buf, sizeof buf, s.up_taps ? "kc_upchain_%08x" : "kc_chain_%08x", h);
-    return buf;
-}
-
-// The value type of the plain generated kernels.  Every record is two roundings on a float4 -- "acc op x", then for the *_INV
-// codes "c - that" -- and gfx950 has packed f32 adds and multiplies that do two lanes of a float4 per instruction.  The
-// compiler selects them for + and * on float pairs but not for -: a <2 x float> fsub is split into two v_sub_f32 (and
-// "a + (-b)" is folded back to fsub first), which made a record 6 vector instructions where 4 do: PMC counted 103 per
-// wave on the 16-record headline program, 64 of them v_sub_f32.  So in these kernels f4 is a struct of two float pairs
-// whose operator- is ONE v_pk_add_f32 with the negate modifier on the subtrahend -- the same IEEE subtraction -- and `pp`
-// is a view of the record table whose .a.c / .b.c carry the 8-byte record { word, c } in scalar registers: "c - x" takes c
-// as the low dword of a scalar pair that both halves read (op_sel_hi 0 on that source, the form the compiler itself uses
-// for a splat from scalar registers), with two scalar moves and no vector register.
-// Where a constant is used as a value it converts to float (f4{ c, c, c, c }); + and * take such a splat from scalar
-// registers by themselves, - copies it to a vector pair first.  The asm statements are not volatile and have plain
-// register operands, so the scheduler moves them like any other instruction.  Division and pow stay per component.
-// The statements of the kernel body keep their spelling (step_expr); the up-sampling form keeps the plain vector f4 of
-// upsample_chain.inc, which the offline build shares.
-static const char kPackedF4[] = R"KCF4(typedef float raw4 __attribute__((ext_vector_type(4)));
-typedef float f2 __attribute__((ext_vector_type(2)));
-typedef unsigned long long __attribute__((may_alias)) rec64;
-static __device__ __forceinline__ f2 pk_sub(f2 a, f2 b)
-{
-    f2 d;
-    asm("v_pk_add_f32 %0, %1, %2 neg_lo:[0,1] neg_hi:[0,1]" : "=v"(d) : "v"(a), "v"(b));
-    return d;
-}
-struct kconst {
-    rec64 rec;  // { word, c }
-    __device__ __forceinline__ operator float() const { return __builtin_bit_cast(float, (unsigned int)(rec >> 32)); }
-    __device__ __forceinline__ f2 minus(f2 b) const
-    {
-        f2 d;
-        asm("v_pk_add_f32 %0, %1, %2 op_sel_hi:[0,1] neg_lo:[0,1] neg_hi:[0,1]" : "=v"(d) : "s"(rec >> 32), "v"(b));
-        return d;
-    }
-};
-struct f4 {
-    f2 lo, hi;
-    f4() = default;
-    __device__ __forceinline__ f4(float x, float y, float z, float w) : lo{ x, y }, hi{ z, w } {}
-    __device__ __forceinline__ f4(f2 l, f2 h) : lo(l), hi(h) {}
-    __device__ __forceinline__ f4(raw4 v) : lo(v.xy), hi(v.zw) {}
-    __device__ __forceinline__ raw4 raw() const { return raw4{ lo.x, lo.y, hi.x, hi.y }; }
-};
-static __device__ __forceinline__ f4 operator+(f4 a, f4 b) { return f4(a.lo + b.lo, a.hi + b.hi); }
-static __device__ __forceinline__ f4 operator*(f4 a, f4 b) { return f4(a.lo * b.lo, a.hi * b.hi); }
-static __device__ __forceinline__ f4 operator-(f4 a, f4 b) { return f4(pk_sub(a.lo, b.lo), pk_sub(a.hi, b.hi)); }
-static __device__ __forceinline__ f4 operator-(kconst c, f4 b) { return f4(c.minus(b.lo), c.minus(b.hi)); }
-static __device__ __forceinline__ f4 operator/(f4 a, f4 b) { return f4(a.raw() / b.raw()); }
-struct StepRecView { kconst c; };
-struct StepPairView { StepRecView a, b; };
-struct StepTableView {
-    const ChainStepPair *p;
-    __device__ __forceinline__ StepPairView operator[](unsigned int i) const
-    {
-        const rec64 *q = reinterpret_cast<const rec64 *>(p + i);
-        return StepPairView{ { { q[0] } }, { { q[1] } } };
-    }
-};
-)KCF4";
-
-// One step as an expression on `acc`; operands are `in<k><suffix>` or the step's constant splatted.  Empty: unknown code.
-static std::string step_expr(const Signature &s, uint32_t i, const char *in_prefix, const char *in_suffix)
-{
-    const uint32_t code = s.word[i] & 0xffu, from = (s.word[i] >> 8) & 0xffu, level = (s.word[i] >> 16) & 3u;
-    char c[48], x[96];
-    std::snprintf(c, sizeof c, "pp[%u].%c.c", i / 2, (i & 1u) ? 'b' : 'a');
-    if (from == 0)
-        std::snprintf(x, sizeof x, "f4{ %s, %s, %s, %s }", c, c, c, c);
-    else if (from == (uint32_t)KC_CHAIN_SRC_SAVED)
-        std::snprintf(x, sizeof x, "saved%u", level);  // the value CH_SAVE_LOAD put aside
-    else
-        std::snprintf(x, sizeof x, "%s%u%s", in_prefix, from - 1, in_suffix);
-    switch (code) {
-    case CH_SAVE_LOAD: return "(saved" + std::to_string(level) + " = acc, " + x + ")";  // acc = (savedN = acc, x)
-    case CH_ADD: return std::string("acc + ") + x;
-    case CH_SUB_L: return std::string("acc - ") + x;
-    case CH_SUB_R: return std::string(x) + " - acc";
-    case CH_MUL: return std::string("acc * ") + x;
-    case CH_DIV_L: return std::string("acc / ") + x;
-    case CH_DIV_R: return std::string(x) + " / acc";
-    case CH_POW_L: return std::string("pow4(acc, ") + x + ", pow_tab)";
-    case CH_POW_R: return std::string("pow4(") + x + ", acc, pow_tab)";
-    case CH_ADD_INV: return std::string(c) + " - (acc + " + x + ")";
-    case CH_SUBL_INV: return std::string(c) + " - (acc - " + x + ")";
-    case CH_SUBR_INV: return std::string(c) + " - (" + x + " - acc)";
-    case CH_MUL_INV: return std::string(c) + " - (acc * " + x + ")";
-    default: return std::string();
-    }
-}
-
-// The program inside the up-sampling kernel: the tile function of the offline build (upsample_chain.inc, embedded as text)
-// instantiated with the chain as a straight-line functor.  {+, -, *} programs only (the host sends nothing else there).
-static std::string generate_up(const Signature &s)
-{
-    std::string src;
-    src.reserve(32768);
-    src += "namespace kc {\n";
-    src += kJitChainProgramH;
-    src += kJitUpsampleH;
-    src += "typedef float f4 __attribute__((ext_vector_type(4)));\n";
-    src += kJitUpsampleChainInc;
-    char buf[320];
-    std::snprintf(buf, sizeof buf,
-                  "struct UpProg {\n    const ChainProgram &P;\n"
-                  "    __device__ __forceinline__ void operator()(const f4 (&in)[%u][%u], f4 (&out)[%u]) const\n    {\n"
-                  "        const unsigned int b = blockIdx.z;\n        const ChainStepPair *pp = P.step[b];\n"
-                  "#pragma unroll\n        for (int u = 0; u < %u; ++u) {\n",
-                  s.n_in, KC_UPSAMPLE_ROWS, KC_UPSAMPLE_ROWS, KC_UPSAMPLE_ROWS);
-    src += buf;
-    if (s.start_src < 0)
-        src += "            f4 acc = f4{ P.start_c[b], P.start_c[b], P.start_c[b], P.start_c[b] };\n";
-    else {
-        std::snprintf(buf, sizeof buf, "            f4 acc = in[%d][u];\n", s.start_src);
-        src += buf;
-    }
-    for (uint32_t i = 0; i < s.n_ops; ++i) {
-        const uint32_t code = s.word[i] & 0xffu;
-        if (code == CH_DIV_L || code == CH_DIV_R || code == CH_POW_L || code == CH_POW_R || code == CH_SAVE_LOAD) return std::string();
-        const std::string e = step_expr(s, i, "in[", "][u]");
-        if (e.empty()) return std::string();
-        src += "            acc = " + e + ";\n";
-    }
-    src += "            out[u] = acc;\n        }\n    }\n};\n}  // namespace kc\nusing namespace kc;\n";
-    std::snprintf(buf, sizeof buf,
-                  "extern \"C\" __global__ __launch_bounds__(256) void %s(const ChainProgram P, const UpsampleArgs U)\n{\n"
-                  "    extern __shared__ __attribute__((aligned(16))) float lds[];\n"
-                  "    upsample_chain_tile<%u, %u, %u, %s, 0x%xu>(P, U, lds, UpProg{ P });\n}\n",
-                  kernel_name(s).c_str(), s.n_in, s.up_taps, KC_UPSAMPLE_ROWS, s.up_wide ? "true" : "false", s.nt_mask);
-    src += buf;
-    return src;
-}
-
-// The body of the flat kernel with s.quads float4 per lane (chain_quads_for): quad u of a lane is unit idx + u * SPEC_WG, so a
-// workgroup still covers one contiguous run of every plane.  Every load of the lane is issued before the first step; then
-// one quad after the other runs the program, under the loads of the quads behind it; the stores come last, together: a
-// store between two bodies makes the compiler wait for everything outstanding (s_waitcnt vmcnt(0), the store included)
-// before the second body, which costs 2-3 us per launch when nothing is resident (profiles/chain_inflight_times.txt,
-// "straight" against "late").  The unit count need not be a multiple of quads * SPEC_WG: a quad past the end reads the
-// last unit again (in bounds) and stores nothing.
-// The load of input plane k at vector unit `at` as an f4 value: a float4, or the quad of the plane's packed copy decoded
-// (chain_pack.h); with the nontemporal hint where the launch's cache policy says so.
-static std::string load_expr(const Signature &s, uint32_t k, const std::string &at)
-{
-    const uint32_t tier = KC_CHAIN_TIER(s.in_tiers, k);
-    const bool nt = (s.nt_mask & KC_CHAIN_NT_BIT(k)) != 0;
-    const std::string in = "P.in[b][" + std::to_string(k) + "]";
-    std::string ptr;
-    if (tier == (uint32_t)KC_PACK_FIX24)
-        ptr = "reinterpret_cast<const pack_u3a *>(reinterpret_cast<const char *>(" + in + ") + (unsigned long long)(" + at + ") * 12u)";
-    else if (tier == (uint32_t)KC_PACK_U8)
-        ptr = "&reinterpret_cast<const unsigned int *>(" + in + ")[" + at + "]";
-    else
-        ptr = "&reinterpret_cast<const raw4 *>(" + in + ")[" + at + "]";
-    const std::string v = nt ? "__builtin_nontemporal_load(" + ptr + ")" : "*(" + ptr + ")";
-    return tier == (uint32_t)KC_PACK_FIX24 ? "pack_decode_fix24(" + v + ")" : tier == (uint32_t)KC_PACK_U8 ? "pack_decode_u8(" + v + ")" : v;
-}
-
-static std::string generate_quads(const Signature &s, int SPEC_WG)
-{
-    std::string src;
-    char buf[320];
-    std::snprintf(buf, sizeof buf,
-                  "    const unsigned int n = P.rows * P.row_units;\n"
-                  "    const unsigned int idx = blockIdx.x * %uu + threadIdx.x;\n    if (idx >= n) return;\n",
-                  s.quads * (uint32_t)SPEC_WG);
-    src += buf;
-    for (uint32_t u = 0; u < s.quads; ++u) {
-        if (u == 0)
-            src += "    const unsigned int at0 = idx;\n";
-        else {
-            std::snprintf(buf, sizeof buf, "    const unsigned int at%u = idx + %uu < n ? idx + %uu : n - 1u;\n", u, u * SPEC_WG, u * SPEC_WG);
-            src += buf;
-        }
-        for (uint32_t k = 0; k < s.n_in; ++k) {
-            if (KC_CHAIN_TIER(s.in_tiers, k)) {
-                src += "    const f4 in" + std::to_string(k) + "_" + std::to_string(u) + " = " + load_expr(s, k, "at" + std::to_string(u)) + ";\n";
-                continue;
-            }
-            if (s.nt_mask & KC_CHAIN_NT_BIT(k))
-                std::snprintf(buf, sizeof buf, "    const f4 in%u_%u = __builtin_nontemporal_load(&reinterpret_cast<const raw4 *>(P.in[b][%u])[at%u]);\n", k, u, k, u);
-            else
-                std::snprintf(buf, sizeof buf, "    const f4 in%u_%u = reinterpret_cast<const raw4 *>(P.in[b][%u])[at%u];\n", k, u, k, u);
-            src += buf;
-        }
-    }
-    src += "    const StepTableView pp{ P.step[b] };\n";
-    for (uint32_t u = 0; u < s.quads; ++u) {
-        char suffix[8];
-        std::snprintf(suffix, sizeof suffix, "_%u", u);
-        std::snprintf(buf, sizeof buf, "    f4 out%u;\n    {\n", u);
-        src += buf;
-        if (s.start_src < 0)
-            src += "        f4 acc = f4{ P.start_c[b], P.start_c[b], P.start_c[b], P.start_c[b] };\n";
-        else {
-            std::snprintf(buf, sizeof buf, "        f4 acc = in%d%s;\n", s.start_src, suffix);
-            src += buf;
-        }
-        src += "        f4 saved0 = acc, saved1 = acc, saved2 = acc;\n";
-        for (uint32_t i = 0; i < s.n_ops; ++i) {
-            const std::string e = step_expr(s, i, "in", suffix);
-            if (e.empty()) return std::string();
-            src += "        acc = " + e + ";\n";
-        }
-        std::snprintf(buf, sizeof buf, "        out%u = acc;\n    }\n", u);
-        src += buf;
-    }
-    for (uint32_t u = 0; u < s.quads; ++u) {
-        std::snprintf(buf, sizeof buf, "    if (idx + %uu < n) ", u * SPEC_WG);
-        src += u ? buf : "    ";
-        std::snprintf(buf, sizeof buf,
-                      s.nt_mask & 0x100u ? "__builtin_nontemporal_store(out%u.raw(), &reinterpret_cast<raw4 *>(P.out[b])[idx + %uu]);\n"
-                                         : "reinterpret_cast<raw4 *>(P.out[b])[idx + %uu] = out%u.raw();\n",
-                      s.nt_mask & 0x100u ? u : u * SPEC_WG, s.nt_mask & 0x100u ? u * SPEC_WG : u);
-        src += buf;
-    }
-    src += "}\n";
-    return src;
-}
-
-std::string generate(const Signature &s)
-{
-    if (s.up_taps) return generate_up(s);
-    const int SPEC_WG = spec_wg();
-    bool pow = false;
-    for (uint32_t i = 0; i < s.n_ops; ++i) pow |= (s.word[i] & 0xffu) == CH_POW_L || (s.word[i] & 0xffu) == CH_POW_R;
-    std::string src;
-    src.reserve(16384);
-    src += "namespace kc {\n";
-    src += kJitChainProgramH;
-    src += kPackedF4;
-    if (s.in_tiers) {
-        const char *pack_text = kJitChainPackH;
-        if (!pack_text) return std::string();
-        src += pack_text;
-    }
-    if (pow) {
-        src += kJitPowPositiveInc;
-        src += "static __device__ __noinline__ float pow_general(float a, float b) { return (float)pow((double)a, (double)b); }\n"
-               "static __device__ __forceinline__ float kc_powf(float a, float b, const PowCtx &pw)\n"
-               "{\n"
-               "    if (a > 0.0f && a < __builtin_inff() && __builtin_fabsf(b) < __builtin_inff()) return pow_positive(a, b, pw);\n"
-               "    return pow_general(a, b);\n"
-               "}\n"
-               "static __device__ __forceinline__ f4 pow4(f4 a, f4 b, const PowCtx &t) { return f4{ kc_powf(a.lo.x, b.lo.x, t), kc_powf(a.lo.y, b.lo.y, t), kc_powf(a.hi.x, b.hi.x, t), kc_powf(a.hi.y, b.hi.y, t) }; }\n";
-    }
-    src += "}  // namespace kc\nusing namespace kc;\n";
-    char buf[256];
-    std::snprintf(buf, sizeof buf, "extern \"C\" __global__ __launch_bounds__(%d) void %s(const ChainProgram P)\n{\n", SPEC_WG,
-                  kernel_name(s).c_str());
-    src += buf;
-    if (pow) src += "    __shared__ double pow_lds[KC_POW_TABLE_DOUBLES];\n    const PowCtx pow_tab = pow_setup(pow_lds);\n";  // before any thread can leave
-    src += "    const unsigned int b = blockIdx.y;\n";
-    if (s.quads > 1) {
-        const std::string body = generate_quads(s, SPEC_WG);
-        return body.empty() ? body : src + body;
-    }
-    std::snprintf(buf, sizeof buf, "    const unsigned int idx = blockIdx.x * %du + threadIdx.x;\n", SPEC_WG);
-    src += buf;
-    src += "    if (idx >= P.rows * P.row_units) return;\n";
-    if (s.flat)
-        src += "    const unsigned int row = 0u, col = idx;\n";
-    else
-        src += "    const unsigned int row = idx / P.row_units, col = idx - row * P.row_units;\n";
-    for (uint32_t k = 0; k < s.n_in; ++k) {
-        if (KC_CHAIN_TIER(s.in_tiers, k)) {  // (flat signatures only: row is 0)
-            src += "    const f4 in" + std::to_string(k) + " = " + load_expr(s, k, "col") + ";\n";
-            continue;
-        }
-        if (s.nt_mask & KC_CHAIN_NT_BIT(k))
-            std::snprintf(buf, sizeof buf, "    const f4 in%u = __builtin_nontemporal_load(&reinterpret_cast<const raw4 *>(P.in[b][%u])[row * P.in_pitch[b][%u] + col]);\n", k, k, k);
-        else
-            std::snprintf(buf, sizeof buf, "    const f4 in%u = reinterpret_cast<const raw4 *>(P.in[b][%u])[row * P.in_pitch[b][%u] + col];\n", k, k, k);
-        src += buf;
-    }
-    src += "    const StepTableView pp{ P.step[b] };\n";
-    if (s.start_src < 0)
-        src += "    f4 acc = f4{ P.start_c[b], P.start_c[b], P.start_c[b], P.start_c[b] };\n";
-    else {
-        std::snprintf(buf, sizeof buf, "    f4 acc = in%d;\n", s.start_src);
-        src += buf;
-    }
-    src += "    f4 saved0 = acc, saved1 = acc, saved2 = acc;\n";  // (only programs that join chains use them)
-    for (uint32_t i = 0; i < s.n_ops; ++i) {
-        const std::string e = step_expr(s, i, "in", "");
-        if (e.empty()) return std::string();
-        src += "    acc = " + e + ";\n";
-    }
-    if (s.nt_mask & 0x100u)
-        src += "    __builtin_nontemporal_store(acc.raw(), &reinterpret_cast<raw4 *>(P.out[b])[row * P.out_pitch[b] + col]);\n}\n";
-    else
-        src += "    reinterpret_cast<raw4 *>(P.out[b])[row * P.out_pitch[b] + col] = acc.raw();\n}\n";
-    return src;
-}
-
-// ---- code objects that outlive the process ----
-// hiprtc takes about two seconds for the first program of a process and the interpreter runs meanwhile; a batch job that
-// evaluates one graph once per process (the reference's own usage, tests/integration_tests.rs:47-49) would never reach the
-// kernel its program deserves.  So every code object the compiler produces is also written to a directory, and a program's
-// FIRST sighting in a later process loads it from there (a file read and hipModuleLoadData: ~0.3 ms).
-//   where   KC_KERNEL_CACHE_DIR (kc_set_kernel_cache_dir), default $XDG_CACHE_HOME/kanter_core_amd or ~/.cache/kanter_core_amd;
-//           "off" disables.  Read-only second place: kernel_cache/ next to the library, which the build fills with the
-//           BASELINE programs (kanter_core_amd/build.py, baseline_programs.jsonl), so that a fresh machine has them too.
-//   file    <kernel name>-<hash of the signature>.kcco = header, the signature's key, the code object.
-//   trust   a file is used only if its key equals the signature's byte for byte, the hash of what the generator emits TODAY for
-//           that signature (source text, compiler options, hiprtc version) equals the one stored, and the code's checksum
-//           holds.  Anything else -- a truncated or edited file, a file from another version of the library or of ROCm -- is
-//           ignored and replaced by a fresh compile; never a wrong kernel.
-//   writes  to a temporary name in the same directory, then rename(): readers see whole files only.
-static const char *const kCompileOpts[] = { "--gpu-architecture=gfx950", "-O3", "-ffp-contract=off", "-fno-fast-math",
-                                            "-fhip-fp32-correctly-rounded-divide-sqrt" };
+// the parity flags of the offline build (kanter_core_amd/build.py)
+const char *const kCompileOpts[] = { "--gpu-architecture=gfx950", "-O3", "-ffp-contract=off", "-fno-fast-math",
+                                     "-fhip-fp32-correctly-rounded-divide-sqrt" };
 constexpr int kNumCompileOpts = (int)(sizeof kCompileOpts / sizeof *kCompileOpts);
 
-uint64_t fnv64(const void *data, size_t n, uint64_t h = 1469598103934665603ull)
+}  // namespace
+
+const CompilerId &compiler_id()
 {
-    const unsigned char *p = (const unsigned char *)data;
-    for (size_t i = 0; i < n; ++i) h = (h ^ p[i]) * 1099511628211ull;
-    return h;
+    static const CompilerId id = [] {
+        CompilerId c{ kCompileOpts, kNumCompileOpts, { 0, 0 } };
+        if (rtc().version) (void)rtc().version(&c.version[0], &c.version[1]);
+        return c;
+    }();
+    return id;
 }
 
-struct CacheHeader {
-    char magic[8];  // "KCCO0001"
-    uint64_t key_len, source_hash, code_len, code_hash;
-};
-
-struct DiskCache {
-    std::mutex mu;
-    bool resolved = false;
-    std::string write_dir;              // empty: nothing is written
-    std::vector<std::string> read_dirs; // write_dir first, then the packaged directory
-    uint64_t hits = 0, rejected = 0, written = 0;
-};
-
-DiskCache &disk()
-{
-    static DiskCache d;
-    return d;
-}
-
-uint64_t disk_hits()
-{
-    std::lock_guard<std::mutex> lk(disk().mu);
-    return disk().hits;
-}
-
-bool make_dirs(const std::string &path)
-{
-    for (size_t i = 1; i <= path.size(); ++i)
-        if (i == path.size() || path[i] == '/') {
-            const std::string part = path.substr(0, i);
-            if (mkdir(part.c_str(), 0755) != 0 && errno != EEXIST) return false;
-        }
-    return true;
-}
-
-void resolve_dirs_locked(DiskCache &d, const char *forced)
-{
-    d.resolved = true;
-    d.write_dir.clear();
-    d.read_dirs.clear();
-    std::string dir;
-    if (forced) dir = forced;
-    else if (const char *e = std::getenv("KC_KERNEL_CACHE_DIR")) dir = e;
-    else if (const char *x = std::getenv("XDG_CACHE_HOME")) dir = *x ? std::string(x) + "/kanter_core_amd" : "";
-    else if (const char *h = std::getenv("HOME")) dir = *h ? std::string(h) + "/.cache/kanter_core_amd" : "";
-    if (dir == "off" || dir == "0") return;  // no cache at all
-    if (!dir.empty() && make_dirs(dir) && access(dir.c_str(), W_OK) == 0) {
-        d.write_dir = dir;
-        d.read_dirs.push_back(dir);
-    } else if (!dir.empty()) {
-        d.read_dirs.push_back(dir);  // readable perhaps, even if it cannot be written
-    }
-    Dl_info info;
-    if (dladdr((const void *)&disk, &info) && info.dli_fname) {
-        std::string lib = info.dli_fname;
-        const size_t slash = lib.rfind('/');
-        d.read_dirs.push_back((slash == std::string::npos ? std::string(".") : lib.substr(0, slash)) + "/kernel_cache");
-    }
-}
-
-std::string cache_file_name(const Signature &sig)
-{
-    char buf[64];
-    const std::string key = sig.key();
-    std::snprintf(buf, sizeof buf, "-%016llx.kcco", (unsigned long long)fnv64(key.data(), key.size()));
-    return kernel_name(sig) + buf;
-}
-
-// What today's generator and compiler would make of this signature, as a hash.
-uint64_t source_hash_of(const std::string &src)
-{
-    uint64_t h = fnv64(src.data(), src.size());
-    for (const char *o : kCompileOpts) h = fnv64(o, std::strlen(o) + 1, h);
-    int ver[2] = { 0, 0 };
-    Rtc &r = rtc();
-    if (r.version) (void)r.version(&ver[0], &ver[1]);
-    return fnv64(ver, sizeof ver, h);
-}
-
-// The code object of `sig` from the directories, if a trustworthy one is there.
-bool disk_load(const Signature &sig, const std::string &src, std::vector<char> &code)
-{
-    DiskCache &d = disk();
-    std::vector<std::string> dirs;
-    {
-        std::lock_guard<std::mutex> lk(d.mu);
-        if (!d.resolved) resolve_dirs_locked(d, nullptr);
-        dirs = d.read_dirs;
-    }
-    if (dirs.empty()) return false;
-    const std::string key = sig.key(), name = cache_file_name(sig);
-    const uint64_t want = source_hash_of(src);
-    for (auto &dir : dirs) {
-        FILE *f = std::fopen((dir + "/" + name).c_str(), "rb");
-        if (!f) continue;
-        CacheHeader h{};
-        bool ok = std::fread(&h, sizeof h, 1, f) == 1 && std::memcmp(h.magic, "KCCO0001", 8) == 0 && h.key_len == key.size() &&
-                  h.source_hash == want && h.code_len > 0 && h.code_len < (64u << 20);
-        std::string fkey;
-        if (ok) {
-            fkey.resize(h.key_len);
-            code.resize(h.code_len);
-            ok = std::fread(&fkey[0], 1, fkey.size(), f) == fkey.size() && fkey == key &&
-                 std::fread(code.data(), 1, code.size(), f) == code.size() && std::fgetc(f) == EOF &&
-                 fnv64(code.data(), code.size()) == h.code_hash;
-        }
-        std::fclose(f);
-        std::lock_guard<std::mutex> lk(d.mu);
-        if (ok) {
-            d.hits++;
-            return true;
-        }
-        d.rejected++;
-    }
-    code.clear();
-    return false;
-}
-
-bool disk_store_in(const std::string &dir, const Signature &sig, const std::string &src, const std::vector<char> &code)
-{
-    const std::string key = sig.key(), final_name = dir + "/" + cache_file_name(sig);
-    char tmp_suffix[48];
-    std::snprintf(tmp_suffix, sizeof tmp_suffix, ".tmp.%d.%llx", (int)getpid(), (unsigned long long)fnv64(&code, sizeof(void *)));
-    const std::string tmp = final_name + tmp_suffix;
-    FILE *f = std::fopen(tmp.c_str(), "wb");
-    if (!f) return false;
-    CacheHeader h{};
-    std::memcpy(h.magic, "KCCO0001", 8);
-    h.key_len = key.size();
-    h.source_hash = source_hash_of(src);
-    h.code_len = code.size();
-    h.code_hash = fnv64(code.data(), code.size());
-    bool ok = std::fwrite(&h, sizeof h, 1, f) == 1 && std::fwrite(key.data(), 1, key.size(), f) == key.size() &&
-              std::fwrite(code.data(), 1, code.size(), f) == code.size();
-    ok = std::fclose(f) == 0 && ok;
-    if (ok) ok = std::rename(tmp.c_str(), final_name.c_str()) == 0;
-    if (!ok) (void)std::remove(tmp.c_str());
-    return ok;
-}
-
-void disk_store(const Signature &sig, const std::string &src, const std::vector<char> &code)
-{
-    DiskCache &d = disk();
-    std::string dir;
-    {
-        std::lock_guard<std::mutex> lk(d.mu);
-        if (!d.resolved) resolve_dirs_locked(d, nullptr);
-        dir = d.write_dir;
-    }
-    if (dir.empty()) return;
-    if (disk_store_in(dir, sig, src, code)) {
-        std::lock_guard<std::mutex> lk(d.mu);
-        if (d.written++ == 0)
-            if (FILE *f = std::fopen((dir + "/.populated").c_str(), "w")) std::fclose(f);
-    }
-}
-
-// Source -> code object with hiprtc (works without a device).
-bool rtc_compile(const std::string &src, std::vector<char> &code, std::string *log)
+// Source -> code object with hiprtc (works without a device).  KC_ERR_UNSUPPORTED: no libhiprtc.
+int rtc_compile(const std::string &src, std::vector<char> &code, std::string *log)
 {
     Rtc &r = rtc();
     if (!r.ok) {
         *log = "libhiprtc not available";
-        return false;
+        return KC_ERR_UNSUPPORTED;
     }
     hiprtcProgram prog = nullptr;
     if (r.create(&prog, src.c_str(), "kc_chain_spec.hip", 0, nullptr, nullptr) != 0) {
         *log = "hiprtcCreateProgram failed";
-        return false;
+        return KC_ERR_GENERIC;
     }
-    // the parity flags of the offline build (kanter_core_amd/build.py)
     const int rc = r.compile(prog, kNumCompileOpts, const_cast<const char **>(kCompileOpts));
     size_t n = 0;
     r.log_size(prog, &n);
     log->assign(n, '\0');
     if (n) r.log(prog, &(*log)[0]);
-    if (rc != 0) {
-        r.destroy(&prog);
-        return false;
+    if (rc == 0) {
+        n = 0;
+        r.code_size(prog, &n);
+        code.resize(n);
+        r.code(prog, code.data());
     }
-    n = 0;
-    r.code_size(prog, &n);
-    code.resize(n);
-    r.code(prog, code.data());
     r.destroy(&prog);
-    return true;
+    return rc == 0 ? KC_OK : KC_ERR_GENERIC;
 }
 
-bool load_code(const Signature &sig, const std::vector<char> &code, hipModule_t *module, hipFunction_t *fn, std::string *log)
-{
-    if (hipModuleLoadData(module, code.data()) != hipSuccess) {
-        (void)hipGetLastError();
-        *log = "hipModuleLoadData failed";
-        return false;
-    }
-    if (hipModuleGetFunction(fn, *module, kernel_name(sig).c_str()) != hipSuccess) {
-        (void)hipGetLastError();
-        (void)hipModuleUnload(*module);
-        *module = nullptr;
-        *log = "hipModuleGetFunction failed";
-        return false;
-    }
-    return true;
-}
+namespace {
 
-// ---- cache + worker ----
+// ---- registry + worker ----
 struct Entry {
     enum State { COUNTING, QUEUED, READY, FAILED } state = COUNTING;
     uint32_t sightings = 0;
-    Signature sig;
     hipModule_t module = nullptr;
     hipFunction_t fn = nullptr;
 };
@@ -747,11 +117,8 @@ struct Entry {
 struct Spec {
     std::mutex mu;
     std::condition_variable cv, idle_cv;
-    std::map<std::string, Entry> cache;
-    // launch-path shortcut: hash of the signature -> its entry, so that a launch neither builds the key string nor walks
-    // the string-keyed map (entries of `cache` are never moved); a hash collision falls back to the map
-    std::unordered_map<uint64_t, std::pair<std::string, Entry *>> by_hash;
-    std::deque<std::string> queue;
+    std::unordered_map<Signature, Entry, SignatureHash> cache;
+    std::deque<Signature> queue;
     std::thread worker;
     bool worker_running = false, stopping = false;
     int busy = 0;
@@ -768,12 +135,9 @@ struct Spec {
         {
             std::lock_guard<std::mutex> lk(mu);
             stopping = true;
-            for (auto &key : queue) {
-                auto it = cache.find(key);
-                if (it != cache.end() && it->second.state == Entry::QUEUED) {
-                    it->second.state = Entry::COUNTING;
-                    it->second.sightings = 0;
-                }
+            for (auto &sig : queue) {
+                auto it = cache.find(sig);
+                if (it != cache.end() && it->second.state == Entry::QUEUED) it->second = Entry{};
             }
             queue.clear();
         }
@@ -794,60 +158,79 @@ Spec &spec()
 
 void specialize_stop_at_exit() { spec().stop(); }
 
-// The kernel of one signature on the bound device: from the directories if a trustworthy code object is there, else
-// compiled (and written there).  `disk_only`: never compile.  Called without the lock held.
-bool compile_entry(const Signature &sig, hipModule_t *module, hipFunction_t *fn, std::string *log, bool disk_only = false)
+// How make_ready came by a kernel.
+struct Ready {
+    enum How { FAILED, FROM_DISK, COMPILED } how = FAILED;
+    hipModule_t module = nullptr;
+    hipFunction_t fn = nullptr;
+    std::string log;
+};
+
+bool load_code(const Signature &sig, const std::vector<char> &code, Ready &r)
 {
-    const std::string src = generate(sig);
-    if (src.empty()) {
-        *log = "unknown step code";
+    if (hipModuleLoadData(&r.module, code.data()) != hipSuccess) {
+        (void)hipGetLastError();
+        r.log = "hipModuleLoadData failed";
         return false;
     }
-    std::vector<char> code;
-    if (disk_load(sig, src, code)) {
-        if (load_code(sig, code, module, fn, log)) return true;
-        std::lock_guard<std::mutex> lk(disk().mu);  // the file passed every check and the driver still refuses it: compile
-        disk().hits--;
-        disk().rejected++;
-    }
-    if (disk_only) {
-        *log = "not in the kernel cache";
+    if (hipModuleGetFunction(&r.fn, r.module, kernel_name(sig).c_str()) != hipSuccess) {
+        (void)hipGetLastError();
+        (void)hipModuleUnload(r.module);
+        r.module = nullptr;
+        r.log = "hipModuleGetFunction failed";
         return false;
-    }
-    if (!rtc_compile(src, code, log)) return false;
-    if (!load_code(sig, code, module, fn, log)) return false;
-    disk_store(sig, src, code);
-    if (const char *m = std::getenv("KC_KERNEL_CACHE_MANIFEST")) {  // which programs a run compiled (tools/dump_baseline_programs.py)
-        if (FILE *f = std::fopen(m, "a")) {
-            std::fprintf(f, "{\"name\": \"%s\", \"n_in\": %u, \"start_src\": %d, \"flat\": %d, \"nt_mask\": %u, \"up_taps\": %u, \"up_wide\": %d, \"words\": [",
-                         kernel_name(sig).c_str(), sig.n_in, sig.start_src, sig.flat ? 1 : 0, sig.nt_mask, sig.up_taps, sig.up_wide ? 1 : 0);
-            for (uint32_t k = 0; k < sig.n_ops; ++k) std::fprintf(f, "%s%u", k ? ", " : "", sig.word[k]);
-            if (sig.in_tiers) std::fprintf(f, "], \"in_tiers\": %u}\n", sig.in_tiers);  // (optional field: packed inputs, chain_pack.h)
-            else std::fprintf(f, "]}\n");
-            std::fclose(f);
-        }
     }
     return true;
 }
 
-void finish(Spec &S, const std::string &key, bool ok, hipModule_t m, hipFunction_t f, const std::string &log, bool from_disk = false)
+// The kernel of one signature on the bound device: from the directories if a trustworthy code object is there, else
+// compiled (and written there).  `disk_only`: never compile.
+Ready make_ready(const Signature &sig, bool disk_only)
 {
-    auto it = S.cache.find(key);
+    Ready r;
+    const std::string src = generate(sig);
+    if (src.empty()) {
+        r.log = "unknown step code";
+        return r;
+    }
+    std::vector<char> code;
+    if (disk_load(sig, src, compiler_id(), code)) {
+        if (load_code(sig, code, r)) {
+            r.how = Ready::FROM_DISK;
+            return r;
+        }
+        disk_load_refused();  // compile
+    }
+    if (disk_only) {
+        r.log = "not in the kernel cache";
+        return r;
+    }
+    if (rtc_compile(src, code, &r.log) != KC_OK || !load_code(sig, code, r)) return r;
+    disk_store(sig, src, compiler_id(), code);
+    r.how = Ready::COMPILED;
+    return r;
+}
+
+// Books what make_ready brought (S.mu held); the kernel, if there is one.
+hipFunction_t finish(Spec &S, const Signature &sig, const Ready &r)
+{
+    auto it = S.cache.find(sig);
     if (it == S.cache.end()) {
-        if (ok) (void)hipModuleUnload(m);
-        return;
+        if (r.module) (void)hipModuleUnload(r.module);
+        return nullptr;
     }
-    if (ok) {
-        it->second.module = m;
-        it->second.fn = f;
-        it->second.state = Entry::READY;
-        if (from_disk) S.loaded_from_disk++;
-        else S.compiled++;
-    } else {
-        it->second.state = Entry::FAILED;
+    Entry &e = it->second;
+    if (r.how == Ready::FAILED) {
+        e.state = Entry::FAILED;
         S.failed++;
-        S.last_log = log;
+        S.last_log = r.log;
+        return nullptr;
     }
+    e.module = r.module;
+    e.fn = r.fn;
+    e.state = Entry::READY;
+    (r.how == Ready::FROM_DISK ? S.loaded_from_disk : S.compiled)++;
+    return e.fn;
 }
 
 void worker_main()
@@ -858,113 +241,52 @@ void worker_main()
     for (;;) {
         S.cv.wait(lk, [&] { return S.stopping || !S.queue.empty(); });
         if (S.stopping) return;
-        const std::string key = S.queue.front();
+        const Signature sig = S.queue.front();
         S.queue.pop_front();
-        auto it = S.cache.find(key);
-        if (it == S.cache.end()) continue;
-        const Signature sig = it->second.sig;
         S.busy++;
         lk.unlock();
-        hipModule_t m = nullptr;
-        hipFunction_t f = nullptr;
-        std::string log;
-        const uint64_t hits0 = disk_hits();
-        const bool ok = compile_entry(sig, &m, &f, &log);
-        const bool from_disk = ok && disk_hits() != hits0;
+        const Ready r = make_ready(sig, /*disk_only=*/false);
         lk.lock();
         S.busy--;
-        finish(S, key, ok, m, f, log, from_disk);
+        finish(S, sig, r);
         S.idle_cv.notify_all();  // specialize_wait() waits for "nothing pending", mode-2 launches for one entry
     }
 }
 
-}  // namespace
-
 // The specialised kernel for this program if there is one; otherwise nullptr (and, depending on the mode,
-// a compile is started).  Called with the context lock held.
-static uint64_t signature_hash(const Signature &s)
-{
-    uint64_t h = 1469598103934665603ull;
-    auto mix = [&](uint64_t v) { h = (h ^ v) * 1099511628211ull; };
-    mix(s.n_in);
-    mix(s.n_ops);
-    mix((uint64_t)(int64_t)s.start_src);
-    mix(s.flat ? 1 : 0);
-    mix(s.up_taps);
-    mix(s.up_wide ? 1 : 0);
-    mix(s.nt_mask);
-    mix(s.quads);
-    mix(s.in_tiers);
-    for (uint32_t i = 0; i < s.n_ops; ++i) mix(s.word[i]);
-    return h;
-}
-
-static bool same_signature(const Signature &a, const Signature &b)
-{
-    return a.n_in == b.n_in && a.n_ops == b.n_ops && a.start_src == b.start_src && a.flat == b.flat && a.up_taps == b.up_taps &&
-           a.up_wide == b.up_wide && a.nt_mask == b.nt_mask && a.quads == b.quads && a.in_tiers == b.in_tiers &&
-           std::memcmp(a.word, b.word, sizeof(uint32_t) * a.n_ops) == 0;
-}
-
-static hipFunction_t spec_lookup(const Signature &sig)
+// a compile is started).  Called with the context lock held.  A launch that finds its kernel READY takes the
+// registry lock once and allocates nothing.
+hipFunction_t spec_lookup(const Signature &sig)
 {
     Spec &S = spec();
     if (S.mode.load(std::memory_order_relaxed) == 0) return nullptr;
-    const uint64_t h = signature_hash(sig);
-    {
-        std::lock_guard<std::mutex> fast(S.mu);
-        auto it = S.by_hash.find(h);
-        if (it != S.by_hash.end() && it->second.second->state == Entry::READY && same_signature(it->second.second->sig, sig))
-            return it->second.second->fn;
-    }
-    const std::string key = sig.key();
     std::unique_lock<std::mutex> lk(S.mu);
-    if (S.mode == 2) {
-        // "compile at once": a compile of this program that is already queued in the background is waited for
-        auto it = S.cache.find(key);
-        if (it != S.cache.end() && it->second.state == Entry::QUEUED)
-            S.idle_cv.wait(lk, [&] { return S.cache[key].state != Entry::QUEUED || !S.worker_running; });
-    }
-    Entry &e = S.cache[key];
-    if (e.state == Entry::READY) {
-        e.sig = sig;
-        S.by_hash[h] = { key, &e };
-        return e.fn;
-    }
+    auto it = S.cache.find(sig);
+    if (it != S.cache.end() && it->second.state == Entry::READY) return it->second.fn;
+    // "compile at once": a compile of this program that is already queued in the background is waited for
+    if (S.mode == 2 && it != S.cache.end() && it->second.state == Entry::QUEUED)
+        S.idle_cv.wait(lk, [&] {
+            auto w = S.cache.find(sig);
+            return w == S.cache.end() || w->second.state != Entry::QUEUED || !S.worker_running;
+        });
+    Entry &e = S.cache[sig];
+    if (e.state == Entry::READY) return e.fn;
     if (e.state != Entry::COUNTING) return nullptr;
     e.sightings++;
     if (e.sightings == 1 && S.mode == 1) {
         // first sighting in this process: a code object from an earlier process (or from the build) is loaded on the spot
-        hipModule_t m = nullptr;
-        hipFunction_t f = nullptr;
-        std::string log;
-        e.sig = sig;
-        if (compile_entry(sig, &m, &f, &log, /*disk_only=*/true)) {
-            e.module = m;
-            e.fn = f;
-            e.state = Entry::READY;
-            S.loaded_from_disk++;
-            S.by_hash[h] = { key, &e };
-            return f;
-        }
+        const Ready r = make_ready(sig, /*disk_only=*/true);
+        if (r.how != Ready::FAILED) return finish(S, sig, r);
     }
     if (S.mode == 1 && e.sightings < S.after) return nullptr;
-    e.sig = sig;
-    if (S.mode == 2) {
-        e.state = Entry::QUEUED;
-        lk.unlock();
-        hipModule_t m = nullptr;
-        hipFunction_t f = nullptr;
-        std::string log;
-        const uint64_t hits0 = disk_hits();
-        const bool ok = compile_entry(sig, &m, &f, &log);
-        const bool from_disk = ok && disk_hits() != hits0;
-        lk.lock();
-        finish(S, key, ok, m, f, log, from_disk);
-        return ok ? f : nullptr;
-    }
     e.state = Entry::QUEUED;
-    S.queue.push_back(key);
+    if (S.mode == 2) {
+        lk.unlock();
+        const Ready r = make_ready(sig, /*disk_only=*/false);
+        lk.lock();
+        return finish(S, sig, r);
+    }
+    S.queue.push_back(sig);
     if (!S.worker_running) {
         S.device = ctx().device;
         S.stopping = false;
@@ -975,6 +297,14 @@ static hipFunction_t spec_lookup(const Signature &sig)
     S.cv.notify_one();
     return nullptr;
 }
+
+void count_launch()
+{
+    std::lock_guard<std::mutex> lk(spec().mu);
+    spec().launches++;
+}
+
+}  // namespace
 
 // Launches the specialised kernel for P if one is ready.  *launched tells the caller whether it still has to
 // run the interpreter; *nt_mask (optional) receives the cache-policy bits the launched kernel was compiled with.
@@ -990,20 +320,17 @@ hipError_t launch_chain_specialized(const ChainProgram &P, int batch, hipStream_
     size_t size = sizeof(ChainProgram);
     const int SPEC_WG = spec_wg();
     void *extra[] = { HIP_LAUNCH_PARAM_BUFFER_POINTER, (void *)&P, HIP_LAUNCH_PARAM_BUFFER_SIZE, &size, HIP_LAUNCH_PARAM_END };
-    const uint64_t per_block = (uint64_t)SPEC_WG * sig.quads;  // the generator's own count (generate_quads)
+    const uint64_t per_block = (uint64_t)SPEC_WG * sig.quads;  // the generator's own count (chain_codegen.cpp, emit_quads)
     const unsigned gx = (unsigned)((total + per_block - 1) / per_block);
     hipError_t e = hipModuleLaunchKernel(fn, gx, (unsigned)batch, 1, SPEC_WG, 1, 1, 0, s, nullptr, extra);
     if (e == hipSuccess) {
         *launched = true;
         if (nt_mask) *nt_mask = sig.nt_mask;
         if (quads) *quads = sig.quads;
-        std::lock_guard<std::mutex> lk(spec().mu);
-        spec().launches++;
+        count_launch();
     }
     return e;
 }
-
-bool chain_pack_program_ok(const ChainProgram &P) { return pack_program_ok(P); }
 
 // The same for a program that runs inside the integer-ratio up-sampling kernel (resize.cpp, chain_resize_launch).
 hipError_t launch_upsample_chain_specialized(const ChainProgram &P, int batch, const UpsampleArgs &U, hipStream_t s, bool *launched)
@@ -1028,8 +355,7 @@ hipError_t launch_upsample_chain_specialized(const ChainProgram &P, int batch, c
     hipError_t e = hipModuleLaunchKernel(fn, grid.x, grid.y, grid.z, 256, 1, 1, (unsigned)upsample_lds_bytes(U), s, nullptr, extra);
     if (e == hipSuccess) {
         *launched = true;
-        std::lock_guard<std::mutex> lk(spec().mu);
-        spec().launches++;
+        count_launch();
     }
     return e;
 }
@@ -1047,11 +373,7 @@ int specialize_set_mode(int mode, int after)
     return KC_OK;
 }
 
-int specialize_get_mode()
-{
-    Spec &S = spec();
-    return S.mode.load();
-}
+int specialize_get_mode() { return spec().mode.load(); }
 
 // Blocks until every queued compile has landed.
 void specialize_wait()
@@ -1071,6 +393,14 @@ void specialize_stats(uint64_t *compiled, uint64_t *failed, uint64_t *launches, 
     if (pending) *pending = S.queue.size() + (uint64_t)S.busy;
 }
 
+void kernel_cache_stats(uint64_t *hits, uint64_t *rejected, uint64_t *written, uint64_t *kernels_loaded)
+{
+    disk_counters(hits, rejected, written);
+    Spec &S = spec();
+    std::lock_guard<std::mutex> lk(S.mu);
+    if (kernels_loaded) *kernels_loaded = S.loaded_from_disk;
+}
+
 std::string specialize_last_log()
 {
     Spec &S = spec();
@@ -1086,120 +416,15 @@ void specialize_shutdown()
     std::lock_guard<std::mutex> lk(S.mu);
     for (auto &kv : S.cache)
         if (kv.second.module) (void)hipModuleUnload(kv.second.module);
-    S.by_hash.clear();
     S.cache.clear();
 }
 
-// chain_quads: 0 = the rule of chain_quads_for, 1 / 2 / 4 = that many float4 per lane wherever the rule allows more than one.
-int specialize_set_chain_quads(int quads)
-{
-    if (quads != 0 && quads != 1 && quads != 2 && quads != 4) return KC_ERR_INVALID_ARG;
-    g_chain_quads.store(quads);
-    return KC_OK;
-}
-
-int specialize_get_chain_quads() { return g_chain_quads.load(); }
-
-// The source the specialiser would compile for P (tests, debugging).
-std::string specialize_source(const ChainProgram &P, const UpsampleArgs *U) { return generate(signature_of(P, U)); }
-
 // Compiles without loading: lets the CPU-only test suite check that every generated program builds for
 // gfx950 with the parity flags (hiprtc cross-compiles without a device).
-int specialize_compile_only(const ChainProgram &P, std::string *log, const UpsampleArgs *U)
+int specialize_compile_only(const std::string &src, std::string *log)
 {
-    if (!rtc().ok) {
-        *log = "libhiprtc not available";
-        return KC_ERR_UNSUPPORTED;
-    }
-    const std::string src = generate(signature_of(P, U));
-    if (src.empty()) return KC_ERR_GENERIC;
     std::vector<char> code;
-    return rtc_compile(src, code, log) ? KC_OK : KC_ERR_GENERIC;
-}
-
-// ---- the kernel cache from outside ----
-// nullptr / "": back to the environment's choice; "off": no cache.
-int kernel_cache_set_dir(const char *dir)
-{
-    DiskCache &d = disk();
-    std::lock_guard<std::mutex> lk(d.mu);
-    resolve_dirs_locked(d, dir && *dir ? dir : nullptr);
-    return KC_OK;
-}
-
-void kernel_cache_stats(uint64_t *hits, uint64_t *rejected, uint64_t *written, uint64_t *kernels_loaded)
-{
-    {
-        DiskCache &d = disk();
-        std::lock_guard<std::mutex> lk(d.mu);
-        if (hits) *hits = d.hits;
-        if (rejected) *rejected = d.rejected;
-        if (written) *written = d.written;
-    }
-    Spec &S = spec();
-    std::lock_guard<std::mutex> lk(S.mu);
-    if (kernels_loaded) *kernels_loaded = S.loaded_from_disk;
-}
-
-// Is there anything a first evaluation could find?  (graph.cpp: whether a graph's first walk builds the wide / joined programs.)
-bool kernel_cache_populated()
-{
-    DiskCache &d = disk();
-    std::vector<std::string> dirs;
-    {
-        std::lock_guard<std::mutex> lk(d.mu);
-        if (!d.resolved) resolve_dirs_locked(d, nullptr);
-        dirs = d.read_dirs;
-        if (dirs.empty()) return false;  // "off"
-        if (d.hits) return true;
-    }
-    static std::map<std::string, bool> seen;  // per directory, asked once (callers hold the context lock)
-    for (auto &dir : dirs) {
-        auto it = seen.find(dir);
-        if (it == seen.end()) {
-            bool any = false;
-            std::string probe = dir + "/.populated";
-            any = access(probe.c_str(), R_OK) == 0;
-            it = seen.emplace(dir, any).first;
-        }
-        if (it->second) return true;
-    }
-    return false;
-}
-
-// Compiles the program of a signature given by value (no device needed) and writes its code object into `dir`: how the build
-// pre-populates kernel_cache/ next to the library.
-int kernel_cache_precompile(const uint32_t *words, uint32_t n_ops, uint32_t n_in, int32_t start_src, bool flat, uint32_t nt_mask, uint32_t in_tiers,
-                            uint32_t up_taps, bool up_wide, const char *dir, std::string *log)
-{
-    if (in_tiers && (!flat || up_taps || (n_in < 16 && in_tiers >> (2 * n_in)))) return KC_ERR_INVALID_ARG;
-    for (uint32_t k = 0; k < n_in; ++k)
-        if (KC_CHAIN_TIER(in_tiers, k) == 3u) return KC_ERR_INVALID_ARG;
-    if (!words || n_ops < 1 || n_ops > (uint32_t)KC_CHAIN_MAX_OPS || n_in > (uint32_t)KC_CHAIN_MAX_IN || !dir || !*dir) return KC_ERR_INVALID_ARG;
-    Signature sig;
-    sig.n_in = n_in;
-    sig.n_ops = n_ops;
-    sig.start_src = start_src;
-    sig.flat = flat;
-    sig.nt_mask = nt_mask;
-    sig.up_taps = up_taps;
-    sig.up_wide = up_wide;
-    sig.in_tiers = in_tiers;
-    for (uint32_t i = 0; i < n_ops; ++i) sig.word[i] = words[i];
-    sig.quads = chain_quads_for(sig, 0);
-    const std::string src = generate(sig);
-    if (src.empty()) {
-        *log = "unknown step code";
-        return KC_ERR_INVALID_ARG;
-    }
-    std::vector<char> code;
-    if (!rtc_compile(src, code, log)) return rtc().ok ? KC_ERR_GENERIC : KC_ERR_UNSUPPORTED;
-    if (!make_dirs(dir) || !disk_store_in(dir, sig, src, code)) {
-        *log = std::string("cannot write into ") + dir;
-        return KC_ERR_IO;
-    }
-    if (FILE *f = std::fopen((std::string(dir) + "/.populated").c_str(), "w")) std::fclose(f);
-    return KC_OK;
+    return src.empty() ? KC_ERR_GENERIC : rtc_compile(src, code, log);
 }
 
 }  // namespace kc

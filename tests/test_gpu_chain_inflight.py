@@ -1,4 +1,4 @@
-"""The compiled chain kernels with more than one float4 per lane (csrc/specialize.cpp, chain_quads_for / generate_quads) on the
+"""The compiled chain kernels with more than one float4 per lane (csrc/chain_codegen.cpp, chain_quads_for / emit_quads) on the
 device: bit for bit against the CPU oracle and against the same evaluation with chain_quads = 1 (one float4 per lane, the
 form every other launch keeps), NaN == NaN.
 
@@ -14,7 +14,7 @@ from util import SEED_A, assert_planes, splitmix_plane, with_edge_cases
 
 pytestmark = pytest.mark.gpu
 
-QUADS = 2  # kQuadsWarm (csrc/specialize.cpp): what the rule picks
+QUADS = 2  # kQuadsWarm (csrc/chain_codegen.cpp): what the rule picks
 SHAPES = [(4, 1), (1020, 1), (1024, 1), (1028, 1), (2044, 1), (2048, 1), (2052, 1), (4092, 1), (4100, 1), (64, 33), (1028, 7)]
 TAIL = [np.nan, np.inf, -np.inf, -0.0, 1e-40, 3e38, 1.25]  # written from the last sample backwards: the guarded end
 CONSTS = [0.375, -1.25, 2.0, 1.5, -0.0, 0.75, -3.0, 0.5, 0.625, 1.75, -0.875, 0.25, 1.0, -2.0, 0.1, 1.1]

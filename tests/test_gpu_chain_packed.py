@@ -1,4 +1,4 @@
-"""The packed-f32 form of the chain kernels compiled at run time (csrc/specialize.cpp: every {+, -, *} step is
+"""The packed-f32 form of the chain kernels compiled at run time (csrc/chain_codegen.cpp: every {+, -, *} step is
 v_pk_add_f32 / v_pk_mul_f32, a subtraction a packed add with the negate modifier, and "c - (acc op x)" reads c for both
 halves from one scalar register) against the step interpreter and the CPU oracle, bit for bit with NaN == NaN.
 

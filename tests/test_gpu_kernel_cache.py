@@ -1,4 +1,4 @@
-"""Compiled kernels outlive the process (csrc/specialize.cpp, "code objects that outlive the process"): a code object hiprtc
+"""Compiled kernels outlive the process (csrc/kernel_cache.cpp): a code object hiprtc
 produced is written to the cache directory, the first sighting of the same program in a later process (here: after
 kc.specialize_reset()) loads it instead of compiling, and a file that is corrupted, truncated, stale (made by another version of
 the generator / compiler) or that belongs to another program is refused and replaced by a fresh compile -- never run."""

@@ -217,3 +217,90 @@ def test_background_compile_takes_over_after_repeated_sightings(kc, orc):
         assert kc.specialize_stats()["specialized_launches"] == s1["specialized_launches"] + 1
     finally:
         kc.set_specialize(1, 2)
+
+
+# ---- the registry of compiled kernels (csrc/specialize.cpp): sharing, queued compiles, switching off ----
+REGISTRY_SHAPES = [(8, 64), (5, 33)]  # dense rows: the flat signature; 33 columns: pitched
+
+
+@pytest.fixture()
+def fresh(kc, tmp_path):
+    """An empty kernel-cache directory and an empty registry, so that no file and no kernel of an earlier test serves the case."""
+    kc.specialize_wait()
+    kc.kernel_cache_set_dir(str(tmp_path))
+    kc.specialize_reset()
+    yield kc
+    kc.specialize_wait()
+    kc.kernel_cache_set_dir(None)
+    kc.set_specialize(1, 2)
+    kc.specialize_reset()
+
+
+def three_steps(kc, orc, shape, c):
+    """(x - b) * c + b on gray planes, c a constant operand: build() -> lazy SlotImage, and what the oracle gives."""
+    h, w = shape
+    a, b = splitmix_plane(SEED_A, 0, h, w), splitmix_plane(SEED_B, 0, h, w)
+    A, B = kc.SlotImage.from_planes([a]), kc.SlotImage.from_planes([b])
+
+    def build():
+        k = kc.resize_image(kc.value_process(float(c)), (w, h))
+        x = kc.mix_process(A, B, kc.MixType.Subtract)
+        x = kc.mix_process(x, k, kc.MixType.Multiply)
+        return kc.mix_process(x, B, kc.MixType.Add)
+
+    want = orc.mix_plane("Add", orc.mix_plane("Multiply", orc.mix_plane("Subtract", a, b), np.full((h, w), c, np.float32)), b)
+    return build, [want]
+
+
+@pytest.mark.parametrize("shape", REGISTRY_SHAPES)
+def test_programs_that_differ_only_in_constants_share_a_kernel(fresh, orc, shape):
+    kc = fresh
+    kc.set_specialize(2)
+    s0 = kc.specialize_stats()
+    for c in (np.float32(0.625), np.float32(0.3125)):
+        build, want = three_steps(kc, orc, shape, c)
+        assert_planes(build().planes(), want, what="constant %g" % c)
+    s1 = kc.specialize_stats()
+    assert s1["kernels_compiled"] == s0["kernels_compiled"] + 1
+    assert s1["specialized_launches"] == s0["specialized_launches"] + 2
+    assert s1["compiles_failed"] == s0["compiles_failed"]
+
+
+@pytest.mark.parametrize("shape", REGISTRY_SHAPES)
+def test_a_compile_that_is_already_queued_is_not_compiled_twice(fresh, orc, shape):
+    kc = fresh
+    build, want = three_steps(kc, orc, shape, np.float32(0.625))
+    s0 = kc.specialize_stats()
+    kc.set_specialize(1, 1)
+    assert_planes(build().planes(), want, what="the evaluation that queues the compile")
+    kc.set_specialize(2)  # at once: the launch below waits for the queued compile instead of starting its own
+    s1 = kc.specialize_stats()
+    assert_planes(build().planes(), want, what="the evaluation that waits for it")
+    assert kc.specialize_stats()["specialized_launches"] == s1["specialized_launches"] + 1
+    kc.specialize_wait()
+    s2 = kc.specialize_stats()
+    assert s2["kernels_compiled"] == s0["kernels_compiled"] + 1 and s2["compiles_pending"] == 0
+    assert s2["compiles_failed"] == s0["compiles_failed"]
+
+
+@pytest.mark.parametrize("shape", REGISTRY_SHAPES)
+def test_switching_off_drops_the_queue_and_restarts_the_count(fresh, orc, shape):
+    kc = fresh
+    build, want = three_steps(kc, orc, shape, np.float32(0.625))
+    s0 = kc.specialize_stats()
+    kc.set_specialize(1, 1)
+    assert_planes(build().planes(), want, what="the evaluation that queues the compile")
+    kc.set_specialize(0)
+    s1 = kc.specialize_stats()
+    assert s1["compiles_pending"] == 0
+    assert_planes(build().planes(), want, what="switched off")
+    assert kc.specialize_stats()["specialized_launches"] == s1["specialized_launches"]
+    kc.set_specialize(1, 2)
+    for i in range(3):
+        assert_planes(build().planes(), want, what="evaluation %d after switching on again" % i)
+    kc.specialize_wait()
+    s2 = kc.specialize_stats()
+    assert_planes(build().planes(), want, what="specialised evaluation")
+    s3 = kc.specialize_stats()
+    assert s3["specialized_launches"] == s2["specialized_launches"] + 1
+    assert s3["kernels_compiled"] - s0["kernels_compiled"] <= 1 and s3["compiles_failed"] == s0["compiles_failed"]

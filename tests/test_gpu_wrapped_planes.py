@@ -15,7 +15,7 @@ pixels; afterwards every parent tensor still holds its bits (assert_untouched). 
 (test_gpu_streaming_variants.scrub_planes), so a result block cannot already hold the answer.
 
 A flat compiled chain launch (runtime.cpp chain_dispatch: every pitch dense, P.rows == 1) has no counter of its own; the two
-quads per lane form ("_q2", specialize.cpp chain_quads_for) exists for flat signatures only, so a {+, -, *} program under
+quads per lane form ("_q2", chain_codegen.cpp chain_quads_for) exists for flat signatures only, so a {+, -, *} program under
 nt_force 0x101 reads "specialized_nt_101_q2" when the launch is flat and "specialized_nt_101" when it is not.  The signature
 the kernel was generated for is read as well, from the list of programs a launch compiles (KC_KERNEL_CACHE_MANIFEST).
 
@@ -354,7 +354,7 @@ COMPILED_CASES = [
 @pytest.mark.parametrize("case", COMPILED_CASES, ids=[c[0] for c in COMPILED_CASES])
 def test_compiled_chain_over_wrapped_inputs(kc, orc, torch, case, tmp_path):
     """The counter says which kernel ran; the signature it was generated for is read from the list of programs the launch
-    compiled (KC_KERNEL_CACHE_MANIFEST, specialize.cpp compile_entry): the first launch of a case starts from no kernels, in
+    compiled (KC_KERNEL_CACHE_MANIFEST, kernel_cache.cpp disk_store): the first launch of a case starts from no kernels, in
     memory or on disk, so it compiles exactly its own program, and that program's `flat` must be the case's."""
     name, (w, h), steps, lays, opts, quads, counter = case
     planes = chain_inputs(3, h, w)

@@ -1,5 +1,5 @@
 """Packed copies of chain inputs without a device: the kernel the headline launches once its sources are packed (csrc/chain_pack.h,
-csrc/specialize.cpp), cross-compiled by hiprtc and read back as ISA, and the optional "in_tiers" field of the manifest of
+csrc/chain_codegen.cpp), cross-compiled by hiprtc and read back as ISA, and the optional "in_tiers" field of the manifest of
 pre-compiled programs."""
 import json
 import os

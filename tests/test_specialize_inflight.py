@@ -1,4 +1,4 @@
-"""The compiled chain kernels with more than one float4 per lane (csrc/specialize.cpp, chain_quads_for / generate_quads),
+"""The compiled chain kernels with more than one float4 per lane (csrc/chain_codegen.cpp, chain_quads_for / emit_quads),
 without a GPU.  A flat {+, -, *} program whose cache-policy mask leaves an input plain beside a nontemporal stream gets
 QUADS float4 per lane if it has at most 16 records: every load of the lane is issued before the first step, then one quad after the other runs the
 program, and the stores follow the last body.  Its listing for gfx950 is counted the way tests/test_specialize_isa.py counts the one-quad form; every signature
@@ -109,6 +109,10 @@ def test_refused_settings(quads):
 
 
 def test_generator_host_code_under_address_and_undefined_sanitizers(tmp_path):
+    """csrc/chain_codegen.cpp and the check program alone: the generator needs no HIP runtime, no context and no other unit.
+    The program's output -- its sweep's verdict and one digest per group of generated texts -- is pinned in
+    tests/golden/chain_kernel_texts.txt.  After an intended change of the generator, from the repository's root:
+    hipcc -x c++ -std=c++17 -D__HIP_PLATFORM_AMD__ -Iinclude -Ikanter_core_amd/csrc kanter_core_amd/csrc/chain_codegen.cpp tests/c_host/specialize_generate_check.cpp -o /tmp/kc_texts && /tmp/kc_texts > tests/golden/chain_kernel_texts.txt"""
     from kanter_core_amd import build as kbuild
     hipcc = shutil.which(kbuild._hipcc()) or kbuild._hipcc()
     rocm = os.path.dirname(os.path.dirname(os.path.realpath(hipcc)))  # <rocm>/bin/hipcc
@@ -116,11 +120,12 @@ def test_generator_host_code_under_address_and_undefined_sanitizers(tmp_path):
     exe = str(tmp_path / "specialize_generate_check")
     cmd = [hipcc, "-x", "c++", "-O1", "-g", "-std=c++17", "-fno-fast-math", "-ffp-contract=off", "-Xarch_host", "-fsanitize=address,undefined",
            "-Xarch_host", "-fno-sanitize-recover=undefined", "-fno-omit-frame-pointer", "-D__HIP_PLATFORM_AMD__", "-I" + os.path.join(rocm, "include"),
-           "-I" + os.path.join(ROOT, "include"), "-I" + csrc, os.path.join(csrc, "specialize.cpp"),
-           os.path.join(ROOT, "tests", "c_host", "specialize_generate_check.cpp"), "-o", exe, "-L" + os.path.join(rocm, "lib"),
-           "-lamdhip64", "-ldl", "-lpthread", "-Wl,-rpath," + os.path.join(rocm, "lib")]
+           "-I" + os.path.join(ROOT, "include"), "-I" + csrc, os.path.join(csrc, "chain_codegen.cpp"),
+           os.path.join(ROOT, "tests", "c_host", "specialize_generate_check.cpp"), "-o", exe]
     r = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, timeout=300)
     assert r.returncode == 0, r.stdout
     env = dict(os.environ, ASAN_OPTIONS="detect_leaks=0:abort_on_error=1", UBSAN_OPTIONS="halt_on_error=1:print_stacktrace=1")
     r = subprocess.run([exe], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, timeout=120, env=env)
     assert r.returncode == 0 and r.stdout.startswith("ok:"), r.stdout
+    with open(os.path.join(ROOT, "tests", "golden", "chain_kernel_texts.txt")) as f:
+        assert r.stdout == f.read()

@@ -3,7 +3,7 @@
 #   tools/dump_baseline_programs.sh            -> gpurun_out/baseline_programs.jsonl
 # then, here:  sort -u gpurun_out/baseline_programs.jsonl > kanter_core_amd/baseline_programs.jsonl
 # Every run starts with an empty kernel cache (so everything is compiled in-process) and appends what it compiled to the
-# manifest (KC_KERNEL_CACHE_MANIFEST, csrc/specialize.cpp).  The build then pre-compiles exactly these (kanter_core_amd/build.py).
+# manifest (KC_KERNEL_CACHE_MANIFEST, csrc/kernel_cache.cpp).  The build then pre-compiles exactly these (kanter_core_amd/build.py).
 # A kernel that reads packed inputs (csrc/chain_pack.cpp) is compiled at the second sighting of its packed form and recorded
 # with the optional field "in_tiers"; the runs below are long enough (4 + 6 steps) for the workloads that pack their sources.
 set -e

@@ -1,6 +1,6 @@
 #!/bin/bash
 # Runs the CPU-side tests of the product library with its HOST code (runtime, graph, JSON, PNG, C API)
-# (runtime, graph, JSON, PNG, specialiser, partitioner, band planner, C API)
+# (runtime, graph, JSON, PNG, chain code generator, kernel cache, specialiser, partitioner, band planner, C API)
 # built under AddressSanitizer + UndefinedBehaviorSanitizer.  Device code is the regular build: GPU
 # sanitizers are not available on the target pool.  Restores the regular library afterwards.
 # On a GPU box the same host-only instrumentation can run the evaluator for real:
