@@ -498,7 +498,8 @@ static bool choose_tile(const TapsHost &v, const TapsHost &h, const Options &o, 
     // tile whose source window is at most 64 quads wastes no lanes; a wave walks 4 (tile of 16) or 8 (tile of 32) rows.
     if (h.stride > KC_RESIZE_REG_TAPS && v.stride > KC_RESIZE_REG_TAPS && o.resize_mode != 2) {
         const uint32_t rows = o.resize_tile_h == 32 ? 32u : 16u;  // KC_RESIZE_TILE_H=32: tuning
-        for (uint32_t tw = 64; tw >= 4; tw -= 4) {
+        // (no wider than the image: the kernels size their tap staging by the tile, and resize_poly_kernel stages once per wave)
+        for (uint32_t tw = std::min(64u, (r.dw + 3u) / 4u * 4u); tw >= 4; tw -= 4) {
             const uint32_t groups = tile_groups(h, r.dw, tw);
             if (groups > 64) continue;  // the intermediate rows hold 256 floats
             if (resize_down_lds_bytes(rows, 4u * groups, tw, h.stride) > 64 * 1024) continue;
@@ -508,7 +509,8 @@ static bool choose_tile(const TapsHost &v, const TapsHost &h, const Options &o, 
             // ... and resize_poly_kernel where the vertical table is regular
             const bool poly = rows == 16 && o.resize_mode != 1 && (v.reg_ages == 2 || v.reg_ages == 4 || v.reg_ages == 6) &&
                               (v.reg_ratio == 2 || v.reg_ratio == 4 || v.reg_ratio == 8) && v.reg_b - v.reg_a >= 16 && v.reg_a <= 16 &&
-                              r.dh - (v.reg_a + (v.reg_b - v.reg_a) / 4 * 4) <= 48;
+                              r.dh - (v.reg_a + (v.reg_b - v.reg_a) / 4 * 4) <= 48 &&
+                              (size_t)4 * resize_down_wave_floats(tw, h.stride) * sizeof(float) <= 64 * 1024;  // plan_poly's LDS
             r.form = poly ? ResizeForm::poly : ResizeForm::down;
             return true;
         }

@@ -139,9 +139,9 @@ def resize_source(seed, channel, h, w):
 SALT_VALUES = [np.nan, np.inf, -np.inf, -0.0, 1e-40, 3e38, 1.25, -0.25]  # 3e38 is written as a vertical pair: its sums overflow
 
 
-def salt(plane, rows, cols, shift=0):
+def salt(plane, rows, cols, shift=0, values=SALT_VALUES):
     """Writes IEEE edge cases at the crossings of the given rows and columns (negative: from the end), cycling through
-    SALT_VALUES; a 3e38 sample gets a 3e38 neighbour below it (above it on the last row), so that vertical sums
+    `values`; a 3e38 sample gets a 3e38 neighbour below it (above it on the last row), so that vertical sums
     overflow to inf although every sample is finite."""
     h, w = plane.shape
     rows = sorted({r % h for r in rows})
@@ -149,7 +149,7 @@ def salt(plane, rows, cols, shift=0):
     k = shift
     for r in rows:
         for c in cols:
-            v = SALT_VALUES[k % len(SALT_VALUES)]
+            v = values[k % len(values)]
             plane[r, c] = v
             if v == 3e38:
                 plane[r + 1 if r + 1 < h else r - 1, c] = v
