@@ -124,6 +124,16 @@ impl SlotImage {
         check(unsafe { kc_image_distance_field(self.raw(), ch, ref_u8 as u32, spread, if tiles { KC_SDF_WRAP } else { 0 }, &mut out) })?;
         Ok(wrap(out))
     }
+    /// A separable Gaussian blur of the image's planes (kc_image_blur): a new image of this type and size, exact as a function
+    /// of its f32 weights (kc_blur_weights, kc_blur_texel).  A sigma of 0 leaves its axis alone; the radius max(1, ceil(3 sigma))
+    /// goes up to KC_BLUR_MAX_RADIUS.  Edges repeat; `tiles`: the image tiles on both axes (KC_BLUR_WRAP).  Bit c of
+    /// `channel_mask` (None: every channel) selects channel c; the other channels are this image's own planes.
+    pub fn blur(&self, sigma_x: f32, sigma_y: f32, channel_mask: Option<u32>, tiles: bool) -> Result<Self> {
+        let mask = channel_mask.unwrap_or(if self.is_rgba() { 15 } else { 1 });
+        let mut out = ptr::null_mut();
+        check(unsafe { kc_image_blur(self.raw(), sigma_x, sigma_y, mask, if tiles { KC_BLUR_WRAP } else { 0 }, &mut out) })?;
+        Ok(wrap(out))
+    }
     /// The image's BC1, BC3, BC4, BC5 or BC7 blocks (kc_image_to_bc), encoded on the device from the bytes to_u8 (`srgb`:
     /// to_u8_srgb, BC1, BC3 and BC7 only) writes: ceil(h/4) rows of ceil(w/4) blocks of 8 (BC1, BC4) or 16 (BC3, BC5, BC7) bytes,
     /// tightly packed.

@@ -917,6 +917,49 @@ KC_API int kc_image_levels_write_dds(kc_image *const *levels, uint32_t count, co
 KC_API int kc_image_distance_field(kc_image *img, uint32_t channel, uint32_t ref_u8, uint32_t spread, uint32_t flags, kc_image **out);
 KC_API int kc_sdf_texel(uint32_t d2, int inside, uint32_t spread, float *v);
 KC_API int kc_sdf_cap(uint32_t spread, uint32_t *cap);
+/* Blur: a separable Gaussian of the planes of an image, on the device -- a height map smoothed before HeightToNormal, a
+ * distance field softened before it is resized down, a mask feathered, roughness low-passed, a tileable texture kept tileable.
+ * The result is exact as a function of its f32 weights (tests/blur_ref.py is the same rule in numpy).
+ *   Radius.   For an axis with sigma > 0: R = max(1, (uint32_t)ceil(3.0 * (double)sigma)); R > KC_BLUR_MAX_RADIUS is refused.
+ *             sigma == 0 means "this axis is not blurred": no pass, no rounding.  NaN, negative and infinite sigmas are refused.
+ *   Weights.  On the host in f64, rounded to f32 once: with s = (double)sigma, g_k = exp(-(double)(k k) / (2.0 s s)) for
+ *             k = 0..R, total = g_0 + 2 (g_1 + g_2 + ... + g_R) with the inner sum taken in ascending k, w_k = (float)(g_k / total).
+ *             Weights that underflow to 0 stay taps.  The f32 weights do not sum to exactly 1, so a constant changes by a few
+ *             ulps: part of the rule, not an error.
+ *   Taps.     For output position i on an axis of n texels, tap j (-R..R) reads position i + j: clamped to 0..n-1 (the edge texel
+ *             repeats), or with KC_BLUR_WRAP reduced by a true modulo n -- R may exceed n, the image may wrap more than once.
+ *   Texel.    All in f32, every operation rounded on its own (no fused multiply-add), the outermost pair first, so that the
+ *             small terms are summed before the large one:
+ *                 acc = w_R (t[-R] + t[+R]);  for k = R-1 down to 1: acc = acc + w_k (t[-k] + t[+k]);  acc = acc + w_0 t[0]
+ *             No tap is skipped: a zero weight times an infinity is NaN, as IEEE says.  Pairing the two sides makes the result
+ *             exactly mirror-symmetric: blur(flip(x)) == flip(blur(x)) bit for bit.
+ *   Passes.   Along x first, into an f32 intermediate, then along y on the intermediate; an axis with sigma == 0 is left out.
+ *   kc_image_blur  `*out` (+1 reference) = a new image of the source's type and size; the source is untouched.  A pending chain
+ *             or resample of the image runs first.  Bit c of channel_mask selects channel c (Gray: bit 0; RGBA: bits 0..3);
+ *             unselected channels are the source's planes themselves.  Channels that are one plane in the source are blurred
+ *             once and are one plane in the result.  A selected constant plane stays constant and is answered on the host: the
+ *             texel rule on all-equal taps with the x weights, then on that result with the y weights; it allocates and launches
+ *             nothing.  With both sigmas 0 the result shares every plane with the source and nothing is launched.  Otherwise one
+ *             launch per blurred axis for all selected resident planes together -- two launches, or one when one sigma is 0,
+ *             whatever the size and the channel count (kc_stats; counters "blur_rows", "blur_columns", and "blur_rows_nt",
+ *             "blur_columns_nt" where the cache policy marks the source of the first pass, the result of the last, nontemporal);
+ *             8 algorithmic bytes per texel, per blurred axis, per distinct resident plane.  The intermediate is a staging block
+ *             of the pool that goes back when the call returns.  Enqueued on the library's stream; the call does not wait.
+ *             Errors, in this order: KC_ERR_NO_DEVICE before kc_init; flag bits other than KC_BLUR_WRAP KC_ERR_UNSUPPORTED; a NULL
+ *             argument, a sigma that is NaN, negative or infinite, a radius above KC_BLUR_MAX_RADIUS, a mask of 0, a mask with a
+ *             bit the image has no channel for, more than 2^31 texels KC_ERR_INVALID_ARG.  Nothing is launched or allocated on a
+ *             refusal, and `*out` is not written.
+ *   kc_blur_weights  weights[0..R] and R for a sigma, as kc_image_blur uses them.  A NULL pointer, a capacity below R + 1, a sigma
+ *             kc_image_blur would refuse, or sigma == 0, is KC_ERR_INVALID_ARG.
+ *   kc_blur_texel    the texel rule on taps[0..2R] (the centre at R) with weights[0..R]; a NULL pointer or a radius outside
+ *             1..KC_BLUR_MAX_RADIUS is KC_ERR_INVALID_ARG.  Both are arithmetic, no kc_init needed.
+ * Not here: a graph node type, radii above 64 (blur twice: variances add; or resize down first), non-Gaussian kernels, per-axis
+ * wrap, a single-launch fused form for small radii. */
+#define KC_BLUR_WRAP 1u        /* the image tiles on both axes: taps are taken modulo the extent */
+#define KC_BLUR_MAX_RADIUS 64  /* ceil(3 sigma): sigma up to 21.33 */
+KC_API int kc_image_blur(kc_image *img, float sigma_x, float sigma_y, uint32_t channel_mask, uint32_t flags, kc_image **out);
+KC_API int kc_blur_weights(float sigma, float *weights, uint32_t capacity, uint32_t *radius);
+KC_API int kc_blur_texel(const float *taps, const float *weights, uint32_t radius, float *v);
 /* The way back: BC blocks decoded on the device, the error of an encoding measured on the device, and .dds files read.
  * Decoding is integer arithmetic on the block's bytes, so the pixels are exact (tests/bc_decode_ref.py is the same rules in
  * numpy).  Pixel (x, y) is texel 4 (y % 4) + x % 4 of block (x / 4, y / 4); texels of edge blocks outside the image are dropped.

@@ -15,6 +15,7 @@ from .api import (Edge, EmbeddedSlotDataId, LiveGraph, MixType, Node, NodeGraph,
                   kernel_cache_precompile, specialize_reset, U8Pipe, device_image_desc, DEVICE_SRGB, DEVICE_GRAY,
                   ChannelStats, STATS_HISTOGRAM, STATS_SRGB, BC_SRGB, BC6H, BC7, BC_BLOCK_BYTES, BC_PUNCH_THROUGH, bc_punch_through_ref, bc1_punch_through_block,
                   MIP_PER_LEVEL, MIP_NORMALS, MIP_COVERAGE, MIP_ALPHA_WEIGHT, mip_alpha_weight, mip_alpha_texel, mip_coverage_ref, MipCoverageLevel, alpha_ref_threshold, mip_coverage_target, mip_coverage_scale, mip_normal_texel, mip_unit_normal, mip_roughness_texel, levels_to_bc_mips, write_dds_levels, mip_level_count, bc_mip_layout, dds_header, BC_GRAY, BC_ALL_MODES, BcError, DdsInfo, dds_parse, preview_level,
-                  PREVIEW_SRGB, PreviewPlan, preview_plan, previews, previews_torch, SDF_WRAP, SDF_MAX_SPREAD, sdf_cap, sdf_texel)
+                  PREVIEW_SRGB, PreviewPlan, preview_plan, previews, previews_torch, SDF_WRAP, SDF_MAX_SPREAD, sdf_cap, sdf_texel,
+                  BLUR_WRAP, BLUR_MAX_RADIUS, blur_weights, blur_texel)
 
 __all__ = [n for n in dir() if not n.startswith("_")]

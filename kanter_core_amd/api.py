@@ -828,6 +828,31 @@ def sdf_texel(d2, inside, spread):
     return np.float32(v.value)
 
 
+BLUR_WRAP = _abi.KC_BLUR_WRAP  # SlotImage.blur: the image tiles on both axes
+BLUR_MAX_RADIUS = _abi.KC_BLUR_MAX_RADIUS
+
+
+def blur_weights(sigma):
+    """-> (R + 1,) float32: the weights w_0..w_R SlotImage.blur uses along an axis of that sigma, R = max(1, ceil(3 sigma)) up to
+    BLUR_MAX_RADIUS (kc_blur_weights; no device)."""
+    w = np.zeros(BLUR_MAX_RADIUS + 1, np.float32)
+    r = C.c_uint32()
+    _check(_lib.load().kc_blur_weights(C.c_float(float(np.float32(sigma))), w.ctypes.data_as(C.POINTER(C.c_float)), w.size, C.byref(r)))
+    return w[:r.value + 1].copy()
+
+
+def blur_texel(taps, weights):
+    """-> np.float32: the blur's texel rule on the 2 R + 1 taps (the centre at R) with the R + 1 weights: the outermost pair
+    first, every f32 operation rounded on its own (kc_blur_texel; no device)."""
+    t = np.ascontiguousarray(taps, np.float32).reshape(-1)
+    w = np.ascontiguousarray(weights, np.float32).reshape(-1)
+    if w.size < 2 or t.size != 2 * w.size - 1:
+        raise ValueError("blur_texel takes R + 1 weights (R >= 1) and 2 R + 1 taps")
+    v = C.c_float()
+    _check(_lib.load().kc_blur_texel(t.ctypes.data_as(C.POINTER(C.c_float)), w.ctypes.data_as(C.POINTER(C.c_float)), w.size - 1, C.byref(v)))
+    return np.float32(v.value)
+
+
 def mip_normal_texel(box):
     """-> (3,) float32: what a texel of a normal-map chain (normals=True) stores for the 2 x 2 boxes `box` of R, G, B -- decoded,
     normalised (a vector without a direction becomes (0, 0, 1)) and encoded again in f32 (kc_mip_normal_texel; no device)."""
@@ -1317,6 +1342,25 @@ class SlotImage:
         ch = (3 if self.is_rgba() else 0) if channel is None else int(channel)
         out = C.c_void_p()
         _check(_lib.load().kc_image_distance_field(self._h, ch, ref, spread, SDF_WRAP if wrap else 0, C.byref(out)))
+        return SlotImage(out.value)
+
+    def blur(self, sigma, sigma_y=None, wrap=False, channels=None):
+        """-> a SlotImage of this type and size: a separable Gaussian blur of the planes (kc_image_blur), exact as a function of
+        its f32 weights (blur_weights, blur_texel).  sigma: along x, and along y too unless sigma_y is given; 0 leaves an axis
+        alone; the radius max(1, ceil(3 sigma)) goes up to BLUR_MAX_RADIUS.  Edges repeat; wrap=True: the image tiles on both
+        axes.  channels: the indices to blur (None: all); the others are this image's own planes."""
+        if channels is None:
+            mask = 15 if self.is_rgba() else 1
+        else:
+            mask = 0
+            for c in channels:
+                if not 0 <= int(c) < 32:
+                    raise ValueError("channel index out of range")
+                mask |= 1 << int(c)
+        sy = sigma if sigma_y is None else sigma_y
+        out = C.c_void_p()
+        _check(_lib.load().kc_image_blur(self._h, C.c_float(float(np.float32(sigma))), C.c_float(float(np.float32(sy))), mask,
+                                         BLUR_WRAP if wrap else 0, C.byref(out)))
         return SlotImage(out.value)
 
     def to_bc_mips(self, fmt, srgb=False, per_level=False, normals=False, coverage=None, alpha_weighted=False, punch_through=None):

@@ -1062,6 +1062,32 @@ try {
 }
 KC_CATCH
 
+int kc_image_blur(kc_image *img, float sigma_x, float sigma_y, uint32_t channel_mask, uint32_t flags, kc_image **out)
+try {
+    Lock api_lock(ctx().mu);  // reference counts are plain integers, see kc_plane::refs
+    return image_blur(img, sigma_x, sigma_y, channel_mask, flags, out);  // need_init(), the flags, then the arguments
+}
+KC_CATCH
+
+int kc_blur_weights(float sigma, float *weights, uint32_t capacity, uint32_t *radius)
+try {
+    KC_ARG(weights && radius);
+    if (blur_weights(sigma, weights, capacity, radius) != KC_OK) {
+        set_error("kc_blur_weights: the sigma is not in (0, KC_BLUR_MAX_RADIUS / 3] or the capacity is below its radius + 1");
+        return KC_ERR_INVALID_ARG;
+    }
+    return KC_OK;
+}
+KC_CATCH
+
+int kc_blur_texel(const float *taps, const float *weights, uint32_t radius, float *v)
+try {
+    KC_ARG(taps && weights && v && radius >= 1 && radius <= KC_BLUR_MAX_RADIUS);
+    *v = blur_texel(taps, weights, radius);
+    return KC_OK;
+}
+KC_CATCH
+
 int kc_image_from_f32(const float *const host_planes[], int n, uint32_t w, uint32_t h, kc_image **out)
 try {
     Lock api_lock(ctx().mu);  // reference counts are plain integers, see kc_plane::refs

@@ -595,5 +595,25 @@ inline uint64_t sdf_columns_groups(uint32_t w, uint32_t h) { return (uint64_t)((
 inline uint64_t sdf_rows_groups(uint32_t w, uint32_t h) { return (uint64_t)((w + KC_SDF_SEG - 1) / KC_SDF_SEG) * ((h + KC_SDF_ROWS - 1) / KC_SDF_ROWS); }
 hipError_t launch_sdf_columns(const SdfArgs &a, bool wrap, bool nt, hipStream_t s);
 hipError_t launch_sdf_rows(const SdfArgs &a, bool wrap, bool nt, hipStream_t s);
+// -- blur.hip --
+// Separable Gaussian blur (blur.hip / blur.cpp): the header's texel rule along one axis of `planes` planes per launch; the plane
+// index is blockIdx.y, the pointers, pitches (floats, multiples of 4; rows start 16-byte aligned) and the R + 1 weights travel
+// in the argument block.  blur_rows_kernel<nt, wrap>: one workgroup per KC_BLUR_SEG columns of KC_BLUR_ROWS rows, a wave per
+// row, a lane per four adjacent texels.  blur_columns_kernel<nt, wrap>: one workgroup per KC_BLUR_COLS columns of a band of
+// KC_BLUR_BAND rows, a lane per four adjacent columns of four adjacent rows; its LDS is (KC_BLUR_BAND + 2 R) rows of
+// KC_BLUR_COLS floats, sized by the launch.  nt: the source loads of the rows kernel, the result stores of the columns kernel.
+constexpr uint32_t KC_BLUR_SEG = 256, KC_BLUR_ROWS = 4, KC_BLUR_COLS = 64, KC_BLUR_BAND = 64;
+struct BlurArgs {
+    const float *src[4];
+    float *dst[4];
+    uint32_t src_pitch[4], dst_pitch[4];  // floats
+    uint32_t w, h, radius, planes;        // radius: R, 1..KC_BLUR_MAX_RADIUS; planes: 1..4
+    float weights[KC_BLUR_MAX_RADIUS + 1];
+};
+inline uint64_t blur_rows_groups(uint32_t w, uint32_t h) { return (uint64_t)((w + KC_BLUR_SEG - 1) / KC_BLUR_SEG) * ((h + KC_BLUR_ROWS - 1) / KC_BLUR_ROWS); }
+inline uint64_t blur_columns_groups(uint32_t w, uint32_t h) { return (uint64_t)((w + KC_BLUR_COLS - 1) / KC_BLUR_COLS) * ((h + KC_BLUR_BAND - 1) / KC_BLUR_BAND); }
+inline size_t blur_columns_lds(uint32_t radius) { return (size_t)(KC_BLUR_BAND + 2u * radius) * KC_BLUR_COLS * sizeof(float); }
+hipError_t launch_blur_rows(const BlurArgs &a, bool wrap, bool nt, hipStream_t s);
+hipError_t launch_blur_columns(const BlurArgs &a, bool wrap, bool nt, hipStream_t s);
 
 }  // namespace kc

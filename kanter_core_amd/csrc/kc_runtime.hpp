@@ -535,6 +535,11 @@ void channel_stats_release();
 uint32_t sdf_cap(uint32_t spread);
 float sdf_texel(uint32_t d2, bool inside, uint32_t spread);
 int image_distance_field(kc_image *img, uint32_t channel, uint32_t ref_u8, uint32_t spread, uint32_t flags, kc_image **out);
+// Gaussian blur (blur.cpp): the rule's arithmetic as kc_blur_weights and kc_blur_texel return it (blur_weights checks the sigma
+// and the capacity itself; blur_texel takes R in 1..KC_BLUR_MAX_RADIUS), and the body of kc_image_blur
+int blur_weights(float sigma, float *weights, uint32_t capacity, uint32_t *radius);
+float blur_texel(const float *taps, const float *weights, uint32_t R);
+int image_blur(kc_image *img, float sigma_x, float sigma_y, uint32_t channel_mask, uint32_t flags, kc_image **out);
 int calculate_size(int policy, const kc_size *sizes, int n, int slot_index, kc_size specific, kc_size *out);
 int mix_process(kc_image *left, kc_image *right, int mix_type, kc_image **out);
 int separate_process(kc_image *in, kc_image *out[4]);
